@@ -2,11 +2,15 @@
 """Headline benchmark of the MI355X decode path: audio-codec frames/s/GPU for Dia-1.6B (+ RTF).
 
     python bench.py --gpus N --steps K --warmup W            (N>1: launched by torch.distributed.run)
+    python bench.py ... --full                               (+ everything beyond the headline figure, below)
+    python bench.py ... --dump-outputs DIR                   (+ what the last timed step computed, DIR/<name>.npy)
 
 A "step" is one decode step of the whole batch (one frame per utterance = 9 codebook tokens).
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds the CPU baseline, the warm prefill
+measurement (`prefill`), the per-kernel roofline tables (`roofline`, `roofline_by_kernel`) and the `configs` object.
 Workload (BASELINE.json):
   N = 1   configs[1] — Dia-1.6B shapes, bf16 weights + bf16 K/V, batch 1, 1024 decode steps, README prompt.
-          The same run also measures, at 1024 steps each whatever --steps says, every other single-GPU
+          With --full the same run also measures, at 1024 steps each whatever --steps says, every other single-GPU
           configuration of BASELINE.json (`configs` object of the JSON line): batch 1 with fp32 K/V (the
           configuration that meets the 1e-3 logit parity bound; also as two bf16 planes per value through the MFMA attention
           kernel, "bf16x2"), batch 8 mixed text lengths 32..512 (configs[2]),
@@ -138,9 +142,29 @@ def kernel_table(sess, w, reps: int, graph_step_us: float):
     return rows, per_op, round(boundary, 3)
 
 
-def measure(w, cfg, *, batch, kv, steps, warmup, use_graph=True, seeds=None, dist=None, dev=None, profile_reps=0):
-    """One configuration: session, prefill (warm pass timed on the GPU), `warmup` untimed + `steps` timed decode steps
-    between barriers; returns the numbers of the JSON line for it."""
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(sess, out_dir, suffix=""):
+    """What a caller of the decode path receives after the last timed step, as float32 .npy files: `logits` [B, 2, C, V]
+    (cond / uncond rows of that step), `tokens` and `pred` [B, steps so far, C] (the delayed token buffer and the
+    per-step predictions).  Over DUMP_CAP_BYTES in all, the first utterances only (the same ones every run)."""
+    cur = int(sess.cur.max().item())
+    arrs = {"logits": sess.logits_host(), "tokens": sess.tokens[:, :cur].cpu().numpy(), "pred": sess.pred[:, :cur].cpu().numpy()}
+    arrs = {k: v.astype(np.float32) for k, v in arrs.items()}
+    per_utt = sum(a[0].nbytes for a in arrs.values())
+    keep = max(1, min(sess.B, DUMP_CAP_BYTES // per_utt))
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrs.items():
+        np.save(os.path.join(out_dir, f"{k}{suffix}.npy"), a[:keep])
+
+
+def measure(w, cfg, *, batch, kv, steps, warmup, use_graph=True, seeds=None, dist=None, dev=None, profile_reps=0,
+            full=True, dump_dir=None, dump_suffix=""):
+    """One configuration: session, prefill, `warmup` untimed + `steps` timed decode steps between barriers; returns the
+    numbers of the JSON line for it.  full: also time a second, warm prefill pass on the GPU (`prefill`) and the
+    `profile_reps` eager steps of the per-kernel table.  The session is sized for those steps either way: its length
+    (max_tokens) moves the forced end of generation, so a plain run computes what --full computes."""
     from dia_hip.engine import DecodeSession
     from dia_hip.tokens import effective_text, encode_text
 
@@ -154,33 +178,35 @@ def measure(w, cfg, *, batch, kv, steps, warmup, use_graph=True, seeds=None, dis
     sess.prefill()
     sess.sync()
     prefill_s = time.time() - tp
-    # second, warm pass bracketed by events on the session's stream: GPU-side prefill time (the first pass pays
-    # module loading and allocator growth), for the MFMA utilisation of the prefill GEMMs (north star)
-    # The ~80 launches are queued BEHIND a device-side spin of a few milliseconds, so that the interval between the events is the GPU's own
-    # time whatever the host needs to enqueue them (0.5-0.8 ms from Python at batch 1 — as long as the GPU takes; reported beside it)
-    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    with torch.cuda.stream(sess.stream):
-        torch.cuda._sleep(int(8e6))
-    ev0.record(sess.stream)
-    th = time.time()
-    sess.prefill()
-    prefill_enqueue_s = time.time() - th
-    ev1.record(sess.stream)
-    sess.sync()
-    prefill_gpu_s = ev0.elapsed_time(ev1) * 1e-3
-    e_ = cfg.model.encoder
-    rows_ = sum(sess.lens)
-    prefill_params = w.prefill_weight_bytes() / 2.0          # encoder + cross-K/V matrices as loaded (compacted if pruned)
-    attn_flops = e_.n_layer * e_.n_head * 4 * 128 * sum(l * l for l in sess.lens)
-    prefill_flops = 2.0 * rows_ * prefill_params + attn_flops
-    alg_tflops = prefill_flops / prefill_gpu_s / 1e12
-    prefill = {"text_bytes": rows_, "gpu_s": round(prefill_gpu_s, 5), "host_enqueue_s": round(prefill_enqueue_s, 5), "host_s_first_call": round(prefill_s, 4),
-               "algorithmic_tflop": round(prefill_flops / 1e12, 4), "achieved_tflops_algorithmic": round(alg_tflops, 1),
-               "peak_tflops_bf16_dense": MFMA_PEAK_TFLOPS, "mfma_frac": round(alg_tflops / MFMA_PEAK_TFLOPS, 4),
-               "mfma_frac_issued": round(3 * alg_tflops / MFMA_PEAK_TFLOPS, 4),
-               "note": "gpu_s = events around the whole warm prefill pass, its launches queued behind a device-side spin (the GPU's own time); host_enqueue_s = "
-                       "what the Python host needed to enqueue them.  mfma_frac = ALGORITHMIC flops (2*rows*params + attention) / gpu_s / 2.5 PFLOP/s; every product is fp32-exact = 3 bf16 MFMAs (hi/mid/lo activation "
-                       "plane x bf16 weight), so the matrix pipe issues 3x that (mfma_frac_issued)"}
+    prefill = None
+    if full:
+        # second, warm pass bracketed by events on the session's stream: GPU-side prefill time (the first pass pays
+        # module loading and allocator growth), for the MFMA utilisation of the prefill GEMMs (north star)
+        # The ~80 launches are queued BEHIND a device-side spin of a few milliseconds, so that the interval between the events is the GPU's own
+        # time whatever the host needs to enqueue them (0.5-0.8 ms from Python at batch 1 — as long as the GPU takes; reported beside it)
+        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        with torch.cuda.stream(sess.stream):
+            torch.cuda._sleep(int(8e6))
+        ev0.record(sess.stream)
+        th = time.time()
+        sess.prefill()
+        prefill_enqueue_s = time.time() - th
+        ev1.record(sess.stream)
+        sess.sync()
+        prefill_gpu_s = ev0.elapsed_time(ev1) * 1e-3
+        e_ = cfg.model.encoder
+        rows_ = sum(sess.lens)
+        prefill_params = w.prefill_weight_bytes() / 2.0          # encoder + cross-K/V matrices as loaded (compacted if pruned)
+        attn_flops = e_.n_layer * e_.n_head * 4 * 128 * sum(l * l for l in sess.lens)
+        prefill_flops = 2.0 * rows_ * prefill_params + attn_flops
+        alg_tflops = prefill_flops / prefill_gpu_s / 1e12
+        prefill = {"text_bytes": rows_, "gpu_s": round(prefill_gpu_s, 5), "host_enqueue_s": round(prefill_enqueue_s, 5), "host_s_first_call": round(prefill_s, 4),
+                   "algorithmic_tflop": round(prefill_flops / 1e12, 4), "achieved_tflops_algorithmic": round(alg_tflops, 1),
+                   "peak_tflops_bf16_dense": MFMA_PEAK_TFLOPS, "mfma_frac": round(alg_tflops / MFMA_PEAK_TFLOPS, 4),
+                   "mfma_frac_issued": round(3 * alg_tflops / MFMA_PEAK_TFLOPS, 4),
+                   "note": "gpu_s = events around the whole warm prefill pass, its launches queued behind a device-side spin (the GPU's own time); host_enqueue_s = "
+                           "what the Python host needed to enqueue them.  mfma_frac = ALGORITHMIC flops (2*rows*params + attention) / gpu_s / 2.5 PFLOP/s; every product is fp32-exact = 3 bf16 MFMAs (hi/mid/lo activation "
+                           "plane x bf16 weight), so the matrix pipe issues 3x that (mfma_frac_issued)"}
 
     sess.ensure_noise(warmup + steps + profile_reps + 2)      # host RNG + upload stay outside the timed region
     sess.decode(warmup, use_graph)
@@ -205,6 +231,8 @@ def measure(w, cfg, *, batch, kv, steps, warmup, use_graph=True, seeds=None, dis
         elapsed = float(tt.item())
     cur_after = int(sess.cur.min().item())
     assert cur_after == 1 + warmup + steps, (cur_after, warmup, steps)        # every timed step really executed
+    if dump_dir is not None:
+        dump_outputs(sess, dump_dir, dump_suffix)
     n_mid = warmup + (steps + 1) / 2.0                      # whole-step algorithmic traffic at the region's mean KV length
     step_bytes = sess.step_bytes(int(round(n_mid)))
     step_gbs = step_bytes / (dev_ms / steps * 1e-3) / 1e9
@@ -216,8 +244,8 @@ def measure(w, cfg, *, batch, kv, steps, warmup, use_graph=True, seeds=None, dis
            "launches_per_step": sess.launches_per_step(), "persistent_segments": bool(getattr(sess, "seg", False)),
            "step_roofline": {"bytes_per_step": int(step_bytes), "achieved": round(step_gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                              "frac": round(step_gbs / HBM_PEAK_GBS, 4)},
-           "prefill": prefill}
-    if profile_reps > 0:
+           "prefill_s": round(prefill_s, 4), "prefill": prefill}
+    if full and profile_reps > 0:
         rows, per_op, boundary = kernel_table(sess, w, profile_reps, dev_ms / steps * 1e3)
         out["kernels"] = rows
         out["us_per_launch_by_op"] = per_op
@@ -233,13 +261,17 @@ def main():
     ap.add_argument("--warmup", type=int, default=16)
     ap.add_argument("--batch", type=int, default=0, help="utterances per GPU (default: 1 on one GPU, 64/N on N GPUs)")
     ap.add_argument("--kv", default="bf16", choices=["bf16", "f32", "bf16x2"])
-    ap.add_argument("--cpu-steps", type=int, default=40, help="decode steps of the CPU baseline sample (0 = skip)")
+    ap.add_argument("--full", action="store_true", help="also the CPU baseline, the warm prefill measurement, the per-kernel roofline "
+                    "tables and the `configs` object (a plain run measures the headline figure only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed "
+                    "(logits, tokens, pred) as DIR/<name>.npy, float32")
+    ap.add_argument("--cpu-steps", type=int, default=40, help="with --full: decode steps of the CPU baseline sample (0 = skip)")
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--profile-steps", type=int, default=3, help="eager steps timed kernel by kernel for the roofline objects (0 = skip)")
+    ap.add_argument("--profile-steps", type=int, default=3, help="with --full: eager steps timed kernel by kernel for the roofline objects (0 = skip)")
     ap.add_argument("--pruned", type=float, default=0.0, help="structured dim-0 pruning amount applied to the synthetic checkpoint (BASELINE config 4: 0.5)")
     ap.add_argument("--no-compact", action="store_true", help="with --pruned: stream the zeros instead of compacting")
-    ap.add_argument("--no-configs", action="store_true", help="skip the `configs` object (the other single-GPU BASELINE configurations)")
-    ap.add_argument("--config-steps", type=int, default=1024, help="decode steps of each `configs` entry")
+    ap.add_argument("--no-configs", action="store_true", help="with --full: skip the `configs` object (the other single-GPU BASELINE configurations)")
+    ap.add_argument("--config-steps", type=int, default=1024, help="with --full: decode steps of each `configs` entry")
     ap.add_argument("--preheat", type=int, default=128, help="untimed decode steps on a throw-away session before anything is measured "
                     "(a freshly leased, idle GPU needs ~0.1 s of load to reach its clocks; independent of --warmup, which is part of the measured session)")
     args = ap.parse_args()
@@ -305,7 +337,8 @@ def main():
         del pre
     seeds = [42 + 1000 * rank + i for i in range(batch)]
     prof = args.profile_steps if (rank == 0) else 0
-    m = measure(w, cfg, batch=batch, kv=args.kv, steps=K, warmup=Wm, use_graph=use_graph, seeds=seeds, dist=dist, dev=dev, profile_reps=prof)
+    m = measure(w, cfg, batch=batch, kv=args.kv, steps=K, warmup=Wm, use_graph=use_graph, seeds=seeds, dist=dist, dev=dev, profile_reps=prof,
+                full=args.full, dump_dir=args.dump_outputs, dump_suffix=f"_rank{rank}" if rank > 0 else "")
 
     frames = world * batch * K
     value = frames / m["elapsed_s"]
@@ -327,11 +360,13 @@ def main():
         "config": {"workload": workload, "batch_per_gpu": batch, "parallelism": f"dp{world}" if world > 1 else "single"},
         "frames_per_s_per_gpu": round(value / world, 2), "rtf_per_gpu": round(value / world / batch / FRAME_RATE, 3),
         "rtf_aggregate": round(value / FRAME_RATE, 2),
-        "prefill_s": m["prefill"]["host_s_first_call"], "prefill": m["prefill"], "weights_load_s": round(load_s, 2),
+        "prefill_s": m["prefill_s"], "weights_load_s": round(load_s, 2),
         "weights_bcast_s": round(bcast_s, 3),
         "device_ms_per_step": m["device_ms_per_step"], "decode_weight_bytes": m["decode_weight_bytes"], "activations": m["activations"], "preheat_steps": args.preheat,
         "step_roofline": m["step_roofline"],
     }
+    if m["prefill"] is not None:
+        out["prefill"] = m["prefill"]
     if "kernels" in m:
         rows = m["kernels"]
         top = dict(rows[0])
@@ -362,7 +397,7 @@ def main():
         out["boundary_us_per_launch"] = m["boundary_us_per_launch"]
 
     # ---- the other single-GPU configurations of BASELINE.json, 1024 steps each whatever --steps says
-    if rank == 0 and world == 1 and not args.no_configs and not args.pruned and args.batch in (0, 1) and args.kv == "bf16":
+    if args.full and rank == 0 and world == 1 and not args.no_configs and not args.pruned and args.batch in (0, 1) and args.kv == "bf16":
         cs = args.config_steps
         cfgs = {}
 
@@ -401,7 +436,7 @@ def main():
 
     # ---- CPU baseline: the oracle in mirror mode (= the reference's op sequence incl. its dead
     #      cross-K/V work), fp32, same weights/prompt/seed, bounded sample, rank 0 at N=1 only
-    if rank == 0 and world == 1 and args.cpu_steps > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_steps > 0:
         from oracle import dia_oracle as O
         nthr = cpu_threads()
         torch.set_num_threads(nthr)

@@ -1,10 +1,11 @@
 #!/bin/bash
 # instruction-cache behaviour of the decode kernels inside the step (kernels alternate, 70 KB of code per layer
 # against a 64 KB instruction cache per CU pair): per-kernel means per launch
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 O=$GRAFT_REPO_ROOT/gpurun_out/s2; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/pmc_ic
-rocprofv3 --pmc SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES --output-format csv -d /tmp/pmc_ic -- python $GRAFT_REPO_ROOT/bench.py --steps 8 --warmup 2 --cpu-steps 0 --profile-steps 0 > /dev/null 2>&1
+rocprofv3 --pmc SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES --output-format csv -d /tmp/pmc_ic -- python $ROOT/bench.py --full --steps 8 --warmup 2 --cpu-steps 0 --profile-steps 0 > /dev/null 2>&1
 python - <<PY
 import csv, glob, collections
 f = glob.glob("/tmp/pmc_ic/*/*counter_collection.csv")[0]

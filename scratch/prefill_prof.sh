@@ -1,7 +1,8 @@
 #!/bin/bash
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/pf
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/pf -- python $GRAFT_REPO_ROOT/bench.py --batch ${1:-8} --steps 2 --warmup 1 --cpu-steps 0 --profile-steps 0 > /tmp/pf.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/pf -- python $ROOT/bench.py --full --batch ${1:-8} --steps 2 --warmup 1 --cpu-steps 0 --profile-steps 0 > /tmp/pf.log 2>&1
 tail -1 /tmp/pf.log | cut -c1-300
 python - <<PY
 import csv,glob

@@ -4,20 +4,21 @@
 set -e
 #   scratch/profile_round.sh r02 pmc      (only the counter passes + traffic.json)
 R=${1:-r03}
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 O=$GRAFT_REPO_ROOT/gpurun_out/prof; mkdir -p $O
 cd $GRAFT_REPO_ROOT
 if [ "$2" != "pmc" ]; then
-python bench.py 2>/dev/null | tail -1 > $O/${R}_bench_default.json; echo "bench default (batch 1 + configs) done"
-python bench.py --steps 20 --warmup 5 2>/dev/null | tail -1 > $O/${R}_bench_driver_style.json; echo "bench driver-style done"
-python bench.py --batch 8 --cpu-steps 0 2>/dev/null | tail -1 > $O/${R}_bench_batch8.json; echo "bench b8 done"
-python bench.py --batch 8 --pruned 0.5 --cpu-steps 0 2>/dev/null | tail -1 > $O/${R}_bench_batch8_pruned50.json; echo "bench b8 pruned done"
-python bench.py --batch 1 --pruned 0.5 --cpu-steps 0 2>/dev/null | tail -1 > $O/${R}_bench_batch1_pruned50.json; echo "bench b1 pruned done"
-python bench.py --kv f32 --cpu-steps 0 2>/dev/null | tail -1 > $O/${R}_bench_batch1_f32kv.json; echo "bench b1 f32 K/V done"
+python bench.py --full 2>/dev/null | tail -1 > $O/${R}_bench_default.json; echo "bench default (batch 1 + configs) done"
+python bench.py --full --steps 20 --warmup 5 2>/dev/null | tail -1 > $O/${R}_bench_driver_style.json; echo "bench driver-style done"
+python bench.py --full --batch 8 --cpu-steps 0 2>/dev/null | tail -1 > $O/${R}_bench_batch8.json; echo "bench b8 done"
+python bench.py --full --batch 8 --pruned 0.5 --cpu-steps 0 2>/dev/null | tail -1 > $O/${R}_bench_batch8_pruned50.json; echo "bench b8 pruned done"
+python bench.py --full --batch 1 --pruned 0.5 --cpu-steps 0 2>/dev/null | tail -1 > $O/${R}_bench_batch1_pruned50.json; echo "bench b1 pruned done"
+python bench.py --full --kv f32 --cpu-steps 0 2>/dev/null | tail -1 > $O/${R}_bench_batch1_f32kv.json; echo "bench b1 f32 K/V done"
 cd /tmp && export TMPDIR=/tmp
 for cfg in "1:" "8:--batch 8" "8p:--batch 8 --pruned 0.5"; do
   tag=${cfg%%:*}; args=${cfg#*:}
   rm -rf /tmp/rp_$tag
-  rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/rp_$tag -- python3 $GRAFT_REPO_ROOT/bench.py $args --cpu-steps 0 --no-configs 2>/dev/null | tail -1 > $O/${R}_bench_batch${tag}_under_rocprof.json
+  rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/rp_$tag -- python3 $ROOT/bench.py --full $args --cpu-steps 0 --no-configs 2>/dev/null | tail -1 > $O/${R}_bench_batch${tag}_under_rocprof.json
   cp /tmp/rp_$tag/*/*_kernel_stats.csv $O/${R}_kernel_stats_batch$tag.csv; echo "rocprof $tag done"
 done
 fi
@@ -27,7 +28,7 @@ cd /tmp && export TMPDIR=/tmp
 # dia_engine_destroy) and the passes run with the default preheat unless PMC_PREHEAT says otherwise
 for c in FETCH_SIZE WRITE_SIZE; do
   rm -rf /tmp/pmc_$c
-  rocprofv3 --pmc $c --output-format csv -d /tmp/pmc_$c -- python3 $GRAFT_REPO_ROOT/bench.py --steps 8 --warmup 2 --cpu-steps 0 --profile-steps 0 --no-configs ${PMC_PREHEAT:+--preheat $PMC_PREHEAT} > $O/${R}_pmc_$c.log 2>&1 || { echo "pmc $c pass FAILED (see ${R}_pmc_$c.log)"; tail -5 $O/${R}_pmc_$c.log; continue; }
+  rocprofv3 --pmc $c --output-format csv -d /tmp/pmc_$c -- python3 $ROOT/bench.py --full --steps 8 --warmup 2 --cpu-steps 0 --profile-steps 0 --no-configs ${PMC_PREHEAT:+--preheat $PMC_PREHEAT} > $O/${R}_pmc_$c.log 2>&1 || { echo "pmc $c pass FAILED (see ${R}_pmc_$c.log)"; tail -5 $O/${R}_pmc_$c.log; continue; }
   python3 - <<PY
 import csv, glob, collections
 f = glob.glob("/tmp/pmc_$c/*/*counter_collection.csv")[0]

@@ -1,9 +1,10 @@
 #!/bin/bash
 # HBM fetch bytes per launch of the z-form GEMMs at batch 16 / 32: do the m-tile workgroups of a strip share its weights through L2?
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
 for b in 8 32; do
   rm -rf /tmp/pmcb_$b
-  rocprofv3 --pmc FETCH_SIZE --output-format csv -d /tmp/pmcb_$b -- python3 $GRAFT_REPO_ROOT/bench.py --batch $b --steps 8 --warmup 2 --cpu-steps 0 --profile-steps 0 --no-configs --preheat 0 > /dev/null 2>&1
+  rocprofv3 --pmc FETCH_SIZE --output-format csv -d /tmp/pmcb_$b -- python3 $ROOT/bench.py --full --batch $b --steps 8 --warmup 2 --cpu-steps 0 --profile-steps 0 --no-configs --preheat 0 > /dev/null 2>&1
   python3 - <<PY
 import csv, glob, collections
 f = glob.glob("/tmp/pmcb_$b/*/*counter_collection.csv")[0]

@@ -6,7 +6,7 @@ timeout -k 10 900 python -m pytest tests -m gpu -x -q -s > $O/r3_tests.log 2>&1;
 tail -5 $O/r3_tests.log
 grep -E "long horizon|batch 64|max-abs" $O/r3_tests.log | tail -30
 [ $rc -ne 0 ] && exit $rc
-timeout -k 10 400 python bench.py > $O/prof/r03_bench_default_a.json 2> $O/r3_bench.err || { tail -5 $O/r3_bench.err; exit 1; }
+timeout -k 10 400 python bench.py --full > $O/prof/r03_bench_default_a.json 2> $O/r3_bench.err || { tail -5 $O/r3_bench.err; exit 1; }
 python - <<'PY'
 import json
 d=json.loads(open("gpurun_out/prof/r03_bench_default_a.json").read().strip().splitlines()[-1])

@@ -1,4 +1,4 @@
-"""The bench line committed under profiles/ (produced by `python bench.py` on the GPU box) carries every key the
+"""The bench line committed under profiles/ (produced by `python bench.py --full` on an MI355X) carries every key the
 driver contract names.  CPU-only: it reads the committed evidence, it does not run the bench."""
 import json
 import os
@@ -75,3 +75,34 @@ def test_default_batch_follows_baseline_configs():
     assert bench.default_batch(1) == 1
     assert [bench.default_batch(n) for n in (2, 4, 8)] == [32, 16, 8]
     assert bench.MIXED_L == [32, 64, 96, 128, 192, 256, 384, 512] and sum(bench.MIXED_L) == 1664
+
+
+def test_dump_outputs_writes_float32_under_the_cap(tmp_path, monkeypatch):
+    """--dump-outputs: the last step's logits and the token buffers up to the current step, float32; over the size cap,
+    the same leading utterances every time"""
+    import sys
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import torch
+    import bench
+
+    class Sess:
+        B = 3
+        cur = torch.tensor([5, 5, 5], dtype=torch.int32)
+        tokens = torch.arange(3 * 16 * 9, dtype=torch.int32).reshape(3, 16, 9)
+        pred = -tokens
+
+        def logits_host(self):
+            return np.arange(3 * 2 * 9 * 7, dtype=np.float32).reshape(3, 2, 9, 7)
+
+    bench.dump_outputs(Sess(), str(tmp_path / "all"))
+    got = {n: np.load(tmp_path / "all" / f"{n}.npy") for n in ("logits", "tokens", "pred")}
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert got["logits"].shape == (3, 2, 9, 7) and got["tokens"].shape == (3, 5, 9) and got["pred"].shape == (3, 5, 9)
+    assert np.array_equal(got["tokens"], Sess.tokens[:, :5].numpy()) and np.array_equal(got["pred"], -got["tokens"])
+    per_utt = (2 * 9 * 7 + 2 * 5 * 9) * 4
+    monkeypatch.setattr(bench, "DUMP_CAP_BYTES", 2 * per_utt + 1)
+    bench.dump_outputs(Sess(), str(tmp_path / "cap"), "_rank1")
+    cap = {n: np.load(tmp_path / "cap" / f"{n}_rank1.npy") for n in ("logits", "tokens", "pred")}
+    assert sum(a.nbytes for a in cap.values()) <= 2 * per_utt + 1
+    assert all(np.array_equal(cap[n], got[n][:2]) for n in cap)

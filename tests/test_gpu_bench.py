@@ -42,6 +42,32 @@ def test_bench_two_ranks_share_device():
     assert "cpu_baseline" not in d or d["cpu_baseline"] is None
 
 
+def test_bench_plain_run_dumps_the_same_outputs_as_full(tmp_path):
+    """A plain single-GPU run (no --full): the headline line without the extra measurements, --steps timed steps, and the
+    outputs of its last timed step written by --dump-outputs: the same bits in a second plain run and in a --full run with
+    the same arguments (24 steps reach the forced end of generation, which the session's length places)."""
+    import numpy as np
+    outs = []
+    for i, extra in enumerate([[], [], ["--full", "--no-configs", "--cpu-steps", "0"]]):
+        d = tmp_path / f"run{i}"
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "24", "--warmup", "3", "--dump-outputs", str(d)] + extra
+        r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        line = json.loads(lines[0])
+        assert line["steps"] == 24 and line["warmup"] == 3 and line["unit"] == "frames/s" and line["higher_is_better"] is True
+        assert line["dtype"] == "bf16" and line["value"] > 0 and abs(line["value"] - 1000.0 / line["ms_per_step"]) <= 1e-2 * line["value"]
+        extras = ("roofline", "roofline_by_kernel", "prefill")
+        assert all((k in line) == bool(extra) for k in extras) and "configs" not in line and "cpu_baseline" not in line
+        outs.append({n: np.load(d / f"{n}.npy") for n in ("logits", "tokens", "pred")})
+    a = outs[0]
+    assert a["logits"].shape == (1, 2, 9, 1028) and a["tokens"].shape == (1, 1 + 3 + 24, 9) and a["pred"].shape == a["tokens"].shape
+    for n in a:
+        assert a[n].dtype == np.float32 and np.isfinite(a[n]).all(), n
+        assert all(np.array_equal(a[n], o[n]) for o in outs[1:]), n
+
+
 def test_rccl_world1_broadcast_and_gather_on_device_tensors():
     """The collectives of dia_hip/dist.py under the production backend ("nccl" = RCCL) with tensors on the GPU, as far as one GPU
     reaches: a world of ONE rank initialises RCCL, takes the arena-signature all-reduces and the broadcast of a flat arena, and
