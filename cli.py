@@ -54,6 +54,9 @@ def build_parser() -> argparse.ArgumentParser:
     g = p.add_argument_group("Infrastructure")
     g.add_argument("--device", type=str, default=None, help="HIP device such as cuda:0 (default: the current one)")
     g.add_argument("--compute-dtype", type=str, default="bfloat16", choices=["float16", "bfloat16", "float32"], help="K/V cache dtype: bfloat16 (default; float16 is accepted and mapped to it) or float32.")
+    g.add_argument("--fp32-weights", type=str, default="exact", choices=["exact", "bf16x2", "round"],
+                   help="compute_dtype float32 with a checkpoint bf16 cannot hold: exact = three bf16 planes (generic kernel), "
+                        "bf16x2 = hi + lo bf16 planes (relative error <= 2^-17, tuned kernels), round = one rounded bf16 tile set")
     g.add_argument("--verbose", action="store_true", help="report prefill and generation timing")
     return p
 
@@ -72,6 +75,7 @@ def main(argv=None) -> int:
 
     from dia_hip.model import Dia
 
+    Dia.fp32_weights = args.fp32_weights
     if args.seed is not None:
         set_seed(args.seed)
         print(f"Using seed: {args.seed}")

@@ -190,6 +190,10 @@ static int enqueue_step(dia_engine* e, bool with_sampler) {
       if (L.kt_wo % 64 == 0 && L.kt_wo / 64 >= 2 && L.kt_wo / 64 <= 8) wo_sk = L.kt_wo / 64;
       if (wo_sk > 1 && L.ns_wo * wo_sk >= 512 && L.ns_wo % 2 == 0) wo_spw = 2;
     }
+    // two-plane weights (kt_wo counts hi and lo tiles): the tuned forms take 128 weight k-tiles per workgroup, so K splits into
+    // kt_wo / 128 ranges at every row count (dense wo: 4); other hidden widths run unsplit on the generic kernel
+    const int w2_sk = (d.w_planes == 2 && L.kt_wo % 128 == 0 && L.kt_wo / 128 <= 8) ? L.kt_wo / 128 : 1;
+    if (d.w_planes == 2) { wo_sk = w2_sk; wo_spw = 0; }
     if (dia_tune(DIA_TUNE_WO_SK) >= 1 && dia_tune(DIA_TUNE_WO_SK) <= 8 && L.kt_wo % dia_tune(DIA_TUNE_WO_SK) == 0) wo_sk = dia_tune(DIA_TUNE_WO_SK);
     g.sk = wo_sk; g.sk_scratch = wo_sk > 1 ? d.sk_scratch : nullptr; g.sk_tickets = wo_sk > 1 ? d.sk_tickets : nullptr;
     bool wo_pair = false;
@@ -199,6 +203,10 @@ static int enqueue_step(dia_engine* e, bool with_sampler) {
       wo_pair = L.kt_wo % 4 == 0 && g.sk_scratch_floats >= (int64_t)((R + 15) / 16) * L.ns_wo * 4 * 256 &&
                 dia_tune(DIA_TUNE_WO_PAIR) != 0;
       g.sk = wo_pair ? 4 : 1;
+      if (d.w_planes == 2) {
+        wo_pair = w2_sk > 1 && g.sk_scratch_floats >= (int64_t)((R + 15) / 16) * L.ns_wo * w2_sk * 256;
+        g.sk = wo_pair ? w2_sk : 1;
+      }
     }
     if (dia_tune(DIA_TUNE_WO_NW) > 0) g.nw = dia_tune(DIA_TUNE_WO_NW);
     g.spw = wo_spw;

@@ -63,19 +63,21 @@ __global__ __launch_bounds__(NW * 64) void k_gemm(GemmK p) {
   const bool live = e_thread && m < p.M;
   float xpre[8], gpre[8];
 
-  // fp32 weights as three bf16 planes (w_planes == 3: hi, mid, lo tile sets back to back): the K loop below once per plane,
-  // into the same accumulators — 9 exact bf16 products per fp32 x fp32 one
+  // fp32 weights as planes: w_planes == 3 (hi, mid, lo tile sets back to back) runs the K loop below once per plane, into the
+  // same accumulators — 9 exact bf16 products per fp32 x fp32 one; w_planes == 2 (hi / lo tiles interleaved per k-tile inside each
+  // strip, layout.tile_weight_bf16x2) runs it once over the doubled k-tiles, weight k-tile kt meeting activation k-tile kt >> 1
   if (p.w_planes > 1) {
     prefetch_epilogue<MT, NW * 64>(p, tid, mt0, m, n0, live, xpre, gpre, inv_s);
     const int kt1 = min(kt0 + kpw, p.KT);
-    for (int pw = 0; pw < p.w_planes; ++pw) {
+    const int npw = p.w_planes == 2 ? 1 : p.w_planes, ash = p.w_planes == 2 ? 1 : 0;
+    for (int pw = 0; pw < npw; ++pw) {
       const bf16x8* Wp = Wt + pw * (p.w_plane_stride / 8);
       for (int kt = kt0; kt < kt1; ++kt) {
         const bf16x8 bb = DIA_WLOAD(Wp + (long)kt * 64);
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) {
           bf16x8 a3[DIA_NPLANES];
-          load_afrag3(p, aoff[mt] + (long)kt * 512, a3[0], a3[1], a3[2]);
+          load_afrag3(p, aoff[mt] + (long)(kt >> ash) * 512, a3[0], a3[1], a3[2]);
 #pragma unroll
           for (int pl = 0; pl < DIA_NPLANES; ++pl)
             acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a3[pl], bb, acc[mt], 0, 0, 0);
@@ -144,7 +146,9 @@ __global__ __launch_bounds__(NW * 64) void k_gemm(GemmK p) {
 // processor hands over in SGPRs at wave launch (kernarg preload, -mllvm -amdgpu-kernarg-preload-count=16) — the operand
 // and weight loads of the prologue then need no scalar load from the argument block, whose lines every CU of the grid
 // otherwise requests at the same moment (in-kernel stamps: 0.8 us from the start of a wave to its first weight load).
-template <int NW, int KPW, int RS, bool MULTI, bool AF32 = false, bool PF32 = false>
+// W2: two-plane weights (w_planes == 2): weight k-tile j of the range is plane j & 1 of activation k-tile j >> 1, so the A image
+// covers KPW / 2 k-tiles per wave; weight stream, prefetch and epilogues are those of the one-plane form.
+template <int NW, int KPW, int RS, bool MULTI, bool AF32 = false, bool PF32 = false, bool W2 = false>
 __global__ __launch_bounds__(NW * 64) void k_gemv_small(const bf16_raw* a_A, long a_aps, const bf16_raw* a_W, int a_KT, int a_M, int a_epi,
                                                         int a_nstrips, float* a_out, int a_ldo, const float* a_gnext, GemmK p) {
   p.A = a_A; p.a_plane_stride = a_aps; p.W = a_W; p.KT = a_KT; p.M = a_M; p.epi = a_epi; p.nstrips = a_nstrips;
@@ -162,6 +166,8 @@ __global__ __launch_bounds__(NW * 64) void k_gemv_small(const bf16_raw* a_A, lon
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int kt0 = w * KPW;                 // k-tile inside this workgroup's K range
   const int ktg = blockIdx.y * (NW * KPW); // first global k-tile of that range (split-K over gridDim.y)
+  constexpr int WS = W2 ? 1 : 0;           // weight k-tile -> activation k-tile: >> WS
+  const int ktga = ktg >> WS;              // first global activation k-tile of the range
   const int G = gridDim.x;                 // the workgroup walks strips blockIdx.x, +G, +2G, ...
   const bf16x8* Wl = reinterpret_cast<const bf16x8*>(p.W) + (long)(ktg + kt0) * 64 + lane;
   auto load_strip = [&](bf16x8* b, int strip) {
@@ -173,7 +179,9 @@ __global__ __launch_bounds__(NW * 64) void k_gemv_small(const bf16_raw* a_A, lon
 
   STAMP(0);
   bf16x8 b0[KPW], b1[MULTI ? KPW : 1];
-  constexpr int KT = NW * KPW;             // the dispatcher only picks this kernel when p.KT == NW*KPW
+  constexpr int KT = (NW * KPW) >> WS;     // activation k-tiles of the image (the dispatcher: p.KT == NW*KPW*gridDim.y)
+  constexpr int KPA = KPW >> WS;           // activation k-tiles per wave
+  static_assert(!W2 || KPW % 2 == 0, "two-plane weights: whole activation k-tiles per wave");
   constexpr int NT = NW * 64;
 #ifdef DIA_X_WFIRST
   load_strip(b0, blockIdx.x);                       // the HBM stream starts here
@@ -184,12 +192,12 @@ __global__ __launch_bounds__(NW * 64) void k_gemv_small(const bf16_raw* a_A, lon
   // retires in order, so anything queued behind 16-32 KiB of HBM loads per wave would stall its first
   // use (and with it the barrier below) until the whole strip has arrived.
   // (1) compact A image: chunk c = ((plane*KT + kt)*4 + kq)*RS + row, 16 bytes each
-  constexpr int CH = (3 * KPW * RS + 15) / 16;        // chunks per thread = 3*KT*4*RS / NT
+  constexpr int CH = (3 * KPA * RS + 15) / 16;        // chunks per thread = 3*KT*4*RS / NT
   constexpr int nchunks = DIA_NPLANES * KT * 4 * RS;
   // AF32: the image arrives as fp32 tiles (common.hpp) — 32 bytes per (k-tile, quarter, row) entry instead of three 16-byte plane
   // chunks, a third less to pull before the barrier; the thread that loads an entry splits it into the three plane chunks
   constexpr int nentries = KT * 4 * RS;
-  constexpr int CE = (KPW * RS + 15) / 16;           // entries per thread = KT*4*RS / NT
+  constexpr int CE = (KPA * RS + 15) / 16;           // entries per thread = KT*4*RS / NT
   bf16x8 v0[AF32 ? 1 : CH];
   float4 ex[AF32 ? CE : 1], ey[AF32 ? CE : 1];
   if constexpr (AF32) {
@@ -198,7 +206,7 @@ __global__ __launch_bounds__(NW * 64) void k_gemv_small(const bf16_raw* a_A, lon
     for (int u = 0; u < CE; ++u) {
       const int c = min(tid + u * NT, nentries - 1);
       const int row = c % RS, kq = (c / RS) & 3, kt = c / (4 * RS);
-      const float4* src = reinterpret_cast<const float4*>(Af + ((long)(ktg + kt) * 64 + row + 16 * kq) * 8);
+      const float4* src = reinterpret_cast<const float4*>(Af + ((long)(ktga + kt) * 64 + row + 16 * kq) * 8);
       ex[u] = src[0]; ey[u] = src[1];
     }
   } else {
@@ -206,7 +214,7 @@ __global__ __launch_bounds__(NW * 64) void k_gemv_small(const bf16_raw* a_A, lon
     for (int u = 0; u < CH; ++u) {
       const int c = min(tid + u * NT, nchunks - 1);
       const int row = c % RS, kq = (c / RS) & 3, kt = (c / (4 * RS)) % KT, pl = c / (4 * RS * KT);
-      v0[u] = *reinterpret_cast<const bf16x8*>(p.A + pl * p.a_plane_stride + ((long)(ktg + kt) * 64 + row + 16 * kq) * 8);
+      v0[u] = *reinterpret_cast<const bf16x8*>(p.A + pl * p.a_plane_stride + ((long)(ktga + kt) * 64 + row + 16 * kq) * 8);
     }
   }
   // (2) strip sums of squares for the row scale: 8 threads per row, up to 16 strips each per round
@@ -288,7 +296,7 @@ __global__ __launch_bounds__(NW * 64) void k_gemv_small(const bf16_raw* a_A, lon
     for (int i = 0; i < KPW; ++i) {
 #pragma unroll
       for (int pl = 0; pl < DIA_NPLANES; ++pl) {
-        const bf16x8 a = As[((pl * KT + kt0 + i) * 4 + akq) * RS + arow];
+        const bf16x8 a = As[((pl * KT + ((kt0 + i) >> WS)) * 4 + akq) * RS + arow];
         acc[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, bc[i], acc[0], 0, 0, 0);
       }
     }
@@ -351,7 +359,8 @@ constexpr size_t g16_alds(int nw, int kpw) { return (size_t)2 * nw * kpw * 64 * 
 // this frees let the z-form run the element-per-thread tail of the 16-row kernels (256 threads sum, scale and emit one tile
 // element each) instead of round 1's 32-thread tail, whose serial reduce + epilogue on ONE wave was what a strip cost
 // (1.7 us per strip at 128 rows against 0.32 us of MFMA time: in-kernel; a deeper weight ring alone changed nothing).
-template <int NW, int KPW, bool MULTI, bool MZ = false, bool AF32 = false, bool PF32 = false, bool PAIR = false, bool ALDS = false>
+// W2: two-plane weights (w_planes == 2, see k_gemv_small): a wave holds the KPW / 2 activation k-tiles its KPW weight tiles meet.
+template <int NW, int KPW, bool MULTI, bool MZ = false, bool AF32 = false, bool PF32 = false, bool PAIR = false, bool ALDS = false, bool W2 = false>
 __global__ __launch_bounds__(NW * 64) void k_gemm16(const bf16_raw* a_A, long a_aps, const bf16_raw* a_W, int a_KT, int a_M, int a_epi,
                                                     int a_nstrips, float* a_out, int a_ldo, const float* a_gnext, GemmK p) {
   // (leading arguments = fields of p, preloaded into SGPRs: see k_gemv_small)
@@ -383,6 +392,10 @@ __global__ __launch_bounds__(NW * 64) void k_gemm16(const bf16_raw* a_A, long a_
   }
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int kt0 = blockIdx.y * (NW * KPW) + w * KPW;      // split-K over gridDim.y
+  constexpr int WS = W2 ? 1 : 0;                          // weight k-tile -> activation k-tile: >> WS
+  constexpr int KPA = KPW >> WS;                          // activation k-tiles per wave
+  static_assert(!W2 || KPW % 2 == 0, "two-plane weights: whole activation k-tiles per wave");
+  const int kta0 = kt0 >> WS;
   const int G = gridDim.x;
   __shared__ int sk_flag;
   const bf16x8* Wl = reinterpret_cast<const bf16x8*>(p.W) + (long)kt0 * 64 + lane;
@@ -401,16 +414,16 @@ __global__ __launch_bounds__(NW * 64) void k_gemm16(const bf16_raw* a_A, long a_
 
   // A fragments (rows >= M alias the last valid row: no extra L2 traffic, results never stored)
   const int alane = (lane & 48) | min(lane & 15, p.M - 1);
-  bf16x8 a[KPW][DIA_NPLANES];
+  bf16x8 a[KPA][DIA_NPLANES];
   constexpr bool ALDS_LATE = ALDS && !MZ;      // see below
   if constexpr (AF32) {     // fp32 tiles (compile-time: a second operand path behind a branch would end the basic block in which
     // all loads of the wave are issued).  32 bytes per fragment; the raw values land in the registers of planes 0 and 1 of their
     // own fragment and are split in place — no second register set beside the 12 * KPW VGPRs of `a`
-    const float4* Af = reinterpret_cast<const float4*>(reinterpret_cast<const float*>(p.A) + ((long)kt0 * 64 + alane) * 8);
+    const float4* Af = reinterpret_cast<const float4*>(reinterpret_cast<const float*>(p.A) + ((long)kta0 * 64 + alane) * 8);
     // (masking the lanes of missing rows off instead of aliasing them to the last row was measured: slower at every row count, -3.5 % at 16 rows where
     // nothing is masked — the branch costs more than the aliased lanes do)
 #pragma unroll
-    for (int i = 0; i < KPW; ++i) {
+    for (int i = 0; i < KPA; ++i) {
 #ifdef DIA_X_NOA                                             /* TIMING ONLY: one k-tile of the image eight times (wrong results) */
       a[i][0] = __builtin_bit_cast(bf16x8, Af[0]);
       a[i][1] = __builtin_bit_cast(bf16x8, Af[1]);
@@ -421,27 +434,27 @@ __global__ __launch_bounds__(NW * 64) void k_gemm16(const bf16_raw* a_A, long a_
     }
     if constexpr (!ALDS_LATE) {
 #pragma unroll
-      for (int i = 0; i < KPW; ++i)
+      for (int i = 0; i < KPA; ++i)
         split3x8(__builtin_bit_cast(float4, a[i][0]), __builtin_bit_cast(float4, a[i][1]), a[i][0], a[i][1], a[i][2]);
     }
   } else {
 #pragma unroll
-    for (int i = 0; i < KPW; ++i)
+    for (int i = 0; i < KPA; ++i)
 #pragma unroll
       for (int pl = 0; pl < DIA_NPLANES; ++pl)
-        a[i][pl] = *reinterpret_cast<const bf16x8*>(p.A + pl * p.a_plane_stride + ((long)(kt0 + i) * 64 + alane) * 8);
+        a[i][pl] = *reinterpret_cast<const bf16x8*>(p.A + pl * p.a_plane_stride + ((long)(kta0 + i) * 64 + alane) * 8);
   }
-  bf16x8* my = reinterpret_cast<bf16x8*>(smem_raw + g16_smem(NW)) + (long)w * 2 * KPW * 64 + lane;     // ALDS: [plane - 1][i][lane]
+  bf16x8* my = reinterpret_cast<bf16x8*>(smem_raw + g16_smem(NW)) + (long)w * 2 * KPA * 64 + lane;     // ALDS: [plane - 1][i][lane]
   // ALDS_LATE (the 16-row persistent form): split and LDS stores wait for the image, so they sit BEHIND the first weight request
   // (batch 8 +0.9 %).  Not in the z-form: there the same move costs qkv / cq 0.9 us at 32 rows (profiles/r03_early_wait_ab.txt)
   if constexpr (ALDS && !ALDS_LATE) {
 #pragma unroll
-    for (int i = 0; i < KPW; ++i) { my[i * 64] = a[i][1]; my[(KPW + i) * 64] = a[i][2]; }
+    for (int i = 0; i < KPA; ++i) { my[i * 64] = a[i][1]; my[(KPA + i) * 64] = a[i][2]; }
   }
-  // plane pl of the wave's i-th A fragment
+  // plane pl of the A fragment that the wave's i-th weight tile meets
   auto afrag = [&](int i, int pl) -> bf16x8 {
-    if constexpr (ALDS) { if (pl > 0) return my[((pl - 1) * KPW + i) * 64]; }
-    return a[i][pl];
+    if constexpr (ALDS) { if (pl > 0) return my[((pl - 1) * KPA + (i >> WS)) * 64]; }
+    return a[i >> WS][pl];
   };
   // strip sums of squares: 8 threads per row
   const bool has_norm = p.ssq_in != nullptr;
@@ -489,9 +502,9 @@ __global__ __launch_bounds__(NW * 64) void k_gemm16(const bf16_raw* a_A, long a_
   __builtin_amdgcn_sched_barrier(0);
   if constexpr (ALDS_LATE) {
 #pragma unroll
-    for (int i = 0; i < KPW; ++i) {
+    for (int i = 0; i < KPA; ++i) {
       if constexpr (AF32) split3x8(__builtin_bit_cast(float4, a[i][0]), __builtin_bit_cast(float4, a[i][1]), a[i][0], a[i][1], a[i][2]);
-      my[i * 64] = a[i][1]; my[(KPW + i) * 64] = a[i][2];
+      my[i * 64] = a[i][1]; my[(KPA + i) * 64] = a[i][2];
     }
   }
   STAMP(1);
@@ -519,7 +532,7 @@ __global__ __launch_bounds__(NW * 64) void k_gemm16(const bf16_raw* a_A, long a_
       for (int i = 0; i < KPW; ++i)
 #pragma unroll
         for (int pl = 0; pl < DIA_NPLANES; ++pl)
-          acc[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[i][pl], bc[i], acc[0], 0, 0, 0);
+          acc[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[i >> WS][pl], bc[i], acc[0], 0, 0, 0);
       reduce_to_tile<1, NW, true>(acc, red, tile, tid, lane, w);
       const bool last_slice = splitk_combine(p, tile, strip, tid, &sk_flag);      // workgroup-uniform; true without split-K
       if (e_thread) {
@@ -667,11 +680,11 @@ __global__ __launch_bounds__(NW * 64) void k_gemm16(const bf16_raw* a_A, long a_
 #pragma unroll
       for (int i = 0; i < KPW; ++i)
 #pragma unroll
-        for (int pl = 0; pl < DIA_NPLANES; ++pl) acc0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[i][pl], b0[i], acc0, 0, 0, 0);
+        for (int pl = 0; pl < DIA_NPLANES; ++pl) acc0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[i >> WS][pl], b0[i], acc0, 0, 0, 0);
 #pragma unroll
       for (int i = 0; i < KPW; ++i)
 #pragma unroll
-        for (int pl = 0; pl < DIA_NPLANES; ++pl) acc1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[i][pl], b1[i], acc1, 0, 0, 0);
+        for (int pl = 0; pl < DIA_NPLANES; ++pl) acc1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[i >> WS][pl], b1[i], acc1, 0, 0, 0);
       STAMP(2);
       red[w * 64 + lane] = acc0;
       red[NW * 64 + w * 64 + lane] = acc1;
@@ -1949,6 +1962,47 @@ int launch_small_rs(const GemmK& k, int nw, int sk, hipStream_t st, bool& handle
   return DIA_OK;
 }
 
+// Two-plane weights (w_planes == 2).  Every tuned form takes 128 weight k-tiles per workgroup (64 activation k-tiles: K = 2048,
+// or a split-K slice of a longer K) as 8 waves x 16 weight tiles — the bytes per wave in flight of the one-plane 8 x 8 forms doubled,
+// the A operand of a wave unchanged (8 activation k-tiles).
+constexpr int W2_KTW = 128;
+
+template <int RS>
+int launch_small_w2(const GemmK& k, int sk, hipStream_t st) {
+  const size_t smem = small_smem(8, W2_KTW / 2, RS);       // the image covers the activation k-tiles: 48 KiB at 4 rows
+  if (sk > 1) {
+    launch_small_kernel<k_gemv_small<8, 16, RS, false, true, true, true>>(dim3(k.nstrips, sk), dim3(512), smem, st, k);
+    return dia_check_launch("k_gemv_small");
+  }
+  int spw = k.spw > 0 ? k.spw : (k.nstrips >= 1024 ? 4 : 1);          // as launch_small
+  if (k.spw <= 0 && k.nstrips > 512 && k.nstrips < 1024) spw = (k.nstrips + 255) / 256;
+  if (dia_tune(DIA_TUNE_GEMM_SPW) > 0) spw = dia_tune(DIA_TUNE_GEMM_SPW);
+  if (spw > 1) launch_small_kernel<k_gemv_small<8, 16, RS, true, true, true, true>>(dim3((k.nstrips + spw - 1) / spw), dim3(512), smem, st, k);
+  else launch_small_kernel<k_gemv_small<8, 16, RS, false, true, true, true>>(dim3(k.nstrips), dim3(512), smem, st, k);
+  return dia_check_launch("k_gemv_small");
+}
+
+// 5..128 rows: the persistent k_gemm16 with the mid / lo planes of A in LDS (ALDS) — the hi plane (32 VGPRs) and two weight strips in
+// flight (128 VGPRs) stay in registers.  mz >= 2: the z-form over the m-tiles, split-K or not.
+int launch_g16_w2(const GemmK& k, int mz, int sk, hipStream_t st) {
+  int rc = dia_kernels_init_once();       // 148 KiB of LDS: the raised dynamic-LDS limit
+  if (rc) return rc;
+  const size_t smem = g16_smem(8) + g16_alds(8, W2_KTW / 16);
+  int spw = k.spw > 0 ? k.spw : (k.nstrips >= 1024 ? 4 : 1);          // as launch_g16
+  if (mz == 1 && k.spw <= 0 && sk == 1 && k.nstrips > 256 && k.nstrips < 1024) spw = (k.nstrips + 255) / 256;
+  if (mz >= 2 && k.spw <= 0) {
+    int per = 256 / mz / sk;
+    per = per >= 8 ? per / 8 * 8 : (per > 0 ? per : 1);
+    spw = (k.nstrips + per - 1) / per;
+  }
+  if (dia_tune(DIA_TUNE_GEMM_SPW) > 0) spw = dia_tune(DIA_TUNE_GEMM_SPW);
+  int gx = (k.nstrips + spw - 1) / spw;
+  if (mz >= 2 && (gx * sk) % 8 != 0 && (gx + 7) / 8 * 8 <= k.nstrips) gx = (gx + 7) / 8 * 8;   // pairs on one XCD
+  if (mz >= 2) launch_small_kernel<k_gemm16<8, 16, true, true, true, true, false, true, true>>(dim3(gx, sk, mz), dim3(512), smem, st, k);
+  else launch_small_kernel<k_gemm16<8, 16, true, false, true, true, false, true, true>>(dim3(gx, sk), dim3(512), smem, st, k);
+  return dia_check_launch("k_gemm16");
+}
+
 template <int NW, int KPW>
 int small_attr() {
   hipError_t e[4];
@@ -2002,6 +2056,8 @@ int dia_gemm_init() {
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm16<8, 8, true, true, false, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(g16_smem(8) + g16_alds(8, 8))) != hipSuccess) rc = 1;
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm16<8, 4, true, true, true, true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(g16_smem(8) + g16_alds(8, 4))) != hipSuccess) rc = 1;
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm16<8, 4, true, true, false, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(g16_smem(8) + g16_alds(8, 4))) != hipSuccess) rc = 1;
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm16<8, 16, true, true, true, true, false, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(g16_smem(8) + g16_alds(8, W2_KTW / 16))) != hipSuccess) rc = 1;
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm16<8, 16, true, false, true, true, false, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(g16_smem(8) + g16_alds(8, W2_KTW / 16))) != hipSuccess) rc = 1;
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm_tile_ws<2, 2, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)gt_smem(2, 8)) != hipSuccess) rc = 1;
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm_tile_ws<2, 2, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)gt_smem(2, 8)) != hipSuccess) rc = 1;
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm_tile_ws<2, 4, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)gt_smem(2, 8)) != hipSuccess) rc = 1;
@@ -2027,9 +2083,41 @@ extern "C" int dia_has_experiments(void) {
 //   5..16 rows        k_gemm16       (register-resident A fragments)
 //   17..128 rows      k_gemm16 over gridDim.z m-tiles (weights shared through one XCD's L2)
 // Prefill (hundreds of packed rows): k_gemm_tile_ws (MFMA-bound).  Everything else: k_gemm (any shape).
+// Two-plane weights (w_planes == 2): gemm_w2 below.
+namespace {
+int gemm_w2(const dia_gemm_args* a, GemmK& k, hipStream_t st) {
+  const int sk = a->sk > 1 ? a->sk : 1;
+  if (sk > 1 && (!a->sk_scratch || !a->sk_tickets || a->KT % sk != 0)) return dia_fail(DIA_E_ARG, "dia_gemm: split-K needs sk_scratch, sk_tickets and KT % sk == 0");
+  const int mtiles = (a->M + 15) / 16;
+  const bool fast_epi = a->epi != DIA_EPI_CROSSKV && !(a->epi == DIA_EPI_RESID_EMIT && !a->gnext);
+  const bool emits = a->epi == DIA_EPI_RESID_EMIT || a->epi == DIA_EPI_SWIGLU_EMIT;
+  const bool uni_f32 = k.a_f32 && (!emits || k.p_f32);             // the decode step's format: fp32 tiles in and out
+  const int mz_max = dia_tune(DIA_TUNE_GEMM_MZ_MAX) >= 0 ? dia_tune(DIA_TUNE_GEMM_MZ_MAX) : 8;
+  if (uni_f32 && fast_epi && a->KT % sk == 0 && a->KT / sk == W2_KTW && (a->nw == 0 || a->nw == 8)) {
+    if (a->M <= 4) return a->M <= 2 ? launch_small_w2<2>(k, sk, st) : launch_small_w2<4>(k, sk, st);
+    if (mtiles == 1) return launch_g16_w2(k, 1, sk, st);
+    if (mtiles <= mz_max && (sk == 1 || a->sk_scratch_floats >= (int64_t)mtiles * a->nstrips * sk * 256)) return launch_g16_w2(k, mtiles, sk, st);
+  }
+  if (sk > 1) return dia_fail(DIA_E_ARG, "dia_gemm: two-plane weights: no split-K kernel for this shape");
+  // every other shape (encoder, cross-K/V, planes or mixed activation formats, compacted K): the generic kernel
+  const int nw = (a->KT % 8 == 0) ? 8 : 4;
+  if (mtiles == 1) return launch_nw<1>(k, nw, 1, st);
+  if (mtiles == 2) return launch_nw<2>(k, nw, 1, st);
+  return launch_nw<4>(k, nw, (mtiles + 3) / 4, st);
+}
+}  // namespace
+
 extern "C" int dia_gemm(const dia_gemm_args* a, void* stream) {
   if (!a || !a->A || (!a->W && !a->sp_blocks)) return dia_fail(DIA_E_ARG, "dia_gemm: null argument");
   if (a->M <= 0 || a->KT <= 0 || a->nstrips <= 0) return dia_fail(DIA_E_ARG, "dia_gemm: empty problem");
+  if (a->w_planes == 2) {
+    if (a->w_layout == 1)
+      return dia_fail(DIA_E_ARG, "dia_gemm: w_planes = 2 interleaves hi / lo tiles inside the strip layout; the diagonal layout (w_layout = 1) has no two-plane form");
+    if (a->sp_blocks || a->sp_toff)
+      return dia_fail(DIA_E_ARG, "dia_gemm: w_planes = 2 streams dense hi / lo tiles; the zero-skipping sparse stream has no two-plane form");
+    if (!a->W || a->KT % 2 != 0) return dia_fail(DIA_E_ARG, "dia_gemm: w_planes = 2 needs W and an even KT (two tiles per activation k-tile)");
+    if (a->KT / 2 > a->a_ktiles) return dia_fail(DIA_E_ARG, "dia_gemm: weight K exceeds the plane layout's K");
+  }
   if (a->w_layout == 1) {     // diagonal 4-column tiles (layout.diag_tile_weight): M <= 4, RESID_EMIT, fp32 tiles in and out
     const int groups = a->nstrips;               // here: 8-column half strips
     if (!a->out || !a->P || !a->ssq_out || a->ssq_ld < a->M || a->a_ktiles < a->KT) return dia_fail(DIA_E_ARG, "dia_gemm: diagonal layout: missing buffer");
@@ -2045,7 +2133,7 @@ extern "C" int dia_gemm(const dia_gemm_args* a, void* stream) {
     else launch_kernel<k_gemv_diag<4>>(dim3(groups), dim3(1024), smem, (hipStream_t)stream, k);
     return dia_check_launch("k_gemv_diag");
   }
-  if (a->KT > a->a_ktiles) return dia_fail(DIA_E_ARG, "dia_gemm: weight K exceeds the plane layout's K");
+  if (a->w_planes != 2 && a->KT > a->a_ktiles) return dia_fail(DIA_E_ARG, "dia_gemm: weight K exceeds the plane layout's K");
   if (a->a_plane_stride % 8 != 0 || a->p_plane_stride % 8 != 0) return dia_fail(DIA_E_ARG, "dia_gemm: plane stride must be a multiple of 8");
   if ((a->epi == DIA_EPI_SCALE_STORE || a->epi == DIA_EPI_RESID_EMIT) && (!a->out || (!a->strip_map && a->ldo < a->nstrips * 16) || a->ldo % 4 != 0))
     return dia_fail(DIA_E_ARG, "dia_gemm: output leading dimension too small");
@@ -2068,8 +2156,9 @@ extern "C" int dia_gemm(const dia_gemm_args* a, void* stream) {
   }
   GemmK k;
   fill_gemmk(a, k);
+  if (a->w_planes == 2) return gemm_w2(a, k, (hipStream_t)stream);
   if (a->w_planes > 1) {      // fp32 weights as three planes: the generic kernel, whatever the shape (exactness, not speed)
-    if (a->w_planes != 3) return dia_fail(DIA_E_ARG, "dia_gemm: w_planes must be 0, 1 or 3");
+    if (a->w_planes != 3) return dia_fail(DIA_E_ARG, "dia_gemm: w_planes must be 0, 1, 2 or 3");
     const int mt_ = (a->M + 15) / 16;
     const int nw_ = (a->KT % 8 == 0) ? 8 : 4;
     hipStream_t st_ = (hipStream_t)stream;

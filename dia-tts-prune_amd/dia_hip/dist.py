@@ -49,8 +49,8 @@ def broadcast_weights(w, src: int = 0, group=None) -> int:
     a DeviceWeights.empty_like_config() of the same config: same tensor order, same offsets.
 
     Every rank first takes part in one MIN and one MAX all-reduce of (arena bytes, compacted, weight planes): a rank
-    whose arena differs — a compacted (structured-pruned) model has checkpoint-dependent shapes, three weight planes
-    triple the arena — makes EVERY rank raise, instead of one rank raising alone while the others wait in the broadcast."""
+    whose arena differs — a compacted (structured-pruned) model has checkpoint-dependent shapes, two or three weight
+    planes double or triple the arena — makes EVERY rank raise, instead of one rank raising alone while the others wait in the broadcast."""
     import torch.distributed as dist
 
     if w.flat is None:

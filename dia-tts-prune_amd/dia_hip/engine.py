@@ -52,14 +52,16 @@ class DeviceWeights:
         """compact: "auto" = drop structure that a structured-pruned checkpoint zeroed (decoder only),
         "off" = keep every matrix at its checkpoint shape (zeros are streamed).
         weight_planes: 1 = every DenseGeneral kernel as ONE bf16 tile set (exact for bf16-representable checkpoints, the fast
-        kernels); 3 = the hi / mid / lo bf16 planes of the fp32 weights (exact for any checkpoint, 3x the bytes, the generic
-        kernel: the parity configuration of a genuine fp32 checkpoint).
+        kernels); 2 = the hi / lo bf16 planes of the fp32 weights interleaved per k-tile (layout.tile_weight_bf16x2: relative
+        error <= 2^-17, 2x the bytes, the tuned decode kernels; every TiledW.kt counts both planes); 3 = the hi / mid / lo bf16
+        planes of the fp32 weights (exact for any checkpoint, 3x the bytes, the generic kernel: the parity configuration of a
+        genuine fp32 checkpoint).
         seg: "on" = a dense Dia-1.6B-shaped decoder on a GPU also carries the ring arenas of the persistent MLP segments
         (layout.seg_ring; + 2.2 GB: co, wi, wo and the following layer's qkv once more, per CU in consumption order), which
         batch 1-2 sessions then run instead of four launches per layer when the knob seg=1 is set.  EXPERIMENT, default "off":
         measured 43 us per segment against 31 us for the four launches it replaces."""
-        if weight_planes not in (1, 3):
-            raise ValueError("weight_planes must be 1 or 3")
+        if weight_planes not in (1, 2, 3):
+            raise ValueError("weight_planes must be 1, 2 or 3")
         self.weight_planes = weight_planes
         m, e, d = cfg.model, cfg.model.encoder, cfg.model.decoder
         if d.gqa_head_dim != HEAD_DIM or d.cross_head_dim != HEAD_DIM or e.head_dim != HEAD_DIM:
@@ -74,7 +76,12 @@ class DeviceWeights:
         self.max_weight_rounding = 0.0                  # largest |w - bf16(w)| / max|w| over the DenseGeneral kernels
 
         def tile(w2d) -> TiledW:
-            t, kt, ns = lay.tile_weight_planes(w2d) if weight_planes == 3 else lay.tile_weight(w2d)
+            if weight_planes == 3:
+                t, kt, ns = lay.tile_weight_planes(w2d)
+            elif weight_planes == 2:
+                t, kt, ns = lay.tile_weight_bf16x2(w2d)
+            else:
+                t, kt, ns = lay.tile_weight(w2d)
             if w2d.numel() and weight_planes == 1:
                 err = (w2d - w2d.to(torch.bfloat16).to(w2d.dtype)).abs().max()
                 scale = w2d.abs().max()
@@ -590,8 +597,9 @@ class DecodeSession:
                 Lmax = _ceil(max(self.lens), 16)
                 Hmax = max(EL["heads"] for EL in w.enc_layers)
                 ekt = E // 32
-                akt = max(max(1, Hmax * HEAD_DIM // 32), max(EL["o"].kt for EL in w.enc_layers))   # o rows may be zero-padded
-                hkt = max(EL["wo"].kt for EL in w.enc_layers)                 # (compacted) hidden width in k-tiles
+                kdiv = 2 if w.weight_planes == 2 else 1                      # (two-plane weights: kt counts hi and lo tiles)
+                akt = max(max(1, Hmax * HEAD_DIM // 32), max(EL["o"].kt // kdiv for EL in w.enc_layers))   # o rows may be zero-padded
+                hkt = max(EL["wo"].kt // kdiv for EL in w.enc_layers)         # (compacted) hidden width in k-tiles
                 # every buffer of the pass is a view of ONE zero-filled allocation (one memset instead of nine), every small integer
                 # table one host array (one copy instead of 3 + B): the chain is ~80 launches, each of these was one more
                 nq_max = 3 * Hmax * HEAD_DIM

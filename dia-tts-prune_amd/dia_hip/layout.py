@@ -41,10 +41,35 @@ def tile_weight_planes(w2d: torch.Tensor) -> Tuple[torch.Tensor, int, int]:
     return torch.stack([t for t, _, _ in planes]).contiguous(), planes[0][1], planes[0][2]
 
 
+def tile_weight_bf16x2(w2d: torch.Tensor) -> Tuple[torch.Tensor, int, int]:
+    """[K, N] fp32 -> (bf16 tiles [N/16, 2*K/32, 64, 8], 2*K/32, N/16): the hi = bf16(w) and lo = bf16(w - hi) planes of the weights
+    (|hi + lo - w| <= 2^-17 |w|), INTERLEAVED per k-tile inside each strip — weight k-tile j is plane j & 1 of activation k-tile
+    j >> 1, so a strip stays one sequential stream and a split-K range over the doubled k-tiles holds both planes of its K
+    range — dia_gemm_args.w_planes = 2."""
+    hi, lo = split2(w2d.float())
+    th, kt, ns = tile_weight(hi.float())
+    tl, _, _ = tile_weight(lo.float())
+    return torch.stack([th, tl], dim=2).reshape(ns, 2 * kt, 64, 8).contiguous(), 2 * kt, ns
+
+
+def untile_weight_bf16x2(tiles: torch.Tensor, K: int, N: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """inverse of tile_weight_bf16x2: the (hi, lo) planes as fp32 [K, N] (their sum approximates w)"""
+    ns, kt2 = tiles.shape[0], tiles.shape[1]
+    t = tiles.reshape(ns, kt2 // 2, 2, 64, 8)
+    return untile_weight(t[:, :, 0], K, N), untile_weight(t[:, :, 1], K, N)
+
+
 def untile_weight(tiles: torch.Tensor, K: int, N: int) -> torch.Tensor:
     ns, kt = tiles.shape[0], tiles.shape[1]
     w = tiles.float().reshape(ns, kt, 4, 16, 8).permute(1, 2, 4, 0, 3).reshape(kt * 32, ns * 16)
     return w[:K, :N].contiguous()
+
+
+def split2(x: torch.Tensor):
+    """fp32 -> (hi, lo) bf16 with hi = bf16(x), lo = bf16(x - hi): 16 significand bits, relative error <= 2^-17"""
+    hi = x.to(torch.bfloat16)
+    lo = (x - hi.float()).to(torch.bfloat16)
+    return hi, lo
 
 
 def split3(x: torch.Tensor):

@@ -45,7 +45,8 @@ def _default_device() -> torch.device:
 
 class Dia:
     # what compute_dtype="float32" does with a checkpoint that bf16 cannot hold: "exact" = three bf16 planes per weight
-    # (the reference's fp32 path, ~3x slower), "round" = one rounded bf16 tile set (fast; the load prints a warning)
+    # (the reference's fp32 path, ~3x slower), "bf16x2" = hi + lo bf16 planes (relative error <= 2^-17, 2x the weight
+    # traffic, the tuned decode kernels), "round" = one rounded bf16 tile set (fast; the load prints a warning)
     fp32_weights = "exact"
 
     def __init__(self, config: DiaConfig, compute_dtype: Union[str, ComputeDtype] = ComputeDtype.FLOAT32,
@@ -100,6 +101,13 @@ class Dia:
                     self.weights_rounded, self.weights_exact_planes = False, True
                     print(f"Note: checkpoint weights are not bf16-representable (largest relative rounding {rounding:.2e}): "
                           f"compute_dtype='float32' keeps them exact as three bf16 planes (3x the weight traffic, generic kernel).")
+                elif self.fp32_weights == "bf16x2":
+                    rounding = self.model.max_weight_rounding
+                    self.model = DeviceWeights(self.config, sd, self.device, weight_planes=2)
+                    self.weights_rounded = False
+                    print(f"Note: checkpoint weights are not bf16-representable (largest relative rounding {rounding:.2e}): "
+                          f"fp32_weights='bf16x2' keeps them as hi + lo bf16 planes (relative error <= 2^-17, 2x the weight traffic, "
+                          f"tuned kernels).")
                 else:
                     print(f"Warning: checkpoint weights are not bf16-representable (largest relative rounding "
                           f"{self.model.max_weight_rounding:.2e}); they are streamed as bf16, so compute_dtype='float32' here means "

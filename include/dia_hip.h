@@ -19,7 +19,7 @@
 extern "C" {
 #endif
 
-#define DIA_ABI_VERSION 6
+#define DIA_ABI_VERSION 7
 
 #define DIA_OK 0
 #define DIA_E_ARG (-1)     /* bad argument / unsupported shape */
@@ -138,7 +138,13 @@ typedef struct {
   /* 0 / 1: W holds one bf16 tile set (exact for bf16-representable checkpoints).  3: W holds THREE tile sets back to back, the
    * hi / mid / lo bf16 planes of fp32 weights (hi + mid + lo == w exactly; plane stride = KT * nstrips * 512 elements): the
    * products of a genuine fp32 checkpoint, exact like the activations' — through the generic kernel only (no split-K, no
-   * persistent forms): the parity configuration for checkpoints that bf16 cannot hold, not a fast path. */
+   * persistent forms): the parity configuration for checkpoints that bf16 cannot hold, not a fast path.
+   * 2: W holds the hi = bf16(w) and lo = bf16(w - hi) planes of fp32 weights (16 significand bits, relative error <= 2^-17),
+   * INTERLEAVED per k-tile inside one tile set (dia_hip/layout.py tile_weight_bf16x2): weight k-tile j of a strip is plane j & 1
+   * of activation k-tile j >> 1, so KT counts hi and lo tiles (KT == 2 * K/32, a_ktiles >= KT/2) and every strip is one
+   * sequential stream of twice the bytes.  The decode step's shapes (fp32 tiles in and out, 128 weight k-tiles per workgroup,
+   * i.e. K = 2048 or split-K slices of it) run the tuned M <= 4 GEMV and 5..128-row kernels; every other shape the generic one.
+   * Not with w_layout = 1 or the sparse stream. */
   int32_t w_planes;
   int64_t kv_plane_stride;  /* CROSSKV with kv_dtype DIA_KV_BF16X2: elements between the hi and the lo plane of kc / vc */
   int32_t w_layout;         /* 0: 16-column strips (above); 1: diagonal tiles of 4-column groups (dia_hip/layout.py diag_tile_weight): W = bf16
@@ -429,7 +435,8 @@ typedef struct {
   int32_t* mlp_barrier;     /* 2 int32 zeroed by the caller once: dia_mlp_fused's barrier words (NULL = never fuse) */
   int32_t act_f32;          /* 1: planes_x / planes_a / planes_h carry fp32 activation tiles (dia_gemm_args.act_f32); needs
                              * sample.embed.act_f32 == 1 */
-  int32_t w_planes;         /* 0 / 1, or 3: every weight pointer holds three bf16 planes of fp32 weights (dia_gemm_args.w_planes) */
+  int32_t w_planes;         /* 0 / 1, 2: every weight pointer holds interleaved hi / lo bf16 planes of fp32 weights and every kt_* counts
+                             * both (2 * K/32), or 3: three bf16 planes back to back (dia_gemm_args.w_planes) */
   dia_sample_args sample;   /* sampler + FSM + embedding parameters */
   /* persistent MLP segments (NULL / 0 = the eight-launch layer): host array [n_layer] of ring arenas (layer l's arena holds
    * co, wi, wo of layer l and, for l + 1 < n_layer, qkv of layer l + 1), used when 2B <= 4 */
