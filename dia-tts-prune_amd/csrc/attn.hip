@@ -906,8 +906,6 @@ extern "C" int dia_dbg_astamps(long long* host, int n) {
 }
 #endif
 
-int dia_attn_init() { return DIA_OK; }   // static LDS only since the split-key rewrite
-
 extern "C" int dia_attn_scratch_floats(int n_rows, int n_kv_heads, int kv_cap) {
   const long chunks = (kv_cap + CHUNK - 1) / CHUNK;
   const long n = (long)n_rows * n_kv_heads * chunks * SLAB;

@@ -51,17 +51,6 @@ static inline void mark(dia_engine* e, int i) {
   }
 }
 
-int dia_kernels_init_once() {
-  static int rc = -100;
-  if (rc == -100) {
-    dia_tuning_init_from_env();
-    rc = dia_attn_init();
-    if (rc == DIA_OK) rc = dia_sample_init();
-    if (rc == DIA_OK) rc = dia_gemm_init();
-  }
-  return rc;
-}
-
 static int enqueue_step(dia_engine* e, bool with_sampler) {
   const dia_engine_desc& d = e->d;
   void* st = (void*)e->stream;
@@ -269,8 +258,6 @@ extern "C" int dia_engine_create(const dia_engine_desc* d, void* stream, dia_eng
   if (!d->x || !d->planes_x || !d->planes_a || !d->planes_h || !d->ssq || !d->qkv || !d->qc || !d->logits || !d->cos_t ||
       !d->sin_t || !d->text_len || !d->w_logits || !d->g_final || !d->attn_scratch || !d->attn_tickets)
     return dia_fail(DIA_E_ARG, "dia_engine_create: missing buffer");
-  int rc = dia_kernels_init_once();
-  if (rc) return rc;
   dia_engine* e = new dia_engine();
   e->d = *d;
   e->layers.assign(d->layers, d->layers + d->n_layer);

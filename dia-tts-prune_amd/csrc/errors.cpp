@@ -7,6 +7,7 @@
 #include <vector>
 
 static thread_local std::string g_err;
+static thread_local hipError_t g_lds_err = hipSuccess;      // a launch skipped by dia_launch, not yet reported
 
 int dia_fail(int code, const char* msg) {
   g_err = msg ? msg : "";
@@ -18,8 +19,15 @@ int dia_fail_hip(hipError_t e, const char* where) {
   return DIA_E_HIP;
 }
 
+void dia_note_lds_raise_failed(hipError_t e) { g_lds_err = e; }
+
 int dia_check_launch(const char* kernel) {
   hipError_t e = hipGetLastError();
+  if (g_lds_err != hipSuccess) {
+    e = g_lds_err;
+    g_lds_err = hipSuccess;
+    return dia_fail_hip(e, (std::string("hipFuncSetAttribute(") + (kernel ? kernel : "kernel") + ")").c_str());
+  }
   if (e == hipSuccess) return DIA_OK;
   return dia_fail_hip(e, kernel);
 }

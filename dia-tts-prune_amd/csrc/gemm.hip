@@ -1762,8 +1762,6 @@ int launch_tile_ws(const GemmK& k, hipStream_t st) {
 
 
 int launch_tile(const GemmK& k, hipStream_t st) {
-  int rc = dia_kernels_init_once();
-  if (rc) return rc;
   // the wave-specialised form (8 consumer + 4 producer waves): wi 113 us, wo 79, qkv 52, o 29 at 1696 rows, against
   // 137 / 97 / 61 / 34 for the plain 8-wave form and 192 / 86 / 79 / 30 for 4-wave 64 x 128 blocks (those two live in
   // gemm_experiments.hip, tuning knob tile_v = 0 / 1 / 2)
@@ -1773,26 +1771,43 @@ int launch_tile(const GemmK& k, hipStream_t st) {
   return launch_tile_ws<2, 2, 4>(k, st);
 }
 
+// z-forms (k_gemm16 over gridDim.z, k_gemm2t): strips per workgroup such that about `budget` workgroups cover the strips
+// times mz m-tile groups times sk K slices, the workgroups along x a multiple of 8
+int z_spw(int nstrips, int budget, int mz, int sk) {
+  int per = budget / mz / sk;
+  per = per >= 8 ? per / 8 * 8 : (per > 0 ? per : 1);
+  return (nstrips + per - 1) / per;
+}
+
+// z-forms: gx rounded up to a multiple of 8 while the strips still fill it, so that the workgroups of one strip group
+// (one per m-tile) share an XCD.  k_gemm16 tests gx * sk, k_gemm2t gx alone (mult = 1).
+int xcd_round(int gx, int mult, int nstrips) {
+  return (gx * mult) % 8 != 0 && (gx + 7) / 8 * 8 <= nstrips ? (gx + 7) / 8 * 8 : gx;
+}
+
+// strips per workgroup of the persistent forms (k_gemv_small, k_gemm16): the caller's spw, else 4 from 1024 strips on
+// (next strip's loads overlap this strip's reduce + epilogue).  One m-tile, no split-K, more than `spread` but fewer than
+// 1024 strips: about 256 workgroups instead of a short last round (logits, 579 strips: 16.1 -> 10.9 us at 16 rows).
+// mz >= 2 m-tiles: about 256 workgroups in all (one per CU, both halves of every pair resident together).  The gemm_spw
+// knob overrides all of it.
+int pick_spw(const GemmK& k, int spread, int mz, int sk) {
+  int spw = k.spw > 0 ? k.spw : (k.nstrips >= 1024 ? 4 : 1);
+  if (k.spw <= 0 && mz == 1 && sk == 1 && k.nstrips > spread && k.nstrips < 1024) spw = (k.nstrips + 255) / 256;
+  if (k.spw <= 0 && mz >= 2) spw = z_spw(k.nstrips, 256, mz, sk);
+  if (dia_tune(DIA_TUNE_GEMM_SPW) > 0) spw = dia_tune(DIA_TUNE_GEMM_SPW);
+  return spw;
+}
+
 template <int NW, int KPW, bool AF32 = false, bool PF32 = false>
 int launch_g16(const GemmK& k, hipStream_t st) {
   const size_t smem = g16_smem(NW);
   const int sk = k.KT / (NW * KPW);
-  int spw = k.spw > 0 ? k.spw : (k.nstrips >= 1024 ? 4 : 1);
   const int mz = k.mz > 1 ? k.mz : 1;
-  // between one and four rounds of workgroups: walk the strips with about one workgroup per CU instead (logits, 579
-  // strips at 16 rows: 16.1 -> 10.9 us with three strips per workgroup)
-  if (mz == 1 && k.spw <= 0 && sk == 1 && k.nstrips > 256 && k.nstrips < 1024) spw = (k.nstrips + 255) / 256;
-  // two m-tiles: about 256 workgroups in all (one per CU, both halves of every pair resident together)
-  if (mz >= 2 && k.spw <= 0) {
-    int per = 256 / mz / sk;
-    per = per >= 8 ? per / 8 * 8 : (per > 0 ? per : 1);
-    spw = (k.nstrips + per - 1) / per;
-  }
-  if (dia_tune(DIA_TUNE_GEMM_SPW) > 0) spw = dia_tune(DIA_TUNE_GEMM_SPW);
+  const int spw = pick_spw(k, 256, mz, sk);
   if constexpr (!(NW == 16 && KPW >= 4)) {
     if (spw > 1) {      // persistent multi-strip form, with or without split-K: A fragments loaded once per workgroup
       int gx = (k.nstrips + spw - 1) / spw;
-      if (mz >= 2 && (gx * sk) % 8 != 0 && (gx + 7) / 8 * 8 <= k.nstrips) gx = (gx + 7) / 8 * 8;   // pairs on one XCD
+      if (mz >= 2) gx = xcd_round(gx, sk, k.nstrips);
       if constexpr (NW == 8 && (KPW == 8 || KPW == 4)) {
         if (mz > 1 && sk == 1 && k.epi != DIA_EPI_CROSSKV && dia_tune(DIA_TUNE_GEMM_ZR) != 0) {       // mid / lo planes of A in LDS: room for the element-per-thread tail
           // (not with split-K: wo at 128 rows 59.9 vs 56.0 us — its hand-off drains the stream either way, the 32-thread tail is shorter there)
@@ -1896,6 +1911,14 @@ int launch_nw(const GemmK& k, int nw, int mgroups, hipStream_t st) {
   }
 }
 
+// the generic kernel (any shape): one, two or four m-tiles per workgroup
+int launch_generic(const GemmK& k, int nw, hipStream_t st) {
+  const int mtiles = (k.M + 15) / 16;
+  if (mtiles == 1) return launch_nw<1>(k, nw, 1, st);
+  if (mtiles == 2) return launch_nw<2>(k, nw, 1, st);
+  return launch_nw<4>(k, nw, (mtiles + 3) / 4, st);
+}
+
 size_t small_smem(int nw, int KT, int rs) {     // KT = k-tiles one workgroup stages (its own K range)
   return sizeof(f32x4) * nw * 64 + sizeof(float) * (16 * 17 + 16) + (size_t)DIA_NPLANES * KT * 4 * rs * 16;
 }
@@ -1903,18 +1926,9 @@ size_t small_smem(int nw, int KT, int rs) {     // KT = k-tiles one workgroup st
 template <int NW, int KPW, int RS, bool F32 = false>
 int launch_small(const GemmK& k, hipStream_t st) {
   size_t smem = small_smem(NW, NW * KPW, RS);
-  if (smem > 64 * 1024) {
-    int rc = dia_kernels_init_once();     // raises the dynamic-LDS limit of every large-LDS kernel, once
-    if (rc) return rc;
-  }
-  // strips per workgroup: enough workgroups to cover every CU, few enough that each streams several
-  // strips back to back (next strip's loads overlap this strip's reduce + epilogue)
-  int spw = k.spw > 0 ? k.spw : (k.nstrips >= 1024 ? 4 : 1);
   const int sk = k.KT / (NW * KPW);          // cross-workgroup split-K factor (1 = none)
-  // between one and two rounds of resident workgroups (logits head: 579 strips, two 8-wave workgroups per CU): walk the
-  // strips with about 256 persistent workgroups instead of leaving a short second round
-  if (k.spw <= 0 && sk == 1 && k.nstrips > 512 && k.nstrips < 1024) spw = (k.nstrips + 255) / 256;
-  if (dia_tune(DIA_TUNE_GEMM_SPW) > 0) spw = dia_tune(DIA_TUNE_GEMM_SPW);
+  // (two 8-wave workgroups per CU: the spread to about 256 workgroups starts above 512 strips)
+  const int spw = pick_spw(k, 512, 1, sk);
   const int grid = (k.nstrips + spw - 1) / spw;
   if (sk > 1) {
     launch_small_kernel<k_gemv_small<NW, KPW, RS, false, F32, F32>>(dim3(k.nstrips, sk), dim3(NW * 64), smem, st, k);
@@ -1974,9 +1988,7 @@ int launch_small_w2(const GemmK& k, int sk, hipStream_t st) {
     launch_small_kernel<k_gemv_small<8, 16, RS, false, true, true, true>>(dim3(k.nstrips, sk), dim3(512), smem, st, k);
     return dia_check_launch("k_gemv_small");
   }
-  int spw = k.spw > 0 ? k.spw : (k.nstrips >= 1024 ? 4 : 1);          // as launch_small
-  if (k.spw <= 0 && k.nstrips > 512 && k.nstrips < 1024) spw = (k.nstrips + 255) / 256;
-  if (dia_tune(DIA_TUNE_GEMM_SPW) > 0) spw = dia_tune(DIA_TUNE_GEMM_SPW);
+  const int spw = pick_spw(k, 512, 1, 1);          // as launch_small
   if (spw > 1) launch_small_kernel<k_gemv_small<8, 16, RS, true, true, true, true>>(dim3((k.nstrips + spw - 1) / spw), dim3(512), smem, st, k);
   else launch_small_kernel<k_gemv_small<8, 16, RS, false, true, true, true>>(dim3(k.nstrips), dim3(512), smem, st, k);
   return dia_check_launch("k_gemv_small");
@@ -1985,43 +1997,13 @@ int launch_small_w2(const GemmK& k, int sk, hipStream_t st) {
 // 5..128 rows: the persistent k_gemm16 with the mid / lo planes of A in LDS (ALDS) — the hi plane (32 VGPRs) and two weight strips in
 // flight (128 VGPRs) stay in registers.  mz >= 2: the z-form over the m-tiles, split-K or not.
 int launch_g16_w2(const GemmK& k, int mz, int sk, hipStream_t st) {
-  int rc = dia_kernels_init_once();       // 148 KiB of LDS: the raised dynamic-LDS limit
-  if (rc) return rc;
   const size_t smem = g16_smem(8) + g16_alds(8, W2_KTW / 16);
-  int spw = k.spw > 0 ? k.spw : (k.nstrips >= 1024 ? 4 : 1);          // as launch_g16
-  if (mz == 1 && k.spw <= 0 && sk == 1 && k.nstrips > 256 && k.nstrips < 1024) spw = (k.nstrips + 255) / 256;
-  if (mz >= 2 && k.spw <= 0) {
-    int per = 256 / mz / sk;
-    per = per >= 8 ? per / 8 * 8 : (per > 0 ? per : 1);
-    spw = (k.nstrips + per - 1) / per;
-  }
-  if (dia_tune(DIA_TUNE_GEMM_SPW) > 0) spw = dia_tune(DIA_TUNE_GEMM_SPW);
+  const int spw = pick_spw(k, 256, mz, sk);          // as launch_g16
   int gx = (k.nstrips + spw - 1) / spw;
-  if (mz >= 2 && (gx * sk) % 8 != 0 && (gx + 7) / 8 * 8 <= k.nstrips) gx = (gx + 7) / 8 * 8;   // pairs on one XCD
+  if (mz >= 2) gx = xcd_round(gx, sk, k.nstrips);
   if (mz >= 2) launch_small_kernel<k_gemm16<8, 16, true, true, true, true, false, true, true>>(dim3(gx, sk, mz), dim3(512), smem, st, k);
   else launch_small_kernel<k_gemm16<8, 16, true, false, true, true, false, true, true>>(dim3(gx, sk), dim3(512), smem, st, k);
   return dia_check_launch("k_gemm16");
-}
-
-template <int NW, int KPW>
-int small_attr() {
-  hipError_t e[4];
-  e[0] = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemv_small<NW, KPW, 2, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024);
-  e[1] = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemv_small<NW, KPW, 4, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024);
-  e[2] = e[3] = hipSuccess;
-  if constexpr (KPW <= 16 && !(NW == 16 && KPW > 4)) {
-    e[2] = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemv_small<NW, KPW, 2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024);
-    e[3] = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemv_small<NW, KPW, 4, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024);
-  }
-  for (int i = 0; i < 4; ++i) if (e[i] != hipSuccess) return dia_fail_hip(e[i], "hipFuncSetAttribute(k_gemv_small)");
-  e[0] = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemv_small<NW, KPW, 2, false, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024);
-  e[1] = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemv_small<NW, KPW, 4, false, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024);
-  if constexpr (KPW <= 16 && !(NW == 16 && KPW > 4)) {
-    e[2] = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemv_small<NW, KPW, 2, true, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024);
-    e[3] = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemv_small<NW, KPW, 4, true, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024);
-  }
-  for (int i = 0; i < 4; ++i) if (e[i] != hipSuccess) return dia_fail_hip(e[i], "hipFuncSetAttribute(k_gemv_small, fp32 tiles)");
-  return DIA_OK;
 }
 
 }  // namespace
@@ -2031,44 +2013,6 @@ extern "C" int dia_dbg_stamps(long long* host, int n) {
   return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_stamps), sizeof(long long) * n) == hipSuccess ? 0 : -2;
 }
 #endif
-
-int dia_gemm_init() {
-  int rc = 0;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemv_diag<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024) != hipSuccess) rc = 1;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemv_diag<4>), hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024) != hipSuccess) rc = 1;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm2t<8, true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)g2t_smem(8)) != hipSuccess) rc = 1;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm2t<8, true, false, 8, false, DIA_EPI_SCALE_STORE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)g2t_smem(8)) != hipSuccess) rc = 1;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm2t<8, true, false, 8, false, DIA_EPI_RESID_EMIT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)g2t_smem(8)) != hipSuccess) rc = 1;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm2t<8, true, false, 8, false, DIA_EPI_SWIGLU_EMIT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)g2t_smem(8)) != hipSuccess) rc = 1;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm2t<8, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)g2t_smem(8)) != hipSuccess) rc = 1;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm2t<8, true, true, 8, false, -1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)g2t_smem(8, 8, true)) != hipSuccess) rc = 1;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm2t<8, false, true, 8, false, -1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)g2t_smem(8, 8, true)) != hipSuccess) rc = 1;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm2t<8, false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)g2t_smem(8)) != hipSuccess) rc = 1;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm2t<8, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)g2t_smem(8)) != hipSuccess) rc = 1;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm2t<4, false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)g2t_smem(4)) != hipSuccess) rc = 1;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm2t<8, false, false, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)g2t_smem(8, 4)) != hipSuccess) rc = 1;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm2t<8, false, false, 4, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)g2t_smem(8, 4)) != hipSuccess) rc = 1;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm2t<8, false, false, 4, false, DIA_EPI_SCALE_STORE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)g2t_smem(8, 4)) != hipSuccess) rc = 1;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm2t<8, false, false, 4, false, DIA_EPI_SWIGLU_EMIT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)g2t_smem(8, 4)) != hipSuccess) rc = 1;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm2t<8, false, false, 8, false, DIA_EPI_RESID_EMIT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)g2t_smem(8)) != hipSuccess) rc = 1;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm16<8, 8, true, true, true, true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(g16_smem(8) + g16_alds(8, 8))) != hipSuccess) rc = 1;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm16<8, 8, true, false, true, true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(g16_smem(8) + g16_alds(8, 8))) != hipSuccess) rc = 1;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm16<8, 8, true, true, false, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(g16_smem(8) + g16_alds(8, 8))) != hipSuccess) rc = 1;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm16<8, 4, true, true, true, true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(g16_smem(8) + g16_alds(8, 4))) != hipSuccess) rc = 1;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm16<8, 4, true, true, false, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(g16_smem(8) + g16_alds(8, 4))) != hipSuccess) rc = 1;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm16<8, 16, true, true, true, true, false, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(g16_smem(8) + g16_alds(8, W2_KTW / 16))) != hipSuccess) rc = 1;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm16<8, 16, true, false, true, true, false, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(g16_smem(8) + g16_alds(8, W2_KTW / 16))) != hipSuccess) rc = 1;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm_tile_ws<2, 2, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)gt_smem(2, 8)) != hipSuccess) rc = 1;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm_tile_ws<2, 2, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)gt_smem(2, 8)) != hipSuccess) rc = 1;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm_tile_ws<2, 4, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)gt_smem(2, 8)) != hipSuccess) rc = 1;
-  rc |= small_attr<4, 4>(); rc |= small_attr<4, 8>(); rc |= small_attr<4, 16>();
-  rc |= small_attr<8, 2>(); rc |= small_attr<8, 3>(); rc |= small_attr<8, 4>(); rc |= small_attr<8, 5>(); rc |= small_attr<8, 6>(); rc |= small_attr<8, 7>(); rc |= small_attr<8, 8>(); rc |= small_attr<8, 10>(); rc |= small_attr<8, 12>(); rc |= small_attr<8, 14>(); rc |= small_attr<8, 16>(); rc |= small_attr<8, 32>();
-  rc |= small_attr<16, 1>(); rc |= small_attr<16, 2>(); rc |= small_attr<16, 4>(); rc |= small_attr<16, 8>();
-#ifdef DIA_EXPERIMENTS
-  rc |= dia_exp_init();
-#endif
-  return rc ? DIA_E_HIP : DIA_OK;
-}
 
 extern "C" int dia_has_experiments(void) {
 #ifdef DIA_EXPERIMENTS
@@ -2085,25 +2029,31 @@ extern "C" int dia_has_experiments(void) {
 // Prefill (hundreds of packed rows): k_gemm_tile_ws (MFMA-bound).  Everything else: k_gemm (any shape).
 // Two-plane weights (w_planes == 2): gemm_w2 below.
 namespace {
-int gemm_w2(const dia_gemm_args* a, GemmK& k, hipStream_t st) {
+// cross-workgroup split-K factor (1 = none), or DIA_E_ARG when the caller's scratch, tickets or K do not allow it
+int split_k(const dia_gemm_args* a) {
   const int sk = a->sk > 1 ? a->sk : 1;
   if (sk > 1 && (!a->sk_scratch || !a->sk_tickets || a->KT % sk != 0)) return dia_fail(DIA_E_ARG, "dia_gemm: split-K needs sk_scratch, sk_tickets and KT % sk == 0");
+  return sk;
+}
+
+// highest m-tile count the z-forms serve (knob gemm_mz_max, 0 = off)
+int gemm_mz_max() { return dia_tune(DIA_TUNE_GEMM_MZ_MAX) >= 0 ? dia_tune(DIA_TUNE_GEMM_MZ_MAX) : 8; }
+
+int gemm_w2(const dia_gemm_args* a, GemmK& k, hipStream_t st) {
+  const int sk = split_k(a);
+  if (sk < 0) return sk;
   const int mtiles = (a->M + 15) / 16;
   const bool fast_epi = a->epi != DIA_EPI_CROSSKV && !(a->epi == DIA_EPI_RESID_EMIT && !a->gnext);
   const bool emits = a->epi == DIA_EPI_RESID_EMIT || a->epi == DIA_EPI_SWIGLU_EMIT;
   const bool uni_f32 = k.a_f32 && (!emits || k.p_f32);             // the decode step's format: fp32 tiles in and out
-  const int mz_max = dia_tune(DIA_TUNE_GEMM_MZ_MAX) >= 0 ? dia_tune(DIA_TUNE_GEMM_MZ_MAX) : 8;
   if (uni_f32 && fast_epi && a->KT % sk == 0 && a->KT / sk == W2_KTW && (a->nw == 0 || a->nw == 8)) {
     if (a->M <= 4) return a->M <= 2 ? launch_small_w2<2>(k, sk, st) : launch_small_w2<4>(k, sk, st);
     if (mtiles == 1) return launch_g16_w2(k, 1, sk, st);
-    if (mtiles <= mz_max && (sk == 1 || a->sk_scratch_floats >= (int64_t)mtiles * a->nstrips * sk * 256)) return launch_g16_w2(k, mtiles, sk, st);
+    if (mtiles <= gemm_mz_max() && (sk == 1 || a->sk_scratch_floats >= (int64_t)mtiles * a->nstrips * sk * 256)) return launch_g16_w2(k, mtiles, sk, st);
   }
   if (sk > 1) return dia_fail(DIA_E_ARG, "dia_gemm: two-plane weights: no split-K kernel for this shape");
   // every other shape (encoder, cross-K/V, planes or mixed activation formats, compacted K): the generic kernel
-  const int nw = (a->KT % 8 == 0) ? 8 : 4;
-  if (mtiles == 1) return launch_nw<1>(k, nw, 1, st);
-  if (mtiles == 2) return launch_nw<2>(k, nw, 1, st);
-  return launch_nw<4>(k, nw, (mtiles + 3) / 4, st);
+  return launch_generic(k, (a->KT % 8 == 0) ? 8 : 4, st);
 }
 }  // namespace
 
@@ -2159,12 +2109,7 @@ extern "C" int dia_gemm(const dia_gemm_args* a, void* stream) {
   if (a->w_planes == 2) return gemm_w2(a, k, (hipStream_t)stream);
   if (a->w_planes > 1) {      // fp32 weights as three planes: the generic kernel, whatever the shape (exactness, not speed)
     if (a->w_planes != 3) return dia_fail(DIA_E_ARG, "dia_gemm: w_planes must be 0, 1, 2 or 3");
-    const int mt_ = (a->M + 15) / 16;
-    const int nw_ = (a->KT % 8 == 0) ? 8 : 4;
-    hipStream_t st_ = (hipStream_t)stream;
-    if (mt_ == 1) return launch_nw<1>(k, nw_, 1, st_);
-    if (mt_ == 2) return launch_nw<2>(k, nw_, 1, st_);
-    return launch_nw<4>(k, nw_, (mt_ + 3) / 4, st_);
+    return launch_generic(k, (a->KT % 8 == 0) ? 8 : 4, (hipStream_t)stream);
   }
   const bool fast_epi = a->epi != DIA_EPI_CROSSKV && !(a->epi == DIA_EPI_RESID_EMIT && !a->gnext);
   int nw = a->nw;
@@ -2183,8 +2128,8 @@ extern "C" int dia_gemm(const dia_gemm_args* a, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   // cross-workgroup split-K (a->sk > 1): sk workgroups per strip, each 1/sk of K, combined by the last arriver.
   // The engine uses it for wo (K = 8192 over 128 strips): 2 at M <= 4, 4 at 5..16 rows and per m-tile above.
-  const int sk = a->sk > 1 ? a->sk : 1;
-  if (sk > 1 && (!a->sk_scratch || !a->sk_tickets || a->KT % sk != 0)) return dia_fail(DIA_E_ARG, "dia_gemm: split-K needs sk_scratch, sk_tickets and KT % sk == 0");
+  const int sk = split_k(a);
+  if (sk < 0) return sk;
   // (M <= 4: sixteen waves x 8 k-tiles beat eight x 16 on wo, 9.4 vs 10.0 us with the fp32 image — half the loads per wave in
   // flight before its first MFMA.  The same wave count for both activation formats: their results stay identical bit for bit)
   if (sk > 1 && !a->nw) { const int ktl = a->KT / sk; nw = (ktl % 16 == 0 && ktl / 16 <= (a->M <= 4 ? 8 : 4)) ? 16 : ((ktl % 8 == 0) ? 8 : 4); }
@@ -2212,7 +2157,7 @@ extern "C" int dia_gemm(const dia_gemm_args* a, void* stream) {
   // 17..128 rows: the one-m-tile kernel over all m-tiles at once (gridDim.z = 2..8, the workgroups of a group share their
   // weight stream through L2).  Split-K (a->sk > 1) needs scratch for every m-tile: mtiles * nstrips * sk * 256 floats,
   // mtiles * nstrips tickets.
-  const int mz_max = dia_tune(DIA_TUNE_GEMM_MZ_MAX) >= 0 ? dia_tune(DIA_TUNE_GEMM_MZ_MAX) : 8;
+  const int mz_max = gemm_mz_max();
   // (the z-form's 32-thread tail runs the shared epilogue: the cross-K/V projections of a short prompt ride it too — the generic
   // kernel they fell to spills and took 21-25 us per launch at 98 rows)
   // two m-tiles per workgroup (k_gemm2t).  Decode (fp32 tiles on both sides, dense K = 2048 shapes): where a workgroup walks many strips —
@@ -2233,11 +2178,8 @@ extern "C" int dia_gemm(const dia_gemm_args* a, void* stream) {
       const bool half = !f32io && ktw == 32 && dia_tune(DIA_TUNE_GEMM_2T) != 3;     // K = 1024: 256-thread workgroups, two per CU (knob 3: the 512-thread form)
       int budget = half ? 512 : 256;
       if (!f32io && dia_tune(DIA_TUNE_G2T_WGS) > 0) budget = dia_tune(DIA_TUNE_G2T_WGS);
-      int per = budget / zp / sk;
-      per = per >= 8 ? per / 8 * 8 : (per > 0 ? per : 1);
-      const int spw_ = (a->nstrips + per - 1) / per;                                              // strips per workgroup
-      int gx = (a->nstrips + spw_ - 1) / spw_;
-      if (gx % 8 != 0 && (gx + 7) / 8 * 8 <= a->nstrips) gx = (gx + 7) / 8 * 8;                   // the pairs of one strip group on one XCD
+      const int spw_ = z_spw(a->nstrips, budget, zp, sk);                                         // strips per workgroup
+      const int gx = xcd_round((a->nstrips + spw_ - 1) / spw_, 1, a->nstrips);
       const dim3 grid(gx, sk, zp), blk(half ? 256 : 512);
       // planes with a compile-time epilogue and the all-thread tail: dense shapes only (no compaction maps), knob 5 = the shared tail (A/B)
       const bool puni = !f32io && !a->cmap && !a->strip_map && (a->epi != DIA_EPI_RESID_EMIT || a->gnext) && dia_tune(DIA_TUNE_GEMM_2T) != 5;
@@ -2299,9 +2241,7 @@ extern "C" int dia_gemm(const dia_gemm_args* a, void* stream) {
       return launch_tile(k, st);
     }
   }
-  if (mtiles == 1) return launch_nw<1>(k, nw, 1, st);
-  if (mtiles == 2) return launch_nw<2>(k, nw, 1, st);
-  return launch_nw<4>(k, nw, (mtiles + 3) / 4, st);
+  return launch_generic(k, nw, st);
 }
 
 extern "C" int dia_gemm_timed(const dia_gemm_args* a, void* stream, float* ms_out) {

@@ -381,8 +381,6 @@ template <int KPW, int RS>
 int launch_sparse(const GemmK& k, hipStream_t st) {
   constexpr int MAXS = 8;
   const size_t smem = sizeof(f32x4) * 16 * 64 + sizeof(float) * (16 * 17 + 16) + (size_t)DIA_NPLANES * (16 * KPW) * 4 * RS * 16 + (size_t)16 * KPW * 1024;
-  int rc = dia_kernels_init_once();
-  if (rc) return rc;
   int grid = (k.nstrips + MAXS - 1) / MAXS;
   if (grid < 256 && k.nstrips >= 256) grid = 256;
   if (grid > k.nstrips) grid = k.nstrips;
@@ -915,24 +913,8 @@ int launch_tile_v(const GemmK& k, hipStream_t st) {
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------------
-// host glue (called by dia_gemm / dia_gemm_init in gemm.hip when built with DIA_EXPERIMENTS)
+// host glue (called by dia_gemm in gemm.hip when built with DIA_EXPERIMENTS)
 // ---------------------------------------------------------------------------------------------------
-template <int KPW, int RS>
-static int sparse_attr() {
-  const size_t smem = sizeof(f32x4) * 16 * 64 + sizeof(float) * (16 * 17 + 16) + (size_t)DIA_NPLANES * (16 * KPW) * 4 * RS * 16 + (size_t)16 * KPW * 1024;
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemv_sparse<KPW, RS, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess;
-}
-
-int dia_exp_init() {
-  int rc = 0;
-  rc |= sparse_attr<4, 2>(); rc |= sparse_attr<4, 4>(); rc |= sparse_attr<2, 2>(); rc |= sparse_attr<2, 4>(); rc |= sparse_attr<1, 2>(); rc |= sparse_attr<1, 4>();
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_mlp_fused<4, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)mlp_smem(64, 128)) != hipSuccess) rc = 1;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_mlp_fused<1, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)mlp_smem(16, 16)) != hipSuccess) rc = 1;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm_tile<2, 4, 2, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)gt_smem(2, 8)) != hipSuccess) rc = 1;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm_tile<2, 4, 1, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)gt_smem(2, 4)) != hipSuccess) rc = 1;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm_tile<2, 2, 1, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)gt_smem(2, 4)) != hipSuccess) rc = 1;
-  return rc;
-}
 
 // zero-skipping stream: M <= 4, K = 16 * {1, 2, 4} k-tiles, no split-K
 int dia_exp_gemm_sparse(const dia_gemm_args* a, void* stream) {
@@ -991,8 +973,6 @@ int dia_exp_gemm_two_mtiles(const dia_gemm_args* a, void* stream, bool& handled)
 
 // prefill tile kernel without wave specialisation: 0 = 8 waves 64 x 256, 1 / 2 = 4 waves 64 x 128 (PD 4 / 2)
 int dia_exp_tile_variant(const dia_gemm_args* a, void* stream, int v) {
-  int rc = dia_kernels_init_once();
-  if (rc) return rc;
   GemmK k;
   fill_gemmk(a, k);
   hipStream_t st = (hipStream_t)stream;
@@ -1015,10 +995,8 @@ extern "C" int dia_mlp_fused(const dia_gemm_args* wi, const dia_gemm_args* wo, i
   if (!n_cu) { int dev = 0; if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n_cu = -1; }
   if (n_cu < G) return dia_fail(DIA_E_ARG, "dia_mlp_fused: the grid barrier needs every workgroup resident (2 * wo strips <= CUs)");
   if (wi->nstrips % G != 0 && wi->nstrips < G) return dia_fail(DIA_E_ARG, "dia_mlp_fused: too few wi strips");
-  int rc = dia_kernels_init_once();
-  if (rc) return rc;
   MlpK q;
-  rc = fill_gemmk(wi, q.wi); if (rc) return rc;
+  int rc = fill_gemmk(wi, q.wi); if (rc) return rc;
   rc = fill_gemmk(wo, q.wo); if (rc) return rc;
   q.bar = barrier;
   const int kpw1 = wi->KT / 16, kpw2 = wo->KT / 32;

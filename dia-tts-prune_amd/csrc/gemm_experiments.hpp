@@ -9,5 +9,4 @@ namespace { struct GemmK; }
 int dia_exp_gemm_sparse(const dia_gemm_args* a, void* stream);
 int dia_exp_gemm_two_mtiles(const dia_gemm_args* a, void* stream, bool& handled);
 int dia_exp_tile_variant(const dia_gemm_args* a, void* stream, int variant);
-int dia_exp_init();
 #endif

@@ -569,12 +569,6 @@ extern "C" int dia_dbg_sstamps(long long* host) {
 }
 #endif
 
-int dia_sample_init() {
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_sample), hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024);
-  if (e != hipSuccess) return dia_fail_hip(e, "hipFuncSetAttribute(k_sample)");
-  return DIA_OK;
-}
-
 extern "C" int dia_sample(const dia_sample_args* a, void* stream) {
   if (!a || !a->logits || !a->tokens || !a->pred || !a->cur || !a->fsm || !a->delay) return dia_fail(DIA_E_ARG, "dia_sample: null argument");
   if (a->V > VCAP || a->C > MAXC || a->C <= 0 || a->B <= 0) return dia_fail(DIA_E_ARG, "dia_sample: vocabulary > 1088 or channels > 16");
@@ -592,10 +586,6 @@ extern "C" int dia_sample(const dia_sample_args* a, void* stream) {
   int rc = fill_embed(&ea, k.e);
   if (rc) return rc;
   const size_t smem = (size_t)a->C * (3 * VCAP) * sizeof(float);
-  if (smem > 64 * 1024) {
-    rc = dia_kernels_init_once();
-    if (rc) return rc;
-  }
   dia_launch<k_sample>(dim3(a->B), dim3(a->C * 64), smem, (hipStream_t)stream, k);
   return dia_check_launch("k_sample");
 }

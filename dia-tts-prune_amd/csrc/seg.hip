@@ -420,17 +420,6 @@ __global__ __launch_bounds__(SG_NT) void k_seg_mlp(SegK p) {
 
 }  // namespace
 
-static bool g_seg_ready = false;
-static int seg_init() {
-  if (g_seg_ready) return DIA_OK;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_seg_mlp<3>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SG_LDS_BYTES);
-  if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_seg_mlp<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SG_LDS_BYTES);
-  if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_seg_mlp<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SG_LDS_BYTES);
-  if (e != hipSuccess) return dia_fail_hip(e, "hipFuncSetAttribute(k_seg_mlp)");
-  g_seg_ready = true;
-  return DIA_OK;
-}
-
 extern "C" int64_t dia_seg_workspace_bytes(void) { return (int64_t)SG_WS_BYTES; }
 extern "C" int64_t dia_seg_workspace_control_bytes(void) { return (int64_t)SG_CTRL_BYTES; }
 extern "C" int32_t dia_seg_slots(int with_qkv) { return with_qkv ? SG_SLOTS_FULL : SG_FIRST_QKV; }
@@ -460,8 +449,6 @@ extern "C" int dia_seg_mlp(const dia_seg_args* a, void* stream) {
   if (a->has_qkv && (!a->qkv_out || a->ldq < SG_NQ)) return dia_fail(DIA_E_ARG, "dia_seg_mlp: q/k/v output missing");
   if (a->nslots != (a->has_qkv ? SG_SLOTS_FULL : SG_FIRST_QKV)) return dia_fail(DIA_E_ARG, "dia_seg_mlp: slot count does not match the ring layout");
   if (a->xkt * 32 < SG_D || a->ssq_ld < a->M || a->ldx < SG_D) return dia_fail(DIA_E_ARG, "dia_seg_mlp: output layout too narrow");
-  int rc = seg_init();
-  if (rc) return rc;
   SegK k;
   k.a_in = a->a_in; k.a_ktiles = a->a_ktiles; k.W = (const bf16_raw*)a->W; k.nslots = a->nslots; k.M = a->M; k.has_qkv = a->has_qkv ? 1 : 0;
   k.x = a->x; k.ldx = a->ldx; k.g_mlp = a->g_mlp; k.g_next = a->g_next; k.qkv_out = a->qkv_out; k.ldq = a->ldq;

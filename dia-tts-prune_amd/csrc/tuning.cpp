@@ -11,7 +11,10 @@ static const char* const k_names[DIA_TUNE_COUNT] = {
     "mlp_fuse", "tile_v", "blk32_kr", "blk32_ws", "no_g32", "g32_all", "g32m"};
 static int g_tune[DIA_TUNE_COUNT] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
 
-int dia_tune(int id) { return (id >= 0 && id < DIA_TUNE_COUNT) ? g_tune[id] : -1; }
+int dia_tune(int id) {
+  dia_tuning_init_from_env();
+  return (id >= 0 && id < DIA_TUNE_COUNT) ? g_tune[id] : -1;
+}
 
 extern "C" int dia_set_tuning(const char* name, int value) {
   if (!name) return dia_fail(DIA_E_ARG, "dia_set_tuning: null name");

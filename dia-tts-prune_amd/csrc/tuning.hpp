@@ -1,7 +1,6 @@
-// Process-wide tuning / debug overrides of the launch heuristics.  Nothing on the launch path reads the
-// environment: values are set through dia_set_tuning() (C ABI) or, once at library initialisation, from the
-// DIA_TUNE environment variable ("name=value,name=value") so that bench and profiling scripts can vary a knob
-// without code changes.  -1 = not set (the heuristic decides).
+// Process-wide tuning / debug overrides of the launch heuristics.  Values are set through dia_set_tuning() (C ABI)
+// or, once at the first knob lookup, from the DIA_TUNE environment variable ("name=value,name=value") so that bench
+// and profiling scripts can vary a knob without code changes.  -1 = not set (the heuristic decides).
 #pragma once
 
 enum dia_tune_id {
@@ -40,4 +39,4 @@ enum dia_tune_id {
 };
 
 int dia_tune(int id);                 // current value, -1 when unset
-void dia_tuning_init_from_env();      // reads DIA_TUNE once (called by dia_kernels_init_once)
+void dia_tuning_init_from_env();      // reads DIA_TUNE once (called by the first dia_tune / dia_set_tuning / dia_get_tuning)

@@ -47,9 +47,9 @@ int dia_abi_version(void);
 /* number of visible HIP devices, or a negative error */
 int dia_device_count(void);
 /* Tuning / debug overrides of the launch heuristics (process-wide; csrc/tuning.hpp lists the knobs, e.g. "attn_nz",
- * "gemm_spw", "wo_sk").  value < 0 clears a knob.  Nothing on the launch path reads the environment; the DIA_TUNE
- * variable ("name=value,...") is read once when the first engine or kernel is initialised.  The reference has no
- * counterpart (its only switches are torch.compile / dtype, model.py:631-647). */
+ * "gemm_spw", "wo_sk").  value < 0 clears a knob.  The DIA_TUNE variable ("name=value,...") is read once, at the
+ * first knob lookup (this call, dia_get_tuning or a launch heuristic); settings made here override it.  The reference
+ * has no counterpart (its only switches are torch.compile / dtype, model.py:631-647). */
 int dia_set_tuning(const char* name, int value);
 int dia_get_tuning(const char* name);
 /* 1 when the library was built with EXPERIMENTS=1 (measured-and-rejected kernels: dia_mlp_fused, the sparse weight

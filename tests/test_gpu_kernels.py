@@ -3,6 +3,9 @@ each op (and the oracle's sampler).  Tolerances: 2e-5 relative to the output sca
 paths; token ids / integer outputs bit-exact."""
 import ctypes as C
 import math
+import os
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -1135,6 +1138,85 @@ def test_gemm_diagonal_layout_resid(M, K, D):
     # what it is not built for is refused
     g.epi = hb.EPI_SCALE_STORE
     assert hb.lib().dia_gemm(C.byref(g), None) == -1
+
+
+_FIRST_CALLS = r'''
+import ctypes as C, os, sys
+sys.path.insert(0, os.path.join(%r, "dia-tts-prune_amd"))
+import torch
+from dia_hip import binding as hb
+from dia_hip import layout as lay
+d = torch.device("cuda:0")
+L = hb.lib()
+bf16r = lambda t: t.bfloat16().float()
+torch.manual_seed(7)
+# 4 rows from the diagonal layout: k_gemv_diag<4>, 100 KiB of dynamic LDS (as test_gemm_diagonal_layout_resid)
+M, K, D = 4, 4096, 2048
+a = torch.randn(M, K, device=d)
+W = bf16r(torch.randn(K, D, device=d) * 0.03)
+x0 = torch.randn(M, D, device=d)
+gn = bf16r(1.0 + 0.1 * torch.randn(D, device=d))
+Wd = lay.diag_tile_weight(W)
+A = lay.pack_f32_tiles(a, ktiles=K // 32, mtiles=1)
+x = torch.zeros(16, D, device=d); x[:M] = x0
+P = torch.zeros(3, 1, D // 32, 64, 8, dtype=torch.bfloat16, device=d)
+ssq = torch.zeros(D // 8, 16, device=d)
+g = hb.GemmArgs()
+g.A, g.a_plane_stride, g.a_ktiles, g.M = hb.ptr(A), A[0].numel() * 2, K // 32, M
+g.W, g.KT, g.nstrips, g.epi = hb.ptr(Wd), K // 32, D // 8, hb.EPI_RESID_EMIT
+g.ssq_ld, g.out, g.ldo, g.gnext = 16, hb.ptr(x), D, hb.ptr(gn)
+g.P, g.p_plane_stride, g.p_ktiles, g.ssq_out = hb.ptr(P), P[0].numel(), D // 32, hb.ptr(ssq)
+g.act_f32, g.w_layout = 3, 1
+hb.check(L.dia_gemm(C.byref(g), None), "dia_gemm(diag)")
+torch.cuda.synchronize()
+ref = x0.double() + a.double() @ W.double()
+assert (x[:M].double() - ref).abs().max().item() <= 2e-5 * ref.abs().max().item()
+
+def store(M, N):
+    """SCALE_STORE at K = 2048 with fp32 tiles (act_f32 = 3); returns the name of the kernel that ran"""
+    K = 2048
+    mpad = (M + 15) // 16 * 16
+    x = torch.randn(M, K, device=d) * 2
+    W = bf16r(torch.randn(K, N, device=d) * 0.03)
+    Wt, kt, ns = lay.tile_weight(W)
+    A = lay.pack_planes(x)
+    A.view(torch.float32).reshape(-1)[: A[0].numel()] = lay.pack_f32_tiles(x).reshape(-1)
+    s = torch.zeros(K // 16, mpad, device=d)
+    s[:, :M] = (x.double() ** 2).reshape(M, K // 16, 16).sum(-1).T.float()
+    out = torch.zeros(mpad, N, device=d)
+    g = hb.GemmArgs()
+    g.A, g.a_plane_stride, g.a_ktiles, g.M = hb.ptr(A), A[0].numel(), A.shape[2], M
+    g.W, g.KT, g.nstrips, g.epi, g.act_f32 = hb.ptr(Wt), kt, ns, hb.EPI_SCALE_STORE, 3
+    g.ssq_in, g.ssq_in_n, g.ssq_ld, g.inv_d, g.eps = hb.ptr(s), s.shape[0], mpad, 1.0 / K, 1e-5
+    g.out, g.ldo = hb.ptr(out), N
+    ms = C.c_float()
+    hb.check(L.dia_gemm_timed(C.byref(g), None, C.byref(ms)), "dia_gemm_timed")
+    torch.cuda.synchronize()
+    xd = x.double()
+    ref = (xd @ W.double()) * torch.rsqrt((xd ** 2).mean(-1, keepdim=True) + 1e-5)
+    assert (out[:M].double() - ref).abs().max().item() <= 2e-5 * max(1.0, ref.abs().max().item())
+    return L.dia_timed_kernel_name(0).decode()
+
+# 64 rows over 512 strips: k_gemm2t (149 KiB); 32 rows over 256 strips: the persistent z-form with A's mid / lo planes in LDS
+print("KERNELS", store(64, 8192), "|", store(32, 4096))
+'''
+
+
+def test_large_lds_kernels_as_first_calls():
+    """Kernels with more than 64 KiB of dynamic LDS launch as the very first calls of a fresh process (each launch raises its
+    own limit), and DIA_TUNE takes effect on the first knob lookup: gemm_2t=0 keeps the 64-row call off k_gemm2t"""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    names = {}
+    for tune in (None, "gemm_2t=0"):
+        env = {k: v for k, v in os.environ.items() if k != "DIA_TUNE"}
+        if tune:
+            env["DIA_TUNE"] = tune
+        r = subprocess.run([sys.executable, "-c", _FIRST_CALLS % root], cwd=root, env=env, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0 and "KERNELS" in r.stdout, (tune, r.stdout[-1500:], r.stderr[-3000:])
+        names[tune] = r.stdout.split("KERNELS", 1)[1].strip().split(" | ")
+    assert names[None][0].startswith("k_gemm2t<"), names
+    assert names[None][1].startswith("k_gemm16<8, 8, true, true, true, true, false, true"), names
+    assert not names["gemm_2t=0"][0].startswith("k_gemm2t"), names
 
 
 @pytest.mark.parametrize("M,K,N,epi,f32", [
