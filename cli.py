@@ -57,6 +57,9 @@ def build_parser() -> argparse.ArgumentParser:
     g.add_argument("--fp32-weights", type=str, default="exact", choices=["exact", "bf16x2", "round"],
                    help="compute_dtype float32 with a checkpoint bf16 cannot hold: exact = three bf16 planes (generic kernel), "
                         "bf16x2 = hi + lo bf16 planes (relative error <= 2^-17, tuned kernels), round = one rounded bf16 tile set")
+    g.add_argument("--sparse-weights", type=str, default="off", choices=["off", "2:4"],
+                   help="2:4 = the checkpoint is 2:4-pruned (offline_prune.py --prune-mode 2:4): batch 1-2 decode steps stream its "
+                        "decoder matrices in the compressed 2:4 form (sparse MFMA); off = dense tiles only")
     g.add_argument("--verbose", action="store_true", help="report prefill and generation timing")
     return p
 
@@ -76,6 +79,7 @@ def main(argv=None) -> int:
     from dia_hip.model import Dia
 
     Dia.fp32_weights = args.fp32_weights
+    Dia.sparse_weights = args.sparse_weights
     if args.seed is not None:
         set_seed(args.seed)
         print(f"Using seed: {args.seed}")

@@ -78,6 +78,16 @@ static int enqueue_step(dia_engine* e, bool with_sampler) {
   bool diag = (R <= 2 || (R <= 4 && d.F <= 4096)) && d.act_f32 && d.w_planes <= 1 && dia_tune(DIA_TUNE_WO_DIAG) == 1 && !seg;     // (the image of 3-4 rows x 8192 does not fit LDS)
   for (int l = 0; l < d.n_layer && diag; ++l) diag = e->layers[l].w_wo_diag != nullptr && e->layers[l].cmap_next == nullptr;
   const int xn_wo = diag ? d.D / 8 : d.D / 16;
+  // 2:4 sparse weight streams (dia_dec_layer.w_*_24): at <= 4 rows (batch 1-2) every matrix that has one.  From 5 rows on the dense
+  // k_gemm16 forms are as fast or faster in the step (wo 10.9 vs 11.7 us at 16 rows, profiles/r04_sparse24_speed.txt): dense tiles
+  auto sparse24 = [&](dia_gemm_args& g, const void* w24) {
+    if (!w24 || !F || d.w_planes > 1 || R > 4) return;
+    g.W = w24; g.KT /= 2; g.w_format = DIA_W_SPARSE24; g.nw = 0; g.spw = 0;
+    int sk = g.sk > 1 ? g.sk : 1;                 // split-K over whole stream groups (8 sparse k-tiles per workgroup and split)
+    while (sk > 1 && g.KT % (8 * sk) != 0) sk /= 2;
+    g.sk = sk;
+    if (sk == 1) { g.sk_scratch = nullptr; g.sk_tickets = nullptr; }
+  };
   for (int l = 0; l < d.n_layer; ++l) {
     const dia_dec_layer& L = e->layers[l];
     dia_gemm_args g = {};
@@ -90,6 +100,7 @@ static int enqueue_step(dia_engine* e, bool with_sampler) {
     lend_scratch(g);
   g.act_f32 = F;            // reads x as fp32 tiles
   g.w_planes = d.w_planes;
+  sparse24(g, L.w_qkv_24);
   if ((rc = dia_gemm(&g, st))) return rc; mark(e, n++);
     }
 
@@ -112,6 +123,7 @@ static int enqueue_step(dia_engine* e, bool with_sampler) {
     lend_scratch(g);
   g.act_f32 = 3 * F;        // attention output in, x out: both fp32 tiles
   g.w_planes = d.w_planes;
+  sparse24(g, L.w_o_24);
   if ((rc = dia_gemm(&g, st))) return rc; mark(e, n++);
 
     // cross-attention query (layers.py:273, 278)
@@ -123,6 +135,7 @@ static int enqueue_step(dia_engine* e, bool with_sampler) {
     lend_scratch(g);
   g.act_f32 = F;
   g.w_planes = d.w_planes;
+  sparse24(g, L.w_cq_24);
   if ((rc = dia_gemm(&g, st))) return rc; mark(e, n++);
 
     a = {};
@@ -153,6 +166,7 @@ static int enqueue_step(dia_engine* e, bool with_sampler) {
     lend_scratch(g);
   g.act_f32 = 3 * F;
   g.w_planes = d.w_planes;
+  sparse24(g, L.w_co_24);
   if ((rc = dia_gemm(&g, st))) return rc; mark(e, n++);
 
     // SwiGLU MLP (layers.py:95-104)
@@ -216,9 +230,12 @@ static int enqueue_step(dia_engine* e, bool with_sampler) {
     }
     lend_scratch(gi);
     gi.act_f32 = 3 * F; g.act_f32 = 3 * F; gi.w_planes = d.w_planes; g.w_planes = d.w_planes;
+    sparse24(gi, L.w_wi_24);
     if ((rc = dia_gemm(&gi, st))) return rc; mark(e, n++);
     if (diag) {
       g.W = L.w_wo_diag; g.w_layout = 1; g.nstrips = d.D / 8; g.sk = 1; g.sk_scratch = nullptr; g.sk_tickets = nullptr; g.nw = 0; g.spw = 0;
+    } else {
+      sparse24(g, L.w_wo_24);
     }
     rc = dia_gemm(&g, st);
     if (rc == DIA_E_ARG && g.sk > 1) {
@@ -238,6 +255,7 @@ static int enqueue_step(dia_engine* e, bool with_sampler) {
   lend_scratch(g);
   g.act_f32 = F;
   g.w_planes = d.w_planes;
+  sparse24(g, d.w_logits_24);
   if ((rc = dia_gemm(&g, st))) return rc; mark(e, n++);
   if (with_sampler) {
     if ((rc = dia_sample(&d.sample, st))) return rc; mark(e, n++);

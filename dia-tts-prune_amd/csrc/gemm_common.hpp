@@ -386,3 +386,7 @@ inline int fill_gemmk(const dia_gemm_args* a, GemmK& k) {
 }
 
 }  // namespace
+
+// gemm_sparse.hip: dia_gemm with w_format == DIA_W_SPARSE24 (2:4 weight stream, M <= 16)
+int dia_gemm_sparse24_check(const dia_gemm_args* a);
+int dia_gemm_sparse24(const dia_gemm_args* a, void* stream);

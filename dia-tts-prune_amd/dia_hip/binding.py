@@ -14,9 +14,10 @@ from typing import Optional
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DIA_HIP_LIB") or os.path.join(_HERE, "libdia_hip.so")   # override: experiments only
 
-ABI_VERSION = 7
+ABI_VERSION = 8
 KV_F32, KV_BF16, KV_BF16X2 = 0, 1, 2
 EPI_SCALE_STORE, EPI_RESID_EMIT, EPI_SWIGLU_EMIT, EPI_CROSSKV = 0, 1, 2, 3
+W_DENSE, W_SPARSE24 = 0, 1                     # dia_gemm_args.w_format
 ATTN_SELF, ATTN_CROSS, ATTN_ENC = 0, 1, 2
 
 EXPORTS = (
@@ -47,6 +48,7 @@ class GemmArgs(C.Structure):
         ("sp_blocks", C.c_void_p), ("sp_toff", C.c_void_p),
         ("act_f32", C.c_int32), ("w_planes", C.c_int32), ("kv_plane_stride", C.c_int64),
         ("w_layout", C.c_int32), ("kv_layer_strips", C.c_int32), ("kv_layer_stride", C.c_int64),
+        ("w_format", C.c_int32), ("_pad2", C.c_int32),
     ]
 
 
@@ -121,6 +123,8 @@ class DecLayer(C.Structure):
         ("kt_wi", C.c_int32), ("ns_wi", C.c_int32), ("kt_wo", C.c_int32), ("ns_wo", C.c_int32),
         ("cmap_ca", C.c_void_p), ("cmap_mlp", C.c_void_p), ("cmap_next", C.c_void_p),
         ("smap_qkv", C.c_void_p), ("smap_cq", C.c_void_p), ("hmap_self", C.c_void_p), ("hmap_cross", C.c_void_p),
+        ("w_qkv_24", C.c_void_p), ("w_o_24", C.c_void_p), ("w_cq_24", C.c_void_p), ("w_co_24", C.c_void_p),
+        ("w_wi_24", C.c_void_p), ("w_wo_24", C.c_void_p),
     ]
 
 
@@ -141,6 +145,7 @@ class EngineDesc(C.Structure):
         ("sample", SampleArgs),
         ("seg_w", C.POINTER(C.c_void_p)), ("seg_ws", C.c_void_p),
         ("kv_plane_self", C.c_int64), ("kv_plane_cross", C.c_int64),
+        ("w_logits_24", C.c_void_p),
     ]
 
 

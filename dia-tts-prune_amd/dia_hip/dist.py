@@ -40,7 +40,7 @@ def _arena_signature(w) -> List[int]:
     """what must agree on every rank before the flat arena may travel: its size in bytes and the layout switches that
     decide the tensor order inside it"""
     return [int(w.flat.numel()) if w.flat is not None else -1, 1 if getattr(w, "compacted", False) else 0,
-            int(getattr(w, "weight_planes", 1))]
+            int(getattr(w, "weight_planes", 1)), 1 if getattr(w, "sparse", "off") == "2:4" else 0]
 
 
 def broadcast_weights(w, src: int = 0, group=None) -> int:
@@ -64,8 +64,8 @@ def broadcast_weights(w, src: int = 0, group=None) -> int:
         raise ValueError("compacted (structured-pruned) weights have checkpoint-dependent shapes: "
                          "load the checkpoint on every rank instead of broadcasting")
     if lo != hi:
-        raise ValueError(f"weight arenas differ across ranks (bytes, compacted, weight planes): min {lo}, max {hi}; "
-                         "build the receivers with DeviceWeights.empty_like_config(cfg, device, weight_planes=...)")
+        raise ValueError(f"weight arenas differ across ranks (bytes, compacted, weight planes, 2:4 streams): min {lo}, max {hi}; "
+                         "build the receivers with DeviceWeights.empty_like_config(cfg, device, weight_planes=..., sparse=...)")
     dist.broadcast(w.flat, src=src, group=group)
     return int(w.flat.numel())
 

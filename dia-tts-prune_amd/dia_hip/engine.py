@@ -25,6 +25,7 @@ from . import binding as hb
 from . import compact as cpt
 from . import layout as lay
 from .config import DiaConfig
+from .pruning import is_2of4
 
 HEAD_DIM = 128
 
@@ -48,7 +49,7 @@ class DeviceWeights:
     """Checkpoint -> kernel layouts, resident in HBM (bf16 tiles; norms / embeddings fp32)."""
 
     def __init__(self, cfg: DiaConfig, sd: Dict[str, torch.Tensor], device: torch.device, compact: str = "auto",
-                 weight_planes: int = 1, seg: str = "off"):
+                 weight_planes: int = 1, seg: str = "off", sparse: str = "off"):
         """compact: "auto" = drop structure that a structured-pruned checkpoint zeroed (decoder only),
         "off" = keep every matrix at its checkpoint shape (zeros are streamed).
         weight_planes: 1 = every DenseGeneral kernel as ONE bf16 tile set (exact for bf16-representable checkpoints, the fast
@@ -59,9 +60,23 @@ class DeviceWeights:
         seg: "on" = a dense Dia-1.6B-shaped decoder on a GPU also carries the ring arenas of the persistent MLP segments
         (layout.seg_ring; + 2.2 GB: co, wi, wo and the following layer's qkv once more, per CU in consumption order), which
         batch 1-2 sessions then run instead of four launches per layer when the knob seg=1 is set.  EXPERIMENT, default "off":
-        measured 43 us per segment against 31 us for the four launches it replaces."""
+        measured 43 us per segment against 31 us for the four launches it replaces.
+        sparse: "2:4" = a 2:4-pruned checkpoint (offline_prune.py --prune-mode 2:4) also carries every decoder q/k/v, o, cross-q,
+        cross-o, wi and wo matrix and the logits head as a 2:4 sparse stream (layout.tile_weight_24, 0.5625 of the dense bytes),
+        which decode steps of at most 4 rows (batch 1-2) stream instead of the dense tiles.  The dense tiles stay
+        resident for the encoder, the cross K/V projections, both prefills and larger batches: the decoder's weights take about
+        1.56x the memory of the dense model's decoder.  Every such matrix must hold at most 2 non-zeros in every group of 4
+        consecutive K (pruning.is_2of4) and every K must be a multiple of 512; not with weight_planes != 1, a compacted
+        checkpoint or seg="on"."""
         if weight_planes not in (1, 2, 3):
             raise ValueError("weight_planes must be 1, 2 or 3")
+        if sparse not in ("off", "2:4"):
+            raise ValueError('sparse must be "off" or "2:4"')
+        if sparse == "2:4" and weight_planes != 1:
+            raise hb.DiaHipError("sparse='2:4': the 2:4 stream holds one bf16 weight plane (weight_planes must be 1)")
+        if sparse == "2:4" and seg == "on":
+            raise hb.DiaHipError("sparse='2:4': the persistent MLP segments stream dense ring arenas (seg must be 'off')")
+        self.sparse = sparse
         self.weight_planes = weight_planes
         m, e, d = cfg.model, cfg.model.encoder, cfg.model.decoder
         if d.gqa_head_dim != HEAD_DIM or d.cross_head_dim != HEAD_DIM or e.head_dim != HEAD_DIM:
@@ -140,6 +155,17 @@ class DeviceWeights:
         keep_logits = cpt.pad_keep(cpt.nonzero_rows(sd["decoder.logits_dense.weight"].reshape(D, -1)))
         logits_pruned = compact != "off" and not bool(keep_logits.all())
         self.compacted = any(p is not None for p in plans) or logits_pruned or self.enc_compacted
+        if sparse == "2:4" and self.compacted:
+            raise hb.DiaHipError("sparse='2:4': a compacted (structured-pruned) checkpoint has no 2:4 form; load it with compact='off' "
+                                 "or prune with --prune-mode 2:4")
+
+        def tile24(name, w2d) -> TiledW:
+            if w2d.shape[0] % 512:
+                raise hb.DiaHipError(f"sparse='2:4': {name}: K = {w2d.shape[0]} is not a multiple of 512")
+            if not is_2of4(w2d):
+                raise hb.DiaHipError(f"sparse='2:4': {name} is not 2:4 sparse (more than 2 non-zeros in a group of 4 consecutive K)")
+            t, kt, ns = lay.tile_weight_24(w2d)
+            return TiledW(t, kt, ns)
         i32 = lambda t: t.to(device=device, dtype=torch.int32).contiguous()
         ones_d = torch.ones(D, dtype=torch.bool)
 
@@ -190,6 +216,12 @@ class DeviceWeights:
                          hmap_self=i32(cpt.head_map(P.live_q_heads)), hmap_cross=i32(cpt.head_map(P.live_c_heads)))
             L.update(qkv=tile(qkv), o=tile(o), cq=tile(cq), co=tile(co), ckv=tile(ckv),
                      wi=tile(lay.interleave_gate_up(wi3)), wo=tile(wo))
+            for k_, w_ in (("qkv", qkv), ("o", o), ("cq", cq), ("co", co), ("wi", wi3), ("wo", wo)):
+                if sparse == "2:4":
+                    w2_ = lay.interleave_gate_up(w_) if k_ == "wi" else w_
+                    L[k_ + "24"] = tile24(f"decoder.layers.{i}.{k_}", w2_)
+                else:
+                    L[k_ + "24"] = None
             # experiment (knob wo_diag=1): wo once more in the diagonal layout (4-column groups: 256 workgroups with the whole K each)
             L["wo_diag"] = None
             if (hb.get_tuning("wo_diag") == 1 and P is None and weight_planes == 1 and device.type == "cuda" and wo.shape[0] % 1024 == 0
@@ -215,6 +247,7 @@ class DeviceWeights:
         lw = dev("decoder.logits_dense.weight").reshape(D, -1)
         self.logits = tile(lw[keep_logits.to(device)] if logits_pruned else lw)
         self.logits_cols = lw.shape[1]
+        self.logits24 = tile24("decoder.logits_dense", lw) if sparse == "2:4" else None
         npos = max(cfg.data.audio_length, cfg.data.text_length) + 1
         cos, sin = lay.rope_tables(npos, HEAD_DIM, m.rope_min_timescale, m.rope_max_timescale)
         self.cos_t, self.sin_t = cos.to(device), sin.to(device)
@@ -262,6 +295,10 @@ class DeviceWeights:
         out += [self.dec_norm, self.logits.t, self.cos_t, self.sin_t]
         out += [t for t in (self.cmap_first, self.enc_cmap_first) if t is not None]
         out += self.seg_layers
+        if self.sparse == "2:4":                    # the 2:4 streams (sparse="2:4"), after everything the dense model holds
+            for L in self.dec_layers:
+                out += [L[k + "24"].t for k in ("qkv", "o", "cq", "co", "wi", "wo")]
+            out.append(self.logits24.t)
         return out
 
     def pack_flat(self):
@@ -282,26 +319,32 @@ class DeviceWeights:
         self.flat = flat
 
     @classmethod
-    def empty_like_config(cls, cfg: DiaConfig, device: torch.device, weight_planes: int = 1, seg: str = "off") -> "DeviceWeights":
+    def empty_like_config(cls, cfg: DiaConfig, device: torch.device, weight_planes: int = 1, seg: str = "off",
+                          sparse: str = "off") -> "DeviceWeights":
         """Same tensors, zero-filled: the receive side of the multi-GPU weight broadcast (dense layout;
         a compacted, i.e. structured-pruned, model has checkpoint-dependent shapes: every rank then
         loads the checkpoint itself instead of receiving a broadcast).  `weight_planes` must be the sender's
         (dist.broadcast_weights checks it on every rank before the arena travels)."""
         from .weights import param_shapes
         sd = {k: torch.zeros(shp, dtype=torch.float32, device=device) for k, shp in param_shapes(cfg).items()}
-        return cls(cfg, sd, device, compact="off", weight_planes=weight_planes, seg=seg)
+        return cls(cfg, sd, device, compact="off", weight_planes=weight_planes, seg=seg, sparse=sparse)
 
     def prefill_weight_bytes(self) -> int:
         """bf16 bytes the prefill streams once per batch: the encoder and the cross K/V projections"""
         n = sum(L[k].nbytes for L in self.enc_layers for k in ("qkv", "o", "wi", "wo"))
         return n + sum(L["ckv"].nbytes for L in self.dec_layers)
 
-    def decode_weight_bytes(self) -> int:
-        """bf16 bytes one decode step streams (SURVEY.md §8d 'W'): every decoder matrix except the
-        prefill-only cross K/V projections, plus the logits head."""
-        n = self.logits.nbytes
+    def decode_weight_bytes(self, rows: int = 2) -> int:
+        """bf16 bytes one decode step of `rows` rows (2 per utterance) streams (SURVEY.md §8d 'W'): every decoder matrix except
+        the prefill-only cross K/V projections, plus the logits head — the 2:4 streams where the step uses them (sparse="2:4",
+        at most 4 rows)."""
+        every = self.sparse == "2:4" and rows <= 4
+
+        def w(L, k):
+            return L[k + "24"].nbytes if every else L[k].nbytes
+        n = self.logits24.nbytes if every else self.logits.nbytes
         for L in self.dec_layers:
-            n += sum(L[k].nbytes for k in ("qkv", "o", "cq", "co", "wi", "wo"))
+            n += sum(w(L, k) for k in ("qkv", "o", "cq", "co", "wi", "wo"))
         return n
 
 
@@ -527,6 +570,9 @@ class DecodeSession:
             for f in ("cmap_ca", "cmap_mlp", "cmap_next", "smap_qkv", "smap_cq", "hmap_self", "hmap_cross"):
                 setattr(dl, f, hb.ptr(L[f]))
             dl.w_wo_diag = hb.ptr(L.get("wo_diag"))
+            for f in ("qkv", "o", "cq", "co", "wi", "wo"):                  # 2:4 streams (sparse="2:4"), NULL = dense only
+                sp = L.get(f + "24")
+                setattr(dl, "w_" + f + "_24", hb.ptr(sp.t) if sp is not None else None)
         ed = hb.EngineDesc()
         ed.n_layer, ed.D, ed.F = n, self.D, self.F
         ed.q_heads, ed.kv_heads, ed.cq_heads = d.gqa_query_heads, d.kv_heads, d.cross_query_heads
@@ -537,6 +583,7 @@ class DecodeSession:
         ed.eps = float(self.cfg.model.normalization_layer_epsilon)
         ed.layers = C.cast(self._layers, C.POINTER(hb.DecLayer))
         ed.w_logits, ed.kt_logits, ed.ns_logits = hb.ptr(w.logits.t), w.logits.kt, w.logits.ns
+        ed.w_logits_24 = hb.ptr(w.logits24.t) if getattr(w, "logits24", None) is not None else None
         ed.g_final = hb.ptr(w.dec_norm)
         ed.x, ed.planes_x, ed.planes_a, ed.planes_h = hb.ptr(self.x), hb.ptr(self.planes_x), hb.ptr(self.planes_a), hb.ptr(self.planes_h)
         ed.ssq, ed.qkv, ed.qc, ed.logits = hb.ptr(self.ssq), hb.ptr(self.qkv), hb.ptr(self.qc), hb.ptr(self.logits)
@@ -1012,4 +1059,4 @@ class DecodeSession:
             n_keys = int(self.cur.max().item())
         kv_self = 2 * d.n_layer * 2 * d.kv_heads * HEAD_DIM * kvb * n_keys      # both rows, K and V
         kv_cross = d.n_layer * 2 * d.cross_query_heads * HEAD_DIM * kvb          # cond row, per text byte
-        return self.w.decode_weight_bytes() + self.B * kv_self + kv_cross * sum(self.lens)
+        return self.w.decode_weight_bytes(self.R) + self.B * kv_self + kv_cross * sum(self.lens)

@@ -235,6 +235,71 @@ def sparse_untile(blocks: torch.Tensor, toff: torch.Tensor, ns: int, kt: int) ->
     return torch.from_numpy(out).view(torch.bfloat16).reshape(ns, kt, 64, 8)
 
 
+# ---- 2:4 sparse weight stream (dia_gemm_args.w_format = DIA_W_SPARSE24, csrc/gemm_sparse.hip) ---------------------------
+SP24_GROUP = 8           # sparse k-tiles (64 K each) behind one metadata block
+
+
+def tile_weight_24(w2d: torch.Tensor) -> Tuple[torch.Tensor, int, int]:
+    """[K, N] float, at most 2 non-zeros in every group of 4 consecutive K of a column (pruning.is_2of4) -> (stream bf16
+    [N/16, G, 9, 64, 8], K/64, N/16): the compressed A operand of ``v_smfmac_f32_16x16x64_bf16``.  K is zero-padded to a
+    multiple of 64 (one sparse k-tile), N to 16, the k-tiles to whole groups of 8 (G = ceil(K/64 / 8)).
+
+    Operand mapping (pinned on the hardware by tests/test_gpu_sparse24.py): lane l of sparse k-tile t holds the 8 kept values of
+    output column 16 strip + (l & 15) over K = 64 t + 16 (l >> 4) + [0, 16): value j belongs to group g = j >> 1
+    (K 64 t + 16 (l >> 4) + 4 g + [0, 4)); the lower kept position is j = 2g, the higher j = 2g + 1.  Its position inside the
+    group (0..3) sits in bits [2j + 1 : 2j] of a 16-bit index word; the instruction's index operand carries two such words,
+    selected by ``abid`` (0: bits 0-15, 1: bits 16-31).  The dense B operand (16 bf16 per lane) holds activation row l & 15 at
+    K = 64 t + 32 (e >> 3) + 8 (l >> 4) + (e & 7) for element e: the two halves are exactly the A fragments of the dense
+    k-tiles 2t and 2t + 1 (fp32 activation tiles, pack_f32_tiles).
+
+    Stream of a strip: one block per group of 8 sparse k-tiles, each a sequential 9 KiB = slot 0, the metadata (16 bytes per lane:
+    dword d = index words of k-tiles 2d (bits 0-15) and 2d + 1 (bits 16-31) of the group), then slots 1..8, the values of the
+    group's k-tiles (16 bytes per lane).  A group with fewer than 2 non-zeros in a K group of 4 keeps zero-valued positions
+    (lowest first), so every index word names two distinct positions in increasing order.  0.5625 of the dense tiles' bytes."""
+    K, N = w2d.shape
+    Kp, Np = _ceil(K, 64), _ceil(N, 16)
+    kt, ns = Kp // 64, Np // 16
+    G = (kt + SP24_GROUP - 1) // SP24_GROUP
+    wp = torch.zeros(G * SP24_GROUP * 64, Np, dtype=torch.float32, device=w2d.device)
+    wp[:K, :N] = w2d.float()
+    g = wp.reshape(-1, 4, Np)                                                  # [K/4, 4, N]
+    nz = (g != 0).to(torch.int32)
+    if bool((nz.sum(dim=1) > 2).any()):
+        raise ValueError("tile_weight_24: more than 2 non-zeros in a group of 4 consecutive K (prune with pruning.semi_structured_prune_state_dict)")
+    # non-zeros first, then the lowest positions; the two picks in increasing position order
+    key = (1 - nz) * 4 + torch.arange(4, device=w2d.device).view(1, 4, 1)
+    pos = torch.sort(torch.topk(key, 2, dim=1, largest=False).indices, dim=1).values       # [K/4, 2, N]
+    val = torch.gather(g, 1, pos)
+    kt8 = G * SP24_GROUP
+    # (t, q, g, s, strip, c) -> (strip, t, lane = 16 q + c, j = 2 g + s)
+    val = val.reshape(kt8, 4, 4, 2, ns, 16).permute(4, 0, 1, 5, 2, 3).reshape(ns, kt8, 64, 8)
+    pos = pos.reshape(kt8, 4, 4, 2, ns, 16).permute(4, 0, 1, 5, 2, 3).reshape(ns, kt8, 64, 8)
+    word = (pos.to(torch.int64) << (2 * torch.arange(8, device=w2d.device, dtype=torch.int64))).sum(dim=3)  # [ns, kt8, 64]
+    word = word.reshape(ns, G, 4, 2, 64)
+    dword = word[:, :, :, 0] | (word[:, :, :, 1] << 16)                                       # [ns, G, 4, 64]
+    meta = dword.permute(0, 1, 3, 2).to(torch.int32).contiguous().view(torch.int16)           # [ns, G, 64, 8] int16
+    vals = val.to(torch.bfloat16).reshape(ns, G, SP24_GROUP, 64, 8)
+    stream = torch.cat([meta.view(torch.bfloat16).reshape(ns, G, 1, 64, 8), vals], dim=2)
+    return stream.contiguous(), kt, ns
+
+
+def untile_weight_24(stream: torch.Tensor, K: int, N: int) -> torch.Tensor:
+    """inverse of tile_weight_24 (test helper): fp32 [K, N]"""
+    ns, G = stream.shape[0], stream.shape[1]
+    kt8 = G * SP24_GROUP
+    meta = stream[:, :, 0].contiguous().view(torch.int16).reshape(ns, G, 64, 8).view(torch.int32).to(torch.int64) & 0xFFFFFFFF  # [ns, G, 64, 4]
+    word = torch.stack([meta & 0xFFFF, meta >> 16], dim=-1).permute(0, 1, 3, 4, 2).reshape(ns, kt8, 64)                    # [ns, kt8, 64]
+    pos = (word[..., None] >> (2 * torch.arange(8, dtype=torch.int64, device=stream.device))) & 3                           # [ns, kt8, 64, 8]
+    val = stream[:, :, 1:].float().reshape(ns, kt8, 64, 8)
+    # (strip, t, q, c, g, s) -> dense [t, q, g, 4 positions, strip, c]
+    val = val.reshape(ns, kt8, 4, 16, 4, 2).permute(1, 2, 4, 5, 0, 3)
+    pos = pos.reshape(ns, kt8, 4, 16, 4, 2).permute(1, 2, 4, 5, 0, 3)
+    dense = torch.zeros(kt8, 4, 4, 4, ns, 16, dtype=torch.float32, device=stream.device)
+    dense.scatter_add_(3, pos[:, :, :, 0:1], val[:, :, :, 0:1])
+    dense.scatter_add_(3, pos[:, :, :, 1:2], val[:, :, :, 1:2])
+    return dense.reshape(kt8 * 64, ns * 16)[:K, :N].contiguous()
+
+
 # ---- ring layout of the persistent MLP segment (csrc/seg.hip) ------------------------------------------------------
 SEG_CUS = 256            # one workgroup per CU of an MI355X
 SEG_K = 2048             # contraction length of one slot (16 tiles of 128 k x 4 columns)

@@ -48,6 +48,9 @@ class Dia:
     # (the reference's fp32 path, ~3x slower), "bf16x2" = hi + lo bf16 planes (relative error <= 2^-17, 2x the weight
     # traffic, the tuned decode kernels), "round" = one rounded bf16 tile set (fast; the load prints a warning)
     fp32_weights = "exact"
+    # "2:4": a 2:4-pruned checkpoint (offline_prune.py --prune-mode 2:4) also carries its decoder matrices and logits head as 2:4
+    # sparse streams, which decode steps of batch 1-2 stream instead of the dense tiles (DeviceWeights sparse="2:4"); "off" = dense
+    sparse_weights = "off"
 
     def __init__(self, config: DiaConfig, compute_dtype: Union[str, ComputeDtype] = ComputeDtype.FLOAT32,
                  device: Optional[torch.device] = None):
@@ -84,7 +87,7 @@ class Dia:
             # leaves the missing tensors at their random initialisation; listed in INTEGRATION.md
             raise RuntimeError(f"Missing keys in checkpoint: {missing}")
         with torch.cuda.device(self.device):
-            self.model = DeviceWeights(self.config, sd, self.device)
+            self.model = DeviceWeights(self.config, sd, self.device, sparse=self.sparse_weights)
             # DenseGeneral kernels are streamed as ONE bf16 tile set by the fast kernels.  A checkpoint whose values are
             # bf16-representable (bf16-trained weights stored as fp32, the synthetic ones) loses nothing.  A genuine fp32
             # checkpoint would be rounded once at load = the reference's bfloat16 configuration, NOT its float32 path:

@@ -80,6 +80,51 @@ def unstructured_prune_state_dict(cfg: DiaConfig, sd: Dict[str, torch.Tensor], a
     return out
 
 
+def _kernel_2d(name: str, w: torch.Tensor) -> torch.Tensor:
+    """a DenseGeneral kernel as [K, N] with K the contraction axis, as DeviceWeights flattens it: o_proj [heads, hd, D] and
+    wo [F, D] keep their leading axes as K, every other kernel ([D, heads, hd], wi_fused [D, 2, F], logits [D, C, V]) its first"""
+    if name.endswith("o_proj.weight"):
+        return w.reshape(-1, w.shape[-1])
+    return w.reshape(w.shape[0], -1)
+
+
+def _prune_2of4_2d(w2d: torch.Tensor) -> torch.Tensor:
+    """[K, N] -> same shape: in every group of 4 consecutive K rows of each column the 2 largest |w| stay, the others become 0
+    (ties: the lower K index stays).  A trailing partial group (K % 4 != 0) is treated as zero-padded."""
+    K, N = w2d.shape
+    Kp = (K + 3) // 4 * 4
+    wp = torch.zeros(Kp, N, dtype=w2d.dtype, device=w2d.device)
+    wp[:K] = w2d
+    g = wp.reshape(Kp // 4, 4, N)
+    # stable descending sort of |w| keeps the lower index first among equals
+    order = torch.sort(g.abs(), dim=1, descending=True, stable=True).indices
+    mask = torch.zeros_like(g, dtype=torch.bool)
+    mask.scatter_(1, order[:, :2], True)
+    return (g * mask).reshape(Kp, N)[:K]
+
+
+def semi_structured_prune_state_dict(cfg: DiaConfig, sd: Dict[str, torch.Tensor]) -> "OrderedDict[str, torch.Tensor]":
+    """2:4 semi-structured pruning (``offline_prune.py --prune-mode 2:4``): every kernel of ``prunable_names(cfg)``, flattened
+    to [K, N] (``_kernel_2d``), keeps the 2 largest |w| of every group of 4 consecutive K rows of each column; ties keep the
+    lower K index.  Half of every kernel becomes zero, in the pattern the sparse MFMA of gfx950 consumes
+    (layout.tile_weight_24).  Idempotent; embeddings and norms are untouched."""
+    out: "OrderedDict[str, torch.Tensor]" = OrderedDict((k, v.clone()) for k, v in sd.items())
+    for name in prunable_names(cfg):
+        w = sd[name]
+        out[name] = _prune_2of4_2d(_kernel_2d(name, w.float())).reshape(w.shape).to(w.dtype)
+    return out
+
+
+def is_2of4(w2d: torch.Tensor) -> bool:
+    """True when every group of 4 consecutive rows (K) of every column of [K, N] holds at most 2 non-zeros
+    (a trailing partial group counts as zero-padded)"""
+    K, N = w2d.shape
+    Kp = (K + 3) // 4 * 4
+    nz = torch.zeros(Kp, N, dtype=torch.int32, device=w2d.device)
+    nz[:K] = (w2d != 0).to(torch.int32)
+    return bool((nz.reshape(Kp // 4, 4, N).sum(dim=1) <= 2).all().item())
+
+
 def kept_slices(w: torch.Tensor, dim: int = 0) -> np.ndarray:
     """Indices along `dim` whose slice is not identically zero."""
     moved = w.movedim(dim, 0).reshape(w.shape[dim], -1)

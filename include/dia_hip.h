@@ -19,7 +19,7 @@
 extern "C" {
 #endif
 
-#define DIA_ABI_VERSION 7
+#define DIA_ABI_VERSION 8
 
 #define DIA_OK 0
 #define DIA_E_ARG (-1)     /* bad argument / unsupported shape */
@@ -36,6 +36,10 @@ extern "C" {
 #define DIA_EPI_RESID_EMIT 1   /* x[m][n] += acc; emit planes(x*g_next), strip ssq   (o_proj, wo)             */
 #define DIA_EPI_SWIGLU_EMIT 2  /* h = silu(gate*inv)* (up*inv); emit planes(h)       (wi_fused)               */
 #define DIA_EPI_CROSSKV 3      /* K = RoPE(acc*inv) , V = acc*inv -> cross caches    (precompute_cross_attn_cache) */
+
+/* weight formats of dia_gemm_args.w_format */
+#define DIA_W_DENSE 0      /* bf16 tiles [nstrips][KT][64][8], KT = K/32 */
+#define DIA_W_SPARSE24 1   /* 2:4 sparse stream (dia_hip/layout.py tile_weight_24), KT = K/64 */
 
 /* attention modes */
 #define DIA_ATTN_SELF 0   /* decoder self-attention over the growing cache (layers.py:541-555) */
@@ -156,6 +160,14 @@ typedef struct {
    * sets back to back, nstrips = their sum.  0 = one layer (above). */
   int32_t kv_layer_strips;
   int64_t kv_layer_stride;
+  /* DIA_W_DENSE (0): W as above.  DIA_W_SPARSE24: W is the 2:4 sparse stream of a matrix with at most 2 non-zeros in every
+   * group of 4 consecutive K of a column (dia_hip/layout.py tile_weight_24: per strip, groups of 8 sparse k-tiles of 64 K, each
+   * a 1 KiB index block followed by 8 KiB of kept values, the A operand of v_smfmac_f32_16x16x64_bf16) and KT counts sparse
+   * k-tiles (K/64, a multiple of 8 per workgroup).  M <= 16, fp32 activation tiles in and out (act_f32 = 3; bit 0 alone when
+   * nothing is emitted), SCALE_STORE / RESID_EMIT (with gnext) / SWIGLU_EMIT, split-K through sk; not with w_planes > 1,
+   * w_layout = 1, sp_blocks, CROSSKV or the compaction maps — those return DIA_E_ARG. */
+  int32_t w_format;
+  int32_t _pad2;
 } dia_gemm_args;
 int dia_gemm(const dia_gemm_args* a, void* stream);
 /* same launch, bracketed by dispatch-level start/stop events (hipExtLaunchKernelGGL); returns the
@@ -398,6 +410,10 @@ typedef struct {
   const int32_t* smap_cq;     /* strip map of the cross-q output */
   const int32_t* hmap_self;   /* head map of self-attention */
   const int32_t* hmap_cross;  /* head map of cross-attention */
+  /* 2:4 sparse streams of the same matrices (dia_gemm_args.w_format = DIA_W_SPARSE24, KT = kt_* / 2), NULL = dense only.  A step
+   * of at most 4 rows (batch 1-2) streams every matrix that has one; more rows (the dense forms are as fast there), planes between
+   * the kernels (act_f32 = 0), two- or three-plane weights and the wo_diag / segment / mlp_fused experiments use the dense tiles */
+  const void *w_qkv_24, *w_o_24, *w_cq_24, *w_co_24, *w_wi_24, *w_wo_24;
 } dia_dec_layer;
 
 typedef struct {
@@ -443,6 +459,7 @@ typedef struct {
   const void* const* seg_w;
   void* seg_ws;             /* workspace of dia_seg_mlp */
   int64_t kv_plane_self, kv_plane_cross;   /* DIA_KV_BF16X2: plane strides (elements) of the self / cross caches */
+  const void* w_logits_24;  /* 2:4 sparse stream of the logits head (as dia_dec_layer.w_*_24: used at <= 4 rows), NULL = dense only */
 } dia_engine_desc;
 
 typedef struct dia_engine dia_engine;

@@ -25,7 +25,8 @@ def main(argv=None) -> int:
     p = argparse.ArgumentParser(description="Prune a Dia checkpoint on the CPU and write it back with the zeros baked in.")
     p.add_argument("--model-path", type=str, required=True, help="directory of the dense model: config.json plus its checkpoint")
     p.add_argument("--output-dir", type=str, required=True, help="where pytorch_model.bin and config.json of the pruned model go")
-    p.add_argument("--prune-mode", type=str, required=True, choices=["unstructured", "structured"], help="global magnitude pruning of single weights, or whole slices along --prune-dim")
+    p.add_argument("--prune-mode", type=str, required=True, choices=["unstructured", "structured", "2:4"],
+                   help="global magnitude pruning of single weights, whole slices along --prune-dim, or 2:4 semi-structured (2 of every 4 consecutive K of each column)")
     p.add_argument("--prune-amount", type=float, required=True, help="share of weights (unstructured) or of slices per matrix (structured) to zero, strictly between 0 and 1")
     p.add_argument("--prune-dim", type=int, default=0, help="structured mode: the axis whose slices are ranked and zeroed")
     p.add_argument("--prune-norm", type=int, default=2, choices=[1, 2], help="structured mode: rank slices by their L1 or L2 norm")
@@ -35,9 +36,12 @@ def main(argv=None) -> int:
     if not (0.0 < a.prune_amount < 1.0):
         print("Error: --prune-amount must be between 0.0 and 1.0 (exclusive).")
         return 1
+    if a.prune_mode == "2:4" and a.prune_amount != 0.5:
+        print("Error: --prune-mode 2:4 zeroes exactly half of every kernel; --prune-amount must be 0.5.")
+        return 1
 
     from dia_hip import weights as W
-    from dia_hip.pruning import sparsity, structured_prune_state_dict, unstructured_prune_state_dict
+    from dia_hip.pruning import semi_structured_prune_state_dict, sparsity, structured_prune_state_dict, unstructured_prune_state_dict
 
     out = Path(a.output_dir)
     out.mkdir(parents=True, exist_ok=True)
@@ -55,6 +59,8 @@ def main(argv=None) -> int:
     print(f"\nApplying {a.prune_mode} pruning...")
     if a.prune_mode == "unstructured":
         psd = unstructured_prune_state_dict(cfg, sd, a.prune_amount)
+    elif a.prune_mode == "2:4":
+        psd = semi_structured_prune_state_dict(cfg, sd)
     else:
         psd, _ = structured_prune_state_dict(cfg, sd, a.prune_amount, dim=a.prune_dim, n=a.prune_norm)
     print(f"Achieved sparsity: {sparsity(cfg, psd):.4f}")
