@@ -39,8 +39,7 @@ def broadcast_tensors(tensors: Iterable[torch.Tensor], src: int = 0, group=None)
 def _arena_signature(w) -> List[int]:
     """what must agree on every rank before the flat arena may travel: its size in bytes and the layout switches that
     decide the tensor order inside it"""
-    return [int(w.flat.numel()) if w.flat is not None else -1, 1 if getattr(w, "compacted", False) else 0,
-            int(getattr(w, "weight_planes", 1)), 1 if getattr(w, "sparse", "off") == "2:4" else 0]
+    return [int(w.flat.numel()) if w.flat is not None else -1, int(bool(w.compacted)), int(w.weight_planes), int(w.sparse == "2:4")]
 
 
 def broadcast_weights(w, src: int = 0, group=None) -> int:

@@ -16,6 +16,7 @@ from __future__ import annotations
 
 import ctypes as C
 from dataclasses import dataclass
+from functools import partial
 from typing import Dict, List, Optional, Sequence
 
 import numpy as np
@@ -28,21 +29,92 @@ from .config import DiaConfig
 from .pruning import is_2of4
 
 HEAD_DIM = 128
+_TILERS = {1: lay.tile_weight, 2: lay.tile_weight_bf16x2, 3: lay.tile_weight_planes}       # weight_planes -> layout of a DenseGeneral kernel
 
 
 def _ceil(v: int, m: int) -> int:
     return (v + m - 1) // m * m
 
 
+DEC_MATS = ("qkv", "o", "cq", "co", "wi", "wo")       # the matrices of a decoder layer that a decode step streams (DecLayer w_* / kt_* / ns_*)
+
+
 @dataclass
 class TiledW:
+    """One weight in a kernel layout.  With two-plane weights `kt` counts hi and lo tiles."""
     t: torch.Tensor
     kt: int
     ns: int
+    planes: int = 1
 
     @property
     def nbytes(self) -> int:
         return self.t.numel() * 2
+
+    @property
+    def a_kt(self) -> int:
+        """k-tiles of the activation this weight multiplies"""
+        return self.kt // 2 if self.planes == 2 else self.kt
+
+
+def _plane_set(P: torch.Tensor, kt: int):
+    """(pointer, plane stride, k-tiles) of an activation plane set [plane][m-tile][kt][64][8]"""
+    return hb.ptr(P), P[0].numel(), kt
+
+
+def pack_segments(lengths: Sequence[int]):
+    """Variable-length segments as runs of whole 32-row blocks (m-tiles and key blocks) of one packed batch:
+    (offset of every segment, total rows, int32 row -> segment with -1 in the padding rows)."""
+    offs, tot = [], 0
+    for n in lengths:
+        offs.append(tot)
+        tot += _ceil(n, 32)
+    row_seg = np.full((tot,), -1, dtype=np.int32)
+    for i, n in enumerate(lengths):
+        row_seg[offs[i]: offs[i] + n] = i
+    return offs, tot, row_seg
+
+
+def _compact_mlp(wi3, wo, live_hidden, keep_wi):
+    """The MLP of a structured-pruned layer: the live hidden units (padded to the kernels' granule, compact.pad_hidden_keep; a padding
+    unit is a zero row of wo) and the kept input rows of wi."""
+    hid = cpt.pad_hidden_keep(live_hidden).to(wi3.device)
+    wi3 = torch.stack([cpt.take_cols_idx(wi3[:, 0, :], hid), cpt.take_cols_idx(wi3[:, 1, :], hid)], dim=1)
+    wi3 = wi3[keep_wi.to(wi3.device)]
+    wo = wo[hid.clamp(min=0)].clone()
+    wo[hid < 0] = 0
+    return wi3, wo
+
+
+def _launch_gemm(st, A, a_kt, W: TiledW, epi, *, M, ssq, ssq_ld, width, eps, w_planes, ssq_in=False, out=None, ldo=0, gnext=None,
+                 P=None, p_kt=0, ssq_out=False, cmap=None, strip_map=None, kv=None, kv_layers=None, row_map=None, sk=None):
+    """One dia_gemm over the M packed rows of a prefill.  `ssq` holds the strip sums of squares of the `width`-wide residual stream.
+    kv: (kc, vc, kv_dtype, kv_heads, kv_cap, kv_batch_index, kv_vblocked, kv_plane_stride, cos_t, sin_t) of the cross-K/V epilogue,
+    kv_layers: (strips, cache stride) per layer of a merged launch; row_map: (row_b, seg_off); sk: (splits, scratch, tickets)."""
+    g = hb.GemmArgs()
+    g.A, g.a_plane_stride, g.a_ktiles = _plane_set(A, a_kt)
+    g.M = M
+    g.W, g.KT, g.nstrips, g.epi = hb.ptr(W.t), W.kt, W.ns, epi
+    g.w_planes = w_planes
+    if ssq_in:
+        g.ssq_in, g.ssq_in_n, g.inv_d, g.eps = hb.ptr(ssq), width // 16, 1.0 / width, eps
+    g.ssq_ld = ssq_ld
+    g.out, g.ldo, g.gnext = hb.ptr(out), ldo, hb.ptr(gnext)
+    if P is not None:
+        g.P, g.p_plane_stride, g.p_ktiles = _plane_set(P, p_kt)
+    if ssq_out:
+        g.ssq_out = hb.ptr(ssq)
+    g.strip_map, g.cmap = hb.ptr(strip_map), hb.ptr(cmap)
+    if kv is not None:
+        g.kc, g.vc, g.kv_dtype, g.kv_heads, g.kv_cap, g.kv_batch_index, g.kv_vblocked, g.kv_plane_stride, g.cos_t, g.sin_t = kv
+        if kv_layers is not None:
+            g.kv_layer_strips, g.kv_layer_stride = kv_layers
+    if row_map is not None:
+        g.row_b, g.seg_off = (hb.ptr(t) for t in row_map)
+    if sk is not None:      # split-K over workgroups through the session's slab scratch (short prompts: the z-form needs K <= 2048 per workgroup)
+        g.sk, scratch, tickets = sk
+        g.sk_scratch, g.sk_tickets, g.sk_scratch_floats = hb.ptr(scratch), hb.ptr(tickets), scratch.numel()
+    hb.check(hb.lib().dia_gemm(C.byref(g), st), "dia_gemm")
 
 
 class DeviceWeights:
@@ -54,7 +126,7 @@ class DeviceWeights:
         "off" = keep every matrix at its checkpoint shape (zeros are streamed).
         weight_planes: 1 = every DenseGeneral kernel as ONE bf16 tile set (exact for bf16-representable checkpoints, the fast
         kernels); 2 = the hi / lo bf16 planes of the fp32 weights interleaved per k-tile (layout.tile_weight_bf16x2: relative
-        error <= 2^-17, 2x the bytes, the tuned decode kernels; every TiledW.kt counts both planes); 3 = the hi / mid / lo bf16
+        error <= 2^-17, 2x the bytes, the tuned decode kernels); 3 = the hi / mid / lo bf16
         planes of the fp32 weights (exact for any checkpoint, 3x the bytes, the generic kernel: the parity configuration of a
         genuine fp32 checkpoint).
         seg: "on" = a dense Dia-1.6B-shaped decoder on a GPU also carries the ring arenas of the persistent MLP segments
@@ -68,7 +140,7 @@ class DeviceWeights:
         1.56x the memory of the dense model's decoder.  Every such matrix must hold at most 2 non-zeros in every group of 4
         consecutive K (pruning.is_2of4) and every K must be a multiple of 512; not with weight_planes != 1, a compacted
         checkpoint or seg="on"."""
-        if weight_planes not in (1, 2, 3):
+        if weight_planes not in _TILERS:
             raise ValueError("weight_planes must be 1, 2 or 3")
         if sparse not in ("off", "2:4"):
             raise ValueError('sparse must be "off" or "2:4"')
@@ -84,114 +156,128 @@ class DeviceWeights:
         if d.n_embd % 32 or d.n_hidden % 32 or e.n_embd % 32 or e.n_hidden % 32:
             raise hb.DiaHipError("embedding / hidden sizes must be multiples of 32")
         self.cfg, self.device = cfg, device
-
-        def dev(name):
-            return sd[name].to(device=device, dtype=torch.float32)
-
         self.max_weight_rounding = 0.0                  # largest |w - bf16(w)| / max|w| over the DenseGeneral kernels
 
-        def tile(w2d) -> TiledW:
-            if weight_planes == 3:
-                t, kt, ns = lay.tile_weight_planes(w2d)
-            elif weight_planes == 2:
-                t, kt, ns = lay.tile_weight_bf16x2(w2d)
-            else:
-                t, kt, ns = lay.tile_weight(w2d)
-            if w2d.numel() and weight_planes == 1:
-                err = (w2d - w2d.to(torch.bfloat16).to(w2d.dtype)).abs().max()
-                scale = w2d.abs().max()
-                if float(scale) > 0.0:
-                    self.max_weight_rounding = max(self.max_weight_rounding, float(err / scale))
-            return TiledW(t, kt, ns)
+        self._build_encoder(sd, compact)
+        keep_logits = self._build_decoder(sd, compact)
+        self._build_seg(sd, seg)
+        self.dec_norm = self._dev(sd, "decoder.norm.weight").contiguous()
+        lw = self._dev(sd, "decoder.logits_dense.weight").reshape(d.n_embd, -1)
+        self.logits = self._tile(lw[keep_logits.to(device)] if keep_logits is not None else lw)
+        self.logits_cols = lw.shape[1]
+        self.logits24 = self._tile24("decoder.logits_dense", lw) if sparse == "2:4" else None
+        npos = max(cfg.data.audio_length, cfg.data.text_length) + 1
+        cos, sin = lay.rope_tables(npos, HEAD_DIM, m.rope_min_timescale, m.rope_max_timescale)
+        self.cos_t, self.sin_t = cos.to(device), sin.to(device)
+        # strip map of the merged cross-K/V launch of a compacted decoder: layer l's compact strip s -> l * (CH * 16) + original strip
+        self.smap_ckv_all = None
+        if any(L["smap_ckv"] is not None for L in self.dec_layers):
+            per_layer = d.cross_query_heads * 16
+            full = torch.arange(per_layer, dtype=torch.int32, device=device)
+            self.smap_ckv_all = torch.cat([(L["smap_ckv"] if L["smap_ckv"] is not None else full) + i * per_layer
+                                           for i, L in enumerate(self.dec_layers)]).to(torch.int32).contiguous()
+        self.flat = None
+        self.pack_flat()
 
-        perm = lay.rope_pair_perm(HEAD_DIM).to(device)
-        self.enc_emb = dev("encoder.embedding.weight").contiguous()
-        self.enc_layers = []
-        i32e = lambda t: t.to(device=device, dtype=torch.int32).contiguous()
+    def _dev(self, sd, name) -> torch.Tensor:
+        return sd[name].to(device=self.device, dtype=torch.float32)
+
+    def _i32(self, t) -> torch.Tensor:
+        return t.to(device=self.device, dtype=torch.int32).contiguous()
+
+    def _tile(self, w2d) -> TiledW:
+        t, kt, ns = _TILERS[self.weight_planes](w2d)
+        if w2d.numel() and self.weight_planes == 1:
+            err = (w2d - w2d.to(torch.bfloat16).to(w2d.dtype)).abs().max()
+            scale = w2d.abs().max()
+            if float(scale) > 0.0:
+                self.max_weight_rounding = max(self.max_weight_rounding, float(err / scale))
+        return TiledW(t, kt, ns, self.weight_planes)
+
+    @staticmethod
+    def _tile24(name, w2d) -> TiledW:
+        if w2d.shape[0] % 512:
+            raise hb.DiaHipError(f"sparse='2:4': {name}: K = {w2d.shape[0]} is not a multiple of 512")
+        if not is_2of4(w2d):
+            raise hb.DiaHipError(f"sparse='2:4': {name} is not 2:4 sparse (more than 2 non-zeros in a group of 4 consecutive K)")
+        return TiledW(*lay.tile_weight_24(w2d))
+
+    def _build_encoder(self, sd, compact: str):
+        e, device = self.cfg.model.encoder, self.device
         E, EH = e.n_embd, e.n_head
-        eplans = []
+        self.enc_emb = self._dev(sd, "encoder.embedding.weight").contiguous()
+        plans = []
         for i in range(e.n_layer):
             pl = cpt.plan_encoder_layer({k: v for k, v in sd.items() if k.startswith(f"encoder.layers.{i}.")},
                                         f"encoder.layers.{i}.", EH)
-            eplans.append(pl if (compact != "off" and cpt.enc_is_pruned(pl)) else None)
-        for i in range(e.n_layer):
+            plans.append(pl if (compact != "off" and cpt.enc_is_pruned(pl)) else None)
+        self.enc_layers = []
+        for i, P in enumerate(plans):
             p = f"encoder.layers.{i}."
-            P = eplans[i]
-            wq, wk, wv = (dev(p + f"self_attention.{n}_proj.weight").reshape(E, -1) for n in "qkv")
-            o = dev(p + "self_attention.o_proj.weight").reshape(-1, E)
-            wi3 = dev(p + "mlp.wi_fused.weight")
-            wo = dev(p + "mlp.wo.weight")
-            EL = dict(g_sa=dev(p + "pre_sa_norm.weight").contiguous(), g_mlp=dev(p + "post_sa_norm.weight").contiguous(),
-                      heads=EH, cmap_mlp=None, cmap_next=None)
-            nxt = eplans[i + 1] if i + 1 < e.n_layer else None
+            wq, wk, wv = (self._dev(sd, p + f"self_attention.{n}_proj.weight").reshape(E, -1) for n in "qkv")
+            o = self._dev(sd, p + "self_attention.o_proj.weight").reshape(-1, E)
+            wi3 = self._dev(sd, p + "mlp.wi_fused.weight")
+            wo = self._dev(sd, p + "mlp.wo.weight")
+            L = dict(g_sa=self._dev(sd, p + "pre_sa_norm.weight").contiguous(), g_mlp=self._dev(sd, p + "post_sa_norm.weight").contiguous(),
+                     heads=EH, cmap_mlp=None, cmap_next=None)
+            nxt = plans[i + 1] if i + 1 < e.n_layer else None
             if nxt is not None:
-                EL["cmap_next"] = i32e(cpt._cmap(nxt.keep_qkv))
+                L["cmap_next"] = self._i32(cpt._cmap(nxt.keep_qkv))
             if P is not None:
                 hc = P.live_heads.to(device).repeat_interleave(HEAD_DIM)            # live head columns
                 kq = P.keep_qkv.to(device)
                 wq, wk, wv = wq[kq][:, hc], wk[kq][:, hc], wv[kq][:, hc]
                 o = cpt.pad_rows(o[hc])
-                hid = cpt.pad_hidden_keep(P.live_hidden).to(device)
-                wi3 = torch.stack([cpt.take_cols_idx(wi3[:, 0, :], hid), cpt.take_cols_idx(wi3[:, 1, :], hid)], dim=1)
-                wi3 = wi3[P.keep_wi.to(device)]
-                wo_c = wo[hid.clamp(min=0)].clone()
-                wo_c[hid < 0] = 0
-                wo = wo_c
-                EL.update(heads=int(P.live_heads.sum()), cmap_mlp=i32e(cpt._cmap(P.keep_wi)))
-            EL.update(qkv=tile(torch.cat([wq, wk, wv], dim=1)), o=tile(o), wi=tile(lay.interleave_gate_up(wi3)), wo=tile(wo))
-            self.enc_layers.append(EL)
-        self.enc_cmap_first = i32e(cpt._cmap(eplans[0].keep_qkv)) if eplans and eplans[0] is not None else None
-        self.enc_compacted = any(pl is not None for pl in eplans)
-        self.enc_norm = dev("encoder.norm.weight").contiguous()
-        self.dec_emb = torch.stack([dev(f"decoder.embeddings.{c}.weight") for c in range(cfg.data.channels)]).contiguous()
-        self.dec_layers = []
+                wi3, wo = _compact_mlp(wi3, wo, P.live_hidden, P.keep_wi)
+                L.update(heads=int(P.live_heads.sum()), cmap_mlp=self._i32(cpt._cmap(P.keep_wi)))
+            L.update(qkv=self._tile(torch.cat([wq, wk, wv], dim=1)), o=self._tile(o), wi=self._tile(lay.interleave_gate_up(wi3)),
+                     wo=self._tile(wo))
+            self.enc_layers.append(L)
+        self.enc_cmap_first = self._i32(cpt._cmap(plans[0].keep_qkv)) if plans and plans[0] is not None else None
+        self.enc_compacted = any(pl is not None for pl in plans)
+        self.enc_norm = self._dev(sd, "encoder.norm.weight").contiguous()
+
+    def _build_decoder(self, sd, compact: str) -> Optional[torch.Tensor]:
+        """Returns the kept input rows of the logits head when compaction dropped some (None: all of them)."""
+        cfg, device = self.cfg, self.device
+        e, d = cfg.model.encoder, cfg.model.decoder
         D = d.n_embd
         QH, KVH, CH = d.gqa_query_heads, d.kv_heads, d.cross_query_heads
+        perm = lay.rope_pair_perm(HEAD_DIM).to(device)
+        self.dec_emb = torch.stack([self._dev(sd, f"decoder.embeddings.{c}.weight") for c in range(cfg.data.channels)]).contiguous()
         plans = []
         for i in range(d.n_layer):
             pl = cpt.plan_decoder_layer({k: v for k, v in sd.items() if k.startswith(f"decoder.layers.{i}.")},
                                         f"decoder.layers.{i}.", QH, KVH, CH)
             plans.append(pl if (compact != "off" and cpt.is_pruned(pl)) else None)
         keep_logits = cpt.pad_keep(cpt.nonzero_rows(sd["decoder.logits_dense.weight"].reshape(D, -1)))
-        logits_pruned = compact != "off" and not bool(keep_logits.all())
-        self.compacted = any(p is not None for p in plans) or logits_pruned or self.enc_compacted
-        if sparse == "2:4" and self.compacted:
+        if compact == "off" or bool(keep_logits.all()):
+            keep_logits = None
+        self.compacted = any(p is not None for p in plans) or keep_logits is not None or self.enc_compacted
+        if self.sparse == "2:4" and self.compacted:
             raise hb.DiaHipError("sparse='2:4': a compacted (structured-pruned) checkpoint has no 2:4 form; load it with compact='off' "
                                  "or prune with --prune-mode 2:4")
-
-        def tile24(name, w2d) -> TiledW:
-            if w2d.shape[0] % 512:
-                raise hb.DiaHipError(f"sparse='2:4': {name}: K = {w2d.shape[0]} is not a multiple of 512")
-            if not is_2of4(w2d):
-                raise hb.DiaHipError(f"sparse='2:4': {name} is not 2:4 sparse (more than 2 non-zeros in a group of 4 consecutive K)")
-            t, kt, ns = lay.tile_weight_24(w2d)
-            return TiledW(t, kt, ns)
-        i32 = lambda t: t.to(device=device, dtype=torch.int32).contiguous()
-        ones_d = torch.ones(D, dtype=torch.bool)
-
-        def next_keep(i):          # input order of what consumes layer i's wo output
-            if i + 1 < d.n_layer:
-                return plans[i + 1].keep_qkv if plans[i + 1] is not None else None
-            return keep_logits if logits_pruned else None
-
-        for i in range(d.n_layer):
+        i32 = self._i32
+        self.dec_layers = []
+        for i, P in enumerate(plans):
             p = f"decoder.layers.{i}."
-            P = plans[i]
-            wq, wk, wv = (dev(p + f"self_attention.{n}_proj.weight").reshape(D, -1) for n in "qkv")
-            qkv = torch.cat([wq, wk, wv], dim=1)
-            o = dev(p + "self_attention.o_proj.weight").reshape(-1, D)
-            cq = dev(p + "cross_attention.q_proj.weight").reshape(D, -1)
-            co = dev(p + "cross_attention.o_proj.weight").reshape(-1, D)
-            ck = dev(p + "cross_attention.k_proj.weight")[:, :, perm].reshape(e.n_embd, -1)
-            cv = dev(p + "cross_attention.v_proj.weight").reshape(e.n_embd, -1)
+            qkv = torch.cat([self._dev(sd, p + f"self_attention.{n}_proj.weight").reshape(D, -1) for n in "qkv"], dim=1)
+            o = self._dev(sd, p + "self_attention.o_proj.weight").reshape(-1, D)
+            cq = self._dev(sd, p + "cross_attention.q_proj.weight").reshape(D, -1)
+            co = self._dev(sd, p + "cross_attention.o_proj.weight").reshape(-1, D)
+            ck = self._dev(sd, p + "cross_attention.k_proj.weight")[:, :, perm].reshape(e.n_embd, -1)
+            cv = self._dev(sd, p + "cross_attention.v_proj.weight").reshape(e.n_embd, -1)
             ckv = torch.cat([ck, cv], dim=1)
-            wi3 = dev(p + "mlp.wi_fused.weight")
-            wo = dev(p + "mlp.wo.weight")
-            L = dict(g_sa=dev(p + "pre_sa_norm.weight").contiguous(), g_ca=dev(p + "pre_ca_norm.weight").contiguous(),
-                     g_mlp=dev(p + "pre_mlp_norm.weight").contiguous(),
+            wi3 = self._dev(sd, p + "mlp.wi_fused.weight")
+            wo = self._dev(sd, p + "mlp.wo.weight")
+            L = dict(g_sa=self._dev(sd, p + "pre_sa_norm.weight").contiguous(), g_ca=self._dev(sd, p + "pre_ca_norm.weight").contiguous(),
+                     g_mlp=self._dev(sd, p + "pre_mlp_norm.weight").contiguous(),
                      cmap_ca=None, cmap_mlp=None, cmap_next=None, smap_qkv=None, smap_cq=None, smap_ckv=None,
                      hmap_self=None, hmap_cross=None)
-            nk = next_keep(i)
+            if i + 1 < d.n_layer:          # input order of what consumes this layer's wo output
+                nk = plans[i + 1].keep_qkv if plans[i + 1] is not None else None
+            else:
+                nk = keep_logits
             if nk is not None:
                 L["cmap_next"] = i32(cpt._cmap(nk))
             if P is not None:
@@ -205,60 +291,42 @@ class DeviceWeights:
                 co = cpt.pad_rows(co[P.live_c_heads.to(device).repeat_interleave(128)])
                 s_ckv = cpt.strips_of_heads(P.live_c_heads, 0) + cpt.strips_of_heads(P.live_c_heads, CH * 128)
                 ckv = ckv[:, cols(s_ckv)]
-                hid = cpt.pad_hidden_keep(P.live_hidden).to(device)
-                wi3 = torch.stack([cpt.take_cols_idx(wi3[:, 0, :], hid), cpt.take_cols_idx(wi3[:, 1, :], hid)], dim=1)
-                wi3 = wi3[P.keep_wi.to(device)]
-                wo_c = wo[hid.clamp(min=0)].clone()
-                wo_c[hid < 0] = 0
-                wo = wo_c
+                wi3, wo = _compact_mlp(wi3, wo, P.live_hidden, P.keep_wi)
                 L.update(cmap_ca=i32(cpt._cmap(P.keep_cq)), cmap_mlp=i32(cpt._cmap(P.keep_wi)),
                          smap_qkv=i32(torch.tensor(s_qkv)), smap_cq=i32(torch.tensor(s_cq)), smap_ckv=i32(torch.tensor(s_ckv)),
                          hmap_self=i32(cpt.head_map(P.live_q_heads)), hmap_cross=i32(cpt.head_map(P.live_c_heads)))
-            L.update(qkv=tile(qkv), o=tile(o), cq=tile(cq), co=tile(co), ckv=tile(ckv),
-                     wi=tile(lay.interleave_gate_up(wi3)), wo=tile(wo))
-            for k_, w_ in (("qkv", qkv), ("o", o), ("cq", cq), ("co", co), ("wi", wi3), ("wo", wo)):
-                if sparse == "2:4":
-                    w2_ = lay.interleave_gate_up(w_) if k_ == "wi" else w_
-                    L[k_ + "24"] = tile24(f"decoder.layers.{i}.{k_}", w2_)
-                else:
-                    L[k_ + "24"] = None
+            mats = dict(qkv=qkv, o=o, cq=cq, co=co, wi=lay.interleave_gate_up(wi3), wo=wo)
+            L["ckv"] = self._tile(ckv)
+            for k in DEC_MATS:
+                L[k] = self._tile(mats[k])
+                L[k + "24"] = self._tile24(p + k, mats[k]) if self.sparse == "2:4" else None
             # experiment (knob wo_diag=1): wo once more in the diagonal layout (4-column groups: 256 workgroups with the whole K each)
             L["wo_diag"] = None
-            if (hb.get_tuning("wo_diag") == 1 and P is None and weight_planes == 1 and device.type == "cuda" and wo.shape[0] % 1024 == 0
+            if (hb.get_tuning("wo_diag") == 1 and P is None and self.weight_planes == 1 and device.type == "cuda" and wo.shape[0] % 1024 == 0
                     and wo.shape[0] <= 8192 and wo.shape[1] % 8 == 0 and nk is None):
                 L["wo_diag"] = lay.diag_tile_weight(wo)
             self.dec_layers.append(L)
         self.cmap_first = i32(cpt._cmap(plans[0].keep_qkv)) if plans[0] is not None else None
+        return keep_logits
+
+    def _build_seg(self, sd, seg: str):
+        """Ring arenas of the persistent MLP segments (experiment, seg="on"): Dia-1.6B-shaped dense decoders on a GPU only."""
+        d = self.cfg.model.decoder
+        D, QH, KVH, CH = d.n_embd, d.gqa_query_heads, d.kv_heads, d.cross_query_heads
         self.seg_layers: List[torch.Tensor] = []
-        nqkv = (QH + 2 * KVH) * HEAD_DIM
-        if (seg == "on" and device.type == "cuda" and weight_planes == 1 and not self.compacted and D == 2048 and d.n_hidden == 8192
-                and QH * HEAD_DIM == 2048 and CH * HEAD_DIM == 2048 and nqkv == 3072):
-            for i in range(d.n_layer):
-                p = f"decoder.layers.{i}."
-                wi3 = dev(p + "mlp.wi_fused.weight")
-                qn = None
-                if i + 1 < d.n_layer:
-                    pn = f"decoder.layers.{i + 1}."
-                    qn = torch.cat([dev(pn + f"self_attention.{n_}_proj.weight").reshape(D, -1) for n_ in "qkv"], dim=1)
-                self.seg_layers.append(lay.seg_ring(dev(p + "cross_attention.o_proj.weight").reshape(-1, D), wi3[:, 0, :], wi3[:, 1, :],
-                                                    dev(p + "mlp.wo.weight"), qn))
-                del wi3, qn
-        self.dec_norm = dev("decoder.norm.weight").contiguous()
-        lw = dev("decoder.logits_dense.weight").reshape(D, -1)
-        self.logits = tile(lw[keep_logits.to(device)] if logits_pruned else lw)
-        self.logits_cols = lw.shape[1]
-        self.logits24 = tile24("decoder.logits_dense", lw) if sparse == "2:4" else None
-        npos = max(cfg.data.audio_length, cfg.data.text_length) + 1
-        cos, sin = lay.rope_tables(npos, HEAD_DIM, m.rope_min_timescale, m.rope_max_timescale)
-        self.cos_t, self.sin_t = cos.to(device), sin.to(device)
-        # strip map of the merged cross-K/V launch of a compacted decoder: layer l's compact strip s -> l * (CH * 16) + original strip
-        self.smap_ckv_all = None
-        if any(L["smap_ckv"] is not None for L in self.dec_layers):
-            full = torch.arange(CH * 16, dtype=torch.int32, device=device)
-            self.smap_ckv_all = torch.cat([(L["smap_ckv"] if L["smap_ckv"] is not None else full) + i * CH * 16
-                                           for i, L in enumerate(self.dec_layers)]).to(torch.int32).contiguous()
-        self.flat = None
-        self.pack_flat()
+        if not (seg == "on" and self.device.type == "cuda" and self.weight_planes == 1 and not self.compacted and D == 2048
+                and d.n_hidden == 8192 and QH * HEAD_DIM == 2048 and CH * HEAD_DIM == 2048 and (QH + 2 * KVH) * HEAD_DIM == 3072):
+            return
+        for i in range(d.n_layer):
+            p = f"decoder.layers.{i}."
+            wi3 = self._dev(sd, p + "mlp.wi_fused.weight")
+            qn = None
+            if i + 1 < d.n_layer:
+                pn = f"decoder.layers.{i + 1}."
+                qn = torch.cat([self._dev(sd, pn + f"self_attention.{n_}_proj.weight").reshape(D, -1) for n_ in "qkv"], dim=1)
+            self.seg_layers.append(lay.seg_ring(self._dev(sd, p + "cross_attention.o_proj.weight").reshape(-1, D), wi3[:, 0, :], wi3[:, 1, :],
+                                                self._dev(sd, p + "mlp.wo.weight"), qn))
+            del wi3, qn
 
     def ckv_all(self) -> Optional[TiledW]:
         """The cross-K/V tile sets of every decoder layer as ONE weight of sum(ns) strips, when they are one bf16 tile set each with
@@ -284,9 +352,9 @@ class DeviceWeights:
             out += [L[k] for k in ("cmap_mlp", "cmap_next") if L[k] is not None]
         out += [self.enc_norm, self.dec_emb]
         for L in self.dec_layers:
-            out += [L["g_sa"], L["g_ca"], L["g_mlp"]] + [L[k].t for k in ("qkv", "o", "cq", "co", "wi", "wo")]
+            out += [L["g_sa"], L["g_ca"], L["g_mlp"]] + [L[k].t for k in DEC_MATS]
             out += [L[k] for k in ("cmap_ca", "cmap_mlp", "cmap_next", "smap_qkv", "smap_cq", "smap_ckv", "hmap_self", "hmap_cross", "wo_diag")
-                    if L.get(k) is not None]
+                    if L[k] is not None]
         # the cross-K/V projections of ALL layers back to back (whole KiB each, so the 256-byte slots leave no gaps): the prefill runs them
         # as ONE GEMM over their common input (ckv_all)
         out += [L["ckv"].t for L in self.dec_layers]
@@ -297,7 +365,7 @@ class DeviceWeights:
         out += self.seg_layers
         if self.sparse == "2:4":                    # the 2:4 streams (sparse="2:4"), after everything the dense model holds
             for L in self.dec_layers:
-                out += [L[k + "24"].t for k in ("qkv", "o", "cq", "co", "wi", "wo")]
+                out += [L[k + "24"].t for k in DEC_MATS]
             out.append(self.logits24.t)
         return out
 
@@ -344,7 +412,7 @@ class DeviceWeights:
             return L[k + "24"].nbytes if every else L[k].nbytes
         n = self.logits24.nbytes if every else self.logits.nbytes
         for L in self.dec_layers:
-            n += sum(w(L, k) for k in ("qkv", "o", "cq", "co", "wi", "wo"))
+            n += sum(w(L, k) for k in DEC_MATS)
         return n
 
 
@@ -416,7 +484,7 @@ class DecodeSession:
         t_ = hb.get_tuning("act_f32")
         self.act_f32 = int(t_ != 0)
         # persistent MLP segments (csrc/seg.hip, experiment): batch 1-2 on a model that carries the ring arenas, knob seg=1
-        self.seg = bool(self.R <= 4 and getattr(w, "seg_layers", None) and self.act_f32 and hb.get_tuning("seg") == 1)
+        self.seg = bool(self.R <= 4 and w.seg_layers and self.act_f32 and hb.get_tuning("seg") == 1)
         self.seg_ws = None
         if self.seg:
             self.seg_ws = torch.zeros(int(hb.lib().dia_seg_workspace_bytes()), dtype=torch.uint8, device=dev)
@@ -446,13 +514,13 @@ class DecodeSession:
         self.attn_scratch = z(max(nsc, 1))
         self.attn_tickets = z(max(self.R * d.kv_heads, B * d.cross_query_heads), dt=torch.int32)
         # split-K slabs: up to 4 splits of wo (one or two m-tiles); with 17..32 rows every GEMM splits K in two
-        ns_max = max([self.D // 16, w.logits.ns] + [DL[k].ns for DL in w.dec_layers for k in ("qkv", "o", "cq", "co", "wi", "wo")])
+        ns_max = max([self.D // 16, w.logits.ns] + [DL[k].ns for DL in w.dec_layers for k in DEC_MATS])
         n_scr = max((self.D // 16) * 4 * 512, ns_max * 2 * 512 if 16 < self.R <= 32 else 0)
         if 16 < self.R <= 128:   # 2..8 m-tiles: wo splits K four ways for every m-tile (k_gemm16 over gridDim.z)
             n_scr = max(n_scr, 2 * -(-self.R // 32) * (self.D // 16) * 4 * 256)       # (whole PAIRS of m-tiles: k_gemm2t hands two tiles over together)
         if 16 < self.R <= 32:    # k_gemm_blk32: column blocks x K ranges of >= 8 k-tiles, 512 floats per strip and range
             n_scr = max([n_scr, w.logits.ns * -(-w.logits.kt // 8) * 512] +
-                        [DL[k].ns * -(-DL[k].kt // 8) * 512 for DL in w.dec_layers for k in ("qkv", "o", "cq", "co", "wi", "wo")])
+                        [DL[k].ns * -(-DL[k].kt // 8) * 512 for DL in w.dec_layers for k in DEC_MATS])
         self.sk_scratch = z(n_scr)
         self.sk_tickets = z(max(ns_max, 8 * (self.D // 16)), dt=torch.int32)
         self.mlp_barrier = z(2, dt=torch.int32)          # dia_mlp_fused: arrivals, error flag
@@ -532,7 +600,7 @@ class DecodeSession:
         e.tokens, e.cur = hb.ptr(self.tokens), hb.ptr(self.cur)
         e.B, e.T, e.C, e.V, e.D = self.B, self.T, self.C, self.V, self.D
         e.emb, e.g, e.x = hb.ptr(self.w.dec_emb), hb.ptr(self.w.dec_layers[0]["g_sa"]), hb.ptr(self.x)
-        e.P, e.p_plane_stride, e.p_ktiles = hb.ptr(self.planes_x), self.planes_x[0].numel(), self.xkt
+        e.P, e.p_plane_stride, e.p_ktiles = _plane_set(self.planes_x, self.xkt)
         e.ssq_ld, e.ssq = self.rows_pad, hb.ptr(self.ssq)
         e.cmap = hb.ptr(self.w.cmap_first)
         e.act_f32 = self.act_f32
@@ -560,19 +628,18 @@ class DecodeSession:
         self._layers = (hb.DecLayer * n)()
         for i, L in enumerate(w.dec_layers):
             dl = self._layers[i]
-            for key, f in (("qkv", "qkv"), ("o", "o"), ("cq", "cq"), ("co", "co"), ("wi", "wi"), ("wo", "wo")):
-                setattr(dl, "w_" + f, hb.ptr(L[key].t))
-                setattr(dl, "kt_" + f, L[key].kt)
-                setattr(dl, "ns_" + f, L[key].ns)
+            for f in DEC_MATS:
+                setattr(dl, "w_" + f, hb.ptr(L[f].t))
+                setattr(dl, "kt_" + f, L[f].kt)
+                setattr(dl, "ns_" + f, L[f].ns)
+                sp = L[f + "24"]                                            # 2:4 stream (sparse="2:4"), NULL = dense only
+                setattr(dl, "w_" + f + "_24", hb.ptr(sp.t) if sp is not None else None)
             dl.g_sa, dl.g_ca, dl.g_mlp = hb.ptr(L["g_sa"]), hb.ptr(L["g_ca"]), hb.ptr(L["g_mlp"])
             dl.k_self, dl.v_self = hb.ptr(self.k_self[i]), hb.ptr(self.v_self[i])
             dl.k_cross, dl.v_cross = hb.ptr(self.k_cross[i]), hb.ptr(self.v_cross[i])
             for f in ("cmap_ca", "cmap_mlp", "cmap_next", "smap_qkv", "smap_cq", "hmap_self", "hmap_cross"):
                 setattr(dl, f, hb.ptr(L[f]))
-            dl.w_wo_diag = hb.ptr(L.get("wo_diag"))
-            for f in ("qkv", "o", "cq", "co", "wi", "wo"):                  # 2:4 streams (sparse="2:4"), NULL = dense only
-                sp = L.get(f + "24")
-                setattr(dl, "w_" + f + "_24", hb.ptr(sp.t) if sp is not None else None)
+            dl.w_wo_diag = hb.ptr(L["wo_diag"])
         ed = hb.EngineDesc()
         ed.n_layer, ed.D, ed.F = n, self.D, self.F
         ed.q_heads, ed.kv_heads, ed.cq_heads = d.gqa_query_heads, d.kv_heads, d.cross_query_heads
@@ -583,7 +650,7 @@ class DecodeSession:
         ed.eps = float(self.cfg.model.normalization_layer_epsilon)
         ed.layers = C.cast(self._layers, C.POINTER(hb.DecLayer))
         ed.w_logits, ed.kt_logits, ed.ns_logits = hb.ptr(w.logits.t), w.logits.kt, w.logits.ns
-        ed.w_logits_24 = hb.ptr(w.logits24.t) if getattr(w, "logits24", None) is not None else None
+        ed.w_logits_24 = hb.ptr(w.logits24.t) if w.logits24 is not None else None
         ed.g_final = hb.ptr(w.dec_norm)
         ed.x, ed.planes_x, ed.planes_a, ed.planes_h = hb.ptr(self.x), hb.ptr(self.planes_x), hb.ptr(self.planes_a), hb.ptr(self.planes_h)
         ed.ssq, ed.qkv, ed.qc, ed.logits = hb.ptr(self.ssq), hb.ptr(self.qkv), hb.ptr(self.qc), hb.ptr(self.logits)
@@ -633,10 +700,7 @@ class DecodeSession:
         st = C.c_void_p(self.stream.cuda_stream)
         E, Fe = e.n_embd, e.n_hidden
         eps = float(cfg.model.normalization_layer_epsilon)
-        offs, tot = [], 0
-        for Lb in self.lens:
-            offs.append(tot)
-            tot += _ceil(Lb, 32)                     # whole 32-key blocks per utterance (blocked V planes)
+        offs, tot, row_utt = pack_segments(self.lens)         # whole 32-key blocks per utterance (blocked V planes)
         self.enc_out = [None] * self.B
         with torch.cuda.stream(self.stream):
             if tot > 0:
@@ -644,9 +708,8 @@ class DecodeSession:
                 Lmax = _ceil(max(self.lens), 16)
                 Hmax = max(EL["heads"] for EL in w.enc_layers)
                 ekt = E // 32
-                kdiv = 2 if w.weight_planes == 2 else 1                      # (two-plane weights: kt counts hi and lo tiles)
-                akt = max(max(1, Hmax * HEAD_DIM // 32), max(EL["o"].kt // kdiv for EL in w.enc_layers))   # o rows may be zero-padded
-                hkt = max(EL["wo"].kt // kdiv for EL in w.enc_layers)         # (compacted) hidden width in k-tiles
+                akt = max(max(1, Hmax * HEAD_DIM // 32), max(EL["o"].a_kt for EL in w.enc_layers))   # o rows may be zero-padded
+                hkt = max(EL["wo"].a_kt for EL in w.enc_layers)               # (compacted) hidden width in k-tiles
                 # every buffer of the pass is a view of ONE zero-filled allocation (one memset instead of nine), every small integer
                 # table one host array (one copy instead of 3 + B): the chain is ~80 launches, each of these was one more
                 nq_max = 3 * Hmax * HEAD_DIM
@@ -667,9 +730,7 @@ class DecodeSession:
                     id_off[b] = n_ids
                     n_ids += _ceil(self.lens[b], 4)                # (16-byte aligned runs)
                 tab = np.zeros((Mp + 2 * _ceil(self.B, 4) + n_ids,), dtype=np.int32)
-                tab[:Mp] = -1
-                for b, Lb in enumerate(self.lens):
-                    tab[offs[b]: offs[b] + Lb] = b
+                tab[:Mp] = row_utt
                 o_so, o_sl = Mp, Mp + _ceil(self.B, 4)
                 tab[o_so: o_so + self.B] = offs
                 tab[o_sl: o_sl + self.B] = self.lens
@@ -693,36 +754,11 @@ class DecodeSession:
                                               rows(x, b, E), planes_at(px, b, ekt), px[0].numel(), ekt,
                                               ssq.data_ptr() + offs[b] * 4, Mp, hb.ptr(w.enc_cmap_first), st), "dia_embed_text")
 
-                def gemm(A, a_kt, W: TiledW, epi, *, M=Mp, a_ptr=None, ssq_ptr=None, ssq_in=False, out=None, ldo=0, gnext=None,
-                         P=None, p_kt=0, ssq_out=False, kv=None, strip_map=None, row_map=False, cmap=None, sk=0, kv_layers=None):
-                    g = hb.GemmArgs()
-                    g.A, g.a_plane_stride, g.a_ktiles, g.M = (a_ptr if a_ptr is not None else hb.ptr(A)), A[0].numel(), a_kt, M
-                    g.W, g.KT, g.nstrips, g.epi = hb.ptr(W.t), W.kt, W.ns, epi
-                    g.w_planes = w.weight_planes
-                    sp = ssq_ptr if ssq_ptr is not None else hb.ptr(ssq)
-                    if ssq_in:
-                        g.ssq_in, g.ssq_in_n, g.inv_d, g.eps = sp, E // 16, 1.0 / E, eps
-                    g.ssq_ld = Mp
-                    g.out, g.ldo = hb.ptr(out), ldo
-                    g.gnext = hb.ptr(gnext)
-                    if P is not None:
-                        g.P, g.p_plane_stride, g.p_ktiles = hb.ptr(P), P[0].numel(), p_kt
-                    if ssq_out:
-                        g.ssq_out = sp
-                    g.strip_map = hb.ptr(strip_map)
-                    g.cmap = hb.ptr(cmap)
-                    g.kv_vblocked = self.v_blocked if kv is not None else 0
-                    if kv is not None:
-                        g.kc, g.vc, g.kv_dtype, g.kv_heads, g.kv_cap, g.kv_batch_index = kv
-                        g.kv_plane_stride = self.kv_plane_cross
-                        g.cos_t, g.sin_t = hb.ptr(w.cos_t), hb.ptr(w.sin_t)
-                        if kv_layers is not None:
-                            g.kv_layer_strips, g.kv_layer_stride = kv_layers
-                    if row_map:
-                        g.row_b, g.seg_off = hb.ptr(row_b), hb.ptr(seg_off)
-                    if sk > 1:      # split-K over workgroups through the session's slab scratch (short prompts: the z-form needs K <= 2048 per workgroup)
-                        g.sk, g.sk_scratch, g.sk_tickets, g.sk_scratch_floats = sk, hb.ptr(self.sk_scratch), hb.ptr(self.sk_tickets), self.sk_scratch.numel()
-                    hb.check(L.dia_gemm(C.byref(g), st), "dia_gemm")
+                gemm = partial(_launch_gemm, st, M=Mp, ssq=ssq, ssq_ld=Mp, width=E, eps=eps, w_planes=w.weight_planes)
+
+                def cross_kv(kc, vc):               # the cross-K/V epilogue writes every utterance's rows of these caches (row_b / seg_off)
+                    return (hb.ptr(kc), hb.ptr(vc), self.kv_code, d.cross_query_heads, self.S, 0, self.v_blocked, self.kv_plane_cross,
+                            hb.ptr(w.cos_t), hb.ptr(w.sin_t))
 
                 for i, EL in enumerate(w.enc_layers):
                     Hl = EL["heads"]                 # live heads of this layer (all of them unless the checkpoint was pruned)
@@ -734,7 +770,7 @@ class DecodeSession:
                         ea_.heads, ea_.rows = Hl, Mp
                         ea_.row_b, ea_.seg_off, ea_.seg_len = hb.ptr(row_b), hb.ptr(seg_off), hb.ptr(seg_len)
                         ea_.cos_t, ea_.sin_t, ea_.kp, ea_.vp = hb.ptr(w.cos_t), hb.ptr(w.sin_t), hb.ptr(kp), hb.ptr(vp)
-                        ea_.P, ea_.p_plane_stride, ea_.p_ktiles = hb.ptr(pa), pa[0].numel(), akt
+                        ea_.P, ea_.p_plane_stride, ea_.p_ktiles = _plane_set(pa, akt)
                         hb.check(L.dia_enc_attn(C.byref(ea_), st), "dia_enc_attn")
                         gemm(pa, akt, EL["o"], hb.EPI_RESID_EMIT, out=x, ldo=E, gnext=EL["g_mlp"], P=px, p_kt=ekt, ssq_out=True,
                              cmap=EL["cmap_mlp"])
@@ -744,24 +780,22 @@ class DecodeSession:
                     gnext = w.enc_layers[i + 1]["g_sa"] if i + 1 < len(w.enc_layers) else w.enc_norm
                     # 17..128 rows: wo (K = 4096) as two K halves per strip, so that it rides the z-form of the 16-row kernel instead
                     # of the generic one (whose 4-m-tile form spills)
-                    wo_sk = 0
+                    wo_sk = None
                     kt_wo, ns_wo = EL["wo"].kt, EL["wo"].ns
                     if (16 < Mp <= 128 and kt_wo % 16 == 0 and kt_wo // 2 <= 64 and w.weight_planes == 1 and EL["cmap_next"] is None
                             and self.sk_scratch.numel() >= mt * ns_wo * 2 * 256 and self.sk_tickets.numel() >= mt * ns_wo):
-                        wo_sk = 2
+                        wo_sk = (2, self.sk_scratch, self.sk_tickets)
                     gemm(ph, hkt, EL["wo"], hb.EPI_RESID_EMIT, out=x, ldo=E, gnext=gnext, P=px, p_kt=ekt, ssq_out=True,
                          cmap=EL["cmap_next"], sk=wo_sk)
                 # px now holds planes(x * encoder.norm.weight); ssq the row sums of squares of x
                 ckv_all = w.ckv_all() if hb.get_tuning("ckv_merge") != 0 else None
                 if ckv_all is not None:             # ONE launch for the 18 layers: their input is the same (18 x 13.8 -> 1 x ~100 us at 98 rows)
-                    gemm(px, ekt, ckv_all, hb.EPI_CROSSKV, ssq_in=True,
-                         kv=(hb.ptr(self.k_cross_all), hb.ptr(self.v_cross_all), self.kv_code, d.cross_query_heads, self.S, 0),
-                         strip_map=w.smap_ckv_all, row_map=True, kv_layers=(d.cross_query_heads * 16, self.k_cross[0].numel()))
+                    gemm(px, ekt, ckv_all, hb.EPI_CROSSKV, ssq_in=True, kv=cross_kv(self.k_cross_all, self.v_cross_all),
+                         strip_map=w.smap_ckv_all, row_map=(row_b, seg_off), kv_layers=(d.cross_query_heads * 16, self.k_cross[0].numel()))
                 else:
                     for i, DL in enumerate(w.dec_layers):
-                        gemm(px, ekt, DL["ckv"], hb.EPI_CROSSKV, ssq_in=True,
-                             kv=(hb.ptr(self.k_cross[i]), hb.ptr(self.v_cross[i]), self.kv_code, d.cross_query_heads, self.S, 0),
-                             strip_map=DL["smap_ckv"], row_map=True)
+                        gemm(px, ekt, DL["ckv"], hb.EPI_CROSSKV, ssq_in=True, kv=cross_kv(self.k_cross[i], self.v_cross[i]),
+                             strip_map=DL["smap_ckv"], row_map=(row_b, seg_off))
                 if keep_encoder_out:
                     for b in live:
                         Lb, o = self.lens[b], offs[b]
@@ -795,14 +829,8 @@ class DecodeSession:
         for b, fs in enumerate(self.first_steps):
             if fs > 2:                              # rows 0..fs-2 are prefilled; fs == 2 (one frame) is left to the replay path
                 segs += [(2 * b, fs - 1), (2 * b + 1, fs - 1)]
-        offs, tot = [], 0
-        for _, n in segs:
-            offs.append(tot)
-            tot += _ceil(n, 32)
-        Mp, mt = tot, tot // 16
-        rs = np.full((Mp,), -1, dtype=np.int32)
-        for i, (_, n) in enumerate(segs):
-            rs[offs[i]: offs[i] + n] = i
+        offs, Mp, rs = pack_segments([n for _, n in segs])
+        mt = Mp // 16
         i32 = lambda a: torch.tensor(a, dtype=torch.int32, device=dev)
         row_seg = torch.from_numpy(rs).to(dev)
         seg_off, seg_len, seg_row = i32(offs), i32([n for _, n in segs]), i32([r for r, _ in segs])
@@ -819,25 +847,13 @@ class DecodeSession:
             a.cos_t, a.sin_t = hb.ptr(w.cos_t), hb.ptr(w.sin_t)
             return a
 
-        def gemm(A, a_kt, W: TiledW, epi, *, ssq_in=False, out=None, ldo=0, gnext=None, P=None, p_kt=0, ssq_out=False):
-            g = hb.GemmArgs()
-            g.A, g.a_plane_stride, g.a_ktiles, g.M = hb.ptr(A), A[0].numel(), a_kt, Mp
-            g.W, g.KT, g.nstrips, g.epi = hb.ptr(W.t), W.kt, W.ns, epi
-            g.w_planes = self.w.weight_planes
-            if ssq_in:
-                g.ssq_in, g.ssq_in_n, g.inv_d, g.eps = hb.ptr(ssq), D // 16, 1.0 / D, eps
-            g.ssq_ld = Mp
-            g.out, g.ldo, g.gnext = hb.ptr(out), ldo, hb.ptr(gnext)
-            if P is not None:
-                g.P, g.p_plane_stride, g.p_ktiles = hb.ptr(P), P[0].numel(), p_kt
-            if ssq_out:
-                g.ssq_out = hb.ptr(ssq)
-            hb.check(L.dia_gemm(C.byref(g), st), "dia_gemm")
+        gemm = partial(_launch_gemm, st, M=Mp, ssq=ssq, ssq_ld=Mp, width=D, eps=eps, w_planes=w.weight_planes)
 
         a = pargs()
         a.tokens, a.T, a.C, a.V, a.D = hb.ptr(self.tokens), self.T, self.C, self.V, D
         a.emb, a.g, a.x = hb.ptr(w.dec_emb), hb.ptr(w.dec_layers[0]["g_sa"]), hb.ptr(x)
-        a.P, a.p_plane_stride, a.p_ktiles, a.ssq, a.ssq_ld = hb.ptr(px), px[0].numel(), xkt, hb.ptr(ssq), Mp
+        a.P, a.p_plane_stride, a.p_ktiles = _plane_set(px, xkt)
+        a.ssq, a.ssq_ld = hb.ptr(ssq), Mp
         hb.check(L.dia_dec_prefill_embed(C.byref(a), st), "dia_dec_prefill_embed")
         for i, DL in enumerate(w.dec_layers):
             gemm(px, xkt, DL["qkv"], hb.EPI_SCALE_STORE, ssq_in=True, out=qkv, ldo=self.nqkv)
@@ -845,7 +861,7 @@ class DecodeSession:
             a.q, a.ldq, a.q_off, a.k_off, a.v_off = hb.ptr(qkv), self.nqkv, 0, QH * HEAD_DIM, (QH + KVH) * HEAD_DIM
             a.q_heads, a.kv_heads, a.kv_cap, a.causal = QH, KVH, self.T, 1
             a.kc, a.vc = hb.ptr(self.k_self[i]), hb.ptr(self.v_self[i])
-            a.P, a.p_plane_stride, a.p_ktiles = hb.ptr(pa), pa[0].numel(), akt
+            a.P, a.p_plane_stride, a.p_ktiles = _plane_set(pa, akt)
             hb.check(L.dia_dec_prefill_kv(C.byref(a), st), "dia_dec_prefill_kv")
             hb.check(L.dia_dec_prefill_attn(C.byref(a), st), "dia_dec_prefill_attn(self)")
             gemm(pa, akt, DL["o"], hb.EPI_RESID_EMIT, out=x, ldo=D, gnext=DL["g_ca"], P=px, p_kt=xkt, ssq_out=True)
@@ -854,7 +870,7 @@ class DecodeSession:
             a.q, a.ldq, a.q_off = hb.ptr(qc), CH * HEAD_DIM, 0
             a.q_heads, a.kv_heads, a.kv_cap, a.causal = CH, CH, self.S, 0
             a.kc, a.vc, a.text_len = hb.ptr(self.k_cross[i]), hb.ptr(self.v_cross[i]), hb.ptr(self.text_len)
-            a.P, a.p_plane_stride, a.p_ktiles = hb.ptr(pa), pa[0].numel(), akt
+            a.P, a.p_plane_stride, a.p_ktiles = _plane_set(pa, akt)
             hb.check(L.dia_dec_prefill_attn(C.byref(a), st), "dia_dec_prefill_attn(cross)")
             gemm(pa, akt, DL["co"], hb.EPI_RESID_EMIT, out=x, ldo=D, gnext=DL["g_mlp"], P=px, p_kt=xkt, ssq_out=True)
             gemm(px, xkt, DL["wi"], hb.EPI_SWIGLU_EMIT, ssq_in=True, P=ph, p_kt=hkt)
@@ -895,12 +911,6 @@ class DecodeSession:
         hb.check(hb.lib().dia_engine_decode(self._engine, int(n_steps), int(bool(use_graph))), "dia_engine_decode")
         self._issued += int(n_steps)
 
-    def set_prefetch(self, lookahead: int):
-        hb.check(hb.lib().dia_engine_set_prefetch(self._engine, int(lookahead)), "dia_engine_set_prefetch")
-
-    def step_logits_only(self):
-        hb.check(hb.lib().dia_engine_step_logits_only(self._engine), "dia_engine_step_logits_only")
-
     def profile_step(self) -> np.ndarray:
         """per-launch milliseconds of one eager decode step (HIP events on the engine's stream)."""
         n = hb.lib().dia_engine_launches_per_step(self._engine)
@@ -932,75 +942,6 @@ class DecodeSession:
         self.last_kernel_names = [hb.lib().dia_timed_kernel_name(i).decode() for i in range(got)]
         self.last_intervals_ms = np.array(ivl[:got], dtype=np.float64)      # end of launch i-1 -> end of launch i
         return np.array(buf[:got], dtype=np.float64)
-
-    def time_wi_launches(self, reps: int = 5) -> float:
-        """Average seconds per launch of the dominant kernel — the wi_fused GEMV with SwiGLU epilogue —
-        each launch bracketed by dispatch-level HIP start/stop events on the engine's stream
-        (hipExtLaunchKernelGGL), cycling through every layer's matrix (1.2 GB, HBM-cold like in a real
-        step) with exactly the arguments the engine uses.  Outputs go to planes_h, which the next step overwrites."""
-        L = hb.lib()
-        st = C.c_void_p(self.stream.cuda_stream)
-        args = []
-        for DL in self.w.dec_layers:
-            g = hb.GemmArgs()
-            g.A, g.a_plane_stride, g.a_ktiles, g.M = hb.ptr(self.planes_x), self.planes_x[0].numel(), self.xkt, self.R
-            g.W, g.KT, g.nstrips, g.epi = hb.ptr(DL["wi"].t), DL["wi"].kt, DL["wi"].ns, hb.EPI_SWIGLU_EMIT
-            g.ssq_in, g.ssq_in_n, g.ssq_ld = hb.ptr(self.ssq), self.D // 16, self.rows_pad
-            g.inv_d, g.eps = 1.0 / self.D, float(self.cfg.model.normalization_layer_epsilon)
-            g.P, g.p_plane_stride, g.p_ktiles = hb.ptr(self.planes_h), self.planes_h[0].numel(), self.hkt
-            g.act_f32 = 3 * self.act_f32             # as in the step
-            g.w_planes = self.w.weight_planes
-            args.append(g)
-        for g in args:                                    # warm
-            hb.check(L.dia_gemm(C.byref(g), st), "dia_gemm(wi)")
-        self.stream.synchronize()
-        ms = C.c_float()
-        tot = 0.0
-        for _ in range(reps):
-            for g in args:
-                hb.check(L.dia_gemm_timed(C.byref(g), st, C.byref(ms)), "dia_gemm_timed(wi)")
-                tot += ms.value
-        return tot * 1e-3 / (reps * len(args))
-
-    def mlp_fused(self) -> bool:
-        return bool(hb.lib().dia_engine_mlp_fused(self._engine))
-
-    def time_mlp_launches(self, reps: int = 5) -> float:
-        """Average seconds per launch of the fused MLP kernel (wi + wo, batch 1), dispatch-level events, cycling
-        through every layer's matrices with the engine's own arguments (outputs are scratch: x is restored)."""
-        L = hb.lib()
-        st = C.c_void_p(self.stream.cuda_stream)
-        x_keep = self.x.clone()
-        pairs = []
-        for i, DL in enumerate(self.w.dec_layers):
-            a = hb.GemmArgs()
-            a.A, a.a_plane_stride, a.a_ktiles, a.M = hb.ptr(self.planes_x), self.planes_x[0].numel(), self.xkt, self.R
-            a.W, a.KT, a.nstrips, a.epi = hb.ptr(DL["wi"].t), DL["wi"].kt, DL["wi"].ns, hb.EPI_SWIGLU_EMIT
-            a.ssq_in, a.ssq_in_n, a.ssq_ld = hb.ptr(self.ssq), self.D // 16, self.rows_pad
-            a.inv_d, a.eps = 1.0 / self.D, float(self.cfg.model.normalization_layer_epsilon)
-            a.P, a.p_plane_stride, a.p_ktiles = hb.ptr(self.planes_h), self.planes_h[0].numel(), self.hkt
-            a.w_planes = self.w.weight_planes
-            b = hb.GemmArgs()
-            b.A, b.a_plane_stride, b.a_ktiles, b.M = hb.ptr(self.planes_h), self.planes_h[0].numel(), self.hkt, self.R
-            b.W, b.KT, b.nstrips, b.epi = hb.ptr(DL["wo"].t), DL["wo"].kt, DL["wo"].ns, hb.EPI_RESID_EMIT
-            b.ssq_ld, b.out, b.ldo = self.rows_pad, hb.ptr(self.x), self.D
-            b.gnext = hb.ptr(self.w.dec_layers[i + 1]["g_sa"] if i + 1 < len(self.w.dec_layers) else self.w.dec_norm)
-            b.P, b.p_plane_stride, b.p_ktiles, b.ssq_out = hb.ptr(self.planes_x), self.planes_x[0].numel(), self.xkt, hb.ptr(self.ssq)
-            b.sk_scratch, b.sk_tickets, b.sk = hb.ptr(self.sk_scratch), hb.ptr(self.sk_tickets), 2
-            b.w_planes = self.w.weight_planes
-            pairs.append((a, b))
-        bar = hb.ptr(self.mlp_barrier)
-        for a, b in pairs:
-            hb.check(L.dia_mlp_fused(C.byref(a), C.byref(b), bar, st), "dia_mlp_fused")
-        self.stream.synchronize()
-        ms = C.c_float()
-        tot = 0.0
-        for _ in range(reps):
-            for a, b in pairs:
-                hb.check(L.dia_mlp_fused_timed(C.byref(a), C.byref(b), bar, st, C.byref(ms)), "dia_mlp_fused_timed")
-                tot += ms.value
-        self.x.copy_(x_keep)
-        return tot * 1e-3 / (reps * len(pairs))
 
     def sync(self):
         self.stream.synchronize()

@@ -87,6 +87,20 @@ def test_weight_tensor_inventory_is_complete():
     assert z.flat.numel() == w.flat.numel()
 
 
+def test_arena_signature_needs_every_layout_switch():
+    """An object that lacks one of the switches deciding the arena's layout is an error, not "switch off": a default
+    there would let a broadcast through between arenas that differ."""
+    sys.path.insert(0, os.path.join(ROOT, "dia-tts-prune_amd"))
+    from types import SimpleNamespace
+    from dia_hip import dist as D
+
+    full = dict(flat=torch.zeros(512, dtype=torch.uint8), compacted=False, weight_planes=2, sparse="2:4")
+    assert D._arena_signature(SimpleNamespace(**full)) == [512, 0, 2, 1]
+    for missing in ("compacted", "weight_planes", "sparse"):
+        with pytest.raises(AttributeError, match=missing):
+            D._arena_signature(SimpleNamespace(**{k: v for k, v in full.items() if k != missing}))
+
+
 def _worker_model(rank, world, port, q):
     """rank 0 holds the model, the other ranks receive it in ONE broadcast of the flat arena; then 5 utterances are
     sharded u -> u mod world, every rank decodes its own (the CPU oracle on the tiny config stands in for the HIP session)

@@ -80,7 +80,7 @@ os.environ.setdefault("MASTER_ADDR", "127.0.0.1"); os.environ.setdefault("MASTER
 dev = torch.device("cuda", 0); torch.cuda.set_device(0)
 dist.init_process_group("nccl", rank=0, world_size=1, device_id=dev)
 class W: pass
-w = W(); w.flat = torch.arange(1 << 20, dtype=torch.uint8, device=dev); w.compacted = False; w.weight_planes = 1
+w = W(); w.flat = torch.arange(1 << 20, dtype=torch.uint8, device=dev); w.compacted = False; w.weight_planes = 1; w.sparse = "off"
 n = D.broadcast_weights(w, src=0)
 assert n == w.flat.numel()
 bufs = [torch.full((5 + u, 9), u, dtype=torch.int32, device=dev) for u in range(3)]

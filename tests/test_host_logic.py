@@ -198,6 +198,24 @@ def test_compaction_plan_from_zeros():
     assert not cpt.is_pruned(dense)
 
 
+def test_pack_segments():
+    """engine.pack_segments: every segment starts on a 32-row boundary, the runs follow each other without gaps, every row of a
+    segment maps to it and every padding row to -1"""
+    from dia_hip.engine import pack_segments
+    offs, tot, rows = pack_segments([])
+    assert offs == [] and tot == 0 and rows.shape == (0,) and rows.dtype == np.int32
+    for lens in ([0], [5], [31, 32, 33], [64, 0, 1], [0, 0], [40, 95, 96, 97, 7]):
+        offs, tot, rows = pack_segments(lens)
+        assert len(offs) == len(lens) and all(o % 32 == 0 for o in offs)
+        assert tot == sum((n + 31) // 32 * 32 for n in lens) and rows.shape == (tot,) and rows.dtype == np.int32
+        want = np.full((tot,), -1, dtype=np.int32)
+        for i, n in enumerate(lens):
+            assert offs[i] == sum((m + 31) // 32 * 32 for m in lens[:i])
+            want[offs[i]: offs[i] + n] = i
+        assert np.array_equal(rows, want)
+        assert int((rows >= 0).sum()) == sum(lens)
+
+
 def test_cross_kv_tile_sets_are_one_weight_for_the_prefill():
     """DeviceWeights.ckv_all(): the cross-K/V tile sets of all decoder layers sit back to back in the arena and are handed to the prefill as ONE
     weight (dia_gemm_args.kv_layer_strips / kv_layer_stride); a compacted decoder brings the strip map of that merged launch; three-plane
