@@ -60,6 +60,9 @@ def build_parser() -> argparse.ArgumentParser:
     g.add_argument("--sparse-weights", type=str, default="off", choices=["off", "2:4"],
                    help="2:4 = the checkpoint is 2:4-pruned (offline_prune.py --prune-mode 2:4): batch 1-2 decode steps stream its "
                         "decoder matrices in the compressed 2:4 form (sparse MFMA); off = dense tiles only")
+    g.add_argument("--weight-format", type=str, default="bf16", choices=["bf16", "mxfp8"],
+                   help="mxfp8 = the checkpoint is MXFP8-quantised (offline_quantize.py): batch 1-8 decode steps stream its decoder "
+                        "matrices as e4m3 elements + block scales (half the weight bytes); bf16 = dense tiles only")
     g.add_argument("--verbose", action="store_true", help="report prefill and generation timing")
     return p
 
@@ -80,6 +83,7 @@ def main(argv=None) -> int:
 
     Dia.fp32_weights = args.fp32_weights
     Dia.sparse_weights = args.sparse_weights
+    Dia.weight_format = args.weight_format
     if args.seed is not None:
         set_seed(args.seed)
         print(f"Using seed: {args.seed}")

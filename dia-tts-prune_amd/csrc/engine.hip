@@ -51,6 +51,18 @@ static inline void mark(dia_engine* e, int i) {
   }
 }
 
+// MXFP8 default policy (DESIGN.md "MXFP8 weight stream"): a launch class streams MXFP8 at a row range only where its in-step time
+// was below the dense launch's in every repetition of the A/B (profiles/r05_mxfp8_speed.txt): wi, wo and the logits head at
+// <= 4 rows, wi and the logits head at 5..16 rows.  The 128..192-strip projections are bound by their fixed cost and lost
+// (+1..6 %), wo at 5..16 rows lost to the dense strip-pair split-K form (+1..4 %)
+constexpr int MXFP8_DEFAULT = 0x5070;
+extern "C" int dia_mxfp8_classes(int rows) {
+  if (rows <= 0 || rows > 16) return 0;
+  const int knob = dia_tune(DIA_TUNE_MXFP8);
+  const int mask = knob >= 0 ? knob : MXFP8_DEFAULT;
+  return (rows <= 4 ? mask : mask >> 8) & 0x7f;
+}
+
 static int enqueue_step(dia_engine* e, bool with_sampler) {
   const dia_engine_desc& d = e->d;
   void* st = (void*)e->stream;
@@ -88,6 +100,20 @@ static int enqueue_step(dia_engine* e, bool with_sampler) {
     g.sk = sk;
     if (sk == 1) { g.sk_scratch = nullptr; g.sk_tickets = nullptr; }
   };
+  // MXFP8 weight streams (dia_dec_layer.w_*_f8): at <= 16 rows (batch 1-8) the launch classes of dia_mxfp8_classes.  K splits
+  // over whole stream groups of 16 k-tiles with at most 128 per workgroup; the kernel picks its own waves and strips per workgroup
+  const int f8_mask = (F && d.w_planes <= 1 && !seg && !diag) ? dia_mxfp8_classes(R) : 0;
+  auto mxfp8 = [&](dia_gemm_args& g, const void* wf8, int cls) {
+    if (!wf8 || !(f8_mask >> cls & 1) || g.cmap || g.strip_map || g.KT % 16 != 0) return;
+    int sk = g.sk > 1 ? g.sk : 1;
+    while (sk > 1 && g.KT % (16 * sk) != 0) sk /= 2;
+    while (g.KT / sk > 128 && g.KT % (32 * sk) == 0 && d.sk_scratch && d.sk_tickets && sk < 4) sk *= 2;
+    if (g.KT / sk > 128) return;                  // (no split that fits: dense tiles)
+    g.W = wf8; g.w_format = DIA_W_MXFP8; g.nw = 0; g.spw = 0;
+    g.sk = sk;
+    if (sk == 1) { g.sk_scratch = nullptr; g.sk_tickets = nullptr; }
+    else { g.sk_scratch = d.sk_scratch; g.sk_tickets = d.sk_tickets; }
+  };
   for (int l = 0; l < d.n_layer; ++l) {
     const dia_dec_layer& L = e->layers[l];
     dia_gemm_args g = {};
@@ -101,6 +127,7 @@ static int enqueue_step(dia_engine* e, bool with_sampler) {
   g.act_f32 = F;            // reads x as fp32 tiles
   g.w_planes = d.w_planes;
   sparse24(g, L.w_qkv_24);
+  mxfp8(g, L.w_qkv_f8, 0);
   if ((rc = dia_gemm(&g, st))) return rc; mark(e, n++);
     }
 
@@ -124,6 +151,7 @@ static int enqueue_step(dia_engine* e, bool with_sampler) {
   g.act_f32 = 3 * F;        // attention output in, x out: both fp32 tiles
   g.w_planes = d.w_planes;
   sparse24(g, L.w_o_24);
+  mxfp8(g, L.w_o_f8, 1);
   if ((rc = dia_gemm(&g, st))) return rc; mark(e, n++);
 
     // cross-attention query (layers.py:273, 278)
@@ -136,6 +164,7 @@ static int enqueue_step(dia_engine* e, bool with_sampler) {
   g.act_f32 = F;
   g.w_planes = d.w_planes;
   sparse24(g, L.w_cq_24);
+  mxfp8(g, L.w_cq_f8, 2);
   if ((rc = dia_gemm(&g, st))) return rc; mark(e, n++);
 
     a = {};
@@ -167,6 +196,7 @@ static int enqueue_step(dia_engine* e, bool with_sampler) {
   g.act_f32 = 3 * F;
   g.w_planes = d.w_planes;
   sparse24(g, L.w_co_24);
+  mxfp8(g, L.w_co_f8, 3);
   if ((rc = dia_gemm(&g, st))) return rc; mark(e, n++);
 
     // SwiGLU MLP (layers.py:95-104)
@@ -231,11 +261,13 @@ static int enqueue_step(dia_engine* e, bool with_sampler) {
     lend_scratch(gi);
     gi.act_f32 = 3 * F; g.act_f32 = 3 * F; gi.w_planes = d.w_planes; g.w_planes = d.w_planes;
     sparse24(gi, L.w_wi_24);
+    mxfp8(gi, L.w_wi_f8, 4);
     if ((rc = dia_gemm(&gi, st))) return rc; mark(e, n++);
     if (diag) {
       g.W = L.w_wo_diag; g.w_layout = 1; g.nstrips = d.D / 8; g.sk = 1; g.sk_scratch = nullptr; g.sk_tickets = nullptr; g.nw = 0; g.spw = 0;
     } else {
       sparse24(g, L.w_wo_24);
+      mxfp8(g, L.w_wo_f8, 5);
     }
     rc = dia_gemm(&g, st);
     if (rc == DIA_E_ARG && g.sk > 1) {
@@ -256,6 +288,7 @@ static int enqueue_step(dia_engine* e, bool with_sampler) {
   g.act_f32 = F;
   g.w_planes = d.w_planes;
   sparse24(g, d.w_logits_24);
+  mxfp8(g, d.w_logits_f8, 6);
   if ((rc = dia_gemm(&g, st))) return rc; mark(e, n++);
   if (with_sampler) {
     if ((rc = dia_sample(&d.sample, st))) return rc; mark(e, n++);

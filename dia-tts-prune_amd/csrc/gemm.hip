@@ -2060,9 +2060,13 @@ int gemm_w2(const dia_gemm_args* a, GemmK& k, hipStream_t st) {
 extern "C" int dia_gemm(const dia_gemm_args* a, void* stream) {
   if (!a || !a->A || (!a->W && !a->sp_blocks)) return dia_fail(DIA_E_ARG, "dia_gemm: null argument");
   if (a->M <= 0 || a->KT <= 0 || a->nstrips <= 0) return dia_fail(DIA_E_ARG, "dia_gemm: empty problem");
-  if (a->w_format != DIA_W_DENSE && a->w_format != DIA_W_SPARSE24) return dia_fail(DIA_E_ARG, "dia_gemm: unknown w_format");
+  if (a->w_format != DIA_W_DENSE && a->w_format != DIA_W_SPARSE24 && a->w_format != DIA_W_MXFP8) return dia_fail(DIA_E_ARG, "dia_gemm: unknown w_format");
   if (a->w_format == DIA_W_SPARSE24) {      // 2:4 sparse weight stream (gemm_sparse.hip)
     const int rc = dia_gemm_sparse24_check(a);
+    if (rc != DIA_OK) return rc;
+  }
+  if (a->w_format == DIA_W_MXFP8) {         // MX e4m3 weight stream (gemm_mxfp8.hip)
+    const int rc = dia_gemm_mxfp8_check(a);
     if (rc != DIA_OK) return rc;
   }
   if (a->w_planes == 2) {
@@ -2103,6 +2107,7 @@ extern "C" int dia_gemm(const dia_gemm_args* a, void* stream) {
   if (a->ssq_in && a->ssq_ld < ((a->M + 15) / 16) * 16) return dia_fail(DIA_E_ARG, "dia_gemm: ssq_ld smaller than padded rows");
 
   if (a->w_format == DIA_W_SPARSE24) return dia_gemm_sparse24(a, stream);
+  if (a->w_format == DIA_W_MXFP8) return dia_gemm_mxfp8(a, stream);
   if (a->sp_blocks || a->sp_toff) {       // zero-skipping stream of an unstructured-pruned matrix: kernel-level experiment
 #ifdef DIA_EXPERIMENTS
     return dia_exp_gemm_sparse(a, stream);

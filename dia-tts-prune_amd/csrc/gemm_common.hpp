@@ -390,3 +390,6 @@ inline int fill_gemmk(const dia_gemm_args* a, GemmK& k) {
 // gemm_sparse.hip: dia_gemm with w_format == DIA_W_SPARSE24 (2:4 weight stream, M <= 16)
 int dia_gemm_sparse24_check(const dia_gemm_args* a);
 int dia_gemm_sparse24(const dia_gemm_args* a, void* stream);
+// gemm_mxfp8.hip: dia_gemm with w_format == DIA_W_MXFP8 (MX e4m3 weight stream, M <= 16)
+int dia_gemm_mxfp8_check(const dia_gemm_args* a);
+int dia_gemm_mxfp8(const dia_gemm_args* a, void* stream);

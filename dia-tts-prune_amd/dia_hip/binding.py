@@ -17,13 +17,13 @@ LIB_PATH = os.environ.get("DIA_HIP_LIB") or os.path.join(_HERE, "libdia_hip.so")
 ABI_VERSION = 8
 KV_F32, KV_BF16, KV_BF16X2 = 0, 1, 2
 EPI_SCALE_STORE, EPI_RESID_EMIT, EPI_SWIGLU_EMIT, EPI_CROSSKV = 0, 1, 2, 3
-W_DENSE, W_SPARSE24 = 0, 1                     # dia_gemm_args.w_format
+W_DENSE, W_SPARSE24, W_MXFP8 = 0, 1, 2                     # dia_gemm_args.w_format
 ATTN_SELF, ATTN_CROSS, ATTN_ENC = 0, 1, 2
 
 EXPORTS = (
     "dia_last_error", "dia_abi_version", "dia_device_count", "dia_set_tuning", "dia_get_tuning", "dia_has_experiments", "dia_gemm", "dia_gemm_timed", "dia_mlp_fused", "dia_mlp_fused_timed", "dia_engine_mlp_fused", "dia_attn", "dia_attn_scratch_floats", "dia_enc_kv_prep", "dia_enc_attn", "dia_dec_prefill_embed", "dia_dec_prefill_kv", "dia_dec_prefill_attn",
     "dia_embed_text", "dia_embed_tokens", "dia_sample", "dia_prefetch", "dia_engine_create", "dia_engine_destroy",
-    "dia_engine_decode", "dia_engine_set_prefetch", "dia_engine_step_logits_only", "dia_engine_profile_step", "dia_engine_time_step", "dia_timed_kernel_name", "dia_engine_launches_per_step",
+    "dia_engine_decode", "dia_engine_set_prefetch", "dia_engine_step_logits_only", "dia_engine_profile_step", "dia_engine_time_step", "dia_timed_kernel_name", "dia_engine_launches_per_step", "dia_mxfp8_classes",
     "dia_seg_mlp", "dia_seg_workspace_bytes", "dia_seg_workspace_control_bytes", "dia_seg_slots", "dia_seg_supported", "dia_seg_error",
 )
 
@@ -125,6 +125,8 @@ class DecLayer(C.Structure):
         ("smap_qkv", C.c_void_p), ("smap_cq", C.c_void_p), ("hmap_self", C.c_void_p), ("hmap_cross", C.c_void_p),
         ("w_qkv_24", C.c_void_p), ("w_o_24", C.c_void_p), ("w_cq_24", C.c_void_p), ("w_co_24", C.c_void_p),
         ("w_wi_24", C.c_void_p), ("w_wo_24", C.c_void_p),
+        ("w_qkv_f8", C.c_void_p), ("w_o_f8", C.c_void_p), ("w_cq_f8", C.c_void_p), ("w_co_f8", C.c_void_p),
+        ("w_wi_f8", C.c_void_p), ("w_wo_f8", C.c_void_p),
     ]
 
 
@@ -145,7 +147,7 @@ class EngineDesc(C.Structure):
         ("sample", SampleArgs),
         ("seg_w", C.POINTER(C.c_void_p)), ("seg_ws", C.c_void_p),
         ("kv_plane_self", C.c_int64), ("kv_plane_cross", C.c_int64),
-        ("w_logits_24", C.c_void_p),
+        ("w_logits_24", C.c_void_p), ("w_logits_f8", C.c_void_p),
     ]
 
 
@@ -219,6 +221,7 @@ def lib() -> C.CDLL:
     L.dia_engine_time_step.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int]
     L.dia_timed_kernel_name.argtypes = [C.c_int]
     L.dia_timed_kernel_name.restype = C.c_char_p
+    L.dia_mxfp8_classes.argtypes = [C.c_int]
     L.dia_seg_mlp.argtypes = [C.POINTER(SegArgs), C.c_void_p]
     L.dia_seg_workspace_bytes.restype = C.c_int64
     L.dia_seg_workspace_control_bytes.restype = C.c_int64
@@ -237,6 +240,12 @@ def set_tuning(name: str, value: int) -> None:
 def get_tuning(name: str) -> int:
     """current value of a launch-heuristic override, -1 = unset (DIA_TUNE is read on first use)"""
     return int(lib().dia_get_tuning(name.encode()))
+
+
+def mxfp8_mask(rows: int) -> int:
+    """launch classes (bit 0 qkv, 1 o, 2 cq, 3 co, 4 wi, 5 wo, 6 logits) that a decode step of `rows` rows streams as MXFP8 when the
+    model carries the streams: the library's measured default, or the knob mxfp8"""
+    return int(lib().dia_mxfp8_classes(int(rows)))
 
 
 def has_experiments() -> bool:

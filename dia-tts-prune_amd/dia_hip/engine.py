@@ -27,6 +27,7 @@ from . import compact as cpt
 from . import layout as lay
 from .config import DiaConfig
 from .pruning import is_2of4
+from .quant import is_mxfp8
 
 HEAD_DIM = 128
 _TILERS = {1: lay.tile_weight, 2: lay.tile_weight_bf16x2, 3: lay.tile_weight_planes}       # weight_planes -> layout of a DenseGeneral kernel
@@ -49,7 +50,7 @@ class TiledW:
 
     @property
     def nbytes(self) -> int:
-        return self.t.numel() * 2
+        return self.t.numel() * self.t.element_size()
 
     @property
     def a_kt(self) -> int:
@@ -121,7 +122,7 @@ class DeviceWeights:
     """Checkpoint -> kernel layouts, resident in HBM (bf16 tiles; norms / embeddings fp32)."""
 
     def __init__(self, cfg: DiaConfig, sd: Dict[str, torch.Tensor], device: torch.device, compact: str = "auto",
-                 weight_planes: int = 1, seg: str = "off", sparse: str = "off"):
+                 weight_planes: int = 1, seg: str = "off", sparse: str = "off", quant: str = "off"):
         """compact: "auto" = drop structure that a structured-pruned checkpoint zeroed (decoder only),
         "off" = keep every matrix at its checkpoint shape (zeros are streamed).
         weight_planes: 1 = every DenseGeneral kernel as ONE bf16 tile set (exact for bf16-representable checkpoints, the fast
@@ -139,7 +140,13 @@ class DeviceWeights:
         resident for the encoder, the cross K/V projections, both prefills and larger batches: the decoder's weights take about
         1.56x the memory of the dense model's decoder.  Every such matrix must hold at most 2 non-zeros in every group of 4
         consecutive K (pruning.is_2of4) and every K must be a multiple of 512; not with weight_planes != 1, a compacted
-        checkpoint or seg="on"."""
+        checkpoint or seg="on".
+        quant: "mxfp8" = an MXFP8-representable checkpoint (offline_quantize.py; quant.is_mxfp8) also carries the same matrices as
+        MXFP8 streams (layout.tile_weight_fp8: e4m3 elements + one E8M0 scale per 32 K of a column, 0.516 of the dense bytes),
+        which decode steps of at most 16 rows (batch 1-8) stream instead of the dense tiles.  The dense tiles stay resident for the
+        encoder, the cross K/V projections, both prefills and larger batches and hold the same numbers, so results do not depend on
+        which form a step used beyond summation order.  Every K must be a multiple of 512; not with sparse="2:4",
+        weight_planes != 1, a compacted checkpoint or seg="on"."""
         if weight_planes not in _TILERS:
             raise ValueError("weight_planes must be 1, 2 or 3")
         if sparse not in ("off", "2:4"):
@@ -148,7 +155,16 @@ class DeviceWeights:
             raise hb.DiaHipError("sparse='2:4': the 2:4 stream holds one bf16 weight plane (weight_planes must be 1)")
         if sparse == "2:4" and seg == "on":
             raise hb.DiaHipError("sparse='2:4': the persistent MLP segments stream dense ring arenas (seg must be 'off')")
+        if quant not in ("off", "mxfp8"):
+            raise ValueError('quant must be "off" or "mxfp8"')
+        if quant == "mxfp8" and sparse == "2:4":
+            raise hb.DiaHipError("quant='mxfp8': the MXFP8 stream and the 2:4 sparse stream exclude each other (sparse must be 'off')")
+        if quant == "mxfp8" and weight_planes != 1:
+            raise hb.DiaHipError("quant='mxfp8': an MXFP8 value is one bf16 value (weight_planes must be 1)")
+        if quant == "mxfp8" and seg == "on":
+            raise hb.DiaHipError("quant='mxfp8': the persistent MLP segments stream dense ring arenas (seg must be 'off')")
         self.sparse = sparse
+        self.quant = quant
         self.weight_planes = weight_planes
         m, e, d = cfg.model, cfg.model.encoder, cfg.model.decoder
         if d.gqa_head_dim != HEAD_DIM or d.cross_head_dim != HEAD_DIM or e.head_dim != HEAD_DIM:
@@ -166,6 +182,7 @@ class DeviceWeights:
         self.logits = self._tile(lw[keep_logits.to(device)] if keep_logits is not None else lw)
         self.logits_cols = lw.shape[1]
         self.logits24 = self._tile24("decoder.logits_dense", lw) if sparse == "2:4" else None
+        self.logits_f8 = self._tile_f8("decoder.logits_dense", lw) if quant == "mxfp8" else None
         npos = max(cfg.data.audio_length, cfg.data.text_length) + 1
         cos, sin = lay.rope_tables(npos, HEAD_DIM, m.rope_min_timescale, m.rope_max_timescale)
         self.cos_t, self.sin_t = cos.to(device), sin.to(device)
@@ -201,6 +218,14 @@ class DeviceWeights:
         if not is_2of4(w2d):
             raise hb.DiaHipError(f"sparse='2:4': {name} is not 2:4 sparse (more than 2 non-zeros in a group of 4 consecutive K)")
         return TiledW(*lay.tile_weight_24(w2d))
+
+    @staticmethod
+    def _tile_f8(name, w2d) -> TiledW:
+        if w2d.shape[0] % 512:
+            raise hb.DiaHipError(f"quant='mxfp8': {name}: K = {w2d.shape[0]} is not a multiple of 512")
+        if not is_mxfp8(w2d):
+            raise hb.DiaHipError(f"quant='mxfp8': {name} is not MXFP8-representable (quantise the checkpoint with offline_quantize.py)")
+        return TiledW(*lay.tile_weight_fp8(w2d))
 
     def _build_encoder(self, sd, compact: str):
         e, device = self.cfg.model.encoder, self.device
@@ -257,6 +282,8 @@ class DeviceWeights:
         if self.sparse == "2:4" and self.compacted:
             raise hb.DiaHipError("sparse='2:4': a compacted (structured-pruned) checkpoint has no 2:4 form; load it with compact='off' "
                                  "or prune with --prune-mode 2:4")
+        if self.quant == "mxfp8" and self.compacted:
+            raise hb.DiaHipError("quant='mxfp8': a compacted (structured-pruned) checkpoint has no MXFP8 stream; load it with compact='off'")
         i32 = self._i32
         self.dec_layers = []
         for i, P in enumerate(plans):
@@ -300,6 +327,7 @@ class DeviceWeights:
             for k in DEC_MATS:
                 L[k] = self._tile(mats[k])
                 L[k + "24"] = self._tile24(p + k, mats[k]) if self.sparse == "2:4" else None
+                L[k + "f8"] = self._tile_f8(p + k, mats[k]) if self.quant == "mxfp8" else None
             # experiment (knob wo_diag=1): wo once more in the diagonal layout (4-column groups: 256 workgroups with the whole K each)
             L["wo_diag"] = None
             if (hb.get_tuning("wo_diag") == 1 and P is None and self.weight_planes == 1 and device.type == "cuda" and wo.shape[0] % 1024 == 0
@@ -367,6 +395,10 @@ class DeviceWeights:
             for L in self.dec_layers:
                 out += [L[k + "24"].t for k in DEC_MATS]
             out.append(self.logits24.t)
+        if self.quant == "mxfp8":                   # the MXFP8 streams (quant="mxfp8"), after everything the dense model holds
+            for L in self.dec_layers:
+                out += [L[k + "f8"].t for k in DEC_MATS]
+            out.append(self.logits_f8.t)
         return out
 
     def pack_flat(self):
@@ -388,14 +420,14 @@ class DeviceWeights:
 
     @classmethod
     def empty_like_config(cls, cfg: DiaConfig, device: torch.device, weight_planes: int = 1, seg: str = "off",
-                          sparse: str = "off") -> "DeviceWeights":
+                          sparse: str = "off", quant: str = "off") -> "DeviceWeights":
         """Same tensors, zero-filled: the receive side of the multi-GPU weight broadcast (dense layout;
         a compacted, i.e. structured-pruned, model has checkpoint-dependent shapes: every rank then
         loads the checkpoint itself instead of receiving a broadcast).  `weight_planes` must be the sender's
         (dist.broadcast_weights checks it on every rank before the arena travels)."""
         from .weights import param_shapes
         sd = {k: torch.zeros(shp, dtype=torch.float32, device=device) for k, shp in param_shapes(cfg).items()}
-        return cls(cfg, sd, device, compact="off", weight_planes=weight_planes, seg=seg, sparse=sparse)
+        return cls(cfg, sd, device, compact="off", weight_planes=weight_planes, seg=seg, sparse=sparse, quant=quant)
 
     def prefill_weight_bytes(self) -> int:
         """bf16 bytes the prefill streams once per batch: the encoder and the cross K/V projections"""
@@ -405,12 +437,16 @@ class DeviceWeights:
     def decode_weight_bytes(self, rows: int = 2) -> int:
         """bf16 bytes one decode step of `rows` rows (2 per utterance) streams (SURVEY.md §8d 'W'): every decoder matrix except
         the prefill-only cross K/V projections, plus the logits head — the 2:4 streams where the step uses them (sparse="2:4",
-        at most 4 rows)."""
+        at most 4 rows) and the MXFP8 streams for the launch classes the library enables at this row count (quant="mxfp8", at
+        most 16 rows: binding.mxfp8_mask)."""
         every = self.sparse == "2:4" and rows <= 4
+        f8 = hb.mxfp8_mask(rows) if self.quant == "mxfp8" else 0
 
         def w(L, k):
+            if f8 >> DEC_MATS.index(k) & 1:
+                return L[k + "f8"].nbytes
             return L[k + "24"].nbytes if every else L[k].nbytes
-        n = self.logits24.nbytes if every else self.logits.nbytes
+        n = self.logits_f8.nbytes if f8 >> len(DEC_MATS) & 1 else (self.logits24.nbytes if every else self.logits.nbytes)
         for L in self.dec_layers:
             n += sum(w(L, k) for k in DEC_MATS)
         return n
@@ -634,6 +670,8 @@ class DecodeSession:
                 setattr(dl, "ns_" + f, L[f].ns)
                 sp = L[f + "24"]                                            # 2:4 stream (sparse="2:4"), NULL = dense only
                 setattr(dl, "w_" + f + "_24", hb.ptr(sp.t) if sp is not None else None)
+                f8 = L[f + "f8"]                                            # MXFP8 stream (quant="mxfp8"), NULL = dense only
+                setattr(dl, "w_" + f + "_f8", hb.ptr(f8.t) if f8 is not None else None)
             dl.g_sa, dl.g_ca, dl.g_mlp = hb.ptr(L["g_sa"]), hb.ptr(L["g_ca"]), hb.ptr(L["g_mlp"])
             dl.k_self, dl.v_self = hb.ptr(self.k_self[i]), hb.ptr(self.v_self[i])
             dl.k_cross, dl.v_cross = hb.ptr(self.k_cross[i]), hb.ptr(self.v_cross[i])
@@ -651,6 +689,7 @@ class DecodeSession:
         ed.layers = C.cast(self._layers, C.POINTER(hb.DecLayer))
         ed.w_logits, ed.kt_logits, ed.ns_logits = hb.ptr(w.logits.t), w.logits.kt, w.logits.ns
         ed.w_logits_24 = hb.ptr(w.logits24.t) if w.logits24 is not None else None
+        ed.w_logits_f8 = hb.ptr(w.logits_f8.t) if w.logits_f8 is not None else None
         ed.g_final = hb.ptr(w.dec_norm)
         ed.x, ed.planes_x, ed.planes_a, ed.planes_h = hb.ptr(self.x), hb.ptr(self.planes_x), hb.ptr(self.planes_a), hb.ptr(self.planes_h)
         ed.ssq, ed.qkv, ed.qc, ed.logits = hb.ptr(self.ssq), hb.ptr(self.qkv), hb.ptr(self.qc), hb.ptr(self.logits)

@@ -300,6 +300,45 @@ def untile_weight_24(stream: torch.Tensor, K: int, N: int) -> torch.Tensor:
     return dense.reshape(kt8 * 64, ns * 16)[:K, :N].contiguous()
 
 
+# ---- MXFP8 weight stream (dia_gemm_args.w_format = DIA_W_MXFP8, csrc/gemm_mxfp8.hip) ------------------------------------
+FP8_GROUP = 16                           # k-tiles (32 K each) behind one scale block
+FP8_GROUP_BYTES = 256 + 8 * 1024         # scale block + 8 value slots
+
+
+def tile_weight_fp8(w2d: torch.Tensor) -> Tuple[torch.Tensor, int, int]:
+    """[K, N] float -> (stream uint8 [N/16, G, 8448], K/32, N/16): the MXFP8 encoding of the matrix (quant.mxfp8_quantize_2d: e4m3
+    elements, one E8M0 scale per 32 consecutive K of a column = per column of a k-tile) in the order csrc/gemm_mxfp8.hip reads.
+    K is zero-padded to a multiple of 32, N to 16, the k-tiles to whole groups of 16 (G = ceil(K/32 / 16)).
+
+    Stream of a strip: one block per group of 16 k-tiles, each a sequential 8448 bytes = a 256-byte scale block
+    ``[16 columns][16 k-tiles]`` (lane l of a wave reads the bytes of column l & 15), then 8 slots of 1 KiB: slot p =
+    ``[64 lanes][16 bytes]``, lane l holding its 8 elements of k-tile 2p (bytes 0-7) and of k-tile 2p + 1 (bytes 8-15), element
+    j of k-tile t = W[32 t + 8 (l >> 4) + j][16 strip + (l & 15)] as in the dense tiles.  0.515625 of the dense tiles' bytes."""
+    from .quant import mxfp8_quantize_2d
+    K, N = w2d.shape
+    Np = _ceil(N, 16)
+    kt, ns = _ceil(K, 32) // 32, Np // 16
+    G = (kt + FP8_GROUP - 1) // FP8_GROUP
+    el, sc = mxfp8_quantize_2d(w2d)
+    elp = torch.zeros(G * FP8_GROUP * 32, Np, dtype=torch.uint8, device=w2d.device)
+    scp = torch.full((G * FP8_GROUP, Np), 127, dtype=torch.uint8, device=w2d.device)
+    elp[: el.shape[0], :N] = el
+    scp[: sc.shape[0], :N] = sc
+    # (G, p, h, kq, j, strip, c) -> (strip, G, p, lane = 16 kq + c, byte = 8 h + j)
+    vals = elp.reshape(G, 8, 2, 4, 8, ns, 16).permute(5, 0, 1, 3, 6, 2, 4).reshape(ns, G, 8 * 1024)
+    scales = scp.reshape(G, FP8_GROUP, ns, 16).permute(2, 0, 3, 1).reshape(ns, G, 256)
+    return torch.cat([scales, vals], dim=2).contiguous(), kt, ns
+
+
+def untile_weight_fp8(stream: torch.Tensor, K: int, N: int) -> torch.Tensor:
+    """inverse of tile_weight_fp8 (test helper): the DEQUANTISED matrix, fp32 [K, N]"""
+    from .quant import mxfp8_dequantize_2d
+    ns, G = stream.shape[0], stream.shape[1]
+    scales = stream[:, :, :256].reshape(ns, G, 16, FP8_GROUP).permute(1, 3, 0, 2).reshape(G * FP8_GROUP, ns * 16)
+    vals = stream[:, :, 256:].reshape(ns, G, 8, 4, 16, 2, 8).permute(1, 2, 5, 3, 6, 0, 4).reshape(G * FP8_GROUP * 32, ns * 16)
+    return mxfp8_dequantize_2d(vals.contiguous(), scales.contiguous())[:K, :N].contiguous()
+
+
 # ---- ring layout of the persistent MLP segment (csrc/seg.hip) ------------------------------------------------------
 SEG_CUS = 256            # one workgroup per CU of an MI355X
 SEG_K = 2048             # contraction length of one slot (16 tiles of 128 k x 4 columns)

@@ -1,0 +1,88 @@
+"""MXFP8 weight-only quantisation (OCP MX, element type e4m3fn, block = 32 consecutive K of one column).
+
+A block of a ``[K, N]`` kernel (K the contraction axis, as DeviceWeights flattens it: ``pruning._kernel_2d``) shares one
+power-of-two scale ``X = 2^e`` with ``e = floor(log2(max|w|)) - 8`` (an all-zero block: ``e = 0``), clamped to [-100, 100] and
+stored as E8M0 (``e + 127``); an element is ``w / X`` clamped to +-448 and rounded to nearest-even e4m3.  The clamp comes
+BEFORE the cast: the block maximum can land in (448, 512), and ``tensor.to(torch.float8_e4m3fn)`` does not saturate.
+
+An e4m3 value times a power of two is exactly a bf16 value, so a dequantised checkpoint is an ordinary state dict that the
+dense bf16 tiles, the oracle and the reference run exactly; the fp8 stream (layout.tile_weight_fp8, csrc/gemm_mxfp8.hip) is a
+second encoding of the same numbers.  "Is MXFP8-representable" is ``dequantise(quantise(w)) == w`` (``is_mxfp8``), which
+holds for everything the quantiser emits (quantise(dequantise(q)) reproduces elements and scales bit for bit).
+"""
+
+from __future__ import annotations
+
+from collections import OrderedDict
+from typing import Dict, List, Tuple
+
+import torch
+
+from .config import DiaConfig
+from .pruning import _kernel_2d
+
+MX_BLOCK = 32            # K per scale
+E4M3_MAX = 448.0
+E8M0_BIAS = 127
+E_MIN, E_MAX = -100, 100  # every dequantised value stays a normal bf16
+
+
+def _blocks(w2d: torch.Tensor) -> torch.Tensor:
+    """[K, N] -> fp32 [ceil(K/32), 32, N], K zero-padded to whole blocks"""
+    K, N = w2d.shape
+    Kp = (K + MX_BLOCK - 1) // MX_BLOCK * MX_BLOCK
+    wp = torch.zeros(Kp, N, dtype=torch.float32, device=w2d.device)
+    wp[:K] = w2d.float()
+    return wp.reshape(Kp // MX_BLOCK, MX_BLOCK, N)
+
+
+def mxfp8_quantize_2d(w2d: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """[K, N] float -> (elements uint8 [Kp, N] (e4m3fn bits), scales uint8 [Kp/32, N] (E8M0)), Kp = K zero-padded to 32"""
+    b = _blocks(w2d)
+    amax = b.abs().amax(dim=1)                                            # [KB, N]
+    # amax = m * 2^ex with m in [0.5, 1): floor(log2 amax) = ex - 1
+    e = torch.frexp(amax)[1].to(torch.int32) - 1 - 8
+    e = torch.where(amax > 0, e, torch.zeros_like(e)).clamp_(E_MIN, E_MAX)
+    scaled = torch.ldexp(b, -e[:, None, :]).clamp_(-E4M3_MAX, E4M3_MAX)  # exact: a power-of-two factor
+    elems = scaled.to(torch.float8_e4m3fn).view(torch.uint8).reshape(-1, b.shape[2])
+    return elems.contiguous(), (e + E8M0_BIAS).to(torch.uint8).contiguous()
+
+
+def mxfp8_dequantize_2d(elements: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
+    """inverse of mxfp8_quantize_2d on the padded shape: fp32 [Kp, N] = element x 2^(scale - 127)"""
+    Kp, N = elements.shape
+    v = elements.contiguous().view(torch.float8_e4m3fn).float().reshape(Kp // MX_BLOCK, MX_BLOCK, N)
+    e = scales.to(torch.int32) - E8M0_BIAS
+    return torch.ldexp(v, e[:, None, :]).reshape(Kp, N)
+
+
+def mxfp8_round_2d(w2d: torch.Tensor) -> torch.Tensor:
+    """[K, N] -> fp32 [K, N]: the nearest MXFP8-representable matrix (dequantise(quantise(w)))"""
+    return mxfp8_dequantize_2d(*mxfp8_quantize_2d(w2d))[: w2d.shape[0]]
+
+
+def is_mxfp8(w2d: torch.Tensor) -> bool:
+    """True when every value of [K, N] is its block's e4m3 element times the block's power-of-two scale"""
+    return bool(torch.equal(mxfp8_round_2d(w2d), w2d.float()))
+
+
+def mxfp8_names(cfg: DiaConfig) -> List[str]:
+    """the DenseGeneral kernels a decode step streams: q/k/v, o, cross-q, cross-o, wi, wo of every decoder layer and the
+    logits head (the encoder and the cross K/V projections run in the prefill only and stay as they are)"""
+    names = []
+    for i in range(cfg.model.decoder.n_layer):
+        p = f"decoder.layers.{i}."
+        names += [p + f"self_attention.{n}_proj.weight" for n in "qkvo"]
+        names += [p + "cross_attention.q_proj.weight", p + "cross_attention.o_proj.weight"]
+        names += [p + "mlp.wi_fused.weight", p + "mlp.wo.weight"]
+    return names + ["decoder.logits_dense.weight"]
+
+
+def mxfp8_quantize_state_dict(cfg: DiaConfig, sd: Dict[str, torch.Tensor]) -> "OrderedDict[str, torch.Tensor]":
+    """An ordinary fp32 state dict holding the dequantised MXFP8 values of every kernel of ``mxfp8_names(cfg)``, each blocked
+    along the K axis of its [K, N] form; everything else untouched.  Idempotent."""
+    out: "OrderedDict[str, torch.Tensor]" = OrderedDict((k, v.clone()) for k, v in sd.items())
+    for name in mxfp8_names(cfg):
+        w = sd[name]
+        out[name] = mxfp8_round_2d(_kernel_2d(name, w.float())).reshape(w.shape)
+    return out

@@ -40,6 +40,7 @@ extern "C" {
 /* weight formats of dia_gemm_args.w_format */
 #define DIA_W_DENSE 0      /* bf16 tiles [nstrips][KT][64][8], KT = K/32 */
 #define DIA_W_SPARSE24 1   /* 2:4 sparse stream (dia_hip/layout.py tile_weight_24), KT = K/64 */
+#define DIA_W_MXFP8 2      /* OCP MX e4m3 stream (dia_hip/layout.py tile_weight_fp8), KT = K/32 */
 
 /* attention modes */
 #define DIA_ATTN_SELF 0   /* decoder self-attention over the growing cache (layers.py:541-555) */
@@ -165,7 +166,12 @@ typedef struct {
    * a 1 KiB index block followed by 8 KiB of kept values, the A operand of v_smfmac_f32_16x16x64_bf16) and KT counts sparse
    * k-tiles (K/64, a multiple of 8 per workgroup).  M <= 16, fp32 activation tiles in and out (act_f32 = 3; bit 0 alone when
    * nothing is emitted), SCALE_STORE / RESID_EMIT (with gnext) / SWIGLU_EMIT, split-K through sk; not with w_planes > 1,
-   * w_layout = 1, sp_blocks, CROSSKV or the compaction maps — those return DIA_E_ARG. */
+   * w_layout = 1, sp_blocks, CROSSKV or the compaction maps — those return DIA_E_ARG.
+   * DIA_W_MXFP8: W is the MXFP8 stream of a matrix whose every value is an e4m3 element times the power-of-two scale of its
+   * block of 32 consecutive K of a column (dia_hip/quant.py; dia_hip/layout.py tile_weight_fp8: per strip, groups of 16 k-tiles,
+   * each a 256-byte block of E8M0 scales followed by 8 KiB of e4m3 elements, expanded to the bf16 B operand of
+   * v_mfma_f32_16x16x32_bf16 in registers) and KT = K/32, a multiple of 16 and at most 128 per workgroup (KT / sk).  Same
+   * restrictions as DIA_W_SPARSE24; results equal the dense tiles of the same matrix up to summation order. */
   int32_t w_format;
   int32_t _pad2;
 } dia_gemm_args;
@@ -414,6 +420,10 @@ typedef struct {
    * of at most 4 rows (batch 1-2) streams every matrix that has one; more rows (the dense forms are as fast there), planes between
    * the kernels (act_f32 = 0), two- or three-plane weights and the wo_diag / segment / mlp_fused experiments use the dense tiles */
   const void *w_qkv_24, *w_o_24, *w_cq_24, *w_co_24, *w_wi_24, *w_wo_24;
+  /* MXFP8 streams of the same matrices (dia_gemm_args.w_format = DIA_W_MXFP8, KT = kt_*), NULL = dense only.  A step of at most 16
+   * rows (batch 1-8) streams the matrices that have one and that the knob mxfp8 (csrc/tuning.hpp) enables for its row range;
+   * more rows, planes between the kernels, two- or three-plane weights and the experiments use the dense tiles */
+  const void *w_qkv_f8, *w_o_f8, *w_cq_f8, *w_co_f8, *w_wi_f8, *w_wo_f8;
 } dia_dec_layer;
 
 typedef struct {
@@ -460,6 +470,7 @@ typedef struct {
   void* seg_ws;             /* workspace of dia_seg_mlp */
   int64_t kv_plane_self, kv_plane_cross;   /* DIA_KV_BF16X2: plane strides (elements) of the self / cross caches */
   const void* w_logits_24;  /* 2:4 sparse stream of the logits head (as dia_dec_layer.w_*_24: used at <= 4 rows), NULL = dense only */
+  const void* w_logits_f8;  /* MXFP8 stream of the logits head (as dia_dec_layer.w_*_f8), NULL = dense only */
 } dia_engine_desc;
 
 typedef struct dia_engine dia_engine;
@@ -487,6 +498,10 @@ int dia_engine_time_step(dia_engine* e, float* ms_per_kernel, float* interval_ms
 /* kernel instantiation name (as rocprofv3 prints it, without the namespace) of the i-th launch of the calling thread's
  * last dia_engine_time_step / dia_gemm_timed; "" when out of range */
 const char* dia_timed_kernel_name(int i);
+/* Launch classes of a decode step of `rows` rows that stream MXFP8 when the model carries the streams (dia_dec_layer.w_*_f8,
+ * dia_engine_desc.w_logits_f8): bit 0 qkv, 1 o, 2 cq, 3 co, 4 wi, 5 wo, 6 logits.  0 above 16 rows.  The knob "mxfp8" overrides the
+ * measured default (bits 0-6: at most 4 rows, bits 8-14: 5..16 rows). */
+int dia_mxfp8_classes(int rows);
 /* number of kernel launches in one decode step */
 int dia_engine_launches_per_step(const dia_engine* e);
 
