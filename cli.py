@@ -51,6 +51,9 @@ def build_parser() -> argparse.ArgumentParser:
     g.add_argument("--top-p", type=float, default=0.95, help="nucleus (top-p) mass kept by the sampler")
     g.add_argument("--cfg-filter-top-k", type=int, default=35, help="keep only the k best logits after guidance; 0 switches the filter off")
     g.add_argument("--seed", type=int, default=None, help="seed of the sampling noise")
+    g.add_argument("--slots", type=int, default=0, help="N > 0: split the text into chunks (the front-end's chunk plan) and generate them as "
+                   "independent utterances sharing N slots of one continuously batched session; needs --codes-output (the chunks' "
+                   "codes are joined in order); not with --audio-prompt (a prompt chain is sequential)")
     g = p.add_argument_group("Infrastructure")
     g.add_argument("--device", type=str, default=None, help="HIP device such as cuda:0 (default: the current one)")
     g.add_argument("--compute-dtype", type=str, default="bfloat16", choices=["float16", "bfloat16", "float32"], help="K/V cache dtype: bfloat16 (default; float16 is accepted and mapped to it) or float32.")
@@ -76,6 +79,8 @@ def main(argv=None) -> int:
         parser.error("--pruned-checkpoint needs --config unless --model-path is a local directory with a config.json")
     if not args.output and not args.codes_output:
         parser.error("one of --output / --codes-output is required.")
+    if args.slots < 0 or (args.slots and (args.audio_prompt or not args.codes_output or args.output)):
+        parser.error("--slots N needs N > 0, --codes-output, and neither --audio-prompt nor --output.")
     if args.no_dac and args.output:
         parser.error("--output needs the audio codec; use --codes-output with --no-dac.")
 
@@ -116,6 +121,25 @@ def main(argv=None) -> int:
     if prompt and prompt.endswith(".npy"):
         prompt = torch.from_numpy(np.load(prompt).astype(np.int64))
     print("Generating audio...")
+    if args.slots:
+        try:
+            from dia_hip.callers import generate_chunks_codes
+            parts = generate_chunks_codes(dia, full_text, slots=args.slots, max_new_tokens=args.max_tokens or dia.config.data.audio_length,
+                                          cfg_scale=args.cfg_scale, temperature=args.temperature, top_p=args.top_p,
+                                          cfg_filter_top_k=args.cfg_filter_top_k, seed=args.seed)
+            if not parts:
+                print("Generation failed to produce codes.")
+                return 1
+            codes = np.concatenate(parts, axis=-1)
+            Path(args.codes_output).parent.mkdir(parents=True, exist_ok=True)
+            np.save(args.codes_output, codes)
+            print(f"Codes of {len(parts)} chunks saved to {args.codes_output}: shape {tuple(codes.shape)}")
+            return 0
+        except Exception as e:
+            print(f"Error during audio generation or saving: {e}")
+            import traceback
+            traceback.print_exc()
+            return 1
     try:
         audio = dia.generate(text=full_text, audio_prompt=prompt, audio_prompt_text=args.audio_prompt_text,
                              max_tokens=args.max_tokens, cfg_scale=args.cfg_scale, temperature=args.temperature,

@@ -19,6 +19,9 @@
 #include "../../include/dia_hip.h"
 #include "errors.hpp"
 #include "launch.hpp"
+#include <algorithm>
+#include <cstdarg>
+#include <cstdio>
 
 namespace {
 
@@ -32,6 +35,7 @@ struct EmbedK {
   bf16_raw* P; long p_plane_stride; int p_ktiles; int ssq_ld; float* ssq;
   const int* cmap;
   int act_f32;
+  const int* slots;                 // k_embed_tokens only: utterance of workgroup i, or null = i
 };
 
 struct SampleK {
@@ -42,6 +46,9 @@ struct SampleK {
   const int* first_step;
   int* tokens; int* pred; int* cur; int* fsm;
   EmbedK e;
+  // per-slot sampling state (k_sample<true> only)
+  const float* slot_cfg_scale; const float* slot_temperature; const float* slot_top_p;
+  const int* slot_top_k; const int* slot_max_tokens;
 };
 
 // x rows (2b, 2b+1) <- sum_c emb[c][tok[c]][:]; planes(x*g); strip ssq.  8 dims per thread.
@@ -96,7 +103,7 @@ __device__ __forceinline__ void embed_rows(const EmbedK& e, int b, const int* to
 
 __global__ __launch_bounds__(256) void k_embed_tokens(EmbedK e) {
   __shared__ int tok[MAXC];
-  const int b = blockIdx.x;
+  const int b = e.slots ? e.slots[blockIdx.x] : blockIdx.x;
   if (threadIdx.x < e.C) tok[threadIdx.x] = e.tokens[((long)b * e.T + (e.cur[b] - 1)) * e.C + threadIdx.x];
   __syncthreads();
   embed_rows(e, b, tok, threadIdx.x, 256);
@@ -194,6 +201,9 @@ __device__ __forceinline__ double wscan_incl(double x, int lane) {
   return x + below;
 }
 
+// SLOTS: the five sampling values come from the per-slot arrays of a continuously batched session instead of the kernel
+// arguments.  Its own instantiation: the closed-batch form keeps them in argument SGPRs and issues no load for them.
+template <bool SLOTS>
 __global__ __launch_bounds__(MAXC * 64) void k_sample(SampleK p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   __shared__ int preds[MAXC];
@@ -215,6 +225,13 @@ __global__ __launch_bounds__(MAXC * 64) void k_sample(SampleK p) {
     cv[i] = co[v]; uv[i] = un[v];
   }
   const int cur = p.cur[b];
+  // sampling values of this utterance: uniform over the workgroup, requested here with cur[] / fsm[] (not behind a branch)
+  float s_cfg = p.cfg_scale, s_temp = p.temperature, s_top_p = p.top_p;
+  int s_top_k = p.top_k, s_max_tokens = p.max_tokens;
+  if constexpr (SLOTS) {
+    s_cfg = p.slot_cfg_scale[b]; s_temp = p.slot_temperature[b]; s_top_p = p.slot_top_p[b];
+    s_top_k = p.slot_top_k[b]; s_max_tokens = p.slot_max_tokens[b];
+  }
   int* fsm = p.fsm + b * 8;
   const bool done = fsm[3] != 0;                    // uniform over the workgroup
   const int first = p.first_step ? p.first_step[b] : 1;
@@ -235,7 +252,7 @@ __global__ __launch_bounds__(MAXC * 64) void k_sample(SampleK p) {
   if (!done && !replay && c < p.C) {
     const int n = cur - first;                                                      // sampled steps so far
     float lg[NV], qn[NV];
-    const bool use_noise = p.temperature != 0.0f;
+    const bool use_noise = s_temp != 0.0f;
     const float* q = use_noise ? p.noise + (((long)b * p.noise_steps + n) * p.C + c) * p.V : co;
 #pragma unroll
     for (int i = 0; i < NV; ++i) qn[i] = q[min(lane + 64 * i, p.V - 1)];
@@ -243,13 +260,13 @@ __global__ __launch_bounds__(MAXC * 64) void k_sample(SampleK p) {
     for (int i = 0; i < NV; ++i) {
       const int v = lane + 64 * i;
       const float t = cv[i] - uv[i];
-      float x = cv[i] + p.cfg_scale * t;                                            // model.py:457
+      float x = cv[i] + s_cfg * t;                                            // model.py:457
       if (v >= p.V || v == p.pad || v == p.bos || (c > 0 && v == p.eos)) x = -INFINITY;   // model.py:462-472
       lg[i] = x;
       if (!use_noise) qn[i] = 1.0f;
     }
     int choice;
-    if (p.temperature == 0.0f) {                                                    // model.py:38-40
+    if (s_temp == 0.0f) {                                                    // model.py:38-40
       float bv = -INFINITY; int bi = 0x7fffffff;
 #pragma unroll
       for (int i = 0; i < NV; ++i) {
@@ -259,7 +276,7 @@ __global__ __launch_bounds__(MAXC * 64) void k_sample(SampleK p) {
       choice = wargmax(bv, bi);
     } else {
 #pragma unroll
-      for (int i = 0; i < NV; ++i) lg[i] = lg[i] / p.temperature;                   // model.py:43
+      for (int i = 0; i < NV; ++i) lg[i] = lg[i] / s_temp;                   // model.py:43
       SSTAMP(1);
       // ---- top-k (model.py:46-52): everything below the k-th largest value goes to -inf.
       // k <= 64 (the reference's default is 35): the k-th largest of the 64 per-lane maxima is a lower bound T0 of the
@@ -267,7 +284,7 @@ __global__ __launch_bounds__(MAXC * 64) void k_sample(SampleK p) {
       // most 64 candidates they are compacted to one per lane, in increasing vocabulary index, and the cut is a count of
       // larger candidates.  More candidates than lanes, k > 64 or no top-k: the k-th value by bitwise search on
       // order-preserving keys, and the survivors are compacted if they fit.
-      const int k = min(p.top_k, p.V);
+      const int k = min(s_top_k, p.V);
       bool compact = false, kcut = false;
       int cnt = 0;
       auto compact_if = [&](auto pred) {               // survivors of pred(lg[i]) -> lp (value), sp (noise), li (index)
@@ -284,7 +301,7 @@ __global__ __launch_bounds__(MAXC * 64) void k_sample(SampleK p) {
         }
         __builtin_amdgcn_wave_barrier();
       };
-      if (p.top_k > 0 && k <= 64) {
+      if (s_top_k > 0 && k <= 64) {
         float lm = lg[0];
 #pragma unroll
         for (int i = 1; i < NV; ++i) lm = fmaxf(lm, lg[i]);
@@ -300,7 +317,7 @@ __global__ __launch_bounds__(MAXC * 64) void k_sample(SampleK p) {
         }
       }
       if (!compact) {
-        if (p.top_k > 0) {
+        if (s_top_k > 0) {
           uint32_t key[NV];
 #pragma unroll
           for (int i = 0; i < NV; ++i) key[i] = (lane + 64 * i < p.V) ? fkey(lg[i]) : 0u;
@@ -340,7 +357,7 @@ __global__ __launch_bounds__(MAXC * 64) void k_sample(SampleK p) {
           act = act0 && gt < k;
           if (!act) l = -INFINITY;
         }
-        if (p.top_p < 1.0f) {                          // model.py:56-70
+        if (s_top_p < 1.0f) {                          // model.py:56-70
           const float m = wmax(l);
           const float e = act ? expf(l - m) : 0.f;
           const float z = wsum(e);
@@ -365,7 +382,7 @@ __global__ __launch_bounds__(MAXC * 64) void k_sample(SampleK p) {
           // cumulative sum in sorted order, in double like torch.cumsum on CPU — in double the scan order moves the
           // sum by ~1e-16 relative, far below the fp32 rounding applied before the comparison
           const double cum = wscan_incl((lane < ns) ? (double)srt[lane] : 0.0, lane);
-          const unsigned long long over = __ballot(lane < ns && (float)cum > p.top_p);
+          const unsigned long long over = __ballot(lane < ns && (float)cum > s_top_p);
           const int first_over = over ? (__ffsll((long long)over) - 1) : ns;      // smallest r with cum[r] > top_p
           int keep = min(ns, first_over + 1);          // entry r+1 is removed iff float(cum[r]) > top_p; monotone in r
           if (ns == 0) keep = 0;
@@ -381,7 +398,7 @@ __global__ __launch_bounds__(MAXC * 64) void k_sample(SampleK p) {
         choice = wargmax(sc, act ? idx : 0x7fffffff);
       } else {
       // ---- top-p (model.py:56-70)
-      if (p.top_p < 1.0f) {
+      if (s_top_p < 1.0f) {
         float m = -INFINITY;
 #pragma unroll
         for (int i = 0; i < NV; ++i) m = fmaxf(m, lg[i]);
@@ -428,7 +445,7 @@ __global__ __launch_bounds__(MAXC * 64) void k_sample(SampleK p) {
             if (lane >= o) cum += up;
           }
           // entry r+1 is removed iff float(cum[r]) > top_p; removal is monotone in r
-          const unsigned long long over = __ballot(lane < ns && (float)cum > p.top_p);
+          const unsigned long long over = __ballot(lane < ns && (float)cum > s_top_p);
           const int first = over ? (__ffsll((long long)over) - 1) : ns;          // smallest r with cum[r] > top_p
           keep = min(ns, first + 1);
           if (ns == 0) keep = 0;
@@ -437,7 +454,7 @@ __global__ __launch_bounds__(MAXC * 64) void k_sample(SampleK p) {
           keep = 1;
           for (int r = 0; r + 1 < ns; ++r) {
             cum += (double)sp[r];
-            if ((float)cum > p.top_p) break;          // entry r+1 is removed, and all after it
+            if ((float)cum > s_top_p) break;          // entry r+1 is removed, and all after it
             keep = r + 2;
           }
         }
@@ -510,13 +527,13 @@ __global__ __launch_bounds__(MAXC * 64) void k_sample(SampleK p) {
         tk = (bos_countdown > 0 && old != -1) ? old : pr;
         if (ch) trow[lane] = tk;
         if (eos_countdown == 0) { finished = 1; last = cur - 1; }                     // model.py:795-797 (break)
-        else if (cur >= p.max_tokens - p.max_delay - 1 && !eos_detected) { eos_detected = 1; eos_countdown = p.max_delay; }
+        else if (cur >= s_max_tokens - p.max_delay - 1 && !eos_detected) { eos_detected = 1; eos_countdown = p.max_delay; }
       }
       // (the row that is embedded next stays inside the table even when all-NaN scores left the argmax sentinel in the token)
       if (ch) tok_next[lane] = min(max(tk, 0), p.e.V - 1);
       if (!finished) {
         last = cur;                                                                    // dec_step += 1
-        if (cur + 1 > p.max_tokens - 1) finished = 1;                                  // while dec_step < max_tokens-1
+        if (cur + 1 > s_max_tokens - 1) finished = 1;                                  // while dec_step < max_tokens-1
         else go = 1;
       }
       if (lane == 0) {
@@ -541,6 +558,7 @@ static int fill_embed(const dia_embed_args* a, EmbedK& e) {
   e.tokens = a->tokens; e.cur = a->cur; e.B = a->B; e.T = a->T; e.C = a->C; e.V = a->V; e.D = a->D;
   e.emb = a->emb; e.g = a->g; e.x = a->x; e.P = (bf16_raw*)a->P; e.p_plane_stride = a->p_plane_stride;
   e.p_ktiles = a->p_ktiles; e.ssq_ld = a->ssq_ld; e.ssq = a->ssq; e.cmap = a->cmap; e.act_f32 = a->act_f32;
+  e.slots = nullptr;
   return DIA_OK;
 }
 
@@ -549,7 +567,9 @@ extern "C" int dia_embed_tokens(const dia_embed_args* a, void* stream) {
   EmbedK e;
   int rc = fill_embed(a, e);
   if (rc) return rc;
-  dia_launch<k_embed_tokens>(dim3(a->B), dim3(256), 0, (hipStream_t)stream, e);
+  if (a->slots && (a->n_slots < 1 || a->n_slots > a->B)) return dia_fail(DIA_E_ARG, "dia_embed_tokens: n_slots must be in [1, B]");
+  e.slots = a->slots;
+  dia_launch<k_embed_tokens>(dim3(a->slots ? a->n_slots : a->B), dim3(256), 0, (hipStream_t)stream, e);
   return dia_check_launch("k_embed_tokens");
 }
 
@@ -572,6 +592,11 @@ extern "C" int dia_dbg_sstamps(long long* host) {
 extern "C" int dia_sample(const dia_sample_args* a, void* stream) {
   if (!a || !a->logits || !a->tokens || !a->pred || !a->cur || !a->fsm || !a->delay) return dia_fail(DIA_E_ARG, "dia_sample: null argument");
   if (a->V > VCAP || a->C > MAXC || a->C <= 0 || a->B <= 0) return dia_fail(DIA_E_ARG, "dia_sample: vocabulary > 1088 or channels > 16");
+  const int nslot = (a->slot_cfg_scale != nullptr) + (a->slot_temperature != nullptr) + (a->slot_top_p != nullptr) +
+                    (a->slot_top_k != nullptr) + (a->slot_max_tokens != nullptr);
+  if (nslot != 0 && nslot != 5) return dia_fail(DIA_E_ARG, "dia_sample: the per-slot sampling arrays come all five or none");
+  if (nslot && (!a->noise || !a->first_step)) return dia_fail(DIA_E_ARG, "dia_sample: per-slot sampling needs the noise buffer and first_step");
+  if (nslot && a->noise_steps < a->max_tokens - 1) return dia_fail(DIA_E_ARG, "dia_sample: noise buffer shorter than max_tokens-1 steps");
   if (a->temperature != 0.0f && !a->noise) return dia_fail(DIA_E_ARG, "dia_sample: temperature > 0 needs the Exp(1) noise buffer");
   if (a->temperature != 0.0f && a->noise_steps < a->max_tokens - 1) return dia_fail(DIA_E_ARG, "dia_sample: noise buffer shorter than max_tokens-1 steps");
   if (a->max_tokens > a->T || a->max_tokens < 2) return dia_fail(DIA_E_ARG, "dia_sample: max_tokens out of range");
@@ -586,6 +611,123 @@ extern "C" int dia_sample(const dia_sample_args* a, void* stream) {
   int rc = fill_embed(&ea, k.e);
   if (rc) return rc;
   const size_t smem = (size_t)a->C * (3 * VCAP) * sizeof(float);
-  dia_launch<k_sample>(dim3(a->B), dim3(a->C * 64), smem, (hipStream_t)stream, k);
+  k.slot_cfg_scale = a->slot_cfg_scale; k.slot_temperature = a->slot_temperature; k.slot_top_p = a->slot_top_p;
+  k.slot_top_k = a->slot_top_k; k.slot_max_tokens = a->slot_max_tokens;
+  if (nslot) dia_launch<k_sample<true>>(dim3(a->B), dim3(a->C * 64), smem, (hipStream_t)stream, k);
+  else dia_launch<k_sample<false>>(dim3(a->B), dim3(a->C * 64), smem, (hipStream_t)stream, k);
   return dia_check_launch("k_sample");
 }
+
+// ---- continuous batching: slot admission / retirement (one workgroup column per slot; plain vector stores, stream order only)
+namespace {
+
+struct SlotEntry { int slot, text_len, first_step, prefix_rows, max_tokens, top_k; float cfg_scale, temperature, top_p; };
+struct SlotK {
+  int n, T, C, max_delay, prefix_ld, retire;
+  const int* prefix;
+  int* tokens; int* pred; int* cur; int* fsm; int* first_step; int* text_len;
+  float* cfg_scale; float* temperature; float* top_p; int* top_k; int* max_tokens;
+  SlotEntry e[DIA_SLOTS_PER_CALL];
+};
+
+// grid (n, chunks): workgroup (i, y) fills its share of slot e[i]'s token and pred rows; workgroup (i, 0) also writes the scalars
+__global__ __launch_bounds__(256) void k_slot_admit(SlotK p) {
+  const SlotEntry& en = p.e[blockIdx.x];
+  const int b = en.slot;
+  if (blockIdx.y == 0 && threadIdx.x == 0) {
+    p.cur[b] = 1;
+    if (p.retire) {
+      p.fsm[b * 8 + 3] = 1;
+      p.text_len[b] = 0;
+    } else {
+      int4* f = reinterpret_cast<int4*>(p.fsm + b * 8);
+      f[0] = int4{0, -1, p.max_delay, 0};
+      f[1] = int4{0, 0, 0, 0};
+      p.first_step[b] = en.first_step; p.text_len[b] = en.text_len;
+      p.cfg_scale[b] = en.cfg_scale; p.temperature[b] = en.temperature; p.top_p[b] = en.top_p;
+      p.top_k[b] = en.top_k; p.max_tokens[b] = en.max_tokens;
+    }
+  }
+  if (p.retire) return;
+  const long n = (long)p.T * p.C;                       // ints per slot
+  const long npre = (long)en.prefix_rows * p.C;         // of which the prefix holds the first
+  const int* pre = p.prefix + (long)blockIdx.x * p.prefix_ld * p.C;
+  int* tok = p.tokens + (long)b * n;
+  int* prd = p.pred + (long)b * n;
+  const long stride = (long)gridDim.y * 256;
+  if ((n & 3) == 0) {                                   // slot rows start 16-byte aligned: 4 ints per store
+    const int4 neg = int4{-1, -1, -1, -1};
+    for (long j = (long)blockIdx.y * 256 + threadIdx.x; j < n / 4; j += stride) {
+      int4 v = neg;
+      if (4 * j < npre) {
+        v.x = pre[4 * j];
+        if (4 * j + 1 < npre) v.y = pre[4 * j + 1];
+        if (4 * j + 2 < npre) v.z = pre[4 * j + 2];
+        if (4 * j + 3 < npre) v.w = pre[4 * j + 3];
+      }
+      reinterpret_cast<int4*>(tok)[j] = v;
+      reinterpret_cast<int4*>(prd)[j] = neg;
+    }
+  } else {
+    for (long j = (long)blockIdx.y * 256 + threadIdx.x; j < n; j += stride) {
+      tok[j] = j < npre ? pre[j] : -1;
+      prd[j] = -1;
+    }
+  }
+}
+
+}  // namespace
+
+static int slot_fail(const char* fmt, ...) {
+  char buf[192];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(buf, sizeof buf, fmt, ap);
+  va_end(ap);
+  return dia_fail(DIA_E_ARG, buf);
+}
+
+static int slot_call(const dia_slot_admit_args* a, void* stream, bool retire) {
+  const char* who = retire ? "dia_slot_retire" : "dia_slot_admit";
+  if (!a || !a->slot || !a->cur || !a->fsm || !a->d_text_len) return slot_fail("%s: null argument", who);
+  if (a->B <= 0 || a->n < 1 || a->n > DIA_SLOTS_PER_CALL || a->n > a->B)
+    return slot_fail("%s: n must be in [1, min(B, %d)]", who, DIA_SLOTS_PER_CALL);
+  if (!retire) {
+    if (!a->text_len || !a->first_step || !a->prefix_rows || !a->max_tokens || !a->cfg_scale || !a->temperature || !a->top_p ||
+        !a->top_k || !a->prefix || !a->tokens || !a->pred || !a->d_first_step || !a->slot_cfg_scale || !a->slot_temperature ||
+        !a->slot_top_p || !a->slot_top_k || !a->slot_max_tokens)
+      return slot_fail("%s: null argument", who);
+    if (a->T < 2 || a->C <= 0 || a->C > MAXC || a->S < 0 || a->prefix_ld < 1)
+      return slot_fail("%s: bad session shape", who);
+  }
+  SlotK k = {};
+  k.n = a->n; k.T = a->T; k.C = a->C; k.max_delay = a->max_delay; k.prefix_ld = a->prefix_ld; k.retire = retire ? 1 : 0;
+  k.prefix = a->prefix; k.tokens = a->tokens; k.pred = a->pred; k.cur = a->cur; k.fsm = a->fsm;
+  k.first_step = a->d_first_step; k.text_len = a->d_text_len;
+  k.cfg_scale = a->slot_cfg_scale; k.temperature = a->slot_temperature; k.top_p = a->slot_top_p; k.top_k = a->slot_top_k;
+  k.max_tokens = a->slot_max_tokens;
+  for (int i = 0; i < a->n; ++i) {
+    SlotEntry& en = k.e[i];
+    en.slot = a->slot[i];
+    if (en.slot < 0 || en.slot >= a->B) return slot_fail("%s: slot %d outside [0, B = %d)", who, en.slot, a->B);
+    for (int j = 0; j < i; ++j)
+      if (k.e[j].slot == en.slot) return slot_fail("%s: slot %d listed twice", who, en.slot);
+    if (retire) continue;
+    en.text_len = a->text_len[i]; en.first_step = a->first_step[i]; en.prefix_rows = a->prefix_rows[i];
+    en.max_tokens = a->max_tokens[i]; en.top_k = a->top_k[i];
+    en.cfg_scale = a->cfg_scale[i]; en.temperature = a->temperature[i]; en.top_p = a->top_p[i];
+    if (en.text_len < 0 || en.text_len > a->S) return slot_fail("%s: text_len %d outside [0, S = %d]", who, en.text_len, a->S);
+    if (en.first_step < 1 || en.first_step > a->T) return slot_fail("%s: first_step %d outside [1, T = %d]", who, en.first_step, a->T);
+    if (en.max_tokens < 2 || en.max_tokens > a->T) return slot_fail("%s: max_tokens %d outside [2, T = %d]", who, en.max_tokens, a->T);
+    if (en.prefix_rows < 1 || en.prefix_rows > a->prefix_ld || en.prefix_rows > a->T)
+      return slot_fail("%s: prefix_rows %d outside [1, min(prefix_ld, T)]", who, en.prefix_rows);
+    if (en.top_k < 0) return slot_fail("%s: top_k %d is negative", who, en.top_k);
+  }
+  const long n4 = ((long)a->T * a->C + 3) / 4;
+  const int chunks = retire ? 1 : (int)std::min<long>(64, std::max<long>(1, (n4 + 1023) / 1024));    // ~4 stores of each kind per thread
+  dia_launch<k_slot_admit>(dim3(a->n, chunks), dim3(256), 0, (hipStream_t)stream, k);
+  return dia_check_launch("k_slot_admit");
+}
+
+extern "C" int dia_slot_admit(const dia_slot_admit_args* a, void* stream) { return slot_call(a, stream, false); }
+extern "C" int dia_slot_retire(const dia_slot_admit_args* a, void* stream) { return slot_call(a, stream, true); }

@@ -22,7 +22,7 @@ ATTN_SELF, ATTN_CROSS, ATTN_ENC = 0, 1, 2
 
 EXPORTS = (
     "dia_last_error", "dia_abi_version", "dia_device_count", "dia_set_tuning", "dia_get_tuning", "dia_has_experiments", "dia_gemm", "dia_gemm_timed", "dia_mlp_fused", "dia_mlp_fused_timed", "dia_engine_mlp_fused", "dia_attn", "dia_attn_scratch_floats", "dia_enc_kv_prep", "dia_enc_attn", "dia_dec_prefill_embed", "dia_dec_prefill_kv", "dia_dec_prefill_attn",
-    "dia_embed_text", "dia_embed_tokens", "dia_sample", "dia_prefetch", "dia_engine_create", "dia_engine_destroy",
+    "dia_embed_text", "dia_embed_tokens", "dia_sample", "dia_slot_admit", "dia_slot_retire", "dia_prefetch", "dia_engine_create", "dia_engine_destroy",
     "dia_engine_decode", "dia_engine_set_prefetch", "dia_engine_step_logits_only", "dia_engine_profile_step", "dia_engine_time_step", "dia_timed_kernel_name", "dia_engine_launches_per_step", "dia_mxfp8_classes",
     "dia_seg_mlp", "dia_seg_workspace_bytes", "dia_seg_workspace_control_bytes", "dia_seg_slots", "dia_seg_supported", "dia_seg_error",
 )
@@ -96,6 +96,7 @@ class EmbedArgs(C.Structure):
         ("emb", C.c_void_p), ("g", C.c_void_p), ("x", C.c_void_p), ("P", C.c_void_p),
         ("p_plane_stride", C.c_int64), ("p_ktiles", C.c_int32), ("ssq_ld", C.c_int32), ("ssq", C.c_void_p),
         ("cmap", C.c_void_p),
+        ("slots", C.c_void_p), ("n_slots", C.c_int32), ("_pad0", C.c_int32),
     ]
 
 
@@ -109,6 +110,28 @@ class SampleArgs(C.Structure):
         ("delay", C.c_void_p), ("noise", C.c_void_p), ("noise_steps", C.c_int32), ("_pad0", C.c_int32),
         ("tokens", C.c_void_p), ("pred", C.c_void_p), ("cur", C.c_void_p), ("fsm", C.c_void_p),
         ("first_step", C.c_void_p), ("embed", EmbedArgs),
+        ("slot_cfg_scale", C.c_void_p), ("slot_temperature", C.c_void_p), ("slot_top_p", C.c_void_p),
+        ("slot_top_k", C.c_void_p), ("slot_max_tokens", C.c_void_p),
+    ]
+
+
+SLOTS_PER_CALL = 64                                       # DIA_SLOTS_PER_CALL
+
+
+class SlotAdmitArgs(C.Structure):
+    """dia_slot_admit_args: the per-slot arrays up to `top_k` are HOST arrays read during the call, `prefix` and everything
+    behind it are device pointers"""
+    _fields_ = [
+        ("B", C.c_int32), ("T", C.c_int32), ("C", C.c_int32), ("S", C.c_int32), ("max_delay", C.c_int32), ("n", C.c_int32),
+        ("slot", C.POINTER(C.c_int32)), ("text_len", C.POINTER(C.c_int32)), ("first_step", C.POINTER(C.c_int32)),
+        ("prefix_rows", C.POINTER(C.c_int32)), ("max_tokens", C.POINTER(C.c_int32)),
+        ("cfg_scale", C.POINTER(C.c_float)), ("temperature", C.POINTER(C.c_float)), ("top_p", C.POINTER(C.c_float)),
+        ("top_k", C.POINTER(C.c_int32)),
+        ("prefix", C.c_void_p), ("prefix_ld", C.c_int32), ("_pad0", C.c_int32),
+        ("tokens", C.c_void_p), ("pred", C.c_void_p), ("cur", C.c_void_p), ("fsm", C.c_void_p),
+        ("d_first_step", C.c_void_p), ("d_text_len", C.c_void_p),
+        ("slot_cfg_scale", C.c_void_p), ("slot_temperature", C.c_void_p), ("slot_top_p", C.c_void_p),
+        ("slot_top_k", C.c_void_p), ("slot_max_tokens", C.c_void_p),
     ]
 
 
@@ -210,6 +233,8 @@ def lib() -> C.CDLL:
                                  C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     L.dia_embed_tokens.argtypes = [C.POINTER(EmbedArgs), C.c_void_p]
     L.dia_sample.argtypes = [C.POINTER(SampleArgs), C.c_void_p]
+    L.dia_slot_admit.argtypes = [C.POINTER(SlotAdmitArgs), C.c_void_p]
+    L.dia_slot_retire.argtypes = [C.POINTER(SlotAdmitArgs), C.c_void_p]
     L.dia_prefetch.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_void_p]
     L.dia_engine_create.argtypes = [C.POINTER(EngineDesc), C.c_void_p, C.POINTER(C.c_void_p)]
     L.dia_engine_destroy.argtypes = [C.c_void_p]

@@ -100,6 +100,22 @@ def generate_long_codes(dia, text: str, *, chunk_size: int = 0, max_new_tokens: 
     return out
 
 
+def generate_chunks_codes(dia, text: str, *, slots: int = 8, chunk_size: int = 0, max_new_tokens: int = 3072, cfg_scale: float = 3.0,
+                          temperature: float = 1.3, top_p: float = 0.95, cfg_filter_top_k: int = 35,
+                          seed: Optional[int] = None) -> List[np.ndarray]:
+    """The same chunk plan WITHOUT the chain: every batch of chunks is an independent utterance (no prompt), so they share
+    `slots` slots of one continuously batched session (Dia.generate_batch(slots=N)) instead of running one after the other.
+    A chain stays sequential (generate_long_codes): batch i + 1 needs the codes of batch i."""
+    if not text or text.isspace():
+        raise ValueError("Text input cannot be empty.")
+    plan = plan_batches(text, chunk_size, max_new_tokens)
+    T_cap = dia.config.data.audio_length
+    out = dia.generate_batch([bt for bt, _ in plan], max_tokens=[min(T_cap, 1 + budget) for _, budget in plan], cfg_scale=cfg_scale,
+                             temperature=temperature, top_p=top_p, cfg_filter_top_k=cfg_filter_top_k,
+                             seeds=None if seed is None else [seed + i for i in range(len(plan))], slots=slots)
+    return [c for c in out if c.shape[-1] > 0]
+
+
 def generate_long(dia, text: str, **kw) -> Optional[np.ndarray]:
     """as the front-end: decode every batch, join with 0.2 s of silence (app.py:238-250).  Needs the codec."""
     segs: List[np.ndarray] = []

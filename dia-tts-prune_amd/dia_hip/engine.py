@@ -453,6 +453,20 @@ class DeviceWeights:
 
 
 @dataclass
+class Request:
+    """One utterance for a continuously batched session (DecodeSession.open / admit / serve): what the reference's generate()
+    takes per call (model.py:631-646).  max_tokens None = the session's."""
+    text_ids: np.ndarray
+    seed: Optional[int] = None
+    max_tokens: Optional[int] = None
+    cfg_scale: float = 3.0
+    temperature: float = 1.3
+    top_p: float = 0.95
+    top_k: int = 35
+    audio_prompt: Optional[np.ndarray] = None      # codes [Tp, C]; the prompt rows are replayed through the decode step
+
+
+@dataclass
 class UtteranceResult:
     tokens: np.ndarray          # int32 [T, C] token buffer (DecoderOutput.generated_tokens)
     codes: np.ndarray           # rows [prefill_step : last_step+1]   (model.py:831)
@@ -470,7 +484,7 @@ class DecodeSession:
                  noise: Optional[torch.Tensor] = None, ignore_eos: bool = False,
                  teacher_tokens: Optional[Sequence[np.ndarray]] = None, stream: Optional[torch.cuda.Stream] = None,
                  s_cap: Optional[int] = None, audio_prompts: Optional[Sequence[Optional[np.ndarray]]] = None,
-                 prompt_prefill: str = "auto", attention: str = "auto"):
+                 prompt_prefill: str = "auto", attention: str = "auto", _slotted: bool = False):
         """audio_prompts: per utterance None or int codes [Tp, C] (reference model.py:311-353).  The prompt
         rows are replayed through the decode step before sampling starts (semantics: oracle.generate), or — with
         bf16 caches — prefilled as one packed MFMA batch; prompt_prefill="replay" forces the replay.
@@ -626,9 +640,13 @@ class DecodeSession:
 
         self.sample_params = dict(cfg_scale=float(cfg_scale), temperature=float(temperature), top_p=float(top_p),
                                   top_k=int(top_k or 0))
+        self._pinned: List[torch.Tensor] = []    # pinned host buffers of asynchronous copies still in the stream (dropped at sync())
+        self.slotted = bool(_slotted)
+        if self.slotted:
+            self._init_slots()
         self._engine = C.c_void_p()
         self._build_engine()
-        self.prefilled = False
+        self.prefilled = self.slotted            # slots are prefilled one by one, at admission
 
     # ------------------------------------------------------------------ engine descriptor
     def _embed_args(self) -> hb.EmbedArgs:
@@ -653,8 +671,11 @@ class DecodeSession:
         s.ignore_eos, s.teacher = int(self.ignore_eos), int(self.teacher)
         s.delay, s.noise, s.noise_steps = hb.ptr(self.delay), hb.ptr(self.noise), self.noise_steps
         s.tokens, s.pred, s.cur, s.fsm = hb.ptr(self.tokens), hb.ptr(self.pred), hb.ptr(self.cur), hb.ptr(self.fsm)
-        s.first_step = hb.ptr(self.first_step) if any(f != 1 for f in self.first_steps) else None
+        s.first_step = hb.ptr(self.first_step) if self.slotted or any(f != 1 for f in self.first_steps) else None
         s.embed = self._embed_args()
+        if self.slotted:
+            s.slot_cfg_scale, s.slot_temperature, s.slot_top_p = (hb.ptr(self.slot_f32[i]) for i in range(3))
+            s.slot_top_k, s.slot_max_tokens = hb.ptr(self.slot_i32[0]), hb.ptr(self.slot_i32[1])
         return s
 
     def _build_engine(self):
@@ -734,17 +755,33 @@ class DecodeSession:
         is what the MFMA-tiled kernel wants — and so are the bidirectional attention (dia_enc_attn) and the cross-K/V projection, which find a row's
         utterance and RoPE position through row_b / seg_off; only the embedding runs per utterance.  Only the non-pad tokens of the cond row are computed (exact)."""
         L = hb.lib()
+        st = C.c_void_p(self.stream.cuda_stream)
+        self.enc_out = [None] * self.B
+        self._encode(list(enumerate(self.text_ids)), keep_encoder_out)
+        with torch.cuda.stream(self.stream):
+            if self._prompt_prefill_batched():
+                self._prompt_prefill(st)
+            ea = self._embed_args()
+            hb.check(L.dia_embed_tokens(C.byref(ea), st), "dia_embed_tokens")
+        self.prefilled = True
+
+    def _encode(self, pairs, keep_encoder_out: bool = False):
+        """The packed encoder pass + cross-K/V precompute of prefill() for a list of (utterance index, text ids): the utterances of
+        a closed batch, or the requests admitted into free slots of a running session.  row_b / seg_off / seg_len carry the
+        utterance index, so the encoder attention and the cross-K/V launch write the rows of exactly these utterances' caches.
+        Everything is enqueued on the session's stream."""
+        L = hb.lib()
         cfg, w, dev = self.cfg, self.w, self.dev
         e, d = cfg.model.encoder, cfg.model.decoder
         st = C.c_void_p(self.stream.cuda_stream)
         E, Fe = e.n_embd, e.n_hidden
         eps = float(cfg.model.normalization_layer_epsilon)
-        offs, tot, row_utt = pack_segments(self.lens)         # whole 32-key blocks per utterance (blocked V planes)
-        self.enc_out = [None] * self.B
+        utt = [int(b) for b, _ in pairs]
+        lens = [int(len(t)) for _, t in pairs]
+        offs, tot, row_seg = pack_segments(lens)              # whole 32-key blocks per utterance (blocked V planes)
         with torch.cuda.stream(self.stream):
             if tot > 0:
                 Mp, mt = tot, tot // 16
-                Lmax = _ceil(max(self.lens), 16)
                 Hmax = max(EL["heads"] for EL in w.enc_layers)
                 ekt = E // 32
                 akt = max(max(1, Hmax * HEAD_DIM // 32), max(EL["o"].a_kt for EL in w.enc_layers))   # o rows may be zero-padded
@@ -763,35 +800,36 @@ class DecodeSession:
                     views.append(ws[o_: o_ + n_el * (4 if dt == torch.float32 else 2)].view(dt).view(*sh))
                     o_ += nb
                 x, px, pa, ph, ssq, qkv, kp, vp = views          # (kp / vp: K / V planes of the attention, scratch)
-                live = [b for b in range(self.B) if self.lens[b] > 0]
+                live = [i for i in range(len(pairs)) if lens[i] > 0]      # (positions in `pairs`; utt[i] = the utterance)
                 id_off, n_ids = {}, 0
-                for b in live:
-                    id_off[b] = n_ids
-                    n_ids += _ceil(self.lens[b], 4)                # (16-byte aligned runs)
+                for i in live:
+                    id_off[i] = n_ids
+                    n_ids += _ceil(lens[i], 4)                     # (16-byte aligned runs)
                 tab = np.zeros((Mp + 2 * _ceil(self.B, 4) + n_ids,), dtype=np.int32)
-                tab[:Mp] = row_utt
+                tab[:Mp] = np.where(row_seg >= 0, np.asarray(utt, dtype=np.int32)[np.maximum(row_seg, 0)], -1)
                 o_so, o_sl = Mp, Mp + _ceil(self.B, 4)
-                tab[o_so: o_so + self.B] = offs
-                tab[o_sl: o_sl + self.B] = self.lens
+                tab[o_so + np.asarray(utt)] = offs
+                tab[o_sl + np.asarray(utt)] = lens
                 o_id = Mp + 2 * _ceil(self.B, 4)
-                for b in live:
-                    tab[o_id + id_off[b]: o_id + id_off[b] + self.lens[b]] = self.text_ids[b]
+                for i in live:
+                    tab[o_id + id_off[i]: o_id + id_off[i] + lens[i]] = pairs[i][1]
                 # pinned + asynchronous: a pageable copy blocks the host until the stream has drained, and every launch behind it starts late
                 self._pf_tab_host = torch.from_numpy(tab).pin_memory()        # (kept until the next prefill: the copy reads it in stream order)
+                self._pinned.append(self._pf_tab_host)
                 tab_d = self._pf_tab_host.to(dev, non_blocking=True)
                 row_b, seg_off, seg_len = tab_d[:Mp], tab_d[o_so: o_so + self.B], tab_d[o_sl: o_sl + self.B]
 
-                def rows(t, b, width):              # device pointer of row off_b of a [Mp, width] fp32 buffer
-                    return t.data_ptr() + offs[b] * width * 4
+                def rows(t, i, width):              # device pointer of row off_i of a [Mp, width] fp32 buffer
+                    return t.data_ptr() + offs[i] * width * 4
 
-                def planes_at(P, b, kt_):           # device pointer of m-tile off_b/16 of a plane set (bf16)
-                    return P.data_ptr() + (offs[b] // 16) * kt_ * 512 * 2
+                def planes_at(P, i, kt_):           # device pointer of m-tile off_i/16 of a plane set (bf16)
+                    return P.data_ptr() + (offs[i] // 16) * kt_ * 512 * 2
 
-                for b in live:
-                    ids = tab_d[o_id + id_off[b]: o_id + id_off[b] + self.lens[b]]
-                    hb.check(L.dia_embed_text(hb.ptr(ids), self.lens[b], hb.ptr(w.enc_emb), E, hb.ptr(w.enc_layers[0]["g_sa"]),
-                                              rows(x, b, E), planes_at(px, b, ekt), px[0].numel(), ekt,
-                                              ssq.data_ptr() + offs[b] * 4, Mp, hb.ptr(w.enc_cmap_first), st), "dia_embed_text")
+                for i in live:
+                    ids = tab_d[o_id + id_off[i]: o_id + id_off[i] + lens[i]]
+                    hb.check(L.dia_embed_text(hb.ptr(ids), lens[i], hb.ptr(w.enc_emb), E, hb.ptr(w.enc_layers[0]["g_sa"]),
+                                              rows(x, i, E), planes_at(px, i, ekt), px[0].numel(), ekt,
+                                              ssq.data_ptr() + offs[i] * 4, Mp, hb.ptr(w.enc_cmap_first), st), "dia_embed_text")
 
                 gemm = partial(_launch_gemm, st, M=Mp, ssq=ssq, ssq_ld=Mp, width=E, eps=eps, w_planes=w.weight_planes)
 
@@ -836,15 +874,10 @@ class DecodeSession:
                         gemm(px, ekt, DL["ckv"], hb.EPI_CROSSKV, ssq_in=True, kv=cross_kv(self.k_cross[i], self.v_cross[i]),
                              strip_map=DL["smap_ckv"], row_map=(row_b, seg_off))
                 if keep_encoder_out:
-                    for b in live:
-                        Lb, o = self.lens[b], offs[b]
+                    for i in live:
+                        Lb, o = lens[i], offs[i]
                         inv = torch.rsqrt(ssq[:, o: o + Lb].sum(dim=0) / E + eps)
-                        self.enc_out[b] = (x[o: o + Lb] * inv[:, None] * w.enc_norm[None, :]).clone()
-            if self._prompt_prefill_batched():
-                self._prompt_prefill(st)
-            ea = self._embed_args()
-            hb.check(L.dia_embed_tokens(C.byref(ea), st), "dia_embed_tokens")
-        self.prefilled = True
+                        self.enc_out[utt[i]] = (x[o: o + Lb] * inv[:, None] * w.enc_norm[None, :]).clone()
 
     # ------------------------------------------------------------------ audio-prompt prefill, batched
     def _prompt_prefill_batched(self) -> bool:
@@ -922,6 +955,8 @@ class DecodeSession:
     def ensure_noise(self, rows: int):
         """Make the Exp(1) rows [0, rows) resident (no-op for explicit noise / greedy sampling).  Step number s of
         an utterance reads row s - first_step, so `rows` = decode steps enqueued so far is always enough."""
+        if self.slotted:
+            return self._ensure_slot_noise(int(rows) - self._issued)
         rows = min(int(rows), self.noise_steps)
         if self._gens is None or rows <= self._noise_rows:
             return
@@ -947,8 +982,11 @@ class DecodeSession:
         if not self.prefilled:
             raise hb.DiaHipError("decode() before prefill()")
         self.ensure_noise(self._issued + int(n_steps))
-        hb.check(hb.lib().dia_engine_decode(self._engine, int(n_steps), int(bool(use_graph))), "dia_engine_decode")
+        self._enqueue_steps(int(n_steps), use_graph)
         self._issued += int(n_steps)
+
+    def _enqueue_steps(self, n_steps: int, use_graph: bool):
+        hb.check(hb.lib().dia_engine_decode(self._engine, int(n_steps), int(bool(use_graph))), "dia_engine_decode")
 
     def profile_step(self) -> np.ndarray:
         """per-launch milliseconds of one eager decode step (HIP events on the engine's stream)."""
@@ -984,6 +1022,7 @@ class DecodeSession:
 
     def sync(self):
         self.stream.synchronize()
+        self._pinned.clear()
 
     def steps_total(self) -> int:
         return self.max_tokens - self.prefill_step
@@ -1011,8 +1050,8 @@ class DecodeSession:
         lg = self.logits[: self.R, : self.C * self.V].reshape(self.B, 2, self.C, self.V)
         return lg.cpu().numpy()
 
-    def results(self) -> List[UtteranceResult]:
-        self.sync()
+    def _raise_if_invalid(self):
+        """after a sync: raise when a persistent kernel of the step gave up waiting (results invalid)"""
         if int(self.mlp_barrier[1].item()) != 0:
             raise hb.DiaHipError("fused MLP kernel: a workgroup gave up waiting at the grid barrier; results are invalid")
         code = self.seg_error()
@@ -1020,6 +1059,10 @@ class DecodeSession:
             self.seg_ws[: int(hb.lib().dia_seg_workspace_control_bytes())].zero_()       # counters are inconsistent after a give-up
             raise hb.DiaHipError(f"persistent MLP segment: an in-kernel wait timed out (code {code}: 1 x1, 2 hidden, 3 wo partials, "
                                  f"4 x2) — were all 256 workgroups resident?  Results are invalid; set DIA_TUNE=seg=0 to run the launches")
+
+    def results(self) -> List[UtteranceResult]:
+        self.sync()
+        self._raise_if_invalid()
         tok = self.tokens.cpu().numpy()
         prd = self.pred.cpu().numpy()
         fsm = self.fsm.cpu().numpy()
@@ -1028,6 +1071,257 @@ class DecodeSession:
         for b in range(self.B):
             last = int(fsm[b, 4]) if fsm[b, 3] else int(cur[b]) - 1
             out.append(UtteranceResult(tok[b], tok[b, self.first_steps[b]: last + 1].copy(), last, prd[b], self.lens[b]))   # model.py:831
+        return out
+
+    # ------------------------------------------------------------------ continuous batching (slots)
+    @classmethod
+    def open(cls, w: DeviceWeights, slots: int, *, s_cap: Optional[int] = None, kv_dtype: str = "bf16",
+             max_tokens: Optional[int] = None, ignore_eos: bool = False, stream: Optional[torch.cuda.Stream] = None,
+             cfg_scale: float = 3.0, temperature: float = 1.3, top_p: float = 0.95, top_k: int = 35,
+             attention: str = "auto") -> "DecodeSession":
+        """A session of `slots` PARKED slots for a stream of requests: admit() puts a request into a free slot between two decode
+        steps, the step graph (captured once) serves whatever the slots hold, retire() parks a finished one; serve() is the
+        driver loop.  Cross caches are sized for texts of `s_cap` bytes (default: the encoder's text_length), the noise buffer for
+        `max_tokens` steps per slot (default: audio_length) — a request's own max_tokens may be smaller, not larger.  The sampling
+        arguments are what a parked slot holds until its first admission; every request brings its own."""
+        if int(slots) < 1:
+            raise ValueError("slots must be >= 1")
+        if float(temperature) == 0.0:
+            temperature = 1.0                      # (the noise buffer is always allocated; requests bring their own temperature)
+        cap = w.cfg.data.text_length if s_cap is None else int(s_cap)
+        if not (1 <= cap <= w.cfg.data.text_length):
+            raise ValueError(f"s_cap must be in [1, {w.cfg.data.text_length}]")
+        empty = np.zeros((0,), dtype=np.int32)
+        s = cls(w, [empty] * int(slots), kv_dtype=kv_dtype, max_tokens=max_tokens, cfg_scale=cfg_scale, temperature=temperature,
+                top_p=top_p, top_k=top_k, ignore_eos=ignore_eos, stream=stream, s_cap=_ceil(cap, 32), attention=attention,
+                _slotted=True)
+        s.text_cap = cap                           # (the caches hold whole 32-key blocks; requests are held to what was asked for)
+        return s
+
+    def _init_slots(self):
+        """Per-slot sampling state on the device (dia_sample_args.slot_*), every slot parked, host-side slot table."""
+        B, dev, sp = self.B, self.dev, self.sample_params
+        self.text_cap = self.S
+        self.slot_f32 = [torch.full((B,), float(sp[k]), dtype=torch.float32).to(dev) for k in ("cfg_scale", "temperature", "top_p")]
+        self.slot_i32 = [torch.full((B,), int(v), dtype=torch.int32).to(dev) for v in (sp["top_k"], self.max_tokens)]
+        fsm = np.zeros((B, 8), dtype=np.int32)
+        fsm[:, 1], fsm[:, 2], fsm[:, 3] = -1, self.max_delay, 1             # done: a parked slot samples nothing
+        self.fsm = torch.from_numpy(fsm).to(dev)
+        self._gens = None                        # (one generator per ADMISSION, below)
+        self._live: Dict[int, dict] = {}         # slot -> request, first_step, max_tokens, generator, noise rows resident, _issued at admission
+        self._parked = set(range(B))
+
+    def free_slots(self) -> List[int]:
+        return [b for b in range(self.B) if b not in self._live]
+
+    def _as_request(self, r) -> Request:
+        if not isinstance(r, Request):
+            r = Request(np.asarray(r, dtype=np.int32))
+        mt = self.max_tokens if r.max_tokens is None else int(r.max_tokens)
+        ids = np.asarray(r.text_ids, dtype=np.int32).reshape(-1)
+        if len(ids) > self.text_cap:
+            raise ValueError(f"request text of {len(ids)} bytes exceeds the session's s_cap = {self.text_cap}")
+        if not (2 <= mt <= self.T):
+            raise ValueError(f"max_tokens must be in [2, {self.T}]")
+        if mt > self.max_tokens:
+            raise ValueError(f"max_tokens {mt} exceeds the session's {self.max_tokens} (the noise buffer's steps per slot)")
+        pr = r.audio_prompt
+        if pr is not None:
+            pr = np.asarray(pr)
+            if pr.ndim == 3 and pr.shape[0] == 1:
+                pr = pr[0]
+            if pr.ndim != 2 or pr.shape[1] != self.C:
+                raise ValueError(f"Unexpected audio_prompt shape: {pr.shape}. Expected [T, C] or [1, T, C].")   # model.py:316
+            if 1 + pr.shape[0] + self.max_delay > self.T:
+                raise ValueError(f"audio prompt of {pr.shape[0]} frames does not fit audio_length {self.T}")
+        return Request(ids, r.seed, mt, float(r.cfg_scale), float(r.temperature), float(r.top_p), int(r.top_k or 0), pr)
+
+    def admit(self, requests: Sequence) -> List[int]:
+        """Put each request (a Request, or bare text ids with the defaults) into a free slot; returns the slot ids.  Enqueues, on the
+        session's stream and without synchronising: the packed encoder pass + cross-K/V of the new texts into their slots' caches,
+        dia_slot_admit (token rows, state machine, sampling values) and the first input embedding of the admitted slots only.
+        The caches of a re-used slot are not cleared (DESIGN.md "Continuous batching")."""
+        if not self.slotted:
+            raise hb.DiaHipError("admit() needs a session made by DecodeSession.open()")
+        reqs = [self._as_request(r) for r in requests]           # every ValueError before anything is enqueued
+        free = self.free_slots()
+        if len(reqs) > len(free):
+            raise hb.DiaHipError(f"admit(): {len(reqs)} requests for {len(free)} free slots")
+        pairs = list(zip(free, reqs))
+        for i in range(0, len(pairs), hb.SLOTS_PER_CALL):
+            self._admit(pairs[i: i + hb.SLOTS_PER_CALL])
+        return [b for b, _ in pairs]
+
+    def _admit(self, pairs):
+        from .tokens import delayed_prefill
+        if not pairs:
+            return
+        for b, _ in pairs:
+            if b in self._live:
+                raise hb.DiaHipError(f"slot {b} is admitted twice before it was collected")
+        pre = [delayed_prefill(self.cfg, r.audio_prompt) for _, r in pairs]         # (rows [P, C], first sampled step)
+        self._enqueue_admit(pairs, pre)
+        for (b, r), (_, pstep) in zip(pairs, pre):
+            g = None
+            if r.temperature != 0.0:             # row 0 of the slot's noise is this request's first draw
+                g = torch.Generator()
+                g.seed() if r.seed is None else g.manual_seed(int(r.seed))
+            self._live[b] = dict(req=r, first_step=int(pstep), gen=g, rows=0, t0=self._issued)
+            self._parked.discard(b)
+            self.lens[b], self.first_steps[b] = len(r.text_ids), int(pstep)
+
+    def _enqueue_admit(self, pairs, pre):
+        """the device side of an admission, in stream order: encoder + cross-K/V, dia_slot_admit, first embedding of these slots"""
+        L, n = hb.lib(), len(pairs)
+        st = C.c_void_p(self.stream.cuda_stream)
+        self._encode([(b, r.text_ids) for b, r in pairs])
+        ld = max(p.shape[0] for p, _ in pre)
+        n_pre = n * ld * self.C
+        host = np.full((_ceil(n_pre, 4) + n,), -1, dtype=np.int32)                  # prefix rows, then the slot list
+        for i, (p_, _) in enumerate(pre):
+            host[i * ld * self.C: i * ld * self.C + p_.size] = np.asarray(p_, dtype=np.int32).reshape(-1)
+        host[_ceil(n_pre, 4):] = [b for b, _ in pairs]
+        pin = torch.from_numpy(host).pin_memory()
+        self._pinned.append(pin)
+        i32 = lambda v: (C.c_int32 * n)(*[int(x) for x in v])
+        f32 = lambda v: (C.c_float * n)(*[float(x) for x in v])
+        with torch.cuda.stream(self.stream):
+            dev_tab = pin.to(self.dev, non_blocking=True)
+            a = self._slot_args(n, [b for b, _ in pairs])
+            a.text_len, a.first_step = i32(len(r.text_ids) for _, r in pairs), i32(ps for _, ps in pre)
+            a.prefix_rows, a.max_tokens = i32(p_.shape[0] for p_, _ in pre), i32(r.max_tokens for _, r in pairs)
+            a.cfg_scale, a.temperature, a.top_p = (f32(getattr(r, k) for _, r in pairs) for k in ("cfg_scale", "temperature", "top_p"))
+            a.top_k = i32(r.top_k for _, r in pairs)
+            a.prefix, a.prefix_ld = dev_tab.data_ptr(), ld
+            hb.check(L.dia_slot_admit(C.byref(a), st), "dia_slot_admit")
+            ea = self._embed_args()
+            ea.slots, ea.n_slots = dev_tab.data_ptr() + 4 * _ceil(n_pre, 4), n
+            hb.check(L.dia_embed_tokens(C.byref(ea), st), "dia_embed_tokens")
+
+    def _slot_args(self, n: int, slots: Sequence[int]) -> hb.SlotAdmitArgs:
+        a = hb.SlotAdmitArgs()
+        a.B, a.T, a.C, a.S, a.max_delay, a.n = self.B, self.T, self.C, self.S, self.max_delay, n
+        a.slot = (C.c_int32 * n)(*[int(b) for b in slots])
+        a.tokens, a.pred, a.cur, a.fsm = hb.ptr(self.tokens), hb.ptr(self.pred), hb.ptr(self.cur), hb.ptr(self.fsm)
+        a.d_first_step, a.d_text_len = hb.ptr(self.first_step), hb.ptr(self.text_len)
+        a.slot_cfg_scale, a.slot_temperature, a.slot_top_p = (hb.ptr(t) for t in self.slot_f32)
+        a.slot_top_k, a.slot_max_tokens = (hb.ptr(t) for t in self.slot_i32)
+        return a
+
+    def retire(self, slots: Sequence[int]):
+        """Park slots (stream order): done, one self-attention key, no cross-attention keys per step until the next admission."""
+        slots = [int(b) for b in slots]
+        for b in slots:
+            if b in self._live:
+                raise hb.DiaHipError(f"slot {b} is live: collect() it before retiring it")
+        for i in range(0, len(slots), hb.SLOTS_PER_CALL):
+            self._enqueue_retire(slots[i: i + hb.SLOTS_PER_CALL])
+        for b in slots:
+            self._parked.add(b)
+            self.lens[b] = 0
+
+    def _enqueue_retire(self, part):
+        a = self._slot_args(len(part), part)
+        hb.check(hb.lib().dia_slot_retire(C.byref(a), C.c_void_p(self.stream.cuda_stream)), "dia_slot_retire")
+
+    def _steps_left(self, b: int) -> int:
+        """decode steps a live slot can still run: it starts at step 1 and its last step is max_tokens - 1"""
+        sl = self._live[b]
+        return sl["req"].max_tokens - 1 - (self._issued - sl["t0"])
+
+    def _ensure_slot_noise(self, n_steps: int):
+        """Every live slot's Exp(1) rows for its next `n_steps` steps: the slot's own generator, restarted at admission, continues
+        where it stopped (row r of a slot = its request's draw number r, read at step first_step + r)."""
+        todo = []
+        for b, sl in self._live.items():
+            if sl["gen"] is None:
+                continue
+            done = self._issued - sl["t0"]
+            need = min(done + int(n_steps), sl["req"].max_tokens - 1)
+            if need > sl["rows"]:
+                todo.append((b, sl, sl["rows"], need))
+        if not todo:
+            return
+
+        def draw(job):
+            _, sl, r0, r1 = job
+            t = torch.empty(r1 - r0, self.C, self.V, dtype=torch.float32)
+            t.exponential_(1.0, generator=sl["gen"])
+            return t
+
+        if len(todo) > 1:
+            from concurrent.futures import ThreadPoolExecutor
+            with ThreadPoolExecutor(max_workers=min(len(todo), 8)) as pool:       # torch releases the GIL while it draws
+                parts = list(pool.map(draw, todo))
+        else:
+            parts = [draw(todo[0])]
+        for (b, sl, r0, r1), t in zip(todo, parts):
+            self._upload_noise(b, r0, t)
+            sl["rows"] = r1
+
+    def _upload_noise(self, b: int, r0: int, rows: torch.Tensor):
+        with torch.cuda.stream(self.stream):
+            self.noise[b, r0: r0 + rows.shape[0]].copy_(rows, non_blocking=False)
+
+    def _read_state(self):
+        """(fsm [B, 8], cur [B]) on the host, after a sync"""
+        self.sync()
+        self._raise_if_invalid()
+        return self.fsm.cpu().numpy(), self.cur.cpu().numpy()
+
+    def _read_slot(self, b: int):
+        """(token rows, raw samples) of slot b on the host"""
+        return self.tokens[b].cpu().numpy(), self.pred[b].cpu().numpy()
+
+    def finished(self) -> List[int]:
+        """live slots whose utterance has ended (synchronises the stream)"""
+        fsm, _ = self._read_state()
+        return [b for b in sorted(self._live) if fsm[b, 3]]
+
+    def collect(self, b: int) -> UtteranceResult:
+        """Result of a finished (or abandoned) live slot — the fields and slicing of results() — and the slot becomes free."""
+        sl = self._live[b]
+        fsm, cur = self._read_state()
+        tok, prd = self._read_slot(b)
+        last = int(fsm[b, 4]) if fsm[b, 3] else int(cur[b]) - 1
+        del self._live[b]
+        return UtteranceResult(tok, tok[sl["first_step"]: last + 1].copy(), last, prd, len(sl["req"].text_ids))   # model.py:831
+
+    def serve_iter(self, requests: Sequence, poll: int = 64, use_graph: bool = True):
+        """The driver loop: fill free slots from the queue, decode up to `poll` steps, collect what finished, retire what stays
+        empty — until the queue is empty and every slot is parked.  Yields (request index, UtteranceResult) as utterances end."""
+        if not self.slotted:
+            raise hb.DiaHipError("serve() needs a session made by DecodeSession.open()")
+        reqs = [self._as_request(r) for r in requests]           # every ValueError before anything is enqueued
+        nxt, owner = 0, {}
+        while nxt < len(reqs) or self._live:
+            free = self.free_slots()
+            take = min(len(free), len(reqs) - nxt)
+            if take:
+                pairs = list(zip(free[:take], reqs[nxt: nxt + take]))
+                for i in range(0, take, hb.SLOTS_PER_CALL):
+                    self._admit(pairs[i: i + hb.SLOTS_PER_CALL])
+                for i, (b, _) in enumerate(pairs):
+                    owner[b] = nxt + i
+                nxt += take
+            idle = [b for b in self.free_slots() if b not in self._parked]
+            if idle:
+                self.retire(idle)
+            n = max(1, min(int(poll), max(self._steps_left(b) for b in self._live)))
+            self.decode(n, use_graph)
+            self.ensure_noise(self._issued + int(poll))          # the next chunk's noise is drawn while this one runs
+            for b in self.finished():
+                yield owner.pop(b), self.collect(b)
+        idle = [b for b in range(self.B) if b not in self._parked]
+        if idle:
+            self.retire(idle)
+
+    def serve(self, requests: Sequence, poll: int = 64, use_graph: bool = True) -> List[UtteranceResult]:
+        """serve_iter() to the end; results in request order."""
+        reqs = list(requests)
+        out: List[Optional[UtteranceResult]] = [None] * len(reqs)
+        for i, r in self.serve_iter(reqs, poll, use_graph):
+            out[i] = r
         return out
 
     # ------------------------------------------------------------------ accounting (SURVEY.md §8d)

@@ -12,6 +12,7 @@ reference hard-codes B=1, dia/state.py:83-84) and a ``load_dac`` switch for offl
 from __future__ import annotations
 
 import time
+from dataclasses import dataclass
 from enum import Enum
 from pathlib import Path
 from typing import Dict, List, Optional, Sequence, Union
@@ -21,7 +22,7 @@ import torch
 
 from . import binding as hb
 from .config import DiaConfig
-from .engine import DecodeSession, DeviceWeights, UtteranceResult
+from .engine import DecodeSession, DeviceWeights, Request, UtteranceResult
 from .tokens import codes_for_codec, effective_text, encode_text
 from . import weights as W
 
@@ -35,6 +36,26 @@ class ComputeDtype(str, Enum):
 
     def to_dtype(self) -> torch.dtype:
         return {"float32": torch.float32, "float16": torch.float16, "bfloat16": torch.bfloat16}[self.value]
+
+
+@dataclass
+class GenerationRequest:
+    """One utterance of Dia.generate_stream / generate_batch(slots=N): the per-call arguments of generate().  None = the call's
+    scalar argument of the same name."""
+    text: str
+    max_tokens: Optional[int] = None
+    cfg_scale: Optional[float] = None
+    temperature: Optional[float] = None
+    top_p: Optional[float] = None
+    cfg_filter_top_k: Optional[int] = None
+    seed: Optional[int] = None
+    audio_prompt: Optional[np.ndarray] = None
+    audio_prompt_text: Optional[str] = None
+
+
+def _nth(arg, i):
+    """the i-th of a per-request sequence, or the scalar itself"""
+    return arg[i] if isinstance(arg, (list, tuple, np.ndarray)) else arg
 
 
 def _default_device() -> torch.device:
@@ -214,14 +235,72 @@ class Dia:
                 s.close()
         return res
 
+    def _requests(self, items, max_tokens, cfg_scale, temperature, top_p, top_k, seeds, audio_prompts, audio_prompt_texts) -> List[Request]:
+        """texts or GenerationRequests + scalar-or-per-request arguments -> engine requests"""
+        out = []
+        for i, it in enumerate(items):
+            g = it if isinstance(it, GenerationRequest) else GenerationRequest(str(it))
+            pick = lambda own, arg: own if own is not None else _nth(arg, i)
+            prompt = pick(g.audio_prompt, audio_prompts)
+            if isinstance(prompt, torch.Tensor):
+                prompt = prompt.detach().cpu().numpy()
+            ptext = pick(g.audio_prompt_text, audio_prompt_texts)
+            if prompt is not None and not ptext:
+                raise ValueError("`audio_prompt_text` is required when `audio_prompt` is provided.")
+            mt = pick(g.max_tokens, max_tokens)
+            out.append(Request(encode_text(effective_text(g.text, ptext), self.config), seed=pick(g.seed, seeds),
+                               max_tokens=None if mt is None else int(mt), cfg_scale=float(pick(g.cfg_scale, cfg_scale)),
+                               temperature=float(pick(g.temperature, temperature)), top_p=float(pick(g.top_p, top_p)),
+                               top_k=int(pick(g.cfg_filter_top_k, top_k) or 0), audio_prompt=prompt))
+        return out
+
+    @torch.inference_mode()
+    def generate_stream(self, requests_or_texts: Sequence[Union[str, GenerationRequest]], slots: int = 8,
+                        max_tokens=None, cfg_scale=3.0, temperature=1.3, top_p=0.95, cfg_filter_top_k=35,
+                        seeds: Optional[Sequence[Optional[int]]] = None, ignore_eos: bool = False,
+                        audio_prompts: Optional[Sequence[Optional[np.ndarray]]] = None,
+                        audio_prompt_texts: Optional[Sequence[Optional[str]]] = None, poll: int = 64, s_cap: Optional[int] = None):
+        """Continuous batching: any number of utterances through `slots` slots of ONE decode session — a finished utterance's slot
+        is refilled from the queue between two decode steps, so the batch stays full while requests last.  Yields
+        (request index, codec input [1, C, T']) as utterances finish.  The sampling arguments are defaults: each may be a per-request
+        sequence, and a GenerationRequest carries its own.  Every utterance's tokens are those of generating it alone with its
+        seed (compute_dtype float32: bit for bit)."""
+        if self.model is None:
+            raise RuntimeError("no weights loaded")
+        items = list(requests_or_texts)
+        reqs = self._requests(items, max_tokens, cfg_scale, temperature, top_p, cfg_filter_top_k, seeds, audio_prompts, audio_prompt_texts)
+        if not reqs:
+            return
+        cap = max([r.max_tokens for r in reqs if r.max_tokens is not None] or [self.config.data.audio_length])
+        if any(r.max_tokens is None for r in reqs):
+            cap = self.config.data.audio_length
+        if s_cap is None:
+            s_cap = max(32, max(len(r.text_ids) for r in reqs))
+        with torch.cuda.device(self.device):
+            s = DecodeSession.open(self.model, min(int(slots), len(reqs)), s_cap=min(int(s_cap), self.config.data.text_length),
+                                   kv_dtype=self._kv_dtype(), max_tokens=cap, ignore_eos=ignore_eos)
+            try:
+                for i, res in s.serve_iter(reqs, poll=poll):
+                    yield i, codes_for_codec(res.codes, self.config)
+            finally:
+                s.close()
+
     @torch.inference_mode()
     def generate_batch(self, texts: Sequence[str], max_tokens: Optional[int] = None, cfg_scale: float = 3.0,
                        temperature: float = 1.3, top_p: float = 0.95, cfg_filter_top_k: int = 35,
                        seeds: Optional[Sequence[Optional[int]]] = None, verbose: bool = False,
                        ignore_eos: bool = False, audio_prompts: Optional[Sequence[Optional[np.ndarray]]] = None,
-                       audio_prompt_texts: Optional[Sequence[Optional[str]]] = None) -> List[np.ndarray]:
+                       audio_prompt_texts: Optional[Sequence[Optional[str]]] = None, slots: Optional[int] = None) -> List[np.ndarray]:
         """B utterances in one decode loop; returns the codec inputs [1, C, T'_b] per utterance.
-        audio_prompts: per utterance None or codes [Tp, C]; audio_prompt_texts: their transcripts."""
+        audio_prompts: per utterance None or codes [Tp, C]; audio_prompt_texts: their transcripts.
+        slots=N: the utterances share N slots of a continuously batched session instead (generate_stream); the list returned is
+        the same."""
+        if slots is not None:
+            out: List[Optional[np.ndarray]] = [None] * len(texts)
+            for i, codes in self.generate_stream(texts, slots, max_tokens, cfg_scale, temperature, top_p, cfg_filter_top_k, seeds,
+                                                 ignore_eos, audio_prompts, audio_prompt_texts):
+                out[i] = codes
+            return out
         apt = audio_prompt_texts or [None] * len(texts)
         eff = [effective_text(t, a) for t, a in zip(texts, apt)]
         res = self._run(eff, max_tokens, cfg_scale, temperature, top_p, cfg_filter_top_k, seeds, verbose, ignore_eos,

@@ -19,6 +19,8 @@
 extern "C" {
 #endif
 
+/* The version stays 8 although dia_embed_args / dia_sample_args grew at their tails and dia_slot_admit / dia_slot_retire were added
+ * (continuous batching): zero-filled tails behave as before, and a binding of the older layout fails the sizeof / export checks. */
 #define DIA_ABI_VERSION 8
 
 #define DIA_OK 0
@@ -316,6 +318,11 @@ typedef struct {
   int32_t ssq_ld;
   float* ssq;               /* [D/16][ssq_ld] */
   const int32_t* cmap;      /* as dia_gemm_args.cmap (first layer's q/k/v input order) or NULL */
+  /* device int32 [n_slots] or NULL: embed the rows of these utterances only (an admission into a running session must not
+   * touch the rows of the live ones); NULL = all B, as before.  Ignored by the sampler's own next-step embedding. */
+  const int32_t* slots;
+  int32_t n_slots;
+  int32_t _pad0;
 } dia_embed_args;
 int dia_embed_tokens(const dia_embed_args* a, void* stream);
 
@@ -350,8 +357,62 @@ typedef struct {
    * row of step cur is cur - first_step[b].  NULL = no prompt anywhere (first_step 1). */
   const int32_t* first_step;
   dia_embed_args embed;     /* next-step embedding; embed.tokens/cur are taken from above */
+  /* per-slot sampling state of a continuously batched session (device arrays [B], written by dia_slot_admit): all five or
+   * none.  NULL = the scalars above for every utterance, the kernel instantiation of a closed batch.  With them, utterance b
+   * samples with slot_*[b] (its own instantiation of the kernel: the values are workgroup-uniform, so the route choice stays
+   * a uniform branch), `max_tokens` above is the session's capacity (noise_steps >= max_tokens - 1) and `noise` is required;
+   * a slot whose temperature is 0 does not read it. */
+  const float* slot_cfg_scale;
+  const float* slot_temperature;
+  const float* slot_top_p;
+  const int32_t* slot_top_k;
+  const int32_t* slot_max_tokens;
 } dia_sample_args;
 int dia_sample(const dia_sample_args* a, void* stream);
+
+/* Continuous batching: (re)initialise the device state of `n` slots (utterance indices) of a running session in ONE launch, in
+ * stream order between two decode steps / graph replays.  For slot[i]: token rows [0, T) = the first prefix_rows[i] rows of
+ * prefix[i] (the BOS / PAD prefill or the delayed audio-prompt rows the host prepared), -1 behind them; pred rows -1;
+ * cur = 1; fsm = {0, -1, max_delay, 0, 0, 0, 0, 0}; first_step, text_len and the five per-slot sampling values.  Replaces
+ * what the reference does per call in Dia._prepare_generation (model.py:355-427) and DecoderInferenceState / DecoderOutput
+ * construction (state.py:178-208) for ONE utterance of a batch.  Caches are NOT cleared: keys at and beyond a slot's length
+ * are weighted by exactly 0 and only have to be finite, which the previous utterance's values are (DESIGN.md
+ * "Continuous batching").  The per-slot HOST arrays are read during the call (they travel as kernel arguments); at most
+ * DIA_SLOTS_PER_CALL slots per call.
+ * dia_slot_retire parks slots (reads n, slot, B and the cur / fsm / text_len pointers only): fsm[3] = 1 (done), cur = 1,
+ * text_len = 0 — an empty slot then costs one self-attention key and no cross-attention key per step. */
+#define DIA_SLOTS_PER_CALL 64
+typedef struct {
+  int32_t B, T, C, S;          /* session shape: slots, token rows, channels, text capacity of the cross caches */
+  int32_t max_delay;
+  int32_t n;                   /* slots in this call, 1..DIA_SLOTS_PER_CALL */
+  const int32_t* slot;         /* host [n], distinct, each < B */
+  const int32_t* text_len;     /* host [n], each <= S */
+  const int32_t* first_step;   /* host [n], 1 + prompt frames, each in [1, T] */
+  const int32_t* prefix_rows;  /* host [n], each in [1, prefix_ld] and <= T */
+  const int32_t* max_tokens;   /* host [n], each in [2, T] */
+  const float* cfg_scale;      /* host [n] */
+  const float* temperature;    /* host [n] */
+  const float* top_p;          /* host [n] */
+  const int32_t* top_k;        /* host [n] */
+  const int32_t* prefix;       /* DEVICE int32 [n][prefix_ld][C] */
+  int32_t prefix_ld;
+  int32_t _pad0;
+  /* device state of the session, as in dia_sample_args / dia_engine_desc */
+  int32_t* tokens;             /* [B][T][C] */
+  int32_t* pred;               /* [B][T][C] */
+  int32_t* cur;                /* [B] */
+  int32_t* fsm;                /* [B][8] */
+  int32_t* d_first_step;       /* [B] */
+  int32_t* d_text_len;         /* [B] */
+  float* slot_cfg_scale;       /* [B] ... */
+  float* slot_temperature;
+  float* slot_top_p;
+  int32_t* slot_top_k;
+  int32_t* slot_max_tokens;
+} dia_slot_admit_args;
+int dia_slot_admit(const dia_slot_admit_args* a, void* stream);
+int dia_slot_retire(const dia_slot_admit_args* a, void* stream);
 
 /* Read-only pass over [ptr, ptr+nbytes) that pulls it into the 256 MiB Infinity Cache ahead of its
  * consumer (weights of the next kernels of the decode chain); writes nothing. */
