@@ -55,12 +55,106 @@ static inline void mark(dia_engine* e, int i) {
 // was below the dense launch's in every repetition of the A/B (profiles/r05_mxfp8_speed.txt): wi, wo and the logits head at
 // <= 4 rows, wi and the logits head at 5..16 rows.  The 128..192-strip projections are bound by their fixed cost and lost
 // (+1..6 %), wo at 5..16 rows lost to the dense strip-pair split-K form (+1..4 %)
-constexpr int MXFP8_DEFAULT = 0x5070;
+constexpr int MXFP8_DEFAULT = (1 << DIA_MAT_WI | 1 << DIA_MAT_WO | 1 << DIA_MAT_LOGITS) | (1 << DIA_MAT_WI | 1 << DIA_MAT_LOGITS) << 8;
+static_assert(MXFP8_DEFAULT == 0x5070 && DIA_MAT_COUNT <= 8, "the knob mxfp8 holds one byte of class bits per row range");
 extern "C" int dia_mxfp8_classes(int rows) {
   if (rows <= 0 || rows > 16) return 0;
   const int knob = dia_tune(DIA_TUNE_MXFP8);
   const int mask = knob >= 0 ? knob : MXFP8_DEFAULT;
-  return (rows <= 4 ? mask : mask >> 8) & 0x7f;
+  return (rows <= 4 ? mask : mask >> 8) & ((1 << DIA_MAT_COUNT) - 1);
+}
+
+// The step's GEMM launches, one row per dia_step_mat (the row index is also the MXFP8 class bit): where the matrix and its streams live in
+// dia_dec_layer (the logits head: dia_engine_desc, see mat_weights), its epilogue, the planes it reads and emits, what it writes
+enum { PL_NONE = -1, PL_X, PL_A, PL_H };                // activation planes: the normed residual stream, attention output, MLP hidden
+enum { OUT_NONE, OUT_QKV, OUT_QC, OUT_LOGITS, OUT_X };  // SCALE_STORE: an fp32 buffer; RESID_EMIT: the residual stream
+struct step_mat_row {
+  int mat;
+  const void* dia_dec_layer::*w; int32_t dia_dec_layer::*kt; int32_t dia_dec_layer::*ns;      // dense tiles, kt * ns * 1024 bytes
+  const void* dia_dec_layer::*w24; const void* dia_dec_layer::*wf8;                            // 2:4 and MXFP8 streams
+  int epi, in, out, emit;
+  const int32_t* dia_dec_layer::*cmap;                  // RESID_EMIT: the consumer's compaction map and norm weight (null: the next
+  const float* dia_dec_layer::*gnext;                   // layer's g_sa, or the final norm)
+};
+#define MAT(M, m) DIA_MAT_##M, &dia_dec_layer::w_##m, &dia_dec_layer::kt_##m, &dia_dec_layer::ns_##m, &dia_dec_layer::w_##m##_24, &dia_dec_layer::w_##m##_f8
+constexpr step_mat_row STEP_MATS[DIA_MAT_COUNT] = {
+  {MAT(QKV, qkv), DIA_EPI_SCALE_STORE, PL_X, OUT_QKV, PL_NONE, nullptr, nullptr},      // q/k/v projection of the pre-SA-normed row (layers.py:541, 273-275)
+  {MAT(O, o), DIA_EPI_RESID_EMIT, PL_A, OUT_X, PL_X, &dia_dec_layer::cmap_ca, &dia_dec_layer::g_ca},       // o_proj + residual; emits the pre-CA-normed planes (layers.py:341-343, 555, 560)
+  {MAT(CQ, cq), DIA_EPI_SCALE_STORE, PL_X, OUT_QC, PL_NONE, nullptr, nullptr},         // cross-attention query (layers.py:273, 278)
+  {MAT(CO, co), DIA_EPI_RESID_EMIT, PL_A, OUT_X, PL_X, &dia_dec_layer::cmap_mlp, &dia_dec_layer::g_mlp},   // cross o_proj + residual; emits the pre-MLP-normed planes
+  {MAT(WI, wi), DIA_EPI_SWIGLU_EMIT, PL_X, OUT_NONE, PL_H, nullptr, nullptr},          // SwiGLU MLP (layers.py:95-104)
+  {MAT(WO, wo), DIA_EPI_RESID_EMIT, PL_H, OUT_X, PL_X, &dia_dec_layer::cmap_next, nullptr},
+  {DIA_MAT_LOGITS, nullptr, nullptr, nullptr, nullptr, nullptr, DIA_EPI_SCALE_STORE, PL_X, OUT_LOGITS, PL_NONE, nullptr, nullptr},   // final norm + logits (layers.py:714-717)
+};
+#undef MAT
+constexpr bool rows_in_order(int m = 0) { return m == DIA_MAT_COUNT || (STEP_MATS[m].mat == m && rows_in_order(m + 1)); }
+static_assert(rows_in_order(), "row m of STEP_MATS describes matrix m of dia_step_mat");
+
+struct mat_w { const void* w; int kt, ns; const void *w24, *wf8; };
+static mat_w mat_weights(const dia_engine* e, int l, int m) {
+  const dia_engine_desc& d = e->d;
+  if (m == DIA_MAT_LOGITS) return {d.w_logits, d.kt_logits, d.ns_logits, d.w_logits_24, d.w_logits_f8};
+  const dia_dec_layer& L = e->layers[l];
+  const step_mat_row& r = STEP_MATS[m];
+  return {L.*r.w, L.*r.kt, L.*r.ns, L.*r.w24, L.*r.wf8};
+}
+
+// The launches of one step, in order: launch(layer, what) for every one, `what` a dia_step_mat or one of the launches below.
+// enqueue_step issues them; the prefetch list and dia_engine_launches_per_step walk the same sequence.
+enum { ATTN_SELF = DIA_MAT_COUNT, ATTN_CROSS, SEG_MLP, SAMPLER };
+template <class Launch>
+static int step_sequence(const dia_engine* e, bool with_sampler, Launch&& launch) {
+  int rc = DIA_OK;                   // the first failure ends the sequence
+  auto run = [&](int l, std::initializer_list<int> seq) { for (int what : seq) if (!rc) rc = launch(l, what); };
+  for (int l = 0; l < e->d.n_layer; ++l) {
+    if (!e->seg || l == 0) run(l, {DIA_MAT_QKV});
+    run(l, {ATTN_SELF, DIA_MAT_O, DIA_MAT_CQ, ATTN_CROSS});
+    if (e->seg) run(l, {SEG_MLP});     // persistent MLP segment: co, wi, wo and the next layer's qkv in one launch
+    else run(l, {DIA_MAT_CO, DIA_MAT_WI, DIA_MAT_WO});
+  }
+  run(e->d.n_layer, {DIA_MAT_LOGITS});
+  if (with_sampler) run(e->d.n_layer, {SAMPLER});
+  return rc;
+}
+
+// wo's cross-workgroup split-K: sets g.sk / spw / nw and the scratch that goes with them; returns wo_pair (17..128 rows split K per m-tile)
+static bool wo_split_k(const dia_engine_desc& d, const dia_dec_layer& L, int R, dia_gemm_args& g) {
+  // K = 8192 over only D/16 = 128 strips: cross-workgroup split-K (fence-free slab hand-off) streams the
+  // matrix from more CUs.  M <= 4: two workgroups per strip, 12.4 -> 11.2 us per launch.  5..16 rows: four
+  // per strip, which also brings the per-wave K range down to what k_gemm16 keeps in registers (23.2 ->
+  // 18.4 us in the step at batch 8).  Shapes without a split kernel fall back to one workgroup per strip.
+  int wo_sk = (R <= 4 && L.kt_wo % 2 == 0) ? 2 : ((R <= 16 && L.kt_wo % 4 == 0) ? 4 : 1);
+  int wo_spw = 0;
+  if (R > 4 && R <= 16) {
+    // 5..16 rows: K ranges of 64 k-tiles (8 waves x 8 k-tiles keep their A fragments in registers: 160 VGPRs, one
+    // workgroup per CU) and as many strips per workgroup as it takes to stay at one round of <= 256 workgroups —
+    // dense wo (K 8192 x 128 strips): 4 ranges x 64 strip PAIRS, both tiles of a pair handed over together
+    // (14.3 -> 11.7 us); the 50 %-pruned wo (K 4096): 2 ranges x 128 strips
+    if (L.kt_wo % 64 == 0 && L.kt_wo / 64 >= 2 && L.kt_wo / 64 <= 8) wo_sk = L.kt_wo / 64;
+    if (wo_sk > 1 && L.ns_wo * wo_sk >= 512 && L.ns_wo % 2 == 0) wo_spw = 2;
+  }
+  // two-plane weights (kt_wo counts hi and lo tiles): the tuned forms take 128 weight k-tiles per workgroup, so K splits into
+  // kt_wo / 128 ranges at every row count (dense wo: 4); other hidden widths run unsplit on the generic kernel
+  const int w2_sk = (d.w_planes == 2 && L.kt_wo % 128 == 0 && L.kt_wo / 128 <= 8) ? L.kt_wo / 128 : 1;
+  if (d.w_planes == 2) { wo_sk = w2_sk; wo_spw = 0; }
+  if (dia_tune(DIA_TUNE_WO_SK) >= 1 && dia_tune(DIA_TUNE_WO_SK) <= 8 && L.kt_wo % dia_tune(DIA_TUNE_WO_SK) == 0) wo_sk = dia_tune(DIA_TUNE_WO_SK);
+  g.sk = wo_sk; g.sk_scratch = wo_sk > 1 ? d.sk_scratch : nullptr; g.sk_tickets = wo_sk > 1 ? d.sk_tickets : nullptr;
+  bool wo_pair = false;
+  if (R > 16 && R <= 128) {     // 2..8 m-tiles: split-K 4 over every m-tile (k_gemm16 with gridDim.z) when the scratch covers
+    g.sk_scratch = d.sk_scratch; g.sk_tickets = d.sk_tickets;    // it, else dia_gemm splits K by itself (two m-tiles: k_gemm32)
+    g.sk_scratch_floats = d.sk_scratch_floats > 0 ? d.sk_scratch_floats : (int64_t)(d.D / 16) * 4 * 512;
+    wo_pair = L.kt_wo % 4 == 0 && g.sk_scratch_floats >= (int64_t)((R + 15) / 16) * L.ns_wo * 4 * 256 &&
+              dia_tune(DIA_TUNE_WO_PAIR) != 0;
+    g.sk = wo_pair ? 4 : 1;
+    if (d.w_planes == 2) {
+      wo_pair = w2_sk > 1 && g.sk_scratch_floats >= (int64_t)((R + 15) / 16) * L.ns_wo * w2_sk * 256;
+      g.sk = wo_pair ? w2_sk : 1;
+    }
+  }
+  if (dia_tune(DIA_TUNE_WO_NW) > 0) g.nw = dia_tune(DIA_TUNE_WO_NW);
+  g.spw = wo_spw;
+  if (dia_tune(DIA_TUNE_WO_SPW) > 0) g.spw = dia_tune(DIA_TUNE_WO_SPW);
+  return wo_pair;
 }
 
 static int enqueue_step(dia_engine* e, bool with_sampler) {
@@ -71,16 +165,13 @@ static int enqueue_step(dia_engine* e, bool with_sampler) {
   const int akt = (max(d.q_heads, d.cq_heads) * 128) / 32;        // k-tiles of the attention planes
   const int hkt = d.F / 32;
   const long mt = d.rows_pad / 16;
-  const long xs = mt * xkt * 512, as = mt * akt * 512, hs = mt * hkt * 512;   // plane strides (elements)
+  const struct { void* p; long stride; int kt; } planes[] = {     // indexed by PL_*; plane strides in elements
+    {d.planes_x, mt * xkt * 512, xkt}, {d.planes_a, mt * akt * 512, akt}, {d.planes_h, mt * hkt * 512, hkt}};
   const int nqkv = (d.q_heads + 2 * d.kv_heads) * 128;
-  int n = 0, rc;
   // activation format of every producer -> consumer edge (common.hpp): fp32 tiles from 5 rows on, three planes below
   const int F = d.act_f32 ? 1 : 0;
   // 17..32 rows: every GEMM may split K inside dia_gemm (k_gemm32 / k_gemm32m) when it is handed the scratch
   const bool two_tiles = R > 16 && R <= 32 && d.sk_scratch && d.sk_tickets && d.sk_scratch_floats > 0;   // (k_gemm32 / k_gemm32m / blk32 only)
-  auto lend_scratch = [&](dia_gemm_args& g) {
-    if (two_tiles) { g.sk_scratch = d.sk_scratch; g.sk_tickets = d.sk_tickets; g.sk_scratch_floats = d.sk_scratch_floats; }
-  };
 
   const bool seg = e->seg;            // persistent MLP segments: co, wi, wo and the next layer's qkv in one launch
   // <= 4 rows, OPT-IN (knob wo_diag=1; measured, not adopted): wo from its diagonal layout (256 workgroups with the whole K each, no
@@ -114,187 +205,96 @@ static int enqueue_step(dia_engine* e, bool with_sampler) {
     if (sk == 1) { g.sk_scratch = nullptr; g.sk_tickets = nullptr; }
     else { g.sk_scratch = d.sk_scratch; g.sk_tickets = d.sk_tickets; }
   };
-  for (int l = 0; l < d.n_layer; ++l) {
-    const dia_dec_layer& L = e->layers[l];
+  bool wo_pair = false;             // of the wo descriptor built last
+  // the descriptor of matrix m of layer l (the logits head: l = n_layer) from its row of STEP_MATS
+  auto step_gemm = [&](int l, int m) {
+    const step_mat_row& r = STEP_MATS[m];
+    const dia_dec_layer* L = l < d.n_layer ? &e->layers[l] : nullptr;
+    const mat_w w = mat_weights(e, l, m);
     dia_gemm_args g = {};
-    if (!seg || l == 0) {
-    // q/k/v projection of the pre-SA-normed row (layers.py:541, 273-275)
-    g.A = d.planes_x; g.a_plane_stride = xs; g.a_ktiles = xkt; g.M = R;
-    g.W = L.w_qkv; g.KT = L.kt_qkv; g.nstrips = L.ns_qkv; g.epi = DIA_EPI_SCALE_STORE;
-    g.ssq_in = d.ssq; g.ssq_in_n = l > 0 ? xn_wo : d.D / 16; g.ssq_ld = d.rows_pad; g.inv_d = 1.0f / d.D; g.eps = d.eps;
-    g.out = d.qkv; g.ldo = nqkv; g.strip_map = L.smap_qkv;
-    lend_scratch(g);
-  g.act_f32 = F;            // reads x as fp32 tiles
-  g.w_planes = d.w_planes;
-  sparse24(g, L.w_qkv_24);
-  mxfp8(g, L.w_qkv_f8, 0);
-  if ((rc = dia_gemm(&g, st))) return rc; mark(e, n++);
+    g.A = planes[r.in].p; g.a_plane_stride = planes[r.in].stride; g.a_ktiles = planes[r.in].kt; g.M = R;
+    g.W = w.w; g.KT = w.kt; g.nstrips = w.ns; g.epi = r.epi; g.ssq_ld = d.rows_pad;
+    if (r.in == PL_X) {             // the normed stream: scaled by the row's inverse RMS; behind a wo, x carries wo's count of partial sums
+      g.ssq_in = d.ssq; g.ssq_in_n = (m == DIA_MAT_LOGITS || (m == DIA_MAT_QKV && l > 0)) ? xn_wo : d.D / 16; g.inv_d = 1.0f / d.D; g.eps = d.eps;
     }
+    if (r.emit != PL_NONE) { g.P = planes[r.emit].p; g.p_plane_stride = planes[r.emit].stride; g.p_ktiles = planes[r.emit].kt; }
+    switch (r.out) {
+      case OUT_QKV: g.out = d.qkv; g.ldo = nqkv; g.strip_map = L->smap_qkv; break;
+      case OUT_QC: g.out = d.qc; g.ldo = d.cq_heads * 128; g.strip_map = L->smap_cq; break;
+      case OUT_LOGITS: g.out = d.logits; g.ldo = d.ld_logits; break;
+      case OUT_X:                   // residual add; emits the planes of x * gnext in the consumer's (compacted) K order
+        g.out = d.x; g.ldo = d.D; g.ssq_out = d.ssq; g.cmap = L->*r.cmap;
+        g.gnext = r.gnext ? L->*r.gnext : ((l + 1 < d.n_layer) ? e->layers[l + 1].g_sa : d.g_final);
+        break;
+    }
+    g.w_planes = d.w_planes; g.act_f32 = r.epi == DIA_EPI_SCALE_STORE ? F : 3 * F;      // x read as fp32 tiles; the emitting epilogues: in and out
+    if (two_tiles) { g.sk_scratch = d.sk_scratch; g.sk_tickets = d.sk_tickets; g.sk_scratch_floats = d.sk_scratch_floats; }
+    if (m == DIA_MAT_WO) wo_pair = wo_split_k(d, *L, R, g);
+    if (m == DIA_MAT_WO && diag) {
+      g.W = L->w_wo_diag; g.w_layout = 1; g.nstrips = d.D / 8; g.sk = 1; g.sk_scratch = nullptr; g.sk_tickets = nullptr; g.nw = 0; g.spw = 0;
+      return g;
+    }
+    sparse24(g, w.w24);
+    mxfp8(g, w.wf8, m);
+    return g;
+  };
 
-    dia_attn_args a = {};
-    a.mode = DIA_ATTN_SELF; a.kv_dtype = d.kv_dtype; a.n_kv_heads = d.kv_heads; a.group = d.q_heads / d.kv_heads;
-    a.n_rows = R; a.kv_cap = d.T; a.q = d.qkv; a.ldq = nqkv; a.q_off = 0; a.k_off = d.q_heads * 128;
-    a.v_off = (d.q_heads + d.kv_heads) * 128; a.kc = L.k_self; a.vc = L.v_self; a.cur = d.sample.cur;
-    a.head_map = L.hmap_self; a.v_blocked = d.v_blocked; a.rope_rows = d.T + 1; a.kv_plane_stride = d.kv_plane_self;
-    a.cos_t = d.cos_t; a.sin_t = d.sin_t; a.P = d.planes_a; a.p_plane_stride = as; a.p_ktiles = akt;
-    a.scratch = d.attn_scratch; a.tickets = d.attn_tickets;
-    a.act_f32 = F;
-    if ((rc = dia_attn(&a, st))) return rc; mark(e, n++);
-
-    // o_proj + residual; emits the pre-CA-normed planes (layers.py:341-343, 555, 560)
-    g = {};
-    g.A = d.planes_a; g.a_plane_stride = as; g.a_ktiles = akt; g.M = R;
-    g.W = L.w_o; g.KT = L.kt_o; g.nstrips = L.ns_o; g.epi = DIA_EPI_RESID_EMIT;
-    g.ssq_ld = d.rows_pad; g.out = d.x; g.ldo = d.D; g.gnext = L.g_ca; g.cmap = L.cmap_ca;
-    g.P = d.planes_x; g.p_plane_stride = xs; g.p_ktiles = xkt; g.ssq_out = d.ssq;
-    lend_scratch(g);
-  g.act_f32 = 3 * F;        // attention output in, x out: both fp32 tiles
-  g.w_planes = d.w_planes;
-  sparse24(g, L.w_o_24);
-  mxfp8(g, L.w_o_f8, 1);
-  if ((rc = dia_gemm(&g, st))) return rc; mark(e, n++);
-
-    // cross-attention query (layers.py:273, 278)
-    g = {};
-    g.A = d.planes_x; g.a_plane_stride = xs; g.a_ktiles = xkt; g.M = R;
-    g.W = L.w_cq; g.KT = L.kt_cq; g.nstrips = L.ns_cq; g.epi = DIA_EPI_SCALE_STORE;
-    g.ssq_in = d.ssq; g.ssq_in_n = d.D / 16; g.ssq_ld = d.rows_pad; g.inv_d = 1.0f / d.D; g.eps = d.eps;
-    g.out = d.qc; g.ldo = d.cq_heads * 128; g.strip_map = L.smap_cq;
-    lend_scratch(g);
-  g.act_f32 = F;
-  g.w_planes = d.w_planes;
-  sparse24(g, L.w_cq_24);
-  mxfp8(g, L.w_cq_f8, 2);
-  if ((rc = dia_gemm(&g, st))) return rc; mark(e, n++);
-
-    a = {};
-    a.mode = DIA_ATTN_CROSS; a.kv_dtype = d.kv_dtype; a.n_kv_heads = d.cq_heads; a.group = 1;
-    a.n_rows = d.B; a.kv_cap = d.S; a.q = d.qc; a.ldq = d.cq_heads * 128; a.q_off = 0;
-    a.kc = L.k_cross; a.vc = L.v_cross; a.cur = d.sample.cur; a.len = d.text_len; a.head_map = L.hmap_cross; a.v_blocked = d.v_blocked;
-    a.kv_plane_stride = d.kv_plane_cross;
-    a.cos_t = d.cos_t; a.sin_t = d.sin_t; a.P = d.planes_a; a.p_plane_stride = as; a.p_ktiles = akt;
-    a.scratch = d.attn_scratch; a.tickets = d.attn_tickets;
-    a.act_f32 = F;
-    if ((rc = dia_attn(&a, st))) return rc; mark(e, n++);
-
-    if (seg) {
+  int n = 0;
+  bool fused = false;         // the wi launch of this layer ran wo as well
+  const int rc = step_sequence(e, with_sampler, [&](int l, int what) -> int {
+    int rc = DIA_OK;
+    if (what == ATTN_SELF || what == ATTN_CROSS) {
+      const dia_dec_layer& L = e->layers[l];
+      dia_attn_args a = {};
+      a.kv_dtype = d.kv_dtype; a.cur = d.sample.cur; a.v_blocked = d.v_blocked; a.cos_t = d.cos_t; a.sin_t = d.sin_t;
+      a.P = planes[PL_A].p; a.p_plane_stride = planes[PL_A].stride; a.p_ktiles = akt;
+      a.scratch = d.attn_scratch; a.tickets = d.attn_tickets; a.act_f32 = F;
+      if (what == ATTN_SELF) {
+        a.mode = DIA_ATTN_SELF; a.n_kv_heads = d.kv_heads; a.group = d.q_heads / d.kv_heads; a.n_rows = R; a.kv_cap = d.T;
+        a.q = d.qkv; a.ldq = nqkv; a.k_off = d.q_heads * 128; a.v_off = (d.q_heads + d.kv_heads) * 128; a.rope_rows = d.T + 1;
+        a.kc = L.k_self; a.vc = L.v_self; a.head_map = L.hmap_self; a.kv_plane_stride = d.kv_plane_self;
+      } else {
+        a.mode = DIA_ATTN_CROSS; a.n_kv_heads = d.cq_heads; a.group = 1; a.n_rows = d.B; a.kv_cap = d.S;
+        a.q = d.qc; a.ldq = d.cq_heads * 128; a.len = d.text_len;
+        a.kc = L.k_cross; a.vc = L.v_cross; a.head_map = L.hmap_cross; a.kv_plane_stride = d.kv_plane_cross;
+      }
+      rc = dia_attn(&a, st);
+    } else if (what == SEG_MLP) {
       dia_seg_args sa = {};
       sa.a_in = (const float*)d.planes_a; sa.a_ktiles = akt; sa.M = R; sa.W = e->seg_w[l];
       sa.has_qkv = l + 1 < d.n_layer; sa.nslots = dia_seg_slots(sa.has_qkv); sa.D = d.D; sa.F = d.F;
-      sa.x = d.x; sa.ldx = d.D; sa.g_mlp = L.g_mlp; sa.g_next = (l + 1 < d.n_layer) ? e->layers[l + 1].g_sa : d.g_final;
+      sa.x = d.x; sa.ldx = d.D; sa.g_mlp = e->layers[l].g_mlp; sa.g_next = (l + 1 < d.n_layer) ? e->layers[l + 1].g_sa : d.g_final;
       sa.qkv_out = d.qkv; sa.ldq = nqkv; sa.planes_x = (float*)d.planes_x; sa.xkt = xkt; sa.ssq = d.ssq; sa.ssq_ld = d.rows_pad;
       sa.eps = d.eps; sa.ws = d.seg_ws;
-      if ((rc = dia_seg_mlp(&sa, st))) return rc; mark(e, n++);
-      continue;
-    }
-    g = {};
-    g.A = d.planes_a; g.a_plane_stride = as; g.a_ktiles = akt; g.M = R;
-    g.W = L.w_co; g.KT = L.kt_co; g.nstrips = L.ns_co; g.epi = DIA_EPI_RESID_EMIT;
-    g.ssq_ld = d.rows_pad; g.out = d.x; g.ldo = d.D; g.gnext = L.g_mlp; g.cmap = L.cmap_mlp;
-    g.P = d.planes_x; g.p_plane_stride = xs; g.p_ktiles = xkt; g.ssq_out = d.ssq;
-    lend_scratch(g);
-  g.act_f32 = 3 * F;
-  g.w_planes = d.w_planes;
-  sparse24(g, L.w_co_24);
-  mxfp8(g, L.w_co_f8, 3);
-  if ((rc = dia_gemm(&g, st))) return rc; mark(e, n++);
-
-    // SwiGLU MLP (layers.py:95-104)
-    dia_gemm_args gi = {};
-    gi.A = d.planes_x; gi.a_plane_stride = xs; gi.a_ktiles = xkt; gi.M = R;
-    gi.W = L.w_wi; gi.KT = L.kt_wi; gi.nstrips = L.ns_wi; gi.epi = DIA_EPI_SWIGLU_EMIT;
-    gi.ssq_in = d.ssq; gi.ssq_in_n = d.D / 16; gi.ssq_ld = d.rows_pad; gi.inv_d = 1.0f / d.D; gi.eps = d.eps;
-    gi.P = d.planes_h; gi.p_plane_stride = hs; gi.p_ktiles = hkt;
-
-    g = {};
-    g.A = d.planes_h; g.a_plane_stride = hs; g.a_ktiles = hkt; g.M = R;
-    g.W = L.w_wo; g.KT = L.kt_wo; g.nstrips = L.ns_wo; g.epi = DIA_EPI_RESID_EMIT;
-    // K = 8192 over only D/16 = 128 strips: cross-workgroup split-K (fence-free slab hand-off) streams the
-    // matrix from more CUs.  M <= 4: two workgroups per strip, 12.4 -> 11.2 us per launch.  5..16 rows: four
-    // per strip, which also brings the per-wave K range down to what k_gemm16 keeps in registers (23.2 ->
-    // 18.4 us in the step at batch 8).  Shapes without a split kernel fall back to one workgroup per strip.
-    int wo_sk = (R <= 4 && L.kt_wo % 2 == 0) ? 2 : ((R <= 16 && L.kt_wo % 4 == 0) ? 4 : 1);
-    int wo_spw = 0;
-    if (R > 4 && R <= 16) {
-      // 5..16 rows: K ranges of 64 k-tiles (8 waves x 8 k-tiles keep their A fragments in registers: 160 VGPRs, one
-      // workgroup per CU) and as many strips per workgroup as it takes to stay at one round of <= 256 workgroups —
-      // dense wo (K 8192 x 128 strips): 4 ranges x 64 strip PAIRS, both tiles of a pair handed over together
-      // (14.3 -> 11.7 us); the 50 %-pruned wo (K 4096): 2 ranges x 128 strips
-      if (L.kt_wo % 64 == 0 && L.kt_wo / 64 >= 2 && L.kt_wo / 64 <= 8) wo_sk = L.kt_wo / 64;
-      if (wo_sk > 1 && L.ns_wo * wo_sk >= 512 && L.ns_wo % 2 == 0) wo_spw = 2;
-    }
-    // two-plane weights (kt_wo counts hi and lo tiles): the tuned forms take 128 weight k-tiles per workgroup, so K splits into
-    // kt_wo / 128 ranges at every row count (dense wo: 4); other hidden widths run unsplit on the generic kernel
-    const int w2_sk = (d.w_planes == 2 && L.kt_wo % 128 == 0 && L.kt_wo / 128 <= 8) ? L.kt_wo / 128 : 1;
-    if (d.w_planes == 2) { wo_sk = w2_sk; wo_spw = 0; }
-    if (dia_tune(DIA_TUNE_WO_SK) >= 1 && dia_tune(DIA_TUNE_WO_SK) <= 8 && L.kt_wo % dia_tune(DIA_TUNE_WO_SK) == 0) wo_sk = dia_tune(DIA_TUNE_WO_SK);
-    g.sk = wo_sk; g.sk_scratch = wo_sk > 1 ? d.sk_scratch : nullptr; g.sk_tickets = wo_sk > 1 ? d.sk_tickets : nullptr;
-    bool wo_pair = false;
-    if (R > 16 && R <= 128) {     // 2..8 m-tiles: split-K 4 over every m-tile (k_gemm16 with gridDim.z) when the scratch covers
-      g.sk_scratch = d.sk_scratch; g.sk_tickets = d.sk_tickets;    // it, else dia_gemm splits K by itself (two m-tiles: k_gemm32)
-      g.sk_scratch_floats = d.sk_scratch_floats > 0 ? d.sk_scratch_floats : (int64_t)(d.D / 16) * 4 * 512;
-      wo_pair = L.kt_wo % 4 == 0 && g.sk_scratch_floats >= (int64_t)((R + 15) / 16) * L.ns_wo * 4 * 256 &&
-                dia_tune(DIA_TUNE_WO_PAIR) != 0;
-      g.sk = wo_pair ? 4 : 1;
-      if (d.w_planes == 2) {
-        wo_pair = w2_sk > 1 && g.sk_scratch_floats >= (int64_t)((R + 15) / 16) * L.ns_wo * w2_sk * 256;
-        g.sk = wo_pair ? w2_sk : 1;
+      rc = dia_seg_mlp(&sa, st);
+    } else if (what == SAMPLER) {
+      rc = dia_sample(&d.sample, st);
+    } else if (what == DIA_MAT_WO && fused) {
+      fused = false;                             // (the fused launch counts as two)
+    } else {
+      dia_gemm_args g = step_gemm(l, what);
+      // opt-in (tuning knob mlp_fuse, EXPERIMENTS=1 builds), batch 1: wi and wo in one persistent launch (dia_mlp_fused).  Anything it refuses
+      // (rows, shapes, CU count) takes the two launches.
+      if (what == DIA_MAT_WI && e->mlp_fused != 0 && R <= 2 && d.mlp_barrier && !e->layers[l].cmap_mlp && d.w_planes <= 1 && !d.act_f32) {
+        dia_gemm_args go = step_gemm(l, DIA_MAT_WO);
+        go.sk = 2; go.sk_scratch = d.sk_scratch; go.sk_tickets = d.sk_tickets; go.nw = 0; go.spw = 0;
+        rc = dia_mlp_fused(&g, &go, d.mlp_barrier, st);
+        if (rc != DIA_OK && rc != DIA_E_ARG) return rc;
+        fused = rc == DIA_OK;
+        e->mlp_fused = fused ? 1 : 0;            // 0: not available for this model, do not try again
+      }
+      if (!fused) rc = dia_gemm(&g, st);
+      if (what == DIA_MAT_WO && rc == DIA_E_ARG && g.sk > 1) {
+        g.sk = 1;
+        if (!wo_pair) { g.sk_scratch = nullptr; g.sk_tickets = nullptr; }     // two m-tiles keep the lent scratch
+        rc = dia_gemm(&g, st);
       }
     }
-    if (dia_tune(DIA_TUNE_WO_NW) > 0) g.nw = dia_tune(DIA_TUNE_WO_NW);
-    g.spw = wo_spw;
-    if (dia_tune(DIA_TUNE_WO_SPW) > 0) g.spw = dia_tune(DIA_TUNE_WO_SPW);
-    g.ssq_ld = d.rows_pad; g.out = d.x; g.ldo = d.D;
-    g.gnext = (l + 1 < d.n_layer) ? e->layers[l + 1].g_sa : d.g_final;
-    g.cmap = L.cmap_next;
-    g.P = d.planes_x; g.p_plane_stride = xs; g.p_ktiles = xkt; g.ssq_out = d.ssq;
-    // opt-in (tuning knob mlp_fuse, EXPERIMENTS=1 builds), batch 1: wi and wo in one persistent launch (dia_mlp_fused).  Anything it refuses
-    // (rows, shapes, CU count) takes the two launches below.
-    if (e->mlp_fused != 0 && R <= 2 && d.mlp_barrier && !L.cmap_mlp && d.w_planes <= 1 && !d.act_f32) {
-      dia_gemm_args go = g;
-      go.sk = 2; go.sk_scratch = d.sk_scratch; go.sk_tickets = d.sk_tickets; go.nw = 0; go.spw = 0;
-      rc = dia_mlp_fused(&gi, &go, d.mlp_barrier, st);
-      if (rc == DIA_OK) { e->mlp_fused = 1; mark(e, n++); mark(e, n++); continue; }
-      if (rc != DIA_E_ARG) return rc;
-      e->mlp_fused = 0;                      // not available for this model: do not try again
-    }
-    lend_scratch(gi);
-    gi.act_f32 = 3 * F; g.act_f32 = 3 * F; gi.w_planes = d.w_planes; g.w_planes = d.w_planes;
-    sparse24(gi, L.w_wi_24);
-    mxfp8(gi, L.w_wi_f8, 4);
-    if ((rc = dia_gemm(&gi, st))) return rc; mark(e, n++);
-    if (diag) {
-      g.W = L.w_wo_diag; g.w_layout = 1; g.nstrips = d.D / 8; g.sk = 1; g.sk_scratch = nullptr; g.sk_tickets = nullptr; g.nw = 0; g.spw = 0;
-    } else {
-      sparse24(g, L.w_wo_24);
-      mxfp8(g, L.w_wo_f8, 5);
-    }
-    rc = dia_gemm(&g, st);
-    if (rc == DIA_E_ARG && g.sk > 1) {
-      g.sk = 1;
-      if (!wo_pair) { g.sk_scratch = nullptr; g.sk_tickets = nullptr; }     // two m-tiles keep the lent scratch
-      rc = dia_gemm(&g, st);
-    }
-    if (rc) return rc;
-    mark(e, n++);
-  }
-  // final norm + logits (layers.py:714-717)
-  dia_gemm_args g = {};
-  g.A = d.planes_x; g.a_plane_stride = xs; g.a_ktiles = xkt; g.M = R;
-  g.W = d.w_logits; g.KT = d.kt_logits; g.nstrips = d.ns_logits; g.epi = DIA_EPI_SCALE_STORE;
-  g.ssq_in = d.ssq; g.ssq_in_n = xn_wo; g.ssq_ld = d.rows_pad; g.inv_d = 1.0f / d.D; g.eps = d.eps;
-  g.out = d.logits; g.ldo = d.ld_logits;
-  lend_scratch(g);
-  g.act_f32 = F;
-  g.w_planes = d.w_planes;
-  sparse24(g, d.w_logits_24);
-  mxfp8(g, d.w_logits_f8, 6);
-  if ((rc = dia_gemm(&g, st))) return rc; mark(e, n++);
-  if (with_sampler) {
-    if ((rc = dia_sample(&d.sample, st))) return rc; mark(e, n++);
-  }
-  e->launches = n;
-  return DIA_OK;
+    if (!rc) mark(e, n++);
+    return rc;
+  });
+  if (!rc) e->launches = n;
+  return rc;
 }
 
 extern "C" int dia_engine_create(const dia_engine_desc* d, void* stream, dia_engine** out) {
@@ -366,17 +366,12 @@ extern "C" int dia_engine_decode(dia_engine* e, int n_steps, int use_graph) {
     if (e->pf_lookahead > 0) {
       int rc0 = ensure_sink();
       if (rc0) return rc0;
-      const dia_engine_desc& d = e->d;
       e->pf_w.clear();
-      for (int l = 0; l < d.n_layer; ++l) {
-        const dia_dec_layer& L = e->layers[l];
-        auto add = [&](const void* w, int kt, int ns) { e->pf_w.push_back({w, (long)kt * ns * 1024}); };
-        add(L.w_qkv, L.kt_qkv, L.ns_qkv); e->pf_w.push_back({nullptr, 0});
-        add(L.w_o, L.kt_o, L.ns_o); add(L.w_cq, L.kt_cq, L.ns_cq); e->pf_w.push_back({nullptr, 0});
-        add(L.w_co, L.kt_co, L.ns_co); add(L.w_wi, L.kt_wi, L.ns_wi); add(L.w_wo, L.kt_wo, L.ns_wo);
-      }
-      e->pf_w.push_back({d.w_logits, (long)d.kt_logits * d.ns_logits * 1024});
-      e->pf_w.push_back({nullptr, 0});
+      (void)step_sequence(e, true, [&](int l, int what) {
+        const mat_w w = what < DIA_MAT_COUNT ? mat_weights(e, l, what) : mat_w{};      // (attention, the sampler, a segment: nothing)
+        e->pf_w.push_back({w.w, (long)w.kt * w.ns * 1024});
+        return DIA_OK;
+      });
       if (!e->side && hipStreamCreateWithFlags(&e->side, hipStreamNonBlocking) != hipSuccess) return dia_fail(DIA_E_HIP, "hipStreamCreate(side)");
       e->pf_ev.assign(e->pf_w.size() + 2, nullptr);
       for (auto& ev : e->pf_ev)
@@ -471,7 +466,9 @@ extern "C" int dia_engine_mlp_fused(const dia_engine* e) { return e && e->mlp_fu
 
 extern "C" int dia_engine_launches_per_step(const dia_engine* e) {
   if (!e) return dia_fail(DIA_E_ARG, "null engine");
-  return e->seg ? e->d.n_layer * 5 + 3 : e->d.n_layer * 8 + 2;
+  int n = 0;
+  (void)step_sequence(e, true, [&](int, int) { return ++n, DIA_OK; });
+  return n;
 }
 
 // ------------------------------------------------------------------------------------------------

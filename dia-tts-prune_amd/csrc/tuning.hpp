@@ -28,7 +28,7 @@ enum dia_tune_id {
   DIA_TUNE_G2T_WGS,            // g2t_wgs: workgroup budget of a k_gemm2t launch over planes (the short-prompt prefill); unset = see dia_gemm
   DIA_TUNE_CKV_MERGE,          // ckv_merge: 0 = the prefill projects cross K/V with one launch per decoder layer (read by dia_hip/engine.py; A/B)
   DIA_TUNE_MXFP8,              // mxfp8: which launch classes stream MXFP8 when the model carries the streams (dia_mxfp8_classes): bit c =
-                               // class c (0 qkv, 1 o, 2 cq, 3 co, 4 wi, 5 wo, 6 logits) at <= 4 rows, bit 8 + c = the same at 5..16 rows;
+                               // matrix c of dia_step_mat (dia_hip.h) at <= 4 rows, bit 8 + c = the same at 5..16 rows;
                                // 0 = dense tiles everywhere; unset = the measured default (csrc/engine.hip)
   // ---- EXPERIMENTS=1 builds only
   DIA_TUNE_MLP_FUSE,           // mlp_fuse: 1 = wi + wo as one persistent launch at batch 1 (dia_mlp_fused)

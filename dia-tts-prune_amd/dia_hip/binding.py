@@ -268,8 +268,8 @@ def get_tuning(name: str) -> int:
 
 
 def mxfp8_mask(rows: int) -> int:
-    """launch classes (bit 0 qkv, 1 o, 2 cq, 3 co, 4 wi, 5 wo, 6 logits) that a decode step of `rows` rows streams as MXFP8 when the
-    model carries the streams: the library's measured default, or the knob mxfp8"""
+    """launch classes (bit m = matrix m of engine.STEP_MATS) that a decode step of `rows` rows streams as MXFP8 when the model carries
+    the streams: the library's measured default, or the knob mxfp8"""
     return int(lib().dia_mxfp8_classes(int(rows)))
 
 

@@ -38,6 +38,7 @@ def _ceil(v: int, m: int) -> int:
 
 
 DEC_MATS = ("qkv", "o", "cq", "co", "wi", "wo")       # the matrices of a decoder layer that a decode step streams (DecLayer w_* / kt_* / ns_*)
+STEP_MATS = DEC_MATS + ("logits",)                    # ... and the head: launch order and MXFP8 class bits (enum dia_step_mat, include/dia_hip.h)
 
 
 @dataclass
@@ -437,16 +438,16 @@ class DeviceWeights:
     def decode_weight_bytes(self, rows: int = 2) -> int:
         """bf16 bytes one decode step of `rows` rows (2 per utterance) streams (SURVEY.md §8d 'W'): every decoder matrix except
         the prefill-only cross K/V projections, plus the logits head — the 2:4 streams where the step uses them (sparse="2:4",
-        at most 4 rows) and the MXFP8 streams for the launch classes the library enables at this row count (quant="mxfp8", at
-        most 16 rows: binding.mxfp8_mask)."""
+        at most 4 rows) and the MXFP8 streams for the matrices of STEP_MATS the library enables at this row count (quant="mxfp8",
+        at most 16 rows: binding.mxfp8_mask)."""
         every = self.sparse == "2:4" and rows <= 4
         f8 = hb.mxfp8_mask(rows) if self.quant == "mxfp8" else 0
 
         def w(L, k):
-            if f8 >> DEC_MATS.index(k) & 1:
+            if f8 >> STEP_MATS.index(k) & 1:
                 return L[k + "f8"].nbytes
             return L[k + "24"].nbytes if every else L[k].nbytes
-        n = self.logits_f8.nbytes if f8 >> len(DEC_MATS) & 1 else (self.logits24.nbytes if every else self.logits.nbytes)
+        n = self.logits_f8.nbytes if f8 >> STEP_MATS.index("logits") & 1 else (self.logits24.nbytes if every else self.logits.nbytes)
         for L in self.dec_layers:
             n += sum(w(L, k) for k in DEC_MATS)
         return n

@@ -534,6 +534,11 @@ typedef struct {
   const void* w_logits_f8;  /* MXFP8 stream of the logits head (as dia_dec_layer.w_*_f8), NULL = dense only */
 } dia_engine_desc;
 
+/* The weight matrices a decode step streams, in launch order: the six of a decoder layer (each layer: qkv, self-attention, o, cq,
+ * cross-attention, co, wi, wo), then the logits head (then the sampler).  The one definition of that order: the engine's launch
+ * table is indexed by it, and bit m of dia_mxfp8_classes / the knob "mxfp8" is matrix m. */
+enum dia_step_mat { DIA_MAT_QKV, DIA_MAT_O, DIA_MAT_CQ, DIA_MAT_CO, DIA_MAT_WI, DIA_MAT_WO, DIA_MAT_LOGITS, DIA_MAT_COUNT };
+
 typedef struct dia_engine dia_engine;
 int dia_engine_create(const dia_engine_desc* d, void* stream, dia_engine** out);
 int dia_engine_destroy(dia_engine* e);
@@ -547,8 +552,7 @@ int dia_engine_set_prefetch(dia_engine* e, int lookahead);
 /* enqueue ONE decode step stopping after the logits GEMM (no sampling); for per-kernel timing */
 int dia_engine_step_logits_only(dia_engine* e);
 /* run ONE eager decode step with a HIP event recorded on the engine's stream after every launch and
- * return the elapsed milliseconds of each launch (launch order: per layer qkv, attn_self, o, cq,
- * attn_cross, co, wi, wo; then logits, sampler).  Synchronises the stream. */
+ * return the elapsed milliseconds of each launch (launch order: dia_step_mat).  Synchronises the stream. */
 int dia_engine_profile_step(dia_engine* e, float* ms_per_launch, int cap);
 /* run ONE eager decode step with every kernel bracketed by dispatch-level start / stop events (timestamps of the
  * dispatch packet itself): ms_per_kernel[i] = begin -> end of the i-th launch (pure execution), interval_ms[i] (may be
@@ -560,8 +564,8 @@ int dia_engine_time_step(dia_engine* e, float* ms_per_kernel, float* interval_ms
  * last dia_engine_time_step / dia_gemm_timed; "" when out of range */
 const char* dia_timed_kernel_name(int i);
 /* Launch classes of a decode step of `rows` rows that stream MXFP8 when the model carries the streams (dia_dec_layer.w_*_f8,
- * dia_engine_desc.w_logits_f8): bit 0 qkv, 1 o, 2 cq, 3 co, 4 wi, 5 wo, 6 logits.  0 above 16 rows.  The knob "mxfp8" overrides the
- * measured default (bits 0-6: at most 4 rows, bits 8-14: 5..16 rows). */
+ * dia_engine_desc.w_logits_f8): bit m = matrix m of dia_step_mat.  0 above 16 rows.  The knob "mxfp8" overrides the measured
+ * default (bits 0-6: at most 4 rows, bits 8-14: 5..16 rows). */
 int dia_mxfp8_classes(int rows);
 /* number of kernel launches in one decode step */
 int dia_engine_launches_per_step(const dia_engine* e);
