@@ -24,6 +24,8 @@ struct dia_engine {
   bool seg = false;               // the step runs persistent MLP segments (dia_seg_mlp)
   std::vector<const void*> seg_w;
   int mlp_fused = -1;             // -1 not tried yet, 1 the MLP runs as one fused launch, 0 two launches
+  int wo_defer = -1;              // -1 not tried yet, 1 wo's split-K slices are merged by the launch behind it, 0 inside wo (dia_gemm_wo_deferred refused)
+  float* x_alt = nullptr;         // dia_engine_set_x_alt: the residual stream of odd layers while wo_defer is in force
   std::vector<hipEvent_t> prof;   // when non-empty: one event recorded after every launch (profile step)
   // weight prefetch beside the chain (graph mode): launch i+lookahead's weights are pulled into the
   // Infinity Cache by a side stream as soon as launch i has been issued
@@ -206,6 +208,12 @@ static int enqueue_step(dia_engine* e, bool with_sampler) {
     else { g.sk_scratch = d.sk_scratch; g.sk_tickets = d.sk_tickets; }
   };
   bool wo_pair = false;             // of the wo descriptor built last
+  // <= 4 rows: wo's two K slices merged by the launch behind it (the next layer's q/k/v projection, the logits head) while it stages
+  // its row, instead of wo's ticket hand-off (dia_gemm_wo_deferred) — decided below, once every descriptor can be looked at.
+  // That launch reads the whole old residual row and writes the new one: the stream alternates between x and x_alt by layer
+  bool defer = false;
+  const int64_t slice_floats = (int64_t)d.rows_pad * d.D;
+  auto xbuf = [&](int l) { return (defer && (l & 1)) ? e->x_alt : d.x; };
   // the descriptor of matrix m of layer l (the logits head: l = n_layer) from its row of STEP_MATS
   auto step_gemm = [&](int l, int m) {
     const step_mat_row& r = STEP_MATS[m];
@@ -223,7 +231,7 @@ static int enqueue_step(dia_engine* e, bool with_sampler) {
       case OUT_QC: g.out = d.qc; g.ldo = d.cq_heads * 128; g.strip_map = L->smap_cq; break;
       case OUT_LOGITS: g.out = d.logits; g.ldo = d.ld_logits; break;
       case OUT_X:                   // residual add; emits the planes of x * gnext in the consumer's (compacted) K order
-        g.out = d.x; g.ldo = d.D; g.ssq_out = d.ssq; g.cmap = L->*r.cmap;
+        g.out = xbuf(l); g.ldo = d.D; g.ssq_out = d.ssq; g.cmap = L->*r.cmap;
         g.gnext = r.gnext ? L->*r.gnext : ((l + 1 < d.n_layer) ? e->layers[l + 1].g_sa : d.g_final);
         break;
     }
@@ -236,8 +244,39 @@ static int enqueue_step(dia_engine* e, bool with_sampler) {
     }
     sparse24(g, w.w24);
     mxfp8(g, w.wf8, m);
+    if (defer && (m == DIA_MAT_LOGITS || (m == DIA_MAT_QKV && l > 0))) g.gnext = L ? L->g_sa : d.g_final;     // the consumer norms the row itself
     return g;
   };
+  // what dia_gemm_wo_deferred needs beside the descriptor; nslices == 0: this launch goes through dia_gemm
+  auto step_defer = [&](int l, int m) {
+    dia_wo_defer_args w = {};
+    if (!defer || !(m == DIA_MAT_WO || m == DIA_MAT_LOGITS || (m == DIA_MAT_QKV && l > 0))) return w;
+    w.nslices = 2; w.slices = d.sk_scratch; w.slice_stride = slice_floats;
+    if (m == DIA_MAT_WO) { w.defer = 1; return w; }
+    w.xold = xbuf(l - 1); w.ldx = d.D;
+    w.xnew = l < d.n_layer ? xbuf(l) : nullptr;   // (nothing reads x behind the logits head: the sampler's embedding overwrites it)
+    return w;
+  };
+  // every wo and every launch behind one in the shape the deferred kernels serve: dense one-plane tiles (no 2:4 / MXFP8 stream picked),
+  // K 8192 in two slices -> a row of D = 2048, no compaction map on the edge; else the whole model keeps the in-launch merge
+  if (R <= 4 && F && d.w_planes <= 1 && !seg && !diag && e->wo_defer != 0 && dia_tune(DIA_TUNE_WO_DEFER) != 0 && dia_tune(DIA_TUNE_MLP_FUSE) <= 0 &&
+      e->x_alt && d.sk_scratch && d.D == 2048 && (d.sk_scratch_floats > 0 ? d.sk_scratch_floats : (int64_t)(d.D / 16) * 4 * 512) >= 2 * slice_floats) {
+    // (everything dia_gemm_wo_deferred checks for either role is checked here for every launch of the model: a refusal can then only
+    // meet the first wo of the first step, before anything of the deferred form has been issued)
+    const auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
+    bool ok = al16(d.x) && al16(e->x_alt) && al16(d.sk_scratch) && slice_floats % 4 == 0 && slice_floats >= (int64_t)xkt * 512 && d.D % 4 == 0 &&
+              dia_tune(DIA_TUNE_GEMM_SPW) <= 0;
+    for (int l = 0; l < d.n_layer && ok; ++l) {
+      const dia_gemm_args go = step_gemm(l, DIA_MAT_WO), gc = step_gemm(l + 1, l + 1 < d.n_layer ? DIA_MAT_QKV : DIA_MAT_LOGITS);
+      const float* gcons = l + 1 < d.n_layer ? e->layers[l + 1].g_sa : d.g_final;       // the consumer's norm weight
+      const int spw = gc.spw > 0 ? gc.spw : (gc.nstrips >= 1024 ? 4 : (gc.nstrips > 512 ? (gc.nstrips + 255) / 256 : 1));   // as pick_spw (gemm.hip)
+      ok = go.w_format == DIA_W_DENSE && go.w_layout == 0 && go.sk == 2 && go.KT == 256 && !go.cmap && go.nw == 0 && go.nstrips == d.D / 16 &&
+           (go.act_f32 & 3) == 3 && go.gnext && go.nstrips * 16 <= go.p_ktiles * 32 &&
+           gc.w_format == DIA_W_DENSE && gc.w_layout == 0 && gc.KT == 64 && gc.nw == 0 && gc.sk <= 1 && !gc.cmap && (gc.act_f32 & 1) && gcons && al16(gcons) &&
+           (l + 1 == d.n_layer || (gc.nstrips + spw - 1) / spw >= d.D / 16);                 // x_new: 16 columns from each of D/16 workgroups
+    }
+    defer = ok;
+  }
 
   int n = 0;
   bool fused = false;         // the wi launch of this layer ran wo as well
@@ -283,7 +322,19 @@ static int enqueue_step(dia_engine* e, bool with_sampler) {
         fused = rc == DIA_OK;
         e->mlp_fused = fused ? 1 : 0;            // 0: not available for this model, do not try again
       }
-      if (!fused) rc = dia_gemm(&g, st);
+      const dia_wo_defer_args wd = step_defer(l, what);
+      if (!fused) rc = wd.nslices ? dia_gemm_wo_deferred(&g, &wd, st, nullptr) : dia_gemm(&g, st);
+      if (rc == DIA_OK && wd.defer) e->wo_defer = 1;
+      if (rc == DIA_E_ARG && wd.nslices) {
+        // dia_gemm_wo_deferred cannot serve the deferred form of this model: from now on the in-launch merge.  The first wo of a step is the
+        // first launch that asks for it, so nothing of this step has been issued in the other form yet — issue it again here
+        const bool first = what == DIA_MAT_WO && l == 0 && e->wo_defer < 0;
+        e->wo_defer = 0;
+        if (!first) return rc;
+        defer = false;
+        g = step_gemm(l, what);
+        rc = dia_gemm(&g, st);
+      }
       if (what == DIA_MAT_WO && rc == DIA_E_ARG && g.sk > 1) {
         g.sk = 1;
         if (!wo_pair) { g.sk_scratch = nullptr; g.sk_tickets = nullptr; }     // two m-tiles keep the lent scratch
@@ -507,6 +558,13 @@ extern "C" int dia_prefetch(const void* ptr, int64_t nbytes, int nblocks, void* 
   int rc = ensure_sink();
   if (rc) return rc;
   return dia_prefetch_launch(ptr, (long)nbytes, nblocks, (hipStream_t)stream);
+}
+
+extern "C" int dia_engine_set_x_alt(dia_engine* e, float* x_alt) {
+  if (!e) return dia_fail(DIA_E_ARG, "dia_engine_set_x_alt: null engine");
+  if (e->exec || e->wo_defer == 1) return dia_fail(DIA_E_STATE, "dia_engine_set_x_alt: a step has already been issued or captured");
+  e->x_alt = x_alt;
+  return DIA_OK;
 }
 
 extern "C" int dia_engine_set_prefetch(dia_engine* e, int lookahead) {

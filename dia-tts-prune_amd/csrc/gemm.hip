@@ -148,7 +148,15 @@ __global__ __launch_bounds__(NW * 64) void k_gemm(GemmK p) {
 // otherwise requests at the same moment (in-kernel stamps: 0.8 us from the start of a wave to its first weight load).
 // W2: two-plane weights (w_planes == 2): weight k-tile j of the range is plane j & 1 of activation k-tile j >> 1, so the A image
 // covers KPW / 2 k-tiles per wave; weight stream, prefetch and epilogues are those of the one-plane form.
-template <int NW, int KPW, int RS, bool MULTI, bool AF32 = false, bool PF32 = false, bool W2 = false>
+// DF: wo's cross-workgroup split-K merged behind the kernel boundary that follows it anyway (dia_gemm_wo_deferred).
+//   1 = producer: each K slice stores the valid rows of its partial tile to its own buffer (fp32 tile order) and returns — no
+//       ticket, no merge, no residual, no sums of squares, no image;
+//   2 = consumer (the PL_X reader behind a wo): its staging prologue loads the slices, the old residual row and its norm weight
+//       instead of the image and the strip sums, and rebuilds what wo's epilogue would have written, in the same order of
+//       operations: x_new = x_old + (0 + s_0 + s_1), the half-strip sums of squares as run_epilogue_rows forms them, the image
+//       mul_rn(x_new, g).  Workgroup b < D/16 stores columns 16 b .. 16 b + 15 of x_new (to another buffer than x_old: every
+//       workgroup reads the whole old row).
+template <int NW, int KPW, int RS, bool MULTI, bool AF32 = false, bool PF32 = false, bool W2 = false, int DF = 0>
 __global__ __launch_bounds__(NW * 64) void k_gemv_small(const bf16_raw* a_A, long a_aps, const bf16_raw* a_W, int a_KT, int a_M, int a_epi,
                                                         int a_nstrips, float* a_out, int a_ldo, const float* a_gnext, GemmK p) {
   p.A = a_A; p.a_plane_stride = a_aps; p.W = a_W; p.KT = a_KT; p.M = a_M; p.epi = a_epi; p.nstrips = a_nstrips;
@@ -162,6 +170,9 @@ __global__ __launch_bounds__(NW * 64) void k_gemv_small(const bf16_raw* a_A, lon
   float* tile = reinterpret_cast<float*>(smem_raw + sizeof(f32x4) * NW * 64);   // [16][17]
   float* inv_s = tile + 16 * 17;                                           // [16]
   bf16x8* As = reinterpret_cast<bf16x8*>(smem_raw + sizeof(f32x4) * NW * 64 + sizeof(float) * (16 * 17 + 16));
+  static_assert(DF == 0 || (AF32 && PF32 && !W2), "the deferred wo merge: fp32 activation tiles, one weight plane");
+  static_assert(DF != 2 || (NW * KPW == 64 && (RS == 2 || RS == 4)), "the deferred consumer holds a whole row of D = 2048: 128 strips");
+  static_assert(DF != 1 || !MULTI, "the deferred producer: one strip per workgroup");
 
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int kt0 = w * KPW;                 // k-tile inside this workgroup's K range
@@ -200,7 +211,22 @@ __global__ __launch_bounds__(NW * 64) void k_gemv_small(const bf16_raw* a_A, lon
   constexpr int CE = (KPA * RS + 15) / 16;           // entries per thread = KT*4*RS / NT
   bf16x8 v0[AF32 ? 1 : CH];
   float4 ex[AF32 ? CE : 1], ey[AF32 ? CE : 1];
-  if constexpr (AF32) {
+  constexpr int CD = DF == 2 ? CE : 1;               // deferred consumer: per entry two slices, the old residual, the norm weight
+  float4 d0x[CD], d0y[CD], d1x[CD], d1y[CD], dxx[CD], dxy[CD], dgx[CD], dgy[CD];
+  float* hs = reinterpret_cast<float*>(As + nchunks);                       // [RS][4 * KT] half-strip sums of squares (DF == 2)
+  if constexpr (DF == 2) {
+#pragma unroll
+    for (int u = 0; u < CE; ++u) {
+      const int c = min(tid + u * NT, nentries - 1);
+      const int row = min(c % RS, p.M - 1), kq = (c / RS) & 3, kt = c / (4 * RS);     // rows >= M: the last valid row once more
+      const float4* s0 = reinterpret_cast<const float4*>(p.wo_slices + ((long)kt * 64 + row + 16 * kq) * 8);
+      const float4* s1 = reinterpret_cast<const float4*>(p.wo_slices + p.wo_slice_stride + ((long)kt * 64 + row + 16 * kq) * 8);
+      const float4* xo = reinterpret_cast<const float4*>(p.wo_xold + (long)row * p.wo_ldx + kt * 32 + kq * 8);
+      const float4* gn = reinterpret_cast<const float4*>(p.gnext + kt * 32 + kq * 8);
+      d0x[u] = s0[0]; d0y[u] = s0[1]; d1x[u] = s1[0]; d1y[u] = s1[1];
+      dxx[u] = xo[0]; dxy[u] = xo[1]; dgx[u] = gn[0]; dgy[u] = gn[1];
+    }
+  } else if constexpr (AF32) {
     const float* Af = reinterpret_cast<const float*>(p.A);
 #pragma unroll
     for (int u = 0; u < CE; ++u) {
@@ -218,19 +244,19 @@ __global__ __launch_bounds__(NW * 64) void k_gemv_small(const bf16_raw* a_A, lon
     }
   }
   // (2) strip sums of squares for the row scale: 8 threads per row, up to 16 strips each per round
-  const bool has_norm = p.ssq_in != nullptr;
+  const bool has_norm = DF == 2 || p.ssq_in != nullptr;
   const int s_row = tid >> 3, s_part = tid & 7;
   const bool s_thread = tid < 128 && has_norm;
   float sq[16];
 #pragma unroll
   for (int i = 0; i < 16; ++i) sq[i] = 0.f;
-  if (s_thread) {        // one exec-masked region, 16 unconditional loads on clamped addresses
+  if (DF != 2 && s_thread) {        // one exec-masked region, 16 unconditional loads on clamped addresses
     const float* sp = p.ssq_in + min(s_row, p.M - 1);
 #pragma unroll
     for (int i = 0; i < 16; ++i) sq[i] = sp[(long)min(s_part + 8 * i, p.ssq_in_n - 1) * p.ssq_ld];
   }
-  // (3) residual row + next norm weight of the first strip (RESID_EMIT only)
-  const bool resid = p.epi == DIA_EPI_RESID_EMIT;
+  // (3) residual row + next norm weight of the first strip (RESID_EMIT only; the deferred producer adds no residual)
+  const bool resid = DF != 1 && p.epi == DIA_EPI_RESID_EMIT;
   const bool r_thread = tid < 16 * RS;                // one tile element per thread in the epilogue (run_epilogue_rows)
   float xpre1 = 0.f, gpre1 = 1.f;
   auto load_resid = [&](int strip) {
@@ -245,7 +271,41 @@ __global__ __launch_bounds__(NW * 64) void k_gemv_small(const bf16_raw* a_A, lon
   __builtin_amdgcn_sched_barrier(0);
 #endif
   STAMP(1);
-  if constexpr (AF32) {
+  if constexpr (DF == 2) {
+#pragma unroll
+    for (int u = 0; u < CE; ++u)
+      if (tid + u * NT < nentries) {
+        const int c = tid + u * NT;
+        const int row = c % RS, kq = (c / RS) & 3, kt = c / (4 * RS);
+        const float s0[8] = {d0x[u].x, d0x[u].y, d0x[u].z, d0x[u].w, d0y[u].x, d0y[u].y, d0y[u].z, d0y[u].w};
+        const float s1[8] = {d1x[u].x, d1x[u].y, d1x[u].z, d1x[u].w, d1y[u].x, d1y[u].y, d1y[u].z, d1y[u].w};
+        const float xo[8] = {dxx[u].x, dxx[u].y, dxx[u].z, dxx[u].w, dxy[u].x, dxy[u].y, dxy[u].z, dxy[u].w};
+        const float gn[8] = {dgx[u].x, dgx[u].y, dgx[u].z, dgx[u].w, dgy[u].x, dgy[u].y, dgy[u].z, dgy[u].w};
+        float xn[8], vg[8];
+        float acc = 0.f;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          xn[j] = add_rn(xo[j], add_rn(add_rn(0.f, s0[j]), s1[j]));      // splitk_combine (slices in split order from 0), then the residual
+          const float q = mul_rn(xn[j], xn[j]);
+          acc = j == 0 ? q : add_rn(acc, q);                              // run_epilogue_rows: columns 0..7 of the half in sequence
+          vg[j] = mul_rn(xn[j], gn[j]);
+        }
+        hs[row * (4 * KT) + kt * 4 + kq] = acc;
+        if (p.wo_xnew != nullptr && kt * 2 + (kq >> 1) == (int)blockIdx.x && row < p.M) {
+          float4* o = reinterpret_cast<float4*>(p.wo_xnew + (long)row * p.wo_ldx + kt * 32 + kq * 8);
+          o[0] = float4{xn[0], xn[1], xn[2], xn[3]}; o[1] = float4{xn[4], xn[5], xn[6], xn[7]};
+        }
+        bf16x8 h, mi, lo;
+        split3x8(float4{vg[0], vg[1], vg[2], vg[3]}, float4{vg[4], vg[5], vg[6], vg[7]}, h, mi, lo);
+        As[c] = h; As[nentries + c] = mi; As[2 * nentries + c] = lo;
+      }
+    lds_barrier();      // the half-strip sums of the whole row
+    if (tid < 128) {    // strip s of the row: half 0 + half 1, as wo's epilogue wrote it to ssq_out
+      const float* h = hs + min(s_row, RS - 1) * (4 * KT);
+#pragma unroll
+      for (int i = 0; i < 16; ++i) sq[i] = h[2 * (s_part + 8 * i)] + h[2 * (s_part + 8 * i) + 1];
+    }
+  } else if constexpr (AF32) {
 #pragma unroll
     for (int u = 0; u < CE; ++u)
       if (tid + u * NT < nentries) {
@@ -262,8 +322,8 @@ __global__ __launch_bounds__(NW * 64) void k_gemv_small(const bf16_raw* a_A, lon
   {
     float s0 = 0.f;
 #pragma unroll
-    for (int i = 0; i < 16; ++i) s0 += (s_part + 8 * i < p.ssq_in_n && s_row < p.M) ? sq[i] : 0.f;
-    if (s_thread && s_row < p.M)
+    for (int i = 0; i < 16; ++i) s0 += ((DF == 2 || s_part + 8 * i < p.ssq_in_n) && s_row < p.M) ? sq[i] : 0.f;
+    if (DF != 2 && s_thread && s_row < p.M)
       for (int idx = s_part + 128; idx < p.ssq_in_n; idx += 8) s0 += p.ssq_in[(long)idx * p.ssq_ld + s_row];   // D > 2048 only
     // the 8 partials of a row sit in 8 consecutive lanes: quad xor 1, quad xor 2, then the other quad of the half row
     // (after two steps a quad is uniform, so the mirror delivers what lane ^ 4 holds) — DPP, no LDS crossbar
@@ -302,7 +362,7 @@ __global__ __launch_bounds__(NW * 64) void k_gemv_small(const bf16_raw* a_A, lon
     }
     STAMP(3);
     float v = 0.f;
-    if (MULTI || gridDim.y == 1) {
+    if (MULTI || DF == 1 || gridDim.y == 1) {
       f32x4* rb = red16 + sbuf * (NW * 16);
       sbuf ^= 1;
       if (lane < 16) rb[w * 16 + lane] = acc[0];
@@ -319,6 +379,12 @@ __global__ __launch_bounds__(NW * 64) void k_gemv_small(const bf16_raw* a_A, lon
       STAMP(4);
       if (!splitk_combine(p, tile, strip, tid, &sk_flag)) return;
       if (r_thread) v = tile[(tid >> 4) * 17 + (tid & 15)];
+    }
+    if constexpr (DF == 1) {      // this K slice's partial (the waves summed in wave order, as reduce_to_tile does) -> its buffer; plain
+      // stores: the next reader is behind a kernel boundary
+      const int m = tid >> 4, n = strip * 16 + (tid & 15);
+      if (r_thread && m < p.M) p.wo_slices[(long)blockIdx.y * p.wo_slice_stride + plane_frag_off(m, n & ~7, p.p_ktiles) + (n & 7)] = v;
+      return;
     }
     if (r_thread) {
       run_epilogue_rows<RS, PF32>(p, v, inv_s, tid, strip, xpre1, gpre1);
@@ -2006,6 +2072,41 @@ int launch_g16_w2(const GemmK& k, int mz, int sk, hipStream_t st) {
   return dia_check_launch("k_gemm16");
 }
 
+// wo's split-K merge deferred to the consumer (k_gemv_small DF): role 1 = the producer, 2 = the consumer (dia_wo_defer_args.defer).
+// One shape each: two K slices of 128 k-tiles (16 waves x 8), a consumer row of D = 2048 (8 waves x 8) — what the tuned in-launch
+// forms of these launches run.  Anything else: DIA_E_ARG, the caller keeps the in-launch merge.
+template <int RS>
+int launch_wo_deferred(const GemmK& k, int role, hipStream_t st) {
+  if (role == 1) {
+    launch_small_kernel<k_gemv_small<16, 8, RS, false, true, true, false, 1>>(dim3(k.nstrips, 2), dim3(1024), small_smem(16, 128, RS), st, k);
+    return dia_check_launch("k_gemv_small");
+  }
+  const size_t smem = small_smem(8, 64, RS) + sizeof(float) * RS * 256;
+  const int spw = pick_spw(k, 512, 1, 1);          // as launch_small
+  const int grid = (k.nstrips + spw - 1) / spw;
+  if (k.wo_xnew && grid < 128) return dia_fail(DIA_E_ARG, "dia_gemm: deferred wo merge: fewer workgroups than strips of x to write back");
+  if (spw > 1) launch_small_kernel<k_gemv_small<8, 8, RS, true, true, true, false, 2>>(dim3(grid), dim3(512), smem, st, k);
+  else launch_small_kernel<k_gemv_small<8, 8, RS, false, true, true, false, 2>>(dim3(grid), dim3(512), smem, st, k);
+  return dia_check_launch("k_gemv_small");
+}
+
+int gemm_wo_deferred(const dia_gemm_args* a, const dia_wo_defer_args* w, GemmK& k, hipStream_t st) {
+  const int role = w->defer ? 1 : 2;
+  const bool emits = a->epi == DIA_EPI_RESID_EMIT;
+  const auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
+  bool ok = a->M <= 4 && a->w_format == DIA_W_DENSE && a->w_planes <= 1 && a->w_layout == 0 && !a->cmap && !a->sp_blocks && !a->sp_toff &&
+            w->nslices == 2 && w->slices && al16(w->slices) && w->slice_stride % 4 == 0 && a->gnext && dia_tune(DIA_TUNE_GEMM_SPW) <= 0;
+  if (role == 1) ok = ok && emits && (a->act_f32 & 3) == 3 && a->sk == 2 && a->KT == 256 && (a->nw == 0 || a->nw == 16) && !w->xold && !w->xnew &&
+                      w->slice_stride >= (int64_t)a->p_ktiles * 512 && (int64_t)a->nstrips * 16 <= (int64_t)a->p_ktiles * 32 && a->P && a->out;
+  else ok = ok && a->epi == DIA_EPI_SCALE_STORE && (a->act_f32 & 1) && a->sk <= 1 && a->KT == 64 && (a->nw == 0 || a->nw == 8) && w->xold &&
+            w->xold != w->xnew && al16(w->xold) && al16(w->xnew) && al16(a->gnext) && w->ldx >= 2048 && w->ldx % 4 == 0 &&
+            w->slice_stride >= 64 * 512;
+  if (!ok) return dia_fail(DIA_E_ARG, "dia_gemm_wo_deferred: serves M <= 4, dense one-plane weights, fp32 tiles, no cmap, two slices: wo as K 8192 "
+                                      "RESID_EMIT with gnext, its consumer as K 2048 SCALE_STORE with xold and gnext (16-byte aligned)");
+  k.wo_slices = w->slices; k.wo_slice_stride = w->slice_stride; k.wo_xold = w->xold; k.wo_xnew = w->xnew; k.wo_ldx = w->ldx;
+  return a->M <= 2 ? launch_wo_deferred<2>(k, role, st) : launch_wo_deferred<4>(k, role, st);
+}
+
 }  // namespace
 
 #ifdef DIA_DBG_STAMPS
@@ -2057,9 +2158,11 @@ int gemm_w2(const dia_gemm_args* a, GemmK& k, hipStream_t st) {
 }
 }  // namespace
 
-extern "C" int dia_gemm(const dia_gemm_args* a, void* stream) {
+static int gemm_impl(const dia_gemm_args* a, const dia_wo_defer_args* wd, void* stream) {
   if (!a || !a->A || (!a->W && !a->sp_blocks)) return dia_fail(DIA_E_ARG, "dia_gemm: null argument");
   if (a->M <= 0 || a->KT <= 0 || a->nstrips <= 0) return dia_fail(DIA_E_ARG, "dia_gemm: empty problem");
+  if (wd && (a->w_format != DIA_W_DENSE || a->w_layout != 0 || a->w_planes > 1 || a->sp_blocks || a->sp_toff))
+    return dia_fail(DIA_E_ARG, "dia_gemm_wo_deferred: dense one-plane weight tiles only");
   if (a->w_format != DIA_W_DENSE && a->w_format != DIA_W_SPARSE24 && a->w_format != DIA_W_MXFP8) return dia_fail(DIA_E_ARG, "dia_gemm: unknown w_format");
   if (a->w_format == DIA_W_SPARSE24) {      // 2:4 sparse weight stream (gemm_sparse.hip)
     const int rc = dia_gemm_sparse24_check(a);
@@ -2117,6 +2220,7 @@ extern "C" int dia_gemm(const dia_gemm_args* a, void* stream) {
   }
   GemmK k;
   fill_gemmk(a, k);
+  if (wd) return gemm_wo_deferred(a, wd, k, (hipStream_t)stream);
   if (a->w_planes == 2) return gemm_w2(a, k, (hipStream_t)stream);
   if (a->w_planes > 1) {      // fp32 weights as three planes: the generic kernel, whatever the shape (exactness, not speed)
     if (a->w_planes != 3) return dia_fail(DIA_E_ARG, "dia_gemm: w_planes must be 0, 1, 2 or 3");
@@ -2253,6 +2357,21 @@ extern "C" int dia_gemm(const dia_gemm_args* a, void* stream) {
     }
   }
   return launch_generic(k, nw, st);
+}
+
+extern "C" int dia_gemm(const dia_gemm_args* a, void* stream) { return gemm_impl(a, nullptr, stream); }
+
+extern "C" int dia_gemm_wo_deferred(const dia_gemm_args* a, const dia_wo_defer_args* w, void* stream, float* ms_out) {
+  if (!w) return dia_fail(DIA_E_ARG, "dia_gemm_wo_deferred: null argument");
+  if (!ms_out) return gemm_impl(a, w, stream);
+  dia_recorder_arm();
+  int rc = gemm_impl(a, w, stream);
+  float ms[4] = {0.f, 0.f, 0.f, 0.f};
+  const int n = dia_recorder_collect(ms, 4);
+  if (rc != DIA_OK) return rc;
+  if (n < 1) return n < 0 ? n : dia_fail(DIA_E_STATE, "dia_gemm_wo_deferred: nothing was launched");
+  *ms_out = ms[0];
+  return DIA_OK;
 }
 
 extern "C" int dia_gemm_timed(const dia_gemm_args* a, void* stream, float* ms_out) {

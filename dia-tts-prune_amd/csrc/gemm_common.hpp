@@ -62,6 +62,8 @@ struct GemmK {
   long kv_layer_stride; int kv_layer_strips;   // CROSSKV over several layers (dia_gemm_args)
   int sk2_quads;                                // k_gemm2t SK2: groups of four strips per hand-off (knob gemm_2t=7: pairs only)
   int w_planes; long w_plane_stride;       // k_gemm only: hi / mid / lo planes of fp32 weights, one tile set each
+  float* wo_slices; long wo_slice_stride;  // k_gemv_small DF: wo's K slices, merged by the launch that follows (dia_wo_defer_args)
+  const float* wo_xold; float* wo_xnew; int wo_ldx;
 };
 
 // the three plane fragments of the A operand at element offset `off` inside a plane / an fp32 tile set
@@ -382,6 +384,7 @@ inline int fill_gemmk(const dia_gemm_args* a, GemmK& k) {
   k.kv_layer_strips = a->kv_layer_strips; k.kv_layer_stride = a->kv_layer_stride;
   k.sk2_quads = dia_tune(DIA_TUNE_GEMM_2T) != 7;
   k.w_planes = a->w_planes > 1 ? a->w_planes : 1; k.w_plane_stride = (long)a->KT * a->nstrips * 512;
+  k.wo_slices = nullptr; k.wo_slice_stride = 0; k.wo_xold = nullptr; k.wo_xnew = nullptr; k.wo_ldx = 0;      // dia_gemm_wo_deferred sets them
   return DIA_OK;
 }
 

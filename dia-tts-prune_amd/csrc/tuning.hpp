@@ -30,6 +30,8 @@ enum dia_tune_id {
   DIA_TUNE_MXFP8,              // mxfp8: which launch classes stream MXFP8 when the model carries the streams (dia_mxfp8_classes): bit c =
                                // matrix c of dia_step_mat (dia_hip.h) at <= 4 rows, bit 8 + c = the same at 5..16 rows;
                                // 0 = dense tiles everywhere; unset = the measured default (csrc/engine.hip)
+  DIA_TUNE_WO_DEFER,           // wo_defer: 0 = <= 4 rows merge wo's split-K slices inside the wo launch (ticket hand-off); unset / 1 = the launch
+                               // behind wo merges them while it stages its row (csrc/engine.hip), where the model allows it
   // ---- EXPERIMENTS=1 builds only
   DIA_TUNE_MLP_FUSE,           // mlp_fuse: 1 = wi + wo as one persistent launch at batch 1 (dia_mlp_fused)
   DIA_TUNE_TILE_V,             // tile_v: prefill tile kernel variant (0..5; 3 = wave-specialised default)

@@ -21,9 +21,9 @@ W_DENSE, W_SPARSE24, W_MXFP8 = 0, 1, 2                     # dia_gemm_args.w_for
 ATTN_SELF, ATTN_CROSS, ATTN_ENC = 0, 1, 2
 
 EXPORTS = (
-    "dia_last_error", "dia_abi_version", "dia_device_count", "dia_set_tuning", "dia_get_tuning", "dia_has_experiments", "dia_gemm", "dia_gemm_timed", "dia_mlp_fused", "dia_mlp_fused_timed", "dia_engine_mlp_fused", "dia_attn", "dia_attn_scratch_floats", "dia_enc_kv_prep", "dia_enc_attn", "dia_dec_prefill_embed", "dia_dec_prefill_kv", "dia_dec_prefill_attn",
+    "dia_last_error", "dia_abi_version", "dia_device_count", "dia_set_tuning", "dia_get_tuning", "dia_has_experiments", "dia_gemm", "dia_gemm_timed", "dia_gemm_wo_deferred", "dia_mlp_fused", "dia_mlp_fused_timed", "dia_engine_mlp_fused", "dia_attn", "dia_attn_scratch_floats", "dia_enc_kv_prep", "dia_enc_attn", "dia_dec_prefill_embed", "dia_dec_prefill_kv", "dia_dec_prefill_attn",
     "dia_embed_text", "dia_embed_tokens", "dia_sample", "dia_slot_admit", "dia_slot_retire", "dia_prefetch", "dia_engine_create", "dia_engine_destroy",
-    "dia_engine_decode", "dia_engine_set_prefetch", "dia_engine_step_logits_only", "dia_engine_profile_step", "dia_engine_time_step", "dia_timed_kernel_name", "dia_engine_launches_per_step", "dia_mxfp8_classes",
+    "dia_engine_decode", "dia_engine_set_prefetch", "dia_engine_set_x_alt", "dia_engine_step_logits_only", "dia_engine_profile_step", "dia_engine_time_step", "dia_timed_kernel_name", "dia_engine_launches_per_step", "dia_mxfp8_classes",
     "dia_seg_mlp", "dia_seg_workspace_bytes", "dia_seg_workspace_control_bytes", "dia_seg_slots", "dia_seg_supported", "dia_seg_error",
 )
 
@@ -49,6 +49,13 @@ class GemmArgs(C.Structure):
         ("act_f32", C.c_int32), ("w_planes", C.c_int32), ("kv_plane_stride", C.c_int64),
         ("w_layout", C.c_int32), ("kv_layer_strips", C.c_int32), ("kv_layer_stride", C.c_int64),
         ("w_format", C.c_int32), ("_pad2", C.c_int32),
+    ]
+
+
+class WoDeferArgs(C.Structure):
+    _fields_ = [
+        ("slices", C.c_void_p), ("slice_stride", C.c_int64), ("nslices", C.c_int32), ("defer", C.c_int32),
+        ("xold", C.c_void_p), ("xnew", C.c_void_p), ("ldx", C.c_int32), ("_pad0", C.c_int32),
     ]
 
 
@@ -219,6 +226,8 @@ def lib() -> C.CDLL:
     L.dia_has_experiments.restype = C.c_int
     L.dia_gemm.argtypes = [C.POINTER(GemmArgs), C.c_void_p]
     L.dia_gemm_timed.argtypes = [C.POINTER(GemmArgs), C.c_void_p, C.POINTER(C.c_float)]
+    L.dia_gemm_wo_deferred.argtypes = [C.POINTER(GemmArgs), C.POINTER(WoDeferArgs), C.c_void_p, C.POINTER(C.c_float)]
+    L.dia_engine_set_x_alt.argtypes = [C.c_void_p, C.c_void_p]
     L.dia_mlp_fused.argtypes = [C.POINTER(GemmArgs), C.POINTER(GemmArgs), C.c_void_p, C.c_void_p]
     L.dia_mlp_fused_timed.argtypes = [C.POINTER(GemmArgs), C.POINTER(GemmArgs), C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
     L.dia_engine_mlp_fused.argtypes = [C.c_void_p]

@@ -528,6 +528,10 @@ class DecodeSession:
         mt = self.rows_pad // 16
         self.xkt, self.akt, self.hkt = self.D // 32, max(d.gqa_query_heads, d.cross_query_heads) * HEAD_DIM // 32, self.F // 32
         self.x = z(self.rows_pad, self.D)
+        # <= 4 rows: handed to the engine for the case that it lets the launch behind a wo merge wo's split-K slices (dia_engine_set_x_alt:
+        # then the residual stream of odd layers).  The engine decides per model; two-plane, 2:4, MXFP8 and compacted models and the
+        # knob wo_defer=0 keep the in-launch merge and leave this buffer (128 KB) unused
+        self.x_alt = z(self.rows_pad, self.D) if self.R <= 4 else None
         # activations between the kernels of a step travel as fp32 tiles in these buffers (the fragment order of one plane, 4-byte
         # values: 4 instead of the 6 bytes of three bf16 planes hi + mid + lo == fp32); every consumer splits the planes itself — the
         # M <= 4 GEMV while staging its image through LDS, the 16-row GEMM in registers — same arithmetic bit for bit.
@@ -572,6 +576,8 @@ class DecodeSession:
         if 16 < self.R <= 32:    # k_gemm_blk32: column blocks x K ranges of >= 8 k-tiles, 512 floats per strip and range
             n_scr = max([n_scr, w.logits.ns * -(-w.logits.kt // 8) * 512] +
                         [DL[k].ns * -(-DL[k].kt // 8) * 512 for DL in w.dec_layers for k in DEC_MATS])
+        if self.R <= 4:          # room for the two K slices of a wo whose merge is deferred (if the engine defers): one padded m-tile of x each
+            n_scr = max(n_scr, 2 * self.rows_pad * self.D)
         self.sk_scratch = z(n_scr)
         self.sk_tickets = z(max(ns_max, 8 * (self.D // 16)), dt=torch.int32)
         self.mlp_barrier = z(2, dt=torch.int32)          # dia_mlp_fused: arrivals, error flag
@@ -730,6 +736,8 @@ class DecodeSession:
         self._desc = ed
         hb.check(hb.lib().dia_engine_create(C.byref(ed), C.c_void_p(self.stream.cuda_stream), C.byref(self._engine)),
                  "dia_engine_create")
+        if self.x_alt is not None:
+            hb.check(hb.lib().dia_engine_set_x_alt(self._engine, hb.ptr(self.x_alt)), "dia_engine_set_x_alt")
 
     def close(self):
         """Tear the engine down: the stream is drained first (queued graph replays read the executable graph's own

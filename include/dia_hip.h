@@ -178,6 +178,29 @@ typedef struct {
   int32_t _pad2;
 } dia_gemm_args;
 int dia_gemm(const dia_gemm_args* a, void* stream);
+/* wo's cross-workgroup split-K merged by the launch that FOLLOWS it instead of inside it (M <= 4, dense one-plane weights, fp32
+ * activation tiles, no cmap; anything else returns DIA_E_ARG and the caller keeps the in-launch merge through dia_gemm).  The
+ * launch is described by a dia_gemm_args as for dia_gemm, plus:
+ * Producer (defer = 1; RESID_EMIT with gnext, KT = 256, sk = 2): K slice s stores the valid rows of its partial tile to
+ * slices + s * slice_stride in the fp32 tile order of P (p_ktiles, nstrips * 16 <= p_ktiles * 32) and returns: no ticket, no
+ * merge; out, P, ssq_out, sk_scratch and sk_tickets are validated as for dia_gemm but not touched.
+ * Consumer (defer = 0; SCALE_STORE, KT = 64, i.e. a row of D = 2048): instead of A and ssq_in its prologue reads the slices,
+ * (2 x 64 * 512 floats), the old residual rows xold [M][ldx >= 2048] and its own norm weight a->gnext [2048] (A must still be a
+ * valid pointer, it is not read; ssq_in is ignored), and rebuilds bit for bit what the in-launch form
+ * leaves: x_new = x_old + (s_0 + s_1), the row's sum of squares, the image x_new * gnext.  xnew (may be NULL; != xold, every
+ * workgroup reads the whole old row) receives x_new, 16 columns from each of the first D/16 workgroups.
+ * ms_out != NULL: timed as dia_gemm_timed (synchronises; dia_timed_kernel_name(0) names the kernel). */
+typedef struct {
+  float* slices;
+  int64_t slice_stride;     /* floats between two slices: at least one m-tile of P (p_ktiles * 512; the consumer: 64 * 512) */
+  int32_t nslices;          /* 2 */
+  int32_t defer;
+  const float* xold;
+  float* xnew;
+  int32_t ldx;
+  int32_t _pad0;
+} dia_wo_defer_args;
+int dia_gemm_wo_deferred(const dia_gemm_args* a, const dia_wo_defer_args* w, void* stream, float* ms_out);
 /* same launch, bracketed by dispatch-level start/stop events (hipExtLaunchKernelGGL); returns the
  * kernel's own duration in milliseconds and synchronises on its end */
 /* Fused SwiGLU MLP for 1-2 rows (batch 1): wi (DIA_EPI_SWIGLU_EMIT into planes P) and wo (DIA_EPI_RESID_EMIT reading
@@ -549,6 +572,11 @@ int dia_engine_decode(dia_engine* e, int n_steps, int use_graph);
 /* before the first graph decode: prefetch the weights of launch i+lookahead into the Infinity Cache
  * on a side branch of the step graph as soon as launch i has been issued (0 = off) */
 int dia_engine_set_prefetch(dia_engine* e, int lookahead);
+/* before the first step: a second residual buffer [rows_pad][D].  With it a step of at most 4 rows over dense one-plane weights
+ * merges wo's two K slices in the launch behind it (dia_gemm_wo_deferred; knob wo_defer=0: never): the slices lie in sk_scratch
+ * (2 * rows_pad * D floats), and the residual stream alternates between x (even layers) and x_alt (odd layers), because that
+ * launch reads the whole old row while it writes the new one.  NULL = the in-launch merge */
+int dia_engine_set_x_alt(dia_engine* e, float* x_alt);
 /* enqueue ONE decode step stopping after the logits GEMM (no sampling); for per-kernel timing */
 int dia_engine_step_logits_only(dia_engine* e);
 /* run ONE eager decode step with a HIP event recorded on the engine's stream after every launch and
