@@ -27,7 +27,13 @@ namespace {
 
 constexpr int NV = 17;                 // 64 * 17 = 1088 >= 1028
 constexpr int VCAP = NV * 64;
-constexpr int MAXC = 16;
+constexpr int MAXC = 16;               // channels the embedding kernels accept
+// k_sample keeps 3 * VCAP floats of top-p scratch per channel in dynamic LDS next to ~132 bytes of static state: 12 channels
+// are 156 672 bytes of the 160 KiB a CU has, 13 would be 169 728
+constexpr int MAXC_SAMPLE = 12;
+constexpr size_t LDS_PER_CU = 160 * 1024;
+static_assert((size_t)MAXC_SAMPLE * 3 * VCAP * sizeof(float) + 256 <= LDS_PER_CU, "k_sample's scratch must fit one CU's LDS");
+static_assert((size_t)(MAXC_SAMPLE + 1) * 3 * VCAP * sizeof(float) > LDS_PER_CU, "MAXC_SAMPLE is the largest count that fits");
 
 struct EmbedK {
   const int* tokens; const int* cur; int B, T, C, V, D;
@@ -515,6 +521,7 @@ __global__ __launch_bounds__(MAXC * 64) void k_sample(SampleK p) {
       if (ch && !replay) prow[lane] = pr;
       const int pr0 = __shfl(pr, 0, 64);
       int finished = 0, last = cur, tk = old;
+      if (!replay) bos_countdown = max(0, bos_countdown - 1);                         // under teacher too, as the reference's loop counts
       if (!p.teacher && !replay) {
         if (!eos_detected && pr0 == p.eos && !p.ignore_eos) { eos_detected = 1; eos_countdown = p.max_delay; }
         if (eos_countdown > 0) {
@@ -523,7 +530,6 @@ __global__ __launch_bounds__(MAXC * 64) void k_sample(SampleK p) {
           else if (after > d && pr != p.eos) pr = p.pad;
           eos_countdown -= 1;
         }
-        bos_countdown = max(0, bos_countdown - 1);
         tk = (bos_countdown > 0 && old != -1) ? old : pr;
         if (ch) trow[lane] = tk;
         if (eos_countdown == 0) { finished = 1; last = cur - 1; }                     // model.py:795-797 (break)
@@ -591,7 +597,9 @@ extern "C" int dia_dbg_sstamps(long long* host) {
 
 extern "C" int dia_sample(const dia_sample_args* a, void* stream) {
   if (!a || !a->logits || !a->tokens || !a->pred || !a->cur || !a->fsm || !a->delay) return dia_fail(DIA_E_ARG, "dia_sample: null argument");
-  if (a->V > VCAP || a->C > MAXC || a->C <= 0 || a->B <= 0) return dia_fail(DIA_E_ARG, "dia_sample: vocabulary > 1088 or channels > 16");
+  if (a->V > VCAP || a->V <= 0 || a->C <= 0 || a->B <= 0) return dia_fail(DIA_E_ARG, "dia_sample: vocabulary > 1088, or an empty shape");
+  if (a->C > MAXC_SAMPLE)
+    return dia_fail(DIA_E_ARG, "dia_sample: channels > 12: the sampler's top-p scratch (13056 bytes per channel) would not fit the 160 KiB LDS of a CU");
   const int nslot = (a->slot_cfg_scale != nullptr) + (a->slot_temperature != nullptr) + (a->slot_top_p != nullptr) +
                     (a->slot_top_k != nullptr) + (a->slot_max_tokens != nullptr);
   if (nslot != 0 && nslot != 5) return dia_fail(DIA_E_ARG, "dia_sample: the per-slot sampling arrays come all five or none");

@@ -357,8 +357,9 @@ typedef struct {
   int32_t ld_logits;
   int32_t B;
   int32_t T;                /* token buffer rows = audio_length */
-  int32_t C;
-  int32_t V;
+  int32_t C;                /* 1..12: the sampler keeps 13056 bytes of LDS scratch per channel, and 13 channels pass the 160 KiB of a
+                             * CU; refused before any launch (the embedding calls above take up to 16) */
+  int32_t V;                /* 1..1088 */
   int32_t max_tokens;
   float cfg_scale, temperature, top_p;
   int32_t top_k;
@@ -373,7 +374,7 @@ typedef struct {
   int32_t* tokens;          /* [B][T][C] */
   int32_t* pred;            /* [B][T][C] raw samples per step (row cur) */
   int32_t* cur;             /* [B] in/out */
-  int32_t* fsm;             /* [B][4]: eos_detected, eos_countdown, bos_countdown, done */
+  int32_t* fsm;             /* [B][8]: eos_detected, eos_countdown, bos_countdown, done, last_step, 3 unused */
   /* audio prompt (model.py:311-353, 406-422): first_step[b] = 1 + prompt frames = the first step that is
    * sampled.  Steps cur < first_step[b] REPLAY rows already in the token buffer: nothing is sampled or
    * written, the state machine does not move, only cur advances and the next row is embedded; the noise

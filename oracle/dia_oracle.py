@@ -382,11 +382,15 @@ def guided_logits(logits_2cv: torch.Tensor, cfg_scale: float, dm: Dims) -> torch
 
 def sample_next_token(lg: torch.Tensor, temperature: float, top_p: float, top_k: Optional[int],
                       noise: Optional[torch.Tensor] = None,
-                      generator: Optional[torch.Generator] = None) -> torch.Tensor:
+                      generator: Optional[torch.Generator] = None, trace: Optional[list] = None) -> torch.Tensor:
     """reference model.py:32-82.  ``noise`` (Exp(1) variates, same shape as lg) switches the
     final draw to argmax(p / noise), which is what torch.multinomial(p, 1) computes on CPU
     from the same generator stream (SURVEY.md §7 'Hard parts'); with ``noise=None`` the
-    draw is torch.multinomial itself."""
+    draw is torch.multinomial itself.
+
+    ``trace`` (a list) receives, for a draw with ``noise`` at temperature > 0, how far this very computation is from its two
+    decision edges, as a pair of floats: the smallest |cumsum[r] - top_p| / top_p over the sorted entries (inf with top-p
+    off) and the smallest (largest - second largest) / largest of p / noise over the rows.  Nothing else changes."""
     if temperature == 0.0:
         return torch.argmax(lg, dim=-1)
     lg = lg / temperature
@@ -396,7 +400,10 @@ def sample_next_token(lg: torch.Tensor, temperature: float, top_p: float, top_k:
     if top_p < 1.0:
         pr = torch.softmax(lg, dim=-1)
         sp, si = torch.sort(pr, dim=-1, descending=True)
-        rm = torch.cumsum(sp, dim=-1) > top_p
+        cs = torch.cumsum(sp, dim=-1)
+        if trace is not None:
+            cut = float(((cs - top_p).abs() / top_p).min())
+        rm = cs > top_p
         rm = torch.roll(rm, shifts=1, dims=-1)
         rm[..., 0] = False
         drop = torch.zeros_like(rm).scatter(dim=-1, index=si, src=rm)
@@ -405,6 +412,9 @@ def sample_next_token(lg: torch.Tensor, temperature: float, top_p: float, top_k:
     if torch.all(torch.isclose(pr.sum(dim=-1), torch.tensor(0.0))):
         return torch.argmax(lg, dim=-1)
     if noise is not None:
+        if trace is not None:
+            two = torch.topk(pr / noise, k=2, dim=-1).values
+            trace.append((cut if top_p < 1.0 else math.inf, float(((two[..., 0] - two[..., 1]) / two[..., 0]).min())))
         return torch.argmax(pr / noise, dim=-1)
     return torch.multinomial(pr, num_samples=1, generator=generator).squeeze(-1)
 
@@ -422,6 +432,85 @@ def exp_noise(seed: int, steps: int, C: int, V: int) -> torch.Tensor:
 # --------------------------------------------------------------------------------------
 # the generate loop (token FSM)
 # --------------------------------------------------------------------------------------
+
+@dataclass
+class LoopStep:
+    """What one pass of ``token_loop`` left behind: the state the reference's loop carries into its next iteration."""
+    cur: int                           # the token row this step worked on
+    replay: bool                       # an audio-prompt row: nothing sampled, nothing written, no state moved
+    pred: Optional[np.ndarray]         # int64 [C], the sample before the EOS logic (None on a replay row)
+    row: np.ndarray                    # tokens[cur] after the masked write
+    eos_detected: bool
+    eos_countdown: int
+    bos_countdown: int
+    finished: bool                     # the loop ends with this step
+    last_step: int                     # dec_step after this step (= dec_step at loop exit when finished)
+    ms: float = 0.0
+
+
+def token_loop(dm: Dims, tokens: np.ndarray, first_step: int, max_tokens: int, step_logits, *, cfg_scale: float,
+               temperature: float, top_p: float, top_k: Optional[int], noise: Optional[torch.Tensor] = None,
+               forced_tokens: Optional[np.ndarray] = None, ignore_eos: bool = False, max_steps: Optional[int] = None,
+               trace: Optional[list] = None):
+    """The token state machine of reference model.py:755-807 around a source of logits: a generator that runs one decode
+    step per ``next()`` and yields a ``LoopStep``.  ``tokens`` [T, C] int32 holds the delayed prefill (-1 behind it) and is
+    written in place.  ``step_logits(tokens[cur - 1], cur)`` returns the step's fp32 [2, C, V] logits; it is also called for
+    the audio-prompt rows ``cur < first_step``, whose result is dropped (see ``generate``).  Sampled step n (0-based, replay
+    rows not counted) draws with ``noise[n]``.  ``trace``: see ``sample_next_token``."""
+    md = max(dm.delay)
+    T = max_tokens
+    for cur in range(1, first_step):                                       # prompt replay (see generate's docstring)
+        step_logits(tokens[cur - 1], cur)
+        yield LoopStep(cur, True, None, tokens[cur].copy(), False, -1, md, False, cur)
+    dec_step = first_step - 1
+    bos_countdown, eos_detected, eos_countdown = md, False, -1
+    n_done = 0
+    while dec_step < T - 1:
+        cur = dec_step + 1
+        t1 = time.time()
+        lg2 = step_logits(tokens[cur - 1], cur)
+        lg = guided_logits(lg2.clone(), cfg_scale, dm)
+        nz = None if noise is None else noise[n_done]
+        pred = sample_next_token(lg.to(torch.float32), temperature, top_p, top_k, noise=nz, trace=trace).numpy().astype(np.int64)
+        sampled = pred.copy()
+        ms = (time.time() - t1) * 1e3
+        if forced_tokens is not None:
+            pred = forced_tokens[cur].astype(np.int64).copy()
+        else:
+            # EOS handling, model.py:771-788
+            if not eos_detected and pred[0] == dm.eos and not ignore_eos:
+                eos_detected, eos_countdown = True, md
+            if eos_countdown > 0:
+                after = md - eos_countdown
+                for i, d in enumerate(dm.delay):
+                    if after == d:
+                        pred[i] = dm.eos
+                    elif after > d and pred[i] != dm.eos:
+                        pred[i] = dm.pad
+                eos_countdown -= 1
+        # masked write, model.py:791-792 + state.py:195-203
+        bos_countdown = max(0, bos_countdown - 1)
+        if forced_tokens is not None:
+            tokens[cur] = pred
+        elif bos_countdown > 0:
+            m = tokens[cur] == -1
+            tokens[cur] = np.where(m, pred, tokens[cur])
+        else:
+            tokens[cur] = pred
+        n_done += 1
+        finished = False
+        if forced_tokens is None:
+            if eos_countdown == 0:
+                finished = True
+            elif cur >= T - md - 1 and not eos_detected:
+                eos_detected, eos_countdown = True, md
+        if not finished:
+            dec_step += 1
+            finished = dec_step >= T - 1 or (max_steps is not None and n_done >= max_steps)
+        yield LoopStep(cur, False, sampled, tokens[cur].copy(), eos_detected, eos_countdown, bos_countdown, finished, dec_step, ms)
+        if finished:
+            return
+
 
 @dataclass
 class GenResult:
@@ -473,56 +562,24 @@ def generate(w: Dict[str, torch.Tensor], cfg, text: str, *, max_tokens: Optional
     prefill, prefill_step = delayed_prefill(dm, audio_prompt)
     tokens = np.full((dm.T, dm.C), -1, dtype=np.int32)                     # state.py:178-188
     tokens[: prefill.shape[0]] = prefill                                  # state.py:205-208
-    for cur in range(1, prefill_step):                                     # prompt replay (see docstring)
-        decode_step(w, st, tokens[cur - 1], cur)
     prep_s = time.time() - t0
+    logits_log, preds_log, step_ms = [], [], []
+
+    def step_logits(row, cur):
+        lg2 = decode_step(w, st, row, cur)
+        if keep_logits and cur >= prefill_step:
+            logits_log.append(lg2.numpy().copy())
+        return lg2
 
     dec_step = prefill_step - 1
-    bos_countdown, eos_detected, eos_countdown = md, False, -1
-    logits_log, preds_log, step_ms = [], [], []
-    n_done = 0
-    while dec_step < T - 1:
-        cur = dec_step + 1
-        t1 = time.time()
-        lg2 = decode_step(w, st, tokens[cur - 1], cur)
-        if keep_logits:
-            logits_log.append(lg2.numpy().copy())
-        lg = guided_logits(lg2.clone(), cfg_scale, dm)
-        nz = None if noise is None else noise[n_done]
-        pred = sample_next_token(lg.to(torch.float32), temperature, top_p, cfg_filter_top_k, noise=nz).numpy().astype(np.int64)
-        preds_log.append(pred.copy())
-        step_ms.append((time.time() - t1) * 1e3)
-        if forced_tokens is not None:
-            pred = forced_tokens[cur].astype(np.int64).copy()
-        else:
-            # EOS handling, model.py:771-788
-            if not eos_detected and pred[0] == dm.eos and not ignore_eos:
-                eos_detected, eos_countdown = True, md
-            if eos_countdown > 0:
-                after = md - eos_countdown
-                for i, d in enumerate(dm.delay):
-                    if after == d:
-                        pred[i] = dm.eos
-                    elif after > d and pred[i] != dm.eos:
-                        pred[i] = dm.pad
-                eos_countdown -= 1
-        # masked write, model.py:791-792 + state.py:195-203
-        bos_countdown = max(0, bos_countdown - 1)
-        if forced_tokens is not None:
-            tokens[cur] = pred
-        elif bos_countdown > 0:
-            m = tokens[cur] == -1
-            tokens[cur] = np.where(m, pred, tokens[cur])
-        else:
-            tokens[cur] = pred
-        n_done += 1
-        if forced_tokens is None:
-            if eos_countdown == 0:
-                break
-            if cur >= T - md - 1 and not eos_detected:
-                eos_detected, eos_countdown = True, md
-        dec_step += 1
-        if max_steps is not None and n_done >= max_steps:
-            break
+    for s in token_loop(dm, tokens, prefill_step, T, step_logits, cfg_scale=cfg_scale, temperature=temperature, top_p=top_p,
+                        top_k=cfg_filter_top_k, noise=noise, forced_tokens=forced_tokens, ignore_eos=ignore_eos,
+                        max_steps=max_steps):
+        if s.replay:
+            prep_s = time.time() - t0
+            continue
+        preds_log.append(s.pred)
+        step_ms.append(s.ms)
+        dec_step = s.last_step
     codes = tokens[prefill_step: dec_step + 1].copy()
     return GenResult(tokens, prefill_step, dec_step, codes, logits_log, preds_log, step_ms, prep_s)

@@ -275,3 +275,27 @@ def test_sample_and_embed_validate_the_slot_tails_without_a_gpu():
     for n in (0, 3):
         e.n_slots = n
         assert L.dia_embed_tokens(ctypes.byref(e), None) == -1 and b"n_slots" in L.dia_last_error()
+
+
+def test_sample_refuses_channel_counts_whose_scratch_exceeds_a_cu():
+    """k_sample keeps 3 * 1088 floats of LDS per channel: 13 channels are 169 728 bytes against the 160 KiB of a CU.  The call
+    is refused with a message that says so, before any launch (no device here); 12 channels pass this check."""
+    L = hb.lib()
+    buf = ctypes.create_string_buffer(64)
+    addr = ctypes.addressof(buf)
+    s = hb.SampleArgs()
+    for k in ("logits", "tokens", "pred", "cur", "fsm", "delay"):
+        setattr(s, k, addr)
+    s.B, s.T, s.V, s.max_tokens = 1, 64, 1028, 65                          # max_tokens > T: the last of dia_sample's checks
+    for c in (13, 14, 16):
+        s.C = c
+        assert L.dia_sample(ctypes.byref(s), None) == -1
+        msg = L.dia_last_error()
+        assert b"channels > 12" in msg and b"LDS" in msg, msg
+    for c, word in ((17, b"channels > 12"), (0, b"an empty shape")):             # in this order: the shape, then the channel bound
+        s.C = c
+        assert L.dia_sample(ctypes.byref(s), None) == -1
+        msg = L.dia_last_error()
+        assert word in msg, (c, msg)
+    s.C = 12
+    assert L.dia_sample(ctypes.byref(s), None) == -1 and b"max_tokens out of range" in L.dia_last_error()
