@@ -54,6 +54,10 @@ def build_parser() -> argparse.ArgumentParser:
     g.add_argument("--slots", type=int, default=0, help="N > 0: split the text into chunks (the front-end's chunk plan) and generate them as "
                    "independent utterances sharing N slots of one continuously batched session; needs --codes-output (the chunks' "
                    "codes are joined in order); not with --audio-prompt (a prompt chain is sequential)")
+    g.add_argument("--stream-chunk", type=int, default=0, help="N > 0: hand the codes out every N decode steps while the utterance is "
+                   "generated (Dia.stream_frames; one slot, or the --slots chunk plan); needs --codes-output, whose file is the one "
+                   "written without this flag; frames are appended to <codes-output>.frames (raw int32 [n, C]) as they arrive when "
+                   "there is one utterance; not with --audio-prompt or --output")
     g = p.add_argument_group("Infrastructure")
     g.add_argument("--device", type=str, default=None, help="HIP device such as cuda:0 (default: the current one)")
     g.add_argument("--compute-dtype", type=str, default="bfloat16", choices=["float16", "bfloat16", "float32"], help="K/V cache dtype: bfloat16 (default; float16 is accepted and mapped to it) or float32.")
@@ -70,6 +74,52 @@ def build_parser() -> argparse.ArgumentParser:
     return p
 
 
+def stream_to_file(dia, args, full_text: str) -> int:
+    """--stream-chunk: the text (one utterance in one slot, or the --slots chunk plan) through Dia.stream_frames.  With one
+    utterance every chunk is appended to <codes-output>.frames the moment it arrives; at the end the chunks are joined into the
+    .npy that the run without --stream-chunk writes, and the .frames file is removed."""
+    import time
+
+    kw = dict(cfg_scale=args.cfg_scale, temperature=args.temperature, top_p=args.top_p, cfg_filter_top_k=args.cfg_filter_top_k)
+    if args.slots:
+        from dia_hip.callers import stream_chunks_codes
+        it = stream_chunks_codes(dia, full_text, slots=args.slots, chunk=args.stream_chunk, seed=args.seed,
+                                 max_new_tokens=args.max_tokens or dia.config.data.audio_length, **kw)
+    else:
+        it = dia.stream_frames([full_text], 1, max_tokens=args.max_tokens, seeds=None if args.seed is None else [args.seed],
+                               chunk=args.stream_chunk, **kw)
+    out = Path(args.codes_output)
+    out.parent.mkdir(parents=True, exist_ok=True)
+    side = None if args.slots else open(str(out) + ".frames", "wb")
+    parts, t0, first = {}, time.time(), None
+    try:
+        for i, start, codes, final in it:
+            now = time.time() - t0
+            parts.setdefault(i, []).append(codes)
+            if codes.shape[-1]:
+                first = now if first is None else first
+                if side is not None:
+                    side.write(np.ascontiguousarray(codes[0].T).tobytes())
+                    side.flush()
+            if args.verbose:
+                print(f"stream: utterance {i} frames [{start}, {start + codes.shape[-1]}){' final' if final else ''} at {now * 1e3:.1f} ms")
+    finally:
+        if side is not None:
+            side.close()
+            os.remove(side.name)
+    joined = [np.concatenate(parts[i], axis=-1) for i in sorted(parts)]
+    joined = [c for c in joined if c.shape[-1] > 0]
+    if not joined:
+        print("Generation failed to produce codes.")
+        return 1
+    codes = np.concatenate(joined, axis=-1)
+    np.save(args.codes_output, codes)
+    if args.verbose and first is not None:
+        print(f"stream: first chunk after {first * 1e3:.1f} ms, {codes.shape[-1]} frames in {time.time() - t0:.3f}s")
+    print(f"Codes saved to {args.codes_output}: shape {tuple(codes.shape)}")
+    return 0
+
+
 def main(argv=None) -> int:
     parser = build_parser()
     args = parser.parse_args(argv)
@@ -81,6 +131,8 @@ def main(argv=None) -> int:
         parser.error("one of --output / --codes-output is required.")
     if args.slots < 0 or (args.slots and (args.audio_prompt or not args.codes_output or args.output)):
         parser.error("--slots N needs N > 0, --codes-output, and neither --audio-prompt nor --output.")
+    if args.stream_chunk < 0 or (args.stream_chunk and (args.audio_prompt or not args.codes_output or args.output)):
+        parser.error("--stream-chunk N needs N > 0, --codes-output, and neither --audio-prompt nor --output.")
     if args.no_dac and args.output:
         parser.error("--output needs the audio codec; use --codes-output with --no-dac.")
 
@@ -121,6 +173,14 @@ def main(argv=None) -> int:
     if prompt and prompt.endswith(".npy"):
         prompt = torch.from_numpy(np.load(prompt).astype(np.int64))
     print("Generating audio...")
+    if args.stream_chunk:
+        try:
+            return stream_to_file(dia, args, full_text)
+        except Exception as e:
+            print(f"Error during audio generation or saving: {e}")
+            import traceback
+            traceback.print_exc()
+            return 1
     if args.slots:
         try:
             from dia_hip.callers import generate_chunks_codes

@@ -22,7 +22,7 @@ ATTN_SELF, ATTN_CROSS, ATTN_ENC = 0, 1, 2
 
 EXPORTS = (
     "dia_last_error", "dia_abi_version", "dia_device_count", "dia_set_tuning", "dia_get_tuning", "dia_has_experiments", "dia_gemm", "dia_gemm_timed", "dia_gemm_wo_deferred", "dia_mlp_fused", "dia_mlp_fused_timed", "dia_engine_mlp_fused", "dia_attn", "dia_attn_scratch_floats", "dia_enc_kv_prep", "dia_enc_attn", "dia_dec_prefill_embed", "dia_dec_prefill_kv", "dia_dec_prefill_attn",
-    "dia_embed_text", "dia_embed_tokens", "dia_sample", "dia_slot_admit", "dia_slot_retire", "dia_prefetch", "dia_engine_create", "dia_engine_destroy",
+    "dia_embed_text", "dia_embed_tokens", "dia_sample", "dia_slot_admit", "dia_slot_retire", "dia_emit_frames", "dia_prefetch", "dia_engine_create", "dia_engine_destroy",
     "dia_engine_decode", "dia_engine_set_prefetch", "dia_engine_set_x_alt", "dia_engine_step_logits_only", "dia_engine_profile_step", "dia_engine_time_step", "dia_timed_kernel_name", "dia_engine_launches_per_step", "dia_mxfp8_classes",
     "dia_seg_mlp", "dia_seg_workspace_bytes", "dia_seg_workspace_control_bytes", "dia_seg_slots", "dia_seg_supported", "dia_seg_error",
 )
@@ -142,6 +142,20 @@ class SlotAdmitArgs(C.Structure):
     ]
 
 
+EMIT_RESET = 1                                            # DIA_EMIT_RESET
+
+
+class EmitArgs(C.Structure):
+    """dia_emit_args: `slot` is a HOST array read during the call, everything behind it are device pointers"""
+    _fields_ = [
+        ("B", C.c_int32), ("T", C.c_int32), ("C", C.c_int32), ("max_delay", C.c_int32), ("codebook_size", C.c_int32),
+        ("cap", C.c_int32), ("n", C.c_int32), ("flags", C.c_int32),
+        ("slot", C.POINTER(C.c_int32)),
+        ("tokens", C.c_void_p), ("cur", C.c_void_p), ("fsm", C.c_void_p), ("first_step", C.c_void_p), ("delay", C.c_void_p),
+        ("emitted", C.c_void_p), ("out", C.c_void_p), ("state", C.c_void_p),
+    ]
+
+
 class DecLayer(C.Structure):
     _fields_ = [
         ("w_qkv", C.c_void_p), ("w_o", C.c_void_p), ("w_cq", C.c_void_p), ("w_co", C.c_void_p),
@@ -244,6 +258,7 @@ def lib() -> C.CDLL:
     L.dia_sample.argtypes = [C.POINTER(SampleArgs), C.c_void_p]
     L.dia_slot_admit.argtypes = [C.POINTER(SlotAdmitArgs), C.c_void_p]
     L.dia_slot_retire.argtypes = [C.POINTER(SlotAdmitArgs), C.c_void_p]
+    L.dia_emit_frames.argtypes = [C.POINTER(EmitArgs), C.c_void_p]
     L.dia_prefetch.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_void_p]
     L.dia_engine_create.argtypes = [C.POINTER(EngineDesc), C.c_void_p, C.POINTER(C.c_void_p)]
     L.dia_engine_destroy.argtypes = [C.c_void_p]

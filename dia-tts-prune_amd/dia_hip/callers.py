@@ -116,6 +116,21 @@ def generate_chunks_codes(dia, text: str, *, slots: int = 8, chunk_size: int = 0
     return [c for c in out if c.shape[-1] > 0]
 
 
+def stream_chunks_codes(dia, text: str, *, slots: int = 8, chunk: int = 16, chunk_size: int = 0, max_new_tokens: int = 3072,
+                        cfg_scale: float = 3.0, temperature: float = 1.3, top_p: float = 0.95, cfg_filter_top_k: int = 35,
+                        seed: Optional[int] = None):
+    """generate_chunks_codes through Dia.stream_frames: the same plan, seeds and slots, but the frames of every batch of the plan
+    arrive while it is generated — yields (plan index, start frame, codes [1, C, n], final).  Joining each batch's chunks and
+    dropping the empty batches gives the list generate_chunks_codes returns."""
+    if not text or text.isspace():
+        raise ValueError("Text input cannot be empty.")
+    plan = plan_batches(text, chunk_size, max_new_tokens)
+    T_cap = dia.config.data.audio_length
+    yield from dia.stream_frames([bt for bt, _ in plan], slots, max_tokens=[min(T_cap, 1 + budget) for _, budget in plan],
+                                 cfg_scale=cfg_scale, temperature=temperature, top_p=top_p, cfg_filter_top_k=cfg_filter_top_k,
+                                 seeds=None if seed is None else [seed + i for i in range(len(plan))], chunk=chunk)
+
+
 def generate_long(dia, text: str, **kw) -> Optional[np.ndarray]:
     """as the front-end: decode every batch, join with 0.2 s of silence (app.py:238-250).  Needs the codec."""
     segs: List[np.ndarray] = []

@@ -28,6 +28,7 @@ from . import layout as lay
 from .config import DiaConfig
 from .pruning import is_2of4
 from .quant import is_mxfp8
+from .tokens import CODEBOOK_SIZE
 
 HEAD_DIM = 128
 _TILERS = {1: lay.tile_weight, 2: lay.tile_weight_bf16x2, 3: lay.tile_weight_planes}       # weight_planes -> layout of a DenseGeneral kernel
@@ -1087,14 +1088,18 @@ class DecodeSession:
     def open(cls, w: DeviceWeights, slots: int, *, s_cap: Optional[int] = None, kv_dtype: str = "bf16",
              max_tokens: Optional[int] = None, ignore_eos: bool = False, stream: Optional[torch.cuda.Stream] = None,
              cfg_scale: float = 3.0, temperature: float = 1.3, top_p: float = 0.95, top_k: int = 35,
-             attention: str = "auto") -> "DecodeSession":
+             attention: str = "auto", stream_cap: Optional[int] = None) -> "DecodeSession":
         """A session of `slots` PARKED slots for a stream of requests: admit() puts a request into a free slot between two decode
         steps, the step graph (captured once) serves whatever the slots hold, retire() parks a finished one; serve() is the
         driver loop.  Cross caches are sized for texts of `s_cap` bytes (default: the encoder's text_length), the noise buffer for
         `max_tokens` steps per slot (default: audio_length) — a request's own max_tokens may be smaller, not larger.  The sampling
-        arguments are what a parked slot holds until its first admission; every request brings its own."""
+        arguments are what a parked slot holds until its first admission; every request brings its own.
+        stream_cap=N adds the buffers of frame streaming (stream_iter): a staging area of N frames per slot on the device, two
+        pinned host copies of it, a side stream for the copies.  None: no such buffer exists and nothing new is launched."""
         if int(slots) < 1:
             raise ValueError("slots must be >= 1")
+        if stream_cap is not None and int(stream_cap) < 1:
+            raise ValueError("stream_cap must be >= 1")
         if float(temperature) == 0.0:
             temperature = 1.0                      # (the noise buffer is always allocated; requests bring their own temperature)
         cap = w.cfg.data.text_length if s_cap is None else int(s_cap)
@@ -1105,6 +1110,8 @@ class DecodeSession:
                 top_p=top_p, top_k=top_k, ignore_eos=ignore_eos, stream=stream, s_cap=_ceil(cap, 32), attention=attention,
                 _slotted=True)
         s.text_cap = cap                           # (the caches hold whole 32-key blocks; requests are held to what was asked for)
+        if stream_cap is not None:
+            s._init_stream(int(stream_cap))
         return s
 
     def _init_slots(self):
@@ -1243,7 +1250,7 @@ class DecodeSession:
         where it stopped (row r of a slot = its request's draw number r, read at step first_step + r)."""
         todo = []
         for b, sl in self._live.items():
-            if sl["gen"] is None:
+            if sl["gen"] is None or sl.get("ended"):         # (ended: stream_iter has seen the slot's finished flag)
                 continue
             done = self._issued - sl["t0"]
             need = min(done + int(n_steps), sl["req"].max_tokens - 1)
@@ -1254,7 +1261,7 @@ class DecodeSession:
 
         def draw(job):
             _, sl, r0, r1 = job
-            t = torch.empty(r1 - r0, self.C, self.V, dtype=torch.float32)
+            t = torch.empty(r1 - r0, self.C, self.V, dtype=torch.float32, pin_memory=self._streaming)
             t.exponential_(1.0, generator=sl["gen"])
             return t
 
@@ -1270,6 +1277,10 @@ class DecodeSession:
 
     def _upload_noise(self, b: int, r0: int, rows: torch.Tensor):
         with torch.cuda.stream(self.stream):
+            if self._streaming:                  # drawn into pinned memory: the copy is queued, the host does not wait for the stream
+                self._pinned.append(rows)
+                self.noise[b, r0: r0 + rows.shape[0]].copy_(rows, non_blocking=True)
+                return
             self.noise[b, r0: r0 + rows.shape[0]].copy_(rows, non_blocking=False)
 
     def _read_state(self):
@@ -1295,6 +1306,11 @@ class DecodeSession:
         last = int(fsm[b, 4]) if fsm[b, 3] else int(cur[b]) - 1
         del self._live[b]
         return UtteranceResult(tok, tok[sl["first_step"]: last + 1].copy(), last, prd, len(sl["req"].text_ids))   # model.py:831
+
+    def release(self, b: int):
+        """A live slot becomes free WITHOUT its result being read (frame streaming took the frames out already; cancel() drops
+        them): nothing is downloaded and nothing enqueued.  The driver loop retires or refills the slot at its next iteration."""
+        del self._live[b]
 
     def serve_iter(self, requests: Sequence, poll: int = 64, use_graph: bool = True):
         """The driver loop: fill free slots from the queue, decode up to `poll` steps, collect what finished, retire what stays
@@ -1332,6 +1348,153 @@ class DecodeSession:
         for i, r in self.serve_iter(reqs, poll, use_graph):
             out[i] = r
         return out
+
+    # ------------------------------------------------------------------ frame streaming (DESIGN.md "Frame streaming")
+    stream_cap: Optional[int] = None             # frames per slot and dia_emit_frames call; None = a session without streaming buffers
+    _streaming = False                           # inside stream_iter: noise top-ups are drawn into pinned memory and copied asynchronously
+
+    def _init_stream(self, cap: int):
+        """Device staging of dia_emit_frames + what brings it to the host: two pinned copies, a side stream, events."""
+        B, dev = self.B, self.dev
+        self.stream_cap = cap
+        self.emitted = torch.zeros(B, dtype=torch.int32).to(dev)
+        self.emit_out = torch.zeros(B, cap, self.C, dtype=torch.int32).to(dev)
+        self.emit_state = torch.tensor([[0, 0, -1, 0]] * B, dtype=torch.int32).to(dev)
+        self._emit_host = [(torch.zeros(B, cap, self.C, dtype=torch.int32).pin_memory(), torch.zeros(B, 4, dtype=torch.int32).pin_memory())
+                           for _ in range(2)]
+        self._emit_side = torch.cuda.Stream(device=dev)
+        self._emit_ev = torch.cuda.Event()                           # session stream: the emit launch of an iteration is behind us
+        self._copy_ev = [torch.cuda.Event(), torch.cuda.Event()]     # side stream: pinned pair i holds that iteration's staging
+        self._copy_busy = None                                       # the copy event the next launch that writes the staging waits for
+        self._owner: Dict[int, int] = {}                             # slot -> request index of the running stream_iter
+        self._queue: List[int] = []                                  # request indices not admitted yet
+
+    def _enqueue_emit(self, slots: Sequence[int], reset: bool = False):
+        """dia_emit_frames for these slots on the session's stream (reset: DIA_EMIT_RESET, behind their admission).  The launch
+        writes the staging area, so the stream first waits (on the device) for the copy that still reads it."""
+        if self._copy_busy is not None:
+            self.stream.wait_event(self._copy_busy)
+            self._copy_busy = None
+        a = hb.EmitArgs()
+        a.B, a.T, a.C, a.max_delay, a.codebook_size, a.cap = self.B, self.T, self.C, self.max_delay, CODEBOOK_SIZE, self.stream_cap
+        a.flags = hb.EMIT_RESET if reset else 0
+        a.tokens, a.cur, a.fsm, a.first_step, a.delay = (hb.ptr(t) for t in (self.tokens, self.cur, self.fsm, self.first_step, self.delay))
+        a.emitted, a.out, a.state = hb.ptr(self.emitted), hb.ptr(self.emit_out), hb.ptr(self.emit_state)
+        slots = [int(b) for b in slots]
+        for i in range(0, len(slots), hb.SLOTS_PER_CALL):
+            part = slots[i: i + hb.SLOTS_PER_CALL]
+            a.n, a.slot = len(part), (C.c_int32 * len(part))(*part)
+            hb.check(hb.lib().dia_emit_frames(C.byref(a), C.c_void_p(self.stream.cuda_stream)), "dia_emit_frames")
+
+    def _enqueue_fetch(self, k: int):
+        """staging + records -> pinned pair k % 2, on the side stream behind everything the session's stream holds so far: two
+        asynchronous copies of fixed size, then the copy event"""
+        out_h, state_h = self._emit_host[k % 2]
+        self._emit_ev.record(self.stream)
+        self._emit_side.wait_event(self._emit_ev)
+        with torch.cuda.stream(self._emit_side):
+            out_h.copy_(self.emit_out, non_blocking=True)
+            state_h.copy_(self.emit_state, non_blocking=True)
+        self._copy_ev[k % 2].record(self._emit_side)
+        self._copy_busy = self._copy_ev[k % 2]
+
+    def _wait_fetch(self, k: int):
+        """(out [B, cap, C], state [B, 4]) of iteration k on the host: waits for that iteration's copy event, nothing else"""
+        self._copy_ev[k % 2].synchronize()
+        out_h, state_h = self._emit_host[k % 2]
+        return out_h.numpy(), state_h.numpy()
+
+    def cancel(self, request_index: int):
+        """Drop a request of the running stream_iter (between two next() calls): no further chunk of it is yielded.  A request
+        still queued is never admitted; a running one gives up its slot with release(), and the loop's next iteration retires or
+        refills that slot.  Other slots are not touched."""
+        ri = int(request_index)
+        if ri in self._queue:
+            self._queue.remove(ri)
+        for b, r in list(self._owner.items()):
+            if r == ri:
+                del self._owner[b]
+                self.release(b)
+
+    def stream_iter(self, requests: Sequence, chunk: int = 16, lag: int = 1, use_graph: bool = True):
+        """serve_iter that hands frames out while the utterances run: yields (request index, start frame, codes [1, C, n], final)
+        — codes is what codes_for_codec would hold at [:, :, start: start + n] once the utterance has ended.  Every utterance ends
+        with exactly one final chunk (empty when its last frames went out earlier or it has no frame at all).
+
+        Iteration k: fill free slots from the queue (DIA_EMIT_RESET behind their admission), retire idle ones, decode up to `chunk`
+        steps, dia_emit_frames for the live slots, copy staging and records to pinned pair k % 2 on the side stream.  The host
+        then waits for the copy event of iteration k - lag only, never for the session's stream: with lag = 1 the next chunk is
+        queued before this one is read.  lag = 0 reads every iteration at once.  A slot is freed (release(): nothing is
+        downloaded) when its record says start + n == total; a backlog larger than stream_cap is drained by further calls."""
+        if not self.slotted or self.stream_cap is None:
+            raise hb.DiaHipError("stream_iter() needs a session made by DecodeSession.open(..., stream_cap=N)")
+        if int(lag) not in (0, 1) or int(chunk) < 1:
+            raise ValueError("lag must be 0 or 1 (two pinned copies), chunk >= 1")
+        if self._live:
+            raise hb.DiaHipError("stream_iter() starts on a session without live slots")
+        reqs = [self._as_request(r) for r in requests]           # every ValueError before anything is enqueued
+        chunk, lag = int(chunk), int(lag)
+        owner, queue = self._owner, self._queue
+        owner.clear()
+        queue[:] = range(len(reqs))
+        pending = []            # (k, [(slot, request index)] of its emit call, pinned sources of the copies queued before it)
+        k = 0
+        self._streaming = True
+        try:
+            while queue or self._live or pending:
+                if queue or self._live:
+                    free = self.free_slots()
+                    take = min(len(free), len(queue))
+                    if take:
+                        pairs = [(b, reqs[ri]) for b, ri in zip(free, queue[:take])]
+                        for i in range(0, take, hb.SLOTS_PER_CALL):
+                            self._admit(pairs[i: i + hb.SLOTS_PER_CALL])
+                        self._enqueue_emit(free[:take], reset=True)
+                        owner.update(zip(free[:take], queue[:take]))
+                        del queue[:take]
+                    idle = [b for b in self.free_slots() if b not in self._parked]
+                    if idle:
+                        self.retire(idle)
+                if self._live:
+                    n = min(chunk, max([self._steps_left(b) for b, sl in self._live.items() if not sl.get("ended")] + [0]))
+                    if n > 0:
+                        self.decode(n, use_graph)
+                    live = sorted(self._live)
+                    self._enqueue_emit(live)
+                    self._enqueue_fetch(k)
+                    pins, self._pinned = self._pinned, []
+                    pending.append((k, [(b, owner[b]) for b in live], pins))
+                    k += 1
+                    if n > 0:
+                        self.ensure_noise(self._issued + chunk)  # the next chunk's noise is drawn while this one runs
+                while pending and (len(pending) > lag or not self._live):
+                    kk, who, _ = pending.pop(0)
+                    out, state = self._wait_fetch(kk)
+                    for b, ri in who:
+                        if owner.get(b) != ri:                   # released or cancelled since that call was queued
+                            continue
+                        start, m, total, fin = (int(v) for v in state[b])
+                        final = bool(fin) and start + m == total
+                        if fin:
+                            self._live[b]["ended"] = True        # (no further decode steps on its account)
+                        if not (m or final):
+                            continue
+                        # an own copy: the pinned pair is overwritten two iterations on (a [1, C] window transposed is
+                        # contiguous as it stands, so ascontiguousarray would hand out a view of it)
+                        codes = np.array(out[b, :m].T, order="C", copy=True)[None]
+                        if final:
+                            del owner[b]
+                            self.release(b)
+                        yield ri, start, codes, final
+            idle = [b for b in range(self.B) if b not in self._parked and b not in self._live]
+            if idle:
+                self.retire(idle)
+            self.sync()
+            self._raise_if_invalid()
+        finally:
+            self._streaming = False
+            for _, _, pins in pending:                           # (an abandoned generator: copies may still be queued)
+                self._pinned.extend(pins)
 
     # ------------------------------------------------------------------ accounting (SURVEY.md §8d)
     def step_bytes(self, n_keys: Optional[int] = None) -> int:

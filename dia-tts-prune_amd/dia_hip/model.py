@@ -286,6 +286,38 @@ class Dia:
                 s.close()
 
     @torch.inference_mode()
+    def stream_frames(self, requests_or_texts: Sequence[Union[str, GenerationRequest]], slots: int = 8,
+                      max_tokens=None, cfg_scale=3.0, temperature=1.3, top_p=0.95, cfg_filter_top_k=35,
+                      seeds: Optional[Sequence[Optional[int]]] = None, ignore_eos: bool = False,
+                      audio_prompts: Optional[Sequence[Optional[np.ndarray]]] = None,
+                      audio_prompt_texts: Optional[Sequence[Optional[str]]] = None, s_cap: Optional[int] = None,
+                      chunk: int = 16, stream_cap: Optional[int] = None, lag: int = 1):
+        """generate_stream that hands the codec input out WHILE the utterances run: yields (request index, start frame,
+        codes [1, C, n], final) every `chunk` decode steps — frames [start, start + n) of what generate_stream would yield for
+        that request at the end, final exactly once per request (possibly with n = 0).  A frame is final max_delay steps after it
+        was sampled (DESIGN.md "Frame streaming").  stream_cap: frames per slot one hand-over can carry (default 4 * chunk);
+        lag = 1 keeps the next chunk queued on the GPU while this one is read, lag = 0 reads each chunk as soon as it is queued."""
+        if self.model is None:
+            raise RuntimeError("no weights loaded")
+        items = list(requests_or_texts)
+        reqs = self._requests(items, max_tokens, cfg_scale, temperature, top_p, cfg_filter_top_k, seeds, audio_prompts, audio_prompt_texts)
+        if not reqs:
+            return
+        cap = max([r.max_tokens for r in reqs if r.max_tokens is not None] or [self.config.data.audio_length])
+        if any(r.max_tokens is None for r in reqs):
+            cap = self.config.data.audio_length
+        if s_cap is None:
+            s_cap = max(32, max(len(r.text_ids) for r in reqs))
+        with torch.cuda.device(self.device):
+            s = DecodeSession.open(self.model, min(int(slots), len(reqs)), s_cap=min(int(s_cap), self.config.data.text_length),
+                                   kv_dtype=self._kv_dtype(), max_tokens=cap, ignore_eos=ignore_eos,
+                                   stream_cap=4 * int(chunk) if stream_cap is None else int(stream_cap))
+            try:
+                yield from s.stream_iter(reqs, chunk=chunk, lag=lag)
+            finally:
+                s.close()
+
+    @torch.inference_mode()
     def generate_batch(self, texts: Sequence[str], max_tokens: Optional[int] = None, cfg_scale: float = 3.0,
                        temperature: float = 1.3, top_p: float = 0.95, cfg_filter_top_k: int = 35,
                        seeds: Optional[Sequence[Optional[int]]] = None, verbose: bool = False,

@@ -91,6 +91,9 @@ def delayed_prefill(cfg: DiaConfig, prompt: Optional[np.ndarray] = None) -> Tupl
     return out.astype(np.int32), step
 
 
+CODEBOOK_SIZE = 1024            # ids the codec accepts: [0, CODEBOOK_SIZE); anything else becomes 0 on the way out
+
+
 def codes_for_codec(codes: np.ndarray, cfg: DiaConfig, codebook_size: int = 1024) -> np.ndarray:
     """Undo the delay pattern and trim, i.e. what ``Dia._generate_output`` hands to the codec
     (reference dia/audio.py:88-163 + dia/model.py:498-533): ``out[t,c] = in[min(t+d_c, T-1), c]``,
@@ -104,5 +107,28 @@ def codes_for_codec(codes: np.ndarray, cfg: DiaConfig, codebook_size: int = 1024
     out = codes[t_src, np.arange(da.channels)[None, :]]
     keep = max(n - int(delay.max()), 0)
     out = out[:keep].copy()
+    out[(out < 0) | (out > codebook_size - 1)] = 0
+    return np.ascontiguousarray(out.T)[None]
+
+
+def ready_frames(cur: int, finished, last: int, first_step: int, max_delay: int) -> int:
+    """The finality rule of frame streaming (DESIGN.md "Frame streaming"), stated once: how many codec frames of an utterance are
+    final, given its device state ``cur[b]``, ``fsm[b, 3]`` (finished), ``fsm[b, 4]`` (last) and ``first_step[b]``.
+    A step writes token row ``cur`` and no later step rewrites it, so rows ``[first_step, W)`` with ``W = last + 1`` once the
+    utterance has finished, ``cur`` while it runs, belong to its output slice for good.  ``codes_for_codec`` reads row ``t + d_c``
+    for frame ``t`` and drops the last ``max_delay`` rows: frame ``t`` is final, and kept, exactly when
+    ``t < max(0, W - first_step - max_delay)``.  Once finished this is the utterance's total frame count."""
+    w = int(last) + 1 if finished else int(cur)
+    return max(0, w - int(first_step) - int(max_delay))
+
+
+def frames_window(tokens_rows: np.ndarray, first_step: int, start: int, n: int, delay, codebook_size: int = 1024) -> np.ndarray:
+    """Frames ``[start, start + n)`` of the utterance whose token buffer is ``tokens_rows`` [T, C], as the codec receives them:
+    ``out[0, c, i] = tokens_rows[first_step + start + i + delay[c], c]``, ids outside ``[0, codebook_size)`` -> 0, layout
+    [1, C, n] (that of ``codes_for_codec``).  Valid for frames below ``ready_frames``; dia_emit_frames computes the same."""
+    tok = np.asarray(tokens_rows)
+    d = np.asarray(delay, dtype=np.int64)
+    rows = int(first_step) + int(start) + np.arange(int(n), dtype=np.int64)[:, None] + d[None, :]       # [n, C]
+    out = tok[rows, np.arange(tok.shape[1])[None, :]].copy()
     out[(out < 0) | (out > codebook_size - 1)] = 0
     return np.ascontiguousarray(out.T)[None]

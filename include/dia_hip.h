@@ -20,7 +20,8 @@ extern "C" {
 #endif
 
 /* The version stays 8 although dia_embed_args / dia_sample_args grew at their tails and dia_slot_admit / dia_slot_retire were added
- * (continuous batching): zero-filled tails behave as before, and a binding of the older layout fails the sizeof / export checks. */
+ * (continuous batching): zero-filled tails behave as before, and a binding of the older layout fails the sizeof / export checks.
+ * dia_emit_frames / dia_emit_args (frame streaming) are a new entry point and a new struct: nothing older changed. */
 #define DIA_ABI_VERSION 8
 
 #define DIA_OK 0
@@ -437,6 +438,41 @@ typedef struct {
 } dia_slot_admit_args;
 int dia_slot_admit(const dia_slot_admit_args* a, void* stream);
 int dia_slot_retire(const dia_slot_admit_args* a, void* stream);
+
+/* Frame streaming: take the codec frames that have become FINAL out of running slots, in ONE launch, in stream order between two
+ * decode steps / graph replays (csrc/stream.hip; DESIGN.md "Frame streaming").  A step writes token row cur and no later step
+ * rewrites it, so with W = fsm[3] ? fsm[4] + 1 : cur the rows [first_step, W) of a slot belong to its output slice for good, and
+ * frame t — what the reference's codec input holds at [t] after the delay pattern is undone and the last max_delay rows are
+ * dropped (dia/audio.py:88-163, model.py:498-533) — is final exactly when t < ready = max(0, W - first_step - max_delay).
+ * For every listed slot b: n = min(ready - emitted[b], cap) frames [emitted[b], emitted[b] + n) go to out[b][0..n)[C] as
+ * tokens[b][first_step + t + delay[c]][c], ids outside [0, codebook_size) -> 0; state[b] = {start = emitted[b], n,
+ * total = finished ? ready : -1, finished}; emitted[b] += n.  A slot has been taken out completely when start + n == total.
+ * Reads tokens / cur / fsm / first_step / delay and writes none of them; rows [n, cap) of out[b] and slots that are not listed are
+ * left alone.  Plain loads and stores, no atomics: stream order is the only ordering.
+ * flags = DIA_EMIT_RESET: the listed slots start over instead — emitted[b] = 0, state[b] = {0, 0, -1, 0} — to be enqueued behind
+ * dia_slot_admit for the same slots (reads n, slot, the shape and the emitted / state pointers only).
+ * The slot list is a HOST array read during the call (it travels as kernel arguments); at most DIA_SLOTS_PER_CALL slots per call. */
+#define DIA_EMIT_RESET 1
+typedef struct {
+  int32_t B, T, C;             /* session shape: slots, token rows, channels (1..16) */
+  int32_t max_delay;           /* largest entry of delay, in [0, T) */
+  int32_t codebook_size;
+  int32_t cap;                 /* frames per slot and call = depth of out, >= 1 */
+  int32_t n;                   /* slots in this call, 1..DIA_SLOTS_PER_CALL */
+  int32_t flags;               /* 0 or DIA_EMIT_RESET */
+  const int32_t* slot;         /* host [n], distinct, each < B */
+  /* device state of the session, as in dia_sample_args (read only) */
+  const int32_t* tokens;       /* [B][T][C] */
+  const int32_t* cur;          /* [B] */
+  const int32_t* fsm;          /* [B][8] */
+  const int32_t* first_step;   /* [B], NULL = 1 everywhere */
+  const int32_t* delay;        /* [C] */
+  /* streaming state (device) */
+  int32_t* emitted;            /* [B] frames taken out of the slot's utterance so far */
+  int32_t* out;                /* [B][cap][C] staging, frame-major */
+  int32_t* state;              /* [B][4] start, n, total, finished of the last call */
+} dia_emit_args;
+int dia_emit_frames(const dia_emit_args* a, void* stream);
 
 /* Read-only pass over [ptr, ptr+nbytes) that pulls it into the 256 MiB Infinity Cache ahead of its
  * consumer (weights of the next kernels of the decode chain); writes nothing. */
