@@ -67,9 +67,10 @@ def build_parser() -> argparse.ArgumentParser:
     g.add_argument("--sparse-weights", type=str, default="off", choices=["off", "2:4"],
                    help="2:4 = the checkpoint is 2:4-pruned (offline_prune.py --prune-mode 2:4): batch 1-2 decode steps stream its "
                         "decoder matrices in the compressed 2:4 form (sparse MFMA); off = dense tiles only")
-    g.add_argument("--weight-format", type=str, default="bf16", choices=["bf16", "mxfp8"],
+    g.add_argument("--weight-format", type=str, default="bf16", choices=["bf16", "mxfp8", "mxfp4"],
                    help="mxfp8 = the checkpoint is MXFP8-quantised (offline_quantize.py): batch 1-8 decode steps stream its decoder "
-                        "matrices as e4m3 elements + block scales (half the weight bytes); bf16 = dense tiles only")
+                        "matrices as e4m3 elements + block scales (half the weight bytes); mxfp4 = the same for an MXFP4-quantised "
+                        "checkpoint (--format mxfp4: e2m1 elements, a quarter of the bytes); bf16 = dense tiles only")
     g.add_argument("--verbose", action="store_true", help="report prefill and generation timing")
     return p
 

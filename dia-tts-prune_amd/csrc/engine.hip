@@ -26,6 +26,8 @@ struct dia_engine {
   int mlp_fused = -1;             // -1 not tried yet, 1 the MLP runs as one fused launch, 0 two launches
   int wo_defer = -1;              // -1 not tried yet, 1 wo's split-K slices are merged by the launch behind it, 0 inside wo (dia_gemm_wo_deferred refused)
   float* x_alt = nullptr;         // dia_engine_set_x_alt: the residual stream of odd layers while wo_defer is in force
+  std::vector<dia_mxfp4_layer> f4;      // dia_engine_set_mxfp4: the MXFP4 streams per layer (empty: none) ...
+  const void* f4_logits = nullptr;      // ... and of the logits head
   std::vector<hipEvent_t> prof;   // when non-empty: one event recorded after every launch (profile step)
   // weight prefetch beside the chain (graph mode): launch i+lookahead's weights are pulled into the
   // Infinity Cache by a side stream as soon as launch i has been issued
@@ -66,6 +68,16 @@ extern "C" int dia_mxfp8_classes(int rows) {
   return (rows <= 4 ? mask : mask >> 8) & ((1 << DIA_MAT_COUNT) - 1);
 }
 
+// MXFP4: not measured yet — the classes MXFP8 streams by default, until profiles/ holds an A/B of its own (DESIGN.md "MXFP4 weight stream")
+constexpr int MXFP4_DEFAULT = (1 << DIA_MAT_WI | 1 << DIA_MAT_WO | 1 << DIA_MAT_LOGITS) | (1 << DIA_MAT_WI | 1 << DIA_MAT_LOGITS) << 8;
+static_assert(MXFP4_DEFAULT == 0x5070, "the knob mxfp4 holds one byte of class bits per row range");
+extern "C" int dia_mxfp4_classes(int rows) {
+  if (rows <= 0 || rows > 16) return 0;
+  const int knob = dia_tune(DIA_TUNE_MXFP4);
+  const int mask = knob >= 0 ? knob : MXFP4_DEFAULT;
+  return (rows <= 4 ? mask : mask >> 8) & ((1 << DIA_MAT_COUNT) - 1);
+}
+
 // The step's GEMM launches, one row per dia_step_mat (the row index is also the MXFP8 class bit): where the matrix and its streams live in
 // dia_dec_layer (the logits head: dia_engine_desc, see mat_weights), its epilogue, the planes it reads and emits, what it writes
 enum { PL_NONE = -1, PL_X, PL_A, PL_H };                // activation planes: the normed residual stream, attention output, MLP hidden
@@ -74,11 +86,12 @@ struct step_mat_row {
   int mat;
   const void* dia_dec_layer::*w; int32_t dia_dec_layer::*kt; int32_t dia_dec_layer::*ns;      // dense tiles, kt * ns * 1024 bytes
   const void* dia_dec_layer::*w24; const void* dia_dec_layer::*wf8;                            // 2:4 and MXFP8 streams
+  const void* dia_mxfp4_layer::*wf4;                                                           // MXFP4 stream (dia_engine_set_mxfp4)
   int epi, in, out, emit;
   const int32_t* dia_dec_layer::*cmap;                  // RESID_EMIT: the consumer's compaction map and norm weight (null: the next
   const float* dia_dec_layer::*gnext;                   // layer's g_sa, or the final norm)
 };
-#define MAT(M, m) DIA_MAT_##M, &dia_dec_layer::w_##m, &dia_dec_layer::kt_##m, &dia_dec_layer::ns_##m, &dia_dec_layer::w_##m##_24, &dia_dec_layer::w_##m##_f8
+#define MAT(M, m) DIA_MAT_##M, &dia_dec_layer::w_##m, &dia_dec_layer::kt_##m, &dia_dec_layer::ns_##m, &dia_dec_layer::w_##m##_24, &dia_dec_layer::w_##m##_f8, &dia_mxfp4_layer::w_##m
 constexpr step_mat_row STEP_MATS[DIA_MAT_COUNT] = {
   {MAT(QKV, qkv), DIA_EPI_SCALE_STORE, PL_X, OUT_QKV, PL_NONE, nullptr, nullptr},      // q/k/v projection of the pre-SA-normed row (layers.py:541, 273-275)
   {MAT(O, o), DIA_EPI_RESID_EMIT, PL_A, OUT_X, PL_X, &dia_dec_layer::cmap_ca, &dia_dec_layer::g_ca},       // o_proj + residual; emits the pre-CA-normed planes (layers.py:341-343, 555, 560)
@@ -86,19 +99,19 @@ constexpr step_mat_row STEP_MATS[DIA_MAT_COUNT] = {
   {MAT(CO, co), DIA_EPI_RESID_EMIT, PL_A, OUT_X, PL_X, &dia_dec_layer::cmap_mlp, &dia_dec_layer::g_mlp},   // cross o_proj + residual; emits the pre-MLP-normed planes
   {MAT(WI, wi), DIA_EPI_SWIGLU_EMIT, PL_X, OUT_NONE, PL_H, nullptr, nullptr},          // SwiGLU MLP (layers.py:95-104)
   {MAT(WO, wo), DIA_EPI_RESID_EMIT, PL_H, OUT_X, PL_X, &dia_dec_layer::cmap_next, nullptr},
-  {DIA_MAT_LOGITS, nullptr, nullptr, nullptr, nullptr, nullptr, DIA_EPI_SCALE_STORE, PL_X, OUT_LOGITS, PL_NONE, nullptr, nullptr},   // final norm + logits (layers.py:714-717)
+  {DIA_MAT_LOGITS, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, DIA_EPI_SCALE_STORE, PL_X, OUT_LOGITS, PL_NONE, nullptr, nullptr},   // final norm + logits (layers.py:714-717)
 };
 #undef MAT
 constexpr bool rows_in_order(int m = 0) { return m == DIA_MAT_COUNT || (STEP_MATS[m].mat == m && rows_in_order(m + 1)); }
 static_assert(rows_in_order(), "row m of STEP_MATS describes matrix m of dia_step_mat");
 
-struct mat_w { const void* w; int kt, ns; const void *w24, *wf8; };
+struct mat_w { const void* w; int kt, ns; const void *w24, *wf8, *wf4; };
 static mat_w mat_weights(const dia_engine* e, int l, int m) {
   const dia_engine_desc& d = e->d;
-  if (m == DIA_MAT_LOGITS) return {d.w_logits, d.kt_logits, d.ns_logits, d.w_logits_24, d.w_logits_f8};
+  if (m == DIA_MAT_LOGITS) return {d.w_logits, d.kt_logits, d.ns_logits, d.w_logits_24, d.w_logits_f8, e->f4_logits};
   const dia_dec_layer& L = e->layers[l];
   const step_mat_row& r = STEP_MATS[m];
-  return {L.*r.w, L.*r.kt, L.*r.ns, L.*r.w24, L.*r.wf8};
+  return {L.*r.w, L.*r.kt, L.*r.ns, L.*r.w24, L.*r.wf8, e->f4.empty() ? nullptr : e->f4[l].*r.wf4};
 }
 
 // The launches of one step, in order: launch(layer, what) for every one, `what` a dia_step_mat or one of the launches below.
@@ -193,19 +206,22 @@ static int enqueue_step(dia_engine* e, bool with_sampler) {
     g.sk = sk;
     if (sk == 1) { g.sk_scratch = nullptr; g.sk_tickets = nullptr; }
   };
-  // MXFP8 weight streams (dia_dec_layer.w_*_f8): at <= 16 rows (batch 1-8) the launch classes of dia_mxfp8_classes.  K splits
-  // over whole stream groups of 16 k-tiles with at most 128 per workgroup; the kernel picks its own waves and strips per workgroup
-  const int f8_mask = (F && d.w_planes <= 1 && !seg && !diag) ? dia_mxfp8_classes(R) : 0;
-  auto mxfp8 = [&](dia_gemm_args& g, const void* wf8, int cls) {
-    if (!wf8 || !(f8_mask >> cls & 1) || g.cmap || g.strip_map || g.KT % 16 != 0) return;
+  // MXFP8 / MXFP4 weight streams (dia_dec_layer.w_*_f8 / dia_engine_set_mxfp4): at <= 16 rows (batch 1-8) the launch classes of
+  // dia_mxfp8_classes / dia_mxfp4_classes.  K splits over whole stream groups of 16 k-tiles with at most 128 per workgroup; the kernel
+  // picks its own waves and strips per workgroup
+  const bool mx_ok = F && d.w_planes <= 1 && !seg && !diag;
+  const int f8_mask = mx_ok ? dia_mxfp8_classes(R) : 0, f4_mask = mx_ok ? dia_mxfp4_classes(R) : 0;
+  auto mx = [&](dia_gemm_args& g, const void* ws, int format, int mask, int cls) {      // true: the launch takes this stream
+    if (!ws || !(mask >> cls & 1) || g.cmap || g.strip_map || g.KT % 16 != 0) return false;
     int sk = g.sk > 1 ? g.sk : 1;
     while (sk > 1 && g.KT % (16 * sk) != 0) sk /= 2;
     while (g.KT / sk > 128 && g.KT % (32 * sk) == 0 && d.sk_scratch && d.sk_tickets && sk < 4) sk *= 2;
-    if (g.KT / sk > 128) return;                  // (no split that fits: dense tiles)
-    g.W = wf8; g.w_format = DIA_W_MXFP8; g.nw = 0; g.spw = 0;
+    if (g.KT / sk > 128) return false;            // (no split that fits: dense tiles)
+    g.W = ws; g.w_format = format; g.nw = 0; g.spw = 0;
     g.sk = sk;
     if (sk == 1) { g.sk_scratch = nullptr; g.sk_tickets = nullptr; }
     else { g.sk_scratch = d.sk_scratch; g.sk_tickets = d.sk_tickets; }
+    return true;
   };
   bool wo_pair = false;             // of the wo descriptor built last
   // <= 4 rows: wo's two K slices merged by the launch behind it (the next layer's q/k/v projection, the logits head) while it stages
@@ -243,7 +259,8 @@ static int enqueue_step(dia_engine* e, bool with_sampler) {
       return g;
     }
     sparse24(g, w.w24);
-    mxfp8(g, w.wf8, m);
+    // a matrix with both streams: the smaller one; what refuses it (class off, no K split that fits) leaves the other its turn
+    if (!mx(g, w.wf4, DIA_W_MXFP4, f4_mask, m)) mx(g, w.wf8, DIA_W_MXFP8, f8_mask, m);
     if (defer && (m == DIA_MAT_LOGITS || (m == DIA_MAT_QKV && l > 0))) g.gnext = L ? L->g_sa : d.g_final;     // the consumer norms the row itself
     return g;
   };
@@ -257,7 +274,7 @@ static int enqueue_step(dia_engine* e, bool with_sampler) {
     w.xnew = l < d.n_layer ? xbuf(l) : nullptr;   // (nothing reads x behind the logits head: the sampler's embedding overwrites it)
     return w;
   };
-  // every wo and every launch behind one in the shape the deferred kernels serve: dense one-plane tiles (no 2:4 / MXFP8 stream picked),
+  // every wo and every launch behind one in the shape the deferred kernels serve: dense one-plane tiles (no 2:4 / MXFP8 / MXFP4 stream picked),
   // K 8192 in two slices -> a row of D = 2048, no compaction map on the edge; else the whole model keeps the in-launch merge
   if (R <= 4 && F && d.w_planes <= 1 && !seg && !diag && e->wo_defer != 0 && dia_tune(DIA_TUNE_WO_DEFER) != 0 && dia_tune(DIA_TUNE_MLP_FUSE) <= 0 &&
       e->x_alt && d.sk_scratch && d.D == 2048 && (d.sk_scratch_floats > 0 ? d.sk_scratch_floats : (int64_t)(d.D / 16) * 4 * 512) >= 2 * slice_floats) {
@@ -564,6 +581,16 @@ extern "C" int dia_engine_set_x_alt(dia_engine* e, float* x_alt) {
   if (!e) return dia_fail(DIA_E_ARG, "dia_engine_set_x_alt: null engine");
   if (e->exec || e->wo_defer == 1) return dia_fail(DIA_E_STATE, "dia_engine_set_x_alt: a step has already been issued or captured");
   e->x_alt = x_alt;
+  return DIA_OK;
+}
+
+extern "C" int dia_engine_set_mxfp4(dia_engine* e, const dia_mxfp4_streams* s) {
+  if (!e) return dia_fail(DIA_E_ARG, "dia_engine_set_mxfp4: null engine");
+  if (e->exec || e->launches > 0) return dia_fail(DIA_E_STATE, "dia_engine_set_mxfp4: a step has already been issued or captured");
+  if (s && (s->n_layer != e->d.n_layer || !s->layers)) return dia_fail(DIA_E_ARG, "dia_engine_set_mxfp4: one dia_mxfp4_layer per decoder layer");
+  e->f4.clear();
+  if (s) e->f4.assign(s->layers, s->layers + s->n_layer);
+  e->f4_logits = s ? s->w_logits : nullptr;
   return DIA_OK;
 }
 

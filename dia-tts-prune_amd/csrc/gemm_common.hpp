@@ -396,3 +396,6 @@ int dia_gemm_sparse24(const dia_gemm_args* a, void* stream);
 // gemm_mxfp8.hip: dia_gemm with w_format == DIA_W_MXFP8 (MX e4m3 weight stream, M <= 16)
 int dia_gemm_mxfp8_check(const dia_gemm_args* a);
 int dia_gemm_mxfp8(const dia_gemm_args* a, void* stream);
+// gemm_mxfp4.hip: dia_gemm with w_format == DIA_W_MXFP4 (MX e2m1 weight stream, M <= 16)
+int dia_gemm_mxfp4_check(const dia_gemm_args* a);
+int dia_gemm_mxfp4(const dia_gemm_args* a, void* stream);

@@ -1,0 +1,287 @@
+// MXFP4 decode GEMM: out[M][N] = X[M][K] . W[K][N] for M <= 16 rows with W stored as OCP MX blocks (e2m1 elements, one E8M0
+// power-of-two scale per 32 consecutive K of a column) in the stream of dia_hip/layout.py tile_weight_fp4
+// (dia_gemm_args.w_format = DIA_W_MXFP4).
+//
+// The kernel of gemm_mxfp8.hip (read its header first: mapping, workgroup shape, activations, reduction and epilogue are the
+// same, line for line) with e2m1 elements.  It is a translation unit of its own because a body shared by both kernels changes
+// the register allocation of an fp8 instantiation (DESIGN.md "MXFP4 weight stream"): a fix to either file belongs in both.
+// What differs:
+//   - a lane's 8 values of a k-tile are ONE dword (element j in byte j >> 1, the even element in the low nibble);
+//     v_cvt_scalef32_pk_bf16_fp4 with byte select b turns byte b and the block's scale (E8M0 byte << 23) into two bf16 — exactly,
+//     an e2m1 value times a power of two is a bf16 value — so a k-tile still costs one scale extraction and four converts in
+//     front of the three MFMAs
+//   - a group of 16 k-tiles is the same 256-byte scale block followed by 4 slots of 1 KiB, slot p = [64 lanes][16 bytes] = the
+//     lane's dwords of k-tiles 4p .. 4p + 3: 4352 bytes per group, 0.265625 of the dense tiles'.  One 16-byte load feeds four B
+//     fragments: a wave's 8 k-tiles are two loads per strip, its 16 four.
+#include "gemm_common.hpp"
+
+namespace {
+
+constexpr int F4_GROUP = 16;                       // k-tiles per stream group (layout.FP8_GROUP)
+constexpr int F4_GROUP_BYTES = 256 + 4 * 1024;     // scale block + 4 value slots (layout.FP4_GROUP_BYTES)
+constexpr int F4_MAXW = 8;                         // waves per workgroup
+
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
+
+// the B fragment of one k-tile: 8 e2m1 nibbles (one dword) of one MX block times its scale
+__device__ __forceinline__ bf16x8 expand_fp4(unsigned d, float scale) {
+  const bf16x2 r0 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(d, scale, 0);
+  const bf16x2 r1 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(d, scale, 1);
+  const bf16x2 r2 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(d, scale, 2);
+  const bf16x2 r3 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(d, scale, 3);
+  typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
+  const bf16x4 lo = __builtin_shufflevector(r0, r1, 0, 1, 2, 3), hi = __builtin_shufflevector(r2, r3, 0, 1, 2, 3);
+  return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+}
+
+constexpr size_t f4_smem_fixed() { return sizeof(f32x4) * 2 * F4_MAXW * 64 + sizeof(float) * (16 * 17 + 16); }
+size_t f4_smem(int ktw, int rs) { return f4_smem_fixed() + (rs == 4 ? (size_t)DIA_NPLANES * ktw * 4 * rs * 16 : 0); }
+
+template <int KPW, int RS, bool MULTI>
+__global__ __launch_bounds__(F4_MAXW * 64) void k_gemm_mxfp4(GemmK p) {
+  static_assert(KPW == 8 || KPW == 16, "half a stream group or a whole one per wave");
+  constexpr int NS = KPW / 4;                          // value slots per wave (four k-tiles each)
+  constexpr int NSC = KPW / 4;                         // dwords of scale bytes per wave
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  f32x4* red = reinterpret_cast<f32x4*>(smem_raw);                                   // [2][F4_MAXW][64]
+  float* tile = reinterpret_cast<float*>(smem_raw + sizeof(f32x4) * 2 * F4_MAXW * 64); // [16][17] (split-K hand-off)
+  float* inv_s = tile + 16 * 17;                                                     // [16]
+  bf16x8* As = reinterpret_cast<bf16x8*>(inv_s + 16);                               // RS = 4: [plane][kt][kq][row]
+  __shared__ int sk_flag;
+
+  const int NT = blockDim.x, NW = NT >> 6;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int ktw = NW * KPW;                          // k-tiles of this workgroup's K range
+  const int kt0 = blockIdx.y * ktw + w * KPW;        // first global k-tile of this wave (a multiple of KPW)
+  const int G = gridDim.x;
+  const long strip_bytes = (long)(p.KT / F4_GROUP) * F4_GROUP_BYTES;
+  // this wave's part of a group: its scale bytes (column l & 15, k-tiles kt0 % 16 ..) and its value slots
+  const unsigned char* Wg = reinterpret_cast<const unsigned char*>(p.W) + (long)(kt0 / F4_GROUP) * F4_GROUP_BYTES;
+  const unsigned char* Wsc = Wg + (lane & 15) * 16 + (kt0 % F4_GROUP);
+  const unsigned char* Wv = Wg + 256 + (long)((kt0 % F4_GROUP) / 4) * 1024 + lane * 16;
+  auto load_strip = [&](u32x4* b, unsigned* sc, int strip) {
+    const long so = (long)strip * strip_bytes;
+    if constexpr (KPW == 8) {
+      const u32x2 s = DIA_WLOAD(reinterpret_cast<const u32x2*>(Wsc + so));
+      sc[0] = s[0]; sc[1] = s[1];
+    } else {
+      const u32x4 s = DIA_WLOAD(reinterpret_cast<const u32x4*>(Wsc + so));
+      sc[0] = s[0]; sc[1] = s[1]; sc[2] = s[2]; sc[3] = s[3];
+    }
+#pragma unroll
+    for (int i = 0; i < NS; ++i) b[i] = DIA_WLOAD(reinterpret_cast<const u32x4*>(Wv + so + (long)i * 1024));
+  };
+  const float* Af = reinterpret_cast<const float*>(p.A);
+
+  // ---- small, L2-resident operands first (see k_gemv_small): activation image / fragments, row scales
+  constexpr int CE = (KPW * 4 * RS + 63) / 64;        // RS = 4: image entries per thread (KPW k-tiles x 4 quarters x RS rows per wave)
+  const int nentries = ktw * 4 * RS;
+  float4 ex[RS == 4 ? CE : 1], ey[RS == 4 ? CE : 1];
+  constexpr int AP = (RS == 16 && KPW == 8) ? KPW : 1;   // RS = 16: fragments of the wave's k-tiles held from the start
+  float4 af[AP][2];
+  const int alane = (lane & 48) | min(lane & 15, p.M - 1);   // rows >= M re-read the last valid row (never stored)
+  auto load_frag = [&](float4* f, int t) {               // global k-tile t, this lane's 8 values
+    const float4* s0 = reinterpret_cast<const float4*>(Af + ((long)t * 64 + alane) * 8);
+    f[0] = s0[0]; f[1] = s0[1];
+  };
+  if constexpr (RS == 4) {
+    const long kta = (long)blockIdx.y * ktw;           // first activation k-tile of the range
+#pragma unroll
+    for (int u = 0; u < CE; ++u) {
+      const int c = min(tid + u * NT, nentries - 1);
+      const int row = c % RS, kq = (c / RS) & 3, kt = c / (4 * RS);
+      const float4* src = reinterpret_cast<const float4*>(Af + ((kta + kt) * 64 + min(row, p.M - 1) + 16 * kq) * 8);
+      ex[u] = src[0]; ey[u] = src[1];
+    }
+  } else if constexpr (AP == KPW) {
+#pragma unroll
+    for (int i = 0; i < KPW; ++i) load_frag(af[i], kt0 + i);
+  }
+  // row scales: 8 threads per row, 16 strip partials each requested at once on clamped addresses (as k_gemv_small: a loop of
+  // dependent loads here delayed the weight stream by 4 us in the step); summed after the weight loads are in flight
+  const bool has_norm = p.ssq_in != nullptr;
+  const int s_row = tid >> 3, s_part = tid & 7;
+  const bool s_thread = tid < 128 && has_norm;
+  float sq[16];
+#pragma unroll
+  for (int i = 0; i < 16; ++i) sq[i] = 0.f;
+  if (s_thread) {
+    const float* sp = p.ssq_in + min(s_row, p.M - 1);
+#pragma unroll
+    for (int i = 0; i < 16; ++i) sq[i] = sp[(long)min(s_part + 8 * i, p.ssq_in_n - 1) * p.ssq_ld];
+  }
+  __builtin_amdgcn_sched_barrier(0);
+  u32x4 b0[NS], b1[MULTI ? NS : 1];
+  unsigned c0[NSC], c1[MULTI ? NSC : 1];
+  load_strip(b0, c0, blockIdx.x);                     // the HBM stream starts here
+  __builtin_amdgcn_sched_barrier(0);
+  bf16x8 a3[AP][DIA_NPLANES];                         // RS = 16: the three planes of the held fragments (12 VGPRs per k-tile, as k_gemm16)
+  if constexpr (AP == KPW) {
+#pragma unroll
+    for (int i = 0; i < KPW; ++i) split3x8(af[i][0], af[i][1], a3[i][0], a3[i][1], a3[i][2]);
+  }
+  if constexpr (RS == 4) {
+#pragma unroll
+    for (int u = 0; u < CE; ++u)
+      if (tid + u * NT < nentries) {
+        const int c = tid + u * NT;
+        bf16x8 h, mi, lo;
+        split3x8(ex[u], ey[u], h, mi, lo);
+        As[c] = h; As[nentries + c] = mi; As[2 * nentries + c] = lo;
+      }
+  }
+  for (int t = tid; t < 128; t += NT) {              // (a one-wave workgroup also serves rows 8..15, loading them here)
+    const int r = t >> 3, part = t & 7;
+    float s0 = 0.f;
+    if (t == tid) {
+#pragma unroll
+      for (int i = 0; i < 16; ++i) s0 += (part + 8 * i < p.ssq_in_n && r < p.M) ? sq[i] : 0.f;
+      if (has_norm && r < p.M)
+        for (int i = part + 128; i < p.ssq_in_n; i += 8) s0 += p.ssq_in[(long)i * p.ssq_ld + r];   // D > 2048 only
+    } else if (has_norm && r < p.M) {
+      for (int i = part; i < p.ssq_in_n; i += 8) s0 += p.ssq_in[(long)i * p.ssq_ld + r];
+    }
+    s0 += __shfl_xor(s0, 1, 64);
+    s0 += __shfl_xor(s0, 2, 64);
+    s0 += __shfl_xor(s0, 4, 64);
+    if (part == 0) inv_s[r] = has_norm ? rsqrtf(s0 * p.inv_d + p.eps) : 1.0f;
+  }
+  lds_barrier();                                      // image + row scales visible; the weight loads stay in flight
+
+  const int arow = min(lane & 15, RS - 1), akq = lane >> 4;
+  int sbuf = 0;
+  auto body = [&](u32x4* bc, unsigned* cc, u32x4* bn, unsigned* cn, int strip) {
+    const int next = strip + G;
+    if constexpr (MULTI) load_strip(bn, cn, DIA_PREFETCH_CLAMP(next, p.nstrips));   // unconditional: see k_gemv_small
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int i = 0; i < KPW; ++i) {
+      bf16x8 h, mi, lo;
+      if constexpr (RS == 4) {
+        const int kt = w * KPW + i;                     // k-tile inside the image
+        h = As[(kt * 4 + akq) * RS + arow];
+        mi = As[nentries + (kt * 4 + akq) * RS + arow];
+        lo = As[2 * nentries + (kt * 4 + akq) * RS + arow];
+      } else if constexpr (AP == KPW) {
+        h = a3[i < AP ? i : 0][0]; mi = a3[i < AP ? i : 0][1]; lo = a3[i < AP ? i : 0][2];
+      } else {
+        float4 f[2];
+        load_frag(f, kt0 + i);
+        split3x8(f[0], f[1], h, mi, lo);
+      }
+      const float scale = __builtin_bit_cast(float, ((cc[i >> 2] >> (8 * (i & 3))) & 0xffu) << 23);
+      const bf16x8 b = expand_fp4(bc[i >> 2][i & 3], scale);
+      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(h, b, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(mi, b, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(lo, b, acc, 0, 0, 0);
+    }
+    // cross-wave sum: element (row m, column c) of the output tile sits in lane 16 (m >> 2) + c, register m & 3 of every wave
+    f32x4* rb = red + sbuf * (F4_MAXW * 64);
+    sbuf ^= 1;
+    if (RS == 16 || lane < 16) rb[w * 64 + lane] = acc;
+    lds_barrier();
+    const bool split = !MULTI && gridDim.y > 1;
+    constexpr int NE = (16 * RS + 63) / 64;          // epilogue elements per thread (at least one wave per workgroup)
+    float vs[NE];
+#pragma unroll
+    for (int u = 0; u < NE; ++u) {
+      const int e = tid + u * NT;
+      vs[u] = 0.f;
+      if (e < 16 * RS) {
+        const int m = e >> 4, c = e & 15;
+        const float* rf = reinterpret_cast<const float*>(rb) + ((m >> 2) * 16 + c) * 4 + (m & 3);
+        float v = rf[0];
+        for (int ww = 1; ww < NW; ++ww) v += rf[ww * 256];
+        vs[u] = v;
+        if (split) tile[m * 17 + c] = v;
+      }
+    }
+    if (split) {            // cross-workgroup split-K (wo): the last arriver sums the slabs in split order and runs the epilogue
+      // (splitk_combine publishes all 16 rows of the tile: rows RS.. carry zeros, never read back)
+      if constexpr (RS < 16)
+        for (int e = 16 * RS + tid; e < 256; e += NT) tile[(e >> 4) * 17 + (e & 15)] = 0.f;
+      lds_barrier();
+      if (!splitk_combine(p, tile, strip, tid, &sk_flag)) return;
+#pragma unroll
+      for (int u = 0; u < NE; ++u)
+        if (tid + u * NT < 16 * RS) vs[u] = tile[((tid + u * NT) >> 4) * 17 + ((tid + u * NT) & 15)];
+    }
+#pragma unroll
+    for (int u = 0; u < NE; ++u) {
+      const int e = tid + u * NT;
+      if (e >= 16 * RS) break;
+      float xpre1 = 0.f, gpre1 = 1.f;
+      if (p.epi == DIA_EPI_RESID_EMIT) {
+        const int m = e >> 4, n = strip * 16 + (e & 15);
+        xpre1 = p.out[(long)min(m, p.M - 1) * p.ldo + n];
+        gpre1 = p.gnext[n];
+      }
+      run_epilogue_rows<RS, true>(p, vs[u], inv_s, e, strip, xpre1, gpre1);
+    }
+  };
+  if constexpr (MULTI) {
+    int strip = blockIdx.x;                            // strip pairs, then at most one more (see k_gemv_small)
+    for (; strip + G < p.nstrips; strip += 2 * G) {
+      body(b0, c0, b1, c1, strip);
+      body(b1, c1, b0, c0, strip + G);
+    }
+    if (strip < p.nstrips) body(b0, c0, b1, c1, strip);
+  } else {
+    body(b0, c0, b1, c1, blockIdx.x);
+  }
+}
+
+template <int KPW, int RS>
+int launch_f4(const GemmK& k, int nw, int sk, int spw, hipStream_t st) {
+  const size_t smem = f4_smem(nw * KPW, RS);
+  if (spw > 1 && sk == 1) {
+    if constexpr (KPW == 8) {     // (16 k-tiles per wave: wo's split-K ranges only, one strip per workgroup)
+      launch_kernel<k_gemm_mxfp4<KPW, RS, true>>(dim3((k.nstrips + spw - 1) / spw), dim3(nw * 64), smem, st, k);
+      return dia_check_launch("k_gemm_mxfp4");
+    }
+  }
+  launch_kernel<k_gemm_mxfp4<KPW, RS, false>>(dim3(k.nstrips, sk), dim3(nw * 64), smem, st, k);
+  return dia_check_launch("k_gemm_mxfp4");
+}
+
+}  // namespace
+
+// dia_gemm with w_format == DIA_W_MXFP4: what the fp4 stream cannot serve (checked before dia_gemm's other weight forms)
+int dia_gemm_mxfp4_check(const dia_gemm_args* a) {
+  if (a->w_planes > 1) return dia_fail(DIA_E_ARG, "dia_gemm: the MXFP4 stream holds one weight encoding (w_planes must be 0 or 1)");
+  if (a->w_layout == 1) return dia_fail(DIA_E_ARG, "dia_gemm: the MXFP4 stream has no diagonal layout (w_layout must be 0)");
+  if (a->sp_blocks || a->sp_toff) return dia_fail(DIA_E_ARG, "dia_gemm: the MXFP4 stream and the zero-skipping stream (sp_blocks) exclude each other");
+  if (a->epi == DIA_EPI_CROSSKV) return dia_fail(DIA_E_ARG, "dia_gemm: the MXFP4 stream has no CROSSKV epilogue (prefill only)");
+  if (a->cmap || a->strip_map) return dia_fail(DIA_E_ARG, "dia_gemm: the MXFP4 stream has no compaction maps (cmap / strip_map)");
+  if (a->M > 16) return dia_fail(DIA_E_ARG, "dia_gemm: the MXFP4 stream serves at most 16 rows");
+  const bool emits = a->epi == DIA_EPI_RESID_EMIT || a->epi == DIA_EPI_SWIGLU_EMIT;
+  if (!(a->act_f32 & 1) || (emits && !(a->act_f32 & 2)))
+    return dia_fail(DIA_E_ARG, "dia_gemm: the MXFP4 stream needs fp32 activation tiles in and out (act_f32 = 3), not planes");
+  if (!a->W) return dia_fail(DIA_E_ARG, "dia_gemm: the MXFP4 stream needs W");
+  if (a->epi == DIA_EPI_RESID_EMIT && !a->gnext) return dia_fail(DIA_E_ARG, "dia_gemm: the MXFP4 stream needs gnext with RESID_EMIT");
+  const int sk = a->sk > 1 ? a->sk : 1;
+  if (a->KT % F4_GROUP != 0 || a->KT % sk != 0 || (a->KT / sk) % F4_GROUP != 0)
+    return dia_fail(DIA_E_ARG, "dia_gemm: the MXFP4 stream needs K a multiple of 512 per workgroup (whole groups of 16 k-tiles)");
+  if (a->KT / sk > 16 * F4_MAXW)
+    return dia_fail(DIA_E_ARG, "dia_gemm: the MXFP4 stream serves at most 128 k-tiles per workgroup (K <= 4096; use split-K)");
+  return DIA_OK;
+}
+
+// the launch (dia_gemm has run dia_gemm_mxfp4_check and its own argument checks)
+int dia_gemm_mxfp4(const dia_gemm_args* a, void* stream) {
+  const int sk = a->sk > 1 ? a->sk : 1;
+  if (sk > 1 && (!a->sk_scratch || !a->sk_tickets)) return dia_fail(DIA_E_ARG, "dia_gemm: split-K needs sk_scratch, sk_tickets and KT % sk == 0");
+  const int ktw = a->KT / sk;                          // k-tiles per workgroup
+  GemmK k;
+  fill_gemmk(a, k);
+  hipStream_t st = (hipStream_t)stream;
+  const int kpw = ktw / 8 <= F4_MAXW ? 8 : 16;
+  const int nw = ktw / kpw;
+  // strips per workgroup (persistent form, next strip's weights in flight during this one's epilogue): the caller's spw, else
+  // 4 from 1024 strips on and about 256 workgroups above 512 strips, as the dense M <= 4 GEMV
+  const int spw = a->spw > 0 ? a->spw : (a->nstrips >= 1024 ? 4 : (a->nstrips > 512 ? (a->nstrips + 255) / 256 : 1));
+  const bool image = a->M <= 4;                        // (128 k-tiles x 4 rows x 3 planes = 96 KiB at most)
+  if (kpw == 8) return image ? launch_f4<8, 4>(k, nw, sk, spw, st) : launch_f4<8, 16>(k, nw, sk, spw, st);
+  return image ? launch_f4<16, 4>(k, nw, sk, 1, st) : launch_f4<16, 16>(k, nw, sk, 1, st);
+}

@@ -39,9 +39,9 @@ def broadcast_tensors(tensors: Iterable[torch.Tensor], src: int = 0, group=None)
 def _arena_signature(w) -> List[int]:
     """what must agree on every rank before the flat arena may travel: its size in bytes and the layout switches that
     decide the tensor order inside it"""
-    # extra weight streams behind the dense model: 0 none, 1 the 2:4 streams, 2 the MXFP8 streams (they exclude each other).  `quant`
-    # is the younger switch: an object without it carries no MXFP8 streams, and their bytes show in the first entry as well
-    streams = 1 if w.sparse == "2:4" else (2 if getattr(w, "quant", "off") == "mxfp8" else 0)
+    # extra weight streams behind the dense model: 0 none, 1 the 2:4 streams, 2 the MXFP8 streams, 3 the MXFP4 streams (they exclude
+    # each other).  `quant` is the younger switch: an object without it carries no MX streams, and their bytes show in the first entry as well
+    streams = 1 if w.sparse == "2:4" else {"mxfp8": 2, "mxfp4": 3}.get(getattr(w, "quant", "off"), 0)
     return [int(w.flat.numel()) if w.flat is not None else -1, int(bool(w.compacted)), int(w.weight_planes), streams]
 
 
@@ -66,7 +66,7 @@ def broadcast_weights(w, src: int = 0, group=None) -> int:
         raise ValueError("compacted (structured-pruned) weights have checkpoint-dependent shapes: "
                          "load the checkpoint on every rank instead of broadcasting")
     if lo != hi:
-        raise ValueError(f"weight arenas differ across ranks (bytes, compacted, weight planes, 2:4 / MXFP8 streams): min {lo}, max {hi}; "
+        raise ValueError(f"weight arenas differ across ranks (bytes, compacted, weight planes, 2:4 / MXFP8 / MXFP4 streams): min {lo}, max {hi}; "
                          "build the receivers with DeviceWeights.empty_like_config(cfg, device, weight_planes=..., sparse=..., quant=...)")
     dist.broadcast(w.flat, src=src, group=group)
     return int(w.flat.numel())

@@ -27,7 +27,7 @@ from . import compact as cpt
 from . import layout as lay
 from .config import DiaConfig
 from .pruning import is_2of4
-from .quant import is_mxfp8
+from .quant import is_mxfp4, is_mxfp8
 from .tokens import CODEBOOK_SIZE
 
 HEAD_DIM = 128
@@ -148,7 +148,9 @@ class DeviceWeights:
         which decode steps of at most 16 rows (batch 1-8) stream instead of the dense tiles.  The dense tiles stay resident for the
         encoder, the cross K/V projections, both prefills and larger batches and hold the same numbers, so results do not depend on
         which form a step used beyond summation order.  Every K must be a multiple of 512; not with sparse="2:4",
-        weight_planes != 1, a compacted checkpoint or seg="on"."""
+        weight_planes != 1, a compacted checkpoint or seg="on".
+        "mxfp4" = the same for an MXFP4-representable checkpoint (offline_quantize.py --format mxfp4; quant.is_mxfp4) and MXFP4
+        streams (layout.tile_weight_fp4: e2m1 elements, 0.266 of the dense bytes), under the same conditions."""
         if weight_planes not in _TILERS:
             raise ValueError("weight_planes must be 1, 2 or 3")
         if sparse not in ("off", "2:4"):
@@ -157,14 +159,15 @@ class DeviceWeights:
             raise hb.DiaHipError("sparse='2:4': the 2:4 stream holds one bf16 weight plane (weight_planes must be 1)")
         if sparse == "2:4" and seg == "on":
             raise hb.DiaHipError("sparse='2:4': the persistent MLP segments stream dense ring arenas (seg must be 'off')")
-        if quant not in ("off", "mxfp8"):
-            raise ValueError('quant must be "off" or "mxfp8"')
-        if quant == "mxfp8" and sparse == "2:4":
-            raise hb.DiaHipError("quant='mxfp8': the MXFP8 stream and the 2:4 sparse stream exclude each other (sparse must be 'off')")
-        if quant == "mxfp8" and weight_planes != 1:
-            raise hb.DiaHipError("quant='mxfp8': an MXFP8 value is one bf16 value (weight_planes must be 1)")
-        if quant == "mxfp8" and seg == "on":
-            raise hb.DiaHipError("quant='mxfp8': the persistent MLP segments stream dense ring arenas (seg must be 'off')")
+        if quant not in ("off", "mxfp8", "mxfp4"):
+            raise ValueError('quant must be "off", "mxfp8" or "mxfp4"')
+        mx = quant.upper()
+        if quant != "off" and sparse == "2:4":
+            raise hb.DiaHipError(f"quant='{quant}': the {mx} stream and the 2:4 sparse stream exclude each other (sparse must be 'off')")
+        if quant != "off" and weight_planes != 1:
+            raise hb.DiaHipError(f"quant='{quant}': an {mx} value is one bf16 value (weight_planes must be 1)")
+        if quant != "off" and seg == "on":
+            raise hb.DiaHipError(f"quant='{quant}': the persistent MLP segments stream dense ring arenas (seg must be 'off')")
         self.sparse = sparse
         self.quant = quant
         self.weight_planes = weight_planes
@@ -184,7 +187,8 @@ class DeviceWeights:
         self.logits = self._tile(lw[keep_logits.to(device)] if keep_logits is not None else lw)
         self.logits_cols = lw.shape[1]
         self.logits24 = self._tile24("decoder.logits_dense", lw) if sparse == "2:4" else None
-        self.logits_f8 = self._tile_f8("decoder.logits_dense", lw) if quant == "mxfp8" else None
+        self.logits_f8 = self._tile_mx("decoder.logits_dense", lw, quant) if quant == "mxfp8" else None
+        self.logits_f4 = self._tile_mx("decoder.logits_dense", lw, quant) if quant == "mxfp4" else None
         npos = max(cfg.data.audio_length, cfg.data.text_length) + 1
         cos, sin = lay.rope_tables(npos, HEAD_DIM, m.rope_min_timescale, m.rope_max_timescale)
         self.cos_t, self.sin_t = cos.to(device), sin.to(device)
@@ -222,12 +226,15 @@ class DeviceWeights:
         return TiledW(*lay.tile_weight_24(w2d))
 
     @staticmethod
-    def _tile_f8(name, w2d) -> TiledW:
+    def _tile_mx(name, w2d, quant) -> TiledW:
+        """the MXFP8 / MXFP4 stream of a matrix that holds nothing but such values"""
+        pred, tiler = (is_mxfp8, lay.tile_weight_fp8) if quant == "mxfp8" else (is_mxfp4, lay.tile_weight_fp4)
         if w2d.shape[0] % 512:
-            raise hb.DiaHipError(f"quant='mxfp8': {name}: K = {w2d.shape[0]} is not a multiple of 512")
-        if not is_mxfp8(w2d):
-            raise hb.DiaHipError(f"quant='mxfp8': {name} is not MXFP8-representable (quantise the checkpoint with offline_quantize.py)")
-        return TiledW(*lay.tile_weight_fp8(w2d))
+            raise hb.DiaHipError(f"quant='{quant}': {name}: K = {w2d.shape[0]} is not a multiple of 512")
+        if not pred(w2d):
+            raise hb.DiaHipError(f"quant='{quant}': {name} is not {quant.upper()}-representable (quantise the checkpoint with "
+                                 f"offline_quantize.py --format {quant})")
+        return TiledW(*tiler(w2d))
 
     def _build_encoder(self, sd, compact: str):
         e, device = self.cfg.model.encoder, self.device
@@ -284,8 +291,9 @@ class DeviceWeights:
         if self.sparse == "2:4" and self.compacted:
             raise hb.DiaHipError("sparse='2:4': a compacted (structured-pruned) checkpoint has no 2:4 form; load it with compact='off' "
                                  "or prune with --prune-mode 2:4")
-        if self.quant == "mxfp8" and self.compacted:
-            raise hb.DiaHipError("quant='mxfp8': a compacted (structured-pruned) checkpoint has no MXFP8 stream; load it with compact='off'")
+        if self.quant != "off" and self.compacted:
+            raise hb.DiaHipError(f"quant='{self.quant}': a compacted (structured-pruned) checkpoint has no {self.quant.upper()} stream; "
+                                 "load it with compact='off'")
         i32 = self._i32
         self.dec_layers = []
         for i, P in enumerate(plans):
@@ -329,7 +337,8 @@ class DeviceWeights:
             for k in DEC_MATS:
                 L[k] = self._tile(mats[k])
                 L[k + "24"] = self._tile24(p + k, mats[k]) if self.sparse == "2:4" else None
-                L[k + "f8"] = self._tile_f8(p + k, mats[k]) if self.quant == "mxfp8" else None
+                L[k + "f8"] = self._tile_mx(p + k, mats[k], self.quant) if self.quant == "mxfp8" else None
+                L[k + "f4"] = self._tile_mx(p + k, mats[k], self.quant) if self.quant == "mxfp4" else None
             # experiment (knob wo_diag=1): wo once more in the diagonal layout (4-column groups: 256 workgroups with the whole K each)
             L["wo_diag"] = None
             if (hb.get_tuning("wo_diag") == 1 and P is None and self.weight_planes == 1 and device.type == "cuda" and wo.shape[0] % 1024 == 0
@@ -401,6 +410,10 @@ class DeviceWeights:
             for L in self.dec_layers:
                 out += [L[k + "f8"].t for k in DEC_MATS]
             out.append(self.logits_f8.t)
+        if self.quant == "mxfp4":                   # the MXFP4 streams (quant="mxfp4"), in the same place
+            for L in self.dec_layers:
+                out += [L[k + "f4"].t for k in DEC_MATS]
+            out.append(self.logits_f4.t)
         return out
 
     def pack_flat(self):
@@ -440,15 +453,17 @@ class DeviceWeights:
         """bf16 bytes one decode step of `rows` rows (2 per utterance) streams (SURVEY.md §8d 'W'): every decoder matrix except
         the prefill-only cross K/V projections, plus the logits head — the 2:4 streams where the step uses them (sparse="2:4",
         at most 4 rows) and the MXFP8 streams for the matrices of STEP_MATS the library enables at this row count (quant="mxfp8",
-        at most 16 rows: binding.mxfp8_mask)."""
+        at most 16 rows: binding.mxfp8_mask; quant="mxfp4": the MXFP4 streams, binding.mxfp4_mask)."""
         every = self.sparse == "2:4" and rows <= 4
-        f8 = hb.mxfp8_mask(rows) if self.quant == "mxfp8" else 0
+        mx = {"mxfp8": hb.mxfp8_mask, "mxfp4": hb.mxfp4_mask}[self.quant](rows) if self.quant != "off" else 0
+        sfx = "f4" if self.quant == "mxfp4" else "f8"
+        logits_mx = self.logits_f4 if self.quant == "mxfp4" else self.logits_f8
 
         def w(L, k):
-            if f8 >> STEP_MATS.index(k) & 1:
-                return L[k + "f8"].nbytes
+            if mx >> STEP_MATS.index(k) & 1:
+                return L[k + sfx].nbytes
             return L[k + "24"].nbytes if every else L[k].nbytes
-        n = self.logits_f8.nbytes if f8 >> STEP_MATS.index("logits") & 1 else (self.logits24.nbytes if every else self.logits.nbytes)
+        n = logits_mx.nbytes if mx >> STEP_MATS.index("logits") & 1 else (self.logits24.nbytes if every else self.logits.nbytes)
         for L in self.dec_layers:
             n += sum(w(L, k) for k in DEC_MATS)
         return n
@@ -739,6 +754,13 @@ class DecodeSession:
                  "dia_engine_create")
         if self.x_alt is not None:
             hb.check(hb.lib().dia_engine_set_x_alt(self._engine, hb.ptr(self.x_alt)), "dia_engine_set_x_alt")
+        if w.quant == "mxfp4":                                              # MXFP4 streams (quant="mxfp4"): beside the description
+            f4_layers = (hb.Mxfp4Layer * n)()                               # (the engine copies the array)
+            for i, L in enumerate(w.dec_layers):
+                for f in DEC_MATS:
+                    setattr(f4_layers[i], "w_" + f, hb.ptr(L[f + "f4"].t))
+            f4 = hb.Mxfp4Streams(n_layer=n, layers=C.cast(f4_layers, C.POINTER(hb.Mxfp4Layer)), w_logits=hb.ptr(w.logits_f4.t))
+            hb.check(hb.lib().dia_engine_set_mxfp4(self._engine, C.byref(f4)), "dia_engine_set_mxfp4")
 
     def close(self):
         """Tear the engine down: the stream is drained first (queued graph replays read the executable graph's own

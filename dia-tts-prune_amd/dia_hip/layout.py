@@ -339,6 +339,50 @@ def untile_weight_fp8(stream: torch.Tensor, K: int, N: int) -> torch.Tensor:
     return mxfp8_dequantize_2d(vals.contiguous(), scales.contiguous())[:K, :N].contiguous()
 
 
+# ---- MXFP4 weight stream (dia_gemm_args.w_format = DIA_W_MXFP4, csrc/gemm_mxfp4.hip) ------------------------------------
+FP4_GROUP_BYTES = 256 + 4 * 1024         # scale block + 4 value slots (FP8_GROUP k-tiles)
+
+
+def tile_weight_fp4(w2d: torch.Tensor) -> Tuple[torch.Tensor, int, int]:
+    """[K, N] float -> (stream uint8 [N/16, G, 4352], K/32, N/16): the MXFP4 encoding of the matrix (quant.mxfp4_quantize_2d: e2m1
+    elements, one E8M0 scale per 32 consecutive K of a column) in the order csrc/gemm_mxfp4.hip reads.  K is zero-padded to a
+    multiple of 32, N to 16, the k-tiles to whole groups of 16 (G = ceil(K/32 / 16)).
+
+    Stream of a strip: one block per group of 16 k-tiles, each a sequential 4352 bytes = the 256-byte scale block of
+    tile_weight_fp8 (``[16 columns][16 k-tiles]``), then 4 slots of 1 KiB: slot p = ``[64 lanes][16 bytes]``, lane l holding its
+    8 elements of k-tile 4p + i in bytes 4i .. 4i + 3 (one dword per k-tile), element j of k-tile t =
+    W[32 t + 8 (l >> 4) + j][16 strip + (l & 15)] as in the dense tiles.  Element j sits in byte j >> 1 of the dword, the even
+    element in the LOW nibble: v_cvt_scalef32_pk_bf16_fp4 with byte select b returns (low nibble, high nibble) of byte b as the
+    (first, second) bf16 of its result, so selects 0..3 give elements 0..7 in order (pinned on the hardware by
+    tests/test_gpu_mxfp4.py::test_operand_probe).  0.265625 of the dense tiles' bytes."""
+    from .quant import mxfp4_quantize_2d
+    K, N = w2d.shape
+    Np = _ceil(N, 16)
+    kt, ns = _ceil(K, 32) // 32, Np // 16
+    G = (kt + FP8_GROUP - 1) // FP8_GROUP
+    el, sc = mxfp4_quantize_2d(w2d)
+    elp = torch.zeros(G * FP8_GROUP * 32, Np, dtype=torch.uint8, device=w2d.device)
+    scp = torch.full((G * FP8_GROUP, Np), 127, dtype=torch.uint8, device=w2d.device)
+    elp[: el.shape[0], :N] = el
+    scp[: sc.shape[0], :N] = sc
+    # (G, p, i, kq, byte, nibble, strip, c) -> (strip, G, p, lane = 16 kq + c, 4 i + byte)
+    nib = elp.reshape(G, 4, 4, 4, 4, 2, ns, 16)
+    vals = (nib[:, :, :, :, :, 0] | (nib[:, :, :, :, :, 1] << 4)).permute(5, 0, 1, 3, 6, 2, 4).reshape(ns, G, 4 * 1024)
+    scales = scp.reshape(G, FP8_GROUP, ns, 16).permute(2, 0, 3, 1).reshape(ns, G, 256)
+    return torch.cat([scales, vals], dim=2).contiguous(), kt, ns
+
+
+def untile_weight_fp4(stream: torch.Tensor, K: int, N: int) -> torch.Tensor:
+    """inverse of tile_weight_fp4 (test helper): the DEQUANTISED matrix, fp32 [K, N]"""
+    from .quant import mxfp4_dequantize_2d
+    ns, G = stream.shape[0], stream.shape[1]
+    scales = stream[:, :, :256].reshape(ns, G, 16, FP8_GROUP).permute(1, 3, 0, 2).reshape(G * FP8_GROUP, ns * 16)
+    by = stream[:, :, 256:].reshape(ns, G, 4, 4, 16, 4, 4)                    # (strip, G, p, kq, c, i, byte)
+    nib = torch.stack([by & 15, by >> 4], dim=-1)                            # ... nibble
+    codes = nib.permute(1, 2, 5, 3, 6, 7, 0, 4).reshape(G * FP8_GROUP * 32, ns * 16)
+    return mxfp4_dequantize_2d(codes.contiguous(), scales.contiguous())[:K, :N].contiguous()
+
+
 # ---- ring layout of the persistent MLP segment (csrc/seg.hip) ------------------------------------------------------
 SEG_CUS = 256            # one workgroup per CU of an MI355X
 SEG_K = 2048             # contraction length of one slot (16 tiles of 128 k x 4 columns)

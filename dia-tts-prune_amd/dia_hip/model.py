@@ -73,7 +73,8 @@ class Dia:
     # sparse streams, which decode steps of batch 1-2 stream instead of the dense tiles (DeviceWeights sparse="2:4"); "off" = dense
     sparse_weights = "off"
     # "mxfp8": an MXFP8-quantised checkpoint (offline_quantize.py) also carries its decoder matrices and logits head as MXFP8
-    # streams, which decode steps of batch 1-8 stream instead of the dense tiles (DeviceWeights quant="mxfp8"); "bf16" = dense
+    # streams, which decode steps of batch 1-8 stream instead of the dense tiles (DeviceWeights quant="mxfp8"); "mxfp4": the same
+    # for an MXFP4-quantised checkpoint (offline_quantize.py --format mxfp4, DeviceWeights quant="mxfp4"); "bf16" = dense
     weight_format = "bf16"
 
     def __init__(self, config: DiaConfig, compute_dtype: Union[str, ComputeDtype] = ComputeDtype.FLOAT32,
@@ -112,7 +113,7 @@ class Dia:
             raise RuntimeError(f"Missing keys in checkpoint: {missing}")
         with torch.cuda.device(self.device):
             self.model = DeviceWeights(self.config, sd, self.device, sparse=self.sparse_weights,
-                                       quant="mxfp8" if self.weight_format == "mxfp8" else "off")
+                                       quant=self.weight_format if self.weight_format in ("mxfp8", "mxfp4") else "off")
             # DenseGeneral kernels are streamed as ONE bf16 tile set by the fast kernels.  A checkpoint whose values are
             # bf16-representable (bf16-trained weights stored as fp32, the synthetic ones) loses nothing.  A genuine fp32
             # checkpoint would be rounded once at load = the reference's bfloat16 configuration, NOT its float32 path:

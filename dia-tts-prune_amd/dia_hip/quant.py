@@ -1,4 +1,4 @@
-"""MXFP8 weight-only quantisation (OCP MX, element type e4m3fn, block = 32 consecutive K of one column).
+"""MXFP8 and MXFP4 weight-only quantisation (OCP MX, element type e4m3fn or e2m1, block = 32 consecutive K of one column).
 
 A block of a ``[K, N]`` kernel (K the contraction axis, as DeviceWeights flattens it: ``pruning._kernel_2d``) shares one
 power-of-two scale ``X = 2^e`` with ``e = floor(log2(max|w|)) - 8`` (an all-zero block: ``e = 0``), clamped to [-100, 100] and
@@ -9,6 +9,12 @@ An e4m3 value times a power of two is exactly a bf16 value, so a dequantised che
 dense bf16 tiles, the oracle and the reference run exactly; the fp8 stream (layout.tile_weight_fp8, csrc/gemm_mxfp8.hip) is a
 second encoding of the same numbers.  "Is MXFP8-representable" is ``dequantise(quantise(w)) == w`` (``is_mxfp8``), which
 holds for everything the quantiser emits (quantise(dequantise(q)) reproduces elements and scales bit for bit).
+
+MXFP4 (``mxfp4_*``) is the same scheme with e2m1 elements: magnitudes {0, 0.5, 1, 1.5, 2, 3, 4, 6} (codes 0..7) and a sign bit
+(code bit 3), ``e = floor(log2(max|w|)) - 2``, ``w / X`` clamped to +-6 and rounded to the nearest magnitude, a tie to the code with
+an even mantissa bit (the even code).  The rounding is a comparison against the seven midpoints, no cast to an fp4 dtype.  An e2m1
+value times a power of two is a bf16 value as well, so everything above holds for ``is_mxfp4`` and the fp4 stream
+(layout.tile_weight_fp4) too.
 """
 
 from __future__ import annotations
@@ -66,6 +72,46 @@ def is_mxfp8(w2d: torch.Tensor) -> bool:
     return bool(torch.equal(mxfp8_round_2d(w2d), w2d.float()))
 
 
+E2M1_MAX = 6.0
+E2M1_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)                 # magnitude of code c (bits e e m), bit 3 = sign
+E2M1_MIDPOINTS = (0.25, 0.75, 1.25, 1.75, 2.5, 3.5, 5.0)              # midpoint i lies between codes i and i + 1
+
+
+def mxfp4_quantize_2d(w2d: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """[K, N] float -> (codes uint8 [Kp, N] (e2m1 in the low 4 bits, one per element), scales uint8 [Kp/32, N] (E8M0)), Kp = K
+    zero-padded to 32"""
+    b = _blocks(w2d)
+    amax = b.abs().amax(dim=1)
+    e = torch.frexp(amax)[1].to(torch.int32) - 1 - 2
+    e = torch.where(amax > 0, e, torch.zeros_like(e)).clamp_(E_MIN, E_MAX)
+    scaled = torch.ldexp(b, -e[:, None, :]).clamp_(-E2M1_MAX, E2M1_MAX)
+    mag = scaled.abs()
+    code = torch.zeros_like(mag, dtype=torch.uint8)
+    for i, m in enumerate(E2M1_MIDPOINTS):                               # a tie stays on an even code i, leaves an odd one
+        code += (mag > m if i % 2 == 0 else mag >= m).to(torch.uint8)
+    code |= ((scaled < 0) & (code > 0)).to(torch.uint8) << 3             # (no negative zero: one code per value)
+    return code.reshape(-1, b.shape[2]).contiguous(), (e + E8M0_BIAS).to(torch.uint8).contiguous()
+
+
+def mxfp4_dequantize_2d(codes: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
+    """inverse of mxfp4_quantize_2d on the padded shape: fp32 [Kp, N] = e2m1 value x 2^(scale - 127)"""
+    Kp, N = codes.shape
+    lut = torch.tensor(E2M1_VALUES + tuple(-v for v in E2M1_VALUES), dtype=torch.float32, device=codes.device)
+    v = lut[(codes & 15).long()].reshape(Kp // MX_BLOCK, MX_BLOCK, N)
+    e = scales.to(torch.int32) - E8M0_BIAS
+    return torch.ldexp(v, e[:, None, :]).reshape(Kp, N)
+
+
+def mxfp4_round_2d(w2d: torch.Tensor) -> torch.Tensor:
+    """[K, N] -> fp32 [K, N]: the nearest MXFP4-representable matrix (dequantise(quantise(w)))"""
+    return mxfp4_dequantize_2d(*mxfp4_quantize_2d(w2d))[: w2d.shape[0]]
+
+
+def is_mxfp4(w2d: torch.Tensor) -> bool:
+    """True when every value of [K, N] is its block's e2m1 element times the block's power-of-two scale"""
+    return bool(torch.equal(mxfp4_round_2d(w2d), w2d.float()))
+
+
 def mxfp8_names(cfg: DiaConfig) -> List[str]:
     """the DenseGeneral kernels a decode step streams: q/k/v, o, cross-q, cross-o, wi, wo of every decoder layer and the
     logits head (the encoder and the cross K/V projections run in the prefill only and stay as they are)"""
@@ -78,6 +124,9 @@ def mxfp8_names(cfg: DiaConfig) -> List[str]:
     return names + ["decoder.logits_dense.weight"]
 
 
+mx_names = mxfp8_names        # the same matrices whatever the MX element type
+
+
 def mxfp8_quantize_state_dict(cfg: DiaConfig, sd: Dict[str, torch.Tensor]) -> "OrderedDict[str, torch.Tensor]":
     """An ordinary fp32 state dict holding the dequantised MXFP8 values of every kernel of ``mxfp8_names(cfg)``, each blocked
     along the K axis of its [K, N] form; everything else untouched.  Idempotent."""
@@ -85,4 +134,13 @@ def mxfp8_quantize_state_dict(cfg: DiaConfig, sd: Dict[str, torch.Tensor]) -> "O
     for name in mxfp8_names(cfg):
         w = sd[name]
         out[name] = mxfp8_round_2d(_kernel_2d(name, w.float())).reshape(w.shape)
+    return out
+
+
+def mxfp4_quantize_state_dict(cfg: DiaConfig, sd: Dict[str, torch.Tensor]) -> "OrderedDict[str, torch.Tensor]":
+    """As mxfp8_quantize_state_dict with e2m1 elements: the dequantised MXFP4 values of every kernel of ``mx_names(cfg)``."""
+    out: "OrderedDict[str, torch.Tensor]" = OrderedDict((k, v.clone()) for k, v in sd.items())
+    for name in mx_names(cfg):
+        w = sd[name]
+        out[name] = mxfp4_round_2d(_kernel_2d(name, w.float())).reshape(w.shape)
     return out

@@ -44,6 +44,8 @@ extern "C" {
 #define DIA_W_DENSE 0      /* bf16 tiles [nstrips][KT][64][8], KT = K/32 */
 #define DIA_W_SPARSE24 1   /* 2:4 sparse stream (dia_hip/layout.py tile_weight_24), KT = K/64 */
 #define DIA_W_MXFP8 2      /* OCP MX e4m3 stream (dia_hip/layout.py tile_weight_fp8), KT = K/32 */
+#define DIA_W_MXFP4 4      /* OCP MX e2m1 stream (dia_hip/layout.py tile_weight_fp4), KT = K/32.  (3 is not assigned: dia_gemm keeps
+                            * refusing it as an unknown format, as callers and tests written against the previous header expect) */
 
 /* attention modes */
 #define DIA_ATTN_SELF 0   /* decoder self-attention over the growing cache (layers.py:541-555) */
@@ -174,7 +176,9 @@ typedef struct {
    * block of 32 consecutive K of a column (dia_hip/quant.py; dia_hip/layout.py tile_weight_fp8: per strip, groups of 16 k-tiles,
    * each a 256-byte block of E8M0 scales followed by 8 KiB of e4m3 elements, expanded to the bf16 B operand of
    * v_mfma_f32_16x16x32_bf16 in registers) and KT = K/32, a multiple of 16 and at most 128 per workgroup (KT / sk).  Same
-   * restrictions as DIA_W_SPARSE24; results equal the dense tiles of the same matrix up to summation order. */
+   * restrictions as DIA_W_SPARSE24; results equal the dense tiles of the same matrix up to summation order.
+   * DIA_W_MXFP4: the same with e2m1 elements (dia_hip/layout.py tile_weight_fp4: the scale block followed by 4 KiB of elements, two
+   * per byte); same shapes, restrictions and results as DIA_W_MXFP8. */
   int32_t w_format;
   int32_t _pad2;
 } dia_gemm_args;
@@ -632,6 +636,23 @@ const char* dia_timed_kernel_name(int i);
  * dia_engine_desc.w_logits_f8): bit m = matrix m of dia_step_mat.  0 above 16 rows.  The knob "mxfp8" overrides the measured
  * default (bits 0-6: at most 4 rows, bits 8-14: 5..16 rows). */
 int dia_mxfp8_classes(int rows);
+/* MXFP4 streams of the matrices a decode step streams (dia_gemm_args.w_format = DIA_W_MXFP4, KT = kt_* of dia_dec_layer /
+ * kt_logits), handed to an engine beside its description: the description structs stay as they are.  NULL = dense only. */
+typedef struct {
+  const void *w_qkv, *w_o, *w_cq, *w_co, *w_wi, *w_wo;
+} dia_mxfp4_layer;
+typedef struct {
+  int32_t n_layer;                  /* must equal dia_engine_desc.n_layer */
+  int32_t _pad;
+  const dia_mxfp4_layer* layers;    /* host array [n_layer], copied */
+  const void* w_logits;
+} dia_mxfp4_streams;
+/* before the first step: a step of at most 16 rows then streams MXFP4 for the matrices that have a stream here and that
+ * dia_mxfp4_classes enables, under the conditions of the MXFP8 streams (an MXFP4 stream goes before an MXFP8 one of the same
+ * matrix).  NULL streams = none.  The streams hold the same numbers as the dense tiles. */
+int dia_engine_set_mxfp4(dia_engine* e, const dia_mxfp4_streams* s);
+/* as dia_mxfp8_classes for the MXFP4 streams and the knob "mxfp4" */
+int dia_mxfp4_classes(int rows);
 /* number of kernel launches in one decode step */
 int dia_engine_launches_per_step(const dia_engine* e);
 

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Offline weight-only quantisation of a Dia checkpoint: ``--format mxfp8`` rounds every DenseGeneral kernel a decode step
+"""Offline weight-only quantisation of a Dia checkpoint: ``--format mxfp8`` (``mxfp4``: the same with e2m1 elements, for
+``--weight-format mxfp4`` / ``quant="mxfp4"``, a quarter of the bytes) rounds every DenseGeneral kernel a decode step
 streams (decoder q/k/v, o, cross-q, cross-o, wi, wo and the logits head) to OCP MXFP8 — e4m3 elements with one power-of-two
 scale per 32 consecutive K of a column (dia_hip/quant.py) — and writes the DEQUANTISED values back as an ordinary
 ``pytorch_model.bin`` + ``config.json``.  Every such value is exactly a bf16 value, so the checkpoint runs anywhere a Dia
@@ -25,12 +26,13 @@ def main(argv=None) -> int:
     p = argparse.ArgumentParser(description="Quantise a Dia checkpoint on the CPU and write it back with the rounded weights baked in.")
     p.add_argument("--model-path", type=str, required=True, help="directory of the model: config.json plus its checkpoint")
     p.add_argument("--output-dir", type=str, required=True, help="where pytorch_model.bin and config.json of the quantised model go")
-    p.add_argument("--format", type=str, default="mxfp8", choices=["mxfp8"], help="mxfp8 = e4m3 elements, E8M0 scale per 32 K of a column")
+    p.add_argument("--format", type=str, default="mxfp8", choices=["mxfp8", "mxfp4"],
+                   help="mxfp8 = e4m3 elements, mxfp4 = e2m1 elements; an E8M0 scale per 32 K of a column")
     a = p.parse_args(argv)
 
     from dia_hip import weights as W
     from dia_hip.pruning import _kernel_2d
-    from dia_hip.quant import mxfp8_names, mxfp8_quantize_state_dict
+    from dia_hip.quant import mxfp4_quantize_state_dict, mxfp8_names, mxfp8_quantize_state_dict
 
     out = Path(a.output_dir)
     out.mkdir(parents=True, exist_ok=True)
@@ -46,7 +48,7 @@ def main(argv=None) -> int:
         print(f"Error loading model: {e}")
         return 1
     print(f"\nQuantising to {a.format}...")
-    qsd = mxfp8_quantize_state_dict(cfg, sd)
+    qsd = (mxfp4_quantize_state_dict if a.format == "mxfp4" else mxfp8_quantize_state_dict)(cfg, sd)
     num = sum(float((_kernel_2d(k, qsd[k]) - _kernel_2d(k, sd[k])).pow(2).sum()) for k in mxfp8_names(cfg))
     den = sum(float(sd[k].pow(2).sum()) for k in mxfp8_names(cfg))
     print(f"Relative RMS error of the quantised kernels: {(num / max(den, 1e-30)) ** 0.5:.4f}")
