@@ -7,6 +7,8 @@ Differences, all forced by the platform: the device is always the HIP device (th
 LoRA adapters are merged into the dense weights at load (dia_hip/lora.py) instead of wrapped by PEFT;
 ``--codes-output`` (build-only) saves the codec input ``[1, 9, T]`` as .npy, which is the only possible
 output where the Descript Audio Codec is not installed; ``--no-dac`` skips loading it.
+``--score-codes FILE.npy`` (build-only) generates nothing: it prints the teacher-forced log-likelihood of the given codes under
+the loaded checkpoint (Dia.score) as one JSON line.
 """
 
 from __future__ import annotations
@@ -58,6 +60,13 @@ def build_parser() -> argparse.ArgumentParser:
                    "generated (Dia.stream_frames; one slot, or the --slots chunk plan); needs --codes-output, whose file is the one "
                    "written without this flag; frames are appended to <codes-output>.frames (raw int32 [n, C]) as they arrive when "
                    "there is one utterance; not with --audio-prompt or --output")
+    g = p.add_argument_group("Scoring")
+    g.add_argument("--score-codes", type=str, default=None, help="(build-only) .npy of codec frames [T, 9] or of a delayed token buffer "
+                   "[rows, 9]: instead of generating, print the teacher-forced NLL / perplexity of these codes for the text under the "
+                   "loaded checkpoint (with --weight-format / --sparse-weights / --compute-dtype as given) as one JSON line; "
+                   "--audio-prompt (a .npy) is replayed and not scored; needs a local --model-path")
+    g.add_argument("--score-output", type=str, default=None, help="with --score-codes: .npz for the per-position arrays "
+                   "(lp_cond, lp_cfg, entropy_cfg, valid)")
     g = p.add_argument_group("Infrastructure")
     g.add_argument("--device", type=str, default=None, help="HIP device such as cuda:0 (default: the current one)")
     g.add_argument("--compute-dtype", type=str, default="bfloat16", choices=["float16", "bfloat16", "float32"], help="K/V cache dtype: bfloat16 (default; float16 is accepted and mapped to it) or float32.")
@@ -121,14 +130,38 @@ def stream_to_file(dia, args, full_text: str) -> int:
     return 0
 
 
+def score_to_stdout(dia, args, text: str, prompt) -> int:
+    """--score-codes: Dia.score of the file's codes; the summary as one JSON line, the arrays to --score-output"""
+    import json
+
+    res = dia.score(text, np.load(args.score_codes), audio_prompt=prompt, cfg_scale=args.cfg_scale,
+                    audio_prompt_text=args.audio_prompt_text)
+    print(json.dumps(res.summary()))
+    if args.score_output:
+        Path(args.score_output).parent.mkdir(parents=True, exist_ok=True)
+        np.savez(args.score_output, lp_cond=res.lp_cond, lp_cfg=res.lp_cfg, entropy_cfg=res.entropy_cfg, valid=res.valid)
+    return 0
+
+
 def main(argv=None) -> int:
     parser = build_parser()
     args = parser.parse_args(argv)
+    if args.score_codes:
+        if not Path(args.model_path).is_dir() and not (args.pruned_checkpoint and args.config):
+            parser.error("--score-codes needs --model-path: a local model directory holding config.json and the checkpoint "
+                         "(or --pruned-checkpoint with --config).")
+        if args.output or args.codes_output or args.slots or args.stream_chunk:
+            parser.error("--score-codes generates nothing: not with --output, --codes-output, --slots or --stream-chunk.")
+        if args.audio_prompt and not args.audio_prompt.endswith(".npy"):
+            parser.error("--score-codes takes --audio-prompt as a .npy of codec codes.")
+        args.no_dac = True
+    elif args.score_output:
+        parser.error("--score-output needs --score-codes.")
     if args.audio_prompt and not args.audio_prompt_text:
         parser.error("--audio-prompt needs its transcript: pass --audio-prompt-text")
     if args.pruned_checkpoint and not args.config and not Path(args.model_path).is_dir():
         parser.error("--pruned-checkpoint needs --config unless --model-path is a local directory with a config.json")
-    if not args.output and not args.codes_output:
+    if not args.output and not args.codes_output and not args.score_codes:
         parser.error("one of --output / --codes-output is required.")
     if args.slots < 0 or (args.slots and (args.audio_prompt or not args.codes_output or args.output)):
         parser.error("--slots N needs N > 0, --codes-output, and neither --audio-prompt nor --output.")
@@ -173,6 +206,14 @@ def main(argv=None) -> int:
     prompt = args.audio_prompt
     if prompt and prompt.endswith(".npy"):
         prompt = torch.from_numpy(np.load(prompt).astype(np.int64))
+    if args.score_codes:
+        try:
+            return score_to_stdout(dia, args, args.text.strip(), None if prompt is None else prompt.numpy())
+        except Exception as e:
+            print(f"Error during scoring: {e}")
+            import traceback
+            traceback.print_exc()
+            return 1
     print("Generating audio...")
     if args.stream_chunk:
         try:

@@ -28,6 +28,8 @@ struct dia_engine {
   float* x_alt = nullptr;         // dia_engine_set_x_alt: the residual stream of odd layers while wo_defer is in force
   std::vector<dia_mxfp4_layer> f4;      // dia_engine_set_mxfp4: the MXFP4 streams per layer (empty: none) ...
   const void* f4_logits = nullptr;      // ... and of the logits head
+  bool score_on = false;                // dia_engine_set_score: every step scores the forced row between the logits GEMM and the sampler
+  dia_score_args score = {};
   std::vector<hipEvent_t> prof;   // when non-empty: one event recorded after every launch (profile step)
   // weight prefetch beside the chain (graph mode): launch i+lookahead's weights are pulled into the
   // Infinity Cache by a side stream as soon as launch i has been issued
@@ -39,6 +41,7 @@ struct dia_engine {
 };
 
 int dia_prefetch_launch(const void* ptr, long nbytes, int nblocks, hipStream_t st);
+int dia_score_validate(const dia_score_args* a, const char* who);
 static int ensure_sink();
 
 static inline void mark(dia_engine* e, int i) {
@@ -116,7 +119,7 @@ static mat_w mat_weights(const dia_engine* e, int l, int m) {
 
 // The launches of one step, in order: launch(layer, what) for every one, `what` a dia_step_mat or one of the launches below.
 // enqueue_step issues them; the prefetch list and dia_engine_launches_per_step walk the same sequence.
-enum { ATTN_SELF = DIA_MAT_COUNT, ATTN_CROSS, SEG_MLP, SAMPLER };
+enum { ATTN_SELF = DIA_MAT_COUNT, ATTN_CROSS, SEG_MLP, SAMPLER, SCORE };
 template <class Launch>
 static int step_sequence(const dia_engine* e, bool with_sampler, Launch&& launch) {
   int rc = DIA_OK;                   // the first failure ends the sequence
@@ -128,6 +131,7 @@ static int step_sequence(const dia_engine* e, bool with_sampler, Launch&& launch
     else run(l, {DIA_MAT_CO, DIA_MAT_WI, DIA_MAT_WO});
   }
   run(e->d.n_layer, {DIA_MAT_LOGITS});
+  if (with_sampler && e->score_on) run(e->d.n_layer, {SCORE});      // reads cur[] before the sampler advances it
   if (with_sampler) run(e->d.n_layer, {SAMPLER});
   return rc;
 }
@@ -325,6 +329,8 @@ static int enqueue_step(dia_engine* e, bool with_sampler) {
       rc = dia_seg_mlp(&sa, st);
     } else if (what == SAMPLER) {
       rc = dia_sample(&d.sample, st);
+    } else if (what == SCORE) {
+      rc = dia_score(&e->score, st);
     } else if (what == DIA_MAT_WO && fused) {
       fused = false;                             // (the fused launch counts as two)
     } else {
@@ -591,6 +597,23 @@ extern "C" int dia_engine_set_mxfp4(dia_engine* e, const dia_mxfp4_streams* s) {
   e->f4.clear();
   if (s) e->f4.assign(s->layers, s->layers + s->n_layer);
   e->f4_logits = s ? s->w_logits : nullptr;
+  return DIA_OK;
+}
+
+extern "C" int dia_engine_set_score(dia_engine* e, const dia_score_args* a) {
+  if (!e) return dia_fail(DIA_E_ARG, "dia_engine_set_score: null engine");
+  if (e->exec || e->launches > 0) return dia_fail(DIA_E_STATE, "dia_engine_set_score: a step has already been issued or captured");
+  if (a) {
+    const dia_sample_args& sp = e->d.sample;
+    if (!sp.teacher) return dia_fail(DIA_E_ARG, "dia_engine_set_score: scoring needs a teacher-forced engine (sample.teacher)");
+    if (sp.slot_cfg_scale || sp.slot_temperature || sp.slot_top_p || sp.slot_top_k || sp.slot_max_tokens)
+      return dia_fail(DIA_E_ARG, "dia_engine_set_score: scoring is for closed batches, this sampler has per-slot state");
+    const int rc = dia_score_validate(a, "dia_engine_set_score");
+    if (rc) return rc;
+    if (a->B != e->d.B) return dia_fail(DIA_E_ARG, "dia_engine_set_score: B differs from the engine's");
+    e->score = *a;
+  }
+  e->score_on = a != nullptr;
   return DIA_OK;
 }
 

@@ -24,6 +24,7 @@ EXPORTS = (
     "dia_last_error", "dia_abi_version", "dia_device_count", "dia_set_tuning", "dia_get_tuning", "dia_has_experiments", "dia_gemm", "dia_gemm_timed", "dia_gemm_wo_deferred", "dia_mlp_fused", "dia_mlp_fused_timed", "dia_engine_mlp_fused", "dia_attn", "dia_attn_scratch_floats", "dia_enc_kv_prep", "dia_enc_attn", "dia_dec_prefill_embed", "dia_dec_prefill_kv", "dia_dec_prefill_attn",
     "dia_embed_text", "dia_embed_tokens", "dia_sample", "dia_slot_admit", "dia_slot_retire", "dia_emit_frames", "dia_prefetch", "dia_engine_create", "dia_engine_destroy",
     "dia_engine_decode", "dia_engine_set_prefetch", "dia_engine_set_x_alt", "dia_engine_step_logits_only", "dia_engine_profile_step", "dia_engine_time_step", "dia_timed_kernel_name", "dia_engine_launches_per_step", "dia_mxfp8_classes", "dia_mxfp4_classes", "dia_engine_set_mxfp4",
+    "dia_score", "dia_engine_set_score",
     "dia_seg_mlp", "dia_seg_workspace_bytes", "dia_seg_workspace_control_bytes", "dia_seg_slots", "dia_seg_supported", "dia_seg_error",
 )
 
@@ -164,6 +165,16 @@ class EmitArgs(C.Structure):
     ]
 
 
+class ScoreArgs(C.Structure):
+    """dia_score_args: teacher-forced scoring of token row cur[b] (csrc/score.hip)"""
+    _fields_ = [
+        ("logits", C.c_void_p), ("ld_logits", C.c_int32), ("B", C.c_int32), ("T", C.c_int32), ("C", C.c_int32),
+        ("V", C.c_int32), ("cfg_scale", C.c_float), ("cfg_scales", C.c_void_p),
+        ("eos", C.c_int32), ("pad", C.c_int32), ("bos", C.c_int32), ("_pad0", C.c_int32),
+        ("tokens", C.c_void_p), ("cur", C.c_void_p), ("first_step", C.c_void_p), ("fsm", C.c_void_p), ("out", C.c_void_p),
+    ]
+
+
 class DecLayer(C.Structure):
     _fields_ = [
         ("w_qkv", C.c_void_p), ("w_o", C.c_void_p), ("w_cq", C.c_void_p), ("w_co", C.c_void_p),
@@ -281,6 +292,8 @@ def lib() -> C.CDLL:
     L.dia_mxfp8_classes.argtypes = [C.c_int]
     L.dia_mxfp4_classes.argtypes = [C.c_int]
     L.dia_engine_set_mxfp4.argtypes = [C.c_void_p, C.POINTER(Mxfp4Streams)]
+    L.dia_score.argtypes = [C.POINTER(ScoreArgs), C.c_void_p]
+    L.dia_engine_set_score.argtypes = [C.c_void_p, C.POINTER(ScoreArgs)]
     L.dia_seg_mlp.argtypes = [C.POINTER(SegArgs), C.c_void_p]
     L.dia_seg_workspace_bytes.restype = C.c_int64
     L.dia_seg_workspace_control_bytes.restype = C.c_int64

@@ -501,11 +501,16 @@ class DecodeSession:
                  noise: Optional[torch.Tensor] = None, ignore_eos: bool = False,
                  teacher_tokens: Optional[Sequence[np.ndarray]] = None, stream: Optional[torch.cuda.Stream] = None,
                  s_cap: Optional[int] = None, audio_prompts: Optional[Sequence[Optional[np.ndarray]]] = None,
-                 prompt_prefill: str = "auto", attention: str = "auto", _slotted: bool = False):
+                 prompt_prefill: str = "auto", attention: str = "auto", score: bool = False,
+                 _slotted: bool = False):
         """audio_prompts: per utterance None or int codes [Tp, C] (reference model.py:311-353).  The prompt
         rows are replayed through the decode step before sampling starts (semantics: oracle.generate), or — with
         bf16 caches — prefilled as one packed MFMA batch; prompt_prefill="replay" forces the replay.
-        attention="valu" keeps bf16 V caches row-major and runs the VALU attention kernel (comparison runs)."""
+        attention="valu" keeps bf16 V caches row-major and runs the VALU attention kernel (comparison runs).
+        score=True (with teacher_tokens): every step also reduces its logits to the log-probability of the forced row, on the
+        device (dia_score; DESIGN.md "Scoring"); scores_host() downloads the [B, T, C, 3] result once at the end."""
+        if score and (teacher_tokens is None or _slotted):
+            raise ValueError("score=True scores teacher-forced rows of a closed batch: pass teacher_tokens (and no slots)")
         if prompt_prefill not in ("auto", "replay") or attention not in ("auto", "valu"):
             raise ValueError("prompt_prefill must be 'auto' or 'replay', attention 'auto' or 'valu'")
         self.prompt_prefill = prompt_prefill
@@ -667,6 +672,8 @@ class DecodeSession:
         self.slotted = bool(_slotted)
         if self.slotted:
             self._init_slots()
+        # teacher-forced scoring: lp_cond, lp_cfg, H_cfg per row and channel; NaN = no step has scored this position
+        self.scores = torch.full((B, self.T, self.C, 3), float("nan"), dtype=torch.float32, device=dev) if score else None
         self._engine = C.c_void_p()
         self._build_engine()
         self.prefilled = self.slotted            # slots are prefilled one by one, at admission
@@ -761,6 +768,12 @@ class DecodeSession:
                     setattr(f4_layers[i], "w_" + f, hb.ptr(L[f + "f4"].t))
             f4 = hb.Mxfp4Streams(n_layer=n, layers=C.cast(f4_layers, C.POINTER(hb.Mxfp4Layer)), w_logits=hb.ptr(w.logits_f4.t))
             hb.check(hb.lib().dia_engine_set_mxfp4(self._engine, C.byref(f4)), "dia_engine_set_mxfp4")
+        if self.scores is not None:
+            sp, sc = ed.sample, hb.ScoreArgs()
+            sc.logits, sc.ld_logits, sc.B, sc.T, sc.C, sc.V = sp.logits, sp.ld_logits, sp.B, sp.T, sp.C, sp.V
+            sc.cfg_scale, sc.eos, sc.pad, sc.bos = sp.cfg_scale, sp.eos, sp.pad, sp.bos
+            sc.tokens, sc.cur, sc.first_step, sc.fsm, sc.out = sp.tokens, sp.cur, sp.first_step, sp.fsm, hb.ptr(self.scores)
+            hb.check(hb.lib().dia_engine_set_score(self._engine, C.byref(sc)), "dia_engine_set_score")
 
     def close(self):
         """Tear the engine down: the stream is drained first (queued graph replays read the executable graph's own
@@ -1081,6 +1094,13 @@ class DecodeSession:
         self.sync()
         lg = self.logits[: self.R, : self.C * self.V].reshape(self.B, 2, self.C, self.V)
         return lg.cpu().numpy()
+
+    def scores_host(self) -> np.ndarray:
+        """fp32 [B, T, C, 3] = (lp_cond, lp_cfg, H_cfg) of every teacher-forced row a step has scored, NaN elsewhere (score=True)"""
+        if self.scores is None:
+            raise hb.DiaHipError("scores_host(): the session was not built with score=True")
+        self.sync()
+        return self.scores.cpu().numpy()
 
     def _raise_if_invalid(self):
         """after a sync: raise when a persistent kernel of the step gave up waiting (results invalid)"""

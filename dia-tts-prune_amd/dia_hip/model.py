@@ -255,6 +255,49 @@ class Dia:
                                top_k=int(pick(g.cfg_filter_top_k, top_k) or 0), audio_prompt=prompt))
         return out
 
+    # ------------------------------------------------------------------ scoring
+    @torch.inference_mode()
+    def score_batch(self, texts: Sequence[str], codes_list: Sequence, *, audio_prompts: Optional[Sequence] = None,
+                    cfg_scale: float = 3.0, audio_prompt_texts: Optional[Sequence[Optional[str]]] = None,
+                    use_graph: bool = True) -> List["ScoreResult"]:
+        """Teacher-forced log-likelihood of known audio codes under the loaded checkpoint, up to 8 utterances of any lengths in
+        one decode session — the session generate() would use: this model's K/V dtype, weight format, pruning and compaction.
+        codes_list[b]: codec frames [T, C] or a delayed token buffer [rows, C] (score.teacher_rows).  The rows are forced through
+        rows - 1 decode steps and every step's logits are reduced on the device (DESIGN.md "Scoring"); with an audio prompt only
+        the rows behind it are scored.  Returns one ScoreResult per utterance (nats; no sampling happens)."""
+        from .score import check_prompt_rows, summarise, teacher_rows, valid_mask
+
+        if self.model is None:
+            raise RuntimeError("no weights loaded")
+        n = len(texts)
+        if not 1 <= n <= 8 or len(codes_list) != n:
+            raise ValueError("score_batch: 1..8 texts and as many codes")
+        prompts = [None] * n if audio_prompts is None else [None if p is None else (p.detach().cpu().numpy() if isinstance(p, torch.Tensor) else np.asarray(p)) for p in audio_prompts]
+        apt = audio_prompt_texts or [None] * n
+        rows = [teacher_rows(self.config, c.detach().cpu().numpy() if isinstance(c, torch.Tensor) else c, prompt=p)
+                for c, p in zip(codes_list, prompts)]
+        first = [1 if p is None else check_prompt_rows(self.config, r, p) for r, p in zip(rows, prompts)]
+        mt = max(r.shape[0] for r in rows)
+        if mt > self.config.data.audio_length:
+            raise ValueError(f"{mt} token rows do not fit audio_length {self.config.data.audio_length}")
+        ids = [encode_text(effective_text(t, a), self.config) for t, a in zip(texts, apt)]
+        with torch.cuda.device(self.device):
+            s = DecodeSession(self.model, ids, kv_dtype=self._kv_dtype(), max_tokens=mt, cfg_scale=cfg_scale, temperature=0.0,
+                              teacher_tokens=rows, audio_prompts=prompts, score=True)
+            try:
+                s.prefill()
+                s.decode(mt - 1, use_graph=use_graph)
+                sc = s.scores_host()
+                s._raise_if_invalid()
+            finally:
+                s.close()
+        return [summarise(sc[b, : r.shape[0]], valid_mask(r, f, self.config.data)) for b, (r, f) in enumerate(zip(rows, first))]
+
+    def score(self, text: str, codes, *, audio_prompt=None, cfg_scale: float = 3.0, audio_prompt_text: Optional[str] = None) -> "ScoreResult":
+        """score_batch for one utterance"""
+        return self.score_batch([text], [codes], audio_prompts=None if audio_prompt is None else [audio_prompt], cfg_scale=cfg_scale,
+                                audio_prompt_texts=[audio_prompt_text])[0]
+
     @torch.inference_mode()
     def generate_stream(self, requests_or_texts: Sequence[Union[str, GenerationRequest]], slots: int = 8,
                         max_tokens=None, cfg_scale=3.0, temperature=1.3, top_p=0.95, cfg_filter_top_k=35,

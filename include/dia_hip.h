@@ -478,6 +478,37 @@ typedef struct {
 } dia_emit_args;
 int dia_emit_frames(const dia_emit_args* a, void* stream);
 
+/* Teacher-forced scoring (csrc/score.hip; DESIGN.md "Scoring"): the log-probability the model gives to tokens that are already in
+ * the token buffer, ONE launch, in stream order behind the logits GEMM of a step and before its sampler (cur not yet advanced).
+ * The reference has no counterpart (it only samples: model.py:447-488).  For every utterance b with t = cur[b], first_step[b] <= t
+ * < T and fsm[b][3] == 0, and every channel c, with tok = tokens[b][t][c], un / co = logits rows 2b / 2b + 1 at columns
+ * [c * V, c * V + V) and g = co + s * (co - un) under the sampler's constraints (-inf on EOS for channels >= 1, on PAD and BOS
+ * everywhere; the expression and rounding of dia_sample):
+ *   out[b][t][c][0] = log_softmax(co)[tok]                    no guidance, no constraints
+ *   out[b][t][c][1] = log_softmax(g)[tok]                     -inf for a masked target
+ *   out[b][t][c][2] = -sum p * log p of softmax(g), in nats   terms with p == 0 count 0
+ * fp32: m = max, z = sum expf(l - m), lp = (l_tok - m) - logf(z).  A target outside [0, V) writes NaN to all three; every other
+ * utterance (prompt replay rows, finished, t outside [0, T)) writes nothing.  Reads only, apart from out: no state moves.
+ * One workgroup per utterance, one wave per channel: C <= 12, V <= 1088, ld_logits >= C * V, else DIA_E_ARG before any launch. */
+typedef struct {
+  const float* logits;         /* [2B rows][ld_logits], channel c at column c*V (dia_sample_args.logits) */
+  int32_t ld_logits;
+  int32_t B;
+  int32_t T;                   /* token buffer rows */
+  int32_t C;                   /* 1..12 */
+  int32_t V;                   /* 1..1088 */
+  float cfg_scale;             /* s of every utterance, unless ... */
+  const float* cfg_scales;     /* ... device float [B] or NULL: s per utterance */
+  int32_t eos, pad, bos;
+  int32_t _pad0;
+  const int32_t* tokens;       /* [B][T][C]: row cur[b] holds the target */
+  const int32_t* cur;          /* [B] */
+  const int32_t* first_step;   /* [B] or NULL = 1 everywhere: rows below it are audio-prompt replay */
+  const int32_t* fsm;          /* [B][8] as dia_sample_args.fsm or NULL: an utterance with fsm[b][3] != 0 (done) is left alone */
+  float* out;                  /* [B][T][C][3] */
+} dia_score_args;
+int dia_score(const dia_score_args* a, void* stream);
+
 /* Read-only pass over [ptr, ptr+nbytes) that pulls it into the 256 MiB Infinity Cache ahead of its
  * consumer (weights of the next kernels of the decode chain); writes nothing. */
 int dia_prefetch(const void* ptr, int64_t nbytes, int nblocks, void* stream);
@@ -653,6 +684,12 @@ typedef struct {
 int dia_engine_set_mxfp4(dia_engine* e, const dia_mxfp4_streams* s);
 /* as dia_mxfp8_classes for the MXFP4 streams and the knob "mxfp4" */
 int dia_mxfp4_classes(int rows);
+/* before the first step (DIA_E_STATE afterwards): every step then issues dia_score(a) between its logits GEMM and its sampler, eager
+ * and in the captured graph, and dia_engine_launches_per_step reports one more; dia_engine_step_logits_only still ends at the
+ * logits.  *a is copied; its pointers must stay valid while the engine steps.  NULL = the step without it, launch for launch.
+ * Scoring is for closed teacher-forced batches: DIA_E_ARG when the engine's sample.teacher == 0 or its sampler has per-slot state,
+ * and for everything dia_score refuses. */
+int dia_engine_set_score(dia_engine* e, const dia_score_args* a);
 /* number of kernel launches in one decode step */
 int dia_engine_launches_per_step(const dia_engine* e);
 
