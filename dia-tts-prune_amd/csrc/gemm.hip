@@ -1121,7 +1121,8 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_gemm2t(const bf16_
   float xpre8[8], gpre8[8];
   auto load_resid8 = [&](int strip) {
     const int n0 = strip * 16 + e_half * 8;
-    const float* o = pe.out + (long)(e_live ? e_r : 0) * p.ldo + n0;
+    // (a thread without a row reads row 0 of the workgroup's FIRST m-tile: the second tile of the last pair may not exist, and x ends with the last m-tile)
+    const float* o = (e_live ? pe.out + (long)e_r * p.ldo : p.out + (long)16 * mt0 * p.ldo) + n0;
     const float4 xa = *reinterpret_cast<const float4*>(o), xb = *reinterpret_cast<const float4*>(o + 4);
     xpre8[0] = xa.x; xpre8[1] = xa.y; xpre8[2] = xa.z; xpre8[3] = xa.w;
     xpre8[4] = xb.x; xpre8[5] = xb.y; xpre8[6] = xb.z; xpre8[7] = xb.w;
@@ -1139,7 +1140,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_gemm2t(const bf16_
   if (ckv && e_thread) {
     const int m = 16 * (mt0 + e_t) + e_r;
     int b = p.kv_batch_index;
-    ep_row = m;
+    ep_row = e_live ? m : 0;                               // (rows past M request table row 0: the tables end with the capacity)
     if (p.row_b) {
       b = e_live ? p.row_b[m] : -1;
       ep_live = b >= 0;
@@ -1170,7 +1171,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void k_gemm2t(const bf16_
     auto look = [&](int r, int& pos, bool& lv, long& base) {
       const int rl_ = 16 * ck_tt + r, m = 16 * mt0 + rl_;
       int b = p.kv_batch_index;
-      pos = m; lv = rl_ < Ml;
+      lv = rl_ < Ml; pos = lv ? m : 0;
       if (p.row_b) {
         b = lv ? p.row_b[m] : -1;
         lv = b >= 0;
@@ -2214,6 +2215,11 @@ static int gemm_impl(const dia_gemm_args* a, const dia_wo_defer_args* wd, void* 
   if (a->epi == DIA_EPI_CROSSKV && (!a->kc || !a->vc || !a->cos_t || !a->sin_t || (!a->strip_map && a->nstrips != a->kv_heads * 16 && !(a->kv_layer_strips == a->kv_heads * 16 && a->nstrips % (a->kv_heads * 16) == 0)) ||
                                      a->kv_layer_strips < 0 || (a->kv_layer_strips > 0 && (a->kv_layer_strips != a->kv_heads * 16 || a->kv_layer_stride <= 0)) || (!a->row_b && a->M > a->kv_cap) || (!a->row_b != !a->seg_off) || (a->kv_vblocked && a->kv_cap % 32 != 0)))
     return dia_fail(DIA_E_ARG, "dia_gemm: CROSSKV shape mismatch");
+  if (a->epi == DIA_EPI_CROSSKV && (a->kv_dtype < DIA_KV_F32 || a->kv_dtype > DIA_KV_BF16X2))
+    return dia_fail(DIA_E_ARG, "dia_gemm: CROSSKV: unknown kv_dtype (DIA_KV_F32, DIA_KV_BF16 or DIA_KV_BF16X2)");
+  // (dia_attn's rule for the same caches: without a plane stride the lo plane would land on the hi plane)
+  if (a->epi == DIA_EPI_CROSSKV && a->kv_dtype == DIA_KV_BF16X2 && (a->kv_plane_stride <= 0 || a->kv_plane_stride % 8 != 0))
+    return dia_fail(DIA_E_ARG, "dia_gemm: CROSSKV: two-plane bf16 K/V needs kv_plane_stride > 0 and a multiple of 8");
   if (a->epi < 0 || a->epi > DIA_EPI_CROSSKV) return dia_fail(DIA_E_ARG, "dia_gemm: unknown epilogue");
   if (a->ssq_in && a->ssq_ld < ((a->M + 15) / 16) * 16) return dia_fail(DIA_E_ARG, "dia_gemm: ssq_ld smaller than padded rows");
 

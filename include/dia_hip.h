@@ -156,7 +156,8 @@ typedef struct {
    * i.e. K = 2048 or split-K slices of it) run the tuned M <= 4 GEMV and 5..128-row kernels; every other shape the generic one.
    * Not with w_layout = 1 or the sparse stream. */
   int32_t w_planes;
-  int64_t kv_plane_stride;  /* CROSSKV with kv_dtype DIA_KV_BF16X2: elements between the hi and the lo plane of kc / vc */
+  int64_t kv_plane_stride;  /* CROSSKV with kv_dtype DIA_KV_BF16X2: elements between the hi and the lo plane of kc / vc.  Must be positive
+                             * and a multiple of 8 then (dia_attn's rule for the same caches), else DIA_E_ARG; so is a kv_dtype outside 0..2. */
   int32_t w_layout;         /* 0: 16-column strips (above); 1: diagonal tiles of 4-column groups (dia_hip/layout.py diag_tile_weight): W = bf16
                              * [N/4][K/128][64][8], `nstrips` = N/8 (8-column half strips, one workgroup each, the whole K, no split-K);
                              * M <= 4, DIA_EPI_RESID_EMIT, fp32 tiles in and out; ssq_out receives N/8 partials per row */
