@@ -142,10 +142,6 @@ __global__ __launch_bounds__(NW * 64) void k_gemm(GemmK p) {
 // LDS as [plane][ktile][kq 0..3][row 0..RS-1] x 16 B; lane l of a wave then reads its A fragment for
 // k-tile kt at ((plane*KT + kt)*4 + (l>>4))*RS + min(l&15, RS-1) (rows >= RS alias row RS-1: broadcast).
 
-// The first ten arguments repeat fields of p: they fill the first 64 bytes of the argument block, which the command
-// processor hands over in SGPRs at wave launch (kernarg preload, -mllvm -amdgpu-kernarg-preload-count=16) — the operand
-// and weight loads of the prologue then need no scalar load from the argument block, whose lines every CU of the grid
-// otherwise requests at the same moment (in-kernel stamps: 0.8 us from the start of a wave to its first weight load).
 // W2: two-plane weights (w_planes == 2): weight k-tile j of the range is plane j & 1 of activation k-tile j >> 1, so the A image
 // covers KPW / 2 k-tiles per wave; weight stream, prefetch and epilogues are those of the one-plane form.
 // DF: wo's cross-workgroup split-K merged behind the kernel boundary that follows it anyway (dia_gemm_wo_deferred).
@@ -156,11 +152,11 @@ __global__ __launch_bounds__(NW * 64) void k_gemm(GemmK p) {
 //       operations: x_new = x_old + (0 + s_0 + s_1), the half-strip sums of squares as run_epilogue_rows forms them, the image
 //       mul_rn(x_new, g).  Workgroup b < D/16 stores columns 16 b .. 16 b + 15 of x_new (to another buffer than x_old: every
 //       workgroup reads the whole old row).
-template <int NW, int KPW, int RS, bool MULTI, bool AF32 = false, bool PF32 = false, bool W2 = false, int DF = 0>
-__global__ __launch_bounds__(NW * 64) void k_gemv_small(const bf16_raw* a_A, long a_aps, const bf16_raw* a_W, int a_KT, int a_M, int a_epi,
-                                                        int a_nstrips, float* a_out, int a_ldo, const float* a_gnext, GemmK p) {
-  p.A = a_A; p.a_plane_stride = a_aps; p.W = a_W; p.KT = a_KT; p.M = a_M; p.epi = a_epi; p.nstrips = a_nstrips;
-  p.out = a_out; p.ldo = a_ldo; p.gnext = a_gnext;
+// SPEC: the two forms of the projections at K = 2048 (k_gemv_small<RS, Form> below) whose epilogue, K range and
+// operand set are compile-time facts: 1 = SCALE_STORE with row scales over at most 128 strip sums, 2 = RESID_EMIT without row scales;
+// one strip per workgroup, no split-K, no compaction maps.  The arithmetic is that of SPEC = 0, operation for operation.
+template <int NW, int KPW, int RS, bool MULTI, bool AF32, bool PF32, bool W2, int DF, int SPEC = 0>
+__device__ __forceinline__ void gemv_small_body(GemmK& p) {
   // (the compiler loads the fields of the 250-byte argument block where they are first used: four s_load round trips
   // lie between the start of a wave and its first weight load.  Fetching every field up front in one batch —
   // asm volatile("" :: "s"(p.A), "s"(p.W), ...) — was measured: the step got 4 % SLOWER, the first wait then covers four
@@ -173,10 +169,11 @@ __global__ __launch_bounds__(NW * 64) void k_gemv_small(const bf16_raw* a_A, lon
   static_assert(DF == 0 || (AF32 && PF32 && !W2), "the deferred wo merge: fp32 activation tiles, one weight plane");
   static_assert(DF != 2 || (NW * KPW == 64 && (RS == 2 || RS == 4)), "the deferred consumer holds a whole row of D = 2048: 128 strips");
   static_assert(DF != 1 || !MULTI, "the deferred producer: one strip per workgroup");
+  static_assert(SPEC == 0 || (AF32 && PF32 && !W2 && DF == 0 && !MULTI), "the specialised forms: fp32 tiles, one plane, one strip");
 
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int kt0 = w * KPW;                 // k-tile inside this workgroup's K range
-  const int ktg = blockIdx.y * (NW * KPW); // first global k-tile of that range (split-K over gridDim.y)
+  const int ktg = SPEC ? 0 : blockIdx.y * (NW * KPW); // first global k-tile of that range (split-K over gridDim.y)
   constexpr int WS = W2 ? 1 : 0;           // weight k-tile -> activation k-tile: >> WS
   const int ktga = ktg >> WS;              // first global activation k-tile of the range
   const int G = gridDim.x;                 // the workgroup walks strips blockIdx.x, +G, +2G, ...
@@ -244,7 +241,7 @@ __global__ __launch_bounds__(NW * 64) void k_gemv_small(const bf16_raw* a_A, lon
     }
   }
   // (2) strip sums of squares for the row scale: 8 threads per row, up to 16 strips each per round
-  const bool has_norm = DF == 2 || p.ssq_in != nullptr;
+  const bool has_norm = DF == 2 || SPEC == 1 || (SPEC == 0 && p.ssq_in != nullptr);
   const int s_row = tid >> 3, s_part = tid & 7;
   const bool s_thread = tid < 128 && has_norm;
   float sq[16];
@@ -270,6 +267,12 @@ __global__ __launch_bounds__(NW * 64) void k_gemv_small(const bf16_raw* a_A, lon
   load_strip(b0, blockIdx.x);                       // the HBM stream starts here
   __builtin_amdgcn_sched_barrier(0);
 #endif
+  if constexpr (SPEC == 1) {
+    // the strip sums stay opaque until the weight requests are out: left alone, the compiler folds the first add of the reduction
+    // below (0 + sq[0]) into the masked region above, with a wait for the oldest three requests in front of the weight stream
+#pragma unroll
+    for (int i = 0; i < 16; ++i) asm volatile("" : "+v"(sq[i]));
+  }
   STAMP(1);
   if constexpr (DF == 2) {
 #pragma unroll
@@ -323,7 +326,7 @@ __global__ __launch_bounds__(NW * 64) void k_gemv_small(const bf16_raw* a_A, lon
     float s0 = 0.f;
 #pragma unroll
     for (int i = 0; i < 16; ++i) s0 += ((DF == 2 || s_part + 8 * i < p.ssq_in_n) && s_row < p.M) ? sq[i] : 0.f;
-    if (DF != 2 && s_thread && s_row < p.M)
+    if (DF != 2 && SPEC == 0 && s_thread && s_row < p.M)
       for (int idx = s_part + 128; idx < p.ssq_in_n; idx += 8) s0 += p.ssq_in[(long)idx * p.ssq_ld + s_row];   // D > 2048 only
     // the 8 partials of a row sit in 8 consecutive lanes: quad xor 1, quad xor 2, then the other quad of the half row
     // (after two steps a quad is uniform, so the mirror delivers what lane ^ 4 holds) — DPP, no LDS crossbar
@@ -362,7 +365,7 @@ __global__ __launch_bounds__(NW * 64) void k_gemv_small(const bf16_raw* a_A, lon
     }
     STAMP(3);
     float v = 0.f;
-    if (MULTI || DF == 1 || gridDim.y == 1) {
+    if (MULTI || DF == 1 || SPEC != 0 || gridDim.y == 1) {
       f32x4* rb = red16 + sbuf * (NW * 16);
       sbuf ^= 1;
       if (lane < 16) rb[w * 16 + lane] = acc[0];
@@ -405,6 +408,52 @@ __global__ __launch_bounds__(NW * 64) void k_gemv_small(const bf16_raw* a_A, lon
     body(b0, b1, blockIdx.x);
   }
   STAMP(5);
+}
+
+// The first ten arguments repeat fields of p: they fill the first 64 bytes of the argument block, which the command
+// processor hands over in SGPRs at wave launch (kernarg preload, -mllvm -amdgpu-kernarg-preload-count=16) — the operand
+// and weight loads of the prologue then need no scalar load from the argument block, whose lines every CU of the grid
+// otherwise requests at the same moment (in-kernel stamps: 0.8 us from the start of a wave to its first weight load).
+template <int NW, int KPW, int RS, bool MULTI, bool AF32 = false, bool PF32 = false, bool W2 = false, int DF = 0>
+__global__ __launch_bounds__(NW * 64) void k_gemv_small(const bf16_raw* a_A, long a_aps, const bf16_raw* a_W, int a_KT, int a_M, int a_epi,
+                                                        int a_nstrips, float* a_out, int a_ldo, const float* a_gnext, GemmK p) {
+  p.A = a_A; p.a_plane_stride = a_aps; p.W = a_W; p.KT = a_KT; p.M = a_M; p.epi = a_epi; p.nstrips = a_nstrips;
+  p.out = a_out; p.ldo = a_ldo; p.gnext = a_gnext;
+  gemv_small_body<NW, KPW, RS, MULTI, AF32, PF32, W2, DF>(p);
+}
+
+// The 1-4-row projections of the decode step at K = 2048 (8 waves x 8 k-tiles, fp32 tiles in and out, dense one-plane weights, one
+// strip per workgroup): one form per epilogue, each with ITS operands in the preloaded leading arguments — a single order cannot
+// serve both.  A form names the types of the eight arguments behind A and W, in the order its prologue wants them, and puts them
+// into p; the epilogue kind, the K range and the absent operands are compile-time constants.
+//   ScaleStore  ssq_in, ssq_in_n, ssq_ld, inv_d, eps, M, ldo, out        (row scales over at most 128 strip sums)
+//   ResidEmit   out (the residual), gnext, P, M, ldo, p_ktiles, ssq_ld, ssq_out        (no norm on the input)
+// The kernel keeps the family name k_gemv_small — it is the same body — as an overload on the template parameter list: tests and
+// the bench tables select the 1-4-row weight streams by the prefix "k_gemv_small<".
+struct ScaleStore {
+  static constexpr int SPEC = 1, EPI = DIA_EPI_SCALE_STORE;
+  using T2 = const float*; using T3 = int; using T4 = int; using T5 = float; using T6 = float; using T7 = int; using T8 = int; using T9 = float*;
+  static __device__ __forceinline__ void set(GemmK& p, T2 ssq_in, T3 ssq_in_n, T4 ssq_ld, T5 inv_d, T6 eps, T7 M, T8 ldo, T9 out) {
+    p.ssq_in = ssq_in; p.ssq_in_n = ssq_in_n; p.ssq_ld = ssq_ld; p.inv_d = inv_d; p.eps = eps; p.M = M; p.ldo = ldo; p.out = out;
+  }
+};
+struct ResidEmit {
+  static constexpr int SPEC = 2, EPI = DIA_EPI_RESID_EMIT;
+  using T2 = float*; using T3 = const float*; using T4 = bf16_raw*; using T5 = int; using T6 = int; using T7 = int; using T8 = int; using T9 = float*;
+  static __device__ __forceinline__ void set(GemmK& p, T2 out, T3 gnext, T4 P, T5 M, T6 ldo, T7 p_ktiles, T8 ssq_ld, T9 ssq_out) {
+    p.out = out; p.gnext = gnext; p.P = P; p.M = M; p.ldo = ldo; p.p_ktiles = p_ktiles; p.ssq_ld = ssq_ld; p.ssq_out = ssq_out;
+    p.ssq_in = nullptr;
+  }
+};
+
+template <int RS, typename Form>
+__global__ __launch_bounds__(512) void k_gemv_small(const bf16_raw* a_A, const bf16_raw* a_W, typename Form::T2 a2, typename Form::T3 a3,
+                                                    typename Form::T4 a4, typename Form::T5 a5, typename Form::T6 a6, typename Form::T7 a7,
+                                                    typename Form::T8 a8, typename Form::T9 a9, GemmK p) {
+  p.A = a_A; p.W = a_W;
+  Form::set(p, a2, a3, a4, a5, a6, a7, a8, a9);
+  p.KT = 64; p.epi = Form::EPI; p.strip_map = nullptr; p.cmap = nullptr;
+  gemv_small_body<8, 8, RS, false, true, true, false, 0, Form::SPEC>(p);
 }
 
 
@@ -2047,6 +2096,35 @@ int launch_small_rs(const GemmK& k, int nw, int sk, hipStream_t st, bool& handle
   return DIA_OK;
 }
 
+// the two per-epilogue forms of the K = 2048 projections (k_gemv_small<RS, Form>): true when this launch is one of theirs.  What they
+// leave to the generic instantiation: an explicit wave count, several strips per workgroup, split-K, compaction maps, row scales over
+// more than 128 strip sums, a RESID_EMIT that norms its input.  Knob gemv_spec=0: the generic form everywhere (A/B).
+bool small_spec_serves(const dia_gemm_args* a, const GemmK& k, int sk) {
+  if (dia_tune(DIA_TUNE_GEMV_SPEC) == 0 || a->M > 4 || a->nw != 0 || sk != 1 || a->KT != 64 || a->cmap || a->strip_map) return false;
+  if (pick_spw(k, 512, 1, 1) != 1) return false;
+  // the one exclusion that is not the kernel's: SCALE_STORE onto 192 strips is the q/k/v projection of Dia-1.6B, whose generic
+  // instantiation tests/test_gpu_wo_deferred.py pins by name as the reference of the deferred-wo consumer (which serves that projection
+  // in every layer but the first)
+  const bool pinned_qkv = a->epi == DIA_EPI_SCALE_STORE && a->nstrips == 192;
+  if (pinned_qkv) return false;
+  if (a->epi == DIA_EPI_SCALE_STORE) return k.a_f32 && a->ssq_in && a->ssq_in_n >= 1 && a->ssq_in_n <= 128;
+  if (a->epi == DIA_EPI_RESID_EMIT) return k.a_f32 && k.p_f32 && !a->ssq_in && a->gnext;
+  return false;
+}
+
+template <int RS>
+int launch_small_spec(const GemmK& k, hipStream_t st) {
+  const size_t smem = small_smem(8, 64, RS);
+  // the argument order behind A and W is the one ScaleStore::set / ResidEmit::set declare (several neighbouring ints: keep them in step)
+  if (k.epi == DIA_EPI_SCALE_STORE)
+    dia_launch<k_gemv_small<RS, ScaleStore>>(dim3(k.nstrips), dim3(512), smem, st, k.A, k.W, k.ssq_in, k.ssq_in_n, k.ssq_ld, k.inv_d, k.eps,
+                                             k.M, k.ldo, k.out, k);
+  else
+    dia_launch<k_gemv_small<RS, ResidEmit>>(dim3(k.nstrips), dim3(512), smem, st, k.A, k.W, k.out, k.gnext, k.P, k.M, k.ldo, k.p_ktiles,
+                                            k.ssq_ld, k.ssq_out, k);
+  return dia_check_launch("k_gemv_small");
+}
+
 // Two-plane weights (w_planes == 2).  Every tuned form takes 128 weight k-tiles per workgroup (64 activation k-tiles: K = 2048,
 // or a split-K slice of a longer K) as 8 waves x 16 weight tiles — the bytes per wave in flight of the one-plane 8 x 8 forms doubled,
 // the A operand of a wave unchanged (8 activation k-tiles).
@@ -2129,7 +2207,8 @@ extern "C" int dia_has_experiments(void) {
 }
 
 // Shape -> kernel.  Decode (M = 2 x batch rows):
-//   M <= 4            k_gemv_small   (LDS-staged compact activations; persistent multi-strip form for N >= 16384)
+//   M <= 4            k_gemv_small   (LDS-staged compact activations; persistent multi-strip form for N >= 16384;
+//                                    K = 2048, one strip per workgroup: the per-epilogue forms k_gemv_small<RS, Form>, small_spec_serves)
 //   5..16 rows        k_gemm16       (register-resident A fragments)
 //   17..128 rows      k_gemm16 over gridDim.z m-tiles (weights shared through one XCD's L2)
 // Prefill (hundreds of packed rows): k_gemm_tile_ws (MFMA-bound).  Everything else: k_gemm (any shape).
@@ -2275,6 +2354,7 @@ static int gemm_impl(const dia_gemm_args* a, const dia_wo_defer_args* wd, void* 
       else rc = (rs == 2) ? launch_small_rs<2>(k, waves, sk, st, handled) : launch_small_rs<4>(k, waves, sk, st, handled);
       return handled;
     };
+    if (uni_f32 && small_spec_serves(a, k, sk)) return rs == 2 ? launch_small_spec<2>(k, st) : launch_small_spec<4>(k, st);
     if (small(nw)) return rc;
     // default wave count under split-K: sixteen waves only where their table has the slice's k-tiles per wave (1, 2, 4, 8); a slice
     // of 48, 80, 96 or 112 k-tiles (compacted hidden 3072, 5120, 6144, 7168 under split-K 2) takes eight waves x 6, 10, 12, 14
