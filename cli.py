@@ -4,7 +4,8 @@ flow (validate -> seed -> load -> optional adapters -> generate -> save, 100-229
 
 Differences, all forced by the platform: the device is always the HIP device (there is no CPU path);
 ``--compute-dtype`` selects the K/V cache dtype (weights are bf16 tiles either way; float32 = parity mode);
-LoRA adapters are merged into the dense weights at load (dia_hip/lora.py) instead of wrapped by PEFT;
+LoRA adapters are merged into the dense weights at load (``--adapter-path``, dia_hip/lora.py) instead of wrapped by PEFT, or kept
+unmerged beside them and chosen per run / per chunk (``--adapter NAME=DIR`` ... ``--use-adapter NAME``);
 ``--codes-output`` (build-only) saves the codec input ``[1, 9, T]`` as .npy, which is the only possible
 output where the Descript Audio Codec is not installed; ``--no-dac`` skips loading it.
 ``--score-codes FILE.npy`` (build-only) generates nothing: it prints the teacher-forced log-likelihood of the given codes under
@@ -42,6 +43,11 @@ def build_parser() -> argparse.ArgumentParser:
     g.add_argument("--config", type=str, default=None, help="config.json to use instead of the one in --model-path")
     g.add_argument("--pruned-checkpoint", type=str, default=None, help="checkpoint file to load instead of the one in --model-path, e.g. an offline_prune.py output")
     g.add_argument("--adapter-path", type=str, default=None, help="LoRA adapter directory; folded into the dense weights while loading")
+    g.add_argument("--adapter", action="append", default=[], metavar="NAME=DIR", help="(build-only, repeatable) LoRA adapter directory kept "
+                   "UNMERGED beside the base weights under NAME (q_proj / k_proj / v_proj adapters, rank <= 64); chosen per run with "
+                   "--use-adapter; not with --adapter-path")
+    g.add_argument("--use-adapter", type=str, default=None, metavar="NAME", help="(build-only) generate (or score) with this --adapter; with "
+                   "--slots N a comma list with one entry per chunk (an empty entry = the base model) or one name for all chunks")
     g.add_argument("--no-dac", action="store_true", help="(build-only) do not load the audio codec; requires --codes-output")
     g = p.add_argument_group("Audio Prompting (Voice Cloning)")
     g.add_argument("--audio-prompt", type=str, default=None, help="voice to clone: an audio file (needs the codec) or a .npy of codec codes [T, 9]")
@@ -84,6 +90,34 @@ def build_parser() -> argparse.ArgumentParser:
     return p
 
 
+def parse_adapter_flags(parser, args):
+    """--adapter NAME=DIR ... / --use-adapter: {name: dir} of the unmerged bank; every conflict goes through parser.error"""
+    if (args.adapter or args.use_adapter) and args.adapter_path:
+        parser.error("--adapter-path merges ONE adapter into the weights at load; it cannot be combined with --adapter / --use-adapter "
+                     "(the unmerged, per-request bank).")
+    dirs = {}
+    for item in args.adapter:
+        name, sep, path = item.partition("=")
+        if not sep or not name or not path:
+            parser.error(f"--adapter takes NAME=DIR, got {item!r}")
+        if name in dirs:
+            parser.error(f"--adapter {name!r} is given twice")
+        dirs[name] = path
+    if args.use_adapter is not None:
+        names = args.use_adapter.split(",")
+        if len(names) > 1 and not args.slots:
+            parser.error("--use-adapter takes a comma list only with --slots N (one entry per chunk).")
+        for n_ in names:
+            if n_ and n_ not in dirs:
+                parser.error(f"--use-adapter {n_!r} is not among the --adapter names {sorted(dirs)}")
+    return dirs
+
+
+def used_adapters(args):
+    """--use-adapter as the callers take it: None, or the list of names (an empty entry = the base model)"""
+    return None if args.use_adapter is None else [n_ or None for n_ in args.use_adapter.split(",")]
+
+
 def stream_to_file(dia, args, full_text: str) -> int:
     """--stream-chunk: the text (one utterance in one slot, or the --slots chunk plan) through Dia.stream_frames.  With one
     utterance every chunk is appended to <codes-output>.frames the moment it arrives; at the end the chunks are joined into the
@@ -93,11 +127,11 @@ def stream_to_file(dia, args, full_text: str) -> int:
     kw = dict(cfg_scale=args.cfg_scale, temperature=args.temperature, top_p=args.top_p, cfg_filter_top_k=args.cfg_filter_top_k)
     if args.slots:
         from dia_hip.callers import stream_chunks_codes
-        it = stream_chunks_codes(dia, full_text, slots=args.slots, chunk=args.stream_chunk, seed=args.seed,
+        it = stream_chunks_codes(dia, full_text, slots=args.slots, chunk=args.stream_chunk, seed=args.seed, adapter=used_adapters(args),
                                  max_new_tokens=args.max_tokens or dia.config.data.audio_length, **kw)
     else:
         it = dia.stream_frames([full_text], 1, max_tokens=args.max_tokens, seeds=None if args.seed is None else [args.seed],
-                               chunk=args.stream_chunk, **kw)
+                               chunk=args.stream_chunk, adapters=used_adapters(args), **kw)
     out = Path(args.codes_output)
     out.parent.mkdir(parents=True, exist_ok=True)
     side = None if args.slots else open(str(out) + ".frames", "wb")
@@ -135,7 +169,7 @@ def score_to_stdout(dia, args, text: str, prompt) -> int:
     import json
 
     res = dia.score(text, np.load(args.score_codes), audio_prompt=prompt, cfg_scale=args.cfg_scale,
-                    audio_prompt_text=args.audio_prompt_text)
+                    audio_prompt_text=args.audio_prompt_text, adapter=args.use_adapter)
     print(json.dumps(res.summary()))
     if args.score_output:
         Path(args.score_output).parent.mkdir(parents=True, exist_ok=True)
@@ -159,6 +193,7 @@ def main(argv=None) -> int:
         parser.error("--score-output needs --score-codes.")
     if args.audio_prompt and not args.audio_prompt_text:
         parser.error("--audio-prompt needs its transcript: pass --audio-prompt-text")
+    bank_dirs = parse_adapter_flags(parser, args)
     if args.pruned_checkpoint and not args.config and not Path(args.model_path).is_dir():
         parser.error("--pruned-checkpoint needs --config unless --model-path is a local directory with a config.json")
     if not args.output and not args.codes_output and not args.score_codes:
@@ -195,6 +230,9 @@ def main(argv=None) -> int:
                                       adapter_path=args.adapter_path)
         if args.adapter_path:
             print("LoRA adapters merged successfully.")
+        if bank_dirs:
+            dia.load_adapters(bank_dirs)
+            print(f"LoRA adapters loaded unmerged: {sorted(bank_dirs)}")
         print("Model loaded successfully.")
     except Exception as e:
         print(f"Error loading model: {e}")
@@ -228,7 +266,7 @@ def main(argv=None) -> int:
             from dia_hip.callers import generate_chunks_codes
             parts = generate_chunks_codes(dia, full_text, slots=args.slots, max_new_tokens=args.max_tokens or dia.config.data.audio_length,
                                           cfg_scale=args.cfg_scale, temperature=args.temperature, top_p=args.top_p,
-                                          cfg_filter_top_k=args.cfg_filter_top_k, seed=args.seed)
+                                          cfg_filter_top_k=args.cfg_filter_top_k, seed=args.seed, adapter=used_adapters(args))
             if not parts:
                 print("Generation failed to produce codes.")
                 return 1
@@ -245,7 +283,8 @@ def main(argv=None) -> int:
     try:
         audio = dia.generate(text=full_text, audio_prompt=prompt, audio_prompt_text=args.audio_prompt_text,
                              max_tokens=args.max_tokens, cfg_scale=args.cfg_scale, temperature=args.temperature,
-                             top_p=args.top_p, cfg_filter_top_k=args.cfg_filter_top_k, seed=args.seed, verbose=args.verbose)
+                             top_p=args.top_p, cfg_filter_top_k=args.cfg_filter_top_k, seed=args.seed, verbose=args.verbose,
+                             adapter=args.use_adapter)
         if args.codes_output and dia.last_codes is not None:
             Path(args.codes_output).parent.mkdir(parents=True, exist_ok=True)
             np.save(args.codes_output, dia.last_codes)

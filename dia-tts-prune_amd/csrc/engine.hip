@@ -30,6 +30,9 @@ struct dia_engine {
   const void* f4_logits = nullptr;      // ... and of the logits head
   bool score_on = false;                // dia_engine_set_score: every step scores the forced row between the logits GEMM and the sampler
   dia_score_args score = {};
+  std::vector<dia_lora_layer> lora;     // dia_engine_set_lora: the adapter tables of the two decode sites per layer (empty: no LoRA launches)
+  const int32_t* lora_slot = nullptr;   // ... and the device array adapter_of_slot [B]
+  int lora_adapters = 0;
   std::vector<hipEvent_t> prof;   // when non-empty: one event recorded after every launch (profile step)
   // weight prefetch beside the chain (graph mode): launch i+lookahead's weights are pulled into the
   // Infinity Cache by a side stream as soon as launch i has been issued
@@ -42,7 +45,9 @@ struct dia_engine {
 
 int dia_prefetch_launch(const void* ptr, long nbytes, int nblocks, hipStream_t st);
 int dia_score_validate(const dia_score_args* a, const char* who);
+int dia_lora_validate(const dia_lora_args* a, const char* who);
 static int ensure_sink();
+static int dia_lora_noop(void* st);
 
 static inline void mark(dia_engine* e, int i) {
   if (!e->prof.empty() && i + 1 < (int)e->prof.size()) (void)hipEventRecord(e->prof[i + 1], e->stream);
@@ -119,14 +124,15 @@ static mat_w mat_weights(const dia_engine* e, int l, int m) {
 
 // The launches of one step, in order: launch(layer, what) for every one, `what` a dia_step_mat or one of the launches below.
 // enqueue_step issues them; the prefetch list and dia_engine_launches_per_step walk the same sequence.
-enum { ATTN_SELF = DIA_MAT_COUNT, ATTN_CROSS, SEG_MLP, SAMPLER, SCORE };
+enum { ATTN_SELF = DIA_MAT_COUNT, ATTN_CROSS, SEG_MLP, SAMPLER, SCORE, LORA_QKV, LORA_CQ };
 template <class Launch>
 static int step_sequence(const dia_engine* e, bool with_sampler, Launch&& launch) {
   int rc = DIA_OK;                   // the first failure ends the sequence
   auto run = [&](int l, std::initializer_list<int> seq) { for (int what : seq) if (!rc) rc = launch(l, what); };
   for (int l = 0; l < e->d.n_layer; ++l) {
     if (!e->seg || l == 0) run(l, {DIA_MAT_QKV});
-    run(l, {ATTN_SELF, DIA_MAT_O, DIA_MAT_CQ, ATTN_CROSS});
+    if (e->lora.empty()) run(l, {ATTN_SELF, DIA_MAT_O, DIA_MAT_CQ, ATTN_CROSS});
+    else run(l, {LORA_QKV, ATTN_SELF, DIA_MAT_O, DIA_MAT_CQ, LORA_CQ, ATTN_CROSS});     // dia_engine_set_lora: the adapters' corrections of qkv / qc
     if (e->seg) run(l, {SEG_MLP});     // persistent MLP segment: co, wi, wo and the next layer's qkv in one launch
     else run(l, {DIA_MAT_CO, DIA_MAT_WI, DIA_MAT_WO});
   }
@@ -174,6 +180,24 @@ static bool wo_split_k(const dia_engine_desc& d, const dia_dec_layer& L, int R, 
   g.spw = wo_spw;
   if (dia_tune(DIA_TUNE_WO_SPW) > 0) g.spw = dia_tune(DIA_TUNE_WO_SPW);
   return wo_pair;
+}
+
+// the dia_lora_apply of one decode site: q / k / v of layer l into d.qkv (cross = false) or its cross-attention query into d.qc, from the
+// residual rows `x` the projection consumed
+static dia_lora_args lora_site(const dia_engine* e, int l, bool cross, const float* x) {
+  const dia_engine_desc& d = e->d;
+  const dia_lora_layer& A = e->lora[l];
+  dia_lora_args a = {};
+  a.x = x; a.ldx = d.D; a.D = d.D; a.gain = cross ? e->layers[l].g_ca : e->layers[l].g_sa; a.eps = d.eps; a.M = 2 * d.B;
+  a.rows_per_slot = 2; a.n_slots = d.B; a.adapter_of_slot = e->lora_slot; a.n_adapters = e->lora_adapters;
+  if (cross) {
+    a.out = d.qc; a.ldo = d.cq_heads * 128;
+    if (A.cq.n_cols > 0) a.seg[a.n_segs++] = A.cq;
+  } else {
+    a.out = d.qkv; a.ldo = (d.q_heads + 2 * d.kv_heads) * 128;
+    for (const dia_lora_seg* s : {&A.q, &A.k, &A.v}) if (s->n_cols > 0) a.seg[a.n_segs++] = *s;
+  }
+  return a;
 }
 
 static int enqueue_step(dia_engine* e, bool with_sampler) {
@@ -331,6 +355,10 @@ static int enqueue_step(dia_engine* e, bool with_sampler) {
       rc = dia_sample(&d.sample, st);
     } else if (what == SCORE) {
       rc = dia_score(&e->score, st);
+    } else if (what == LORA_QKV || what == LORA_CQ) {
+      // the rows the projection read: layer l's residual stream — under deferral the q/k/v launch of layer l > 0 has just written it (xnew)
+      const dia_lora_args la = lora_site(e, l, what == LORA_CQ, xbuf(l));
+      rc = la.n_segs ? dia_lora_apply(&la, st) : dia_lora_noop(st);
     } else if (what == DIA_MAT_WO && fused) {
       fused = false;                             // (the fused launch counts as two)
     } else {
@@ -614,6 +642,41 @@ extern "C" int dia_engine_set_score(dia_engine* e, const dia_score_args* a) {
     e->score = *a;
   }
   e->score_on = a != nullptr;
+  return DIA_OK;
+}
+
+// a site no adapter of the bank touches keeps its place in the sequence (the launch count does not depend on the bank's contents)
+__global__ void k_lora_none() {}
+static int dia_lora_noop(void* st) {
+  dia_launch<k_lora_none>(dim3(1), dim3(64), 0, (hipStream_t)st);
+  return dia_check_launch("k_lora_none");
+}
+
+extern "C" int dia_engine_set_lora(dia_engine* e, const dia_lora_step* s) {
+  if (!e) return dia_fail(DIA_E_ARG, "dia_engine_set_lora: null engine");
+  if (e->exec || e->launches > 0) return dia_fail(DIA_E_STATE, "dia_engine_set_lora: a step has already been issued or captured");
+  if (!s) { e->lora.clear(); e->lora_slot = nullptr; e->lora_adapters = 0; return DIA_OK; }
+  const dia_engine_desc& d = e->d;
+  if (s->n_layer != d.n_layer || !s->layers) return dia_fail(DIA_E_ARG, "dia_engine_set_lora: one dia_lora_layer per decoder layer");
+  if (!s->adapter_of_slot || s->n_adapters <= 0) return dia_fail(DIA_E_ARG, "dia_engine_set_lora: adapter_of_slot and at least one adapter");
+  if (e->seg) return dia_fail(DIA_E_ARG, "dia_engine_set_lora: the persistent MLP segments run the q/k/v projection inside their launch (seg must be off)");
+  if (d.sample.embed.cmap) return dia_fail(DIA_E_ARG, "dia_engine_set_lora: compacted checkpoint (compaction map on the first layer's q/k/v input)");
+  for (int l = 0; l < d.n_layer; ++l) {
+    const dia_dec_layer& L = e->layers[l];
+    if (L.smap_qkv || L.smap_cq || L.cmap_ca || L.cmap_next)
+      return dia_fail(DIA_E_ARG, "dia_engine_set_lora: compacted checkpoint (strip or compaction map on an adapted projection)");
+  }
+  e->lora.assign(s->layers, s->layers + s->n_layer);
+  e->lora_slot = s->adapter_of_slot; e->lora_adapters = s->n_adapters;
+  for (int l = 0; l < d.n_layer; ++l) {        // every site's descriptor, on either residual buffer, is checked before a step exists
+    for (int site = 0; site < 4; ++site) {
+      const float* x = (site & 2) ? e->x_alt : d.x;
+      if (!x) continue;
+      const dia_lora_args a = lora_site(e, l, (site & 1) != 0, x);
+      const int rc = a.n_segs ? dia_lora_validate(&a, "dia_engine_set_lora") : DIA_OK;
+      if (rc) { e->lora.clear(); e->lora_slot = nullptr; e->lora_adapters = 0; return rc; }
+    }
+  }
   return DIA_OK;
 }
 

@@ -103,6 +103,19 @@ __device__ __forceinline__ void kv_store(void* base, int dtype, long idx, float 
   } else KVElem<bf16_raw>::store(reinterpret_cast<bf16_raw*>(base) + idx, v);
 }
 
+// Element index of (utterance kvb, head, key m, dim 0) in a K cache and in an unblocked V cache [kv rows][heads][kv_cap][128] ...
+__device__ __forceinline__ long kv_row_index(int kvb, int heads, int head, int cap, int m) {
+  return (((long)kvb * heads + head) * cap + m) * 128;
+}
+// ... and of (utterance kvb, head, key m, dim 0) in a blocked V cache [key/32][128 dims][32 keys]: dim d lies d * 32 elements behind it
+// (the MFMA attention reads 8 consecutive keys per lane).  These restate the index expressions of the CROSSKV epilogue below (run_epilogue,
+// whose text stays as it is so that the tuned GEMM kernels compile to the code they had) for the adapters' cache update (lora.hip): a
+// layout change must change both, and tests/test_gpu_lora_model.py's cache-format cases fail if they part ways
+__device__ __forceinline__ long kv_vblocked_index(int kvb, int heads, int head, int cap, int m) {
+  const long hb = ((long)kvb * heads + head) * cap * 128;
+  return hb + (long)(m >> 5) * 128 * 32 + (m & 31);
+}
+
 // Everything the epilogue needs from memory is requested early, behind the weight loads, so that its
 // latency overlaps theirs instead of adding dependent round trips at the end of the kernel.
 template <int MT, int NT>

@@ -25,6 +25,7 @@ EXPORTS = (
     "dia_embed_text", "dia_embed_tokens", "dia_sample", "dia_slot_admit", "dia_slot_retire", "dia_emit_frames", "dia_prefetch", "dia_engine_create", "dia_engine_destroy",
     "dia_engine_decode", "dia_engine_set_prefetch", "dia_engine_set_x_alt", "dia_engine_step_logits_only", "dia_engine_profile_step", "dia_engine_time_step", "dia_timed_kernel_name", "dia_engine_launches_per_step", "dia_mxfp8_classes", "dia_mxfp4_classes", "dia_engine_set_mxfp4",
     "dia_score", "dia_engine_set_score",
+    "dia_lora_apply", "dia_lora_crosskv", "dia_engine_set_lora",
     "dia_seg_mlp", "dia_seg_workspace_bytes", "dia_seg_workspace_control_bytes", "dia_seg_slots", "dia_seg_supported", "dia_seg_error",
 )
 
@@ -175,6 +176,48 @@ class ScoreArgs(C.Structure):
     ]
 
 
+LORA_MAX_RANK, LORA_MAX_SEGS = 64, 3                     # DIA_LORA_MAX_RANK, DIA_LORA_MAX_SEGS
+
+
+class LoraSeg(C.Structure):
+    """dia_lora_seg: one adapted module; A / B / rank / scale are DEVICE tables indexed by adapter"""
+    _fields_ = [
+        ("col_off", C.c_int32), ("n_cols", C.c_int32), ("A", C.c_void_p), ("B", C.c_void_p), ("rank", C.c_void_p),
+        ("scale", C.c_void_p), ("max_rank", C.c_int32), ("_pad0", C.c_int32),
+    ]
+
+
+class LoraArgs(C.Structure):
+    """dia_lora_args: the low-rank correction of a SCALE_STORE projection's output (csrc/lora.hip)"""
+    _fields_ = [
+        ("x", C.c_void_p), ("ldx", C.c_int32), ("D", C.c_int32), ("gain", C.c_void_p), ("eps", C.c_float), ("M", C.c_int32),
+        ("row_slot", C.c_void_p), ("rows_per_slot", C.c_int32), ("n_slots", C.c_int32), ("adapter_of_slot", C.c_void_p),
+        ("n_adapters", C.c_int32), ("n_segs", C.c_int32), ("seg", LoraSeg * LORA_MAX_SEGS),
+        ("out", C.c_void_p), ("ldo", C.c_int32), ("_pad0", C.c_int32),
+    ]
+
+
+class LoraCrossKvArgs(C.Structure):
+    """dia_lora_crosskv_args: the same correction added into the cross K/V caches"""
+    _fields_ = [
+        ("x", C.c_void_p), ("ldx", C.c_int32), ("D", C.c_int32), ("gain", C.c_void_p), ("eps", C.c_float), ("M", C.c_int32),
+        ("row_b", C.c_void_p), ("seg_off", C.c_void_p), ("adapter_of_slot", C.c_void_p), ("n_slots", C.c_int32),
+        ("n_adapters", C.c_int32), ("k", LoraSeg), ("v", LoraSeg), ("kc", C.c_void_p), ("vc", C.c_void_p),
+        ("kv_dtype", C.c_int32), ("kv_heads", C.c_int32), ("kv_cap", C.c_int32), ("kv_batch_index", C.c_int32),
+        ("kv_vblocked", C.c_int32), ("rope_rows", C.c_int32), ("kv_plane_stride", C.c_int64),
+        ("cos_t", C.c_void_p), ("sin_t", C.c_void_p),
+    ]
+
+
+class LoraLayer(C.Structure):
+    _fields_ = [("q", LoraSeg), ("k", LoraSeg), ("v", LoraSeg), ("cq", LoraSeg)]
+
+
+class LoraStep(C.Structure):
+    """dia_lora_step: what dia_engine_set_lora takes beside the engine's description"""
+    _fields_ = [("n_layer", C.c_int32), ("n_adapters", C.c_int32), ("layers", C.POINTER(LoraLayer)), ("adapter_of_slot", C.c_void_p)]
+
+
 class DecLayer(C.Structure):
     _fields_ = [
         ("w_qkv", C.c_void_p), ("w_o", C.c_void_p), ("w_cq", C.c_void_p), ("w_co", C.c_void_p),
@@ -294,6 +337,9 @@ def lib() -> C.CDLL:
     L.dia_engine_set_mxfp4.argtypes = [C.c_void_p, C.POINTER(Mxfp4Streams)]
     L.dia_score.argtypes = [C.POINTER(ScoreArgs), C.c_void_p]
     L.dia_engine_set_score.argtypes = [C.c_void_p, C.POINTER(ScoreArgs)]
+    L.dia_lora_apply.argtypes = [C.POINTER(LoraArgs), C.c_void_p]
+    L.dia_lora_crosskv.argtypes = [C.POINTER(LoraCrossKvArgs), C.c_void_p]
+    L.dia_engine_set_lora.argtypes = [C.c_void_p, C.POINTER(LoraStep)]
     L.dia_seg_mlp.argtypes = [C.POINTER(SegArgs), C.c_void_p]
     L.dia_seg_workspace_bytes.restype = C.c_int64
     L.dia_seg_workspace_control_bytes.restype = C.c_int64

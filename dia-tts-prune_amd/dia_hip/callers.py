@@ -100,9 +100,21 @@ def generate_long_codes(dia, text: str, *, chunk_size: int = 0, max_new_tokens: 
     return out
 
 
+def _plan_adapters(adapter, n: int):
+    """adapter= of the chunk-plan callers: None, one name for every chunk, or one entry per chunk (None = the base model)"""
+    if adapter is None or isinstance(adapter, (str, int)):
+        return None if adapter is None else [adapter] * n
+    names = list(adapter)
+    if len(names) == 1:
+        names = names * n
+    if len(names) != n:
+        raise ValueError(f"{len(names)} adapters for a plan of {n} chunks")
+    return names
+
+
 def generate_chunks_codes(dia, text: str, *, slots: int = 8, chunk_size: int = 0, max_new_tokens: int = 3072, cfg_scale: float = 3.0,
                           temperature: float = 1.3, top_p: float = 0.95, cfg_filter_top_k: int = 35,
-                          seed: Optional[int] = None) -> List[np.ndarray]:
+                          seed: Optional[int] = None, adapter=None) -> List[np.ndarray]:
     """The same chunk plan WITHOUT the chain: every batch of chunks is an independent utterance (no prompt), so they share
     `slots` slots of one continuously batched session (Dia.generate_batch(slots=N)) instead of running one after the other.
     A chain stays sequential (generate_long_codes): batch i + 1 needs the codes of batch i."""
@@ -112,13 +124,14 @@ def generate_chunks_codes(dia, text: str, *, slots: int = 8, chunk_size: int = 0
     T_cap = dia.config.data.audio_length
     out = dia.generate_batch([bt for bt, _ in plan], max_tokens=[min(T_cap, 1 + budget) for _, budget in plan], cfg_scale=cfg_scale,
                              temperature=temperature, top_p=top_p, cfg_filter_top_k=cfg_filter_top_k,
-                             seeds=None if seed is None else [seed + i for i in range(len(plan))], slots=slots)
+                             seeds=None if seed is None else [seed + i for i in range(len(plan))], slots=slots,
+                             adapters=_plan_adapters(adapter, len(plan)))
     return [c for c in out if c.shape[-1] > 0]
 
 
 def stream_chunks_codes(dia, text: str, *, slots: int = 8, chunk: int = 16, chunk_size: int = 0, max_new_tokens: int = 3072,
                         cfg_scale: float = 3.0, temperature: float = 1.3, top_p: float = 0.95, cfg_filter_top_k: int = 35,
-                        seed: Optional[int] = None):
+                        seed: Optional[int] = None, adapter=None):
     """generate_chunks_codes through Dia.stream_frames: the same plan, seeds and slots, but the frames of every batch of the plan
     arrive while it is generated — yields (plan index, start frame, codes [1, C, n], final).  Joining each batch's chunks and
     dropping the empty batches gives the list generate_chunks_codes returns."""
@@ -128,7 +141,8 @@ def stream_chunks_codes(dia, text: str, *, slots: int = 8, chunk: int = 16, chun
     T_cap = dia.config.data.audio_length
     yield from dia.stream_frames([bt for bt, _ in plan], slots, max_tokens=[min(T_cap, 1 + budget) for _, budget in plan],
                                  cfg_scale=cfg_scale, temperature=temperature, top_p=top_p, cfg_filter_top_k=cfg_filter_top_k,
-                                 seeds=None if seed is None else [seed + i for i in range(len(plan))], chunk=chunk)
+                                 seeds=None if seed is None else [seed + i for i in range(len(plan))], chunk=chunk,
+                                 adapters=_plan_adapters(adapter, len(plan)))
 
 
 def generate_long(dia, text: str, **kw) -> Optional[np.ndarray]:

@@ -17,7 +17,7 @@ from __future__ import annotations
 import ctypes as C
 from dataclasses import dataclass
 from functools import partial
-from typing import Dict, List, Optional, Sequence
+from typing import Dict, List, Optional, Sequence, Union
 
 import numpy as np
 import torch
@@ -481,6 +481,7 @@ class Request:
     top_p: float = 0.95
     top_k: int = 35
     audio_prompt: Optional[np.ndarray] = None      # codes [Tp, C]; the prompt rows are replayed through the decode step
+    adapter: Optional[Union[str, int]] = None      # name or index in the session's AdapterBank; None = the base model
 
 
 @dataclass
@@ -502,13 +503,18 @@ class DecodeSession:
                  teacher_tokens: Optional[Sequence[np.ndarray]] = None, stream: Optional[torch.cuda.Stream] = None,
                  s_cap: Optional[int] = None, audio_prompts: Optional[Sequence[Optional[np.ndarray]]] = None,
                  prompt_prefill: str = "auto", attention: str = "auto", score: bool = False,
-                 _slotted: bool = False):
+                 adapters=None, adapter_ids: Optional[Sequence[Union[None, str, int]]] = None, _slotted: bool = False):
         """audio_prompts: per utterance None or int codes [Tp, C] (reference model.py:311-353).  The prompt
         rows are replayed through the decode step before sampling starts (semantics: oracle.generate), or — with
         bf16 caches — prefilled as one packed MFMA batch; prompt_prefill="replay" forces the replay.
         attention="valu" keeps bf16 V caches row-major and runs the VALU attention kernel (comparison runs).
         score=True (with teacher_tokens): every step also reduces its logits to the log-probability of the forced row, on the
-        device (dia_score; DESIGN.md "Scoring"); scores_host() downloads the [B, T, C, 3] result once at the end."""
+        device (dia_score; DESIGN.md "Scoring"); scores_host() downloads the [B, T, C, 3] result once at the end.
+        adapters: a lora.AdapterBank whose adapters stay UNMERGED beside the base weights (DESIGN.md "Per-request adapters");
+        adapter_ids[b] = name or index of utterance b's adapter, None = base model.  The bank is fixed from here on.  Such a session
+        replays audio prompts through the decode step (no batched prompt prefill), and refuses a compacted model and seg="on"."""
+        if adapter_ids is not None and adapters is None:
+            raise ValueError("adapter_ids needs adapters= (an AdapterBank)")
         if score and (teacher_tokens is None or _slotted):
             raise ValueError("score=True scores teacher-forced rows of a closed batch: pass teacher_tokens (and no slots)")
         if prompt_prefill not in ("auto", "replay") or attention not in ("auto", "valu"):
@@ -672,11 +678,50 @@ class DecodeSession:
         self.slotted = bool(_slotted)
         if self.slotted:
             self._init_slots()
+        self.adapters = adapters
+        if adapters is not None:
+            self._init_adapters(adapter_ids)
         # teacher-forced scoring: lp_cond, lp_cfg, H_cfg per row and channel; NaN = no step has scored this position
         self.scores = torch.full((B, self.T, self.C, 3), float("nan"), dtype=torch.float32, device=dev) if score else None
         self._engine = C.c_void_p()
         self._build_engine()
         self.prefilled = self.slotted            # slots are prefilled one by one, at admission
+
+    # ------------------------------------------------------------------ per-request adapters (DESIGN.md "Per-request adapters")
+    def _init_adapters(self, adapter_ids):
+        """adapter_of_slot on the device (-1 = base model) + the bank's tables; everything the unmerged path cannot serve raises here"""
+        w, bank = self.w, self.adapters
+        if w.compacted:
+            raise hb.DiaHipError("adapters=: a compacted (structured-pruned) checkpoint permutes the columns the corrections address; "
+                                 "load it with compact='off' or merge the adapter at load (adapter_path=)")
+        if w.seg_layers:
+            raise hb.DiaHipError("adapters=: the persistent MLP segments run the q/k/v projection inside their launch (seg must be 'off')")
+        if bank.cfg.model != self.cfg.model:
+            raise hb.DiaHipError("adapters=: the bank was built for another model configuration")
+        if adapter_ids is not None and (self.slotted or len(adapter_ids) != self.B):
+            raise ValueError("adapter_ids: one entry per utterance of a closed batch (slot sessions take Request.adapter)")
+        ids = [bank.index_of(a) for a in (adapter_ids if adapter_ids is not None else [None] * self.B)]
+        bank.freeze()
+        if bank.arena.device != self.x.device:       # (tensors' own devices: "cuda" and "cuda:0" name the same one)
+            raise hb.DiaHipError(f"adapters=: the bank lives on {bank.arena.device}, the session on {self.x.device}")
+        self._adapter_host = np.asarray(ids, dtype=np.int32)
+        self.adapter_of_slot = torch.from_numpy(self._adapter_host.copy()).to(self.dev)
+
+    def _push_adapter_slots(self):
+        """the host's adapter_of_slot -> the device, in stream order (pinned + asynchronous, like every table of an admission)"""
+        pin = torch.from_numpy(self._adapter_host.copy()).pin_memory()
+        self._pinned.append(pin)
+        with torch.cuda.stream(self.stream):
+            self.adapter_of_slot.copy_(pin, non_blocking=True)
+
+    def _zero_ranks(self) -> torch.Tensor:
+        if getattr(self, "_zero_rank_t", None) is None:
+            self._zero_rank_t = torch.zeros(len(self.adapters), dtype=torch.int32, device=self.dev)
+        return self._zero_rank_t
+
+    def _lora_common(self, a, x, ldx, D, gain, M):
+        a.x, a.ldx, a.D, a.gain, a.eps, a.M = x, ldx, D, hb.ptr(gain), float(self.cfg.model.normalization_layer_epsilon), M
+        a.adapter_of_slot, a.n_slots, a.n_adapters = hb.ptr(self.adapter_of_slot), self.B, len(self.adapters)
 
     # ------------------------------------------------------------------ engine descriptor
     def _embed_args(self) -> hb.EmbedArgs:
@@ -774,6 +819,15 @@ class DecodeSession:
             sc.cfg_scale, sc.eos, sc.pad, sc.bos = sp.cfg_scale, sp.eos, sp.pad, sp.bos
             sc.tokens, sc.cur, sc.first_step, sc.fsm, sc.out = sp.tokens, sp.cur, sp.first_step, sp.fsm, hb.ptr(self.scores)
             hb.check(hb.lib().dia_engine_set_score(self._engine, C.byref(sc)), "dia_engine_set_score")
+        if self.adapters is not None:                                       # unmerged adapters: two more launches per layer
+            bank, QH, KVH = self.adapters, d.gqa_query_heads, d.kv_heads
+            ll = (hb.LoraLayer * n)()                                       # (the engine copies the array)
+            for i in range(n):
+                ll[i].q, ll[i].k = bank.seg(("self", i, "q"), 0), bank.seg(("self", i, "k"), QH * HEAD_DIM)
+                ll[i].v, ll[i].cq = bank.seg(("self", i, "v"), (QH + KVH) * HEAD_DIM), bank.seg(("cross", i, "q"), 0)
+            ls = hb.LoraStep(n_layer=n, n_adapters=len(bank), layers=C.cast(ll, C.POINTER(hb.LoraLayer)),
+                             adapter_of_slot=hb.ptr(self.adapter_of_slot))
+            hb.check(hb.lib().dia_engine_set_lora(self._engine, C.byref(ls)), "dia_engine_set_lora")
 
     def close(self):
         """Tear the engine down: the stream is drained first (queued graph replays read the executable graph's own
@@ -823,6 +877,8 @@ class DecodeSession:
         eps = float(cfg.model.normalization_layer_epsilon)
         utt = [int(b) for b, _ in pairs]
         lens = [int(len(t)) for _, t in pairs]
+        # unmerged adapters: the corrections of the encoder's q/k/v and of the cross K/V caches, for the utterances that have one
+        bank = self.adapters if self.adapters is not None and any(self._adapter_host[b] >= 0 for b in utt) else None
         offs, tot, row_seg = pack_segments(lens)              # whole 32-key blocks per utterance (blocked V planes)
         with torch.cuda.stream(self.stream):
             if tot > 0:
@@ -887,6 +943,15 @@ class DecodeSession:
                     nq = 3 * Hl * HEAD_DIM
                     if Hl > 0:
                         gemm(px, ekt, EL["qkv"], hb.EPI_SCALE_STORE, ssq_in=True, out=qkv, ldo=nq)
+                        segs = [bank.seg(("enc", i, p_), j * Hl * HEAD_DIM) for j, p_ in enumerate("qkv")] if bank is not None else []
+                        segs = [s_ for s_ in segs if s_.n_cols]
+                        if segs:                     # x is still the row this GEMM's input was normed from (g_sa), o_proj has not run
+                            la = hb.LoraArgs()
+                            self._lora_common(la, hb.ptr(x), E, E, EL["g_sa"], Mp)
+                            la.row_slot, la.rows_per_slot, la.n_segs, la.out, la.ldo = hb.ptr(row_b), 1, len(segs), hb.ptr(qkv), nq
+                            for j, s_ in enumerate(segs):
+                                la.seg[j] = s_
+                            hb.check(L.dia_lora_apply(C.byref(la), st), "dia_lora_apply")
                         ea_ = hb.EncAttnArgs()
                         ea_.qkv, ea_.ldq, ea_.q_off, ea_.k_off, ea_.v_off = hb.ptr(qkv), nq, 0, Hl * HEAD_DIM, 2 * Hl * HEAD_DIM
                         ea_.heads, ea_.rows = Hl, Mp
@@ -918,6 +983,25 @@ class DecodeSession:
                     for i, DL in enumerate(w.dec_layers):
                         gemm(px, ekt, DL["ckv"], hb.EPI_CROSSKV, ssq_in=True, kv=cross_kv(self.k_cross[i], self.v_cross[i]),
                              strip_map=DL["smap_ckv"], row_map=(row_b, seg_off))
+                for i in range(len(w.dec_layers) if bank is not None else 0):
+                    # RoPE is linear: RoPE(dK) and dV are added to what the CROSSKV epilogue stored, for the rows of these utterances
+                    # only (row_b).  x holds the encoder's last residual rows, encoder.norm is the consumer's weight
+                    ks, vs = bank.seg(("cross", i, "k"), 0), bank.seg(("cross", i, "v"), 0)
+                    if not (ks.n_cols or vs.n_cols):
+                        continue
+                    ca = hb.LoraCrossKvArgs()
+                    self._lora_common(ca, hb.ptr(x), E, E, w.enc_norm, Mp)
+                    ca.row_b, ca.seg_off = hb.ptr(row_b), hb.ptr(seg_off)
+                    for s_ in (ks, vs):              # a module no adapter touches: an all-zero rank table of the right width
+                        if not s_.n_cols:
+                            o_ = ks if ks.n_cols else vs
+                            s_.n_cols, s_.A, s_.B, s_.scale = d.cross_query_heads * HEAD_DIM, o_.A, o_.B, o_.scale
+                            s_.rank = hb.ptr(self._zero_ranks())
+                    ca.k, ca.v = ks, vs
+                    (ca.kc, ca.vc, ca.kv_dtype, ca.kv_heads, ca.kv_cap, ca.kv_batch_index, ca.kv_vblocked, ca.kv_plane_stride, ca.cos_t,
+                     ca.sin_t) = cross_kv(self.k_cross[i], self.v_cross[i])
+                    ca.rope_rows = w.cos_t.shape[0]
+                    hb.check(L.dia_lora_crosskv(C.byref(ca), st), "dia_lora_crosskv")
                 if keep_encoder_out:
                     for i in live:
                         Lb, o = lens[i], offs[i]
@@ -927,8 +1011,9 @@ class DecodeSession:
     # ------------------------------------------------------------------ audio-prompt prefill, batched
     def _prompt_prefill_batched(self) -> bool:
         """The batched MFMA prefill of the prompt rows needs bf16 caches with the blocked V layout and an
-        uncompacted decoder; everything else replays the prompt rows through the decode step (first_step)."""
-        return (any(f > 2 for f in self.first_steps) and self.v_blocked == 1 and self.kv_code == hb.KV_BF16 and not self.w.compacted and not self.teacher
+        uncompacted decoder; everything else replays the prompt rows through the decode step (first_step).  A session with
+        adapters= always replays: the batched prefill's projections carry no adapter correction, the decode step's do."""
+        return (self.adapters is None and any(f > 2 for f in self.first_steps) and self.v_blocked == 1 and self.kv_code == hb.KV_BF16 and not self.w.compacted and not self.teacher
                 and self.prompt_prefill != "replay" and self.w.weight_planes == 1)
 
     def _prompt_prefill(self, st):
@@ -1130,14 +1215,16 @@ class DecodeSession:
     def open(cls, w: DeviceWeights, slots: int, *, s_cap: Optional[int] = None, kv_dtype: str = "bf16",
              max_tokens: Optional[int] = None, ignore_eos: bool = False, stream: Optional[torch.cuda.Stream] = None,
              cfg_scale: float = 3.0, temperature: float = 1.3, top_p: float = 0.95, top_k: int = 35,
-             attention: str = "auto", stream_cap: Optional[int] = None) -> "DecodeSession":
+             attention: str = "auto", stream_cap: Optional[int] = None, adapters=None) -> "DecodeSession":
         """A session of `slots` PARKED slots for a stream of requests: admit() puts a request into a free slot between two decode
         steps, the step graph (captured once) serves whatever the slots hold, retire() parks a finished one; serve() is the
         driver loop.  Cross caches are sized for texts of `s_cap` bytes (default: the encoder's text_length), the noise buffer for
         `max_tokens` steps per slot (default: audio_length) — a request's own max_tokens may be smaller, not larger.  The sampling
         arguments are what a parked slot holds until its first admission; every request brings its own.
         stream_cap=N adds the buffers of frame streaming (stream_iter): a staging area of N frames per slot on the device, two
-        pinned host copies of it, a side stream for the copies.  None: no such buffer exists and nothing new is launched."""
+        pinned host copies of it, a side stream for the copies.  None: no such buffer exists and nothing new is launched.
+        adapters: a lora.AdapterBank; each Request then names its adapter (Request.adapter), and the admission writes the slot's
+        entry of adapter_of_slot — the step graph is captured once, with the corrections' launches in it."""
         if int(slots) < 1:
             raise ValueError("slots must be >= 1")
         if stream_cap is not None and int(stream_cap) < 1:
@@ -1150,7 +1237,7 @@ class DecodeSession:
         empty = np.zeros((0,), dtype=np.int32)
         s = cls(w, [empty] * int(slots), kv_dtype=kv_dtype, max_tokens=max_tokens, cfg_scale=cfg_scale, temperature=temperature,
                 top_p=top_p, top_k=top_k, ignore_eos=ignore_eos, stream=stream, s_cap=_ceil(cap, 32), attention=attention,
-                _slotted=True)
+                adapters=adapters, _slotted=True)
         s.text_cap = cap                           # (the caches hold whole 32-key blocks; requests are held to what was asked for)
         if stream_cap is not None:
             s._init_stream(int(stream_cap))
@@ -1192,7 +1279,13 @@ class DecodeSession:
                 raise ValueError(f"Unexpected audio_prompt shape: {pr.shape}. Expected [T, C] or [1, T, C].")   # model.py:316
             if 1 + pr.shape[0] + self.max_delay > self.T:
                 raise ValueError(f"audio prompt of {pr.shape[0]} frames does not fit audio_length {self.T}")
-        return Request(ids, r.seed, mt, float(r.cfg_scale), float(r.temperature), float(r.top_p), int(r.top_k or 0), pr)
+        ad = None
+        if r.adapter is not None:
+            if self.adapters is None:
+                raise ValueError("the request names an adapter but the session was opened without adapters=")
+            ad = self.adapters.index_of(r.adapter)
+            ad = None if ad < 0 else ad
+        return Request(ids, r.seed, mt, float(r.cfg_scale), float(r.temperature), float(r.top_p), int(r.top_k or 0), pr, ad)
 
     def admit(self, requests: Sequence) -> List[int]:
         """Put each request (a Request, or bare text ids with the defaults) into a free slot; returns the slot ids.  Enqueues, on the
@@ -1232,6 +1325,10 @@ class DecodeSession:
         """the device side of an admission, in stream order: encoder + cross-K/V, dia_slot_admit, first embedding of these slots"""
         L, n = hb.lib(), len(pairs)
         st = C.c_void_p(self.stream.cuda_stream)
+        if self.adapters is not None:            # the slots' adapters first: the encoder pass below already reads them
+            for b, r in pairs:
+                self._adapter_host[b] = -1 if r.adapter is None else int(r.adapter)
+            self._push_adapter_slots()
         self._encode([(b, r.text_ids) for b, r in pairs])
         ld = max(p.shape[0] for p, _ in pre)
         n_pre = n * ld * self.C
@@ -1281,6 +1378,9 @@ class DecodeSession:
     def _enqueue_retire(self, part):
         a = self._slot_args(len(part), part)
         hb.check(hb.lib().dia_slot_retire(C.byref(a), C.c_void_p(self.stream.cuda_stream)), "dia_slot_retire")
+        if self.adapters is not None:            # a parked slot runs the base model
+            self._adapter_host[list(part)] = -1
+            self._push_adapter_slots()
 
     def _steps_left(self, b: int) -> int:
         """decode steps a live slot can still run: it starts at step 1 and its last step is max_tokens - 1"""

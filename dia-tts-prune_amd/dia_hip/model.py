@@ -51,6 +51,7 @@ class GenerationRequest:
     seed: Optional[int] = None
     audio_prompt: Optional[np.ndarray] = None
     audio_prompt_text: Optional[str] = None
+    adapter: Optional[Union[str, int]] = None       # an adapter of Dia.load_adapters (name or index); None = the call's / the base model
 
 
 def _nth(arg, i):
@@ -95,6 +96,7 @@ class Dia:
         self.last_codes: Optional[np.ndarray] = None
         self.weights_rounded = False
         self.weights_exact_planes = False
+        self.adapters = None                            # lora.AdapterBank of load_adapters(): adapters that stay unmerged, per request
         hb.lib()                                        # fail now, not at first generate()
 
     # ------------------------------------------------------------------ loaders
@@ -205,21 +207,47 @@ class Dia:
             raise RuntimeError(f"Failed to load DAC model: {e}") from e
         self.dac_model = m
 
+    def load_adapters(self, adapters: Dict[str, str]) -> List[int]:
+        """Load LoRA adapter directories {name: dir} into the model's adapter bank, UNMERGED: one base model then serves every one
+        of them, per request (``adapter=`` / ``adapters=`` of the generate and score calls; DESIGN.md "Per-request adapters").
+        Only q_proj / k_proj / v_proj adapters (the reference's default target set is q_proj v_proj) of rank <= 64; anything else
+        raises and can be merged at load instead (``adapter_path=``, one voice per process).  Call it before the first generation
+        that uses an adapter: the bank is fixed once a session has been opened with it.  Returns the adapters' indices."""
+        from .lora import AdapterBank
+        if self.model is None:
+            raise RuntimeError("no weights loaded")
+        if self.adapters is None:
+            self.adapters = AdapterBank(self.config, self.device)
+        return [self.adapters.add(name, path) for name, path in adapters.items()]
+
+    def _bank_for(self, wanted: Sequence) -> Optional["object"]:
+        """the bank when any of `wanted` names an adapter (sessions without one are the sessions of a model without a bank)"""
+        if all(a is None for a in wanted):
+            return None
+        if self.adapters is None:
+            raise ValueError("adapter= given but no adapter is loaded: call Dia.load_adapters({name: dir}) first")
+        for a in wanted:
+            self.adapters.index_of(a)               # unknown names raise here, before a session exists
+        return self.adapters
+
     # ------------------------------------------------------------------ generation
     def _kv_dtype(self) -> str:
         return "f32" if self.compute_dtype == torch.float32 else "bf16"
 
     def _run(self, texts: Sequence[str], max_tokens, cfg_scale, temperature, top_p, top_k,
              seeds: Optional[Sequence[Optional[int]]], verbose: bool, ignore_eos: bool = False,
-             use_graph: bool = True, audio_prompts: Optional[Sequence[Optional[np.ndarray]]] = None) -> List[UtteranceResult]:
+             use_graph: bool = True, audio_prompts: Optional[Sequence[Optional[np.ndarray]]] = None,
+             adapters: Optional[Sequence] = None) -> List[UtteranceResult]:
         if self.model is None:
             raise RuntimeError("no weights loaded")
         ids = [encode_text(t, self.config) for t in texts]
+        adapters = list(adapters) if adapters is not None else [None] * len(ids)
+        bank = self._bank_for(adapters)
         t0 = time.time()
         with torch.cuda.device(self.device):
             s = DecodeSession(self.model, ids, kv_dtype=self._kv_dtype(), max_tokens=max_tokens, cfg_scale=cfg_scale,
                               temperature=temperature, top_p=top_p, top_k=top_k, seeds=seeds, ignore_eos=ignore_eos,
-                              audio_prompts=audio_prompts)
+                              audio_prompts=audio_prompts, adapters=bank, adapter_ids=adapters if bank is not None else None)
             try:
                 s.prefill()
                 s.sync()
@@ -236,8 +264,11 @@ class Dia:
                 s.close()
         return res
 
-    def _requests(self, items, max_tokens, cfg_scale, temperature, top_p, top_k, seeds, audio_prompts, audio_prompt_texts) -> List[Request]:
+    def _requests(self, items, max_tokens, cfg_scale, temperature, top_p, top_k, seeds, audio_prompts, audio_prompt_texts,
+                  adapters=None) -> List[Request]:
         """texts or GenerationRequests + scalar-or-per-request arguments -> engine requests"""
+        if adapters is not None and len(adapters) != len(items):
+            raise ValueError(f"adapters: {len(adapters)} entries for {len(items)} requests (one per request, None = the base model)")
         out = []
         for i, it in enumerate(items):
             g = it if isinstance(it, GenerationRequest) else GenerationRequest(str(it))
@@ -252,19 +283,21 @@ class Dia:
             out.append(Request(encode_text(effective_text(g.text, ptext), self.config), seed=pick(g.seed, seeds),
                                max_tokens=None if mt is None else int(mt), cfg_scale=float(pick(g.cfg_scale, cfg_scale)),
                                temperature=float(pick(g.temperature, temperature)), top_p=float(pick(g.top_p, top_p)),
-                               top_k=int(pick(g.cfg_filter_top_k, top_k) or 0), audio_prompt=prompt))
+                               top_k=int(pick(g.cfg_filter_top_k, top_k) or 0), audio_prompt=prompt,
+                               adapter=g.adapter if g.adapter is not None else (None if adapters is None else adapters[i])))
         return out
 
     # ------------------------------------------------------------------ scoring
     @torch.inference_mode()
     def score_batch(self, texts: Sequence[str], codes_list: Sequence, *, audio_prompts: Optional[Sequence] = None,
                     cfg_scale: float = 3.0, audio_prompt_texts: Optional[Sequence[Optional[str]]] = None,
-                    use_graph: bool = True) -> List["ScoreResult"]:
+                    use_graph: bool = True, adapters: Optional[Sequence] = None) -> List["ScoreResult"]:
         """Teacher-forced log-likelihood of known audio codes under the loaded checkpoint, up to 8 utterances of any lengths in
         one decode session — the session generate() would use: this model's K/V dtype, weight format, pruning and compaction.
         codes_list[b]: codec frames [T, C] or a delayed token buffer [rows, C] (score.teacher_rows).  The rows are forced through
         rows - 1 decode steps and every step's logits are reduced on the device (DESIGN.md "Scoring"); with an audio prompt only
-        the rows behind it are scored.  Returns one ScoreResult per utterance (nats; no sampling happens)."""
+        the rows behind it are scored.  Returns one ScoreResult per utterance (nats; no sampling happens).
+        adapters: per utterance the name / index of an adapter of load_adapters(), None = the base model."""
         from .score import check_prompt_rows, summarise, teacher_rows, valid_mask
 
         if self.model is None:
@@ -281,9 +314,14 @@ class Dia:
         if mt > self.config.data.audio_length:
             raise ValueError(f"{mt} token rows do not fit audio_length {self.config.data.audio_length}")
         ids = [encode_text(effective_text(t, a), self.config) for t, a in zip(texts, apt)]
+        adapters = list(adapters) if adapters is not None else [None] * n
+        if len(adapters) != n:
+            raise ValueError("score_batch: one adapter entry per text")
+        bank = self._bank_for(adapters)
         with torch.cuda.device(self.device):
             s = DecodeSession(self.model, ids, kv_dtype=self._kv_dtype(), max_tokens=mt, cfg_scale=cfg_scale, temperature=0.0,
-                              teacher_tokens=rows, audio_prompts=prompts, score=True)
+                              teacher_tokens=rows, audio_prompts=prompts, score=True, adapters=bank,
+                              adapter_ids=adapters if bank is not None else None)
             try:
                 s.prefill()
                 s.decode(mt - 1, use_graph=use_graph)
@@ -293,26 +331,31 @@ class Dia:
                 s.close()
         return [summarise(sc[b, : r.shape[0]], valid_mask(r, f, self.config.data)) for b, (r, f) in enumerate(zip(rows, first))]
 
-    def score(self, text: str, codes, *, audio_prompt=None, cfg_scale: float = 3.0, audio_prompt_text: Optional[str] = None) -> "ScoreResult":
+    def score(self, text: str, codes, *, audio_prompt=None, cfg_scale: float = 3.0, audio_prompt_text: Optional[str] = None,
+              adapter: Optional[Union[str, int]] = None) -> "ScoreResult":
         """score_batch for one utterance"""
         return self.score_batch([text], [codes], audio_prompts=None if audio_prompt is None else [audio_prompt], cfg_scale=cfg_scale,
-                                audio_prompt_texts=[audio_prompt_text])[0]
+                                audio_prompt_texts=[audio_prompt_text], adapters=[adapter])[0]
 
     @torch.inference_mode()
     def generate_stream(self, requests_or_texts: Sequence[Union[str, GenerationRequest]], slots: int = 8,
                         max_tokens=None, cfg_scale=3.0, temperature=1.3, top_p=0.95, cfg_filter_top_k=35,
                         seeds: Optional[Sequence[Optional[int]]] = None, ignore_eos: bool = False,
                         audio_prompts: Optional[Sequence[Optional[np.ndarray]]] = None,
-                        audio_prompt_texts: Optional[Sequence[Optional[str]]] = None, poll: int = 64, s_cap: Optional[int] = None):
+                        audio_prompt_texts: Optional[Sequence[Optional[str]]] = None, poll: int = 64, s_cap: Optional[int] = None,
+                        adapters: Optional[Sequence] = None):
         """Continuous batching: any number of utterances through `slots` slots of ONE decode session — a finished utterance's slot
         is refilled from the queue between two decode steps, so the batch stays full while requests last.  Yields
         (request index, codec input [1, C, T']) as utterances finish.  The sampling arguments are defaults: each may be a per-request
         sequence, and a GenerationRequest carries its own.  Every utterance's tokens are those of generating it alone with its
-        seed (compute_dtype float32: bit for bit)."""
+        seed (compute_dtype float32: bit for bit).  adapters: per request the name / index of an adapter of load_adapters()
+        (None = the base model); a GenerationRequest's own `adapter` goes first."""
         if self.model is None:
             raise RuntimeError("no weights loaded")
         items = list(requests_or_texts)
-        reqs = self._requests(items, max_tokens, cfg_scale, temperature, top_p, cfg_filter_top_k, seeds, audio_prompts, audio_prompt_texts)
+        reqs = self._requests(items, max_tokens, cfg_scale, temperature, top_p, cfg_filter_top_k, seeds, audio_prompts, audio_prompt_texts,
+                              adapters)
+        bank = self._bank_for([r.adapter for r in reqs])
         if not reqs:
             return
         cap = max([r.max_tokens for r in reqs if r.max_tokens is not None] or [self.config.data.audio_length])
@@ -322,7 +365,7 @@ class Dia:
             s_cap = max(32, max(len(r.text_ids) for r in reqs))
         with torch.cuda.device(self.device):
             s = DecodeSession.open(self.model, min(int(slots), len(reqs)), s_cap=min(int(s_cap), self.config.data.text_length),
-                                   kv_dtype=self._kv_dtype(), max_tokens=cap, ignore_eos=ignore_eos)
+                                   kv_dtype=self._kv_dtype(), max_tokens=cap, ignore_eos=ignore_eos, adapters=bank)
             try:
                 for i, res in s.serve_iter(reqs, poll=poll):
                     yield i, codes_for_codec(res.codes, self.config)
@@ -335,16 +378,19 @@ class Dia:
                       seeds: Optional[Sequence[Optional[int]]] = None, ignore_eos: bool = False,
                       audio_prompts: Optional[Sequence[Optional[np.ndarray]]] = None,
                       audio_prompt_texts: Optional[Sequence[Optional[str]]] = None, s_cap: Optional[int] = None,
-                      chunk: int = 16, stream_cap: Optional[int] = None, lag: int = 1):
+                      chunk: int = 16, stream_cap: Optional[int] = None, lag: int = 1, adapters: Optional[Sequence] = None):
         """generate_stream that hands the codec input out WHILE the utterances run: yields (request index, start frame,
         codes [1, C, n], final) every `chunk` decode steps — frames [start, start + n) of what generate_stream would yield for
         that request at the end, final exactly once per request (possibly with n = 0).  A frame is final max_delay steps after it
         was sampled (DESIGN.md "Frame streaming").  stream_cap: frames per slot one hand-over can carry (default 4 * chunk);
-        lag = 1 keeps the next chunk queued on the GPU while this one is read, lag = 0 reads each chunk as soon as it is queued."""
+        lag = 1 keeps the next chunk queued on the GPU while this one is read, lag = 0 reads each chunk as soon as it is queued.
+        adapters: as generate_stream."""
         if self.model is None:
             raise RuntimeError("no weights loaded")
         items = list(requests_or_texts)
-        reqs = self._requests(items, max_tokens, cfg_scale, temperature, top_p, cfg_filter_top_k, seeds, audio_prompts, audio_prompt_texts)
+        reqs = self._requests(items, max_tokens, cfg_scale, temperature, top_p, cfg_filter_top_k, seeds, audio_prompts, audio_prompt_texts,
+                              adapters)
+        bank = self._bank_for([r.adapter for r in reqs])
         if not reqs:
             return
         cap = max([r.max_tokens for r in reqs if r.max_tokens is not None] or [self.config.data.audio_length])
@@ -355,7 +401,7 @@ class Dia:
         with torch.cuda.device(self.device):
             s = DecodeSession.open(self.model, min(int(slots), len(reqs)), s_cap=min(int(s_cap), self.config.data.text_length),
                                    kv_dtype=self._kv_dtype(), max_tokens=cap, ignore_eos=ignore_eos,
-                                   stream_cap=4 * int(chunk) if stream_cap is None else int(stream_cap))
+                                   stream_cap=4 * int(chunk) if stream_cap is None else int(stream_cap), adapters=bank)
             try:
                 yield from s.stream_iter(reqs, chunk=chunk, lag=lag)
             finally:
@@ -366,37 +412,40 @@ class Dia:
                        temperature: float = 1.3, top_p: float = 0.95, cfg_filter_top_k: int = 35,
                        seeds: Optional[Sequence[Optional[int]]] = None, verbose: bool = False,
                        ignore_eos: bool = False, audio_prompts: Optional[Sequence[Optional[np.ndarray]]] = None,
-                       audio_prompt_texts: Optional[Sequence[Optional[str]]] = None, slots: Optional[int] = None) -> List[np.ndarray]:
+                       audio_prompt_texts: Optional[Sequence[Optional[str]]] = None, slots: Optional[int] = None,
+                       adapters: Optional[Sequence] = None) -> List[np.ndarray]:
         """B utterances in one decode loop; returns the codec inputs [1, C, T'_b] per utterance.
         audio_prompts: per utterance None or codes [Tp, C]; audio_prompt_texts: their transcripts.
         slots=N: the utterances share N slots of a continuously batched session instead (generate_stream); the list returned is
-        the same."""
+        the same.  adapters: per utterance the name / index of an adapter of load_adapters(), None = the base model."""
+        if adapters is not None and len(adapters) != len(texts):
+            raise ValueError("generate_batch: one adapter entry per text")
         if slots is not None:
             out: List[Optional[np.ndarray]] = [None] * len(texts)
             for i, codes in self.generate_stream(texts, slots, max_tokens, cfg_scale, temperature, top_p, cfg_filter_top_k, seeds,
-                                                 ignore_eos, audio_prompts, audio_prompt_texts):
+                                                 ignore_eos, audio_prompts, audio_prompt_texts, adapters=adapters):
                 out[i] = codes
             return out
         apt = audio_prompt_texts or [None] * len(texts)
         eff = [effective_text(t, a) for t, a in zip(texts, apt)]
         res = self._run(eff, max_tokens, cfg_scale, temperature, top_p, cfg_filter_top_k, seeds, verbose, ignore_eos,
-                        audio_prompts=audio_prompts)
+                        audio_prompts=audio_prompts, adapters=adapters)
         return [codes_for_codec(r.codes, self.config) for r in res]
 
     @torch.inference_mode()
     def generate_codes(self, text: str, max_tokens: Optional[int] = None, cfg_scale: float = 3.0,
                        temperature: float = 1.3, top_p: float = 0.95, cfg_filter_top_k: int = 35,
-                       seed: Optional[int] = None, verbose: bool = False) -> Optional[np.ndarray]:
+                       seed: Optional[int] = None, verbose: bool = False, adapter: Optional[Union[str, int]] = None) -> Optional[np.ndarray]:
         out = self.generate_batch([text], max_tokens, cfg_scale, temperature, top_p, cfg_filter_top_k,
-                                  None if seed is None else [seed], verbose)
+                                  None if seed is None else [seed], verbose, adapters=[adapter])
         return out[0]
 
     @torch.inference_mode()
     def generate(self, text: str, max_tokens: Optional[int] = None, cfg_scale: float = 3.0, temperature: float = 1.3,
                  top_p: float = 0.95, use_torch_compile: bool = False, cfg_filter_top_k: int = 35,
                  audio_prompt: Union[str, torch.Tensor, None] = None, audio_prompt_text: Optional[str] = None,
-                 seed: Optional[int] = None, verbose: bool = False) -> Optional[np.ndarray]:
-        """reference model.py:631-846.  Failures inside generation are printed and turned into
+                 seed: Optional[int] = None, verbose: bool = False, adapter: Optional[Union[str, int]] = None) -> Optional[np.ndarray]:
+        """reference model.py:631-846.  ``adapter``: an adapter of load_adapters() for this call (None = the base model).  Failures inside generation are printed and turned into
         ``None`` exactly like the reference (model.py:729-733, 817-821, 841-845); ``use_torch_compile``
         is accepted and ignored (there is nothing to compile)."""
         if audio_prompt is not None and not audio_prompt_text:
@@ -418,7 +467,7 @@ class Dia:
         try:
             res = self._run([eff], max_tokens, cfg_scale, temperature, top_p, cfg_filter_top_k,
                             None if seed is None else [seed], verbose,
-                            audio_prompts=None if prompt is None else [prompt])[0]
+                            audio_prompts=None if prompt is None else [prompt], adapters=[adapter])[0]
         except Exception as e:
             print(f"Error during generation loop: {e}")
             import traceback

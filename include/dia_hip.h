@@ -694,6 +694,99 @@ int dia_engine_set_score(dia_engine* e, const dia_score_args* a);
 /* number of kernel launches in one decode step */
 int dia_engine_launches_per_step(const dia_engine* e);
 
+/* ------------------------------------------------------------------------------------------------
+ * Per-request LoRA adapters, unmerged (csrc/lora.hip; DESIGN.md "Per-request adapters").  The reference wraps the model with
+ * PEFT for ONE adapter per process (cli.py:166-174); here several adapters stay resident beside the base weights and every row
+ * of a projection's output receives the correction of the adapter its slot selected:
+ *   out[m][col_off + n] += scale[a] * sum_j B_a[j][n] * sum_k A_a[j][k] * xn[m][k],   a = adapter_of_slot[slot(m)],
+ * nothing for a < 0.  xn[m] = x[m] * gain * rsqrt(mean(x[m]^2) + eps) is rebuilt from the fp32 residual row, so the call does not
+ * depend on the activation format between the GEMMs.  Everything below is appended: no existing struct or entry point changed.
+ * ------------------------------------------------------------------------------------------------ */
+#define DIA_LORA_MAX_RANK 64
+#define DIA_LORA_MAX_SEGS 3
+/* One adapted module = one column range of the output.  The tables are DEVICE arrays indexed by adapter: A[a] -> fp32
+ * [rank[a]][D] (PEFT's lora_A.weight), B[a] -> fp32 [rank[a]][n_cols] (lora_B.weight transposed: the DenseGeneral order
+ * [in, out]), both 16-byte aligned, NULL or rank 0 = this adapter leaves the module alone; scale[a] = lora_alpha / r. */
+typedef struct {
+  int32_t col_off;             /* first output column, a multiple of 4 */
+  int32_t n_cols;              /* width, a multiple of 4 */
+  const float* const* A;       /* device [n_adapters] of device pointers */
+  const float* const* B;
+  const int32_t* rank;         /* device [n_adapters], each 0..DIA_LORA_MAX_RANK */
+  const float* scale;          /* device [n_adapters] */
+  int32_t max_rank;            /* the caller's statement of the largest entry of rank[]: above DIA_LORA_MAX_RANK -> DIA_E_ARG (the
+                                * kernel skips such an entry) */
+  int32_t _pad0;
+} dia_lora_seg;
+/* The SCALE_STORE sites (q/k/v of the decoder's and the encoder's self-attention, the cross-attention query): ONE launch, in
+ * stream order behind the projection's dia_gemm and before whatever reads `out`.  One workgroup per (row, segment); segments must
+ * not overlap.  D a multiple of 256, at most 2048.  DIA_E_ARG with a message for everything else that is refused. */
+typedef struct {
+  const float* x;              /* fp32 residual rows [M][ldx] the projection's input was normed from */
+  int32_t ldx;
+  int32_t D;
+  const float* gain;           /* the consumer's RMSNorm weight [D] */
+  float eps;
+  int32_t M;                   /* rows */
+  const int32_t* row_slot;     /* device [M]: slot (utterance) of row m, < 0 = skipped; NULL: slot = m / rows_per_slot */
+  int32_t rows_per_slot;       /* 2 for the decode step's rows 2b + {0, 1} */
+  int32_t n_slots;
+  const int32_t* adapter_of_slot;   /* device [n_slots]: adapter index or < 0 = base model */
+  int32_t n_adapters;
+  int32_t n_segs;              /* 1..DIA_LORA_MAX_SEGS */
+  dia_lora_seg seg[DIA_LORA_MAX_SEGS];
+  float* out;                  /* [M][ldo], updated in place */
+  int32_t ldo;
+  int32_t _pad0;
+} dia_lora_args;
+int dia_lora_apply(const dia_lora_args* a, void* stream);
+/* The cross K/V projections (DIA_EPI_CROSSKV stored RoPE(K) and V into the caches): adds RoPE(dK) and dV to the cache rows of the
+ * packed rows' utterances, in stream order behind that dia_gemm.  The cache arguments are dia_gemm_args' (one layer); row m belongs
+ * to utterance row_b[m] (< 0 = skipped) at position m - seg_off[row_b[m]], both NULL = utterance kv_batch_index, position m; the
+ * adapter is adapter_of_slot[utterance].  f32: read, add, store; bf16: read, add in fp32, round once; bf16x2: hi + lo, add, split
+ * again.  k / v: the segments (col_off unused, n_cols = kv_heads * 128, columns in checkpoint order [head][128]). */
+typedef struct {
+  const float* x;              /* encoder output rows before the final norm [M][ldx] */
+  int32_t ldx;
+  int32_t D;
+  const float* gain;           /* encoder.norm weight [D] */
+  float eps;
+  int32_t M;
+  const int32_t* row_b;
+  const int32_t* seg_off;
+  const int32_t* adapter_of_slot;   /* device [n_slots] */
+  int32_t n_slots;
+  int32_t n_adapters;
+  dia_lora_seg k, v;
+  void* kc;
+  void* vc;
+  int32_t kv_dtype, kv_heads, kv_cap, kv_batch_index;
+  int32_t kv_vblocked;
+  int32_t rope_rows;           /* rows of cos_t / sin_t (positions at or beyond it are skipped) */
+  int64_t kv_plane_stride;
+  const float* cos_t;
+  const float* sin_t;
+} dia_lora_crosskv_args;
+int dia_lora_crosskv(const dia_lora_crosskv_args* a, void* stream);
+/* The two decode-step sites of one decoder layer: self-attention q / k / v (column ranges of dia_engine_desc.qkv) and the
+ * cross-attention query (dia_engine_desc.qc); n_cols == 0 = module not adapted by any adapter of the bank. */
+typedef struct {
+  dia_lora_seg q, k, v, cq;
+} dia_lora_layer;
+typedef struct {
+  int32_t n_layer;                   /* must equal dia_engine_desc.n_layer */
+  int32_t n_adapters;
+  const dia_lora_layer* layers;      /* host array [n_layer], copied */
+  const int32_t* adapter_of_slot;    /* device int32 [B]: written by the caller in stream order (admission / retirement), read by every step */
+} dia_lora_step;
+/* before the first step (DIA_E_STATE afterwards): every step then issues one dia_lora_apply behind each layer's q/k/v projection
+ * (before self-attention) and one behind its cross-query projection (before cross-attention), eager and in the captured graph;
+ * dia_engine_launches_per_step reports 2 * n_layer more, and the prefetch walk and dia_engine_profile_step follow.  The rows read
+ * are the residual stream the projection consumed (x, or x_alt on odd layers while wo's merge is deferred) with g_sa / g_ca.
+ * DIA_E_ARG for a compacted model (strip or compaction maps on either site), persistent segments and everything dia_lora_apply
+ * refuses.  NULL = the step without it, launch for launch. */
+int dia_engine_set_lora(dia_engine* e, const dia_lora_step* s);
+
 #ifdef __cplusplus
 }
 #endif
