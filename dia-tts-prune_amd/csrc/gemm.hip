@@ -155,6 +155,9 @@ __global__ __launch_bounds__(NW * 64) void k_gemm(GemmK p) {
 // SPEC: the two forms of the projections at K = 2048 (k_gemv_small<RS, Form> below) whose epilogue, K range and
 // operand set are compile-time facts: 1 = SCALE_STORE with row scales over at most 128 strip sums, 2 = RESID_EMIT without row scales;
 // one strip per workgroup, no split-K, no compaction maps.  The arithmetic is that of SPEC = 0, operation for operation.
+// 3, 4: the same treatment for wo's deferred pair (k_gemv_small<..., DF> with a LeadForm below), again one shape each: 3 = the
+// consumer (DF = 2, SCALE_STORE, K = 2048, no strip map; one strip per workgroup or MULTI), 4 = the producer (DF = 1, two slices of
+// 128 k-tiles, no row scales).  (wi as a form of its own — MULTI, SWIGLU_EMIT, K = 2048 — was built and lost its A/B: DESIGN 9.)
 template <int NW, int KPW, int RS, bool MULTI, bool AF32, bool PF32, bool W2, int DF, int SPEC = 0>
 __device__ __forceinline__ void gemv_small_body(GemmK& p) {
   // (the compiler loads the fields of the 250-byte argument block where they are first used: four s_load round trips
@@ -169,11 +172,13 @@ __device__ __forceinline__ void gemv_small_body(GemmK& p) {
   static_assert(DF == 0 || (AF32 && PF32 && !W2), "the deferred wo merge: fp32 activation tiles, one weight plane");
   static_assert(DF != 2 || (NW * KPW == 64 && (RS == 2 || RS == 4)), "the deferred consumer holds a whole row of D = 2048: 128 strips");
   static_assert(DF != 1 || !MULTI, "the deferred producer: one strip per workgroup");
-  static_assert(SPEC == 0 || (AF32 && PF32 && !W2 && DF == 0 && !MULTI), "the specialised forms: fp32 tiles, one plane, one strip");
+  static_assert(SPEC == 0 || (AF32 && PF32 && !W2), "the specialised forms: fp32 tiles, one plane");
+  static_assert((SPEC != 1 && SPEC != 2) || (DF == 0 && !MULTI), "the per-epilogue projection forms: one strip per workgroup");
+  static_assert((SPEC == 3) <= (DF == 2) && (SPEC == 4) <= (DF == 1), "the forms of the deferred pair");
 
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int kt0 = w * KPW;                 // k-tile inside this workgroup's K range
-  const int ktg = SPEC ? 0 : blockIdx.y * (NW * KPW); // first global k-tile of that range (split-K over gridDim.y)
+  const int ktg = (SPEC && DF != 1) ? 0 : blockIdx.y * (NW * KPW); // first global k-tile of that range (split-K over gridDim.y)
   constexpr int WS = W2 ? 1 : 0;           // weight k-tile -> activation k-tile: >> WS
   const int ktga = ktg >> WS;              // first global activation k-tile of the range
   const int G = gridDim.x;                 // the workgroup walks strips blockIdx.x, +G, +2G, ...
@@ -185,6 +190,9 @@ __device__ __forceinline__ void gemv_small_body(GemmK& p) {
   };
   __shared__ int sk_flag;
 
+#ifdef DIA_DBG_STAMP_KINDS      // 1 cq, 2 o / co, 3 wo's consumer (q/k/v), 4 wo's producer, 5 the consumer over several strips (logits), 6 wi, 7 the rest
+  constexpr int stamp_kind = SPEC == 1 ? 1 : SPEC == 2 ? 2 : DF == 2 ? (MULTI ? 5 : 3) : DF == 1 ? 4 : (NW == 16 && KPW == 4 && MULTI) ? 6 : 7;
+#endif
   STAMP(0);
   bf16x8 b0[KPW], b1[MULTI ? KPW : 1];
   constexpr int KT = (NW * KPW) >> WS;     // activation k-tiles of the image (the dispatcher: p.KT == NW*KPW*gridDim.y)
@@ -455,6 +463,56 @@ __global__ __launch_bounds__(512) void k_gemv_small(const bf16_raw* a_A, const b
   p.KT = 64; p.epi = Form::EPI; p.strip_map = nullptr; p.cmap = nullptr;
   gemv_small_body<8, 8, RS, false, true, true, false, 0, Form::SPEC>(p);
 }
+
+// wo's deferred producer and consumer kept the generic body until now, and each serves ONE shape (launch_wo_deferred).
+// LeadForm<DF, MULTI> gives such a launch what ScaleStore / ResidEmit give the projections: its own ten leading arguments,
+// in the order its prologue wants them (the first 64 bytes arrive in SGPRs: every one of them but the consumer's ldo at byte 64,
+// which only the epilogue reads), and its epilogue kind, K range and absent operands as compile-time constants.  The kernel is an overload of k_gemv_small on the FUNCTION parameter list with the template parameter list of
+// the generic instantiation it replaces: the instantiation name a launch reports stays what it was, and the knob gemv_spec selects
+// between the two at the launch (generic_small / form_small below).
+//   consumer (DF 2)   W, wo_slices, wo_slice_stride, wo_xold, gnext, wo_ldx, M, wo_xnew, out, ldo       (nstrips, inv_d, eps: behind the barrier)
+//   producer (DF 1)   A, W, wo_slices, wo_slice_stride, M, p_ktiles
+template <int DF, bool MULTI> struct LeadForm;
+template <bool MULTI> struct LeadForm<2, MULTI> {
+  static constexpr int SPEC = 3;
+  using T0 = const bf16_raw*; using T1 = float*; using T2 = long; using T3 = const float*; using T4 = const float*; using T5 = int; using T6 = int;
+  using T7 = float*; using T8 = float*; using T9 = int;
+  static __device__ __forceinline__ void set(GemmK& p, T0 W, T1 slices, T2 slice_stride, T3 xold, T4 gnext, T5 ldx, T6 M, T7 xnew, T8 out, T9 ldo) {
+    p.W = W; p.wo_slices = slices; p.wo_slice_stride = slice_stride; p.wo_xold = xold; p.gnext = gnext; p.wo_ldx = ldx; p.M = M; p.wo_xnew = xnew;
+    p.out = out; p.ldo = ldo;
+    p.KT = 64; p.epi = DIA_EPI_SCALE_STORE;
+  }
+  static auto args(const GemmK& k) { return std::make_tuple(k.W, k.wo_slices, k.wo_slice_stride, k.wo_xold, k.gnext, k.wo_ldx, k.M, k.wo_xnew, k.out, k.ldo); }
+};
+template <> struct LeadForm<1, false> {
+  static constexpr int SPEC = 4;
+  using T0 = const bf16_raw*; using T1 = const bf16_raw*; using T2 = float*; using T3 = long; using T4 = int; using T5 = int; using T6 = int;
+  using T7 = int; using T8 = int; using T9 = int;
+  static __device__ __forceinline__ void set(GemmK& p, T0 A, T1 W, T2 slices, T3 slice_stride, T4 M, T5 p_ktiles, T6, T7, T8, T9) {
+    p.A = A; p.W = W; p.wo_slices = slices; p.wo_slice_stride = slice_stride; p.M = M; p.p_ktiles = p_ktiles;
+    p.KT = 256; p.epi = DIA_EPI_RESID_EMIT; p.ssq_in = nullptr;
+  }
+  static auto args(const GemmK& k) { return std::make_tuple(k.A, k.W, k.wo_slices, k.wo_slice_stride, k.M, k.p_ktiles, 0, 0, 0, 0); }
+};
+template <int NW, int KPW, int RS, bool MULTI, bool AF32, bool PF32, bool W2, int DF>
+__global__ __launch_bounds__(NW * 64) void k_gemv_small(typename LeadForm<DF, MULTI>::T0 a0, typename LeadForm<DF, MULTI>::T1 a1, typename LeadForm<DF, MULTI>::T2 a2,
+                                                        typename LeadForm<DF, MULTI>::T3 a3, typename LeadForm<DF, MULTI>::T4 a4, typename LeadForm<DF, MULTI>::T5 a5,
+                                                        typename LeadForm<DF, MULTI>::T6 a6, typename LeadForm<DF, MULTI>::T7 a7, typename LeadForm<DF, MULTI>::T8 a8,
+                                                        typename LeadForm<DF, MULTI>::T9 a9, GemmK p) {
+  LeadForm<DF, MULTI>::set(p, a0, a1, a2, a3, a4, a5, a6, a7, a8, a9);
+  p.strip_map = nullptr; p.cmap = nullptr;
+  gemv_small_body<NW, KPW, RS, MULTI, AF32, PF32, W2, DF, LeadForm<DF, MULTI>::SPEC>(p);
+}
+
+// the two overloads behind one instantiation name, told apart by their parameter lists
+template <int NW, int KPW, int RS, bool MULTI, int DF>
+constexpr auto generic_small = static_cast<void (*)(const bf16_raw*, long, const bf16_raw*, int, int, int, int, float*, int, const float*, GemmK)>(
+    k_gemv_small<NW, KPW, RS, MULTI, true, true, false, DF>);
+template <int NW, int KPW, int RS, bool MULTI, int DF>
+constexpr auto form_small = static_cast<void (*)(typename LeadForm<DF, MULTI>::T0, typename LeadForm<DF, MULTI>::T1, typename LeadForm<DF, MULTI>::T2,
+                                                 typename LeadForm<DF, MULTI>::T3, typename LeadForm<DF, MULTI>::T4, typename LeadForm<DF, MULTI>::T5,
+                                                 typename LeadForm<DF, MULTI>::T6, typename LeadForm<DF, MULTI>::T7, typename LeadForm<DF, MULTI>::T8,
+                                                 typename LeadForm<DF, MULTI>::T9, GemmK)>(k_gemv_small<NW, KPW, RS, MULTI, true, true, false, DF>);
 
 
 // 5..16 rows (batch 3-8): one m-tile, A fragments held in registers for the workgroup's whole life
@@ -2035,6 +2093,23 @@ int launch_generic(const GemmK& k, int nw, hipStream_t st) {
   return launch_nw<4>(k, nw, (mtiles + 3) / 4, st);
 }
 
+// knob gemv_spec: -1 = every form, 0 = none (the generic body everywhere), otherwise a mask for the A/B of one form at a time:
+// 1 = the per-epilogue projections, 2 = the deferred consumer, 4 = the deferred producer
+enum { SPEC_PROJ = 1, SPEC_CONSUMER = 2, SPEC_PRODUCER = 4 };
+// which body the last dia_gemm / dia_gemm_wo_deferred call launched: the SPEC of gemv_small_body (0 = generic or another kernel, 1 ScaleStore,
+// 2 ResidEmit, 3 deferred consumer, 4 deferred producer).  Two bodies share one instantiation name, so the name cannot tell (dia_last_gemv_form).
+int g_last_gemv_form = 0;
+bool gemv_spec_on(int form) {
+  const int v = dia_tune(DIA_TUNE_GEMV_SPEC);
+  return v < 0 || (v & form) != 0;
+}
+
+template <auto Kern, typename Lead>
+void launch_form(dim3 grid, dim3 block, size_t smem, hipStream_t st, const GemmK& k) {
+  std::apply([&](auto... lead) { dia_launch<Kern>(grid, block, smem, st, lead..., k); }, Lead::args(k));
+  g_last_gemv_form = Lead::SPEC;
+}
+
 size_t small_smem(int nw, int KT, int rs) {     // KT = k-tiles one workgroup stages (its own K range)
   return sizeof(f32x4) * nw * 64 + sizeof(float) * (16 * 17 + 16) + (size_t)DIA_NPLANES * KT * 4 * rs * 16;
 }
@@ -2100,7 +2175,7 @@ int launch_small_rs(const GemmK& k, int nw, int sk, hipStream_t st, bool& handle
 // leave to the generic instantiation: an explicit wave count, several strips per workgroup, split-K, compaction maps, row scales over
 // more than 128 strip sums, a RESID_EMIT that norms its input.  Knob gemv_spec=0: the generic form everywhere (A/B).
 bool small_spec_serves(const dia_gemm_args* a, const GemmK& k, int sk) {
-  if (dia_tune(DIA_TUNE_GEMV_SPEC) == 0 || a->M > 4 || a->nw != 0 || sk != 1 || a->KT != 64 || a->cmap || a->strip_map) return false;
+  if (!gemv_spec_on(SPEC_PROJ) || a->M > 4 || a->nw != 0 || sk != 1 || a->KT != 64 || a->cmap || a->strip_map) return false;
   if (pick_spw(k, 512, 1, 1) != 1) return false;
   // the one exclusion that is not the kernel's: SCALE_STORE onto 192 strips is the q/k/v projection of Dia-1.6B, whose generic
   // instantiation tests/test_gpu_wo_deferred.py pins by name as the reference of the deferred-wo consumer (which serves that projection
@@ -2122,6 +2197,7 @@ int launch_small_spec(const GemmK& k, hipStream_t st) {
   else
     dia_launch<k_gemv_small<RS, ResidEmit>>(dim3(k.nstrips), dim3(512), smem, st, k.A, k.W, k.out, k.gnext, k.P, k.M, k.ldo, k.p_ktiles,
                                             k.ssq_ld, k.ssq_out, k);
+  g_last_gemv_form = k.epi == DIA_EPI_SCALE_STORE ? ScaleStore::SPEC : ResidEmit::SPEC;
   return dia_check_launch("k_gemv_small");
 }
 
@@ -2161,15 +2237,24 @@ int launch_g16_w2(const GemmK& k, int mz, int sk, hipStream_t st) {
 template <int RS>
 int launch_wo_deferred(const GemmK& k, int role, hipStream_t st) {
   if (role == 1) {
-    launch_small_kernel<k_gemv_small<16, 8, RS, false, true, true, false, 1>>(dim3(k.nstrips, 2), dim3(1024), small_smem(16, 128, RS), st, k);
+    // (the form drops ssq_in: with DF = 1 the body returns before any row scale is used, so strip sums a caller hands over are ignored
+    // by the form as the generic body ignores them after reading them)
+    if (gemv_spec_on(SPEC_PRODUCER))
+      launch_form<form_small<16, 8, RS, false, 1>, LeadForm<1, false>>(dim3(k.nstrips, 2), dim3(1024), small_smem(16, 128, RS), st, k);
+    else
+      launch_small_kernel<generic_small<16, 8, RS, false, 1>>(dim3(k.nstrips, 2), dim3(1024), small_smem(16, 128, RS), st, k);
     return dia_check_launch("k_gemv_small");
   }
   const size_t smem = small_smem(8, 64, RS) + sizeof(float) * RS * 256;
   const int spw = pick_spw(k, 512, 1, 1);          // as launch_small
   const int grid = (k.nstrips + spw - 1) / spw;
   if (k.wo_xnew && grid < 128) return dia_fail(DIA_E_ARG, "dia_gemm: deferred wo merge: fewer workgroups than strips of x to write back");
-  if (spw > 1) launch_small_kernel<k_gemv_small<8, 8, RS, true, true, true, false, 2>>(dim3(grid), dim3(512), smem, st, k);
-  else launch_small_kernel<k_gemv_small<8, 8, RS, false, true, true, false, 2>>(dim3(grid), dim3(512), smem, st, k);
+  // (the form has neither compaction map: strip_map is checked here, cmap cannot arrive — gemm_wo_deferred refuses it for either role)
+  if (gemv_spec_on(SPEC_CONSUMER) && !k.strip_map) {
+    if (spw > 1) launch_form<form_small<8, 8, RS, true, 2>, LeadForm<2, true>>(dim3(grid), dim3(512), smem, st, k);
+    else launch_form<form_small<8, 8, RS, false, 2>, LeadForm<2, false>>(dim3(grid), dim3(512), smem, st, k);
+  } else if (spw > 1) launch_small_kernel<generic_small<8, 8, RS, true, 2>>(dim3(grid), dim3(512), smem, st, k);
+  else launch_small_kernel<generic_small<8, 8, RS, false, 2>>(dim3(grid), dim3(512), smem, st, k);
   return dia_check_launch("k_gemv_small");
 }
 
@@ -2197,6 +2282,9 @@ extern "C" int dia_dbg_stamps(long long* host, int n) {
   return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_stamps), sizeof(long long) * n) == hipSuccess ? 0 : -2;
 }
 #endif
+
+// test and measurement hook, outside include/dia_hip.h like dia_dbg_stamps: the body the last dia_gemm / dia_gemm_timed / dia_gemm_wo_deferred call launched
+extern "C" int dia_last_gemv_form(void) { return g_last_gemv_form; }
 
 extern "C" int dia_has_experiments(void) {
 #ifdef DIA_EXPERIMENTS
@@ -2243,6 +2331,7 @@ int gemm_w2(const dia_gemm_args* a, GemmK& k, hipStream_t st) {
 }  // namespace
 
 static int gemm_impl(const dia_gemm_args* a, const dia_wo_defer_args* wd, void* stream) {
+  g_last_gemv_form = 0;
   if (!a || !a->A || (!a->W && !a->sp_blocks)) return dia_fail(DIA_E_ARG, "dia_gemm: null argument");
   if (a->M <= 0 || a->KT <= 0 || a->nstrips <= 0) return dia_fail(DIA_E_ARG, "dia_gemm: empty problem");
   if (wd && (a->w_format != DIA_W_DENSE || a->w_layout != 0 || a->w_planes > 1 || a->sp_blocks || a->sp_toff))

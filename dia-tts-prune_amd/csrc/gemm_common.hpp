@@ -4,6 +4,7 @@
 #pragma once
 #include "common.hpp"
 #include <type_traits>
+#include <tuple>
 #include "../../include/dia_hip.h"
 #include "errors.hpp"
 #include <hip/hip_ext.h>
@@ -370,7 +371,14 @@ __device__ __forceinline__ bool splitk_combine(const GemmK& p, float* tile, int 
 
 #ifdef DIA_DBG_STAMPS
 __device__ long long g_stamps[4096 * 8];
+// -DDIA_DBG_STAMP_KINDS: the table is eight groups of 512 workgroups, one per kind of 1-4-row GEMV (stamp_kind in gemv_small_body; 0 =
+// everything else), so that after a whole replayed step the last launch of EVERY kind can still be read (scratch/stamps_step.py)
+#ifdef DIA_DBG_STAMP_KINDS
+constexpr int stamp_kind = 0;
+#define STAMP(i) do { if (tid == 0) g_stamps[(stamp_kind * 512 + ((blockIdx.y * gridDim.x + blockIdx.x) & 511)) * 8 + (i)] = wall_clock64(); } while (0)
+#else
 #define STAMP(i) do { if (tid == 0) g_stamps[((blockIdx.y * gridDim.x + blockIdx.x) & 4095) * 8 + (i)] = wall_clock64(); } while (0)
+#endif
 #else
 #define STAMP(i) do {} while (0)
 #endif

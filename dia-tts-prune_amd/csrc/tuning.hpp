@@ -35,6 +35,7 @@ enum dia_tune_id {
   DIA_TUNE_MXFP4,              // mxfp4: as mxfp8 for the MXFP4 streams (dia_mxfp4_classes, dia_engine_set_mxfp4)
   DIA_TUNE_GEMV_SPEC,          // gemv_spec: 0 = the 1-4-row projections at K = 2048 keep the generic k_gemv_small<8, 8, RS, false, true, true> instead of
                                // the per-epilogue forms k_gemv_small<RS, Form> (csrc/gemm.hip, small_spec_serves; A/B)
+                               // otherwise a mask of the forms in use: 1 = those projections, 2 = the deferred-wo consumer, 4 = its producer (gemv_spec_on)
   // ---- EXPERIMENTS=1 builds only
   DIA_TUNE_MLP_FUSE,           // mlp_fuse: 1 = wi + wo as one persistent launch at batch 1 (dia_mlp_fused)
   DIA_TUNE_TILE_V,             // tile_v: prefill tile kernel variant (0..5; 3 = wave-specialised default)

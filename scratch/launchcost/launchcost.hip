@@ -3,6 +3,8 @@
 // per launch.  Build: hipcc -O3 --offload-arch=gfx950 -o launchcost launchcost.hip
 #include <hip/hip_runtime.h>
 #include <cstdio>
+#include <cstring>
+#include <type_traits>
 #include <vector>
 typedef unsigned int u4 __attribute__((ext_vector_type(4)));
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("%s: %s\n", #x, hipGetErrorString(e)); return 1; } } while (0)
@@ -181,6 +183,108 @@ __global__ void k_gemvlike_stamped(const u4* w, const u4* a_in, u4* a_out, float
   if (tid == 0) stamps[blockIdx.x * 4 + 3] = wall_clock64();
 }
 
+// ---- start bisect (r09): from skeleton (k) towards the real 1-4-row GEMV, one property at a time -------------------------------------
+// `launchcost bisect`.  The same binary built twice: plain, and with -mllvm -amdgpu-kernarg-preload-count=16 (property a).
+//   PAD   never-executed 8-byte instructions appended to the kernel's code (property c; with ID, property d)
+//   ID    distinct instantiations of the same code, alternated in the chain (property d)
+//   NS    small dependent-free requests (one float per lane) issued in front of the weight stream, consumed after it (property g)
+//   BIG   a 256-byte block passed by value behind the leading scalars, one field read in the epilogue (property b)
+// run time: dynamic LDS bytes (property e), priv = every workgroup reads a 24 KB operand of its own instead of the one the previous
+// launch wrote (property f), stamps = where each workgroup writes its start time (null in the timed chains).
+struct BigArg { int f[64]; };
+struct NoArg { int f[1]; };
+template <int PAD, int ID, int NS, bool BIG>
+__global__ __attribute__((amdgpu_num_vgpr(128))) void k_bis(const u4* w, const u4* a_in, u4* a_out, float* out, int per_wg, const float* sm, int priv,
+                                                            long long* stamps, typename std::conditional<BIG, BigArg, NoArg>::type big) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char dyn[];
+  u4* As = reinterpret_cast<u4*>(dyn);
+  float (*red)[64] = reinterpret_cast<float (*)[64]>(dyn + 1536 * 16);
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  if (stamps && tid == 0) stamps[blockIdx.x] = wall_clock64();
+  float sv[NS > 0 ? NS : 1];
+#pragma unroll
+  for (int i = 0; i < NS; ++i) sv[i] = sm[i * 64 + lane];
+  const u4* ain = a_in + (priv ? (size_t)blockIdx.x * 1536 : 0);
+  u4 av[3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) av[i] = ain[tid + 512 * i];
+  const u4* base = w + (size_t)blockIdx.x * per_wg + tid;
+  u4 v[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) v[i] = __builtin_nontemporal_load(base + i * 512);
+  unsigned s = ID;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) As[tid + 512 * i] = av[i];
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < 3; ++i) { const u4 t = As[(tid * 7 + 512 * i + 13) % 1536]; s += t.x ^ t.w; }
+#pragma unroll
+  for (int i = 0; i < 8; ++i) s += v[i].x ^ v[i].y ^ v[i].z ^ v[i].w;
+  float fs = (float)s;
+#pragma unroll
+  for (int i = 0; i < NS; ++i) fs += sv[i];
+  red[wv][lane] = fs;
+  __syncthreads();
+  if (tid < 64) {
+    float a = 0.f;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) a += red[k][tid];
+    red[0][tid] = a;
+  }
+  __syncthreads();
+  if (tid < 32) {
+    float x = red[0][tid] + red[0][tid + 32];
+    if (BIG) x += (float)big.f[40];
+    const unsigned xb = __float_as_uint(x) | 1u;
+    const u4 o = {xb, xb + 1, xb + 2, xb + 3};
+    if (tid < 12) a_out[(blockIdx.x % 128) * 12 + tid] = o;
+  }
+  if (PAD > 0 && per_wg < 0) asm volatile(".rept %0\n v_mov_b32 v1, 0x12345678\n .endr" ::"n"(PAD));
+}
+
+struct Chain { double us_min, us_max, spread; };
+// one chain of n launches, captured and replayed: us per launch (min .. max of three timings of 20 replays), then the same chain with
+// start stamps: max - min of the workgroup starts of a launch, mean over the launches of one replay (100 MHz clock)
+template <typename F>
+int run_bis(const char* name, hipStream_t st, int n, int grid, long long* st_d, F launch) {
+  Chain c{1e9, 0, 0};
+  for (int pass = 0; pass < 2; ++pass) {
+    hipGraph_t g; hipGraphExec_t ge;
+    CK(hipStreamBeginCapture(st, hipStreamCaptureModeGlobal));
+    for (int i = 0; i < n; ++i) launch(i, pass ? st_d + (size_t)i * 256 : nullptr);
+    CK(hipStreamEndCapture(st, &g));
+    CK(hipGraphInstantiate(&ge, g, nullptr, nullptr, 0));
+    for (int r = 0; r < 3; ++r) CK(hipGraphLaunch(ge, st));
+    CK(hipStreamSynchronize(st));
+    if (!pass) {
+      hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
+      for (int t = 0; t < 3; ++t) {
+        CK(hipEventRecord(e0, st));
+        for (int r = 0; r < 20; ++r) CK(hipGraphLaunch(ge, st));
+        CK(hipEventRecord(e1, st));
+        CK(hipStreamSynchronize(st));
+        float ms = 0; CK(hipEventElapsedTime(&ms, e0, e1));
+        const double us = ms * 1e3 / (20 * n);
+        c.us_min = us < c.us_min ? us : c.us_min; c.us_max = us > c.us_max ? us : c.us_max;
+      }
+      CK(hipEventDestroy(e0)); CK(hipEventDestroy(e1));
+    } else {
+      std::vector<long long> h((size_t)n * 256);
+      CK(hipMemcpy(h.data(), st_d, h.size() * sizeof(long long), hipMemcpyDeviceToHost));
+      double sum = 0;
+      for (int i = 8; i < n; ++i) {
+        long long mn = h[(size_t)i * 256], mx = mn;
+        for (int b = 0; b < grid; ++b) { const long long t = h[(size_t)i * 256 + b]; mn = t < mn ? t : mn; mx = t > mx ? t : mx; }
+        sum += (mx - mn) / 100.0;
+      }
+      c.spread = sum / (n - 8);
+    }
+    CK(hipGraphExecDestroy(ge)); CK(hipGraphDestroy(g));
+  }
+  printf("%-78s %5.2f .. %5.2f us per launch   start spread %4.2f us\n", name, c.us_min, c.us_max, c.spread);
+  return 0;
+}
+
 template <typename F>
 int run(const char* name, hipStream_t st, int n, F launch) {
   hipGraph_t g; hipGraphExec_t ge;
@@ -202,7 +306,7 @@ int run(const char* name, hipStream_t st, int n, F launch) {
   return 0;
 }
 
-int main() {
+int main(int argc, char** argv) {
   hipStream_t st; CK(hipStreamCreate(&st));
   u4* big; CK(hipMalloc(&big, 544u << 20)); CK(hipMemset(big, 1, 544u << 20));   // 64 x 8 MB: beyond L2 + Infinity Cache
   float* out; CK(hipMalloc(&out, 1 << 20));
@@ -210,6 +314,47 @@ int main() {
   int* dummy = nullptr;
   const int N = 146;
   auto wb = [&](int i) { return big + (size_t)(i % 64) * ((8u << 20) / 16); };
+  if (argc > 1 && !strcmp(argv[1], "bisect")) {
+    long long* st_d; CK(hipMalloc(&st_d, (size_t)N * 256 * sizeof(long long)));
+    float* sm; CK(hipMalloc(&sm, 20 * 64 * sizeof(float))); CK(hipMemset(sm, 0, 20 * 64 * sizeof(float)));
+    u4* apriv; CK(hipMalloc(&apriv, 128 * 24576)); CK(hipMemset(apriv, 1, 128 * 24576));
+    const BigArg bg{}; const NoArg ng{};
+#define KB(PAD, ID, NS, BIG) k_bis<PAD, ID, NS, BIG>
+#define SETLDS(PAD, ID, NS, BIG) CK(hipFuncSetAttribute(reinterpret_cast<const void*>(KB(PAD, ID, NS, BIG)), hipFuncAttributeMaxDynamicSharedMemorySize, 69632))
+#define PING (i & 1) ? a1 : a0, (i & 1) ? a0 : a1
+#define BIS(name, PAD, NS, BIG, lds, arg) SETLDS(PAD, 0, NS, BIG); \
+    if (run_bis(name, st, N, 128, st_d, [&](int i, long long* sp) { hipLaunchKernelGGL((KB(PAD, 0, NS, BIG)), dim3(128), dim3(512), lds, st, wb(i), PING, out, 4096, sm, 0, sp, arg); })) return 1
+#define ALT(name, PAD) SETLDS(PAD, 0, 0, false); SETLDS(PAD, 1, 0, false); SETLDS(PAD, 2, 0, false); SETLDS(PAD, 3, 0, false); SETLDS(PAD, 4, 0, false); \
+    if (run_bis(name, st, N, 128, st_d, [&](int i, long long* sp) { switch (i % 5) { \
+      case 0: hipLaunchKernelGGL((KB(PAD, 0, 0, false)), dim3(128), dim3(512), 34816, st, wb(i), PING, out, 4096, sm, 0, sp, ng); break; \
+      case 1: hipLaunchKernelGGL((KB(PAD, 1, 0, false)), dim3(128), dim3(512), 34816, st, wb(i), PING, out, 4096, sm, 0, sp, ng); break; \
+      case 2: hipLaunchKernelGGL((KB(PAD, 2, 0, false)), dim3(128), dim3(512), 34816, st, wb(i), PING, out, 4096, sm, 0, sp, ng); break; \
+      case 3: hipLaunchKernelGGL((KB(PAD, 3, 0, false)), dim3(128), dim3(512), 34816, st, wb(i), PING, out, 4096, sm, 0, sp, ng); break; \
+      default: hipLaunchKernelGGL((KB(PAD, 4, 0, false)), dim3(128), dim3(512), 34816, st, wb(i), PING, out, 4096, sm, 0, sp, ng); } })) return 1
+    for (int rep = 0; rep < 2; ++rep) {       // the base twice: its own run-to-run spread
+      BIS("(k') skeleton (k): 34 KB LDS, 128 VGPRs, operand written by the previous launch", 0, 0, false, 34816, ng);
+    }
+    BIS("(b) + 256-byte block by value behind the scalars", 0, 0, true, 34816, bg);
+    BIS("(c) + code padded by 363 never-executed instructions (2.9 KB)", 363, 0, false, 34816, ng);
+    BIS("(c) + code padded by 497 (4.0 KB)", 497, 0, false, 34816, ng);
+    BIS("(c) + code padded by 1080 (8.6 KB)", 1080, 0, false, 34816, ng);
+    BIS("(c) + code padded by 2600 (20.8 KB)", 2600, 0, false, 34816, ng);
+    ALT("(d) five kernels alternating, no padding", 0);
+    ALT("(d) five kernels alternating, each padded by 497 (20 KB in all)", 497);
+    ALT("(d) five kernels alternating, each padded by 1080 (43 KB in all)", 1080);
+    ALT("(d) five kernels alternating, each padded by 2600 (104 KB in all: beyond 64 KB)", 2600);
+    BIS("(e) + 48 KB of dynamic LDS", 0, 0, false, 49152, ng);
+    BIS("(e) + 66688 B of dynamic LDS (the wo producer's)", 0, 0, false, 66688, ng);
+    SETLDS(0, 0, 0, false);
+    if (run_bis("(f) operand: a 24 KB copy per workgroup, never rewritten", st, N, 128, st_d, [&](int i, long long* sp) {
+          hipLaunchKernelGGL((KB(0, 0, 0, false)), dim3(128), dim3(512), 34816, st, wb(i), apriv, (i & 1) ? a0 : a1, out, 4096, sm, 1, sp, ng); })) return 1;
+    BIS("(g) + 4 small requests in front of the stream", 0, 4, false, 34816, ng);
+    BIS("(g) + 18 small requests", 0, 18, false, 34816, ng);
+    BIS("(g) + 20 small requests", 0, 20, false, 34816, ng);
+    BIS("(b+c+g) block + 1080 padding + 18 requests", 1080, 18, true, 34816, bg);
+    BIS("(k') skeleton (k) again", 0, 0, false, 34816, ng);
+    return 0;
+  }
 #define RUN(name, F, grid, ain, aout) if (run(name, st, N, [&](int i) { hipLaunchKernelGGL(k_gemvlike<F>, dim3(grid), dim3(512), 0, st, wb(i), ain, aout, out, 4096); })) return 1
   if (run("(a) 1 x 64 threads, empty", st, N, [&](int) { hipLaunchKernelGGL(k_empty, dim3(1), dim3(64), 0, st, dummy); })) return 1;
   if (run("(b) 256 x 512 threads, empty", st, N, [&](int) { hipLaunchKernelGGL(k_empty, dim3(256), dim3(512), 0, st, dummy); })) return 1;
