@@ -86,6 +86,9 @@ def build_parser() -> argparse.ArgumentParser:
                    help="mxfp8 = the checkpoint is MXFP8-quantised (offline_quantize.py): batch 1-8 decode steps stream its decoder "
                         "matrices as e4m3 elements + block scales (half the weight bytes); mxfp4 = the same for an MXFP4-quantised "
                         "checkpoint (--format mxfp4: e2m1 elements, a quarter of the bytes); bf16 = dense tiles only")
+    g.add_argument("--cross-kv", type=str, default="bf16", choices=["bf16", "fp8"],
+                   help="(build-only) fp8: the decode step reads an e4m3 copy of the cross-attention K/V caches (one power-of-two scale per "
+                        "key and head) instead of the bf16 caches; needs a bf16 --compute-dtype")
     g.add_argument("--verbose", action="store_true", help="report prefill and generation timing")
     return p
 
@@ -210,6 +213,7 @@ def main(argv=None) -> int:
     Dia.fp32_weights = args.fp32_weights
     Dia.sparse_weights = args.sparse_weights
     Dia.weight_format = args.weight_format
+    Dia.cross_kv = args.cross_kv
     if args.seed is not None:
         set_seed(args.seed)
         print(f"Using seed: {args.seed}")

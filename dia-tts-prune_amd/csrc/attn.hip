@@ -644,6 +644,272 @@ __global__ __launch_bounds__(NT, 2) void k_attn_mfma(AttnK p) {
 }
 
 // ---------------------------------------------------------------------------------------------------
+// FP8 cross K/V (dia_hip.h "FP8 cross K/V"): k_attn_mfma<1, 1> for DIA_ATTN_CROSS over the e4m3 copy of the cross caches.
+// A K / V fragment is 8 bytes instead of 16 and is expanded to bf16x8 in registers (v_cvt_scalef32_pk_bf16_fp8 at scale 1, exact:
+// every e4m3 value is a bf16 value); a granule also brings its 32 K and 32 V scales, one of each per lane and key tile (lane l of
+// tile t = key key0 + 16t + (l & 15), the lane that holds the key's score).  The scales are powers of two and fold in behind the
+// MFMAs: S[key] * ks[key] == q . (k8 * ks) and bf16(p * vs) == bf16(p) * vs exactly, so every MFMA receives products equal to
+// those of the bf16 kernel over the dequantised caches and the output is the same bit for bit.  Key -> workgroup -> wave
+// assignment, gpw rule, two-granule prefetch, online softmax, slab merge and output are k_attn_mfma's; there is no slot to append.
+struct AttnF8 { const uint8_t* k8; const uint8_t* v8; const float* ks; const float* vs; };
+struct F8Frag { uint2 kb[2][4]; uint2 vb[8]; float ksc[2], vsc[2]; };
+
+typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
+__device__ __forceinline__ bf16x8 expand_e4m3(uint2 d) {      // (gemm_mxfp8.hip expand_fp8 at scale 1)
+  const bf16x2 r0 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(d.x, 1.0f, false);
+  const bf16x2 r1 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(d.x, 1.0f, true);
+  const bf16x2 r2 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(d.y, 1.0f, false);
+  const bf16x2 r3 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(d.y, 1.0f, true);
+  typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
+  const bf16x4 lo = __builtin_shufflevector(r0, r1, 0, 1, 2, 3), hi = __builtin_shufflevector(r2, r3, 0, 1, 2, 3);
+  return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+}
+
+__global__ __launch_bounds__(NT, 2) void k_attn_mfma_f8(AttnK p, AttnF8 f8) {
+  constexpr int G = 1;
+  __shared__ __attribute__((aligned(16))) bf16_raw qf[4][DIA_NPLANES][G][4][8];   // q planes in A-fragment order
+  __shared__ float part[NWV * G * HD];
+  __shared__ float pm_s[NWV * 8], pl_s[NWV * 8];
+  __shared__ __attribute__((aligned(16))) bf16_raw pbuf[NWV][2][16][32];
+  __shared__ int last_s;
+
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int kvh = blockIdx.x, chunk = blockIdx.z;
+  const int arow = lane & 15, akq = lane >> 4;
+  ASTAMP(0);
+  const int by = blockIdx.y;
+  const int qrow = 2 * by + 1;
+  // ---- the load that does not need cur[]: q of the head (every wave reads it, wave 0 ropes it)
+  const float* qh = p.q + (long)qrow * p.ldq + p.q_off + kvh * HD;
+  const float qx1 = qh[lane], qx2 = qh[lane + 64];
+
+  const int pos = p.cur[by];
+  const int nkeys = p.len[by];
+  const int kvrow = by, head_row = by;
+  const int NZ = gridDim.z;
+  const int ngran = (nkeys + 31) >> 5;
+  const int gpw = (ngran <= 2 * NWV) ? max(p.gpw, 2) : p.gpw;
+  const int nchunks = min(NZ, max(1, (ngran + NWV * gpw - 1) / (NWV * gpw)));
+  if (chunk >= nchunks) return;
+  ASTAMP(1);
+  if (p.head_map && p.head_map[kvh] < 0) return;
+  const float rc = p.cos_t[(long)pos * 64 + lane], rs = p.sin_t[(long)pos * 64 + lane];
+
+  const long pair_keys = ((long)kvrow * p.n_kv_heads + kvh) * p.kv_cap;
+  const uint8_t* K8 = f8.k8 + pair_keys * HD;
+  const uint8_t* V8 = f8.v8 + pair_keys * HD;
+  const float* KS = f8.ks + pair_keys;
+  const float* VS = f8.vs + pair_keys;
+  const int klast = max(nkeys - 1, 0);
+  const int gstride = NWV * nchunks;
+  const int g_first = chunk * NWV + w;
+  auto load_gran = [&](F8Frag& f, int gi) {
+    const int key0 = gi << 5;
+    // K and its scales first (S = Q.K^T runs before P.V, and vmcnt retires in order), then V and its scales.  The quantiser writes
+    // whole granules, so every scale of granule gi < ngran is finite; K rows are clamped like the bf16 kernel's
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks)
+        f.kb[t][ks] = KVLOAD(reinterpret_cast<const uint2*>(K8 + (long)min(key0 + 16 * t + arow, klast) * HD + 32 * ks + 8 * akq));
+#pragma unroll
+    for (int t = 0; t < 2; ++t) f.ksc[t] = KVLOAD(KS + key0 + 16 * t + arow);
+    const uint8_t* Vblk = V8 + (long)gi * HD * 32;
+#pragma unroll
+    for (int nb = 0; nb < 8; ++nb) f.vb[nb] = KVLOAD(reinterpret_cast<const uint2*>(Vblk + (long)(16 * nb + arow) * 32 + 8 * akq));
+#pragma unroll
+    for (int t = 0; t < 2; ++t) f.vsc[t] = KVLOAD(VS + key0 + 16 * t + arow);
+  };
+  F8Frag fa, fb;
+  const bool have0 = g_first < ngran;
+  load_gran(fa, have0 ? g_first : 0);          // idle waves re-read granule 0 (cache hit) and never use it
+
+  // ---- RoPE(q) -> LDS.  Each value is one rounded product inside one fused multiply-add, and WHICH product is the rounded one is
+  // spelt out: it is what the compiler's contraction makes of `qx1 * rc - qx2 * rs, qx1 * rs + qx2 * rc` in k_attn_mfma<1, 1>
+  // (left to itself it fused the other product of the second value here, and q differed in the last bit)
+  if (w < G) {
+    const float qv[2] = {__builtin_fmaf(qx1, rc, -mul_rn(qx2, rs)), __builtin_fmaf(qx2, rc, mul_rn(qx1, rs))};
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+      const int D = lane + 64 * e;
+      __bf16 a, b, c;
+      split3(qv[e], a, b, c);
+      qf[D >> 5][0][w][(D >> 3) & 3][D & 7] = *reinterpret_cast<const bf16_raw*>(&a);
+      qf[D >> 5][1][w][(D >> 3) & 3][D & 7] = *reinterpret_cast<const bf16_raw*>(&b);
+      qf[D >> 5][2][w][(D >> 3) & 3][D & 7] = *reinterpret_cast<const bf16_raw*>(&c);
+    }
+  }
+  lds_barrier();     // q in LDS; global loads stay in flight
+  ASTAMP(2);
+
+  const float scale = 0.08838834764831845f;
+  f32x4 O[8];
+#pragma unroll
+  for (int nb = 0; nb < 8; ++nb) O[nb] = f32x4{0.f, 0.f, 0.f, 0.f};
+  float mrun = -INFINITY, lrun = 0.f;
+
+  auto consume = [&](F8Frag& f, int gi) {
+    const int key0 = gi << 5;
+    f32x4 S[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) {
+      const bf16x8 kx[2] = {expand_e4m3(f.kb[0][ks]), expand_e4m3(f.kb[1][ks])};
+#pragma unroll
+      for (int pl = 0; pl < DIA_NPLANES; ++pl) {
+        const bf16x8 qa = *reinterpret_cast<const bf16x8*>(&qf[ks][pl][0][akq][0]);
+#pragma unroll
+        for (int t = 0; t < 2; ++t) S[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qa, kx[t], S[t], 0, 0, 0);
+      }
+    }
+    // online softmax: in lanes 0..15, S[t][0] is the score of the head against key key0 + 16t + lane, in units of the key's K scale
+    const bool v0 = key0 + arow < nkeys, v1 = key0 + 16 + arow < nkeys;
+    const float s0 = v0 ? mul_rn(mul_rn(S[0][0], f.ksc[0]), scale) : -INFINITY, s1 = v1 ? mul_rn(mul_rn(S[1][0], f.ksc[1]), scale) : -INFINITY;
+    const float mnew = fmaxf(mrun, row16_max(fmaxf(s0, s1)));
+    const float alpha = (mrun == -INFINITY) ? 0.f : __expf(mrun - mnew);
+    const float p0 = (s0 == -INFINITY) ? 0.f : __expf(s0 - mnew), p1 = (s1 == -INFINITY) ? 0.f : __expf(s1 - mnew);
+    lrun = __builtin_fmaf(lrun, alpha, row16_sum(p0 + p1));      // (the sum takes the unscaled p; fused as in k_attn_mfma)
+    mrun = mnew;
+    if (lane < 16) {      // p * vs -> LDS as hi + lo bf16, [plane][head][key]
+      const float pv0 = mul_rn(p0, f.vsc[0]), pv1 = mul_rn(p1, f.vsc[1]);
+      const __bf16 h0 = (__bf16)pv0, h1 = (__bf16)pv1;
+      const __bf16 l0 = (__bf16)(pv0 - (float)h0), l1 = (__bf16)(pv1 - (float)h1);
+      pbuf[w][0][0][lane] = *reinterpret_cast<const bf16_raw*>(&h0);
+      pbuf[w][0][0][16 + lane] = *reinterpret_cast<const bf16_raw*>(&h1);
+      pbuf[w][1][0][lane] = *reinterpret_cast<const bf16_raw*>(&l0);
+      pbuf[w][1][0][16 + lane] = *reinterpret_cast<const bf16_raw*>(&l1);
+    }
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int nb = 0; nb < 8; ++nb) O[nb][0] *= alpha;
+    const bf16x8 pa0 = *reinterpret_cast<const bf16x8*>(&pbuf[w][0][arow][8 * akq]);
+    const bf16x8 pa1 = *reinterpret_cast<const bf16x8*>(&pbuf[w][1][arow][8 * akq]);
+#pragma unroll
+    for (int nb = 0; nb < 8; ++nb) {
+      const bf16x8 vx = expand_e4m3(f.vb[nb]);
+      O[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pa0, vx, O[nb], 0, 0, 0);
+      O[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pa1, vx, O[nb], 0, 0, 0);
+    }
+    __builtin_amdgcn_wave_barrier();     // pbuf is rewritten by the next granule
+  };
+
+  // k_attn_mfma's trip: steady state without a branch around a prefetch, then a tail of at most two granules
+  int gi = g_first;
+  for (; gi + 2 * gstride < ngran; gi += 2 * gstride) {
+    load_gran(fb, gi + gstride);
+    consume(fa, gi);
+    load_gran(fa, gi + 2 * gstride);
+    consume(fb, gi + gstride);
+  }
+  if (gi < ngran) {                // fa holds granule gi
+    const int g1 = gi + gstride;
+    if (g1 < ngran) load_gran(fb, g1);
+    consume(fa, gi);
+    if (g1 < ngran) consume(fb, g1);
+  }
+  ASTAMP(3);
+  if (lane < 16) {
+#pragma unroll
+    for (int nb = 0; nb < 8; ++nb) part[w * HD + 16 * nb + lane] = O[nb][0];
+    if (lane == 0) { pm_s[w * 8] = mrun; pl_s[w * 8] = lrun; }
+  }
+  __syncthreads();
+  ASTAMP(4);
+  attn_finish<G>(p, part, pm_s, pl_s, &last_s, tid, qrow, kvh, head_row, chunk, nchunks);
+}
+
+// OCP e4m3 (bias 7, subnormal step 2^-9, finite max 448 = 0x7E) of a finite x with |x| <= 448, rounded to nearest even
+__device__ __forceinline__ unsigned e4m3_rne(float x) {
+  unsigned u = __float_as_uint(x);
+  const unsigned s = (u >> 24) & 0x80u;
+  u &= 0x7fffffffu;
+  if (u < 0x3c800000u) return s | (unsigned)rintf(__uint_as_float(u) * 512.f);     // below 2^-6: multiples of 2^-9 (8 = the first normal)
+  u += 0x7ffffu + ((u >> 20) & 1u);          // three mantissa bits stay
+  return s | ((u >> 20) - (120u << 3));
+}
+// the scale of a key from the largest |bf16| bit pattern of its 128 values: bits of 2^e, e = the smallest with amax / 2^e <= 448
+// (448 = 1.75 * 2^8: e = exponent - 8, one more when the significand is above 1.75), at least -126; 1 for an all-zero key
+__device__ __forceinline__ unsigned kv_scale_bits(unsigned amax_bf16) {
+  if (amax_bf16 == 0) return 0x3f800000u;
+  const int se = (int)(amax_bf16 >> 7) - 8 + ((amax_bf16 & 0x7fu) > 0x60u ? 1 : 0);
+  return (unsigned)max(se, 1) << 23;
+}
+__device__ __forceinline__ unsigned e4m3x4(unsigned lo2, unsigned hi2, float inv) {      // four bf16 (two dwords) -> four bytes
+  return e4m3_rne(__uint_as_float(lo2 << 16) * inv) | e4m3_rne(__uint_as_float(lo2 & 0xffff0000u) * inv) << 8 |
+         e4m3_rne(__uint_as_float(hi2 << 16) * inv) << 16 | e4m3_rne(__uint_as_float(hi2 & 0xffff0000u) * inv) << 24;
+}
+__device__ __forceinline__ unsigned amax2(unsigned d) { return max(d & 0x7fffu, (d >> 16) & 0x7fffu); }
+
+struct KvQuantK {
+  const bf16_raw* kc; const bf16_raw* vc;
+  uint8_t* k8; uint8_t* v8; float* ks; float* vs;
+  int heads, S, n;
+  long kv_layer_stride, f8_layer_stride;
+  int row[DIA_SLOTS_PER_CALL], len[DIA_SLOTS_PER_CALL];
+};
+
+// grid (granule, head, layer * n + listed row), 256 threads: one 32-key granule of one (row, head) — 8 KB of K rows and the 8 KB
+// V block.  K: thread = (key, 16 dims), amax over the key's 8 threads by shuffles.  V (blocked [dim][32 keys]): thread = (dim, 16
+// keys), amax per key over the 128 dims through LDS (integer max of the |bf16| patterns).  16-byte loads and stores.
+__global__ __launch_bounds__(256) void k_kv_quantize_fp8(KvQuantK p) {
+  __shared__ unsigned vmax_s[32];
+  const int gi = blockIdx.x, h = blockIdx.y, i = blockIdx.z % p.n, l = blockIdx.z / p.n, tid = threadIdx.x;
+  const int len = p.len[i];
+  if (gi * 32 >= len) return;                     // (uniform) behind the row's last granule: not touched
+  const long pair_keys = ((long)p.row[i] * p.heads + h) * p.S;
+  const long in_off = l * p.kv_layer_stride + pair_keys * HD, out_off = l * p.f8_layer_stride + pair_keys * HD;
+  const long sc_off = l * (p.f8_layer_stride / HD) + pair_keys;
+  if (tid < 32) vmax_s[tid] = 0;
+  // every load first
+  const int r = tid >> 3, d0 = (tid & 7) * 16, key = gi * 32 + r;
+  const bf16_raw* kr = p.kc + in_off + (long)key * HD + d0;
+  const uint4 ka = *reinterpret_cast<const uint4*>(kr), kb = *reinterpret_cast<const uint4*>(kr + 8);
+  const int vd = tid >> 1, vk0 = (tid & 1) * 16;
+  const long vblk = (long)gi * HD * 32 + vd * 32 + vk0;
+  const uint4 va = *reinterpret_cast<const uint4*>(p.vc + in_off + vblk), vb = *reinterpret_cast<const uint4*>(p.vc + in_off + vblk + 8);
+  __syncthreads();
+  const unsigned kw[8] = {ka.x, ka.y, ka.z, ka.w, kb.x, kb.y, kb.z, kb.w};
+  const unsigned vw[8] = {va.x, va.y, va.z, va.w, vb.x, vb.y, vb.z, vb.w};
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {                   // keys vk0 + 2j, vk0 + 2j + 1 of dim vd
+    atomicMax(&vmax_s[vk0 + 2 * j], vw[j] & 0x7fffu);
+    atomicMax(&vmax_s[vk0 + 2 * j + 1], (vw[j] >> 16) & 0x7fffu);
+  }
+  // ---- K
+  {
+    unsigned am = 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) am = max(am, amax2(kw[j]));
+    am = max(am, (unsigned)__shfl_xor((int)am, 1, 64));
+    am = max(am, (unsigned)__shfl_xor((int)am, 2, 64));
+    am = max(am, (unsigned)__shfl_xor((int)am, 4, 64));
+    const bool live = key < len;
+    const unsigned sb = kv_scale_bits(live ? am : 0);
+    const float inv = live ? __uint_as_float((254u << 23) - sb) : 0.f;      // 1 / scale (a key past the length: zero bytes)
+    uint4 o;
+    o.x = e4m3x4(kw[0], kw[1], inv); o.y = e4m3x4(kw[2], kw[3], inv); o.z = e4m3x4(kw[4], kw[5], inv); o.w = e4m3x4(kw[6], kw[7], inv);
+    if (!live) o = uint4{0, 0, 0, 0};            // (no -0 bytes either)
+    *reinterpret_cast<uint4*>(p.k8 + out_off + (long)key * HD + d0) = o;
+    if ((tid & 7) == 0) p.ks[sc_off + key] = __uint_as_float(sb);
+  }
+  __syncthreads();
+  // ---- V
+  {
+    unsigned ob[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+      const int k = vk0 + j;
+      const bool live = gi * 32 + k < len;
+      const float inv = __uint_as_float((254u << 23) - kv_scale_bits(vmax_s[k]));
+      const unsigned hw = (j & 1) ? (vw[j >> 1] & 0xffff0000u) : (vw[j >> 1] << 16);
+      const unsigned byte = live ? e4m3_rne(__uint_as_float(hw) * inv) : 0u;
+      ob[j >> 2] |= byte << (8 * (j & 3));
+    }
+    *reinterpret_cast<uint4*>(p.v8 + out_off + vblk) = uint4{ob[0], ob[1], ob[2], ob[3]};
+    if (tid < 32) p.vs[sc_off + gi * 32 + tid] = __uint_as_float(gi * 32 + tid < len ? kv_scale_bits(vmax_s[tid]) : 0x3f800000u);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------
 // Encoder self-attention for the packed prefill batch (layers.py:385-462: bidirectional over the L non-pad
 // positions of each utterance, RoPE positions = byte indices).  Two launches per layer for ALL utterances:
 //   k_enc_kv_planes   K = RoPE(k) and V of every packed row as three bf16 planes each (hi+mid+lo == fp32
@@ -981,6 +1247,73 @@ extern "C" int dia_attn(const dia_attn_args* a, void* stream) {
     default:
       return dia_fail(DIA_E_ARG, "dia_attn: unknown mode");
   }
+}
+
+extern "C" int dia_attn_cross_fp8(const dia_attn_args* a, const dia_kv_fp8_ptrs* f, void* stream) {
+  if (!a || !f) return dia_fail(DIA_E_ARG, "dia_attn_cross_fp8: null argument");
+  if (!a->q || !a->kc || !a->vc || !a->P || !a->cos_t || !a->sin_t || !f->k8 || !f->v8 || !f->ks || !f->vs)
+    return dia_fail(DIA_E_ARG, "dia_attn_cross_fp8: null argument");
+  if (a->mode != DIA_ATTN_CROSS) return dia_fail(DIA_E_ARG, "dia_attn_cross_fp8: mode must be DIA_ATTN_CROSS");
+  if (a->group != 1) return dia_fail(DIA_E_ARG, "dia_attn_cross_fp8: group must be 1");
+  if (a->kv_dtype != DIA_KV_BF16 || !a->v_blocked) return dia_fail(DIA_E_ARG, "dia_attn_cross_fp8: kv_dtype must be DIA_KV_BF16 with the blocked V layout (v_blocked)");
+  if (a->kv_cap <= 0 || a->kv_cap % 32 != 0) return dia_fail(DIA_E_ARG, "dia_attn_cross_fp8: kv_cap must be a positive multiple of 32");
+  if (a->n_rows <= 0 || a->n_kv_heads <= 0) return dia_fail(DIA_E_ARG, "dia_attn_cross_fp8: empty problem");
+  if (a->p_plane_stride % 8 != 0) return dia_fail(DIA_E_ARG, "dia_attn_cross_fp8: plane stride must be a multiple of 8");
+  if (!a->cur || !a->len) return dia_fail(DIA_E_ARG, "dia_attn_cross_fp8: CROSS needs cur and len");
+  if ((a->n_kv_heads * 128 + 31) / 32 > a->p_ktiles) return dia_fail(DIA_E_ARG, "dia_attn_cross_fp8: output planes too narrow");
+  if (((uintptr_t)f->k8 & 7) || ((uintptr_t)f->v8 & 7) || ((uintptr_t)f->ks & 3) || ((uintptr_t)f->vs & 3))
+    return dia_fail(DIA_E_ARG, "dia_attn_cross_fp8: k8 / v8 must be 8-byte aligned, ks / vs 4-byte");
+  // the key split of dia_attn, so that the slabs merge in the same order
+  const int cap_chunks = (a->kv_cap + CHUNK - 1) / CHUNK;
+  int max_chunks = (512 + a->n_rows * a->n_kv_heads - 1) / (a->n_rows * a->n_kv_heads);
+  if (dia_tune(DIA_TUNE_ATTN_NZ) > 0) max_chunks = dia_tune(DIA_TUNE_ATTN_NZ);
+  if (max_chunks > cap_chunks) max_chunks = cap_chunks;
+  if (max_chunks < 1) max_chunks = 1;
+  if (max_chunks > 1 && (!a->scratch || !a->tickets)) return dia_fail(DIA_E_ARG, "dia_attn_cross_fp8: more than 128 keys possible: scratch and tickets are required");
+  AttnK k = {};
+  k.mode = a->mode; k.n_kv_heads = a->n_kv_heads; k.n_rows = a->n_rows; k.kv_cap = a->kv_cap;
+  k.q = a->q; k.ldq = a->ldq; k.q_off = a->q_off;
+  k.kc = a->kc; k.vc = a->vc; k.cur = a->cur; k.len = a->len;
+  k.cos_t = a->cos_t; k.sin_t = a->sin_t;
+  k.P = (bf16_raw*)a->P; k.p_plane_stride = a->p_plane_stride; k.p_ktiles = a->p_ktiles; k.act_f32 = a->act_f32;
+  k.head_map = a->head_map; k.v_blocked = 1;
+  k.gpw = 1;
+  { const int g = dia_tune(DIA_TUNE_ATTN_GPW_CROSS); if (g > 0) k.gpw = g; }
+  k.scratch = a->scratch; k.tickets = a->tickets; k.max_chunks = cap_chunks;
+  const AttnF8 f8 = {(const uint8_t*)f->k8, (const uint8_t*)f->v8, f->ks, f->vs};
+  dia_launch<k_attn_mfma_f8>(dim3(a->n_kv_heads, a->n_rows, max_chunks), dim3(NT), 0, (hipStream_t)stream, k, f8);
+  return dia_check_launch("k_attn_mfma_f8");
+}
+
+extern "C" int dia_kv_quantize_fp8(const dia_kv_fp8_args* a, void* stream) {
+  if (!a || !a->kc || !a->vc || !a->out.k8 || !a->out.v8 || !a->out.ks || !a->out.vs) return dia_fail(DIA_E_ARG, "dia_kv_quantize_fp8: null argument");
+  if (a->B <= 0 || a->heads <= 0 || a->S <= 0 || a->S % 32 != 0) return dia_fail(DIA_E_ARG, "dia_kv_quantize_fp8: B, heads and S must be positive, S a multiple of 32");
+  if (a->n < 1 || a->n > DIA_SLOTS_PER_CALL || !a->row || !a->len) return dia_fail(DIA_E_ARG, "dia_kv_quantize_fp8: empty row list (1..64 rows with their lengths per call)");
+  if (a->n_layer < 0) return dia_fail(DIA_E_ARG, "dia_kv_quantize_fp8: negative layer count");
+  const int nl = a->n_layer > 1 ? a->n_layer : 1;
+  const int64_t layer_elems = (int64_t)a->B * a->heads * a->S * HD;
+  if (nl > 1 && (a->kv_layer_stride < layer_elems || a->kv_layer_stride % 8 != 0 || a->f8_layer_stride < layer_elems || a->f8_layer_stride % 2048 != 0))
+    return dia_fail(DIA_E_ARG, "dia_kv_quantize_fp8: layer strides must cover a layer (B * heads * S * 128), kv a multiple of 8, f8 of 2048");
+  if ((long)nl * a->n > 65535 || a->heads > 65535) return dia_fail(DIA_E_ARG, "dia_kv_quantize_fp8: too many layers x rows or heads for one grid");
+  if (((uintptr_t)a->kc & 15) || ((uintptr_t)a->vc & 15) || ((uintptr_t)a->out.k8 & 15) || ((uintptr_t)a->out.v8 & 15) || ((uintptr_t)a->out.ks & 3) || ((uintptr_t)a->out.vs & 3))
+    return dia_fail(DIA_E_ARG, "dia_kv_quantize_fp8: kc / vc / k8 / v8 must be 16-byte aligned, ks / vs 4-byte");
+  KvQuantK k = {};
+  k.kc = (const bf16_raw*)a->kc; k.vc = (const bf16_raw*)a->vc;
+  k.k8 = (uint8_t*)a->out.k8; k.v8 = (uint8_t*)a->out.v8; k.ks = a->out.ks; k.vs = a->out.vs;
+  k.heads = a->heads; k.S = a->S; k.n = a->n;
+  k.kv_layer_stride = nl > 1 ? a->kv_layer_stride : 0; k.f8_layer_stride = nl > 1 ? a->f8_layer_stride : 0;
+  int max_len = 0;
+  for (int i = 0; i < a->n; ++i) {
+    k.row[i] = a->row[i]; k.len[i] = a->len[i];
+    if (k.row[i] < 0 || k.row[i] >= a->B) return dia_fail(DIA_E_ARG, "dia_kv_quantize_fp8: row outside [0, B)");
+    if (k.len[i] < 0 || k.len[i] > a->S) return dia_fail(DIA_E_ARG, "dia_kv_quantize_fp8: length outside [0, S]");
+    for (int j = 0; j < i; ++j)
+      if (k.row[j] == k.row[i]) return dia_fail(DIA_E_ARG, "dia_kv_quantize_fp8: row listed twice");
+    if (k.len[i] > max_len) max_len = k.len[i];
+  }
+  if (max_len == 0) return DIA_OK;               // empty texts only: no granule to write
+  dia_launch<k_kv_quantize_fp8>(dim3((max_len + 31) / 32, a->heads, nl * a->n), dim3(256), 0, (hipStream_t)stream, k);
+  return dia_check_launch("k_kv_quantize_fp8");
 }
 
 extern "C" int dia_enc_kv_prep(const float* qkv, int ldq, int k_off, int v_off, int heads, int L, int cap,

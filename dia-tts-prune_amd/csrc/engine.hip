@@ -33,6 +33,7 @@ struct dia_engine {
   std::vector<dia_lora_layer> lora;     // dia_engine_set_lora: the adapter tables of the two decode sites per layer (empty: no LoRA launches)
   const int32_t* lora_slot = nullptr;   // ... and the device array adapter_of_slot [B]
   int lora_adapters = 0;
+  std::vector<dia_kv_fp8_ptrs> f8kv;    // dia_engine_set_cross_fp8: the e4m3 copy of every layer's cross caches (empty: the bf16 caches)
   std::vector<hipEvent_t> prof;   // when non-empty: one event recorded after every launch (profile step)
   // weight prefetch beside the chain (graph mode): launch i+lookahead's weights are pulled into the
   // Infinity Cache by a side stream as soon as launch i has been issued
@@ -342,7 +343,7 @@ static int enqueue_step(dia_engine* e, bool with_sampler) {
         a.q = d.qc; a.ldq = d.cq_heads * 128; a.len = d.text_len;
         a.kc = L.k_cross; a.vc = L.v_cross; a.head_map = L.hmap_cross; a.kv_plane_stride = d.kv_plane_cross;
       }
-      rc = dia_attn(&a, st);
+      rc = (what == ATTN_CROSS && !e->f8kv.empty()) ? dia_attn_cross_fp8(&a, &e->f8kv[l], st) : dia_attn(&a, st);
     } else if (what == SEG_MLP) {
       dia_seg_args sa = {};
       sa.a_in = (const float*)d.planes_a; sa.a_ktiles = akt; sa.M = R; sa.W = e->seg_w[l];
@@ -677,6 +678,19 @@ extern "C" int dia_engine_set_lora(dia_engine* e, const dia_lora_step* s) {
       if (rc) { e->lora.clear(); e->lora_slot = nullptr; e->lora_adapters = 0; return rc; }
     }
   }
+  return DIA_OK;
+}
+
+extern "C" int dia_engine_set_cross_fp8(dia_engine* e, const dia_kv_fp8_ptrs* layers) {
+  if (!e) return dia_fail(DIA_E_ARG, "dia_engine_set_cross_fp8: null engine");
+  if (e->exec || e->launches > 0) return dia_fail(DIA_E_STATE, "dia_engine_set_cross_fp8: a step has already been issued or captured");
+  if (!layers) { e->f8kv.clear(); return DIA_OK; }
+  const dia_engine_desc& d = e->d;
+  if (d.kv_dtype != DIA_KV_BF16 || !d.v_blocked || d.S <= 0 || d.S % 32 != 0)
+    return dia_fail(DIA_E_ARG, "dia_engine_set_cross_fp8: the engine needs bf16 K/V (DIA_KV_BF16) with the blocked V layout and S % 32 == 0");
+  for (int l = 0; l < d.n_layer; ++l)
+    if (!layers[l].k8 || !layers[l].v8 || !layers[l].ks || !layers[l].vs) return dia_fail(DIA_E_ARG, "dia_engine_set_cross_fp8: null buffer in a layer");
+  e->f8kv.assign(layers, layers + d.n_layer);
   return DIA_OK;
 }
 

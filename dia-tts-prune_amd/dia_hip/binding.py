@@ -26,6 +26,7 @@ EXPORTS = (
     "dia_engine_decode", "dia_engine_set_prefetch", "dia_engine_set_x_alt", "dia_engine_step_logits_only", "dia_engine_profile_step", "dia_engine_time_step", "dia_timed_kernel_name", "dia_engine_launches_per_step", "dia_mxfp8_classes", "dia_mxfp4_classes", "dia_engine_set_mxfp4",
     "dia_score", "dia_engine_set_score",
     "dia_lora_apply", "dia_lora_crosskv", "dia_engine_set_lora",
+    "dia_kv_quantize_fp8", "dia_attn_cross_fp8", "dia_engine_set_cross_fp8",
     "dia_seg_mlp", "dia_seg_workspace_bytes", "dia_seg_workspace_control_bytes", "dia_seg_slots", "dia_seg_supported", "dia_seg_error",
 )
 
@@ -218,6 +219,21 @@ class LoraStep(C.Structure):
     _fields_ = [("n_layer", C.c_int32), ("n_adapters", C.c_int32), ("layers", C.POINTER(LoraLayer)), ("adapter_of_slot", C.c_void_p)]
 
 
+class KvFp8Ptrs(C.Structure):
+    """dia_kv_fp8_ptrs: the e4m3 copy of one layer's cross caches (k8 / v8 bytes, ks / vs one fp32 scale per key and head)"""
+    _fields_ = [("k8", C.c_void_p), ("v8", C.c_void_p), ("ks", C.c_void_p), ("vs", C.c_void_p)]
+
+
+class KvFp8Args(C.Structure):
+    """dia_kv_fp8_args: `row` and `len` are HOST arrays read during the call, everything else device pointers and shapes"""
+    _fields_ = [
+        ("kc", C.c_void_p), ("vc", C.c_void_p), ("out", KvFp8Ptrs),
+        ("B", C.c_int32), ("heads", C.c_int32), ("S", C.c_int32), ("n", C.c_int32),
+        ("row", C.POINTER(C.c_int32)), ("len", C.POINTER(C.c_int32)),
+        ("n_layer", C.c_int32), ("_pad0", C.c_int32), ("kv_layer_stride", C.c_int64), ("f8_layer_stride", C.c_int64),
+    ]
+
+
 class DecLayer(C.Structure):
     _fields_ = [
         ("w_qkv", C.c_void_p), ("w_o", C.c_void_p), ("w_cq", C.c_void_p), ("w_co", C.c_void_p),
@@ -340,6 +356,9 @@ def lib() -> C.CDLL:
     L.dia_lora_apply.argtypes = [C.POINTER(LoraArgs), C.c_void_p]
     L.dia_lora_crosskv.argtypes = [C.POINTER(LoraCrossKvArgs), C.c_void_p]
     L.dia_engine_set_lora.argtypes = [C.c_void_p, C.POINTER(LoraStep)]
+    L.dia_kv_quantize_fp8.argtypes = [C.POINTER(KvFp8Args), C.c_void_p]
+    L.dia_attn_cross_fp8.argtypes = [C.POINTER(AttnArgs), C.POINTER(KvFp8Ptrs), C.c_void_p]
+    L.dia_engine_set_cross_fp8.argtypes = [C.c_void_p, C.POINTER(KvFp8Ptrs)]
     L.dia_seg_mlp.argtypes = [C.POINTER(SegArgs), C.c_void_p]
     L.dia_seg_workspace_bytes.restype = C.c_int64
     L.dia_seg_workspace_control_bytes.restype = C.c_int64

@@ -503,7 +503,8 @@ class DecodeSession:
                  teacher_tokens: Optional[Sequence[np.ndarray]] = None, stream: Optional[torch.cuda.Stream] = None,
                  s_cap: Optional[int] = None, audio_prompts: Optional[Sequence[Optional[np.ndarray]]] = None,
                  prompt_prefill: str = "auto", attention: str = "auto", score: bool = False,
-                 adapters=None, adapter_ids: Optional[Sequence[Union[None, str, int]]] = None, _slotted: bool = False):
+                 adapters=None, adapter_ids: Optional[Sequence[Union[None, str, int]]] = None, cross_kv: str = "bf16",
+                 _slotted: bool = False):
         """audio_prompts: per utterance None or int codes [Tp, C] (reference model.py:311-353).  The prompt
         rows are replayed through the decode step before sampling starts (semantics: oracle.generate), or — with
         bf16 caches — prefilled as one packed MFMA batch; prompt_prefill="replay" forces the replay.
@@ -512,13 +513,18 @@ class DecodeSession:
         device (dia_score; DESIGN.md "Scoring"); scores_host() downloads the [B, T, C, 3] result once at the end.
         adapters: a lora.AdapterBank whose adapters stay UNMERGED beside the base weights (DESIGN.md "Per-request adapters");
         adapter_ids[b] = name or index of utterance b's adapter, None = base model.  The bank is fixed from here on.  Such a session
-        replays audio prompts through the decode step (no batched prompt prefill), and refuses a compacted model and seg="on"."""
+        replays audio prompts through the decode step (no batched prompt prefill), and refuses a compacted model and seg="on".
+        cross_kv="fp8": the decode step's cross-attention reads an e4m3 copy of the cross caches with one power-of-two scale per key
+        and head (DESIGN.md "FP8 cross K/V"), quantised from the bf16 caches behind every encoder pass; needs bf16 K/V with the
+        blocked V layout.  "bf16" (default): nothing of it exists."""
         if adapter_ids is not None and adapters is None:
             raise ValueError("adapter_ids needs adapters= (an AdapterBank)")
         if score and (teacher_tokens is None or _slotted):
             raise ValueError("score=True scores teacher-forced rows of a closed batch: pass teacher_tokens (and no slots)")
         if prompt_prefill not in ("auto", "replay") or attention not in ("auto", "valu"):
             raise ValueError("prompt_prefill must be 'auto' or 'replay', attention 'auto' or 'valu'")
+        if cross_kv not in ("bf16", "fp8"):
+            raise ValueError("cross_kv must be 'bf16' or 'fp8'")
         self.prompt_prefill = prompt_prefill
         cfg, dev = w.cfg, w.device
         self.w, self.cfg, self.dev = w, cfg, dev
@@ -538,6 +544,13 @@ class DecodeSession:
             raise ValueError("kv_dtype 'bf16x2' is served by the MFMA attention kernel only")
         # bf16 caches keep V blocked as [key/32][128][32] for the MFMA attention kernel
         self.v_blocked = int(self.kv_code in (hb.KV_BF16, hb.KV_BF16X2) and attention != "valu")
+        if cross_kv == "fp8":
+            if self.kv_code != hb.KV_BF16:
+                raise ValueError(f"cross_kv='fp8' is quantised from one-plane bf16 cross caches: kv_dtype '{kv_dtype}' (fp32 or two-plane K/V) "
+                                 "is not served")
+            if attention == "valu" or not self.v_blocked:
+                raise ValueError("cross_kv='fp8' needs the blocked V layout of the MFMA attention kernel (attention='valu' keeps V row-major)")
+        self.cross_kv = cross_kv
         kvt = torch.float32 if self.kv_code == hb.KV_F32 else torch.bfloat16
         self.kv_planes = 2 if self.kv_code == hb.KV_BF16X2 else 1
         self.stream = stream if stream is not None else torch.cuda.Stream(device=dev)
@@ -588,6 +601,14 @@ class DecodeSession:
         self.v_cross_all = z(d.n_layer, *pl, B, d.cross_query_heads, self.S, HEAD_DIM, dt=kvt)
         self.k_cross = [self.k_cross_all[i] for i in range(d.n_layer)]
         self.v_cross = [self.v_cross_all[i] for i in range(d.n_layer)]
+        # cross_kv="fp8": the e4m3 copy the step's cross-attention reads, all layers in one allocation each like the bf16 caches (which
+        # stay: +50 % cross-cache memory); zero bytes and zero scales until dia_kv_quantize_fp8 writes a row's granules
+        self.k8_cross_all = self.v8_cross_all = self.ks_cross_all = self.vs_cross_all = None
+        if cross_kv == "fp8":
+            self.k8_cross_all = z(d.n_layer, B, d.cross_query_heads, self.S, HEAD_DIM, dt=torch.uint8)
+            self.v8_cross_all = z(d.n_layer, B, d.cross_query_heads, self.S // 32, HEAD_DIM, 32, dt=torch.uint8)
+            self.ks_cross_all = z(d.n_layer, B, d.cross_query_heads, self.S)
+            self.vs_cross_all = z(d.n_layer, B, d.cross_query_heads, self.S)
         self.kv_plane_self = self.R * d.kv_heads * self.T * HEAD_DIM if self.kv_planes > 1 else 0
         self.kv_plane_cross = B * d.cross_query_heads * self.S * HEAD_DIM if self.kv_planes > 1 else 0
         self.text_len = torch.tensor(self.lens, dtype=torch.int32, device=dev)
@@ -806,6 +827,12 @@ class DecodeSession:
                  "dia_engine_create")
         if self.x_alt is not None:
             hb.check(hb.lib().dia_engine_set_x_alt(self._engine, hb.ptr(self.x_alt)), "dia_engine_set_x_alt")
+        if self.cross_kv == "fp8":                                          # the step's cross-attention reads the e4m3 copy
+            f8 = (hb.KvFp8Ptrs * n)()                                       # (the engine copies the array)
+            for i in range(n):
+                f8[i].k8, f8[i].v8 = hb.ptr(self.k8_cross_all[i]), hb.ptr(self.v8_cross_all[i])
+                f8[i].ks, f8[i].vs = hb.ptr(self.ks_cross_all[i]), hb.ptr(self.vs_cross_all[i])
+            hb.check(hb.lib().dia_engine_set_cross_fp8(self._engine, f8), "dia_engine_set_cross_fp8")
         if w.quant == "mxfp4":                                              # MXFP4 streams (quant="mxfp4"): beside the description
             f4_layers = (hb.Mxfp4Layer * n)()                               # (the engine copies the array)
             for i, L in enumerate(w.dec_layers):
@@ -1002,11 +1029,30 @@ class DecodeSession:
                      ca.sin_t) = cross_kv(self.k_cross[i], self.v_cross[i])
                     ca.rope_rows = w.cos_t.shape[0]
                     hb.check(L.dia_lora_crosskv(C.byref(ca), st), "dia_lora_crosskv")
+                if self.cross_kv == "fp8":         # behind the CROSSKV epilogue AND the adapters' corrections: the copy the step reads
+                    self._quantize_cross(utt, lens)
                 if keep_encoder_out:
                     for i in live:
                         Lb, o = lens[i], offs[i]
                         inv = torch.rsqrt(ssq[:, o: o + Lb].sum(dim=0) / E + eps)
                         self.enc_out[utt[i]] = (x[o: o + Lb] * inv[:, None] * w.enc_norm[None, :]).clone()
+
+    def _quantize_cross(self, utt: Sequence[int], lens: Sequence[int]):
+        """dia_kv_quantize_fp8 for exactly these utterances' rows of the cross caches: ONE launch over all decoder layers per
+        DIA_SLOTS_PER_CALL rows, on the session's stream (the caller holds it)."""
+        d = self.cfg.model.decoder
+        st = C.c_void_p(self.stream.cuda_stream)
+        for i0 in range(0, len(utt), hb.SLOTS_PER_CALL):
+            rows, ln = list(utt[i0: i0 + hb.SLOTS_PER_CALL]), list(lens[i0: i0 + hb.SLOTS_PER_CALL])
+            a = hb.KvFp8Args()
+            a.kc, a.vc = hb.ptr(self.k_cross_all), hb.ptr(self.v_cross_all)
+            a.out.k8, a.out.v8 = hb.ptr(self.k8_cross_all), hb.ptr(self.v8_cross_all)
+            a.out.ks, a.out.vs = hb.ptr(self.ks_cross_all), hb.ptr(self.vs_cross_all)
+            a.B, a.heads, a.S, a.n = self.B, d.cross_query_heads, self.S, len(rows)
+            a.row, a.len = (C.c_int32 * len(rows))(*rows), (C.c_int32 * len(rows))(*ln)
+            a.n_layer = d.n_layer
+            a.kv_layer_stride = a.f8_layer_stride = self.k_cross[0].numel()
+            hb.check(hb.lib().dia_kv_quantize_fp8(C.byref(a), st), "dia_kv_quantize_fp8")
 
     # ------------------------------------------------------------------ audio-prompt prefill, batched
     def _prompt_prefill_batched(self) -> bool:
@@ -1215,7 +1261,7 @@ class DecodeSession:
     def open(cls, w: DeviceWeights, slots: int, *, s_cap: Optional[int] = None, kv_dtype: str = "bf16",
              max_tokens: Optional[int] = None, ignore_eos: bool = False, stream: Optional[torch.cuda.Stream] = None,
              cfg_scale: float = 3.0, temperature: float = 1.3, top_p: float = 0.95, top_k: int = 35,
-             attention: str = "auto", stream_cap: Optional[int] = None, adapters=None) -> "DecodeSession":
+             attention: str = "auto", stream_cap: Optional[int] = None, adapters=None, cross_kv: str = "bf16") -> "DecodeSession":
         """A session of `slots` PARKED slots for a stream of requests: admit() puts a request into a free slot between two decode
         steps, the step graph (captured once) serves whatever the slots hold, retire() parks a finished one; serve() is the
         driver loop.  Cross caches are sized for texts of `s_cap` bytes (default: the encoder's text_length), the noise buffer for
@@ -1237,7 +1283,7 @@ class DecodeSession:
         empty = np.zeros((0,), dtype=np.int32)
         s = cls(w, [empty] * int(slots), kv_dtype=kv_dtype, max_tokens=max_tokens, cfg_scale=cfg_scale, temperature=temperature,
                 top_p=top_p, top_k=top_k, ignore_eos=ignore_eos, stream=stream, s_cap=_ceil(cap, 32), attention=attention,
-                adapters=adapters, _slotted=True)
+                adapters=adapters, cross_kv=cross_kv, _slotted=True)
         s.text_cap = cap                           # (the caches hold whole 32-key blocks; requests are held to what was asked for)
         if stream_cap is not None:
             s._init_stream(int(stream_cap))

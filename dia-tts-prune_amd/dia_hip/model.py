@@ -77,6 +77,10 @@ class Dia:
     # streams, which decode steps of batch 1-8 stream instead of the dense tiles (DeviceWeights quant="mxfp8"); "mxfp4": the same
     # for an MXFP4-quantised checkpoint (offline_quantize.py --format mxfp4, DeviceWeights quant="mxfp4"); "bf16" = dense
     weight_format = "bf16"
+    # "fp8": every session of generate* / stream_frames / score* keeps an e4m3 copy of the cross K/V caches with one power-of-two
+    # scale per key and head, and its decode steps read that instead of the bf16 caches (DecodeSession cross_kv="fp8"; needs a
+    # bf16 compute_dtype).  "bf16" = the caches as they are
+    cross_kv = "bf16"
 
     def __init__(self, config: DiaConfig, compute_dtype: Union[str, ComputeDtype] = ComputeDtype.FLOAT32,
                  device: Optional[torch.device] = None):
@@ -245,7 +249,7 @@ class Dia:
         bank = self._bank_for(adapters)
         t0 = time.time()
         with torch.cuda.device(self.device):
-            s = DecodeSession(self.model, ids, kv_dtype=self._kv_dtype(), max_tokens=max_tokens, cfg_scale=cfg_scale,
+            s = DecodeSession(self.model, ids, kv_dtype=self._kv_dtype(), cross_kv=self.cross_kv, max_tokens=max_tokens, cfg_scale=cfg_scale,
                               temperature=temperature, top_p=top_p, top_k=top_k, seeds=seeds, ignore_eos=ignore_eos,
                               audio_prompts=audio_prompts, adapters=bank, adapter_ids=adapters if bank is not None else None)
             try:
@@ -319,7 +323,7 @@ class Dia:
             raise ValueError("score_batch: one adapter entry per text")
         bank = self._bank_for(adapters)
         with torch.cuda.device(self.device):
-            s = DecodeSession(self.model, ids, kv_dtype=self._kv_dtype(), max_tokens=mt, cfg_scale=cfg_scale, temperature=0.0,
+            s = DecodeSession(self.model, ids, kv_dtype=self._kv_dtype(), cross_kv=self.cross_kv, max_tokens=mt, cfg_scale=cfg_scale, temperature=0.0,
                               teacher_tokens=rows, audio_prompts=prompts, score=True, adapters=bank,
                               adapter_ids=adapters if bank is not None else None)
             try:
@@ -365,7 +369,7 @@ class Dia:
             s_cap = max(32, max(len(r.text_ids) for r in reqs))
         with torch.cuda.device(self.device):
             s = DecodeSession.open(self.model, min(int(slots), len(reqs)), s_cap=min(int(s_cap), self.config.data.text_length),
-                                   kv_dtype=self._kv_dtype(), max_tokens=cap, ignore_eos=ignore_eos, adapters=bank)
+                                   kv_dtype=self._kv_dtype(), cross_kv=self.cross_kv, max_tokens=cap, ignore_eos=ignore_eos, adapters=bank)
             try:
                 for i, res in s.serve_iter(reqs, poll=poll):
                     yield i, codes_for_codec(res.codes, self.config)
@@ -400,7 +404,7 @@ class Dia:
             s_cap = max(32, max(len(r.text_ids) for r in reqs))
         with torch.cuda.device(self.device):
             s = DecodeSession.open(self.model, min(int(slots), len(reqs)), s_cap=min(int(s_cap), self.config.data.text_length),
-                                   kv_dtype=self._kv_dtype(), max_tokens=cap, ignore_eos=ignore_eos,
+                                   kv_dtype=self._kv_dtype(), cross_kv=self.cross_kv, max_tokens=cap, ignore_eos=ignore_eos,
                                    stream_cap=4 * int(chunk) if stream_cap is None else int(stream_cap), adapters=bank)
             try:
                 yield from s.stream_iter(reqs, chunk=chunk, lag=lag)

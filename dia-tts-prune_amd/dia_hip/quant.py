@@ -144,3 +144,30 @@ def mxfp4_quantize_state_dict(cfg: DiaConfig, sd: Dict[str, torch.Tensor]) -> "O
         w = sd[name]
         out[name] = mxfp4_round_2d(_kernel_2d(name, w.float())).reshape(w.shape)
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# FP8 cross K/V (DESIGN.md "FP8 cross K/V"): e4m3 elements with ONE scale per key (the 128 values of a head's K or V row), the
+# reference dia_kv_quantize_fp8 (csrc/attn.hip) is pinned to.  The scale is the smallest power of two 2^e with amax / 2^e <= 448
+# (so amax / scale lies in (224, 448] and nothing saturates), e >= KV_E_MIN (the smallest normal fp32), 1 for an all-zero key;
+# elements round to nearest even.  An e4m3 value times a power of two is a bf16 value: the dequantised cache is an ordinary bf16
+# cache, and quantising it again returns the same bytes and scales.
+KV_E_MIN = -126
+
+
+def quantize_kv_fp8(x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """[..., 128] (any float dtype; keys in the second-to-last position or flattened into the lead) -> (bytes uint8 [..., 128]
+    (e4m3fn bits), scales float32 [...]), one scale per row of the last axis"""
+    xf = x.float()
+    amax = xf.abs().amax(dim=-1)
+    m, ex = torch.frexp(amax)                                             # amax = m * 2^ex, m in [0.5, 1); 448 = 0.875 * 2^9
+    e = ex.to(torch.int32) - 9 + (m > 0.875).to(torch.int32)
+    e = torch.where(amax > 0, e, torch.zeros_like(e)).clamp_(min=KV_E_MIN)
+    scaled = torch.ldexp(xf, -e[..., None]).clamp_(-E4M3_MAX, E4M3_MAX)   # exact: a power-of-two factor (the clamp never bites)
+    q = scaled.to(torch.float8_e4m3fn).view(torch.uint8)
+    return q.contiguous(), torch.ldexp(torch.ones_like(amax), e).contiguous()
+
+
+def dequantize_kv_fp8(q: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
+    """inverse of quantize_kv_fp8: float32 [..., 128] = e4m3(byte) x scale, every value bf16-representable"""
+    return q.contiguous().view(torch.float8_e4m3fn).float() * scales[..., None].float()

@@ -787,6 +787,56 @@ typedef struct {
  * refuses.  NULL = the step without it, launch for launch. */
 int dia_engine_set_lora(dia_engine* e, const dia_lora_step* s);
 
+/* ------------------------------------------------------------------------------------------------
+ * FP8 cross K/V (csrc/attn.hip; DESIGN.md "FP8 cross K/V").  The cross caches are written once per request and read on every
+ * step: a second, OCP e4m3 copy of them (finite max 448) with one power-of-two scale per key and head halves what the step reads.
+ * The bf16 cross caches stay as they are (the cross-K/V GEMM, dia_lora_crosskv and the prompt prefill keep writing / reading
+ * them); the copy is made from them by dia_kv_quantize_fp8 and read by dia_attn_cross_fp8.  The reference has no counterpart
+ * (its cross caches are bf16 or fp32 tensors, state.py:142-151).  Everything below is appended: no existing struct or entry point
+ * changed.
+ *   k8  uint8 [B][heads][S][128]          row layout of the bf16 K cache
+ *   v8  uint8 [B][heads][S/32][128][32]   the blocked V layout (dia_attn_args.v_blocked)
+ *   ks, vs  float [B][heads][S]           scale of key s: the smallest 2^e (e >= -126) with amax / 2^e <= 448 over the key's 128
+ *                                         values, 1 for an all-zero key; value = e4m3(byte) * scale, rounded to nearest even
+ * All four zero-initialised once by the caller (a zero byte times any finite scale is 0).
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct {
+  void* k8;
+  void* v8;
+  float* ks;
+  float* vs;
+} dia_kv_fp8_ptrs;
+/* ONE launch quantises the bf16 cross K and V of the listed cache rows (utterances / slots), in stream order behind whatever wrote
+ * them: row[i] gets len[i] keys, always in WHOLE 32-key granules — keys from len[i] to the end of its last granule receive zero
+ * bytes and scale 1, so a masked key of a re-used slot never contributes a stale NaN pattern.  Granules behind that and rows that
+ * are not listed are not touched.  n_layer > 1: the same rows of n_layer layers whose caches lie kv_layer_stride ELEMENTS apart
+ * (kc / vc) and f8_layer_stride elements apart (k8 / v8; ks / vs: f8_layer_stride / 128 floats).  The row and length lists are
+ * HOST arrays read during the call (they travel as kernel arguments); at most DIA_SLOTS_PER_CALL rows per call. */
+typedef struct {
+  const void* kc;              /* bf16 [B][heads][S][128] */
+  const void* vc;              /* bf16 [B][heads][S/32][128][32] */
+  dia_kv_fp8_ptrs out;         /* (of the first layer) */
+  int32_t B, heads, S;         /* S a multiple of 32 */
+  int32_t n;                   /* rows in this call, 1..DIA_SLOTS_PER_CALL */
+  const int32_t* row;          /* host [n], distinct, each < B */
+  const int32_t* len;          /* host [n], each in [0, S] */
+  int32_t n_layer;             /* 0 or 1: one layer */
+  int32_t _pad0;
+  int64_t kv_layer_stride;     /* n_layer > 1: at least B * heads * S * 128, a multiple of 8 */
+  int64_t f8_layer_stride;     /* n_layer > 1: at least B * heads * S * 128, a multiple of 2048 */
+} dia_kv_fp8_args;
+int dia_kv_quantize_fp8(const dia_kv_fp8_args* a, void* stream);
+/* dia_attn for DIA_ATTN_CROSS over the e4m3 copy: the MFMA kernel of the one-plane bf16 caches with 8-byte K and V fragments
+ * expanded to bf16 in registers and the scales folded in behind the MFMAs (score * ks before the softmax scale, p * vs before p is
+ * split for P.V) — bit for bit what dia_attn computes over bf16 caches holding the dequantised values, with the same key split.
+ * *a describes the launch as for dia_attn (kc / vc: the bf16 caches, validated, not read).  Refused with DIA_E_ARG: anything but
+ * mode == DIA_ATTN_CROSS, group == 1, v_blocked, kv_dtype == DIA_KV_BF16 and kv_cap % 32 == 0, and what dia_attn refuses. */
+int dia_attn_cross_fp8(const dia_attn_args* a, const dia_kv_fp8_ptrs* p, void* stream);
+/* before the first step (DIA_E_STATE afterwards): the step's cross-attention launch of layer l is dia_attn_cross_fp8 over
+ * layers[l] from then on, launch for launch in the place of dia_attn.  DIA_E_ARG unless the engine has bf16 K/V with blocked V
+ * and S % 32 == 0.  NULL = dia_attn over the bf16 caches, as without the call. */
+int dia_engine_set_cross_fp8(dia_engine* e, const dia_kv_fp8_ptrs* layers /* host [n_layer], copied */);
+
 #ifdef __cplusplus
 }
 #endif
