@@ -7,7 +7,8 @@ Differences, all forced by the platform: the device is always the HIP device (th
 LoRA adapters are merged into the dense weights at load (``--adapter-path``, dia_hip/lora.py) instead of wrapped by PEFT, or kept
 unmerged beside them and chosen per run / per chunk (``--adapter NAME=DIR`` ... ``--use-adapter NAME``);
 ``--codes-output`` (build-only) saves the codec input ``[1, 9, T]`` as .npy, which is the only possible
-output where the Descript Audio Codec is not installed; ``--no-dac`` skips loading it.
+output where neither codec is available; ``--no-dac`` skips loading the third-party one.  ``--codec-path FILE`` (build-only) loads
+the native DAC decoder (dia_hip/codec.py) from a DAC checkpoint: ``--output`` then needs no ``dac`` package, also with ``--stream-chunk``.
 ``--score-codes FILE.npy`` (build-only) generates nothing: it prints the teacher-forced log-likelihood of the given codes under
 the loaded checkpoint (Dia.score) as one JSON line.
 """
@@ -49,6 +50,9 @@ def build_parser() -> argparse.ArgumentParser:
     g.add_argument("--use-adapter", type=str, default=None, metavar="NAME", help="(build-only) generate (or score) with this --adapter; with "
                    "--slots N a comma list with one entry per chunk (an empty entry = the base model) or one name for all chunks")
     g.add_argument("--no-dac", action="store_true", help="(build-only) do not load the audio codec; requires --codes-output")
+    g.add_argument("--codec-path", type=str, default=None, metavar="FILE", help="(build-only) DAC checkpoint (.pth / state dict) for the "
+                   "native codec: --output is decoded on the device by this library, the third-party dac package is not loaded "
+                   "(as with --no-dac), and --stream-chunk N may be combined with --output")
     g = p.add_argument_group("Audio Prompting (Voice Cloning)")
     g.add_argument("--audio-prompt", type=str, default=None, help="voice to clone: an audio file (needs the codec) or a .npy of codec codes [T, 9]")
     g.add_argument("--audio-prompt-text", type=str, default=None, help="what is said in --audio-prompt (mandatory with it)")
@@ -167,6 +171,34 @@ def stream_to_file(dia, args, full_text: str) -> int:
     return 0
 
 
+def stream_audio_to_file(dia, args, full_text: str) -> int:
+    """--stream-chunk with --output (needs --codec-path): one utterance through Dia.stream_frames, every chunk decoded as it arrives
+    by the native codec's streaming state; the file is written from the chunks' samples (and --codes-output from their codes)"""
+    state = dia.codec.stream()
+    samples, frames = [], []
+    for _, start, codes, final in dia.stream_frames([full_text], 1, max_tokens=args.max_tokens, seeds=None if args.seed is None else [args.seed],
+                                                    chunk=args.stream_chunk, adapters=used_adapters(args), cfg_scale=args.cfg_scale,
+                                                    temperature=args.temperature, top_p=args.top_p, cfg_filter_top_k=args.cfg_filter_top_k):
+        y = state.push(codes, final)
+        frames.append(codes)
+        samples.append(y)
+        if args.verbose:
+            print(f"stream: frames [{start}, {start + codes.shape[-1]}) -> {y.shape[0]} samples{' final' if final else ''}")
+    audio = np.concatenate(samples) if samples else np.zeros(0, dtype=np.float32)
+    if audio.shape[0] == 0:
+        print("Generation failed to produce audio.")
+        return 1
+    if args.codes_output:
+        Path(args.codes_output).parent.mkdir(parents=True, exist_ok=True)
+        np.save(args.codes_output, np.concatenate(frames, axis=-1))
+        print(f"Codes saved to {args.codes_output}")
+    Path(args.output).parent.mkdir(parents=True, exist_ok=True)
+    print(f"Saving audio to {args.output}...")
+    dia.save_audio(args.output, audio)
+    print(f"Audio successfully saved to {args.output}")
+    return 0
+
+
 def score_to_stdout(dia, args, text: str, prompt) -> int:
     """--score-codes: Dia.score of the file's codes; the summary as one JSON line, the arrays to --score-output"""
     import json
@@ -203,10 +235,18 @@ def main(argv=None) -> int:
         parser.error("one of --output / --codes-output is required.")
     if args.slots < 0 or (args.slots and (args.audio_prompt or not args.codes_output or args.output)):
         parser.error("--slots N needs N > 0, --codes-output, and neither --audio-prompt nor --output.")
-    if args.stream_chunk < 0 or (args.stream_chunk and (args.audio_prompt or not args.codes_output or args.output)):
-        parser.error("--stream-chunk N needs N > 0, --codes-output, and neither --audio-prompt nor --output.")
-    if args.no_dac and args.output:
+    stream_wav = bool(args.stream_chunk and args.codec_path and args.output and not args.slots and not args.audio_prompt)
+    if args.stream_chunk < 0 or (args.stream_chunk and not stream_wav and (args.audio_prompt or not args.codes_output or args.output)):
+        parser.error("--stream-chunk N needs N > 0, --codes-output, and neither --audio-prompt nor --output "
+                     "(--output is allowed with --codec-path).")
+    if args.no_dac and args.output and not args.codec_path:
         parser.error("--output needs the audio codec; use --codes-output with --no-dac.")
+    if args.codec_path:
+        if args.score_codes:
+            parser.error("--codec-path decodes generated codes: not with --score-codes.")
+        if not Path(args.codec_path).is_file():
+            parser.error(f"--codec-path {args.codec_path!r} is not a file.")
+        args.no_dac = True                                     # the native codec replaces the third-party import
 
     from dia_hip.model import Dia
 
@@ -234,6 +274,9 @@ def main(argv=None) -> int:
                                       adapter_path=args.adapter_path)
         if args.adapter_path:
             print("LoRA adapters merged successfully.")
+        if args.codec_path:
+            dia.load_codec(args.codec_path)
+            print(f"Native codec loaded from {args.codec_path}")
         if bank_dirs:
             dia.load_adapters(bank_dirs)
             print(f"LoRA adapters loaded unmerged: {sorted(bank_dirs)}")
@@ -259,6 +302,8 @@ def main(argv=None) -> int:
     print("Generating audio...")
     if args.stream_chunk:
         try:
+            if stream_wav:
+                return stream_audio_to_file(dia, args, full_text)
             return stream_to_file(dia, args, full_text)
         except Exception as e:
             print(f"Error during audio generation or saving: {e}")

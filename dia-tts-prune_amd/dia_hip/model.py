@@ -97,6 +97,7 @@ class Dia:
         self.compute_dtype = compute_dtype.to_dtype()
         self.model: Optional[DeviceWeights] = None      # resident weights (reference: DiaModel nn.Module)
         self.dac_model = None
+        self.codec = None                               # codec.DeviceCodec of load_codec(): the native DAC decoder
         self.last_codes: Optional[np.ndarray] = None
         self.weights_rounded = False
         self.weights_exact_planes = False
@@ -160,7 +161,7 @@ class Dia:
     def from_local(cls, config_path: str, checkpoint_path: str,
                    compute_dtype: Union[str, ComputeDtype] = ComputeDtype.FLOAT32,
                    device: Optional[torch.device] = None, load_dac: bool = True,
-                   adapter_path: Optional[str] = None) -> "Dia":
+                   adapter_path: Optional[str] = None, codec_path: Optional[str] = None) -> "Dia":
         """reference model.py:139-187: config JSON + pickled/safetensors state_dict (this is the
         loader for ``offline_prune.py`` outputs).  ``adapter_path``: LoRA adapter directory merged into the
         dense weights before they are tiled (reference cli.py:166-174 wraps with PEFT at run time)."""
@@ -177,13 +178,15 @@ class Dia:
         dia._install(sd, adapter_path)
         if load_dac:
             dia._load_dac_model()
+        if codec_path is not None:
+            dia.load_codec(codec_path)
         return dia
 
     @classmethod
     def from_pretrained(cls, model_name: str = "nari-labs/Dia-1.6B",
                         compute_dtype: Union[str, ComputeDtype] = ComputeDtype.FLOAT32,
                         device: Optional[torch.device] = None, load_dac: bool = True,
-                        adapter_path: Optional[str] = None, **kwargs) -> "Dia":
+                        adapter_path: Optional[str] = None, codec_path: Optional[str] = None, **kwargs) -> "Dia":
         """reference model.py:189-236.  ``model_name`` must be a local directory holding
         ``config.json`` and ``model.safetensors`` / ``pytorch_model.bin`` (hub download needs a network)."""
         p = Path(model_name)
@@ -196,7 +199,18 @@ class Dia:
         dia._install(W.load_state_dict_file(ckpt), adapter_path)
         if load_dac:
             dia._load_dac_model()
+        if codec_path is not None:
+            dia.load_codec(codec_path)
         return dia
+
+    def load_codec(self, path_or_state, window: int = 128):
+        """Set the native DAC decoder (dia_hip/codec.py, csrc/codec.hip) on this instance: a DAC ``.pth`` / bare state dict, as a
+        path or in memory.  generate() then returns waveforms and generate_audio_batch / stream_audio work; the third-party
+        ``dac`` package is not needed.  A missing or unexpected decoder / quantizer key is refused by name."""
+        from .codec import DeviceCodec
+        with torch.cuda.device(self.device):
+            self.codec = DeviceCodec(path_or_state, self.device, window=window)
+        return self.codec
 
     def _load_dac_model(self):
         """reference model.py:238-252 — raises RuntimeError when the codec cannot be loaded."""
@@ -411,6 +425,37 @@ class Dia:
             finally:
                 s.close()
 
+    def _need_codec(self):
+        if self.codec is None:
+            raise RuntimeError("no native codec loaded: call Dia.load_codec(path_or_state) first")
+        return self.codec
+
+    @torch.inference_mode()
+    def generate_audio_batch(self, texts: Sequence[str], *args, **kw) -> List[np.ndarray]:
+        """generate_batch (same arguments), then the native codec over all utterances at once: one float32 waveform
+        [T'_b * 512] per utterance, each as when decoded alone.  Needs load_codec()."""
+        codec = self._need_codec()
+        return codec.decode_batch(self.generate_batch(texts, *args, **kw))
+
+    @torch.inference_mode()
+    def stream_audio(self, requests_or_texts: Sequence[Union[str, GenerationRequest]], slots: int = 8, **kw):
+        """stream_frames (same arguments) with the native codec behind it: yields (request index, start sample, samples, final)
+        while the utterances run.  The samples of a request, joined, equal codec.decode() of its whole code tensor; the last
+        context_frames frames of a running utterance are held back until more arrive or it ends (DESIGN.md "Codec").  Needs
+        load_codec()."""
+        codec = self._need_codec()
+        states, starts = {}, {}
+        for i, _, codes, final in self.stream_frames(requests_or_texts, slots, **kw):
+            st = states.get(i)
+            if st is None:
+                st = states[i] = codec.stream()
+                starts[i] = 0
+            y = st.push(codes, final)
+            yield i, starts[i], y, final
+            starts[i] += y.shape[0]
+            if final:
+                del states[i]
+
     @torch.inference_mode()
     def generate_batch(self, texts: Sequence[str], max_tokens: Optional[int] = None, cfg_scale: float = 3.0,
                        temperature: float = 1.3, top_p: float = 0.95, cfg_filter_top_k: int = 35,
@@ -489,7 +534,10 @@ class Dia:
             return None
 
     def _generate_output(self, codec_input: np.ndarray) -> Optional[np.ndarray]:
-        """codes [1, C, T'] -> waveform through the third-party codec (model.py:535-544)."""
+        """codes [1, C, T'] -> waveform: through the native codec when load_codec() set one, else through the third-party codec
+        (model.py:535-544)."""
+        if self.codec is not None:
+            return self.codec.decode(codec_input)
         if self.dac_model is None:
             raise RuntimeError("DAC model not loaded. Cannot decode audio.")
         codes = torch.from_numpy(codec_input.astype(np.int64)).to(self.device)
@@ -531,7 +579,13 @@ class Dia:
             print("Warning: Cannot save None audio.")
             return
         try:
-            import soundfile  # type: ignore
+            try:
+                import soundfile  # type: ignore
+            except ImportError:
+                if not str(path).lower().endswith(".wav"):
+                    raise
+                _save_wav_pcm16(path, audio, sample_rate)
+                return
             out = Path(path)
             out.parent.mkdir(parents=True, exist_ok=True)
             samples = np.asarray(audio)
@@ -540,3 +594,20 @@ class Dia:
             soundfile.write(str(out), samples.clip(-1.0, 1.0), sample_rate)
         except Exception as e:
             print(f"Error saving audio to {path}: {e}")
+
+
+def _save_wav_pcm16(path: str, audio: np.ndarray, sample_rate: int) -> None:
+    """save_audio without soundfile: mono 16-bit PCM through the standard library's wave module"""
+    import wave
+
+    out = Path(path)
+    out.parent.mkdir(parents=True, exist_ok=True)
+    samples = np.asarray(audio)
+    if samples.dtype.kind in "iu":
+        samples = samples.astype(np.float32) / float(np.iinfo(samples.dtype).max)
+    pcm = np.round(samples.reshape(-1).astype(np.float64).clip(-1.0, 1.0) * 32767.0).astype("<i2")
+    with wave.open(str(out), "wb") as f:
+        f.setnchannels(1)
+        f.setsampwidth(2)
+        f.setframerate(int(sample_rate))
+        f.writeframes(pcm.tobytes())

@@ -837,6 +837,56 @@ int dia_attn_cross_fp8(const dia_attn_args* a, const dia_kv_fp8_ptrs* p, void* s
  * and S % 32 == 0.  NULL = dia_attn over the bf16 caches, as without the call. */
 int dia_engine_set_cross_fp8(dia_engine* e, const dia_kv_fp8_ptrs* layers /* host [n_layer], copied */);
 
+/* ------------------------------------------------------------------------------------------------
+ * Codec (csrc/codec.hip; DESIGN.md "Codec"): the Descript Audio Codec decoder, codes [B, 9, T] -> waveform, in exact fp32 on the
+ * f32-input MFMA (reference dia/audio.py:166-185: quantizer.from_codes, then decode).  Three new entry points and two new structs;
+ * nothing older changed.  Activations are fp32 [B][C][ld] with time contiguous; the batch stride is C * ld.  Every row b carries
+ * its own length lens[b] (device int32, clamped to [0, T]; NULL = T for every row): positions at or beyond it read as zero padding
+ * and are not written, so a row of a batch comes out bit for bit as when launched alone.
+ *
+ * Weights are prepared by the host (dia_hip/codec.py, weight norm folded in float64), TAP-MAJOR with the output channel contiguous:
+ *   dia_codec_conv   w float [k][C_in][Cp]        w[j][ci][co] = weight[co][ci][j];             Cp = C_out rounded up to 32, zero-filled
+ *   dia_codec_convt  w float [s][2][C_in][Cp]     w[r][0][ci][co] = weight[ci][co][r], w[r][1][ci][co] = weight[ci][co][r + s]
+ * Snake on the INPUT, x + sin(alpha x)^2 * inv, is applied once per staged element when `alpha` is set; `inv` holds
+ * 1 / (alpha + 1e-9) per input channel (both or neither).
+ * ------------------------------------------------------------------------------------------------ */
+#define DIA_CODEC_MAX_CHANNELS 4096
+#define DIA_CODEC_MAX_T (1 << 24)
+#define DIA_CODEC_MAX_CODEBOOKS 16
+typedef struct {
+  const int32_t* codes;        /* [B][n_codebooks][ld_codes]; ids are clamped into [0, codebook_size) */
+  const int32_t* lens;         /* device [B] or NULL */
+  int32_t B, T;
+  int32_t n_codebooks, codebook_size, latent_dim, ld_codes;
+  const float* tables;         /* [n_codebooks][codebook_size][latent_dim]: out_proj_i(codebook_i[id]) without its bias */
+  const float* bias;           /* [latent_dim]: the out_proj biases summed */
+  float* z;                    /* [B][latent_dim][ldz] */
+  int32_t ldz, _pad0;
+} dia_codec_embed_args;
+/* z[b][c][t] = bias[c] + sum_i tables[i][codes[b][i][t]][c] for t < lens[b] */
+int dia_codec_embed(const dia_codec_embed_args* a, void* stream);
+
+typedef struct {
+  const float* x;              /* [B][C_in][ldx] */
+  const float* w;              /* layout above */
+  const float* bias;           /* [C_out] */
+  const float* alpha;          /* [C_in] or NULL: Snake on the input */
+  const float* inv;            /* [C_in], with alpha */
+  const float* res;            /* [B][C_out][ldy] or NULL: added in the epilogue; may be y itself (dia_codec_conv only) */
+  float* y;                    /* [B][C_out][ldy]; never x */
+  const int32_t* lens;         /* device [B] or NULL: INPUT lengths */
+  int32_t B, T;                /* T: input positions per row (grid extent and clamp of lens) */
+  int32_t C_in, C_out, ldx, ldy;
+  int32_t k, dilation;         /* dia_codec_conv: k 1 (dilation 1) or 7 (dilation 1, 3, 9), "same" padding */
+  int32_t stride;              /* dia_codec_convt: 2, 4 or 8 (kernel 2 * stride, padding stride / 2: output length T * stride); else 0 */
+  int32_t tanh_out;            /* tanh behind bias and residual */
+} dia_codec_conv_args;
+/* y[b][co][t] = bias[co] + sum_{ci, j} w[j][ci][co] * f(x[b][ci][t + (j - k / 2) * dilation]) (+ res) (tanh), t < lens[b] */
+int dia_codec_conv(const dia_codec_conv_args* a, void* stream);
+/* y[b][co][o] = bias[co] + sum_{ci} w[r][0][ci][co] * f(x[b][ci][m]) + w[r][1][ci][co] * f(x[b][ci][m - 1]),
+ * o + stride / 2 = m * stride + r, o < lens[b] * stride.  res must be NULL. */
+int dia_codec_convt(const dia_codec_conv_args* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
