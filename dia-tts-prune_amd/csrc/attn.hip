@@ -655,7 +655,7 @@ struct AttnF8 { const uint8_t* k8; const uint8_t* v8; const float* ks; const flo
 struct F8Frag { uint2 kb[2][4]; uint2 vb[8]; float ksc[2], vsc[2]; };
 
 typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-__device__ __forceinline__ bf16x8 expand_e4m3(uint2 d) {      // (gemm_mxfp8.hip expand_fp8 at scale 1)
+__device__ __forceinline__ bf16x8 expand_e4m3(uint2 d) {      // (gemm_mx.hip Fp8::frag at scale 1)
   const bf16x2 r0 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(d.x, 1.0f, false);
   const bf16x2 r1 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(d.x, 1.0f, true);
   const bf16x2 r2 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(d.y, 1.0f, false);

@@ -2341,12 +2341,8 @@ static int gemm_impl(const dia_gemm_args* a, const dia_wo_defer_args* wd, void* 
     const int rc = dia_gemm_sparse24_check(a);
     if (rc != DIA_OK) return rc;
   }
-  if (a->w_format == DIA_W_MXFP8) {         // MX e4m3 weight stream (gemm_mxfp8.hip)
-    const int rc = dia_gemm_mxfp8_check(a);
-    if (rc != DIA_OK) return rc;
-  }
-  if (a->w_format == DIA_W_MXFP4) {         // MX e2m1 weight stream (gemm_mxfp4.hip)
-    const int rc = dia_gemm_mxfp4_check(a);
+  if (a->w_format == DIA_W_MXFP8 || a->w_format == DIA_W_MXFP4) {      // MX e4m3 / e2m1 weight stream (gemm_mx.hip)
+    const int rc = dia_gemm_mx_check(a);
     if (rc != DIA_OK) return rc;
   }
   if (a->w_planes == 2) {
@@ -2392,8 +2388,7 @@ static int gemm_impl(const dia_gemm_args* a, const dia_wo_defer_args* wd, void* 
   if (a->ssq_in && a->ssq_ld < ((a->M + 15) / 16) * 16) return dia_fail(DIA_E_ARG, "dia_gemm: ssq_ld smaller than padded rows");
 
   if (a->w_format == DIA_W_SPARSE24) return dia_gemm_sparse24(a, stream);
-  if (a->w_format == DIA_W_MXFP8) return dia_gemm_mxfp8(a, stream);
-  if (a->w_format == DIA_W_MXFP4) return dia_gemm_mxfp4(a, stream);
+  if (a->w_format == DIA_W_MXFP8 || a->w_format == DIA_W_MXFP4) return dia_gemm_mx(a, stream);
   if (a->sp_blocks || a->sp_toff) {       // zero-skipping stream of an unstructured-pruned matrix: kernel-level experiment
 #ifdef DIA_EXPERIMENTS
     return dia_exp_gemm_sparse(a, stream);

@@ -409,14 +409,15 @@ inline int fill_gemmk(const dia_gemm_args* a, GemmK& k) {
   return DIA_OK;
 }
 
+// strips per workgroup of the weight-stream kernels' persistent form (2:4, MXFP8, MXFP4): the caller's spw, else 4 from 1024
+// strips on and about 256 workgroups above 512 strips, as the dense M <= 4 GEMV (the dense kernels' gemm_spw knob does not apply)
+inline int stream_spw(int spw, int nstrips) { return spw > 0 ? spw : (nstrips >= 1024 ? 4 : (nstrips > 512 ? (nstrips + 255) / 256 : 1)); }
+
 }  // namespace
 
 // gemm_sparse.hip: dia_gemm with w_format == DIA_W_SPARSE24 (2:4 weight stream, M <= 16)
 int dia_gemm_sparse24_check(const dia_gemm_args* a);
 int dia_gemm_sparse24(const dia_gemm_args* a, void* stream);
-// gemm_mxfp8.hip: dia_gemm with w_format == DIA_W_MXFP8 (MX e4m3 weight stream, M <= 16)
-int dia_gemm_mxfp8_check(const dia_gemm_args* a);
-int dia_gemm_mxfp8(const dia_gemm_args* a, void* stream);
-// gemm_mxfp4.hip: dia_gemm with w_format == DIA_W_MXFP4 (MX e2m1 weight stream, M <= 16)
-int dia_gemm_mxfp4_check(const dia_gemm_args* a);
-int dia_gemm_mxfp4(const dia_gemm_args* a, void* stream);
+// gemm_mx.hip: dia_gemm with w_format == DIA_W_MXFP8 / DIA_W_MXFP4 (MX e4m3 / e2m1 weight stream, M <= 16)
+int dia_gemm_mx_check(const dia_gemm_args* a);
+int dia_gemm_mx(const dia_gemm_args* a, void* stream);

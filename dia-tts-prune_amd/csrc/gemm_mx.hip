@@ -1,18 +1,24 @@
-// MXFP8 decode GEMM: out[M][N] = X[M][K] . W[K][N] for M <= 16 rows with W stored as OCP MX blocks (e4m3 elements, one E8M0
-// power-of-two scale per 32 consecutive K of a column) in the stream of dia_hip/layout.py tile_weight_fp8
-// (dia_gemm_args.w_format = DIA_W_MXFP8).
+// MX decode GEMMs: out[M][N] = X[M][K] . W[K][N] for M <= 16 rows with W stored as OCP MX blocks (one E8M0 power-of-two scale per
+// 32 consecutive K of a column) in the streams of dia_hip/layout.py: e4m3 elements (tile_weight_fp8, dia_gemm_args.w_format =
+// DIA_W_MXFP8) or e2m1 elements (tile_weight_fp4, DIA_W_MXFP4).  One kernel template, k_gemm_mx<Fmt, ...>, serves both: the
+// formats differ in the traits Fp8 / Fp4 below (k-tiles per value slot, bytes per group, the converts of a B fragment) and in
+// nothing else (DESIGN.md "MXFP4 weight stream" says why the kernel itself is the shared body).
 //
 // Mapping (CDNA4): the weights stay the B operand of the dense v_mfma_f32_16x16x32_bf16 (lane l: column l & 15 of the strip,
 // K = 8 (l >> 4) + [0, 8) of the k-tile), so the accumulator keeps the dense kernels' orientation (lane l, element i = row
-// 4 (l >> 4) + i, column l & 15).  A lane's 8 values of a k-tile are 8 e4m3 bytes of ONE MX block (the block is the 4 lanes x 8
-// values of a column inside a k-tile): v_cvt_scalef32_pk_bf16_fp8 turns two bytes and the block's scale (E8M0 byte << 23 is
-// the float it wants) into two bf16 — exactly, an e4m3 value times a power of two is a bf16 value — so a k-tile costs one
+// 4 (l >> 4) + i, column l & 15).  A lane's 8 values of a k-tile belong to ONE MX block (the block is the 4 lanes x 8 values of
+// a column inside a k-tile): v_cvt_scalef32_pk_bf16_fp8 / _fp4 turns two of them and the block's scale (E8M0 byte << 23 is the
+// float it wants) into two bf16 — exactly, an e4m3 or e2m1 value times a power of two is a bf16 value — so a k-tile costs one
 // scale extraction and four converts in front of the same three MFMAs (hi / mid / lo planes of the fp32 activations), with
 // no LDS round trip on the weight side.
 //
 // Stream of a strip: groups of 16 k-tiles (512 K), each a 256-byte scale block [16 columns][16 k-tiles] (lane l reads the
-// bytes of column l & 15) followed by 8 slots of 1 KiB, slot p = [64 lanes][16 bytes] = the lane's 8 values of k-tile 2p and
-// its 8 of k-tile 2p + 1: 8448 bytes per group, 0.515625 of the dense tiles'.
+// bytes of column l & 15) followed by value slots of 1 KiB, slot p = [64 lanes][16 bytes]:
+//   MXFP8  a lane's 8 values of a k-tile are 8 bytes (two dwords); slot p holds its 8 of k-tile 2p and its 8 of k-tile 2p + 1:
+//          8 slots, 8448 bytes per group, 0.515625 of the dense tiles'
+//   MXFP4  a lane's 8 values of a k-tile are ONE dword (element j in byte j >> 1, the even element in the low nibble; the convert's
+//          byte select b takes byte b); slot p holds its dwords of k-tiles 4p .. 4p + 3: 4 slots, 4352 bytes per group, 0.265625
+//          of the dense tiles'.  One 16-byte load feeds four B fragments: a wave's 8 k-tiles are two loads per strip, its 16 four.
 //
 // One workgroup owns one 16-column strip (persistent form: several, the next one's weights streaming during this one's
 // reduction and epilogue); its waves split K into ranges of KPW k-tiles (8 = half a group, 16 = a whole one); gridDim.y > 1
@@ -23,38 +29,67 @@
 //            (as k_gemm16: 96 VGPRs at 8 k-tiles per wave); with 16 k-tiles per wave it reads them from L2 inside the loop
 // Partial tiles of the waves are summed through LDS in wave order; the element-per-thread epilogue (run_epilogue_rows) follows.
 #include "gemm_common.hpp"
+#include <cstdio>
 
 namespace {
 
-constexpr int F8_GROUP = 16;                       // k-tiles per stream group (layout.FP8_GROUP)
-constexpr int F8_GROUP_BYTES = 256 + 8 * 1024;     // scale block + 8 value slots
-constexpr int F8_MAXW = 8;                         // waves per workgroup
+constexpr int MX_GROUP = 16;                       // k-tiles per stream group (layout.FP8_GROUP)
+constexpr int MX_MAXW = 8;                         // waves per workgroup
+constexpr int MX_SCALE_BYTES = 256;                // scale block of a group
+constexpr int MX_SLOT_BYTES = 1024;                // one value slot
 
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
+typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
 
-// the B fragment of one k-tile: 8 e4m3 bytes (two dwords) of one MX block times its scale
-__device__ __forceinline__ bf16x8 expand_fp8(unsigned d0, unsigned d1, float scale) {
-  const bf16x2 r0 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(d0, scale, false);
-  const bf16x2 r1 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(d0, scale, true);
-  const bf16x2 r2 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(d1, scale, false);
-  const bf16x2 r3 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(d1, scale, true);
-  typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
+__device__ __forceinline__ bf16x8 join4(bf16x2 r0, bf16x2 r1, bf16x2 r2, bf16x2 r3) {
   const bf16x4 lo = __builtin_shufflevector(r0, r1, 0, 1, 2, 3), hi = __builtin_shufflevector(r2, r3, 0, 1, 2, 3);
   return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
 }
 
-constexpr size_t f8_smem_fixed() { return sizeof(f32x4) * 2 * F8_MAXW * 64 + sizeof(float) * (16 * 17 + 16); }
-size_t f8_smem(int ktw, int rs) { return f8_smem_fixed() + (rs == 4 ? (size_t)DIA_NPLANES * ktw * 4 * rs * 16 : 0); }
+// Per element format: k-tiles per value slot, bytes per group (layout.FP8_GROUP_BYTES / FP4_GROUP_BYTES), the name in messages
+// and frag(): the B fragment of k-tile i of a wave's loaded slots bc, the 8 values of one MX block times its scale
+struct Fp8 {
+  static constexpr int SLOT_KT = 2;
+  static constexpr int GROUP_BYTES = MX_SCALE_BYTES + (MX_GROUP / SLOT_KT) * MX_SLOT_BYTES;
+  static constexpr const char* NAME = "MXFP8";
+  static constexpr const char* KERNEL = "k_gemm_mx<Fp8>";
+  static __device__ __forceinline__ bf16x8 frag(const u32x4* bc, int i, float scale) {      // 8 e4m3 bytes (two dwords)
+    const unsigned d0 = bc[i >> 1][2 * (i & 1)], d1 = bc[i >> 1][2 * (i & 1) + 1];
+    const bf16x2 r0 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(d0, scale, false);
+    const bf16x2 r1 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(d0, scale, true);
+    const bf16x2 r2 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(d1, scale, false);
+    const bf16x2 r3 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(d1, scale, true);
+    return join4(r0, r1, r2, r3);
+  }
+};
+struct Fp4 {
+  static constexpr int SLOT_KT = 4;
+  static constexpr int GROUP_BYTES = MX_SCALE_BYTES + (MX_GROUP / SLOT_KT) * MX_SLOT_BYTES;
+  static constexpr const char* NAME = "MXFP4";
+  static constexpr const char* KERNEL = "k_gemm_mx<Fp4>";
+  static __device__ __forceinline__ bf16x8 frag(const u32x4* bc, int i, float scale) {      // 8 e2m1 nibbles (one dword)
+    const unsigned d = bc[i >> 2][i & 3];
+    const bf16x2 r0 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(d, scale, 0);
+    const bf16x2 r1 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(d, scale, 1);
+    const bf16x2 r2 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(d, scale, 2);
+    const bf16x2 r3 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(d, scale, 3);
+    return join4(r0, r1, r2, r3);
+  }
+};
+static_assert(Fp8::GROUP_BYTES == 8448 && Fp4::GROUP_BYTES == 4352, "the group sizes of dia_hip/layout.py");
 
-template <int KPW, int RS, bool MULTI>
-__global__ __launch_bounds__(F8_MAXW * 64) void k_gemm_mxfp8(GemmK p) {
+constexpr size_t mx_smem_fixed() { return sizeof(f32x4) * 2 * MX_MAXW * 64 + sizeof(float) * (16 * 17 + 16); }
+size_t mx_smem(int ktw, int rs) { return mx_smem_fixed() + (rs == 4 ? (size_t)DIA_NPLANES * ktw * 4 * rs * 16 : 0); }
+
+template <class Fmt, int KPW, int RS, bool MULTI>
+__global__ __launch_bounds__(MX_MAXW * 64) void k_gemm_mx(GemmK p) {
   static_assert(KPW == 8 || KPW == 16, "half a stream group or a whole one per wave");
-  constexpr int NS = KPW / 2;                          // value slots per wave
+  constexpr int NS = KPW / Fmt::SLOT_KT;               // value slots per wave
   constexpr int NSC = KPW / 4;                         // dwords of scale bytes per wave
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  f32x4* red = reinterpret_cast<f32x4*>(smem_raw);                                   // [2][F8_MAXW][64]
-  float* tile = reinterpret_cast<float*>(smem_raw + sizeof(f32x4) * 2 * F8_MAXW * 64); // [16][17] (split-K hand-off)
+  f32x4* red = reinterpret_cast<f32x4*>(smem_raw);                                   // [2][MX_MAXW][64]
+  float* tile = reinterpret_cast<float*>(smem_raw + sizeof(f32x4) * 2 * MX_MAXW * 64); // [16][17] (split-K hand-off)
   float* inv_s = tile + 16 * 17;                                                     // [16]
   bf16x8* As = reinterpret_cast<bf16x8*>(inv_s + 16);                               // RS = 4: [plane][kt][kq][row]
   __shared__ int sk_flag;
@@ -64,11 +99,11 @@ __global__ __launch_bounds__(F8_MAXW * 64) void k_gemm_mxfp8(GemmK p) {
   const int ktw = NW * KPW;                          // k-tiles of this workgroup's K range
   const int kt0 = blockIdx.y * ktw + w * KPW;        // first global k-tile of this wave (a multiple of KPW)
   const int G = gridDim.x;
-  const long strip_bytes = (long)(p.KT / F8_GROUP) * F8_GROUP_BYTES;
+  const long strip_bytes = (long)(p.KT / MX_GROUP) * Fmt::GROUP_BYTES;
   // this wave's part of a group: its scale bytes (column l & 15, k-tiles kt0 % 16 ..) and its value slots
-  const unsigned char* Wg = reinterpret_cast<const unsigned char*>(p.W) + (long)(kt0 / F8_GROUP) * F8_GROUP_BYTES;
-  const unsigned char* Wsc = Wg + (lane & 15) * 16 + (kt0 % F8_GROUP);
-  const unsigned char* Wv = Wg + 256 + (long)((kt0 % F8_GROUP) / 2) * 1024 + lane * 16;
+  const unsigned char* Wg = reinterpret_cast<const unsigned char*>(p.W) + (long)(kt0 / MX_GROUP) * Fmt::GROUP_BYTES;
+  const unsigned char* Wsc = Wg + (lane & 15) * 16 + (kt0 % MX_GROUP);
+  const unsigned char* Wv = Wg + MX_SCALE_BYTES + (long)((kt0 % MX_GROUP) / Fmt::SLOT_KT) * MX_SLOT_BYTES + lane * 16;
   auto load_strip = [&](u32x4* b, unsigned* sc, int strip) {
     const long so = (long)strip * strip_bytes;
     if constexpr (KPW == 8) {
@@ -79,7 +114,7 @@ __global__ __launch_bounds__(F8_MAXW * 64) void k_gemm_mxfp8(GemmK p) {
       sc[0] = s[0]; sc[1] = s[1]; sc[2] = s[2]; sc[3] = s[3];
     }
 #pragma unroll
-    for (int i = 0; i < NS; ++i) b[i] = DIA_WLOAD(reinterpret_cast<const u32x4*>(Wv + so + (long)i * 1024));
+    for (int i = 0; i < NS; ++i) b[i] = DIA_WLOAD(reinterpret_cast<const u32x4*>(Wv + so + (long)i * MX_SLOT_BYTES));
   };
   const float* Af = reinterpret_cast<const float*>(p.A);
 
@@ -180,13 +215,13 @@ __global__ __launch_bounds__(F8_MAXW * 64) void k_gemm_mxfp8(GemmK p) {
         split3x8(f[0], f[1], h, mi, lo);
       }
       const float scale = __builtin_bit_cast(float, ((cc[i >> 2] >> (8 * (i & 3))) & 0xffu) << 23);
-      const bf16x8 b = expand_fp8(bc[i >> 1][2 * (i & 1)], bc[i >> 1][2 * (i & 1) + 1], scale);
+      const bf16x8 b = Fmt::frag(bc, i, scale);
       acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(h, b, acc, 0, 0, 0);
       acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(mi, b, acc, 0, 0, 0);
       acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(lo, b, acc, 0, 0, 0);
     }
     // cross-wave sum: element (row m, column c) of the output tile sits in lane 16 (m >> 2) + c, register m & 3 of every wave
-    f32x4* rb = red + sbuf * (F8_MAXW * 64);
+    f32x4* rb = red + sbuf * (MX_MAXW * 64);
     sbuf ^= 1;
     if (RS == 16 || lane < 16) rb[w * 64 + lane] = acc;
     lds_barrier();
@@ -241,56 +276,64 @@ __global__ __launch_bounds__(F8_MAXW * 64) void k_gemm_mxfp8(GemmK p) {
   }
 }
 
-template <int KPW, int RS>
-int launch_f8(const GemmK& k, int nw, int sk, int spw, hipStream_t st) {
-  const size_t smem = f8_smem(nw * KPW, RS);
+template <class Fmt, int KPW, int RS>
+int launch_mx(const GemmK& k, int nw, int sk, int spw, hipStream_t st) {
+  const size_t smem = mx_smem(nw * KPW, RS);
   if (spw > 1 && sk == 1) {
     if constexpr (KPW == 8) {     // (16 k-tiles per wave: wo's split-K ranges only, one strip per workgroup)
-      launch_kernel<k_gemm_mxfp8<KPW, RS, true>>(dim3((k.nstrips + spw - 1) / spw), dim3(nw * 64), smem, st, k);
-      return dia_check_launch("k_gemm_mxfp8");
+      launch_kernel<k_gemm_mx<Fmt, KPW, RS, true>>(dim3((k.nstrips + spw - 1) / spw), dim3(nw * 64), smem, st, k);
+      return dia_check_launch(Fmt::KERNEL);
     }
   }
-  launch_kernel<k_gemm_mxfp8<KPW, RS, false>>(dim3(k.nstrips, sk), dim3(nw * 64), smem, st, k);
-  return dia_check_launch("k_gemm_mxfp8");
+  launch_kernel<k_gemm_mx<Fmt, KPW, RS, false>>(dim3(k.nstrips, sk), dim3(nw * 64), smem, st, k);
+  return dia_check_launch(Fmt::KERNEL);
+}
+
+template <class Fmt>
+int launch_mx_shape(const GemmK& k, int ktw, int sk, int spw, bool image, hipStream_t st) {
+  const int kpw = ktw / 8 <= MX_MAXW ? 8 : 16;
+  const int nw = ktw / kpw;
+  if (kpw == 8) return image ? launch_mx<Fmt, 8, 4>(k, nw, sk, spw, st) : launch_mx<Fmt, 8, 16>(k, nw, sk, spw, st);
+  return image ? launch_mx<Fmt, 16, 4>(k, nw, sk, 1, st) : launch_mx<Fmt, 16, 16>(k, nw, sk, 1, st);
 }
 
 }  // namespace
 
-// dia_gemm with w_format == DIA_W_MXFP8: what the fp8 stream cannot serve (checked before dia_gemm's other weight forms)
-int dia_gemm_mxfp8_check(const dia_gemm_args* a) {
-  if (a->w_planes > 1) return dia_fail(DIA_E_ARG, "dia_gemm: the MXFP8 stream holds one weight encoding (w_planes must be 0 or 1)");
-  if (a->w_layout == 1) return dia_fail(DIA_E_ARG, "dia_gemm: the MXFP8 stream has no diagonal layout (w_layout must be 0)");
-  if (a->sp_blocks || a->sp_toff) return dia_fail(DIA_E_ARG, "dia_gemm: the MXFP8 stream and the zero-skipping stream (sp_blocks) exclude each other");
-  if (a->epi == DIA_EPI_CROSSKV) return dia_fail(DIA_E_ARG, "dia_gemm: the MXFP8 stream has no CROSSKV epilogue (prefill only)");
-  if (a->cmap || a->strip_map) return dia_fail(DIA_E_ARG, "dia_gemm: the MXFP8 stream has no compaction maps (cmap / strip_map)");
-  if (a->M > 16) return dia_fail(DIA_E_ARG, "dia_gemm: the MXFP8 stream serves at most 16 rows");
+// dia_gemm with w_format == DIA_W_MXFP8 / DIA_W_MXFP4: what an MX stream cannot serve (checked before dia_gemm's other weight forms)
+int dia_gemm_mx_check(const dia_gemm_args* a) {
+  const char* name = a->w_format == DIA_W_MXFP4 ? Fp4::NAME : Fp8::NAME;
+  auto refuse = [name](const char* what) {           // "dia_gemm: the MXFP8 stream <what>" (dia_fail copies its message)
+    char msg[160];
+    snprintf(msg, sizeof msg, "dia_gemm: the %s stream %s", name, what);
+    return dia_fail(DIA_E_ARG, msg);
+  };
+  if (a->w_planes > 1) return refuse("holds one weight encoding (w_planes must be 0 or 1)");
+  if (a->w_layout == 1) return refuse("has no diagonal layout (w_layout must be 0)");
+  if (a->sp_blocks || a->sp_toff) return refuse("and the zero-skipping stream (sp_blocks) exclude each other");
+  if (a->epi == DIA_EPI_CROSSKV) return refuse("has no CROSSKV epilogue (prefill only)");
+  if (a->cmap || a->strip_map) return refuse("has no compaction maps (cmap / strip_map)");
+  if (a->M > 16) return refuse("serves at most 16 rows");
   const bool emits = a->epi == DIA_EPI_RESID_EMIT || a->epi == DIA_EPI_SWIGLU_EMIT;
-  if (!(a->act_f32 & 1) || (emits && !(a->act_f32 & 2)))
-    return dia_fail(DIA_E_ARG, "dia_gemm: the MXFP8 stream needs fp32 activation tiles in and out (act_f32 = 3), not planes");
-  if (!a->W) return dia_fail(DIA_E_ARG, "dia_gemm: the MXFP8 stream needs W");
-  if (a->epi == DIA_EPI_RESID_EMIT && !a->gnext) return dia_fail(DIA_E_ARG, "dia_gemm: the MXFP8 stream needs gnext with RESID_EMIT");
+  if (!(a->act_f32 & 1) || (emits && !(a->act_f32 & 2))) return refuse("needs fp32 activation tiles in and out (act_f32 = 3), not planes");
+  if (!a->W) return refuse("needs W");
+  if (a->epi == DIA_EPI_RESID_EMIT && !a->gnext) return refuse("needs gnext with RESID_EMIT");
   const int sk = a->sk > 1 ? a->sk : 1;
-  if (a->KT % F8_GROUP != 0 || a->KT % sk != 0 || (a->KT / sk) % F8_GROUP != 0)
-    return dia_fail(DIA_E_ARG, "dia_gemm: the MXFP8 stream needs K a multiple of 512 per workgroup (whole groups of 16 k-tiles)");
-  if (a->KT / sk > 16 * F8_MAXW)
-    return dia_fail(DIA_E_ARG, "dia_gemm: the MXFP8 stream serves at most 128 k-tiles per workgroup (K <= 4096; use split-K)");
+  if (a->KT % MX_GROUP != 0 || a->KT % sk != 0 || (a->KT / sk) % MX_GROUP != 0)
+    return refuse("needs K a multiple of 512 per workgroup (whole groups of 16 k-tiles)");
+  if (a->KT / sk > 16 * MX_MAXW) return refuse("serves at most 128 k-tiles per workgroup (K <= 4096; use split-K)");
   return DIA_OK;
 }
 
-// the launch (dia_gemm has run dia_gemm_mxfp8_check and its own argument checks)
-int dia_gemm_mxfp8(const dia_gemm_args* a, void* stream) {
+// the launch (dia_gemm has run dia_gemm_mx_check and its own argument checks)
+int dia_gemm_mx(const dia_gemm_args* a, void* stream) {
   const int sk = a->sk > 1 ? a->sk : 1;
   if (sk > 1 && (!a->sk_scratch || !a->sk_tickets)) return dia_fail(DIA_E_ARG, "dia_gemm: split-K needs sk_scratch, sk_tickets and KT % sk == 0");
   const int ktw = a->KT / sk;                          // k-tiles per workgroup
   GemmK k;
   fill_gemmk(a, k);
   hipStream_t st = (hipStream_t)stream;
-  const int kpw = ktw / 8 <= F8_MAXW ? 8 : 16;
-  const int nw = ktw / kpw;
-  // strips per workgroup (persistent form, next strip's weights in flight during this one's epilogue): the caller's spw, else
-  // 4 from 1024 strips on and about 256 workgroups above 512 strips, as the dense M <= 4 GEMV
-  const int spw = a->spw > 0 ? a->spw : (a->nstrips >= 1024 ? 4 : (a->nstrips > 512 ? (a->nstrips + 255) / 256 : 1));
+  const int spw = stream_spw(a->spw, a->nstrips);      // persistent form: next strip's weights in flight during this one's epilogue
   const bool image = a->M <= 4;                        // (128 k-tiles x 4 rows x 3 planes = 96 KiB at most)
-  if (kpw == 8) return image ? launch_f8<8, 4>(k, nw, sk, spw, st) : launch_f8<8, 16>(k, nw, sk, spw, st);
-  return image ? launch_f8<16, 4>(k, nw, sk, 1, st) : launch_f8<16, 16>(k, nw, sk, 1, st);
+  if (a->w_format == DIA_W_MXFP4) return launch_mx_shape<Fp4>(k, ktw, sk, spw, image, st);
+  return launch_mx_shape<Fp8>(k, ktw, sk, spw, image, st);
 }

@@ -272,10 +272,7 @@ int dia_gemm_sparse24(const dia_gemm_args* a, void* stream) {
     return dia_fail(DIA_E_ARG, "dia_gemm: the 2:4 sparse stream needs the sparse k-tiles per workgroup (KT / sk) to be at most 64, "
                                "or a multiple of 16 up to 128 (K <= 8192 per workgroup; use split-K)");
   const int nw = ktw / kpw;
-  // strips per workgroup (persistent form, next strip's weights in flight during this one's epilogue): the caller's spw, else
-  // 4 from 1024 strips on and about 256 workgroups above 512 strips, as the dense M <= 4 GEMV (the dense kernels' gemm_spw
-  // knob does not apply here)
-  const int spw = a->spw > 0 ? a->spw : (a->nstrips >= 1024 ? 4 : (a->nstrips > 512 ? (a->nstrips + 255) / 256 : 1));
+  const int spw = stream_spw(a->spw, a->nstrips);      // persistent form: next strip's weights in flight during this one's epilogue
   const bool image = a->M <= 4 && sp_smem(2 * ktw, 4) <= 150 * 1024;
   if (kpw == 8) return image ? launch24<8, 4>(k, nw, sk, spw, st) : launch24<8, 16>(k, nw, sk, spw, st);
   return launch24<16, 16>(k, nw, sk, 1, st);

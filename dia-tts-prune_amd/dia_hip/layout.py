@@ -300,14 +300,14 @@ def untile_weight_24(stream: torch.Tensor, K: int, N: int) -> torch.Tensor:
     return dense.reshape(kt8 * 64, ns * 16)[:K, :N].contiguous()
 
 
-# ---- MXFP8 weight stream (dia_gemm_args.w_format = DIA_W_MXFP8, csrc/gemm_mxfp8.hip) ------------------------------------
+# ---- MXFP8 weight stream (dia_gemm_args.w_format = DIA_W_MXFP8, csrc/gemm_mx.hip) ------------------------------------
 FP8_GROUP = 16                           # k-tiles (32 K each) behind one scale block
 FP8_GROUP_BYTES = 256 + 8 * 1024         # scale block + 8 value slots
 
 
 def tile_weight_fp8(w2d: torch.Tensor) -> Tuple[torch.Tensor, int, int]:
     """[K, N] float -> (stream uint8 [N/16, G, 8448], K/32, N/16): the MXFP8 encoding of the matrix (quant.mxfp8_quantize_2d: e4m3
-    elements, one E8M0 scale per 32 consecutive K of a column = per column of a k-tile) in the order csrc/gemm_mxfp8.hip reads.
+    elements, one E8M0 scale per 32 consecutive K of a column = per column of a k-tile) in the order csrc/gemm_mx.hip reads.
     K is zero-padded to a multiple of 32, N to 16, the k-tiles to whole groups of 16 (G = ceil(K/32 / 16)).
 
     Stream of a strip: one block per group of 16 k-tiles, each a sequential 8448 bytes = a 256-byte scale block
@@ -339,13 +339,13 @@ def untile_weight_fp8(stream: torch.Tensor, K: int, N: int) -> torch.Tensor:
     return mxfp8_dequantize_2d(vals.contiguous(), scales.contiguous())[:K, :N].contiguous()
 
 
-# ---- MXFP4 weight stream (dia_gemm_args.w_format = DIA_W_MXFP4, csrc/gemm_mxfp4.hip) ------------------------------------
+# ---- MXFP4 weight stream (dia_gemm_args.w_format = DIA_W_MXFP4, csrc/gemm_mx.hip) ------------------------------------
 FP4_GROUP_BYTES = 256 + 4 * 1024         # scale block + 4 value slots (FP8_GROUP k-tiles)
 
 
 def tile_weight_fp4(w2d: torch.Tensor) -> Tuple[torch.Tensor, int, int]:
     """[K, N] float -> (stream uint8 [N/16, G, 4352], K/32, N/16): the MXFP4 encoding of the matrix (quant.mxfp4_quantize_2d: e2m1
-    elements, one E8M0 scale per 32 consecutive K of a column) in the order csrc/gemm_mxfp4.hip reads.  K is zero-padded to a
+    elements, one E8M0 scale per 32 consecutive K of a column) in the order csrc/gemm_mx.hip reads.  K is zero-padded to a
     multiple of 32, N to 16, the k-tiles to whole groups of 16 (G = ceil(K/32 / 16)).
 
     Stream of a strip: one block per group of 16 k-tiles, each a sequential 4352 bytes = the 256-byte scale block of

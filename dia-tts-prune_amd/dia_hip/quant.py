@@ -6,7 +6,7 @@ stored as E8M0 (``e + 127``); an element is ``w / X`` clamped to +-448 and round
 BEFORE the cast: the block maximum can land in (448, 512), and ``tensor.to(torch.float8_e4m3fn)`` does not saturate.
 
 An e4m3 value times a power of two is exactly a bf16 value, so a dequantised checkpoint is an ordinary state dict that the
-dense bf16 tiles, the oracle and the reference run exactly; the fp8 stream (layout.tile_weight_fp8, csrc/gemm_mxfp8.hip) is a
+dense bf16 tiles, the oracle and the reference run exactly; the fp8 stream (layout.tile_weight_fp8, csrc/gemm_mx.hip) is a
 second encoding of the same numbers.  "Is MXFP8-representable" is ``dequantise(quantise(w)) == w`` (``is_mxfp8``), which
 holds for everything the quantiser emits (quantise(dequantise(q)) reproduces elements and scales bit for bit).
 

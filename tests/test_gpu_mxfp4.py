@@ -1,4 +1,4 @@
-"""The MXFP4 weight stream (dia_gemm_args.w_format = DIA_W_MXFP4, csrc/gemm_mxfp4.hip) on a real MI355X, through the C ABI.
+"""The MXFP4 weight stream (dia_gemm_args.w_format = DIA_W_MXFP4, csrc/gemm_mx.hip) on a real MI355X, through the C ABI.
 Reference: the float64 product of the fp32 activations with the DEQUANTISED weights (an MXFP4 value is exactly a bf16 value, so
 the stream is a second encoding of numbers the dense tiles hold exactly).  Bound: 2e-5 relative to the output scale, the
 project's GEMM bound (tests/test_gpu_kernels.py); in every case the dense dia_gemm on tile_weight(dequantised) must meet it

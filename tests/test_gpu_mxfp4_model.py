@@ -87,7 +87,7 @@ def test_mid_mxfp4_vs_oracle(mid_f4, B):
 
 @pytest.mark.parametrize("B", [1, 8])
 def test_mid_mxfp4_step_runs_the_mxfp4_kernel(mid_f4, B):
-    """the step really streams MXFP4: its GEMMs are k_gemm_mxfp4 launches with every class on, and none with the knob at 0"""
+    """the step really streams MXFP4: its GEMMs are k_gemm_mx<Fp4, ...> launches with every class on, and none with the knob at 0"""
     cfg, sd, w = mid_f4
     ids = [encode_text(effective_text(synthetic_text(32 + 16 * b, cfg)), cfg) for b in range(B)]
     for mask, expect in ((EVERY, True), (0, False)):
@@ -95,10 +95,11 @@ def test_mid_mxfp4_step_runs_the_mxfp4_kernel(mid_f4, B):
         s = DecodeSession(w, ids, kv_dtype="f32", max_tokens=8, seeds=list(range(B)), ignore_eos=True)
         s.prefill()
         s.time_step()
-        names = set(n.split("<")[0].split("::")[-1] for n in s.last_kernel_names)
+        # (an MX launch keeps its format: "k_gemm_mx<Fp4, 8, 4, false>" -> "k_gemm_mx<Fp4")
+        names = set(n.split(",")[0] if n.startswith("k_gemm_mx<") else n.split("<")[0].split("::")[-1] for n in s.last_kernel_names)
         s.close()
-        assert ("k_gemm_mxfp4" in names) == expect, names
-        assert "k_gemm_mxfp8" not in names
+        assert ("k_gemm_mx<Fp4" in names) == expect, names
+        assert "k_gemm_mx<Fp8" not in names
         if expect:
             assert not any(n.startswith(("k_gemv_small", "k_gemm16")) for n in names), names
 
@@ -145,7 +146,7 @@ def _deferred_forms_and_tokens(cfg, w, wo_defer):
     s.close()
     small = [n for n in names if "k_gemv_small<" in n]
     forms = (sum(n.endswith(", 1>") for n in small), sum(n.endswith(", 2>") for n in small))
-    return forms, sum("k_gemm_mxfp4<" in n for n in names), _free_run(cfg, w, 1)[0]
+    return forms, sum("k_gemm_mx<Fp4," in n for n in names), _free_run(cfg, w, 1)[0]
 
 
 @pytest.mark.parametrize("mask,f4_launches", [(-1, 7), (1 << 5, 3), (1 << 6, 1), (1 << 0, 3), (0, 0)],

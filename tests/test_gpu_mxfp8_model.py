@@ -31,7 +31,8 @@ def every_class_streams_mxfp8():
 
 def _kernels_of_a_step(s):
     s.time_step()
-    return set(n.split("<")[0].split("::")[-1] for n in s.last_kernel_names)
+    # (an MX launch keeps its format: "k_gemm_mx<Fp8, 8, 4, false>" -> "k_gemm_mx<Fp8")
+    return set(n.split(",")[0] if n.startswith("k_gemm_mx<") else n.split("<")[0].split("::")[-1] for n in s.last_kernel_names)
 
 
 def _teacher_forced(cfg, sd, w, texts, mt):
@@ -81,7 +82,7 @@ def test_mid_mxfp8_vs_oracle(mid_f8, B):
 
 @pytest.mark.parametrize("B", [1, 8])
 def test_mid_mxfp8_step_runs_the_mxfp8_kernel(mid_f8, B):
-    """the step really streams MXFP8: its GEMMs are k_gemm_mxfp8 launches, and none with the knob at 0"""
+    """the step really streams MXFP8: its GEMMs are k_gemm_mx<Fp8, ...> launches, and none with the knob at 0"""
     cfg, sd, w = mid_f8
     ids = [encode_text(effective_text(synthetic_text(32 + 16 * b, cfg)), cfg) for b in range(B)]
     for mask, expect in ((0x7f7f, True), (0, False)):
@@ -90,7 +91,7 @@ def test_mid_mxfp8_step_runs_the_mxfp8_kernel(mid_f8, B):
         s.prefill()
         names = _kernels_of_a_step(s)
         s.close()
-        assert ("k_gemm_mxfp8" in names) == expect, names
+        assert ("k_gemm_mx<Fp8" in names) == expect, names
         if expect:
             assert not any(n.startswith(("k_gemv_small", "k_gemm16")) for n in names), names
 

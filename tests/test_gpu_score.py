@@ -359,7 +359,8 @@ def test_step_scores_with_the_mxfp8_stream(mid, tuning):
     s = DecodeSession(w8, mid.ids, kv_dtype="f32", max_tokens=ROWS, temperature=0.0, teacher_tokens=mid.rows, score=True)
     s.prefill()
     s.time_step()
-    names = set(n.split("<")[0].split("::")[-1] for n in s.last_kernel_names)
+    # (an MX launch keeps its format: "k_gemm_mx<Fp8, 8, 4, false>" -> "k_gemm_mx<Fp8")
+    names = set(n.split(",")[0] if n.startswith("k_gemm_mx<") else n.split("<")[0].split("::")[-1] for n in s.last_kernel_names)
     s.close()
-    assert "k_gemm_mxfp8" in names and "k_score" in names, names
+    assert "k_gemm_mx<Fp8" in names and "k_score" in names, names
     check_against_own_logits(mid, run_session(mid, w8, score=True, graph=False, keep_logits=True))
