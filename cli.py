@@ -9,6 +9,8 @@ unmerged beside them and chosen per run / per chunk (``--adapter NAME=DIR`` ... 
 ``--codes-output`` (build-only) saves the codec input ``[1, 9, T]`` as .npy, which is the only possible
 output where neither codec is available; ``--no-dac`` skips loading the third-party one.  ``--codec-path FILE`` (build-only) loads
 the native DAC decoder (dia_hip/codec.py) from a DAC checkpoint: ``--output`` then needs no ``dac`` package, also with ``--stream-chunk``.
+With a checkpoint that holds the encoder too, ``--audio-prompt voice.wav`` is encoded by the same native codec, and
+``--encode-audio IN.wav --codes-output out.npy`` (build-only) writes the file's codes ``[T, 9]`` and exits; no model is loaded.
 ``--score-codes FILE.npy`` (build-only) generates nothing: it prints the teacher-forced log-likelihood of the given codes under
 the loaded checkpoint (Dia.score) as one JSON line.
 """
@@ -37,7 +39,7 @@ def set_seed(seed: int):
 def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(description="Dia text-to-dialogue on MI355X: text in, audio (or codec codes) out.")
     p.add_argument("text", type=str, help="text to synthesise ([S1]/[S2] speaker tags); with --audio-prompt give only the new text here, the prompt transcript goes to --audio-prompt-text")
-    p.add_argument("--output", type=str, default=None, help="audio file to write (needs the codec)")
+    p.add_argument("--output", type=str, default=None, help="audio file to write (needs a codec: --codec-path FILE, or the dac package)")
     p.add_argument("--codes-output", type=str, default=None, help="(build-only) path for the codec input codes [1, C, T] as .npy")
     g = p.add_argument_group("Model Loading")
     g.add_argument("--model-path", type=str, default="nari-labs/Dia-1.6B", help="model directory holding config.json and the checkpoint (hub ids cannot be fetched offline)")
@@ -52,9 +54,14 @@ def build_parser() -> argparse.ArgumentParser:
     g.add_argument("--no-dac", action="store_true", help="(build-only) do not load the audio codec; requires --codes-output")
     g.add_argument("--codec-path", type=str, default=None, metavar="FILE", help="(build-only) DAC checkpoint (.pth / state dict) for the "
                    "native codec: --output is decoded on the device by this library, the third-party dac package is not loaded "
-                   "(as with --no-dac), and --stream-chunk N may be combined with --output")
+                   "(as with --no-dac), and --stream-chunk N may be combined with --output; a checkpoint that holds the encoder "
+                   "also encodes an --audio-prompt file and serves --encode-audio")
+    g.add_argument("--encode-audio", type=str, default=None, metavar="IN.wav", help="(build-only) encode this audio file with the native "
+                   "codec and write its codes [T, 9] to --codes-output as .npy, then exit: needs --codec-path, loads no model, and the "
+                   "text argument is ignored (44.1 kHz; another rate needs torchaudio)")
     g = p.add_argument_group("Audio Prompting (Voice Cloning)")
-    g.add_argument("--audio-prompt", type=str, default=None, help="voice to clone: an audio file (needs the codec) or a .npy of codec codes [T, 9]")
+    g.add_argument("--audio-prompt", type=str, default=None, help="voice to clone: an audio file (encoded by the native codec of --codec-path when its checkpoint holds "
+                   "the encoder, else by the dac package) or a .npy of codec codes [T, 9]")
     g.add_argument("--audio-prompt-text", type=str, default=None, help="what is said in --audio-prompt (mandatory with it)")
     g = p.add_argument_group("Generation Parameters")
     g.add_argument("--max-tokens", type=int, default=None, help="cap on generated frames incl. the prompt (default: audio_length of the config)")
@@ -212,9 +219,37 @@ def score_to_stdout(dia, args, text: str, prompt) -> int:
     return 0
 
 
+def encode_to_file(args) -> int:
+    """--encode-audio: the file through the native codec alone, codes [T, C] to --codes-output"""
+    try:
+        from dia_hip.codec import DeviceCodec
+        from dia_hip.model import read_audio_mono, resample_to
+
+        device = torch.device(args.device) if args.device else None
+        codec = DeviceCodec(args.codec_path, device)
+        mono, rate = read_audio_mono(args.encode_audio)
+        codes = codec.encode(resample_to(mono, rate, codec.cfg.sample_rate, args.encode_audio))[0].T.copy()
+        Path(args.codes_output).parent.mkdir(parents=True, exist_ok=True)
+        np.save(args.codes_output, codes)
+        print(f"Codes saved to {args.codes_output}: shape {tuple(codes.shape)}")
+        return 0
+    except Exception as e:
+        print(f"Error encoding {args.encode_audio}: {e}")
+        import traceback
+        traceback.print_exc()
+        return 1
+
+
 def main(argv=None) -> int:
     parser = build_parser()
     args = parser.parse_args(argv)
+    if args.encode_audio:
+        if not args.codec_path or not Path(args.codec_path).is_file():
+            parser.error("--encode-audio needs --codec-path FILE: a DAC checkpoint that holds the encoder.")
+        if not args.codes_output or args.output or args.score_codes or args.slots or args.stream_chunk or args.audio_prompt:
+            parser.error("--encode-audio writes codes only: it needs --codes-output and takes none of --output, --score-codes, "
+                         "--slots, --stream-chunk or --audio-prompt.")
+        return encode_to_file(args)
     if args.score_codes:
         if not Path(args.model_path).is_dir() and not (args.pruned_checkpoint and args.config):
             parser.error("--score-codes needs --model-path: a local model directory holding config.json and the checkpoint "

@@ -1,4 +1,6 @@
-// Codec: the Descript Audio Codec decoder in exact fp32 (dia_codec_embed / dia_codec_conv / dia_codec_convt, DESIGN.md "Codec").
+// Codec: the Descript Audio Codec in exact fp32.  Decoder: dia_codec_embed / dia_codec_conv / dia_codec_convt (DESIGN.md "Codec");
+// encoder: the same dia_codec_conv plus dia_codec_convs (strided and k-3 forms) and dia_codec_quantize, the residual VQ search
+// (DESIGN.md "Codec: encode side").
 //
 // One implicit-GEMM kernel serves every convolution of the decoder.  M = output channels, N = time, K = input channels x taps, on
 // v_mfma_f32_32x32x2_f32: f32 operands, f32 accumulate, bit for bit an fmaf chain, so no plane splitting is needed for reference
@@ -12,6 +14,11 @@
 // staged row: tap j reads position n + tap_off0 + j * tap_step.  That covers
 //   conv, k 7 / 1, dilation d:  tap_step = d, tap_off0 = -(k / 2) d, output o = n
 //   transposed conv, k = 2 s:   one launch phase r per output residue, two taps (x[m], x[m - 1]), output o = m s + r - s / 2
+//   conv, k 3:                  tap_step = 1, tap_off0 = -1, output o = n
+//   strided conv, k = 2 s:      tap j = r + t s, y[o] = sum_{r, t} w[r + t s] x[(o + t) s + r - s / 2]: the s residues r of every input
+//                               channel are staged as s rows of their own, row (ci, r) holding x[ci][i s + r - s / 2] at position i
+//                               (every input element lands in exactly one of them), and the layer is a two-tap convolution
+//                               (offsets 0 and 1) over K = C_in s rows, output o = n (template flag STRIDED: the staging gather)
 // Every chunk accumulates from zero and is then added to the running total: the sum over K is blocked (112 products, then the
 // chunks), which keeps the rounding error of the 5376-term sums of the 768-channel layers near that of a blocked CPU sum.  The
 // order depends on nothing but (channel, tap), so an output element has the same bits wherever its tile, window or batch row lies.
@@ -45,9 +52,10 @@ struct ConvK {
   int lo, width;                       // smallest tap offset (<= 0); staged positions per row = NT + largest - smallest
   int ostride, phases, pad, extra;     // o = n * ostride + phase - pad; n runs over [0, len + extra)
   int tanh_out;
+  int xstride;                         // STRIDED only: s; C_in then counts the staged rows, C_in of the layer x s
 };
 
-template <int MW>
+template <int MW, bool STRIDED = false>
 __global__ __launch_bounds__(256) void k_codec_conv(ConvK p) {
   constexpr int MT = 32 * MW, WAVES_N = 4 / MW, WN = NT / WAVES_N, NACC = WN / 32;
   __shared__ __attribute__((aligned(16))) float xs[KC * XS];
@@ -56,11 +64,12 @@ __global__ __launch_bounds__(256) void k_codec_conv(ConvK p) {
   const int r = lane & 31, h = lane >> 5;
   const int wm = wave % MW, wn = wave / MW;
   const int b = blockIdx.z / p.phases, ph = blockIdx.z - b * p.phases;
-  const int len = p.lens ? min(max(p.lens[b], 0), p.T) : p.T;
+  const int lin = p.lens ? min(max(p.lens[b], 0), p.T) : p.T;    // input positions of this row
+  const int len = STRIDED ? lin / p.xstride : lin;               // positions n of this row
   const int n0 = blockIdx.x * NT;
   if (n0 >= len + p.extra) return;                               // workgroup-uniform
   const int co0 = blockIdx.y * MT;
-  const float* xb = p.x + (long)b * p.C_in * p.ldx;
+  const float* xb = p.x + (long)b * (STRIDED ? p.C_in / p.xstride : p.C_in) * p.ldx;
   const float* wp = p.w + (long)ph * p.ntaps * p.C_in * p.Cp;
 
   f32x16 tot[NACC];
@@ -75,13 +84,15 @@ __global__ __launch_bounds__(256) void k_codec_conv(ConvK p) {
     for (int kk = 0; kk < KC / 4; ++kk) {
       const int ci = wave * (KC / 4) + kk, cg = c0 + ci;
       const bool row = cg < p.C_in;
-      const float al = (row && p.alpha) ? p.alpha[cg] : 0.f;
-      const float iv = (row && p.alpha) ? p.inv[cg] : 0.f;
-      const float* xr = xb + (long)(row ? cg : 0) * p.ldx;
+      const int ch = STRIDED ? cg / p.xstride : cg;              // the layer's input channel
+      const float al = (row && p.alpha) ? p.alpha[ch] : 0.f;
+      const float iv = (row && p.alpha) ? p.inv[ch] : 0.f;
+      const float* xr = xb + (long)(row ? ch : 0) * p.ldx;
+      const int roff = STRIDED ? cg - ch * p.xstride - p.xstride / 2 : 0;
       for (int c = lane; c < p.width; c += 64) {
-        const int i = n0 + p.lo + c;
+        const int i = STRIDED ? (n0 + p.lo + c) * p.xstride + roff : n0 + p.lo + c;
         float v = 0.f;
-        if (row && i >= 0 && i < len) {
+        if (row && i >= 0 && i < lin) {
           v = xr[i];
           if (p.alpha) {
             const float s = sinf(al * v);                        // accurate sinf: alpha x is not range-limited
@@ -179,6 +190,83 @@ __global__ __launch_bounds__(256) void k_codec_embed(EmbK p) {
   }
 }
 
+constexpr int QF = 8;                  // frames per quantiser workgroup: two per wave, one after the other
+constexpr int QMAXDIM = 32;
+
+struct QuantK {
+  const float* z; const int* lens; const float* in_w; const float* in_b; const float* cb; const float* cb2; const float* tables;
+  const float* bias; int* codes;
+  int T, n_cb, cb_size, dim, latent, ldz, ld_codes;
+};
+
+// sum over the 64 lanes by an xor butterfly: every lane ends with the same bits (a + b == b + a), in an order that is fixed
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+  return v;
+}
+
+// The residual VQ search, all stages in one launch.  A wave owns a frame from its latent column to its last code: the column sits
+// in LDS (res), is never written back, and nothing a wave computes depends on which frames share its workgroup.  Per stage:
+// z_e = in_proj(res) (lanes along the latent, butterfly sum), e = z_e / max(|z_e|, 1e-12), the rows of the normalised codebook
+// spread over the lanes (row j on lane j % 64, ascending per lane, strict <), then a butterfly arg-min on (distance, index): the
+// smaller distance wins and, on equal distances, the smaller index -- whatever the lane order.  Control flow is uniform over the
+// workgroup (frames past a row's end are searched on zeros and not written), so the barriers are plain __syncthreads().
+__global__ __launch_bounds__(256) void k_codec_quantize(QuantK p) {
+  extern __shared__ __attribute__((aligned(16))) float qres[];   // [QF][latent]
+  __shared__ float ze[4][QMAXDIM];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int b = blockIdx.y, t0 = blockIdx.x * QF;
+  const int len = p.lens ? min(max(p.lens[b], 0), p.T) : p.T;
+  if (t0 >= len) return;                                         // workgroup-uniform
+  const float* zb = p.z + (long)b * p.latent * p.ldz;
+  for (int e = tid; e < p.latent * QF; e += 256) {
+    const int c = e / QF, tt = e - c * QF, t = t0 + tt;
+    qres[tt * p.latent + c] = t < len ? zb[(long)c * p.ldz + t] : 0.f;
+  }
+  __syncthreads();
+  for (int f = 0; f < QF / 4; ++f) {
+    const int tt = wave * (QF / 4) + f, t = t0 + tt;
+    float* res = qres + tt * p.latent;
+    for (int i = 0; i < p.n_cb; ++i) {
+      const float* wi = p.in_w + (long)i * p.dim * p.latent;
+      for (int d = 0; d < p.dim; ++d) {
+        float s = 0.f;
+        for (int c = lane; c < p.latent; c += 64) s = fmaf(wi[(long)d * p.latent + c], res[c], s);
+        s = wave_sum(s) + p.in_b[i * p.dim + d];
+        if (lane == 0) ze[wave][d] = s;
+      }
+      __syncthreads();
+      float n2 = 0.f;
+      for (int d = 0; d < p.dim; ++d) n2 = fmaf(ze[wave][d], ze[wave][d], n2);
+      const float rn = 1.f / fmaxf(sqrtf(n2), 1e-12f);
+      float e2 = 0.f;
+      for (int d = 0; d < p.dim; ++d) { const float v = ze[wave][d] * rn; e2 = fmaf(v, v, e2); }
+      float best = __builtin_inff();
+      int idx = 0x7fffffff;
+      const float* cbi = p.cb + (long)i * p.cb_size * p.dim;
+      for (int j = lane; j < p.cb_size; j += 64) {
+        float dot = 0.f;
+        for (int d = 0; d < p.dim; ++d) dot = fmaf(ze[wave][d] * rn, cbi[(long)j * p.dim + d], dot);
+        const float dist = e2 - 2.f * dot + p.cb2[i * p.cb_size + j];
+        if (dist < best) { best = dist; idx = j; }
+      }
+#pragma unroll
+      for (int m = 32; m >= 1; m >>= 1) {
+        const float ob = __shfl_xor(best, m, 64);
+        const int oi = __shfl_xor(idx, m, 64);
+        if (ob < best || (ob == best && oi < idx)) { best = ob; idx = oi; }
+      }
+      idx = min(idx, p.cb_size - 1);                             // a column of NaN finds nothing: stay inside the table
+      const float* tab = p.tables + ((long)i * p.cb_size + idx) * p.latent;
+      const float* bs = p.bias + (long)i * p.latent;
+      for (int c = lane; c < p.latent; c += 64) res[c] -= tab[c] + bs[c];
+      if (lane == 0 && t < len) p.codes[((long)b * p.n_cb + i) * p.ld_codes + t] = idx;
+      __syncthreads();                                           // ze is rewritten by the next stage
+    }
+  }
+}
+
 int codec_fail(const char* fmt, ...) {
   char buf[224];
   va_list ap;
@@ -189,7 +277,7 @@ int codec_fail(const char* fmt, ...) {
 }
 
 // what dia_codec_conv and dia_codec_convt share; 0 when clean
-int conv_common(const dia_codec_conv_args* a, const char* fn, int phases, int out_per_in) {
+int conv_common(const dia_codec_conv_args* a, const char* fn, int phases, int out_per_in, int in_per_out = 1) {
   if (!a) return codec_fail("%s: null argument", fn);
   if (!a->x || !a->w || !a->bias || !a->y) return codec_fail("%s: null pointer (x, w, bias and y are required)", fn);
   if ((a->alpha == nullptr) != (a->inv == nullptr)) return codec_fail("%s: alpha and inv go together", fn);
@@ -200,15 +288,25 @@ int conv_common(const dia_codec_conv_args* a, const char* fn, int phases, int ou
   if (a->T < 1 || a->T > DIA_CODEC_MAX_T) return codec_fail("%s: T = %d outside [1, %d]", fn, a->T, DIA_CODEC_MAX_T);
   if (a->B < 1 || (long)a->B * phases > 65535) return codec_fail("%s: B = %d outside [1, %d]", fn, a->B, 65535 / phases);
   if (a->ldx < a->T) return codec_fail("%s: ldx = %d below T = %d", fn, a->ldx, a->T);
-  if ((long)a->ldy < (long)a->T * out_per_in) return codec_fail("%s: ldy = %d below the output length %ld", fn, a->ldy, (long)a->T * out_per_in);
+  if ((long)a->ldy < (long)a->T * out_per_in / in_per_out)
+    return codec_fail("%s: ldy = %d below the output length %ld", fn, a->ldy, (long)a->T * out_per_in / in_per_out);
   if (a->tanh_out != 0 && a->tanh_out != 1) return codec_fail("%s: tanh_out = %d is not 0 or 1", fn, a->tanh_out);
   return 0;
 }
 
-int conv_launch(const dia_codec_conv_args* a, ConvK k, void* stream, const char* name) {
+int conv_launch(const dia_codec_conv_args* a, ConvK k, void* stream, const char* name, bool strided = false) {
   k.x = a->x; k.w = a->w; k.bias = a->bias; k.alpha = a->alpha; k.inv = a->inv; k.res = a->res; k.y = a->y; k.lens = a->lens;
   k.T = a->T; k.C_in = a->C_in; k.C_out = a->C_out; k.Cp = (a->C_out + 31) / 32 * 32; k.ldx = a->ldx; k.ldy = a->ldy;
   k.tanh_out = a->tanh_out;
+  if (strided) {                                                 // K runs over C_in x s staged rows, n over the T / s outputs
+    k.C_in = a->C_in * k.xstride;
+    const int nbs = (a->T / k.xstride + NT - 1) / NT;
+    if (a->C_out <= 32)
+      dia_launch<k_codec_conv<1, true>>(dim3(nbs, 1, a->B), dim3(256), 0, (hipStream_t)stream, k);
+    else
+      dia_launch<k_codec_conv<2, true>>(dim3(nbs, (a->C_out + 63) / 64, a->B), dim3(256), 0, (hipStream_t)stream, k);
+    return dia_check_launch(name);
+  }
   const int nb = (a->T + k.extra + NT - 1) / NT;
   if (a->C_out <= 32)
     dia_launch<k_codec_conv<1>>(dim3(nb, 1, a->B * k.phases), dim3(256), 0, (hipStream_t)stream, k);
@@ -243,6 +341,49 @@ extern "C" int dia_codec_convt(const dia_codec_conv_args* a, void* stream) {
   k.ntaps = 2; k.tap_step = -1; k.tap_off0 = 0; k.lo = -1; k.width = NT + 1;
   k.ostride = s; k.phases = s; k.pad = s / 2; k.extra = 1;
   return conv_launch(a, k, stream, "k_codec_conv (transposed)");
+}
+
+extern "C" int dia_codec_convs(const dia_codec_conv_args* a, void* stream) {
+  const int s = a ? a->stride : 0;
+  if (a && s != 0 && s != 2 && s != 4 && s != 8) return codec_fail("dia_codec_convs: stride %d is not 0 (the k-3 form), 2, 4 or 8", s);
+  if (int rc = conv_common(a, "dia_codec_convs", 1, 1, s ? s : 1)) return rc;
+  if (a->dilation != 0 && a->dilation != 1) return codec_fail("dia_codec_convs: dilation %d is not supported", a->dilation);
+  if (a->res) return codec_fail("dia_codec_convs: a residual is not supported");
+  ConvK k = {};
+  k.ostride = 1; k.phases = 1; k.pad = 0; k.extra = 0;
+  if (s == 0) {
+    if (a->k != 3) return codec_fail("dia_codec_convs: kernel size %d is not 3 (stride 0) or 2 * stride", a->k);
+    k.ntaps = 3; k.tap_step = 1; k.tap_off0 = -1; k.lo = -1; k.width = NT + 2;
+    return conv_launch(a, k, stream, "k_codec_conv (k 3)");
+  }
+  if (a->k != 0 && a->k != 2 * s) return codec_fail("dia_codec_convs: kernel size %d is not 2 * stride = %d", a->k, 2 * s);
+  if (a->T % s != 0) return codec_fail("dia_codec_convs: T = %d is not a multiple of stride %d", a->T, s);
+  k.ntaps = 2; k.tap_step = 1; k.tap_off0 = 0; k.lo = 0; k.width = NT + 1; k.xstride = s;
+  return conv_launch(a, k, stream, "k_codec_conv (strided)", true);
+}
+
+extern "C" int dia_codec_quantize(const dia_codec_quantize_args* a, void* stream) {
+  if (!a) return codec_fail("dia_codec_quantize: null argument");
+  if (!a->z || !a->in_w || !a->in_b || !a->codebook || !a->codebook_sq || !a->tables || !a->bias || !a->codes)
+    return codec_fail("dia_codec_quantize: null pointer (z, in_w, in_b, codebook, codebook_sq, tables, bias and codes are required)");
+  if (a->n_codebooks < 1 || a->n_codebooks > DIA_CODEC_MAX_CODEBOOKS)
+    return codec_fail("dia_codec_quantize: n_codebooks = %d outside [1, %d]", a->n_codebooks, DIA_CODEC_MAX_CODEBOOKS);
+  if (a->codebook_size < 1 || a->codebook_size > DIA_CODEC_MAX_CODEBOOK_SIZE)
+    return codec_fail("dia_codec_quantize: codebook_size = %d outside [1, %d]", a->codebook_size, DIA_CODEC_MAX_CODEBOOK_SIZE);
+  if (a->codebook_dim < 1 || a->codebook_dim > QMAXDIM)
+    return codec_fail("dia_codec_quantize: codebook_dim = %d outside [1, %d]", a->codebook_dim, QMAXDIM);
+  if (a->latent_dim < 1 || a->latent_dim > DIA_CODEC_MAX_CHANNELS)
+    return codec_fail("dia_codec_quantize: latent_dim = %d outside [1, %d]", a->latent_dim, DIA_CODEC_MAX_CHANNELS);
+  if (a->T < 1 || a->T > DIA_CODEC_MAX_T) return codec_fail("dia_codec_quantize: T = %d outside [1, %d]", a->T, DIA_CODEC_MAX_T);
+  if (a->B < 1 || a->B > 65535) return codec_fail("dia_codec_quantize: B = %d outside [1, 65535]", a->B);
+  if (a->ldz < a->T || a->ld_codes < a->T) return codec_fail("dia_codec_quantize: ldz = %d / ld_codes = %d below T = %d", a->ldz, a->ld_codes, a->T);
+  QuantK k = {};
+  k.z = a->z; k.lens = a->lens; k.in_w = a->in_w; k.in_b = a->in_b; k.cb = a->codebook; k.cb2 = a->codebook_sq; k.tables = a->tables;
+  k.bias = a->bias; k.codes = a->codes;
+  k.T = a->T; k.n_cb = a->n_codebooks; k.cb_size = a->codebook_size; k.dim = a->codebook_dim; k.latent = a->latent_dim;
+  k.ldz = a->ldz; k.ld_codes = a->ld_codes;
+  dia_launch<k_codec_quantize>(dim3((a->T + QF - 1) / QF, a->B), dim3(256), (size_t)QF * a->latent_dim * sizeof(float), (hipStream_t)stream, k);
+  return dia_check_launch("k_codec_quantize");
 }
 
 extern "C" int dia_codec_embed(const dia_codec_embed_args* a, void* stream) {

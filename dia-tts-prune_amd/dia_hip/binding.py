@@ -27,7 +27,7 @@ EXPORTS = (
     "dia_score", "dia_engine_set_score",
     "dia_lora_apply", "dia_lora_crosskv", "dia_engine_set_lora",
     "dia_kv_quantize_fp8", "dia_attn_cross_fp8", "dia_engine_set_cross_fp8",
-    "dia_codec_embed", "dia_codec_conv", "dia_codec_convt",
+    "dia_codec_embed", "dia_codec_conv", "dia_codec_convt", "dia_codec_convs", "dia_codec_quantize",
     "dia_seg_mlp", "dia_seg_workspace_bytes", "dia_seg_workspace_control_bytes", "dia_seg_slots", "dia_seg_supported", "dia_seg_error",
 )
 

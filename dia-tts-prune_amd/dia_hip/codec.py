@@ -1,16 +1,18 @@
-"""Native decoder of the Descript Audio Codec (44 kHz): codes [B, 9, T] -> waveform on the HIP device (csrc/codec.hip,
-DESIGN.md "Codec").  The reference goes through the third-party ``dac`` package (dia/audio.py:166-185:
-``quantizer.from_codes`` then ``decode``); this module restates that network from its state dict and needs no package.
+"""The Descript Audio Codec (44 kHz) on the HIP device (csrc/codec.hip): codes [B, 9, T] -> waveform (DESIGN.md "Codec") and
+waveform -> codes (DESIGN.md "Codec: encode side").  The reference goes through the third-party ``dac`` package
+(dia/audio.py:166-185: ``quantizer.from_codes`` then ``decode``; model.py:546-575: ``preprocess`` then ``encode``); this module
+restates those networks from the state dict and needs no package.
 
 Host side only: configuration, checkpoint loading, weight-norm folding (float64), the HBM weight layouts, windowing and the
-streaming state.  All arithmetic on activations happens in the library (dia_codec_embed / dia_codec_conv / dia_codec_convt).
+streaming state.  All arithmetic on activations happens in the library (dia_codec_embed / dia_codec_conv / dia_codec_convt, and
+dia_codec_convs / dia_codec_quantize on the encode side).
 """
 
 from __future__ import annotations
 
 import ctypes as C
 import re
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 from typing import Callable, Dict, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
@@ -29,6 +31,10 @@ class CodecConfig:
     decoder_dim: int = 1536
     decoder_rates: Tuple[int, ...] = (8, 8, 4, 2)
     sample_rate: int = 44100
+    # the encode side.  A decode-side checkpoint says nothing about these two, so they take no part in equality: the configuration
+    # load_codec_state() reads from a decoder's shapes equals the one the checkpoint was made with
+    encoder_dim: int = field(default=64, compare=False)
+    encoder_rates: Tuple[int, ...] = field(default=(2, 4, 8, 8), compare=False)
 
     @property
     def hop(self) -> int:
@@ -37,7 +43,7 @@ class CodecConfig:
 
 def mini_config() -> CodecConfig:
     """the real layer sequence and rates at an eighth of the width (tests)"""
-    return CodecConfig(latent_dim=64, decoder_dim=192)
+    return CodecConfig(latent_dim=64, decoder_dim=192, encoder_dim=8)
 
 
 # ---------------------------------------------------------------------------------------------- the layer list
@@ -80,6 +86,41 @@ def expected_keys(cfg: CodecConfig) -> Dict[str, Tuple[int, ...]]:
     return out
 
 
+def encoder_plan(cfg: CodecConfig) -> List[dict]:
+    """the encoder as a flat list of convolutions, as layer_plan: "conv" is dia_codec_conv (k 7 / 1), "convs" the strided form
+    (k = 2 s, padding s / 2) and "conv3" the final k-3 layer, both dia_codec_convs"""
+    c = cfg.encoder_dim
+    plan = [dict(kind="conv", key="encoder.block.0", snake=None, cin=1, cout=c, k=7, d=1)]
+    for i, s in enumerate(cfg.encoder_rates):
+        blk = f"encoder.block.{i + 1}.block"
+        for u, d in enumerate((1, 3, 9)):
+            ru = f"{blk}.{u}.block"
+            plan.append(dict(kind="conv", key=f"{ru}.1", snake=f"{ru}.0", cin=c, cout=c, k=7, d=d))
+            plan.append(dict(kind="conv", key=f"{ru}.3", snake=f"{ru}.2", cin=c, cout=c, k=1, d=1, res=True))
+        plan.append(dict(kind="convs", key=f"{blk}.4", snake=f"{blk}.3", cin=c, cout=2 * c, s=int(s)))
+        c *= 2
+    n = len(cfg.encoder_rates)
+    plan.append(dict(kind="conv3", key=f"encoder.block.{n + 2}", snake=f"encoder.block.{n + 1}", cin=c, cout=cfg.latent_dim, k=3, d=1))
+    return plan
+
+
+def expected_encoder_keys(cfg: CodecConfig) -> Dict[str, Tuple[int, ...]]:
+    """every encode-side key of the checkpoint with its shape: the encoder and the quantizers' in_proj"""
+    out: Dict[str, Tuple[int, ...]] = {}
+    for L in encoder_plan(cfg):
+        if L["snake"]:
+            out[L["snake"] + ".alpha"] = (1, L["cin"], 1)
+        out[L["key"] + ".weight_g"] = (L["cout"], 1, 1)
+        out[L["key"] + ".weight_v"] = (L["cout"], L["cin"], 2 * L["s"] if L["kind"] == "convs" else L["k"])
+        out[L["key"] + ".bias"] = (L["cout"],)
+    for i in range(cfg.n_codebooks):
+        q = f"quantizer.quantizers.{i}.in_proj"
+        out[f"{q}.weight_g"] = (cfg.codebook_dim, 1, 1)
+        out[f"{q}.weight_v"] = (cfg.codebook_dim, cfg.latent_dim, 1)
+        out[f"{q}.bias"] = (cfg.codebook_dim,)
+    return out
+
+
 _ENCODE_SIDE = re.compile(r"^(encoder\.|quantizer\.quantizers\.\d+\.in_proj\.)")
 
 
@@ -98,6 +139,43 @@ def check_codec_state(cfg: CodecConfig, sd: Dict[str, torch.Tensor]) -> Dict[str
         if tuple(have[k].shape) != shp:
             raise ValueError(f"codec checkpoint: {k} has shape {tuple(have[k].shape)}, expected {shp}")
     return {k: have[k] for k in want}
+
+
+def check_codec_encoder_state(cfg: CodecConfig, sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """the encode-side tensors of `sd` (encoder.*, quantizers' in_proj); a missing or unexpected one, or a wrong shape, is refused
+    by name.  check_codec_state() is the decode side's and ignores exactly these keys."""
+    want = expected_encoder_keys(cfg)
+    have = {k: v for k, v in sd.items() if _ENCODE_SIDE.match(k)}
+    missing = [k for k in want if k not in have]
+    unexpected = [k for k in have if k not in want]
+    if missing:
+        raise KeyError(f"codec checkpoint (encode side): missing keys {missing[:8]}{' ...' if len(missing) > 8 else ''}")
+    if unexpected:
+        raise KeyError(f"codec checkpoint (encode side): unexpected keys {unexpected[:8]}{' ...' if len(unexpected) > 8 else ''}")
+    for k, shp in want.items():
+        if tuple(have[k].shape) != shp:
+            raise ValueError(f"codec checkpoint (encode side): {k} has shape {tuple(have[k].shape)}, expected {shp}")
+    return {k: have[k] for k in want}
+
+
+def infer_encoder_config(cfg: CodecConfig, sd: Dict[str, torch.Tensor], kwargs: Optional[dict] = None) -> CodecConfig:
+    """`cfg` with encoder_dim / encoder_rates read from the encoder's shapes (metadata fields win where present); shapes that do
+    not say are left to check_codec_encoder_state to refuse"""
+    kwargs = kwargs or {}
+    dim, rates = cfg.encoder_dim, []
+    w0 = sd.get("encoder.block.0.weight_v")
+    if w0 is not None and w0.dim() == 3:
+        dim = int(w0.shape[0])
+    while True:
+        w = sd.get(f"encoder.block.{len(rates) + 1}.block.4.weight_v")
+        if w is None or w.dim() != 3:
+            break
+        rates.append(int(w.shape[2]) // 2)
+    if kwargs.get("encoder_dim") is not None:
+        dim = int(kwargs["encoder_dim"])
+    if kwargs.get("encoder_rates") is not None:
+        rates = [int(r) for r in kwargs["encoder_rates"]]
+    return CodecConfig(**{**cfg.__dict__, "encoder_dim": dim, "encoder_rates": tuple(rates) if rates else cfg.encoder_rates})
 
 
 def infer_config(sd: Dict[str, torch.Tensor], sample_rate: int = 44100) -> CodecConfig:
@@ -119,14 +197,13 @@ def infer_config(sd: Dict[str, torch.Tensor], sample_rate: int = 44100) -> Codec
                        decoder_dim=int(ddim), decoder_rates=tuple(int(r) for r in rates), sample_rate=int(sample_rate))
 
 
-def load_codec_state(path_or_obj) -> Tuple[CodecConfig, Dict[str, torch.Tensor]]:
-    """a DAC ``.pth`` ({"state_dict": ..., "metadata": {"kwargs": {...}}}), a bare state dict, or either as an object already in
-    memory -> (configuration, checked decode-side state dict).  Metadata fields win over shapes where they are present."""
+def _open_codec_state(path_or_obj) -> Tuple[CodecConfig, Dict[str, torch.Tensor], dict]:
+    """what load_codec_state() accepts -> (configuration of the decode side, the WHOLE state dict unchecked, metadata kwargs)"""
     obj = path_or_obj
     if isinstance(obj, (str, bytes)) or hasattr(obj, "__fspath__"):
         obj = torch.load(obj, map_location="cpu", weights_only=True)
     if isinstance(obj, tuple) and len(obj) == 2 and isinstance(obj[0], CodecConfig):
-        return obj[0], check_codec_state(obj[0], obj[1])
+        return obj[0], obj[1], {"encoder_dim": obj[0].encoder_dim, "encoder_rates": obj[0].encoder_rates}
     if not isinstance(obj, dict):
         raise TypeError(f"codec checkpoint: expected a dict, got {type(obj).__name__}")
     kwargs = {}
@@ -142,7 +219,14 @@ def load_codec_state(path_or_obj) -> Tuple[CodecConfig, Dict[str, torch.Tensor]]
         over["decoder_rates"] = tuple(int(r) for r in kwargs["decoder_rates"])
     if over:
         cfg = CodecConfig(**{**cfg.__dict__, **over})
-    return cfg, check_codec_state(cfg, obj)
+    return cfg, obj, kwargs
+
+
+def load_codec_state(path_or_obj) -> Tuple[CodecConfig, Dict[str, torch.Tensor]]:
+    """a DAC ``.pth`` ({"state_dict": ..., "metadata": {"kwargs": {...}}}), a bare state dict, or either as an object already in
+    memory -> (configuration, checked decode-side state dict).  Metadata fields win over shapes where they are present."""
+    cfg, sd, _ = _open_codec_state(path_or_obj)
+    return cfg, check_codec_state(cfg, sd)
 
 
 def synthetic_state_dict(cfg: CodecConfig, seed: int = 0) -> Dict[str, torch.Tensor]:
@@ -179,6 +263,32 @@ def synthetic_state_dict(cfg: CodecConfig, seed: int = 0) -> Dict[str, torch.Ten
     return sd
 
 
+def synthetic_encoder_state(cfg: CodecConfig, seed: int = 0) -> Dict[str, torch.Tensor]:
+    """random encode-side weights in checkpoint form, from a generator of their own (synthetic_state_dict's draws are untouched).
+    Gains as there: fan-in scaling (weight_g = gain makes the output of unit-scale inputs ~ gain), small residual branches; the
+    first layer lifts a waveform of RMS ~ 0.2 to unit scale.  The latent's RMS lies in [0.05, 5] on the test inputs."""
+    g = torch.Generator().manual_seed(int(seed) + 0x5eed)
+
+    def rnd(*shape):
+        return torch.randn(*shape, generator=g, dtype=torch.float32)
+
+    sd: Dict[str, torch.Tensor] = {}
+    for L in encoder_plan(cfg):
+        if L["snake"]:
+            sd[L["snake"] + ".alpha"] = 0.5 + torch.rand(1, L["cin"], 1, generator=g, dtype=torch.float32)
+        k = 2 * L["s"] if L["kind"] == "convs" else L["k"]
+        gain = 0.3 if L.get("res") else (4.0 if L["cin"] == 1 else 1.0)
+        sd[L["key"] + ".weight_g"] = gain * (1.0 + 0.1 * rnd(L["cout"], 1, 1))
+        sd[L["key"] + ".weight_v"] = rnd(L["cout"], L["cin"], k)
+        sd[L["key"] + ".bias"] = 0.05 * rnd(L["cout"])
+    for i in range(cfg.n_codebooks):
+        q = f"quantizer.quantizers.{i}.in_proj"
+        sd[f"{q}.weight_g"] = 1.0 + 0.1 * rnd(cfg.codebook_dim, 1, 1)
+        sd[f"{q}.weight_v"] = rnd(cfg.codebook_dim, cfg.latent_dim, 1)
+        sd[f"{q}.bias"] = 0.05 * rnd(cfg.codebook_dim)
+    return sd
+
+
 # ---------------------------------------------------------------------------------------------- folding and layouts
 def fold_weight_norm(g: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
     """w = g v / |v| in float64, the norm over every dimension but 0 (torch.nn.utils.weight_norm, dim = 0).  For a transposed
@@ -211,6 +321,34 @@ def convt_layout(w: torch.Tensor) -> torch.Tensor:
     return out.contiguous()
 
 
+def convs_layout(w: torch.Tensor) -> torch.Tensor:
+    """strided convolution [C_out, C_in, 2 s] -> fp32 [2][C_in * s][Cp]: out[t][ci * s + r][co] = w[co][ci][r + t s], the weight of
+    x[ci][(o + t) s + r - s / 2] in output o"""
+    co, ci, k2 = w.shape
+    s = k2 // 2
+    out = torch.zeros(2, ci * s, _pad32(co), dtype=torch.float32)
+    out[:, :, :co] = w.reshape(co, ci, 2, s).permute(2, 1, 3, 0).reshape(2, ci * s, co).to(torch.float32)
+    return out.contiguous()
+
+
+def quantizer_tables(cfg: CodecConfig, sd: Dict[str, torch.Tensor], enc: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """the search's operands, prepared in float64 and stored fp32: in_proj folded [n][dim][latent] with its bias [n][dim], the
+    codebook rows L2-normalised (eps 1e-12) [n][size][dim], the squared norm of each stored row [n][size], and the out_proj bias
+    per codebook [n][latent] (the tables themselves are embed_tables')"""
+    in_w, in_b, cb, cb2, ob = [], [], [], [], []
+    for i in range(cfg.n_codebooks):
+        q = f"quantizer.quantizers.{i}"
+        in_w.append(fold_weight_norm(enc[f"{q}.in_proj.weight_g"], enc[f"{q}.in_proj.weight_v"])[:, :, 0].to(torch.float32))
+        in_b.append(enc[f"{q}.in_proj.bias"].to(torch.float32))
+        c = sd[f"{q}.codebook.weight"].to(torch.float64)
+        c = (c / c.norm(dim=1, keepdim=True).clamp_min(1e-12)).to(torch.float32)
+        cb.append(c)
+        cb2.append(c.to(torch.float64).pow(2).sum(dim=1).to(torch.float32))
+        ob.append(sd[f"{q}.out_proj.bias"].to(torch.float32))
+    return dict(in_w=torch.stack(in_w).contiguous(), in_b=torch.stack(in_b).contiguous(), cb=torch.stack(cb).contiguous(),
+                cb2=torch.stack(cb2).contiguous(), bias=torch.stack(ob).contiguous())
+
+
 def embed_tables(cfg: CodecConfig, sd: Dict[str, torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
     """codebook_i x out_proj_i folded in float64: tables fp32 [n_codebooks][codebook_size][latent_dim] and the summed bias"""
     tabs, bias = [], torch.zeros(cfg.latent_dim, dtype=torch.float64)
@@ -237,6 +375,40 @@ def context_frames(cfg: CodecConfig) -> int:
             s = L["s"]
             a, b = (a + s // 2) // s - 1, (b + s // 2) // s
     return max(-a, b)
+
+
+def encode_context_frames(cfg: CodecConfig) -> int:
+    """frames of real samples an encode window needs on each side so that its interior latents equal the whole encode: the
+    interval of samples latent frame 0 depends on, walked back through encoder_plan.  k 3 widens [a, b] to [a - 1, b + 1], k 7 of
+    dilation d to [a - 3 d, b + 3 d]; a strided convolution (kernel 2 s, padding s / 2) reads [o s - s / 2, o s + 3 s / 2 - 1] for
+    output o, so [a, b] becomes [a s - s / 2, b s + 3 s / 2 - 1].  The quantiser is per frame and adds nothing."""
+    a, b = 0, 0
+    for L in reversed(encoder_plan(cfg)):
+        if L["kind"] == "convs":
+            s = L["s"]
+            a, b = a * s - s // 2, b * s + (3 * s) // 2 - 1
+        else:
+            r = (L["k"] // 2) * L["d"]
+            a, b = a - r, b + r
+    hop = int(np.prod(cfg.encoder_rates))
+    return max(-(a // hop), b // hop)                           # ceil(-a / hop) frames before, the frame of sample b behind
+
+
+def encode_windowed(latent_fn: Callable[[np.ndarray], np.ndarray], wave: np.ndarray, window: int, ctx: int, hop: int) -> np.ndarray:
+    """samples [L] (L a multiple of hop) through latent_fn (samples of one utterance -> its latents [latent, frames]) window by
+    window: every window is encoded with ctx frames of samples on each side as an utterance of its own, the interiors are joined"""
+    parts = []
+    for lo, f0, f1, hi in window_plan(wave.shape[-1] // hop, window, ctx):
+        z = latent_fn(wave[lo * hop:hi * hop])
+        parts.append(z[:, f0 - lo:f1 - lo])
+    return np.concatenate(parts, axis=1)
+
+
+def preprocess(wave: np.ndarray, hop: int) -> np.ndarray:
+    """DAC's preprocess: zeros on the right up to a multiple of hop"""
+    w = np.asarray(wave, dtype=np.float32).reshape(-1)
+    pad = -w.shape[0] % hop
+    return np.concatenate([w, np.zeros(pad, dtype=np.float32)]) if pad else w
 
 
 def window_plan(T: int, window: int, ctx: int) -> List[Tuple[int, int, int, int]]:
@@ -315,11 +487,23 @@ class CodecConvArgs(C.Structure):
     ]
 
 
+class CodecQuantizeArgs(C.Structure):
+    _fields_ = [
+        ("z", C.c_void_p), ("lens", C.c_void_p), ("B", C.c_int32), ("T", C.c_int32),
+        ("n_codebooks", C.c_int32), ("codebook_size", C.c_int32), ("codebook_dim", C.c_int32), ("latent_dim", C.c_int32),
+        ("ldz", C.c_int32), ("ld_codes", C.c_int32),
+        ("in_w", C.c_void_p), ("in_b", C.c_void_p), ("codebook", C.c_void_p), ("codebook_sq", C.c_void_p), ("tables", C.c_void_p),
+        ("bias", C.c_void_p), ("codes", C.c_void_p),
+    ]
+
+
 def _fns():
     L = hb.lib()
     L.dia_codec_embed.argtypes = [C.POINTER(CodecEmbedArgs), C.c_void_p]
     L.dia_codec_conv.argtypes = [C.POINTER(CodecConvArgs), C.c_void_p]
     L.dia_codec_convt.argtypes = [C.POINTER(CodecConvArgs), C.c_void_p]
+    L.dia_codec_convs.argtypes = [C.POINTER(CodecConvArgs), C.c_void_p]
+    L.dia_codec_quantize.argtypes = [C.POINTER(CodecQuantizeArgs), C.c_void_p]
     return L
 
 
@@ -357,9 +541,39 @@ def codec_conv(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, *, c_out: i
     return y
 
 
+def codec_convs(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, *, c_out: int, stride: int = 0, alpha: Optional[torch.Tensor] = None,
+                inv: Optional[torch.Tensor] = None, lens: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """dia_codec_convs on device tensors: the strided form (stride s, k = 2 s; w from convs_layout) or the k-3 form (stride 0; w
+    from conv_layout): x fp32 [B, C_in, T] -> y fp32 [B, c_out, T // s]; `lens` are input lengths; positions beyond stay 0"""
+    B, cin, T = x.shape
+    To = max(1, T // stride) if stride else T
+    y = torch.zeros(B, c_out, To, dtype=torch.float32, device=x.device)
+    a = CodecConvArgs(x=hb.ptr(x), w=hb.ptr(w), bias=hb.ptr(bias), alpha=hb.ptr(alpha), inv=hb.ptr(inv), y=hb.ptr(y), lens=hb.ptr(lens),
+                      B=B, T=T, C_in=cin, C_out=c_out, ldx=T, ldy=To, k=0 if stride else 3, dilation=1, stride=stride)
+    hb.check(_fns().dia_codec_convs(C.byref(a), C.c_void_p(torch.cuda.current_stream().cuda_stream)), "dia_codec_convs")
+    return y
+
+
+def codec_quantize(z: torch.Tensor, q: Dict[str, torch.Tensor], tables: torch.Tensor, lens: Optional[torch.Tensor] = None,
+                   T: Optional[int] = None) -> torch.Tensor:
+    """dia_codec_quantize on device tensors: z fp32 [B, latent, ld], q = quantizer_tables() on the device, tables = embed_tables()[0]
+    -> codes int32 [B, n_codebooks, ld] (frames beyond a row's length stay 0)"""
+    B, latent, ld = z.shape
+    n, size, dim = q["cb"].shape
+    codes = torch.zeros(B, n, ld, dtype=torch.int32, device=z.device)
+    a = CodecQuantizeArgs(z=hb.ptr(z), lens=hb.ptr(lens), B=B, T=ld if T is None else T, n_codebooks=n, codebook_size=size,
+                          codebook_dim=dim, latent_dim=latent, ldz=ld, ld_codes=ld, in_w=hb.ptr(q["in_w"]), in_b=hb.ptr(q["in_b"]),
+                          codebook=hb.ptr(q["cb"]), codebook_sq=hb.ptr(q["cb2"]), tables=hb.ptr(tables), bias=hb.ptr(q["bias"]),
+                          codes=hb.ptr(codes))
+    hb.check(_fns().dia_codec_quantize(C.byref(a), C.c_void_p(torch.cuda.current_stream().cuda_stream)), "dia_codec_quantize")
+    return codes
+
+
 class DeviceCodec:
-    """The decoder resident on a HIP device: weight norm folded once on the host in float64, weights uploaded in the library's
-    tap-major layouts, two ping-pong activation buffers sized by `window` (never by an utterance's length).
+    """The codec resident on a HIP device: weight norm folded once on the host in float64, weights uploaded in the library's
+    tap-major layouts, two ping-pong activation buffers sized by `window` (never by an utterance's length).  The decoder is always
+    there; the encoder is prepared when the checkpoint has any ``encoder.`` key, and a checkpoint without one, or with a
+    malformed one, still decodes: `encoder_error` keeps what encode() will raise.
 
     decode() cuts every utterance into windows of at most `window` frames with context_frames(cfg) frames of context on each side,
     runs the windows of all rows as rows of batched launches (each with its own length) and keeps the interiors."""
@@ -368,7 +582,8 @@ class DeviceCodec:
                  workspace_bytes: int = 1 << 30):
         if cfg is not None:
             state = (cfg, state)
-        self.cfg, sd = load_codec_state(state)
+        self.cfg, whole, meta = _open_codec_state(state)
+        sd = check_codec_state(self.cfg, whole)
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         if self.device.type != "cuda":
             raise hb.DiaHipError(f"device {self.device} is not a HIP device; there is no CPU fallback")
@@ -403,6 +618,48 @@ class DeviceCodec:
         self._bufs: Optional[Tuple[torch.Tensor, torch.Tensor]] = None
         self._rows = 0
         self.layer_events: Optional[list] = None                # scratch/codec_speed.py: set to [] to collect (label, start, stop) events per launch
+        self.enc_layers: Optional[List[dict]] = None
+        self.encoder_error: Optional[Exception] = None
+        if any(k.startswith("encoder.") for k in whole):
+            try:
+                self._prepare_encoder(sd, whole, meta, int(workspace_bytes))
+            except (KeyError, ValueError) as e:
+                self.enc_layers, self.encoder_error = None, e
+        else:
+            self.encoder_error = KeyError("codec checkpoint: no encode side (missing keys ['encoder.block.0.weight_g', ...]); encode() needs "
+                                          "the encoder.* and quantizer.quantizers.N.in_proj.* tensors")
+
+    def _prepare_encoder(self, sd, whole, meta, workspace_bytes: int) -> None:
+        self.cfg = cfg = infer_encoder_config(self.cfg, whole, meta)
+        if int(np.prod(cfg.encoder_rates)) != cfg.hop:
+            raise ValueError(f"codec checkpoint (encode side): encoder_rates {cfg.encoder_rates} do not multiply to the hop {cfg.hop}")
+        enc = check_codec_encoder_state(cfg, whole)
+        dev = self.device
+        layers, div, per_frame = [], 1, cfg.hop
+        for L in encoder_plan(cfg):
+            w = fold_weight_norm(enc[L["key"] + ".weight_g"], enc[L["key"] + ".weight_v"])
+            D = dict(L)
+            D["w"] = (convs_layout(w) if L["kind"] == "convs" else conv_layout(w)).to(dev)
+            D["b"] = enc[L["key"] + ".bias"].to(torch.float32).to(dev)
+            if L["snake"]:
+                al = enc[L["snake"] + ".alpha"]
+                D["alpha"] = al.reshape(-1).to(torch.float32).to(dev)
+                D["inv"] = snake_inverse(al).to(dev)
+            D["div_in"] = div                                   # samples per position of this layer's input
+            if L["kind"] == "convs":
+                div *= L["s"]
+            per_frame = max(per_frame, L["cin"] * cfg.hop // D["div_in"], L["cout"] * cfg.hop // div)
+            layers.append(D)
+        self.qtabs = {k: v.to(dev) for k, v in quantizer_tables(cfg, sd, enc).items()}
+        self.enc_ctx = encode_context_frames(cfg)
+        self.enc_wmax = self.window + 2 * self.enc_ctx
+        self.enc_row_floats = per_frame * self.enc_wmax
+        self.enc_rows_cap = int(max(1, min(4096, workspace_bytes // (2 * 4 * self.enc_row_floats))))
+        self.enc_layers = layers
+
+    @property
+    def has_encoder(self) -> bool:
+        return self.enc_layers is not None
 
     # -------------------------------------------------------------------------------------- device side
     def _workspace(self, rows: int) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -503,6 +760,124 @@ class DeviceCodec:
         if len(lengths) != c.shape[0] or any(n < 0 or n > c.shape[2] for n in lengths):
             raise ValueError("codec: one length in [0, T] per row")
         return self.decode_batch([c[b, :, :n] for b, n in enumerate(lengths)], window)
+
+    # -------------------------------------------------------------------------------------- encode
+    def _run_encode(self, jobs: Sequence[Tuple[np.ndarray, int, int]]) -> List[Tuple[np.ndarray, np.ndarray]]:
+        """every job (samples [n hop] with n <= enc_wmax, first kept frame, kept frames) encoded as an utterance of its own: rows of
+        one chain of batched launches; the kept latents [latent, kept] alone go to the quantiser -> (codes [n_codebooks, kept], latents)"""
+        cfg, lib = self.cfg, _fns()
+        hop, out = cfg.hop, []
+        with torch.cuda.device(self.device):
+            st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            for g0 in range(0, len(jobs), self.enc_rows_cap):
+                grp = jobs[g0:g0 + self.enc_rows_cap]
+                J, W = len(grp), self.enc_wmax
+                Tg = max(j[0].shape[0] for j in grp) // hop
+                host = np.zeros((J, W * hop), dtype=np.float32)
+                for r, (w, _, _) in enumerate(grp):
+                    host[r, :w.shape[0]] = w
+                x0 = torch.from_numpy(host).to(self.device)
+                lens = torch.tensor([j[0].shape[0] for j in grp], dtype=torch.int32, device=self.device)
+                cur, oth = self._workspace(-(-J * self.enc_row_floats // self.row_floats))
+                stage_lens = {1: lens}
+                for L in self.enc_layers:
+                    d = L["div_in"]
+                    if self.layer_events is not None:
+                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        self.layer_events.append((f"{L['kind']} {L['cin']}->{L['cout']} k{L.get('k', 2 * L.get('s', 0))} d{L.get('d', 1)}", e0, e1))
+                        e0.record()
+                    if d not in stage_lens:
+                        stage_lens[d] = lens // d
+                    ld = W * hop // d
+                    a = CodecConvArgs(w=hb.ptr(L["w"]), bias=hb.ptr(L["b"]), alpha=hb.ptr(L.get("alpha")), inv=hb.ptr(L.get("inv")),
+                                      lens=hb.ptr(stage_lens[d]), B=J, T=Tg * hop // d, C_in=L["cin"], C_out=L["cout"], ldx=ld)
+                    if L["kind"] == "convs":
+                        a.x, a.y, a.ldy, a.stride, a.k, a.dilation = hb.ptr(cur), hb.ptr(oth), ld // L["s"], L["s"], 2 * L["s"], 1
+                        hb.check(lib.dia_codec_convs(C.byref(a), st), "dia_codec_convs")
+                        cur, oth = oth, cur
+                    elif L["kind"] == "conv3":
+                        a.x, a.y, a.ldy, a.k, a.dilation = hb.ptr(cur), hb.ptr(oth), ld, 3, 1
+                        hb.check(lib.dia_codec_convs(C.byref(a), st), "dia_codec_convs")
+                        cur, oth = oth, cur
+                    elif L.get("res"):                         # as in the decoder: the sum lands on the unit's input
+                        a.x, a.y, a.res, a.ldy, a.k, a.dilation = hb.ptr(oth), hb.ptr(cur), hb.ptr(cur), ld, 1, 1
+                        hb.check(lib.dia_codec_conv(C.byref(a), st), "dia_codec_conv")
+                    else:
+                        a.x, a.y, a.ldy, a.k, a.dilation = hb.ptr(x0 if L["cin"] == 1 and not L["snake"] else cur), hb.ptr(oth), ld, L["k"], L["d"]
+                        hb.check(lib.dia_codec_conv(C.byref(a), st), "dia_codec_conv")
+                        if not L["snake"]:                     # the first layer: its result is the new stream
+                            cur, oth = oth, cur
+                    if self.layer_events is not None:
+                        self.layer_events[-1][2].record()
+                # the kept frames of every job, gathered to the front of a tensor of their own: the quantiser sees nothing else
+                zall = cur[:J * cfg.latent_dim * W].view(J, cfg.latent_dim, W)
+                Wq = max(j[2] for j in grp)
+                first = torch.tensor([j[1] for j in grp], dtype=torch.int64, device=self.device)
+                at = (first[:, None] + torch.arange(Wq, device=self.device)[None, :]).clamp_(max=W - 1)
+                z = torch.gather(zall, 2, at[:, None, :].expand(J, cfg.latent_dim, Wq)).contiguous()
+                qlens = torch.tensor([j[2] for j in grp], dtype=torch.int32, device=self.device)
+                if self.layer_events is not None:
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    self.layer_events.append((f"quantize {cfg.latent_dim} x {cfg.n_codebooks}", e0, e1))
+                    e0.record()
+                codes = codec_quantize(z, self.qtabs, self.tables, lens=qlens)
+                if self.layer_events is not None:
+                    self.layer_events[-1][2].record()
+                codes_h, z_h = codes.cpu().numpy(), z.cpu().numpy()
+                for r, (_, _, n) in enumerate(grp):
+                    out.append((codes_h[r, :, :n].astype(np.int64), z_h[r, :, :n].copy()))
+        return out
+
+    def encode_batch(self, rows: Sequence, window: Optional[int] = None, return_latents: bool = False):
+        """one mono float waveform [L_b] per utterance -> int64 codes [n_codebooks, ceil(L_b / hop)] per utterance (with
+        return_latents: also the list of fp32 latents [latent, T_b] the codes were searched from).  Every row is padded with zeros
+        on the right to a multiple of hop (DAC's preprocess) and comes out as when encoded alone; long rows run in windows of
+        `window` frames with encode_context_frames(cfg) frames of samples on each side."""
+        if self.enc_layers is None:
+            raise self.encoder_error
+        window = self.window if window is None else int(window)
+        if not 1 <= window <= self.window:
+            raise ValueError(f"window = {window} outside [1, {self.window}] (the workspace is sized by the codec's window)")
+        hop, waves = self.cfg.hop, []
+        for r in rows:
+            w = np.asarray(r.detach().cpu() if isinstance(r, torch.Tensor) else r)
+            if w.ndim == 2 and w.shape[0] == 1:
+                w = w[0]
+            if w.ndim != 1 or w.dtype.kind != "f":
+                raise ValueError(f"codec: a waveform of shape {tuple(w.shape)} and dtype {w.dtype}, expected mono float samples [L]")
+            waves.append(preprocess(w, hop))
+        jobs, plan = [], []
+        for b, w in enumerate(waves):
+            for lo, f0, f1, hi in window_plan(w.shape[0] // hop, window, self.enc_ctx):
+                jobs.append((w[lo * hop:hi * hop], f0 - lo, f1 - f0))
+                plan.append(b)
+        codes: List[List[np.ndarray]] = [[] for _ in waves]
+        lat: List[List[np.ndarray]] = [[] for _ in waves]
+        for b, (c, z) in zip(plan, self._run_encode(jobs)):
+            codes[b].append(c)
+            lat[b].append(z)
+        n, m = self.cfg.n_codebooks, self.cfg.latent_dim
+        cs = [np.concatenate(p, axis=1) if p else np.zeros((n, 0), dtype=np.int64) for p in codes]
+        if not return_latents:
+            return cs
+        return cs, [np.concatenate(p, axis=1) if p else np.zeros((m, 0), dtype=np.float32) for p in lat]
+
+    def encode(self, wave, lengths: Optional[Sequence[int]] = None, window: Optional[int] = None) -> np.ndarray:
+        """mono float samples [L] or [B, L] (per-row `lengths` in samples, default L) -> int64 codes [B, n_codebooks, T],
+        T = ceil(max length / hop); a shorter row's codes end at ceil(lengths[b] / hop) and are 0 behind"""
+        w = np.asarray(wave.detach().cpu() if isinstance(wave, torch.Tensor) else wave)
+        if w.ndim == 1:
+            w = w[None]
+        if w.ndim != 2:
+            raise ValueError(f"codec: a waveform of shape {tuple(w.shape)}, expected [L] or [B, L]")
+        lengths = [w.shape[1]] * w.shape[0] if lengths is None else [int(n) for n in lengths]
+        if len(lengths) != w.shape[0] or any(n < 0 or n > w.shape[1] for n in lengths):
+            raise ValueError("codec: one length in [0, L] per row")
+        rows = self.encode_batch([w[b, :n] for b, n in enumerate(lengths)], window)
+        out = np.zeros((len(rows), self.cfg.n_codebooks, max([r.shape[1] for r in rows] + [0])), dtype=np.int64)
+        for b, r in enumerate(rows):
+            out[b, :, :r.shape[1]] = r
+        return out
 
     def stream(self, window: Optional[int] = None) -> CodecStream:
         """a streaming state for one utterance on this codec"""

@@ -15,7 +15,7 @@ import time
 from dataclasses import dataclass
 from enum import Enum
 from pathlib import Path
-from typing import Dict, List, Optional, Sequence, Union
+from typing import Dict, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -97,7 +97,7 @@ class Dia:
         self.compute_dtype = compute_dtype.to_dtype()
         self.model: Optional[DeviceWeights] = None      # resident weights (reference: DiaModel nn.Module)
         self.dac_model = None
-        self.codec = None                               # codec.DeviceCodec of load_codec(): the native DAC decoder
+        self.codec = None                               # codec.DeviceCodec of load_codec(): the native DAC codec
         self.last_codes: Optional[np.ndarray] = None
         self.weights_rounded = False
         self.weights_exact_planes = False
@@ -204,9 +204,10 @@ class Dia:
         return dia
 
     def load_codec(self, path_or_state, window: int = 128):
-        """Set the native DAC decoder (dia_hip/codec.py, csrc/codec.hip) on this instance: a DAC ``.pth`` / bare state dict, as a
+        """Set the native DAC codec (dia_hip/codec.py, csrc/codec.hip) on this instance: a DAC ``.pth`` / bare state dict, as a
         path or in memory.  generate() then returns waveforms and generate_audio_batch / stream_audio work; the third-party
-        ``dac`` package is not needed.  A missing or unexpected decoder / quantizer key is refused by name."""
+        ``dac`` package is not needed.  A missing or unexpected decoder / quantizer key is refused by name.  A checkpoint that
+        also holds the encoder makes load_audio() / encode_audio() and file prompts work; one without still decodes."""
         from .codec import DeviceCodec
         with torch.cuda.device(self.device):
             self.codec = DeviceCodec(path_or_state, self.device, window=window)
@@ -547,11 +548,28 @@ class Dia:
         return audio.squeeze().cpu().numpy()
 
     # ------------------------------------------------------------------ audio file IO (host side)
-    # Both need third-party pieces that do not exist offline (the DAC codec, torchaudio, soundfile): row (f)-3 of
-    # SURVEY.md section 8 stays outside this build.  The methods keep the reference's names, arguments and failure
-    # behaviour (reference model.py:546-595) so that callers written against it run unchanged once a codec is attached.
+    # With a native codec that has an encode side (load_codec() of a full DAC checkpoint) a file prompt needs no third-party
+    # piece: the file is read by torchaudio when that is importable and by the standard library's wave module otherwise, and
+    # encoded by DeviceCodec.encode.  Without one the methods keep the reference's names, arguments and failure behaviour
+    # (reference model.py:546-595), which need the dac package and torchaudio.
+    @torch.inference_mode()
+    def encode_audio(self, wave, sample_rate: int = DEFAULT_SAMPLE_RATE) -> torch.Tensor:
+        """mono float samples [L] (array or tensor) -> codec frames [T, C] (int64), through the native codec: zeros on the right up
+        to a multiple of 512 samples (DAC's preprocess), T = ceil(L / 512).  A rate other than the codec's is resampled by
+        torchaudio where that is importable and refused otherwise."""
+        codec = self._need_codec()
+        w = np.asarray(wave.detach().cpu() if isinstance(wave, torch.Tensor) else wave, dtype=np.float32)
+        if w.ndim == 2:
+            w = w.mean(axis=0)
+        w = resample_to(w.reshape(-1), int(sample_rate), codec.cfg.sample_rate, "the waveform")
+        return torch.from_numpy(codec.encode(w)[0].T.copy())
+
     def load_audio(self, audio_path: str) -> torch.Tensor:
         """waveform file -> codec frames [T, C] for ``generate(audio_prompt=...)`` (mono, 44.1 kHz)."""
+        if self.codec is not None and self.codec.has_encoder:
+            mono, rate = read_audio_mono(audio_path)
+            mono = resample_to(mono, rate, self.codec.cfg.sample_rate, audio_path)
+            return self.encode_audio(mono, self.codec.cfg.sample_rate)
         codec = self.dac_model
         if codec is None:
             raise RuntimeError("DAC model not loaded. Cannot encode audio.")
@@ -594,6 +612,54 @@ class Dia:
             soundfile.write(str(out), samples.clip(-1.0, 1.0), sample_rate)
         except Exception as e:
             print(f"Error saving audio to {path}: {e}")
+
+
+def read_audio_mono(path: str) -> Tuple[np.ndarray, int]:
+    """audio file -> (mono float32 samples in [-1, 1), sample rate): torchaudio where it is importable, else ``.wav`` through the
+    standard library's wave module (8-bit unsigned, 16 / 24 / 32-bit signed PCM); channels are averaged"""
+    if not Path(path).is_file():
+        raise FileNotFoundError(f"Audio file not found: {path}")
+    try:
+        import torchaudio  # type: ignore
+    except ImportError:
+        torchaudio = None
+    if torchaudio is not None:
+        wav, rate = torchaudio.load(path)
+        return wav.mean(dim=0).to(torch.float32).numpy(), int(rate)
+    if not str(path).lower().endswith(".wav"):
+        raise RuntimeError(f"Error loading audio file {path}: without torchaudio only .wav files can be read")
+    import wave
+
+    with wave.open(str(path), "rb") as f:
+        ch, width, rate, n = f.getnchannels(), f.getsampwidth(), f.getframerate(), f.getnframes()
+        if f.getcomptype() != "NONE":
+            raise RuntimeError(f"Error loading audio file {path}: compression {f.getcomptype()} is not PCM")
+        raw = f.readframes(n)
+    if width == 1:
+        x = (np.frombuffer(raw, dtype=np.uint8).astype(np.float64) - 128.0) / 128.0
+    elif width == 2:
+        x = np.frombuffer(raw, dtype="<i2").astype(np.float64) / 32768.0
+    elif width == 3:
+        b = np.frombuffer(raw, dtype=np.uint8).reshape(-1, 3).astype(np.int32)
+        x = (((b[:, 0] | (b[:, 1] << 8) | (b[:, 2] << 16)) ^ 0x800000) - 0x800000).astype(np.float64) / 8388608.0
+    elif width == 4:
+        x = np.frombuffer(raw, dtype="<i4").astype(np.float64) / 2147483648.0
+    else:
+        raise RuntimeError(f"Error loading audio file {path}: {8 * width}-bit samples are not supported")
+    return x.reshape(-1, ch).mean(axis=1).astype(np.float32), int(rate)
+
+
+def resample_to(mono: np.ndarray, rate: int, want: int, what: str) -> np.ndarray:
+    """`mono` at `want` Hz: unchanged at that rate, through torchaudio.functional.resample where torchaudio is importable, refused
+    by rate otherwise (this library has no resampler of its own)"""
+    if int(rate) == int(want):
+        return mono
+    try:
+        import torchaudio  # type: ignore
+    except ImportError:
+        raise RuntimeError(f"{what} has a sample rate of {rate} Hz; the codec takes {want} Hz and resampling needs torchaudio, "
+                           f"which is not installed: resample the audio to {want} Hz first") from None
+    return torchaudio.functional.resample(torch.from_numpy(np.ascontiguousarray(mono))[None], int(rate), int(want))[0].numpy()
 
 
 def _save_wav_pcm16(path: str, audio: np.ndarray, sample_rate: int) -> None:

@@ -887,6 +887,37 @@ int dia_codec_conv(const dia_codec_conv_args* a, void* stream);
  * o + stride / 2 = m * stride + r, o < lens[b] * stride.  res must be NULL. */
 int dia_codec_convt(const dia_codec_conv_args* a, void* stream);
 
+/* Encode side (DESIGN.md "Codec: encode side"): waveform -> codes [B, 9, T].  Two more entry points and one more struct; the three
+ * above are unchanged.  The encoder's k-7 and 1x1 layers are dia_codec_conv; its two other forms are dia_codec_convs, over the same
+ * dia_codec_conv_args and the same rules for `lens`:
+ *   stride 2, 4 or 8 (k = 0 or 2 * stride, padding stride / 2): T and lens count INPUT positions, T % stride == 0, the output row
+ *     has lens[b] / stride positions;  w float [2][C_in * stride][Cp], w[t][ci * stride + r][co] = weight[co][ci][r + t * stride]:
+ *     y[b][co][o] = bias[co] + sum_{ci, r, t} w[t][ci * stride + r][co] * f(x[b][ci][(o + t) * stride + r - stride / 2])
+ *   stride 0, k = 3 (padding 1): w float [3][C_in][Cp] as for dia_codec_conv.
+ * dilation is 0 or 1, res must be NULL, tanh_out as above. */
+int dia_codec_convs(const dia_codec_conv_args* a, void* stream);
+
+#define DIA_CODEC_MAX_CODEBOOK_SIZE 4096
+typedef struct {
+  const float* z;              /* [B][latent_dim][ldz]: the encoder's latent */
+  const int32_t* lens;         /* device [B] or NULL: frames per row */
+  int32_t B, T;
+  int32_t n_codebooks, codebook_size, codebook_dim /* 1..32 */, latent_dim;
+  int32_t ldz, ld_codes;
+  const float* in_w;           /* [n_codebooks][codebook_dim][latent_dim]: in_proj, weight norm folded */
+  const float* in_b;           /* [n_codebooks][codebook_dim] */
+  const float* codebook;       /* [n_codebooks][codebook_size][codebook_dim]: rows L2-normalised (eps 1e-12) */
+  const float* codebook_sq;    /* [n_codebooks][codebook_size]: |normalised row|^2 */
+  const float* tables;         /* [n_codebooks][codebook_size][latent_dim]: as dia_codec_embed's */
+  const float* bias;           /* [n_codebooks][latent_dim]: out_proj bias PER codebook */
+  int32_t* codes;              /* [B][n_codebooks][ld_codes]; frames at or beyond lens[b] are not written */
+} dia_codec_quantize_args;
+/* the residual VQ search, all stages in one launch; per frame, residual = z[b][:][t], and for i in 0 .. n_codebooks - 1:
+ *   z_e = in_w[i] residual + in_b[i];  e = z_e / max(|z_e|, 1e-12);  codes[b][i][t] = argmin_j |e|^2 - 2 e . codebook[i][j] +
+ *   codebook_sq[i][j], the LOWEST j among equal distances;  residual -= tables[i][j] + bias[i].
+ * The residual stays on chip between the stages. */
+int dia_codec_quantize(const dia_codec_quantize_args* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
