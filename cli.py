@@ -11,6 +11,8 @@ output where neither codec is available; ``--no-dac`` skips loading the third-pa
 the native DAC decoder (dia_hip/codec.py) from a DAC checkpoint: ``--output`` then needs no ``dac`` package, also with ``--stream-chunk``.
 With a checkpoint that holds the encoder too, ``--audio-prompt voice.wav`` is encoded by the same native codec, and
 ``--encode-audio IN.wav --codes-output out.npy`` (build-only) writes the file's codes ``[T, 9]`` and exits; no model is loaded.
+A prompt file at any sample rate is converted to the codec's 44100 Hz by the native resampler, and ``--output-rate HZ`` (build-only)
+converts ``--output`` from 44100 Hz to HZ the same way.
 ``--score-codes FILE.npy`` (build-only) generates nothing: it prints the teacher-forced log-likelihood of the given codes under
 the loaded checkpoint (Dia.score) as one JSON line.
 """
@@ -60,6 +62,8 @@ def build_parser() -> argparse.ArgumentParser:
                    "codec and write its codes [T, 9] to --codes-output as .npy, then exit: needs --codec-path, loads no model, and the "
                    "text argument is ignored (44.1 kHz; another rate needs torchaudio)")
     g = p.add_argument_group("Audio Prompting (Voice Cloning)")
+    g.add_argument("--output-rate", type=int, default=None, metavar="HZ", help="(build-only) sample rate of --output: the waveform is converted "
+                   "from the codec's 44100 Hz on the device by the native codec's resampler (needs --codec-path); default: 44100 as it comes")
     g.add_argument("--audio-prompt", type=str, default=None, help="voice to clone: an audio file (encoded by the native codec of --codec-path when its checkpoint holds "
                    "the encoder, else by the dac package) or a .npy of codec codes [T, 9]")
     g.add_argument("--audio-prompt-text", type=str, default=None, help="what is said in --audio-prompt (mandatory with it)")
@@ -182,11 +186,13 @@ def stream_audio_to_file(dia, args, full_text: str) -> int:
     """--stream-chunk with --output (needs --codec-path): one utterance through Dia.stream_frames, every chunk decoded as it arrives
     by the native codec's streaming state; the file is written from the chunks' samples (and --codes-output from their codes)"""
     state = dia.codec.stream()
+    rate = dia.output_sample_rate or dia.codec.cfg.sample_rate
+    to_rate = dia.codec.resample_stream(dia.codec.cfg.sample_rate, rate)       # equal rates: chunks pass through
     samples, frames = [], []
     for _, start, codes, final in dia.stream_frames([full_text], 1, max_tokens=args.max_tokens, seeds=None if args.seed is None else [args.seed],
                                                     chunk=args.stream_chunk, adapters=used_adapters(args), cfg_scale=args.cfg_scale,
                                                     temperature=args.temperature, top_p=args.top_p, cfg_filter_top_k=args.cfg_filter_top_k):
-        y = state.push(codes, final)
+        y = to_rate.push(state.push(codes, final), final)
         frames.append(codes)
         samples.append(y)
         if args.verbose:
@@ -201,7 +207,7 @@ def stream_audio_to_file(dia, args, full_text: str) -> int:
         print(f"Codes saved to {args.codes_output}")
     Path(args.output).parent.mkdir(parents=True, exist_ok=True)
     print(f"Saving audio to {args.output}...")
-    dia.save_audio(args.output, audio)
+    dia.save_audio(args.output, audio, rate)
     print(f"Audio successfully saved to {args.output}")
     return 0
 
@@ -228,7 +234,7 @@ def encode_to_file(args) -> int:
         device = torch.device(args.device) if args.device else None
         codec = DeviceCodec(args.codec_path, device)
         mono, rate = read_audio_mono(args.encode_audio)
-        codes = codec.encode(resample_to(mono, rate, codec.cfg.sample_rate, args.encode_audio))[0].T.copy()
+        codes = codec.encode(resample_to(mono, rate, codec.cfg.sample_rate, args.encode_audio, codec))[0].T.copy()
         Path(args.codes_output).parent.mkdir(parents=True, exist_ok=True)
         np.save(args.codes_output, codes)
         print(f"Codes saved to {args.codes_output}: shape {tuple(codes.shape)}")
@@ -274,6 +280,8 @@ def main(argv=None) -> int:
     if args.stream_chunk < 0 or (args.stream_chunk and not stream_wav and (args.audio_prompt or not args.codes_output or args.output)):
         parser.error("--stream-chunk N needs N > 0, --codes-output, and neither --audio-prompt nor --output "
                      "(--output is allowed with --codec-path).")
+    if args.output_rate is not None and (args.output_rate < 1 or not args.codec_path or not args.output):
+        parser.error("--output-rate HZ needs HZ > 0, --output and --codec-path (the native codec converts the rate).")
     if args.no_dac and args.output and not args.codec_path:
         parser.error("--output needs the audio codec; use --codes-output with --no-dac.")
     if args.codec_path:
@@ -311,6 +319,7 @@ def main(argv=None) -> int:
             print("LoRA adapters merged successfully.")
         if args.codec_path:
             dia.load_codec(args.codec_path)
+            dia.output_sample_rate = args.output_rate
             print(f"Native codec loaded from {args.codec_path}")
         if bank_dirs:
             dia.load_adapters(bank_dirs)
@@ -379,7 +388,7 @@ def main(argv=None) -> int:
                 return 1
             Path(args.output).parent.mkdir(parents=True, exist_ok=True)
             print(f"Saving audio to {args.output}...")
-            dia.save_audio(args.output, audio)
+            dia.save_audio(args.output, audio, args.output_rate or 44100)
             print(f"Audio successfully saved to {args.output}")
         elif dia.last_codes is None:
             print("Generation failed to produce codes.")

@@ -28,6 +28,7 @@ EXPORTS = (
     "dia_lora_apply", "dia_lora_crosskv", "dia_engine_set_lora",
     "dia_kv_quantize_fp8", "dia_attn_cross_fp8", "dia_engine_set_cross_fp8",
     "dia_codec_embed", "dia_codec_conv", "dia_codec_convt", "dia_codec_convs", "dia_codec_quantize",
+    "dia_resample",
     "dia_seg_mlp", "dia_seg_workspace_bytes", "dia_seg_workspace_control_bytes", "dia_seg_slots", "dia_seg_supported", "dia_seg_error",
 )
 
@@ -235,6 +236,19 @@ class KvFp8Args(C.Structure):
     ]
 
 
+RESAMPLE_OPEN = -1                                        # DIA_RESAMPLE_OPEN
+
+
+class ResampleArgs(C.Structure):
+    """dia_resample_args: x / y / bank / first are device pointers, the five per-row arrays HOST arrays read during the call"""
+    _fields_ = [
+        ("x", C.c_void_p), ("y", C.c_void_p), ("bank", C.c_void_p), ("first", C.c_void_p),
+        ("B", C.c_int32), ("ldx", C.c_int32), ("ldy", C.c_int32), ("o", C.c_int32), ("n", C.c_int32), ("nt", C.c_int32),
+        ("in_start", C.POINTER(C.c_int64)), ("out_start", C.POINTER(C.c_int64)), ("total", C.POINTER(C.c_int64)),
+        ("in_count", C.POINTER(C.c_int32)), ("out_count", C.POINTER(C.c_int32)),
+    ]
+
+
 class DecLayer(C.Structure):
     _fields_ = [
         ("w_qkv", C.c_void_p), ("w_o", C.c_void_p), ("w_cq", C.c_void_p), ("w_co", C.c_void_p),
@@ -360,6 +374,7 @@ def lib() -> C.CDLL:
     L.dia_kv_quantize_fp8.argtypes = [C.POINTER(KvFp8Args), C.c_void_p]
     L.dia_attn_cross_fp8.argtypes = [C.POINTER(AttnArgs), C.POINTER(KvFp8Ptrs), C.c_void_p]
     L.dia_engine_set_cross_fp8.argtypes = [C.c_void_p, C.POINTER(KvFp8Ptrs)]
+    L.dia_resample.argtypes = [C.POINTER(ResampleArgs), C.c_void_p]
     L.dia_seg_mlp.argtypes = [C.POINTER(SegArgs), C.c_void_p]
     L.dia_seg_workspace_bytes.restype = C.c_int64
     L.dia_seg_workspace_control_bytes.restype = C.c_int64

@@ -620,6 +620,7 @@ class DeviceCodec:
         self.layer_events: Optional[list] = None                # scratch/codec_speed.py: set to [] to collect (label, start, stop) events per launch
         self.enc_layers: Optional[List[dict]] = None
         self.encoder_error: Optional[Exception] = None
+        self._resampler = None                                  # resample.DeviceResampler, made on first use
         if any(k.startswith("encoder.") for k in whole):
             try:
                 self._prepare_encoder(sd, whole, meta, int(workspace_bytes))
@@ -828,16 +829,21 @@ class DeviceCodec:
                     out.append((codes_h[r, :, :n].astype(np.int64), z_h[r, :, :n].copy()))
         return out
 
-    def encode_batch(self, rows: Sequence, window: Optional[int] = None, return_latents: bool = False):
+    def encode_batch(self, rows: Sequence, window: Optional[int] = None, return_latents: bool = False,
+                     sample_rates: Optional[Sequence[Optional[int]]] = None):
         """one mono float waveform [L_b] per utterance -> int64 codes [n_codebooks, ceil(L_b / hop)] per utterance (with
         return_latents: also the list of fp32 latents [latent, T_b] the codes were searched from).  Every row is padded with zeros
         on the right to a multiple of hop (DAC's preprocess) and comes out as when encoded alone; long rows run in windows of
-        `window` frames with encode_context_frames(cfg) frames of samples on each side."""
+        `window` frames with encode_context_frames(cfg) frames of samples on each side.  sample_rates: per row its rate in Hz
+        (None = the codec's); rows at another rate are resampled first, those of one rate in one launch (L_b then counts the
+        resampled samples)."""
         if self.enc_layers is None:
             raise self.encoder_error
         window = self.window if window is None else int(window)
         if not 1 <= window <= self.window:
             raise ValueError(f"window = {window} outside [1, {self.window}] (the workspace is sized by the codec's window)")
+        if sample_rates is not None and len(sample_rates) != len(rows):
+            raise ValueError("codec: one sample rate (or None) per row")
         hop, waves = self.cfg.hop, []
         for r in rows:
             w = np.asarray(r.detach().cpu() if isinstance(r, torch.Tensor) else r)
@@ -845,7 +851,12 @@ class DeviceCodec:
                 w = w[0]
             if w.ndim != 1 or w.dtype.kind != "f":
                 raise ValueError(f"codec: a waveform of shape {tuple(w.shape)} and dtype {w.dtype}, expected mono float samples [L]")
-            waves.append(preprocess(w, hop))
+            waves.append(w)
+        for rate in sorted({int(r) for r in sample_rates or () if r is not None and int(r) != self.cfg.sample_rate}):
+            at = [b for b, r in enumerate(sample_rates) if r is not None and int(r) == rate]
+            for b, y in zip(at, self.resample([waves[b] for b in at], rate, self.cfg.sample_rate)):
+                waves[b] = y
+        waves = [preprocess(w, hop) for w in waves]
         jobs, plan = [], []
         for b, w in enumerate(waves):
             for lo, f0, f1, hi in window_plan(w.shape[0] // hop, window, self.enc_ctx):
@@ -878,6 +889,23 @@ class DeviceCodec:
         for b, r in enumerate(rows):
             out[b, :, :r.shape[1]] = r
         return out
+
+    # -------------------------------------------------------------------------------------- sample rates
+    def _resample(self):
+        if self._resampler is None:
+            from .resample import DeviceResampler
+            self._resampler = DeviceResampler(self.device)
+        return self._resampler
+
+    def resample(self, waves, rate_in: int, rate_out: int):
+        """mono float samples [L], or a list of them (one launch), at rate_in -> float32 [ceil(L rate_out / rate_in)] at rate_out
+        (csrc/resample.hip, DESIGN.md "Resampler"); equal rates return the input"""
+        return self._resample().resample(waves, rate_in, rate_out)
+
+    def resample_stream(self, rate_in: int, rate_out: int):
+        """a resample.ResampleStream for one signal: push(chunk, final) -> the samples that have become final; joined they equal
+        resample() of the whole signal bit for bit"""
+        return self._resample().stream(rate_in, rate_out)
 
     def stream(self, window: Optional[int] = None) -> CodecStream:
         """a streaming state for one utterance on this codec"""

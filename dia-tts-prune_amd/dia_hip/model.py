@@ -81,6 +81,9 @@ class Dia:
     # scale per key and head, and its decode steps read that instead of the bf16 caches (DecodeSession cross_kv="fp8"; needs a
     # bf16 compute_dtype).  "bf16" = the caches as they are
     cross_kv = "bf16"
+    # HZ: generate(), generate_audio_batch() and stream_audio() return their samples at this rate, converted from the codec's
+    # 44.1 kHz by the native codec's resampler (DeviceCodec.resample / resample_stream); None = the codec's rate, as it comes
+    output_sample_rate: Optional[int] = None
 
     def __init__(self, config: DiaConfig, compute_dtype: Union[str, ComputeDtype] = ComputeDtype.FLOAT32,
                  device: Optional[torch.device] = None):
@@ -436,22 +439,38 @@ class Dia:
         """generate_batch (same arguments), then the native codec over all utterances at once: one float32 waveform
         [T'_b * 512] per utterance, each as when decoded alone.  Needs load_codec()."""
         codec = self._need_codec()
-        return codec.decode_batch(self.generate_batch(texts, *args, **kw))
+        waves = codec.decode_batch(self.generate_batch(texts, *args, **kw))
+        rate = self._output_rate(codec)
+        return codec.resample(waves, codec.cfg.sample_rate, rate) if rate else waves
+
+    def _output_rate(self, codec) -> Optional[int]:
+        """output_sample_rate where it asks for another rate than the codec's, else None; the conversion is the native codec's"""
+        rate = self.output_sample_rate
+        if rate is None or int(rate) == (DEFAULT_SAMPLE_RATE if codec is None else codec.cfg.sample_rate):
+            return None
+        if int(rate) < 1:
+            raise ValueError(f"output_sample_rate = {rate} is not a positive rate in Hz")
+        if codec is None or not hasattr(codec, "resample"):
+            raise RuntimeError(f"output_sample_rate = {rate} Hz needs the native codec's resampler: call Dia.load_codec(path_or_state) first")
+        return int(rate)
 
     @torch.inference_mode()
     def stream_audio(self, requests_or_texts: Sequence[Union[str, GenerationRequest]], slots: int = 8, **kw):
         """stream_frames (same arguments) with the native codec behind it: yields (request index, start sample, samples, final)
         while the utterances run.  The samples of a request, joined, equal codec.decode() of its whole code tensor; the last
         context_frames frames of a running utterance are held back until more arrive or it ends (DESIGN.md "Codec").  Needs
-        load_codec()."""
+        load_codec().  With output_sample_rate set the samples are at that rate and equal codec.resample() of the whole waveform."""
         codec = self._need_codec()
+        rate = self._output_rate(codec)
         states, starts = {}, {}
         for i, _, codes, final in self.stream_frames(requests_or_texts, slots, **kw):
             st = states.get(i)
             if st is None:
-                st = states[i] = codec.stream()
+                st = states[i] = (codec.stream(), codec.resample_stream(codec.cfg.sample_rate, rate) if rate else None)
                 starts[i] = 0
-            y = st.push(codes, final)
+            y = st[0].push(codes, final)
+            if st[1] is not None:                               # one resampling state per request: start offsets count output-rate samples
+                y = st[1].push(y, final)
             yield i, starts[i], y, final
             starts[i] += y.shape[0]
             if final:
@@ -535,10 +554,12 @@ class Dia:
             return None
 
     def _generate_output(self, codec_input: np.ndarray) -> Optional[np.ndarray]:
-        """codes [1, C, T'] -> waveform: through the native codec when load_codec() set one, else through the third-party codec
-        (model.py:535-544)."""
+        """codes [1, C, T'] -> waveform: through the native codec when load_codec() set one (at output_sample_rate when that is
+        set), else through the third-party codec (model.py:535-544)."""
+        rate = self._output_rate(self.codec)
         if self.codec is not None:
-            return self.codec.decode(codec_input)
+            wave = self.codec.decode(codec_input)
+            return self.codec.resample(wave, self.codec.cfg.sample_rate, rate) if rate else wave
         if self.dac_model is None:
             raise RuntimeError("DAC model not loaded. Cannot decode audio.")
         codes = torch.from_numpy(codec_input.astype(np.int64)).to(self.device)
@@ -555,20 +576,21 @@ class Dia:
     @torch.inference_mode()
     def encode_audio(self, wave, sample_rate: int = DEFAULT_SAMPLE_RATE) -> torch.Tensor:
         """mono float samples [L] (array or tensor) -> codec frames [T, C] (int64), through the native codec: zeros on the right up
-        to a multiple of 512 samples (DAC's preprocess), T = ceil(L / 512).  A rate other than the codec's is resampled by
-        torchaudio where that is importable and refused otherwise."""
+        to a multiple of 512 samples (DAC's preprocess), T = ceil(L / 512).  A rate other than the codec's is resampled by the
+        codec's own resampler (resample_to)."""
         codec = self._need_codec()
         w = np.asarray(wave.detach().cpu() if isinstance(wave, torch.Tensor) else wave, dtype=np.float32)
         if w.ndim == 2:
             w = w.mean(axis=0)
-        w = resample_to(w.reshape(-1), int(sample_rate), codec.cfg.sample_rate, "the waveform")
+        w = resample_to(w.reshape(-1), int(sample_rate), codec.cfg.sample_rate, "the waveform", codec)
         return torch.from_numpy(codec.encode(w)[0].T.copy())
 
     def load_audio(self, audio_path: str) -> torch.Tensor:
-        """waveform file -> codec frames [T, C] for ``generate(audio_prompt=...)`` (mono, 44.1 kHz)."""
+        """waveform file -> codec frames [T, C] for ``generate(audio_prompt=...)`` (mono; any sample rate with the native codec,
+        which resamples to its 44.1 kHz on the device)."""
         if self.codec is not None and self.codec.has_encoder:
             mono, rate = read_audio_mono(audio_path)
-            mono = resample_to(mono, rate, self.codec.cfg.sample_rate, audio_path)
+            mono = resample_to(mono, rate, self.codec.cfg.sample_rate, audio_path, self.codec)
             return self.encode_audio(mono, self.codec.cfg.sample_rate)
         codec = self.dac_model
         if codec is None:
@@ -649,11 +671,14 @@ def read_audio_mono(path: str) -> Tuple[np.ndarray, int]:
     return x.reshape(-1, ch).mean(axis=1).astype(np.float32), int(rate)
 
 
-def resample_to(mono: np.ndarray, rate: int, want: int, what: str) -> np.ndarray:
-    """`mono` at `want` Hz: unchanged at that rate, through torchaudio.functional.resample where torchaudio is importable, refused
-    by rate otherwise (this library has no resampler of its own)"""
+def resample_to(mono: np.ndarray, rate: int, want: int, what: str, codec=None) -> np.ndarray:
+    """`mono` at `want` Hz: unchanged at that rate; through `codec.resample` where the codec object offers one (DeviceCodec: the
+    library's own kernel, the same result with or without torchaudio installed); else through torchaudio.functional.resample
+    where torchaudio is importable, and refused by rate otherwise"""
     if int(rate) == int(want):
         return mono
+    if codec is not None and hasattr(codec, "resample"):
+        return codec.resample(np.ascontiguousarray(mono, dtype=np.float32), int(rate), int(want))
     try:
         import torchaudio  # type: ignore
     except ImportError:

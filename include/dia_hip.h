@@ -918,6 +918,42 @@ typedef struct {
  * The residual stays on chip between the stages. */
 int dia_codec_quantize(const dia_codec_quantize_args* a, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Resampler (csrc/resample.hip; DESIGN.md "Resampler"): polyphase sample-rate conversion of a batch of rows in ONE launch.  One
+ * new entry point and one new struct; nothing older changed.
+ *
+ * The rates are reduced to o : n (input : output samples per period).  Output m = q * n + p of a signal x of `total` samples is
+ *   y[m] = sum_{k = 0 .. nt - 1} bank[k][p] * x[q * o + first[p] + k],      x = 0 outside [0, total)
+ * an fp32 fma chain from 0 in ascending k: the order depends on (o, n, nt, first, bank) alone, never on the row, the tile or the
+ * window, so an output has the same bits however the signal is cut into rows, windows and launches.
+ *
+ * A row is a WINDOW of a longer signal: it holds input samples [in_start, in_start + in_count) at x[b][0 ..] and receives
+ * outputs [out_start, out_start + out_count) at y[b][0 ..].  Absolute indices are 64-bit and stay on the host: the kernel gets
+ * them reduced to (q, p) of the first output and a 32-bit offset.  A tap outside the window reads as ZERO (that is right outside
+ * [0, total); the caller sees to it that no tap inside the signal falls outside the window — dia_hip/resample.py checks before it
+ * launches); memory outside x[b][0 .. in_count) is never read, memory outside y[b][0 .. out_count) never written.
+ * ------------------------------------------------------------------------------------------------ */
+#define DIA_RESAMPLE_MAX_ROWS 64           /* rows of one launch */
+#define DIA_RESAMPLE_MAX_T (1 << 24)       /* ldx, ldy */
+#define DIA_RESAMPLE_MAX_TAPS 4096         /* nt */
+#define DIA_RESAMPLE_TILE 1024             /* consecutive outputs of one workgroup */
+#define DIA_RESAMPLE_MAX_TILE_FLOATS 16000 /* its staged input span, ceil((TILE - 1) * o / n) + 2 + nt floats of LDS: DIA_E_ARG above */
+#define DIA_RESAMPLE_OPEN (-1)             /* total[b] of a running stream: the signal has no end yet */
+typedef struct {
+  const float* x;              /* device [B][ldx] */
+  float* y;                    /* device [B][ldy]; never x */
+  const float* bank;           /* device [nt][n]: tap-major, the phase contiguous */
+  const int32_t* first;        /* device [n]: tap 0 of phase p sits at input q * o + first[p]; nondecreasing, first[n - 1] <= first[0] + o */
+  int32_t B, ldx, ldy;
+  int32_t o, n, nt;
+  const int64_t* in_start;     /* HOST [B], read during the call (as the four below): absolute index of x[b][0], >= 0 */
+  const int64_t* out_start;    /* HOST [B]: absolute index of y[b][0], >= 0 */
+  const int64_t* total;        /* HOST [B]: the signal's length, or DIA_RESAMPLE_OPEN */
+  const int32_t* in_count;     /* HOST [B]: 0 .. ldx */
+  const int32_t* out_count;    /* HOST [B]: 0 .. ldy */
+} dia_resample_args;
+int dia_resample(const dia_resample_args* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
