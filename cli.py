@@ -104,6 +104,9 @@ def build_parser() -> argparse.ArgumentParser:
     g.add_argument("--cross-kv", type=str, default="bf16", choices=["bf16", "fp8"],
                    help="(build-only) fp8: the decode step reads an e4m3 copy of the cross-attention K/V caches (one power-of-two scale per "
                         "key and head) instead of the bf16 caches; needs a bf16 --compute-dtype")
+    g.add_argument("--self-kv", type=str, default="bf16", choices=["bf16", "fp8"],
+                   help="(build-only) fp8: the self-attention K/V caches are kept as e4m3 (one power-of-two scale per key and head, the new "
+                        "key quantised as it is appended) instead of bf16: 0.516 of the bytes; needs a bf16 --compute-dtype")
     g.add_argument("--verbose", action="store_true", help="report prefill and generation timing")
     return p
 
@@ -297,6 +300,7 @@ def main(argv=None) -> int:
     Dia.sparse_weights = args.sparse_weights
     Dia.weight_format = args.weight_format
     Dia.cross_kv = args.cross_kv
+    Dia.self_kv = args.self_kv
     if args.seed is not None:
         set_seed(args.seed)
         print(f"Using seed: {args.seed}")

@@ -910,6 +910,252 @@ __global__ __launch_bounds__(256) void k_kv_quantize_fp8(KvQuantK p) {
 }
 
 // ---------------------------------------------------------------------------------------------------
+// FP8 self K/V (dia_hip.h "FP8 self K/V"): k_attn_mfma<G, 1> for DIA_ATTN_SELF over e4m3 self caches — there is no bf16 cache beside
+// them.  Fragments, scale loads and the fold-in behind the MFMAs are k_attn_mfma_f8's; key -> workgroup -> wave assignment, gpw rule,
+// two-granule prefetch, online softmax, slab merge and output are k_attn_mfma's.  New is the owner wave's append: RoPE(k) in fp32,
+// amax of K and of V over the key's 128 dims (two per lane, wave reduction of the |fp32| bit patterns), scale by quantize_kv_fp8's
+// rule, e4m3_rne, then 2 x 64 byte stores into the K row, 2 x 64 at stride 32 into the blocked V granule and the two scales.  The
+// owner's fragments of granule slot >> 5 were requested before the append and hold stale bytes AND stale scales for the slot: the
+// new key's 256 bytes and two scales stay in LDS and consume() patches kb, one byte per vb[nb], and ksc / vsc of the lane that holds
+// the key.  The caches are allocated zeroed and every byte the encoder writes is finite (|x| / scale <= 448, and the byte is clamped
+// to 0x7E for a non-finite input), so a masked key — not yet written, or left over in a re-used slot — contributes 0 x finite.
+struct AttnF8W { uint8_t* k8; uint8_t* v8; float* ks; float* vs; };
+
+// kv_scale_bits for an fp32 amax bit pattern: 448 = 1.75 * 2^8, so e = exponent - 8, one more when the significand is above 1.75
+__device__ __forceinline__ unsigned kv_scale_bits_f32(unsigned amax) {
+  if (amax == 0) return 0x3f800000u;
+  const int se = (int)(amax >> 23) - 8 + ((amax & 0x7fffffu) > 0x600000u ? 1 : 0);
+  return (unsigned)min(max(se, 1), 254) << 23;
+}
+__device__ __forceinline__ unsigned e4m3_finite(float x) {      // e4m3_rne, a non-finite or oversized input held to +-448
+  const unsigned b = e4m3_rne(x);
+  return (b & 0x80u) | min(b & 0x7fu, 0x7eu);
+}
+__device__ __forceinline__ unsigned wave_umax(unsigned v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = max(v, (unsigned)__shfl_xor((int)v, o, 64));
+  return v;
+}
+
+template <int G>
+__global__ __launch_bounds__(NT, 2) void k_attn_self_f8(AttnK p, AttnF8W f8) {
+  __shared__ __attribute__((aligned(16))) bf16_raw qf[4][DIA_NPLANES][G][4][8];   // q planes in A-fragment order
+  __shared__ float part[NWV * G * HD];
+  __shared__ float pm_s[NWV * 8], pl_s[NWV * 8];
+  __shared__ __attribute__((aligned(16))) bf16_raw pbuf[NWV][2][16][32];
+  __shared__ __attribute__((aligned(8))) uint8_t knew_s[HD], vnew_s[HD];          // the appended key: e4m3 bytes ...
+  __shared__ float scnew_s[2];                                                    // ... and its K and V scale
+  __shared__ int last_s;
+
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int kvh = blockIdx.x, chunk = blockIdx.z;
+  const int arow = lane & 15, akq = lane >> 4;
+  ASTAMP(0);
+  const int by = blockIdx.y;
+  const int qrow = by;
+  // ---- loads that do not need cur[]: this wave's q head (waves >= G re-read head G-1, branch-free), the new k / v of the kv head
+  const float* qr = p.q + (long)qrow * p.ldq;
+  const float* qh = qr + p.q_off + (kvh * G + min(w, G - 1)) * HD;
+  const float* kh = qr + p.k_off + kvh * HD;
+  const float* vh = qr + p.v_off + kvh * HD;
+  const float qx1 = qh[lane], qx2 = qh[lane + 64];
+  const float kx1 = kh[lane], kx2 = kh[lane + 64];
+  const float vx1 = vh[lane], vx2 = vh[lane + 64];
+
+  const int c_cur = min(p.cur[by >> 1], p.kv_cap);        // (a step beyond the capacity appends nothing outside the row)
+  const int kvrow = by, pos = c_cur;
+  const int nkeys = c_cur;
+  const int slot = c_cur - 1;
+  const int head_row = by;
+  const int NZ = gridDim.z;
+  const int ngran = (nkeys + 31) >> 5;
+  const int gpw = (ngran <= 2 * NWV) ? max(p.gpw, 2) : p.gpw;
+  const int nchunks = min(NZ, max(1, (ngran + NWV * gpw - 1) / (NWV * gpw)));   // workgroups that take keys
+  if (chunk >= nchunks) return;
+  ASTAMP(1);
+  // (a kv head whose query heads are all pruned still appends: no early exit on head_map)
+  const float rc = p.cos_t[(long)pos * 64 + lane], rs = p.sin_t[(long)pos * 64 + lane];
+
+  const long pair_keys = ((long)kvrow * p.n_kv_heads + kvh) * p.kv_cap;
+  uint8_t* K8 = f8.k8 + pair_keys * HD;
+  uint8_t* V8 = f8.v8 + pair_keys * HD;
+  float* KS = f8.ks + pair_keys;
+  float* VS = f8.vs + pair_keys;
+  const int klast = max(nkeys - 1, 0);
+  const int gstride = NWV * nchunks;
+  const int g_first = chunk * NWV + w;
+  auto load_gran = [&](F8Frag& f, int gi) {
+    const int key0 = gi << 5;
+    // K and its scales first (S = Q.K^T runs before P.V, and vmcnt retires in order), then V and its scales.  gi < kv_cap / 32: the
+    // 32 scales of a granule are inside the row, finite (zero until written); K rows are clamped like the bf16 kernel's
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks)
+        f.kb[t][ks] = KVLOAD(reinterpret_cast<const uint2*>(K8 + (long)min(key0 + 16 * t + arow, klast) * HD + 32 * ks + 8 * akq));
+#pragma unroll
+    for (int t = 0; t < 2; ++t) f.ksc[t] = KVLOAD(KS + key0 + 16 * t + arow);
+    const uint8_t* Vblk = V8 + (long)gi * HD * 32;
+#pragma unroll
+    for (int nb = 0; nb < 8; ++nb) f.vb[nb] = KVLOAD(reinterpret_cast<const uint2*>(Vblk + (long)(16 * nb + arow) * 32 + 8 * akq));
+#pragma unroll
+    for (int t = 0; t < 2; ++t) f.vsc[t] = KVLOAD(VS + key0 + 16 * t + arow);
+  };
+  F8Frag fa, fb;
+  const bool have0 = g_first < ngran;
+  load_gran(fa, have0 ? g_first : 0);          // idle waves re-read granule 0 (cache hit) and never use it
+
+  // ---- RoPE(q) -> LDS, each value one rounded product inside one fused multiply-add: the products k_attn_mfma<4, 1> rounds
+  if (w < G) {
+    const float qv[2] = {__builtin_fmaf(qx1, rc, -mul_rn(qx2, rs)), __builtin_fmaf(qx2, rc, mul_rn(qx1, rs))};
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+      const int D = lane + 64 * e;
+      __bf16 a, b, c;
+      split3(qv[e], a, b, c);
+      qf[D >> 5][0][w][(D >> 3) & 3][D & 7] = *reinterpret_cast<const bf16_raw*>(&a);
+      qf[D >> 5][1][w][(D >> 3) & 3][D & 7] = *reinterpret_cast<const bf16_raw*>(&b);
+      qf[D >> 5][2][w][(D >> 3) & 3][D & 7] = *reinterpret_cast<const bf16_raw*>(&c);
+    }
+  }
+  // ---- the wave that owns the new slot's granule ropes k, quantises k and v (lane: dims lane and lane + 64 of each), appends them
+  //      and keeps the bytes and the scales in LDS for its own fragments
+  const int gslot = slot >> 5;
+  const bool owner = slot >= 0 && (gslot % gstride) == g_first;      // wave-uniform
+  if (owner) {
+    const float k1 = __builtin_fmaf(kx1, rc, -mul_rn(kx2, rs)), k2 = __builtin_fmaf(kx2, rc, mul_rn(kx1, rs));
+    const unsigned ksb = kv_scale_bits_f32(wave_umax(max(__float_as_uint(k1) & 0x7fffffffu, __float_as_uint(k2) & 0x7fffffffu)));
+    const unsigned vsb = kv_scale_bits_f32(wave_umax(max(__float_as_uint(vx1) & 0x7fffffffu, __float_as_uint(vx2) & 0x7fffffffu)));
+    const float kinv = __uint_as_float((254u << 23) - ksb), vinv = __uint_as_float((254u << 23) - vsb);      // 1 / scale, exact
+    const uint8_t kb1 = (uint8_t)e4m3_finite(k1 * kinv), kb2 = (uint8_t)e4m3_finite(k2 * kinv);
+    const uint8_t vb1 = (uint8_t)e4m3_finite(vx1 * vinv), vb2 = (uint8_t)e4m3_finite(vx2 * vinv);
+    knew_s[lane] = kb1; knew_s[lane + 64] = kb2; vnew_s[lane] = vb1; vnew_s[lane + 64] = vb2;
+    K8[(long)slot * HD + lane] = kb1; K8[(long)slot * HD + lane + 64] = kb2;
+    uint8_t* vdst = V8 + (long)gslot * HD * 32 + (slot & 31);
+    vdst[(long)lane * 32] = vb1; vdst[(long)(lane + 64) * 32] = vb2;
+    if (lane == 0) {
+      scnew_s[0] = __uint_as_float(ksb); scnew_s[1] = __uint_as_float(vsb);
+      KS[slot] = __uint_as_float(ksb); VS[slot] = __uint_as_float(vsb);
+    }
+  }
+  lds_barrier();     // q (and the owner's copy of the new key) in LDS; global loads stay in flight
+  ASTAMP(2);
+
+  // q fragments are re-read from LDS per k-step (rows >= G alias row G-1: their score rows are unused)
+  const int qrow_l = min(arow, G - 1);
+  const float scale = 0.08838834764831845f;
+  f32x4 O[8];
+#pragma unroll
+  for (int nb = 0; nb < 8; ++nb) O[nb] = f32x4{0.f, 0.f, 0.f, 0.f};
+  float mrun[4], lrun[4];
+#pragma unroll
+  for (int g = 0; g < 4; ++g) { mrun[g] = -INFINITY; lrun[g] = 0.f; }
+
+  auto consume = [&](F8Frag& f, int gi) {
+    const int key0 = gi << 5;
+    if (owner && gi == gslot) {                 // the slot written this step: bytes and scales from the LDS copy
+      const int ts = (slot >> 4) & 1, ns = slot & 15, js = slot & 7, kqs = (slot & 31) >> 3;
+      const bool klane = arow == ns;            // this lane holds the key's K row (tile ts), its score and its scales
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks) {
+        const uint2 kn = *reinterpret_cast<const uint2*>(&knew_s[32 * ks + 8 * akq]);
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+          if (t == ts && klane) f.kb[t][ks] = kn;
+      }
+      const int sh = 8 * (js & 3);
+#pragma unroll
+      for (int nb = 0; nb < 8; ++nb) {          // byte js of the 8 keys 8 * kqs .. of dim 16 nb + arow
+        const unsigned vn = vnew_s[16 * nb + arow];
+        if (akq == kqs) {
+          if (js < 4) f.vb[nb].x = (f.vb[nb].x & ~(0xffu << sh)) | (vn << sh);
+          else f.vb[nb].y = (f.vb[nb].y & ~(0xffu << sh)) | (vn << sh);
+        }
+      }
+      const float ksn = scnew_s[0], vsn = scnew_s[1];
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+        if (t == ts && klane) { f.ksc[t] = ksn; f.vsc[t] = vsn; }
+    }
+    f32x4 S[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) {
+      const bf16x8 kx[2] = {expand_e4m3(f.kb[0][ks]), expand_e4m3(f.kb[1][ks])};
+#pragma unroll
+      for (int pl = 0; pl < DIA_NPLANES; ++pl) {
+        const bf16x8 qa = *reinterpret_cast<const bf16x8*>(&qf[ks][pl][qrow_l][akq][0]);
+#pragma unroll
+        for (int t = 0; t < 2; ++t) S[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qa, kx[t], S[t], 0, 0, 0);
+      }
+    }
+    // online softmax: in lanes 0..15, S[t][g] is the score of head g against key key0 + 16t + lane, in units of the key's K scale
+    float alpha[4];
+    const bool v0 = key0 + arow < nkeys, v1 = key0 + 16 + arow < nkeys;
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+      const float s0 = v0 ? mul_rn(mul_rn(S[0][g], f.ksc[0]), scale) : -INFINITY, s1 = v1 ? mul_rn(mul_rn(S[1][g], f.ksc[1]), scale) : -INFINITY;
+      const float mnew = fmaxf(mrun[g], row16_max(fmaxf(s0, s1)));
+      alpha[g] = (mrun[g] == -INFINITY) ? 0.f : __expf(mrun[g] - mnew);
+      const float p0 = (s0 == -INFINITY) ? 0.f : __expf(s0 - mnew), p1 = (s1 == -INFINITY) ? 0.f : __expf(s1 - mnew);
+      lrun[g] = __builtin_fmaf(lrun[g], alpha[g], row16_sum(p0 + p1));      // (the sum takes the unscaled p; fused as in k_attn_mfma)
+      mrun[g] = mnew;
+      if (lane < 16) {      // p * vs -> LDS as hi + lo bf16, [plane][head][key]
+        const float pv0 = mul_rn(p0, f.vsc[0]), pv1 = mul_rn(p1, f.vsc[1]);
+        const __bf16 h0 = (__bf16)pv0, h1 = (__bf16)pv1;
+        const __bf16 l0 = (__bf16)(pv0 - (float)h0), l1 = (__bf16)(pv1 - (float)h1);
+        pbuf[w][0][g][lane] = *reinterpret_cast<const bf16_raw*>(&h0);
+        pbuf[w][0][g][16 + lane] = *reinterpret_cast<const bf16_raw*>(&h1);
+        pbuf[w][1][g][lane] = *reinterpret_cast<const bf16_raw*>(&l0);
+        pbuf[w][1][g][16 + lane] = *reinterpret_cast<const bf16_raw*>(&l1);
+      }
+    }
+    __builtin_amdgcn_wave_barrier();
+    // rescale what is accumulated (register r of lanes 0..15 = head r)
+#pragma unroll
+    for (int nb = 0; nb < 8; ++nb)
+#pragma unroll
+      for (int g = 0; g < G; ++g) O[nb][g] *= alpha[g];
+    const bf16x8 pa0 = *reinterpret_cast<const bf16x8*>(&pbuf[w][0][arow][8 * akq]);
+    const bf16x8 pa1 = *reinterpret_cast<const bf16x8*>(&pbuf[w][1][arow][8 * akq]);
+#pragma unroll
+    for (int nb = 0; nb < 8; ++nb) {
+      const bf16x8 vx = expand_e4m3(f.vb[nb]);
+      O[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pa0, vx, O[nb], 0, 0, 0);
+      O[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pa1, vx, O[nb], 0, 0, 0);
+    }
+    __builtin_amdgcn_wave_barrier();     // pbuf is rewritten by the next granule
+  };
+
+  // k_attn_mfma's trip: steady state without a branch around a prefetch, then a tail of at most two granules
+  int gi = g_first;
+  for (; gi + 2 * gstride < ngran; gi += 2 * gstride) {
+    load_gran(fb, gi + gstride);
+    consume(fa, gi);
+    load_gran(fa, gi + 2 * gstride);
+    consume(fb, gi + gstride);
+  }
+  if (gi < ngran) {                // fa holds granule gi
+    const int g1 = gi + gstride;
+    if (g1 < ngran) load_gran(fb, g1);
+    consume(fa, gi);
+    if (g1 < ngran) consume(fb, g1);
+  }
+  ASTAMP(3);
+  // per-wave partial -> LDS (lanes 0..15: dim 16*nb + lane, register g = head)
+  if (lane < 16) {
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+#pragma unroll
+      for (int nb = 0; nb < 8; ++nb) part[(w * G + g) * HD + 16 * nb + lane] = O[nb][g];
+      if (lane == 0) { pm_s[w * 8 + g] = mrun[g]; pl_s[w * 8 + g] = lrun[g]; }
+    }
+  }
+  __syncthreads();
+  ASTAMP(4);
+  attn_finish<G>(p, part, pm_s, pl_s, &last_s, tid, qrow, kvh, head_row, chunk, nchunks);
+}
+
+// ---------------------------------------------------------------------------------------------------
 // Encoder self-attention for the packed prefill batch (layers.py:385-462: bidirectional over the L non-pad
 // positions of each utterance, RoPE positions = byte indices).  Two launches per layer for ALL utterances:
 //   k_enc_kv_planes   K = RoPE(k) and V of every packed row as three bf16 planes each (hi+mid+lo == fp32
@@ -1283,6 +1529,48 @@ extern "C" int dia_attn_cross_fp8(const dia_attn_args* a, const dia_kv_fp8_ptrs*
   const AttnF8 f8 = {(const uint8_t*)f->k8, (const uint8_t*)f->v8, f->ks, f->vs};
   dia_launch<k_attn_mfma_f8>(dim3(a->n_kv_heads, a->n_rows, max_chunks), dim3(NT), 0, (hipStream_t)stream, k, f8);
   return dia_check_launch("k_attn_mfma_f8");
+}
+
+extern "C" int dia_attn_self_fp8(const dia_attn_args* a, const dia_kv_fp8_ptrs* f, void* stream) {
+  if (!a || !f) return dia_fail(DIA_E_ARG, "dia_attn_self_fp8: null argument");
+  if (!a->q || !a->P || !a->cos_t || !a->sin_t || !f->k8 || !f->v8 || !f->ks || !f->vs)      // (kc / vc: there is no bf16 cache, NULL is fine)
+    return dia_fail(DIA_E_ARG, "dia_attn_self_fp8: null argument");
+  if (a->mode != DIA_ATTN_SELF) return dia_fail(DIA_E_ARG, "dia_attn_self_fp8: mode must be DIA_ATTN_SELF");
+  if (a->kv_dtype != DIA_KV_BF16) return dia_fail(DIA_E_ARG, "dia_attn_self_fp8: kv_dtype must be DIA_KV_BF16 (one plane)");
+  if (!a->v_blocked) return dia_fail(DIA_E_ARG, "dia_attn_self_fp8: the blocked V layout (v_blocked) is required");
+  if (a->kv_cap <= 0 || a->kv_cap % 32 != 0) return dia_fail(DIA_E_ARG, "dia_attn_self_fp8: kv_cap must be a positive multiple of 32");
+  if (a->n_rows <= 0 || a->n_kv_heads <= 0) return dia_fail(DIA_E_ARG, "dia_attn_self_fp8: empty problem");
+  if (a->p_plane_stride % 8 != 0) return dia_fail(DIA_E_ARG, "dia_attn_self_fp8: plane stride must be a multiple of 8");
+  if (!a->cur) return dia_fail(DIA_E_ARG, "dia_attn_self_fp8: SELF needs cur");
+  if (a->group != 1 && a->group != 2 && a->group != 4) return dia_fail(DIA_E_ARG, "dia_attn_self_fp8: GQA group must be 1, 2 or 4");
+  if (a->rope_rows > 0 && a->kv_cap + 1 > a->rope_rows) return dia_fail(DIA_E_ARG, "dia_attn_self_fp8: RoPE tables shorter than the positions this launch can reach");
+  if ((a->n_kv_heads * a->group * 128 + 31) / 32 > a->p_ktiles) return dia_fail(DIA_E_ARG, "dia_attn_self_fp8: output planes too narrow");
+  if (((uintptr_t)f->k8 & 7) || ((uintptr_t)f->v8 & 7) || ((uintptr_t)f->ks & 3) || ((uintptr_t)f->vs & 3))
+    return dia_fail(DIA_E_ARG, "dia_attn_self_fp8: k8 / v8 must be 8-byte aligned, ks / vs 4-byte");
+  // the key split of dia_attn, so that the slabs merge in the same order
+  const int cap_chunks = (a->kv_cap + CHUNK - 1) / CHUNK;
+  int max_chunks = (512 + a->n_rows * a->n_kv_heads - 1) / (a->n_rows * a->n_kv_heads);
+  if (dia_tune(DIA_TUNE_ATTN_NZ) > 0) max_chunks = dia_tune(DIA_TUNE_ATTN_NZ);
+  if (max_chunks > cap_chunks) max_chunks = cap_chunks;
+  if (max_chunks < 1) max_chunks = 1;
+  if (max_chunks > 1 && (!a->scratch || !a->tickets)) return dia_fail(DIA_E_ARG, "dia_attn_self_fp8: more than 128 keys possible: scratch and tickets are required");
+  AttnK k = {};
+  k.mode = a->mode; k.n_kv_heads = a->n_kv_heads; k.n_rows = a->n_rows; k.kv_cap = a->kv_cap;
+  k.q = a->q; k.ldq = a->ldq; k.q_off = a->q_off; k.k_off = a->k_off; k.v_off = a->v_off;
+  k.cur = a->cur; k.len = a->cur;
+  k.cos_t = a->cos_t; k.sin_t = a->sin_t;
+  k.P = (bf16_raw*)a->P; k.p_plane_stride = a->p_plane_stride; k.p_ktiles = a->p_ktiles; k.act_f32 = a->act_f32;
+  k.head_map = a->head_map; k.v_blocked = 1;
+  k.gpw = 1;
+  { const int g = dia_tune(DIA_TUNE_ATTN_GPW); if (g > 0) k.gpw = g; }
+  k.scratch = a->scratch; k.tickets = a->tickets; k.max_chunks = cap_chunks;
+  const AttnF8W f8 = {(uint8_t*)f->k8, (uint8_t*)f->v8, f->ks, f->vs};
+  const dim3 grid(a->n_kv_heads, a->n_rows, max_chunks);
+  hipStream_t st = (hipStream_t)stream;
+  if (a->group == 4) dia_launch<k_attn_self_f8<4>>(grid, dim3(NT), 0, st, k, f8);
+  else if (a->group == 2) dia_launch<k_attn_self_f8<2>>(grid, dim3(NT), 0, st, k, f8);
+  else dia_launch<k_attn_self_f8<1>>(grid, dim3(NT), 0, st, k, f8);
+  return dia_check_launch("k_attn_self_f8");
 }
 
 extern "C" int dia_kv_quantize_fp8(const dia_kv_fp8_args* a, void* stream) {

@@ -34,6 +34,7 @@ struct dia_engine {
   const int32_t* lora_slot = nullptr;   // ... and the device array adapter_of_slot [B]
   int lora_adapters = 0;
   std::vector<dia_kv_fp8_ptrs> f8kv;    // dia_engine_set_cross_fp8: the e4m3 copy of every layer's cross caches (empty: the bf16 caches)
+  std::vector<dia_kv_fp8_ptrs> f8self;  // dia_engine_set_self_fp8: the e4m3 self caches of every layer (empty: the bf16 caches k_self / v_self)
   std::vector<hipEvent_t> prof;   // when non-empty: one event recorded after every launch (profile step)
   // weight prefetch beside the chain (graph mode): launch i+lookahead's weights are pulled into the
   // Infinity Cache by a side stream as soon as launch i has been issued
@@ -343,7 +344,9 @@ static int enqueue_step(dia_engine* e, bool with_sampler) {
         a.q = d.qc; a.ldq = d.cq_heads * 128; a.len = d.text_len;
         a.kc = L.k_cross; a.vc = L.v_cross; a.head_map = L.hmap_cross; a.kv_plane_stride = d.kv_plane_cross;
       }
-      rc = (what == ATTN_CROSS && !e->f8kv.empty()) ? dia_attn_cross_fp8(&a, &e->f8kv[l], st) : dia_attn(&a, st);
+      if (what == ATTN_CROSS && !e->f8kv.empty()) rc = dia_attn_cross_fp8(&a, &e->f8kv[l], st);
+      else if (what == ATTN_SELF && !e->f8self.empty()) rc = dia_attn_self_fp8(&a, &e->f8self[l], st);
+      else rc = dia_attn(&a, st);
     } else if (what == SEG_MLP) {
       dia_seg_args sa = {};
       sa.a_in = (const float*)d.planes_a; sa.a_ktiles = akt; sa.M = R; sa.W = e->seg_w[l];
@@ -698,5 +701,18 @@ extern "C" int dia_engine_set_prefetch(dia_engine* e, int lookahead) {
   if (!e || lookahead < 0) return dia_fail(DIA_E_ARG, "dia_engine_set_prefetch: bad argument");
   if (e->exec) return dia_fail(DIA_E_STATE, "dia_engine_set_prefetch: the step graph is already captured");
   e->pf_lookahead = lookahead;
+  return DIA_OK;
+}
+
+extern "C" int dia_engine_set_self_fp8(dia_engine* e, const dia_kv_fp8_ptrs* layers) {
+  if (!e) return dia_fail(DIA_E_ARG, "dia_engine_set_self_fp8: null engine");
+  if (e->exec || e->launches > 0) return dia_fail(DIA_E_STATE, "dia_engine_set_self_fp8: a step has already been issued or captured");
+  if (!layers) { e->f8self.clear(); return DIA_OK; }
+  const dia_engine_desc& d = e->d;
+  if (d.kv_dtype != DIA_KV_BF16 || !d.v_blocked || d.T <= 0 || d.T % 32 != 0)
+    return dia_fail(DIA_E_ARG, "dia_engine_set_self_fp8: the engine needs bf16 K/V (DIA_KV_BF16) with the blocked V layout and T % 32 == 0");
+  for (int l = 0; l < d.n_layer; ++l)
+    if (!layers[l].k8 || !layers[l].v8 || !layers[l].ks || !layers[l].vs) return dia_fail(DIA_E_ARG, "dia_engine_set_self_fp8: null buffer in a layer");
+  e->f8self.assign(layers, layers + d.n_layer);
   return DIA_OK;
 }

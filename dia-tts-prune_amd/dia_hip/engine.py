@@ -504,7 +504,7 @@ class DecodeSession:
                  s_cap: Optional[int] = None, audio_prompts: Optional[Sequence[Optional[np.ndarray]]] = None,
                  prompt_prefill: str = "auto", attention: str = "auto", score: bool = False,
                  adapters=None, adapter_ids: Optional[Sequence[Union[None, str, int]]] = None, cross_kv: str = "bf16",
-                 _slotted: bool = False):
+                 self_kv: str = "bf16", _slotted: bool = False):
         """audio_prompts: per utterance None or int codes [Tp, C] (reference model.py:311-353).  The prompt
         rows are replayed through the decode step before sampling starts (semantics: oracle.generate), or — with
         bf16 caches — prefilled as one packed MFMA batch; prompt_prefill="replay" forces the replay.
@@ -516,7 +516,11 @@ class DecodeSession:
         replays audio prompts through the decode step (no batched prompt prefill), and refuses a compacted model and seg="on".
         cross_kv="fp8": the decode step's cross-attention reads an e4m3 copy of the cross caches with one power-of-two scale per key
         and head (DESIGN.md "FP8 cross K/V"), quantised from the bf16 caches behind every encoder pass; needs bf16 K/V with the
-        blocked V layout.  "bf16" (default): nothing of it exists."""
+        blocked V layout.  "bf16" (default): nothing of it exists.
+        self_kv="fp8": the SELF caches are e4m3 bytes with one power-of-two scale per key and head (DESIGN.md "FP8 self K/V"): the step's
+        self-attention quantises the new key as it appends it, k_self / v_self are not allocated (self_cache_bytes is 0.516 of the
+        bf16 session's) and audio prompts replay through the decode step.  Needs bf16 K/V with the blocked V layout and
+        audio_length % 32 == 0; independent of cross_kv.  "bf16" (default): nothing of it exists."""
         if adapter_ids is not None and adapters is None:
             raise ValueError("adapter_ids needs adapters= (an AdapterBank)")
         if score and (teacher_tokens is None or _slotted):
@@ -525,6 +529,8 @@ class DecodeSession:
             raise ValueError("prompt_prefill must be 'auto' or 'replay', attention 'auto' or 'valu'")
         if cross_kv not in ("bf16", "fp8"):
             raise ValueError("cross_kv must be 'bf16' or 'fp8'")
+        if self_kv not in ("bf16", "fp8"):
+            raise ValueError("self_kv must be 'bf16' or 'fp8'")
         self.prompt_prefill = prompt_prefill
         cfg, dev = w.cfg, w.device
         self.w, self.cfg, self.dev = w, cfg, dev
@@ -551,6 +557,14 @@ class DecodeSession:
             if attention == "valu" or not self.v_blocked:
                 raise ValueError("cross_kv='fp8' needs the blocked V layout of the MFMA attention kernel (attention='valu' keeps V row-major)")
         self.cross_kv = cross_kv
+        if self_kv == "fp8":
+            if self.kv_code != hb.KV_BF16:
+                raise ValueError(f"self_kv='fp8' replaces one-plane bf16 self caches: kv_dtype '{kv_dtype}' (fp32 or two-plane K/V) is not served")
+            if attention == "valu" or not self.v_blocked:
+                raise ValueError("self_kv='fp8' needs the blocked V layout of the MFMA attention kernel (attention='valu' keeps V row-major)")
+            if self.T % 32 != 0:
+                raise ValueError(f"self_kv='fp8' needs audio_length % 32 == 0 (whole 32-key granules), not {self.T}")
+        self.self_kv = self_kv
         kvt = torch.float32 if self.kv_code == hb.KV_F32 else torch.bfloat16
         self.kv_planes = 2 if self.kv_code == hb.KV_BF16X2 else 1
         self.stream = stream if stream is not None else torch.cuda.Stream(device=dev)
@@ -593,8 +607,18 @@ class DecodeSession:
         self.ld_logits = w.logits.ns * 16
         self.logits = z(self.rows_pad, self.ld_logits)
         pl = (self.kv_planes,) if self.kv_planes > 1 else ()           # two-plane caches: [plane][...]
-        self.k_self = [z(*pl, self.R, d.kv_heads, self.T, HEAD_DIM, dt=kvt) for _ in range(d.n_layer)]
-        self.v_self = [z(*pl, self.R, d.kv_heads, self.T, HEAD_DIM, dt=kvt) for _ in range(d.n_layer)]
+        # self_kv="fp8": the self caches ARE four e4m3 buffers (all layers in one allocation each), no bf16 cache beside them.  Zeroed
+        # once: a key that was never written, or is left over in a re-used slot, is finite bytes times a finite scale
+        self.k8_self_all = self.v8_self_all = self.ks_self_all = self.vs_self_all = None
+        if self_kv == "fp8":
+            self.k_self = self.v_self = [None] * d.n_layer
+            self.k8_self_all = z(d.n_layer, self.R, d.kv_heads, self.T, HEAD_DIM, dt=torch.uint8)
+            self.v8_self_all = z(d.n_layer, self.R, d.kv_heads, self.T // 32, HEAD_DIM, 32, dt=torch.uint8)
+            self.ks_self_all = z(d.n_layer, self.R, d.kv_heads, self.T)
+            self.vs_self_all = z(d.n_layer, self.R, d.kv_heads, self.T)
+        else:
+            self.k_self = [z(*pl, self.R, d.kv_heads, self.T, HEAD_DIM, dt=kvt) for _ in range(d.n_layer)]
+            self.v_self = [z(*pl, self.R, d.kv_heads, self.T, HEAD_DIM, dt=kvt) for _ in range(d.n_layer)]
         # cross caches of all layers in ONE allocation each (per-layer views): the prefill's merged cross-K/V launch addresses a layer
         # as kc + layer * kv_layer_stride
         self.k_cross_all = z(d.n_layer, *pl, B, d.cross_query_heads, self.S, HEAD_DIM, dt=kvt)
@@ -833,6 +857,12 @@ class DecodeSession:
                 f8[i].k8, f8[i].v8 = hb.ptr(self.k8_cross_all[i]), hb.ptr(self.v8_cross_all[i])
                 f8[i].ks, f8[i].vs = hb.ptr(self.ks_cross_all[i]), hb.ptr(self.vs_cross_all[i])
             hb.check(hb.lib().dia_engine_set_cross_fp8(self._engine, f8), "dia_engine_set_cross_fp8")
+        if self.self_kv == "fp8":                                           # the step's self-attention appends to and reads the e4m3 caches
+            f8 = (hb.KvFp8Ptrs * n)()
+            for i in range(n):
+                f8[i].k8, f8[i].v8 = hb.ptr(self.k8_self_all[i]), hb.ptr(self.v8_self_all[i])
+                f8[i].ks, f8[i].vs = hb.ptr(self.ks_self_all[i]), hb.ptr(self.vs_self_all[i])
+            hb.check(hb.lib().dia_engine_set_self_fp8(self._engine, f8), "dia_engine_set_self_fp8")
         if w.quant == "mxfp4":                                              # MXFP4 streams (quant="mxfp4"): beside the description
             f4_layers = (hb.Mxfp4Layer * n)()                               # (the engine copies the array)
             for i, L in enumerate(w.dec_layers):
@@ -1058,8 +1088,10 @@ class DecodeSession:
     def _prompt_prefill_batched(self) -> bool:
         """The batched MFMA prefill of the prompt rows needs bf16 caches with the blocked V layout and an
         uncompacted decoder; everything else replays the prompt rows through the decode step (first_step).  A session with
-        adapters= always replays: the batched prefill's projections carry no adapter correction, the decode step's do."""
-        return (self.adapters is None and any(f > 2 for f in self.first_steps) and self.v_blocked == 1 and self.kv_code == hb.KV_BF16 and not self.w.compacted and not self.teacher
+        adapters= always replays: the batched prefill's projections carry no adapter correction, the decode step's do.  So does
+        self_kv="fp8": the replay quantises every prompted key exactly like a generated one (a batched prefill onto fp8 caches is the
+        follow-up)."""
+        return (self.self_kv != "fp8" and self.adapters is None and any(f > 2 for f in self.first_steps) and self.v_blocked == 1 and self.kv_code == hb.KV_BF16 and not self.w.compacted and not self.teacher
                 and self.prompt_prefill != "replay" and self.w.weight_planes == 1)
 
     def _prompt_prefill(self, st):
@@ -1261,7 +1293,8 @@ class DecodeSession:
     def open(cls, w: DeviceWeights, slots: int, *, s_cap: Optional[int] = None, kv_dtype: str = "bf16",
              max_tokens: Optional[int] = None, ignore_eos: bool = False, stream: Optional[torch.cuda.Stream] = None,
              cfg_scale: float = 3.0, temperature: float = 1.3, top_p: float = 0.95, top_k: int = 35,
-             attention: str = "auto", stream_cap: Optional[int] = None, adapters=None, cross_kv: str = "bf16") -> "DecodeSession":
+             attention: str = "auto", stream_cap: Optional[int] = None, adapters=None, cross_kv: str = "bf16",
+             self_kv: str = "bf16") -> "DecodeSession":
         """A session of `slots` PARKED slots for a stream of requests: admit() puts a request into a free slot between two decode
         steps, the step graph (captured once) serves whatever the slots hold, retire() parks a finished one; serve() is the
         driver loop.  Cross caches are sized for texts of `s_cap` bytes (default: the encoder's text_length), the noise buffer for
@@ -1283,7 +1316,7 @@ class DecodeSession:
         empty = np.zeros((0,), dtype=np.int32)
         s = cls(w, [empty] * int(slots), kv_dtype=kv_dtype, max_tokens=max_tokens, cfg_scale=cfg_scale, temperature=temperature,
                 top_p=top_p, top_k=top_k, ignore_eos=ignore_eos, stream=stream, s_cap=_ceil(cap, 32), attention=attention,
-                adapters=adapters, cross_kv=cross_kv, _slotted=True)
+                adapters=adapters, cross_kv=cross_kv, self_kv=self_kv, _slotted=True)
         s.text_cap = cap                           # (the caches hold whole 32-key blocks; requests are held to what was asked for)
         if stream_cap is not None:
             s._init_stream(int(stream_cap))
@@ -1685,6 +1718,14 @@ class DecodeSession:
                 self._pinned.extend(pins)
 
     # ------------------------------------------------------------------ accounting
+    @property
+    def self_cache_bytes(self) -> int:
+        """Bytes of the self K/V caches of all layers and rows as allocated: bf16 / fp32 K and V, or (self_kv="fp8") the e4m3 bytes
+        and their scales — (1 + 1/32) / 2 of the bf16 caches at the same R and T."""
+        if self.self_kv == "fp8":
+            return sum(t.numel() * t.element_size() for t in (self.k8_self_all, self.v8_self_all, self.ks_self_all, self.vs_self_all))
+        return sum(t.numel() * t.element_size() for t in self.k_self + self.v_self)
+
     def step_bytes(self, n_keys: Optional[int] = None) -> int:
         """Algorithmic HBM bytes of one decode step at self-KV length `n_keys` (default: current)."""
         d = self.cfg.model.decoder
@@ -1692,5 +1733,7 @@ class DecodeSession:
         if n_keys is None:
             n_keys = int(self.cur.max().item())
         kv_self = 2 * d.n_layer * 2 * d.kv_heads * HEAD_DIM * kvb * n_keys      # both rows, K and V
+        if self.self_kv == "fp8":                                                # one byte per value, one 4-byte scale per key and head
+            kv_self = 2 * d.n_layer * 2 * d.kv_heads * (HEAD_DIM + 4) * n_keys
         kv_cross = d.n_layer * 2 * d.cross_query_heads * HEAD_DIM * kvb          # cond row, per text byte
         return self.w.decode_weight_bytes(self.R) + self.B * kv_self + kv_cross * sum(self.lens)

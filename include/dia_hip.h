@@ -838,6 +838,31 @@ int dia_attn_cross_fp8(const dia_attn_args* a, const dia_kv_fp8_ptrs* p, void* s
 int dia_engine_set_cross_fp8(dia_engine* e, const dia_kv_fp8_ptrs* layers /* host [n_layer], copied */);
 
 /* ------------------------------------------------------------------------------------------------
+ * FP8 self K/V (csrc/attn.hip; DESIGN.md "FP8 self K/V").  The self caches are the K/V traffic that grows with every step and the
+ * largest allocation of a session.  In this mode a layer's self cache IS four buffers in the format above with the self shapes —
+ * there is no bf16 cache beside them:
+ *   k8  uint8 [R][kv_heads][T][128]         v8  uint8 [R][kv_heads][T/32][128][32]         ks, vs  float [R][kv_heads][T]
+ * (0.516 of the bf16 bytes), all four zero-initialised once by the caller.  The step's new key is quantised as it is appended, by
+ * the rule of dia_kv_quantize_fp8 applied to the fp32 RoPE(k) and the fp32 v.  Every byte the append writes is a finite e4m3 value,
+ * so a key that is masked (not yet written, or left over from an earlier request in a re-used slot) contributes 0 x finite.  The
+ * reference has no counterpart (its self caches are bf16 or fp32 tensors, state.py:99-103).  Appended: no existing struct or entry
+ * point changed.
+ * ------------------------------------------------------------------------------------------------ */
+/* dia_attn for DIA_ATTN_SELF over e4m3 self caches: the MFMA kernel of the one-plane bf16 caches with the 8-byte fragments and
+ * folded-in scales of dia_attn_cross_fp8, for 1, 2 or 4 query heads per kv head.  The wave that owns slot cur - 1 ropes the new k,
+ * quantises k and v and writes 128 + 128 bytes and two scales (and patches its own fragments, bytes and scales, from a copy in
+ * LDS).  With a new key that quantises to itself the outputs equal dia_attn's over bf16 caches holding the dequantised values bit
+ * for bit, with the same key split.  *a describes the launch as for dia_attn; kc / vc are not read and may be NULL.  Refused with
+ * DIA_E_ARG: anything but mode == DIA_ATTN_SELF, kv_dtype == DIA_KV_BF16, v_blocked, kv_cap % 32 == 0, a cur, group 1 / 2 / 4,
+ * k8 / v8 aligned to 8 bytes and ks / vs to 4, scratch and tickets when kv_cap > 128, and what dia_attn refuses. */
+int dia_attn_self_fp8(const dia_attn_args* a, const dia_kv_fp8_ptrs* p, void* stream);
+/* before the first step (DIA_E_STATE afterwards): the step's self-attention launch of layer l is dia_attn_self_fp8 over layers[l]
+ * from then on, launch for launch in the place of dia_attn; dia_dec_layer.k_self / v_self are not read and may be NULL.
+ * DIA_E_ARG unless the engine has one-plane bf16 K/V (DIA_KV_BF16) with blocked V and T % 32 == 0.  Independent of
+ * dia_engine_set_cross_fp8: either, both or neither.  NULL = dia_attn over the bf16 caches, as without the call. */
+int dia_engine_set_self_fp8(dia_engine* e, const dia_kv_fp8_ptrs* layers /* host [n_layer], copied */);
+
+/* ------------------------------------------------------------------------------------------------
  * Codec (csrc/codec.hip; DESIGN.md "Codec"): the Descript Audio Codec decoder, codes [B, 9, T] -> waveform, in exact fp32 on the
  * f32-input MFMA (reference dia/audio.py:166-185: quantizer.from_codes, then decode).  Three new entry points and two new structs;
  * nothing older changed.  Activations are fp32 [B][C][ld] with time contiguous; the batch stride is C * ld.  Every row b carries
