@@ -104,6 +104,10 @@ def build_parser() -> argparse.ArgumentParser:
     g.add_argument("--cross-kv", type=str, default="bf16", choices=["bf16", "fp8"],
                    help="(build-only) fp8: the decode step reads an e4m3 copy of the cross-attention K/V caches (one power-of-two scale per "
                         "key and head) instead of the bf16 caches; needs a bf16 --compute-dtype")
+    g.add_argument("--prompt-prefill", type=str, default="auto", choices=["auto", "replay", "batched"],
+                   help="(build-only) batched: audio prompts of more than one frame are prefilled as one packed batch also at slot admission "
+                        "(--slots N) and onto --self-kv fp8 caches; auto: closed bf16 sessions prefill, everything else replays the prompt "
+                        "through the decode step; replay: always replay")
     g.add_argument("--self-kv", type=str, default="bf16", choices=["bf16", "fp8"],
                    help="(build-only) fp8: the self-attention K/V caches are kept as e4m3 (one power-of-two scale per key and head, the new "
                         "key quantised as it is appended) instead of bf16: 0.516 of the bytes; needs a bf16 --compute-dtype")
@@ -301,6 +305,7 @@ def main(argv=None) -> int:
     Dia.weight_format = args.weight_format
     Dia.cross_kv = args.cross_kv
     Dia.self_kv = args.self_kv
+    Dia.prompt_prefill = args.prompt_prefill
     if args.seed is not None:
         set_seed(args.seed)
         print(f"Using seed: {args.seed}")

@@ -16,6 +16,7 @@
 // (hipGraph): splits beyond the current length exit at once.
 // The output leaves as three bf16 planes in MFMA A-operand order for the o_proj GEMM.
 #include "common.hpp"
+#include "kv_fp8.hpp"
 #include "../../include/dia_hip.h"
 #include "errors.hpp"
 #include "launch.hpp"
@@ -652,18 +653,7 @@ __global__ __launch_bounds__(NT, 2) void k_attn_mfma(AttnK p) {
 // those of the bf16 kernel over the dequantised caches and the output is the same bit for bit.  Key -> workgroup -> wave
 // assignment, gpw rule, two-granule prefetch, online softmax, slab merge and output are k_attn_mfma's; there is no slot to append.
 struct AttnF8 { const uint8_t* k8; const uint8_t* v8; const float* ks; const float* vs; };
-struct F8Frag { uint2 kb[2][4]; uint2 vb[8]; float ksc[2], vsc[2]; };
-
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-__device__ __forceinline__ bf16x8 expand_e4m3(uint2 d) {      // (gemm_mx.hip Fp8::frag at scale 1)
-  const bf16x2 r0 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(d.x, 1.0f, false);
-  const bf16x2 r1 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(d.x, 1.0f, true);
-  const bf16x2 r2 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(d.y, 1.0f, false);
-  const bf16x2 r3 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(d.y, 1.0f, true);
-  typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
-  const bf16x4 lo = __builtin_shufflevector(r0, r1, 0, 1, 2, 3), hi = __builtin_shufflevector(r2, r3, 0, 1, 2, 3);
-  return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-}
+struct F8Frag { uint2 kb[2][4]; uint2 vb[8]; float ksc[2], vsc[2]; };      // (expand_e4m3: kv_fp8.hpp)
 
 __global__ __launch_bounds__(NT, 2) void k_attn_mfma_f8(AttnK p, AttnF8 f8) {
   constexpr int G = 1;
@@ -817,15 +807,7 @@ __global__ __launch_bounds__(NT, 2) void k_attn_mfma_f8(AttnK p, AttnF8 f8) {
   attn_finish<G>(p, part, pm_s, pl_s, &last_s, tid, qrow, kvh, head_row, chunk, nchunks);
 }
 
-// OCP e4m3 (bias 7, subnormal step 2^-9, finite max 448 = 0x7E) of a finite x with |x| <= 448, rounded to nearest even
-__device__ __forceinline__ unsigned e4m3_rne(float x) {
-  unsigned u = __float_as_uint(x);
-  const unsigned s = (u >> 24) & 0x80u;
-  u &= 0x7fffffffu;
-  if (u < 0x3c800000u) return s | (unsigned)rintf(__uint_as_float(u) * 512.f);     // below 2^-6: multiples of 2^-9 (8 = the first normal)
-  u += 0x7ffffu + ((u >> 20) & 1u);          // three mantissa bits stay
-  return s | ((u >> 20) - (120u << 3));
-}
+// (e4m3_rne: kv_fp8.hpp)
 // the scale of a key from the largest |bf16| bit pattern of its 128 values: bits of 2^e, e = the smallest with amax / 2^e <= 448
 // (448 = 1.75 * 2^8: e = exponent - 8, one more when the significand is above 1.75), at least -126; 1 for an all-zero key
 __device__ __forceinline__ unsigned kv_scale_bits(unsigned amax_bf16) {
@@ -919,23 +901,7 @@ __global__ __launch_bounds__(256) void k_kv_quantize_fp8(KvQuantK p) {
 // new key's 256 bytes and two scales stay in LDS and consume() patches kb, one byte per vb[nb], and ksc / vsc of the lane that holds
 // the key.  The caches are allocated zeroed and every byte the encoder writes is finite (|x| / scale <= 448, and the byte is clamped
 // to 0x7E for a non-finite input), so a masked key — not yet written, or left over in a re-used slot — contributes 0 x finite.
-struct AttnF8W { uint8_t* k8; uint8_t* v8; float* ks; float* vs; };
-
-// kv_scale_bits for an fp32 amax bit pattern: 448 = 1.75 * 2^8, so e = exponent - 8, one more when the significand is above 1.75
-__device__ __forceinline__ unsigned kv_scale_bits_f32(unsigned amax) {
-  if (amax == 0) return 0x3f800000u;
-  const int se = (int)(amax >> 23) - 8 + ((amax & 0x7fffffu) > 0x600000u ? 1 : 0);
-  return (unsigned)min(max(se, 1), 254) << 23;
-}
-__device__ __forceinline__ unsigned e4m3_finite(float x) {      // e4m3_rne, a non-finite or oversized input held to +-448
-  const unsigned b = e4m3_rne(x);
-  return (b & 0x80u) | min(b & 0x7fu, 0x7eu);
-}
-__device__ __forceinline__ unsigned wave_umax(unsigned v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = max(v, (unsigned)__shfl_xor((int)v, o, 64));
-  return v;
-}
+struct AttnF8W { uint8_t* k8; uint8_t* v8; float* ks; float* vs; };      // (kv_scale_bits_f32, e4m3_finite, wave_umax: kv_fp8.hpp)
 
 template <int G>
 __global__ __launch_bounds__(NT, 2) void k_attn_self_f8(AttnK p, AttnF8W f8) {

@@ -3,15 +3,17 @@
 // batch through the MFMA-tiled GEMMs, with the three kernels below for what is not a GEMM.  Semantics are the
 // replay's (oracle.generate docstring): token row r -> cache slot r at RoPE position r + 1; the K/V written to
 // the caches are rounded to the cache dtype first and attention reads them back from the caches, exactly what
-// the decode steps will do afterwards.  bf16 caches with the blocked V layout only (the perf configuration);
-// fp32 caches keep the replay.
+// the decode steps will do afterwards.  bf16 caches with the blocked V layout (the perf configuration), or FP8 self caches
+// (k_prefill_kv_f8 / k_prefill_attn_f8 below: every prompted key quantised like a generated one); fp32 caches keep the replay.
 //
 // Packing: segment s = (utterance b, CFG row c) owns packed rows [seg_off[s], seg_off[s] + seg_len[s]),
 // seg_off a multiple of 32; row_seg[m] = segment of packed row m or -1 (padding); seg_row[s] = 2b + c.
 #include "common.hpp"
+#include "kv_fp8.hpp"
 #include "../../include/dia_hip.h"
 #include "errors.hpp"
 #include "launch.hpp"
+#include <cstdio>
 
 namespace {
 
@@ -240,6 +242,208 @@ __global__ __launch_bounds__(256) void k_prefill_attn(PrefK p) {
   }
 }
 
+// ---------------------------------------------------------------------------------------------------
+// The same two steps onto FP8 self caches (dia_hip.h "FP8 self K/V"): k8 [row][kv_heads][T][128], v8 [row][kv_heads][T/32][128][32],
+// ks / vs float [row][kv_heads][T].  The cross call keeps k_prefill_attn: the cross caches stay bf16.
+struct PrefF8 { uint8_t* k8; uint8_t* v8; float* ks; float* vs; };
+
+// grid (kv head, 32-row block), 4 waves.  seg_off is a multiple of 32, so a block is keys [r0, r0 + 32) of ONE segment: one K run of
+// 32 x 128 bytes and one blocked V granule.  One wave per (row, kv head) at a time, lane l holding dims l and l + 64 of k and of v:
+// RoPE, amax, scale and bytes are k_attn_self_f8's owner-wave append, spelt the same way, from the fp32 projection values.  The
+// bytes are staged in LDS; a block of 32 live rows leaves as 16-byte stores, a partial one as the live keys' K rows (16-byte
+// stores) and the live keys' V bytes one by one — no byte or scale outside keys [0, seg_len) of the segment's cache row changes.
+__global__ __launch_bounds__(256) void k_prefill_kv_f8(PrefK p, PrefF8 f8) {
+  __shared__ __attribute__((aligned(16))) uint8_t kst[32 * HD];      // [key][dim]
+  __shared__ __attribute__((aligned(16))) uint8_t vst[HD * 32];      // [dim][key]: the granule as it lies in the cache
+  const int h = blockIdx.x, blk = blockIdx.y, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int s = p.row_seg[blk * 32];
+  if (s < 0) return;                                    // (uniform) a block of padding rows
+  const int off = p.seg_off[s], r0 = blk * 32 - off;
+  const int nlive = min(min(32, p.seg_len[s] - r0), p.kv_cap - r0);      // live rows are the block's first nlive
+  if (r0 < 0 || (r0 & 31) != 0 || nlive <= 0) return;
+  const long pair_keys = ((long)p.seg_row[s] * p.kv_heads + h) * p.kv_cap;
+  uint8_t* K8 = f8.k8 + (pair_keys + r0) * HD;          // this block's 32 K rows ...
+  uint8_t* V8 = f8.v8 + (pair_keys + r0) * HD;          // ... and its V granule (r0 / 32 granules of 128 x 32 bytes)
+  float* KS = f8.ks + pair_keys + r0;
+  float* VS = f8.vs + pair_keys + r0;
+  for (int rr = w; rr < nlive; rr += 4) {               // (wave-uniform trip)
+    const int m = blk * 32 + rr;
+    if (p.row_seg[m] != s) continue;
+    const int pos = r0 + rr + 1;
+    const float* qr = p.q + (long)m * p.ldq;
+    const float* kh = qr + p.k_off + h * HD;
+    const float* vh = qr + p.v_off + h * HD;
+    const float kx1 = kh[lane], kx2 = kh[lane + 64];
+    const float vx1 = vh[lane], vx2 = vh[lane + 64];
+    const float rc = p.cos_t[(long)pos * 64 + lane], rs = p.sin_t[(long)pos * 64 + lane];
+    const float k1 = __builtin_fmaf(kx1, rc, -mul_rn(kx2, rs)), k2 = __builtin_fmaf(kx2, rc, mul_rn(kx1, rs));
+    const unsigned ksb = kv_scale_bits_f32(wave_umax(max(__float_as_uint(k1) & 0x7fffffffu, __float_as_uint(k2) & 0x7fffffffu)));
+    const unsigned vsb = kv_scale_bits_f32(wave_umax(max(__float_as_uint(vx1) & 0x7fffffffu, __float_as_uint(vx2) & 0x7fffffffu)));
+    const float kinv = __uint_as_float((254u << 23) - ksb), vinv = __uint_as_float((254u << 23) - vsb);      // 1 / scale, exact
+    kst[rr * HD + lane] = (uint8_t)e4m3_finite(k1 * kinv); kst[rr * HD + lane + 64] = (uint8_t)e4m3_finite(k2 * kinv);
+    vst[lane * 32 + rr] = (uint8_t)e4m3_finite(vx1 * vinv); vst[(lane + 64) * 32 + rr] = (uint8_t)e4m3_finite(vx2 * vinv);
+    if (lane == 0) { KS[rr] = __uint_as_float(ksb); VS[rr] = __uint_as_float(vsb); }
+  }
+  __syncthreads();
+  // live mask of the block (bit rr), the same in every thread
+  unsigned live = 0;
+  for (int rr = 0; rr < nlive; ++rr) live |= (p.row_seg[blk * 32 + rr] == s ? 1u : 0u) << rr;
+  if ((live >> (tid >> 3)) & 1u)                        // K: thread = (key tid / 8, 16 dims)
+    *reinterpret_cast<uint4*>(K8 + tid * 16) = *reinterpret_cast<const uint4*>(kst + tid * 16);
+  if (live == 0xffffffffu) {                            // V: thread = (dim tid / 2, 16 keys)
+    *reinterpret_cast<uint4*>(V8 + tid * 16) = *reinterpret_cast<const uint4*>(vst + tid * 16);
+  } else {
+    for (int t = tid; t < HD * 32; t += 256)
+      if ((live >> (t & 31)) & 1u) V8[t] = vst[t];
+  }
+}
+
+// k_prefill_attn (causal) over the e4m3 self caches: 8-byte K / V fragments expanded to bf16 in registers (exact), the scales folded
+// in behind the MFMAs — S[key] *= ks[key] before the softmax scale and the mask, p[key] *= vs[key] before split3, lrun from the
+// unscaled p.  The scales are powers of two, so every MFMA receives products equal to those of k_prefill_attn over bf16 caches
+// holding the dequantised values and the output is the same bit for bit (as long as p * vs is a normal fp32).  A lane holds the score
+// of key key0 + 16t + arow in S[t][.], so it loads that key's two scales; the clamped re-read of klast clamps the K scale index too.
+__global__ __launch_bounds__(256) void k_prefill_attn_f8(PrefK p, PrefF8 f8) {
+  constexpr int NWV = 4;
+  __shared__ __attribute__((aligned(16))) bf16_raw qf[4][DIA_NPLANES][16][4][8];
+  __shared__ __attribute__((aligned(16))) bf16_raw pbuf[NWV][DIA_NPLANES][16][32];
+  __shared__ float part[NWV * 16 * HD];
+  __shared__ float pm_s[NWV * 16], pl_s[NWV * 16];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int h = blockIdx.x, qt = blockIdx.y;
+  const int arow = lane & 15, akq = lane >> 4;
+  const int s = p.row_seg[qt * 16];
+  if (s < 0) return;
+  const int off = p.seg_off[s], len = min(p.seg_len[s], p.kv_cap), crow = p.seg_row[s];
+  const int r0 = qt * 16 - off;                       // first prompt row of this tile
+  const int group = p.q_heads / p.kv_heads;
+  const int nkeys = min(len, r0 + 16);
+  const long pair_keys = ((long)crow * p.kv_heads + h / group) * p.kv_cap;
+  const uint8_t* K8 = f8.k8 + pair_keys * HD;
+  const uint8_t* V8 = f8.v8 + pair_keys * HD;
+  const float* KS = f8.ks + pair_keys;
+  const float* VS = f8.vs + pair_keys;
+  {
+    const int r = tid >> 4, m = min(qt * 16 + r, off + len - 1), pos = (m - off) + 1;
+    const float* qh = p.q + (long)m * p.ldq + p.q_off + h * HD;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int d = (tid & 15) * 4 + i;
+      const float x1 = qh[d], x2 = qh[d + 64];
+      const float c = p.cos_t[(long)pos * 64 + d], sn = p.sin_t[(long)pos * 64 + d];
+      const float qv[2] = {x1 * c - x2 * sn, x1 * sn + x2 * c};
+#pragma unroll
+      for (int e = 0; e < 2; ++e) {
+        const int D = d + 64 * e;
+        __bf16 a, bb, c3;
+        split3(qv[e], a, bb, c3);
+        qf[D >> 5][0][r][(D >> 3) & 3][D & 7] = *reinterpret_cast<const bf16_raw*>(&a);
+        qf[D >> 5][1][r][(D >> 3) & 3][D & 7] = *reinterpret_cast<const bf16_raw*>(&bb);
+        qf[D >> 5][2][r][(D >> 3) & 3][D & 7] = *reinterpret_cast<const bf16_raw*>(&c3);
+      }
+    }
+  }
+  __syncthreads();
+  const float scale = 0.08838834764831845f;
+  f32x4 O[8];
+#pragma unroll
+  for (int nb = 0; nb < 8; ++nb) O[nb] = f32x4{0.f, 0.f, 0.f, 0.f};
+  float mrun[4], lrun[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) { mrun[r] = -INFINITY; lrun[r] = 0.f; }
+  const int klast = max(nkeys - 1, 0);
+  const int ngran = (nkeys + 31) >> 5;
+  for (int g = w; g < ngran; g += NWV) {
+    const int key0 = g << 5;
+    f32x4 S[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
+    const int kidx[2] = {min(key0 + arow, klast), min(key0 + 16 + arow, klast)};
+    const float ksc[2] = {KS[kidx[0]], KS[kidx[1]]};
+    const float vsc[2] = {VS[min(key0 + arow, p.kv_cap - 1)], VS[min(key0 + 16 + arow, p.kv_cap - 1)]};     // (inside the row: finite)
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) {
+      bf16x8 qa[DIA_NPLANES];
+#pragma unroll
+      for (int pl = 0; pl < DIA_NPLANES; ++pl) qa[pl] = *reinterpret_cast<const bf16x8*>(&qf[ks][pl][arow][akq][0]);
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        const bf16x8 kb = expand_e4m3(*reinterpret_cast<const uint2*>(K8 + (long)kidx[t] * HD + 32 * ks + 8 * akq));
+#pragma unroll
+        for (int pl = 0; pl < DIA_NPLANES; ++pl) S[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qa[pl], kb, S[t], 0, 0, 0);
+      }
+    }
+    float alpha[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int lim = min(nkeys, r0 + 4 * akq + r + 1);      // keys this query row may see
+      const bool v0 = key0 + arow < lim, v1 = key0 + 16 + arow < lim;
+      const float s0 = v0 ? mul_rn(mul_rn(S[0][r], ksc[0]), scale) : -INFINITY, s1 = v1 ? mul_rn(mul_rn(S[1][r], ksc[1]), scale) : -INFINITY;
+      const float mnew = fmaxf(mrun[r], row16_max_p(fmaxf(s0, s1)));
+      alpha[r] = (mrun[r] == -INFINITY) ? 0.f : expf(mrun[r] - mnew);
+      const float p0 = (s0 == -INFINITY) ? 0.f : expf(s0 - mnew), p1 = (s1 == -INFINITY) ? 0.f : expf(s1 - mnew);
+      lrun[r] = lrun[r] * alpha[r] + row16_sum(p0 + p1);      // (the sum takes the unscaled p)
+      mrun[r] = mnew;
+      __bf16 a, bb, c3;
+      split3(mul_rn(p0, vsc[0]), a, bb, c3);
+      pbuf[w][0][4 * akq + r][arow] = *reinterpret_cast<const bf16_raw*>(&a);
+      pbuf[w][1][4 * akq + r][arow] = *reinterpret_cast<const bf16_raw*>(&bb);
+      pbuf[w][2][4 * akq + r][arow] = *reinterpret_cast<const bf16_raw*>(&c3);
+      split3(mul_rn(p1, vsc[1]), a, bb, c3);
+      pbuf[w][0][4 * akq + r][16 + arow] = *reinterpret_cast<const bf16_raw*>(&a);
+      pbuf[w][1][4 * akq + r][16 + arow] = *reinterpret_cast<const bf16_raw*>(&bb);
+      pbuf[w][2][4 * akq + r][16 + arow] = *reinterpret_cast<const bf16_raw*>(&c3);
+    }
+    __builtin_amdgcn_wave_barrier();
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+    for (int nb = 0; nb < 8; ++nb)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) O[nb][r] *= alpha[r];
+    bf16x8 pa[DIA_NPLANES];
+#pragma unroll
+    for (int pl = 0; pl < DIA_NPLANES; ++pl) pa[pl] = *reinterpret_cast<const bf16x8*>(&pbuf[w][pl][arow][8 * akq]);
+    const uint8_t* Vblk = V8 + (long)g * HD * 32;
+#pragma unroll
+    for (int nb = 0; nb < 8; ++nb) {
+      const bf16x8 vb = expand_e4m3(*reinterpret_cast<const uint2*>(Vblk + (long)(16 * nb + arow) * 32 + 8 * akq));
+#pragma unroll
+      for (int pl = 0; pl < DIA_NPLANES; ++pl) O[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pa[pl], vb, O[nb], 0, 0, 0);
+    }
+    __builtin_amdgcn_wave_barrier();
+  }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+#pragma unroll
+    for (int nb = 0; nb < 8; ++nb) part[(w * 16 + 4 * akq + r) * HD + 16 * nb + arow] = O[nb][r];
+    if (arow == 0) { pm_s[w * 16 + 4 * akq + r] = mrun[r]; pl_s[w * 16 + 4 * akq + r] = lrun[r]; }
+  }
+  __syncthreads();
+  {
+    const int r = tid >> 4, d0 = (tid & 15) * 8, m = qt * 16 + r;
+    if (m - off >= len) return;
+    float mm = -INFINITY;
+#pragma unroll
+    for (int ww = 0; ww < NWV; ++ww) mm = fmaxf(mm, pm_s[ww * 16 + r]);
+    float o[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, Ls = 0.f;
+#pragma unroll
+    for (int ww = 0; ww < NWV; ++ww) {
+      const float pmw = pm_s[ww * 16 + r];
+      const float f = (pmw == -INFINITY) ? 0.f : expf(pmw - mm);
+      // the wave merge, each sum spelt as the compiler's contraction leaves `Ls += pl * f; o[j] += part * f` in k_prefill_attn: dims
+      // 0..5 of a thread's eight are fused multiply-adds, dims 6 and 7 and the softmax sum a rounded product and an add (left to
+      // itself the compiler fused other terms here, and rows of more than one granule differed in the last bit)
+      Ls = add_rn(Ls, mul_rn(pl_s[ww * 16 + r], f));
+#pragma unroll
+      for (int j = 0; j < 6; ++j) o[j] = __builtin_fmaf(part[(ww * 16 + r) * HD + d0 + j], f, o[j]);
+#pragma unroll
+      for (int j = 6; j < 8; ++j) o[j] = add_rn(o[j], mul_rn(part[(ww * 16 + r) * HD + d0 + j], f));
+    }
+    const float inv = Ls > 0.f ? 1.0f / Ls : 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) o[j] *= inv;
+    emit_planes8(p.P, p.p_plane_stride, p.p_ktiles, m, h * HD + d0, o);
+  }
+}
+
 int fill(const dia_dec_prefill_args* a, PrefK& k) {
   if (!a || !a->row_seg || !a->seg_off || !a->seg_len || !a->seg_row || a->rows <= 0 || a->rows % 32 != 0)
     return dia_fail(DIA_E_ARG, "dia_dec_prefill: packing arrays missing or rows not a multiple of 32");
@@ -268,6 +472,42 @@ extern "C" int dia_dec_prefill_kv(const dia_dec_prefill_args* a, void* stream) {
     return dia_fail(DIA_E_ARG, "dia_dec_prefill_kv: bad argument");
   dia_launch<k_prefill_kv>(dim3(a->kv_heads, a->rows / 32), dim3(256), 0, (hipStream_t)stream, k);
   return dia_check_launch("k_prefill_kv");
+}
+
+namespace {
+// what both fp8 entry points refuse before they look at anything else; `who` prefixes the message
+int fill_f8(const char* who, const dia_dec_prefill_args* a, const dia_kv_fp8_ptrs* f, PrefK& k, PrefF8& f8) {
+  static thread_local char msg[160];
+  auto fail = [&](const char* what) { snprintf(msg, sizeof msg, "%s: %s", who, what); return dia_fail(DIA_E_ARG, msg); };
+  if (!a || !f) return fail("null argument");
+  if (!f->k8 || !f->v8 || !f->ks || !f->vs) return fail("null argument (k8 / v8 / ks / vs)");
+  if (a->kc || a->vc) return fail("kc / vc must be NULL: the fp8 self caches are the only caches of this call");
+  if (!a->causal) return fail("causal must be 1 (the cross caches stay bf16: dia_dec_prefill_attn serves the cross call)");
+  if (a->kv_cap <= 0 || a->kv_cap % 32 != 0) return fail("kv_cap must be a positive multiple of 32");
+  if (((uintptr_t)f->k8 | (uintptr_t)f->v8) % 16 != 0 || ((uintptr_t)f->ks | (uintptr_t)f->vs) % 4 != 0)
+    return fail("k8 / v8 must be 16-byte aligned, ks / vs 4-byte");
+  const int rc = fill(a, k);
+  if (rc) return rc;
+  f8 = PrefF8{(uint8_t*)f->k8, (uint8_t*)f->v8, f->ks, f->vs};
+  return DIA_OK;
+}
+}  // namespace
+
+extern "C" int dia_dec_prefill_kv_fp8(const dia_dec_prefill_args* a, const dia_kv_fp8_ptrs* f, void* stream) {
+  PrefK k; PrefF8 f8; int rc = fill_f8("dia_dec_prefill_kv_fp8", a, f, k, f8); if (rc) return rc;
+  if (!a->q || !a->cos_t || !a->sin_t || a->kv_heads <= 0)
+    return dia_fail(DIA_E_ARG, "dia_dec_prefill_kv_fp8: bad argument");
+  dia_launch<k_prefill_kv_f8>(dim3(a->kv_heads, a->rows / 32), dim3(256), 0, (hipStream_t)stream, k, f8);
+  return dia_check_launch("k_prefill_kv_f8");
+}
+
+extern "C" int dia_dec_prefill_attn_fp8(const dia_dec_prefill_args* a, const dia_kv_fp8_ptrs* f, void* stream) {
+  PrefK k; PrefF8 f8; int rc = fill_f8("dia_dec_prefill_attn_fp8", a, f, k, f8); if (rc) return rc;
+  if (!a->q || !a->cos_t || !a->sin_t || !a->P || a->q_heads <= 0 || a->kv_heads <= 0 || a->q_heads % a->kv_heads != 0 ||
+      a->p_plane_stride % 8 != 0 || (a->q_heads * 128 + 31) / 32 > a->p_ktiles)
+    return dia_fail(DIA_E_ARG, "dia_dec_prefill_attn_fp8: bad argument");
+  dia_launch<k_prefill_attn_f8>(dim3(a->q_heads, a->rows / 16), dim3(256), 0, (hipStream_t)stream, k, f8);
+  return dia_check_launch("k_prefill_attn_f8");
 }
 
 extern "C" int dia_dec_prefill_attn(const dia_dec_prefill_args* a, void* stream) {

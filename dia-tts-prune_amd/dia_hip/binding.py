@@ -27,7 +27,7 @@ EXPORTS = (
     "dia_score", "dia_engine_set_score",
     "dia_lora_apply", "dia_lora_crosskv", "dia_engine_set_lora",
     "dia_kv_quantize_fp8", "dia_attn_cross_fp8", "dia_engine_set_cross_fp8",
-    "dia_attn_self_fp8", "dia_engine_set_self_fp8",
+    "dia_attn_self_fp8", "dia_engine_set_self_fp8", "dia_dec_prefill_kv_fp8", "dia_dec_prefill_attn_fp8",
     "dia_codec_embed", "dia_codec_conv", "dia_codec_convt", "dia_codec_convs", "dia_codec_quantize",
     "dia_resample",
     "dia_seg_mlp", "dia_seg_workspace_bytes", "dia_seg_workspace_control_bytes", "dia_seg_slots", "dia_seg_supported", "dia_seg_error",
@@ -377,6 +377,8 @@ def lib() -> C.CDLL:
     L.dia_engine_set_cross_fp8.argtypes = [C.c_void_p, C.POINTER(KvFp8Ptrs)]
     L.dia_attn_self_fp8.argtypes = [C.POINTER(AttnArgs), C.POINTER(KvFp8Ptrs), C.c_void_p]
     L.dia_engine_set_self_fp8.argtypes = [C.c_void_p, C.POINTER(KvFp8Ptrs)]
+    for fn in (L.dia_dec_prefill_kv_fp8, L.dia_dec_prefill_attn_fp8):
+        fn.argtypes = [C.POINTER(DecPrefillArgs), C.POINTER(KvFp8Ptrs), C.c_void_p]
     L.dia_resample.argtypes = [C.POINTER(ResampleArgs), C.c_void_p]
     L.dia_seg_mlp.argtypes = [C.POINTER(SegArgs), C.c_void_p]
     L.dia_seg_workspace_bytes.restype = C.c_int64

@@ -480,7 +480,7 @@ class Request:
     temperature: float = 1.3
     top_p: float = 0.95
     top_k: int = 35
-    audio_prompt: Optional[np.ndarray] = None      # codes [Tp, C]; the prompt rows are replayed through the decode step
+    audio_prompt: Optional[np.ndarray] = None      # codes [Tp, C]; the prompt rows are replayed through the decode step (prompt_prefill="batched": prefilled)
     adapter: Optional[Union[str, int]] = None      # name or index in the session's AdapterBank; None = the base model
 
 
@@ -496,6 +496,8 @@ class UtteranceResult:
 class DecodeSession:
     """Buffers + engine for one batch of utterances."""
 
+    prompt_prefill = "auto"                      # (set per session; "batched" also prefills at slot admission and onto fp8 self caches)
+
     def __init__(self, w: DeviceWeights, text_ids: Sequence[np.ndarray], *, kv_dtype: str = "bf16",
                  max_tokens: Optional[int] = None, cfg_scale: float = 3.0, temperature: float = 1.3,
                  top_p: float = 0.95, top_k: int = 35, seeds: Optional[Sequence[Optional[int]]] = None,
@@ -508,6 +510,10 @@ class DecodeSession:
         """audio_prompts: per utterance None or int codes [Tp, C] (reference model.py:311-353).  The prompt
         rows are replayed through the decode step before sampling starts (semantics: oracle.generate), or — with
         bf16 caches — prefilled as one packed MFMA batch; prompt_prefill="replay" forces the replay.
+        prompt_prefill="batched" (opt-in; DESIGN.md "Prompt prefill at admission and onto fp8 caches"): every prompt of more than
+        one frame is prefilled as a packed batch — also at slot admission (admit / serve / stream_iter) and onto self_kv="fp8"
+        caches, which "auto" leaves to the replay.  Whatever the prefill kernels cannot serve raises ValueError here: fp32 or
+        two-plane K/V, attention="valu", adapters=, teacher_tokens= / score=True, a compacted decoder, weight_planes != 1.
         attention="valu" keeps bf16 V caches row-major and runs the VALU attention kernel (comparison runs).
         score=True (with teacher_tokens): every step also reduces its logits to the log-probability of the forced row, on the
         device (dia_score; DESIGN.md "Scoring"); scores_host() downloads the [B, T, C, 3] result once at the end.
@@ -519,14 +525,14 @@ class DecodeSession:
         blocked V layout.  "bf16" (default): nothing of it exists.
         self_kv="fp8": the SELF caches are e4m3 bytes with one power-of-two scale per key and head (DESIGN.md "FP8 self K/V"): the step's
         self-attention quantises the new key as it appends it, k_self / v_self are not allocated (self_cache_bytes is 0.516 of the
-        bf16 session's) and audio prompts replay through the decode step.  Needs bf16 K/V with the blocked V layout and
+        bf16 session's) and audio prompts replay through the decode step unless prompt_prefill="batched".  Needs bf16 K/V with the blocked V layout and
         audio_length % 32 == 0; independent of cross_kv.  "bf16" (default): nothing of it exists."""
         if adapter_ids is not None and adapters is None:
             raise ValueError("adapter_ids needs adapters= (an AdapterBank)")
         if score and (teacher_tokens is None or _slotted):
             raise ValueError("score=True scores teacher-forced rows of a closed batch: pass teacher_tokens (and no slots)")
-        if prompt_prefill not in ("auto", "replay") or attention not in ("auto", "valu"):
-            raise ValueError("prompt_prefill must be 'auto' or 'replay', attention 'auto' or 'valu'")
+        if prompt_prefill not in ("auto", "replay", "batched") or attention not in ("auto", "valu"):
+            raise ValueError("prompt_prefill must be 'auto', 'replay' or 'batched', attention 'auto' or 'valu'")
         if cross_kv not in ("bf16", "fp8"):
             raise ValueError("cross_kv must be 'bf16' or 'fp8'")
         if self_kv not in ("bf16", "fp8"):
@@ -565,6 +571,22 @@ class DecodeSession:
             if self.T % 32 != 0:
                 raise ValueError(f"self_kv='fp8' needs audio_length % 32 == 0 (whole 32-key granules), not {self.T}")
         self.self_kv = self_kv
+        if prompt_prefill == "batched":              # everything the dia_dec_prefill_* kernels cannot serve, by name, before anything is allocated
+            why = None
+            if self.kv_code != hb.KV_BF16:
+                why = f"kv_dtype '{kv_dtype}' (fp32 or two-plane K/V): the prefill kernels write and read one-plane bf16 or fp8 self caches"
+            elif not self.v_blocked:
+                why = "attention='valu' keeps V row-major: the prefill kernels need the blocked V layout"
+            elif adapters is not None:
+                why = "adapters=: the batched prefill's projections carry no adapter correction"
+            elif teacher_tokens is not None or score:
+                why = "teacher_tokens= / score=True: forced rows are scored step by step"
+            elif w.compacted:
+                why = "a compacted decoder: the prefill GEMMs address the uncompacted columns"
+            elif w.weight_planes != 1:
+                why = f"weight_planes = {w.weight_planes}: the prefill GEMMs read one-plane weights"
+            if why is not None:
+                raise ValueError(f"prompt_prefill='batched' is not served with {why}")
         kvt = torch.float32 if self.kv_code == hb.KV_F32 else torch.bfloat16
         self.kv_planes = 2 if self.kv_code == hb.KV_BF16X2 else 1
         self.stream = stream if stream is not None else torch.cuda.Stream(device=dev)
@@ -1089,31 +1111,56 @@ class DecodeSession:
         """The batched MFMA prefill of the prompt rows needs bf16 caches with the blocked V layout and an
         uncompacted decoder; everything else replays the prompt rows through the decode step (first_step).  A session with
         adapters= always replays: the batched prefill's projections carry no adapter correction, the decode step's do.  So does
-        self_kv="fp8": the replay quantises every prompted key exactly like a generated one (a batched prefill onto fp8 caches is the
-        follow-up)."""
-        return (self.self_kv != "fp8" and self.adapters is None and any(f > 2 for f in self.first_steps) and self.v_blocked == 1 and self.kv_code == hb.KV_BF16 and not self.w.compacted and not self.teacher
+        self_kv="fp8" under "auto": the replay quantises every prompted key exactly like a generated one; and so does a slot
+        session, whose admissions replay.  prompt_prefill="batched" (checked at construction) prefills in all of these."""
+        if self.prompt_prefill == "batched":
+            return any(f > 2 for f in self.first_steps)
+        return (not self.slotted and self.self_kv != "fp8" and self.adapters is None and any(f > 2 for f in self.first_steps) and self.v_blocked == 1 and self.kv_code == hb.KV_BF16 and not self.w.compacted and not self.teacher
                 and self.prompt_prefill != "replay" and self.w.weight_planes == 1)
 
-    def _prompt_prefill(self, st):
-        """Decoder.forward in prefill mode (layers.py:722-766) for the audio prompts of all utterances at once, with
-        the replay's semantics (token row r -> slot r, position r + 1): packed rows = both CFG rows of every
-        prompted utterance; dense layers on the MFMA-tiled GEMM, K/V append / causal self-attention / cross
-        attention over the caches by the dia_dec_prefill_* kernels.  Afterwards cur[b] = first_step[b]."""
+    def _prompt_prefill(self, st, slots=None):
+        """Decoder.forward in prefill mode (layers.py:722-766) for the audio prompts of the given (utterance / slot b, first_step)
+        pairs at once (None: every utterance of a closed batch), with the replay's semantics (token row r -> slot r, position
+        r + 1): packed rows = both CFG rows of every prompted utterance; dense layers on the MFMA-tiled GEMM, K/V append / causal
+        self-attention / cross attention over the caches by the dia_dec_prefill_* kernels (the _fp8 entry points over e4m3 self
+        caches).  Afterwards cur[b] = first_step[b]: the whole tensor for a closed batch; for admitted slots an indexed device
+        write of exactly those slots (a live slot's cur is the device's), from one pinned table with the packing — no host wait."""
         L = hb.lib()
         cfg, w, dev = self.cfg, self.w, self.dev
         d = cfg.model.decoder
         D, F = self.D, self.F
         QH, KVH, CH = d.gqa_query_heads, d.kv_heads, d.cross_query_heads
         eps = float(cfg.model.normalization_layer_epsilon)
+        closed = slots is None
+        pairs = list(enumerate(self.first_steps)) if closed else [(int(b), int(fs)) for b, fs in slots]
+        pairs = [(b, fs) for b, fs in pairs if fs > 2]       # rows 0..fs-2 are prefilled; fs == 2 (one frame) is left to the replay path
+        if not pairs:
+            return
         segs = []                                   # (cache row 2b+c, prompt rows)
-        for b, fs in enumerate(self.first_steps):
-            if fs > 2:                              # rows 0..fs-2 are prefilled; fs == 2 (one frame) is left to the replay path
-                segs += [(2 * b, fs - 1), (2 * b + 1, fs - 1)]
+        for b, fs in pairs:
+            segs += [(2 * b, fs - 1), (2 * b + 1, fs - 1)]
         offs, Mp, rs = pack_segments([n for _, n in segs])
         mt = Mp // 16
-        i32 = lambda a: torch.tensor(a, dtype=torch.int32, device=dev)
-        row_seg = torch.from_numpy(rs).to(dev)
-        seg_off, seg_len, seg_row = i32(offs), i32([n for _, n in segs]), i32([r for r, _ in segs])
+        if closed:
+            i32 = lambda a: torch.tensor(a, dtype=torch.int32, device=dev)
+            row_seg = torch.from_numpy(rs).to(dev)
+            seg_off, seg_len, seg_row = i32(offs), i32([n for _, n in segs]), i32([r for r, _ in segs])
+        else:                                       # one pinned table, one asynchronous copy: packing, then the slots and their cur
+            ns, nb = _ceil(len(segs), 4), _ceil(len(pairs), 4)
+            tab = np.zeros((Mp + 3 * ns + 2 * nb,), dtype=np.int32)
+            tab[:Mp] = rs
+            for j, col in enumerate((offs, [n for _, n in segs], [r for r, _ in segs])):
+                tab[Mp + j * ns: Mp + j * ns + len(segs)] = col
+            o_b = Mp + 3 * ns
+            tab[o_b: o_b + len(pairs)] = [b for b, _ in pairs]
+            tab[o_b + nb: o_b + nb + len(pairs)] = [fs for _, fs in pairs]
+            pin = torch.from_numpy(tab).pin_memory()
+            self._pinned.append(pin)
+            tab_d = pin.to(dev, non_blocking=True)
+            row_seg, seg_off, seg_len, seg_row = (tab_d[:Mp], tab_d[Mp: Mp + len(segs)], tab_d[Mp + ns: Mp + ns + len(segs)],
+                                                  tab_d[Mp + 2 * ns: Mp + 2 * ns + len(segs)])
+            cur_idx, cur_val = tab_d[o_b: o_b + len(pairs)], tab_d[o_b + nb: o_b + nb + len(pairs)]
+        fp8 = self.self_kv == "fp8"
         z = lambda *sh, dt=torch.float32: torch.zeros(*sh, dtype=dt, device=dev)
         xkt, akt, hkt = D // 32, max(QH, CH) * HEAD_DIM // 32, F // 32
         x = z(Mp, D)
@@ -1140,10 +1187,16 @@ class DecodeSession:
             a = pargs()
             a.q, a.ldq, a.q_off, a.k_off, a.v_off = hb.ptr(qkv), self.nqkv, 0, QH * HEAD_DIM, (QH + KVH) * HEAD_DIM
             a.q_heads, a.kv_heads, a.kv_cap, a.causal = QH, KVH, self.T, 1
-            a.kc, a.vc = hb.ptr(self.k_self[i]), hb.ptr(self.v_self[i])
             a.P, a.p_plane_stride, a.p_ktiles = _plane_set(pa, akt)
-            hb.check(L.dia_dec_prefill_kv(C.byref(a), st), "dia_dec_prefill_kv")
-            hb.check(L.dia_dec_prefill_attn(C.byref(a), st), "dia_dec_prefill_attn(self)")
+            if fp8:                                 # kc == vc == NULL: the e4m3 caches are the only self caches
+                f8 = hb.KvFp8Ptrs(k8=hb.ptr(self.k8_self_all[i]), v8=hb.ptr(self.v8_self_all[i]),
+                                  ks=hb.ptr(self.ks_self_all[i]), vs=hb.ptr(self.vs_self_all[i]))
+                hb.check(L.dia_dec_prefill_kv_fp8(C.byref(a), C.byref(f8), st), "dia_dec_prefill_kv_fp8")
+                hb.check(L.dia_dec_prefill_attn_fp8(C.byref(a), C.byref(f8), st), "dia_dec_prefill_attn_fp8")
+            else:
+                a.kc, a.vc = hb.ptr(self.k_self[i]), hb.ptr(self.v_self[i])
+                hb.check(L.dia_dec_prefill_kv(C.byref(a), st), "dia_dec_prefill_kv")
+                hb.check(L.dia_dec_prefill_attn(C.byref(a), st), "dia_dec_prefill_attn(self)")
             gemm(pa, akt, DL["o"], hb.EPI_RESID_EMIT, out=x, ldo=D, gnext=DL["g_ca"], P=px, p_kt=xkt, ssq_out=True)
             gemm(px, xkt, DL["cq"], hb.EPI_SCALE_STORE, ssq_in=True, out=qc, ldo=CH * HEAD_DIM)
             a = pargs()
@@ -1156,8 +1209,11 @@ class DecodeSession:
             gemm(px, xkt, DL["wi"], hb.EPI_SWIGLU_EMIT, ssq_in=True, P=ph, p_kt=hkt)
             gnext = w.dec_layers[i + 1]["g_sa"] if i + 1 < len(w.dec_layers) else w.dec_norm
             gemm(ph, hkt, DL["wo"], hb.EPI_RESID_EMIT, out=x, ldo=D, gnext=gnext, P=px, p_kt=xkt, ssq_out=True)
-        cur = [fs if fs > 2 else 1 for fs in self.first_steps]
-        self.cur.copy_(torch.tensor(cur, dtype=torch.int32))
+        if closed:
+            cur = [fs if fs > 2 else 1 for fs in self.first_steps]
+            self.cur.copy_(torch.tensor(cur, dtype=torch.int32))
+        else:
+            self.cur.index_copy_(0, cur_idx.long(), cur_val)
 
     # ------------------------------------------------------------------ decode
     def ensure_noise(self, rows: int):
@@ -1294,7 +1350,7 @@ class DecodeSession:
              max_tokens: Optional[int] = None, ignore_eos: bool = False, stream: Optional[torch.cuda.Stream] = None,
              cfg_scale: float = 3.0, temperature: float = 1.3, top_p: float = 0.95, top_k: int = 35,
              attention: str = "auto", stream_cap: Optional[int] = None, adapters=None, cross_kv: str = "bf16",
-             self_kv: str = "bf16") -> "DecodeSession":
+             self_kv: str = "bf16", prompt_prefill: str = "auto") -> "DecodeSession":
         """A session of `slots` PARKED slots for a stream of requests: admit() puts a request into a free slot between two decode
         steps, the step graph (captured once) serves whatever the slots hold, retire() parks a finished one; serve() is the
         driver loop.  Cross caches are sized for texts of `s_cap` bytes (default: the encoder's text_length), the noise buffer for
@@ -1303,7 +1359,9 @@ class DecodeSession:
         stream_cap=N adds the buffers of frame streaming (stream_iter): a staging area of N frames per slot on the device, two
         pinned host copies of it, a side stream for the copies.  None: no such buffer exists and nothing new is launched.
         adapters: a lora.AdapterBank; each Request then names its adapter (Request.adapter), and the admission writes the slot's
-        entry of adapter_of_slot — the step graph is captured once, with the corrections' launches in it."""
+        entry of adapter_of_slot — the step graph is captured once, with the corrections' launches in it.
+        prompt_prefill="batched": an admitted request's audio prompt (more than one frame) is prefilled as one packed batch behind
+        dia_slot_admit and the slot starts at step first_step; "auto" / "replay": it replays through first_step - 1 decode steps."""
         if int(slots) < 1:
             raise ValueError("slots must be >= 1")
         if stream_cap is not None and int(stream_cap) < 1:
@@ -1316,7 +1374,7 @@ class DecodeSession:
         empty = np.zeros((0,), dtype=np.int32)
         s = cls(w, [empty] * int(slots), kv_dtype=kv_dtype, max_tokens=max_tokens, cfg_scale=cfg_scale, temperature=temperature,
                 top_p=top_p, top_k=top_k, ignore_eos=ignore_eos, stream=stream, s_cap=_ceil(cap, 32), attention=attention,
-                adapters=adapters, cross_kv=cross_kv, self_kv=self_kv, _slotted=True)
+                adapters=adapters, cross_kv=cross_kv, self_kv=self_kv, prompt_prefill=prompt_prefill, _slotted=True)
         s.text_cap = cap                           # (the caches hold whole 32-key blocks; requests are held to what was asked for)
         if stream_cap is not None:
             s._init_stream(int(stream_cap))
@@ -1369,7 +1427,8 @@ class DecodeSession:
     def admit(self, requests: Sequence) -> List[int]:
         """Put each request (a Request, or bare text ids with the defaults) into a free slot; returns the slot ids.  Enqueues, on the
         session's stream and without synchronising: the packed encoder pass + cross-K/V of the new texts into their slots' caches,
-        dia_slot_admit (token rows, state machine, sampling values) and the first input embedding of the admitted slots only.
+        dia_slot_admit (token rows, state machine, sampling values), with prompt_prefill="batched" the packed prefill of the admitted
+        requests' audio prompts (cur[b] = first_step[b]), and the first input embedding of the admitted slots only.
         The caches of a re-used slot are not cleared (DESIGN.md "Continuous batching")."""
         if not self.slotted:
             raise hb.DiaHipError("admit() needs a session made by DecodeSession.open()")
@@ -1396,7 +1455,10 @@ class DecodeSession:
             if r.temperature != 0.0:             # row 0 of the slot's noise is this request's first draw
                 g = torch.Generator()
                 g.seed() if r.seed is None else g.manual_seed(int(r.seed))
-            self._live[b] = dict(req=r, first_step=int(pstep), gen=g, rows=0, t0=self._issued)
+            # t0: the session's step count at which this slot stood at step 1.  A prefilled slot starts at step first_step, as if
+            # first_step - 1 steps had been issued for it already (_steps_left, _ensure_slot_noise: row r stays draw number r)
+            skipped = int(pstep) - 1 if self.prompt_prefill == "batched" and int(pstep) > 2 else 0
+            self._live[b] = dict(req=r, first_step=int(pstep), gen=g, rows=0, t0=self._issued - skipped, skip=skipped)
             self._parked.discard(b)
             self.lens[b], self.first_steps[b] = len(r.text_ids), int(pstep)
 
@@ -1428,6 +1490,8 @@ class DecodeSession:
             a.top_k = i32(r.top_k for _, r in pairs)
             a.prefix, a.prefix_ld = dev_tab.data_ptr(), ld
             hb.check(L.dia_slot_admit(C.byref(a), st), "dia_slot_admit")
+            if self.prompt_prefill == "batched":     # behind the token rows, ahead of the embedding: cur[b] = first_step[b] of the prefilled slots
+                self._prompt_prefill(st, [(b, ps) for (b, _), (_, ps) in zip(pairs, pre)])
             ea = self._embed_args()
             ea.slots, ea.n_slots = dev_tab.data_ptr() + 4 * _ceil(n_pre, 4), n
             hb.check(L.dia_embed_tokens(C.byref(ea), st), "dia_embed_tokens")
@@ -1474,7 +1538,7 @@ class DecodeSession:
             if sl["gen"] is None or sl.get("ended"):         # (ended: stream_iter has seen the slot's finished flag)
                 continue
             done = self._issued - sl["t0"]
-            need = min(done + int(n_steps), sl["req"].max_tokens - 1)
+            need = min(done + int(n_steps), sl["req"].max_tokens - 1) - sl.get("skip", 0)      # (prefilled steps drew nothing)
             if need > sl["rows"]:
                 todo.append((b, sl, sl["rows"], need))
         if not todo:

@@ -85,6 +85,12 @@ class Dia:
     # key is quantised as it is appended, no bf16 self cache exists (0.516 of its bytes) and audio prompts replay through the decode
     # step (DecodeSession self_kv="fp8"; needs a bf16 compute_dtype).  "bf16" = the caches as they are
     self_kv = "bf16"
+    # "batched": every such session prefills audio prompts of more than one frame as ONE packed batch wherever it can be asked for —
+    # also when a request is admitted into a slot (generate_stream / stream_frames / generate_batch(slots=N)) and onto
+    # self_kv="fp8" caches — instead of replaying them through the decode step (DecodeSession prompt_prefill="batched"; a session
+    # that cannot serve it — fp32 K/V, adapters, scoring, a compacted or two-plane model — raises ValueError).  "auto" = closed
+    # bf16 sessions prefill, everything else replays; "replay" = always replay
+    prompt_prefill = "auto"
     # HZ: generate(), generate_audio_batch() and stream_audio() return their samples at this rate, converted from the codec's
     # 44.1 kHz by the native codec's resampler (DeviceCodec.resample / resample_stream); None = the codec's rate, as it comes
     output_sample_rate: Optional[int] = None
@@ -271,7 +277,7 @@ class Dia:
         bank = self._bank_for(adapters)
         t0 = time.time()
         with torch.cuda.device(self.device):
-            s = DecodeSession(self.model, ids, kv_dtype=self._kv_dtype(), cross_kv=self.cross_kv, self_kv=self.self_kv, max_tokens=max_tokens, cfg_scale=cfg_scale,
+            s = DecodeSession(self.model, ids, kv_dtype=self._kv_dtype(), cross_kv=self.cross_kv, self_kv=self.self_kv, prompt_prefill=self.prompt_prefill, max_tokens=max_tokens, cfg_scale=cfg_scale,
                               temperature=temperature, top_p=top_p, top_k=top_k, seeds=seeds, ignore_eos=ignore_eos,
                               audio_prompts=audio_prompts, adapters=bank, adapter_ids=adapters if bank is not None else None)
             try:
@@ -345,7 +351,7 @@ class Dia:
             raise ValueError("score_batch: one adapter entry per text")
         bank = self._bank_for(adapters)
         with torch.cuda.device(self.device):
-            s = DecodeSession(self.model, ids, kv_dtype=self._kv_dtype(), cross_kv=self.cross_kv, self_kv=self.self_kv, max_tokens=mt, cfg_scale=cfg_scale, temperature=0.0,
+            s = DecodeSession(self.model, ids, kv_dtype=self._kv_dtype(), cross_kv=self.cross_kv, self_kv=self.self_kv, prompt_prefill=self.prompt_prefill, max_tokens=mt, cfg_scale=cfg_scale, temperature=0.0,
                               teacher_tokens=rows, audio_prompts=prompts, score=True, adapters=bank,
                               adapter_ids=adapters if bank is not None else None)
             try:
@@ -391,7 +397,7 @@ class Dia:
             s_cap = max(32, max(len(r.text_ids) for r in reqs))
         with torch.cuda.device(self.device):
             s = DecodeSession.open(self.model, min(int(slots), len(reqs)), s_cap=min(int(s_cap), self.config.data.text_length),
-                                   kv_dtype=self._kv_dtype(), cross_kv=self.cross_kv, self_kv=self.self_kv, max_tokens=cap, ignore_eos=ignore_eos, adapters=bank)
+                                   kv_dtype=self._kv_dtype(), cross_kv=self.cross_kv, self_kv=self.self_kv, prompt_prefill=self.prompt_prefill, max_tokens=cap, ignore_eos=ignore_eos, adapters=bank)
             try:
                 for i, res in s.serve_iter(reqs, poll=poll):
                     yield i, codes_for_codec(res.codes, self.config)
@@ -426,7 +432,7 @@ class Dia:
             s_cap = max(32, max(len(r.text_ids) for r in reqs))
         with torch.cuda.device(self.device):
             s = DecodeSession.open(self.model, min(int(slots), len(reqs)), s_cap=min(int(s_cap), self.config.data.text_length),
-                                   kv_dtype=self._kv_dtype(), cross_kv=self.cross_kv, self_kv=self.self_kv, max_tokens=cap, ignore_eos=ignore_eos,
+                                   kv_dtype=self._kv_dtype(), cross_kv=self.cross_kv, self_kv=self.self_kv, prompt_prefill=self.prompt_prefill, max_tokens=cap, ignore_eos=ignore_eos,
                                    stream_cap=4 * int(chunk) if stream_cap is None else int(stream_cap), adapters=bank)
             try:
                 yield from s.stream_iter(reqs, chunk=chunk, lag=lag)

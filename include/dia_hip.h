@@ -861,6 +861,19 @@ int dia_attn_self_fp8(const dia_attn_args* a, const dia_kv_fp8_ptrs* p, void* st
  * DIA_E_ARG unless the engine has one-plane bf16 K/V (DIA_KV_BF16) with blocked V and T % 32 == 0.  Independent of
  * dia_engine_set_cross_fp8: either, both or neither.  NULL = dia_attn over the bf16 caches, as without the call. */
 int dia_engine_set_self_fp8(dia_engine* e, const dia_kv_fp8_ptrs* layers /* host [n_layer], copied */);
+/* The batched prompt prefill onto e4m3 self caches (csrc/prefill.hip; DESIGN.md "Prompt prefill at admission and onto fp8 caches"):
+ * dia_dec_prefill_kv / dia_dec_prefill_attn (causal) with *p in the place of kc / vc, same packing (row_seg / seg_off / seg_len /
+ * seg_row, rows % 32 == 0).  dia_dec_prefill_kv_fp8 appends every packed row r of a segment to key slot r of the segment's cache row,
+ * quantised by the step's own arithmetic (fp32 RoPE(k) at position r + 1 and fp32 v, amax over the 128 dims, power-of-two scale,
+ * e4m3 bytes held finite): the bytes and scales dia_attn_self_fp8 would have written at cur = r + 1 for the same qkv row.  No
+ * byte or scale outside key slots [0, seg_len) of the listed cache rows changes; padding rows write nothing.
+ * dia_dec_prefill_attn_fp8 is the causal dia_dec_prefill_attn with 8-byte fragments and the scales folded in behind the MFMAs:
+ * bit for bit its output over bf16 caches holding the dequantised values.  The cross call of a prefill stays
+ * dia_dec_prefill_attn (the cross caches are bf16 under either cache mode).  Refused with DIA_E_ARG before any launch: a NULL
+ * argument or fp8 pointer, kc / vc not NULL, causal == 0, kv_cap % 32 != 0, k8 / v8 not aligned to 16 bytes or ks / vs to 4, and
+ * what dia_dec_prefill_kv / _attn refuse.  Appended: no struct grew. */
+int dia_dec_prefill_kv_fp8(const dia_dec_prefill_args* a, const dia_kv_fp8_ptrs* p, void* stream);
+int dia_dec_prefill_attn_fp8(const dia_dec_prefill_args* a, const dia_kv_fp8_ptrs* p, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Codec (csrc/codec.hip; DESIGN.md "Codec"): the Descript Audio Codec decoder, codes [B, 9, T] -> waveform, in exact fp32 on the
