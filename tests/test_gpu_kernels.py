@@ -505,6 +505,7 @@ def test_enc_attn_packed_batch():
             worst = max(worst, (out[o: o + Lb, h] - attn_ref(q[:, h], k[:, h], v[:, h])).abs().max().item())
     assert worst <= 2e-5, worst
     pad = torch.from_numpy(rb < 0).to(d)
+    assert torch.isfinite(out[~pad]).all()                    # (max() above keeps `worst` when an error is NaN)
     assert (out[pad] == sentinel).all()                       # padding rows are not written
     # the three planes reproduce fp32 K exactly (k rows of utterance 0, head 1)
     kk = (kp[0].float() + kp[1].float() + kp[2].float())[1, : lens[0]]
