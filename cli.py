@@ -12,7 +12,8 @@ the native DAC decoder (dia_hip/codec.py) from a DAC checkpoint: ``--output`` th
 With a checkpoint that holds the encoder too, ``--audio-prompt voice.wav`` is encoded by the same native codec, and
 ``--encode-audio IN.wav --codes-output out.npy`` (build-only) writes the file's codes ``[T, 9]`` and exits; no model is loaded.
 A prompt file at any sample rate is converted to the codec's 44100 Hz by the native resampler, and ``--output-rate HZ`` (build-only)
-converts ``--output`` from 44100 Hz to HZ the same way.
+converts ``--output`` from 44100 Hz to HZ the same way.  ``--codec-precision {fp32,bf16x2,bf16}`` (build-only, with ``--codec-path``)
+picks the decoder's arithmetic: the exact fp32 kernel, or bf16 MFMA operands in two planes / one; encoding stays fp32.
 ``--score-codes FILE.npy`` (build-only) generates nothing: it prints the teacher-forced log-likelihood of the given codes under
 the loaded checkpoint (Dia.score) as one JSON line.
 """
@@ -58,6 +59,10 @@ def build_parser() -> argparse.ArgumentParser:
                    "native codec: --output is decoded on the device by this library, the third-party dac package is not loaded "
                    "(as with --no-dac), and --stream-chunk N may be combined with --output; a checkpoint that holds the encoder "
                    "also encodes an --audio-prompt file and serves --encode-audio")
+    g.add_argument("--codec-precision", type=str, default=None, choices=["fp32", "bf16x2", "bf16"], help="(build-only) precision of the "
+                   "native codec's decoder convolutions (needs --codec-path): fp32 (default) is the exact kernel; bf16x2 runs them on the "
+                   "bf16 MFMA with two planes per operand (errors near the 16-bit PCM step), bf16 with one (lossy, for previews); the "
+                   "encode side stays fp32 in every mode")
     g.add_argument("--encode-audio", type=str, default=None, metavar="IN.wav", help="(build-only) encode this audio file with the native "
                    "codec and write its codes [T, 9] to --codes-output as .npy, then exit: needs --codec-path, loads no model, and the "
                    "text argument is ignored (44.1 kHz; another rate needs torchaudio)")
@@ -289,6 +294,8 @@ def main(argv=None) -> int:
                      "(--output is allowed with --codec-path).")
     if args.output_rate is not None and (args.output_rate < 1 or not args.codec_path or not args.output):
         parser.error("--output-rate HZ needs HZ > 0, --output and --codec-path (the native codec converts the rate).")
+    if args.codec_precision is not None and not args.codec_path:
+        parser.error("--codec-precision belongs to the native codec: it needs --codec-path FILE.")
     if args.no_dac and args.output and not args.codec_path:
         parser.error("--output needs the audio codec; use --codes-output with --no-dac.")
     if args.codec_path:
@@ -327,9 +334,9 @@ def main(argv=None) -> int:
         if args.adapter_path:
             print("LoRA adapters merged successfully.")
         if args.codec_path:
-            dia.load_codec(args.codec_path)
+            dia.load_codec(args.codec_path, precision=args.codec_precision or "fp32")
             dia.output_sample_rate = args.output_rate
-            print(f"Native codec loaded from {args.codec_path}")
+            print(f"Native codec loaded from {args.codec_path}" + (f" ({args.codec_precision} decoder)" if args.codec_precision else ""))
         if bank_dirs:
             dia.load_adapters(bank_dirs)
             print(f"LoRA adapters loaded unmerged: {sorted(bank_dirs)}")

@@ -29,6 +29,7 @@ EXPORTS = (
     "dia_kv_quantize_fp8", "dia_attn_cross_fp8", "dia_engine_set_cross_fp8",
     "dia_attn_self_fp8", "dia_engine_set_self_fp8", "dia_dec_prefill_kv_fp8", "dia_dec_prefill_attn_fp8",
     "dia_codec_embed", "dia_codec_conv", "dia_codec_convt", "dia_codec_convs", "dia_codec_quantize",
+    "dia_codec_conv_bf16", "dia_codec_convt_bf16",
     "dia_resample",
     "dia_seg_mlp", "dia_seg_workspace_bytes", "dia_seg_workspace_control_bytes", "dia_seg_slots", "dia_seg_supported", "dia_seg_error",
 )

@@ -321,6 +321,46 @@ def convt_layout(w: torch.Tensor) -> torch.Tensor:
     return out.contiguous()
 
 
+PRECISIONS = {"fp32": 0, "bf16": 1, "bf16x2": 2}                # DeviceCodec(precision=...) -> bf16 planes of the decoder's MFMA operands
+
+
+def precision_planes(precision) -> int:
+    """0 for "fp32" (the exact kernel), 1 for "bf16", 2 for "bf16x2"; anything else is refused by name"""
+    if not isinstance(precision, str) or precision not in PRECISIONS:
+        raise ValueError(f"codec precision {precision!r} is not one of 'fp32', 'bf16x2', 'bf16'")
+    return PRECISIONS[precision]
+
+
+def bf16_planes(w: torch.Tensor, planes: int) -> torch.Tensor:
+    """fp32 -> [planes, ...] bf16: hi = bf16(w) (round to nearest even) and, for planes = 2, lo = bf16(w - hi), the residual exact
+    in fp32: the split k_codec_conv_bf applies to its staged inputs"""
+    if planes not in (1, 2):
+        raise ValueError(f"planes = {planes} is not 1 or 2")
+    w = w.to(torch.float32)
+    hi = w.to(torch.bfloat16)
+    return torch.stack([hi, (w - hi.to(torch.float32)).to(torch.bfloat16)][:planes])
+
+
+def _group8(p: torch.Tensor) -> torch.Tensor:
+    """[..., C_in, Cp] -> [..., Ci / 8, Cp, 8] with C_in zero-filled to Ci, the next multiple of 16 (the kernel's channel chunk)"""
+    ci, cp = p.shape[-2:]
+    cpad = (ci + 15) // 16 * 16
+    out = torch.zeros(*p.shape[:-2], cpad, cp, dtype=p.dtype)
+    out[..., :ci, :] = p
+    return out.reshape(*p.shape[:-2], cpad // 8, 8, cp).transpose(-1, -2).contiguous()
+
+
+def conv_layout_bf16(w: torch.Tensor, planes: int) -> torch.Tensor:
+    """[C_out, C_in, k] -> bf16 [planes][k][Ci / 8][Cp][8]: the planes of conv_layout(w) with 8 input channels contiguous per
+    (tap, output channel); Ci = C_in rounded up to 16, Cp = C_out rounded up to 32, zero-filled"""
+    return _group8(bf16_planes(conv_layout(w), planes))
+
+
+def convt_layout_bf16(w: torch.Tensor, planes: int) -> torch.Tensor:
+    """[C_in, C_out, 2 s] -> bf16 [planes][s][2][Ci / 8][Cp][8]: the planes of convt_layout(w), grouped as conv_layout_bf16"""
+    return _group8(bf16_planes(convt_layout(w), planes))
+
+
 def convs_layout(w: torch.Tensor) -> torch.Tensor:
     """strided convolution [C_out, C_in, 2 s] -> fp32 [2][C_in * s][Cp]: out[t][ci * s + r][co] = w[co][ci][r + t s], the weight of
     x[ci][(o + t) s + r - s / 2] in output o"""
@@ -504,6 +544,8 @@ def _fns():
     L.dia_codec_convt.argtypes = [C.POINTER(CodecConvArgs), C.c_void_p]
     L.dia_codec_convs.argtypes = [C.POINTER(CodecConvArgs), C.c_void_p]
     L.dia_codec_quantize.argtypes = [C.POINTER(CodecQuantizeArgs), C.c_void_p]
+    L.dia_codec_conv_bf16.argtypes = [C.POINTER(CodecConvArgs), C.c_int, C.c_void_p]
+    L.dia_codec_convt_bf16.argtypes = [C.POINTER(CodecConvArgs), C.c_int, C.c_void_p]
     return L
 
 
@@ -526,9 +568,11 @@ def codec_embed(codes: torch.Tensor, tables: torch.Tensor, bias: torch.Tensor, l
 
 def codec_conv(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, *, c_out: int, k: int = 7, dilation: int = 1, stride: int = 0,
                alpha: Optional[torch.Tensor] = None, inv: Optional[torch.Tensor] = None, res: Optional[torch.Tensor] = None,
-               tanh: bool = False, lens: Optional[torch.Tensor] = None) -> torch.Tensor:
+               tanh: bool = False, lens: Optional[torch.Tensor] = None, precision: str = "fp32") -> torch.Tensor:
     """dia_codec_conv (stride 0) / dia_codec_convt (stride s) on device tensors: x fp32 [B, C_in, T], w in the library's layout ->
-    y fp32 [B, c_out, T (* s)]; positions beyond a row's length stay 0"""
+    y fp32 [B, c_out, T (* s)]; positions beyond a row's length stay 0.  precision "bf16" / "bf16x2": the _bf16 entry points, w
+    from conv_layout_bf16 / convt_layout_bf16 with 1 / 2 planes"""
+    planes = precision_planes(precision)
     B, cin, T = x.shape
     To = T * (stride or 1)
     y = torch.zeros(B, c_out, To, dtype=torch.float32, device=x.device)
@@ -537,6 +581,10 @@ def codec_conv(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, *, c_out: i
                       dilation=0 if stride else dilation, stride=stride, tanh_out=int(tanh))
     L = _fns()
     st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    if planes:
+        hb.check((L.dia_codec_convt_bf16 if stride else L.dia_codec_conv_bf16)(C.byref(a), planes, st),
+                 "dia_codec_convt_bf16" if stride else "dia_codec_conv_bf16")
+        return y
     hb.check((L.dia_codec_convt if stride else L.dia_codec_conv)(C.byref(a), st), "dia_codec_convt" if stride else "dia_codec_conv")
     return y
 
@@ -576,10 +624,17 @@ class DeviceCodec:
     malformed one, still decodes: `encoder_error` keeps what encode() will raise.
 
     decode() cuts every utterance into windows of at most `window` frames with context_frames(cfg) frames of context on each side,
-    runs the windows of all rows as rows of batched launches (each with its own length) and keeps the interiors."""
+    runs the windows of all rows as rows of batched launches (each with its own length) and keeps the interiors.
+
+    precision: "fp32" (default) decodes on the exact-fp32 kernel.  "bf16x2" and "bf16" run the DECODER's convolutions on the bf16
+    MFMA with two planes / one plane per operand (DESIGN.md "Codec: bf16 modes"): only that mode's bf16 weight image is uploaded
+    for the decoder, activations stay fp32.  The encode side (encoder, quantiser) and the embedding stay fp32 in every mode: the
+    codes are an arg-min and must not move."""
 
     def __init__(self, state, device: Optional[torch.device] = None, cfg: Optional[CodecConfig] = None, window: int = 128,
-                 workspace_bytes: int = 1 << 30):
+                 workspace_bytes: int = 1 << 30, precision: str = "fp32"):
+        self.planes = precision_planes(precision)
+        self.precision = precision
         if cfg is not None:
             state = (cfg, state)
         self.cfg, whole, meta = _open_codec_state(state)
@@ -602,7 +657,10 @@ class DeviceCodec:
         for L in layer_plan(cfg):
             w = fold_weight_norm(sd[L["key"] + ".weight_g"], sd[L["key"] + ".weight_v"])
             D = dict(L)
-            D["w"] = (conv_layout(w) if L["kind"] == "conv" else convt_layout(w)).to(dev)
+            if self.planes:                                     # a reduced mode holds its own image and no fp32 one
+                D["w_bf16"] = (conv_layout_bf16 if L["kind"] == "conv" else convt_layout_bf16)(w, self.planes).to(dev)
+            else:
+                D["w"] = (conv_layout(w) if L["kind"] == "conv" else convt_layout(w)).to(dev)
             D["b"] = sd[L["key"] + ".bias"].to(torch.float32).to(dev)
             if L["snake"]:
                 al = sd[L["snake"] + ".alpha"]
@@ -675,6 +733,13 @@ class DeviceCodec:
         """every job (codes [n_codebooks, n], n <= wmax) decoded as an utterance of its own: rows of one chain of batched launches"""
         cfg, lib = self.cfg, _fns()
         out: List[np.ndarray] = []
+        if self.planes:
+            planes = self.planes
+            conv = lambda a, st: lib.dia_codec_conv_bf16(a, planes, st)
+            convt = lambda a, st: lib.dia_codec_convt_bf16(a, planes, st)
+            wkey, sfx = "w_bf16", "_bf16"
+        else:
+            conv, convt, wkey, sfx = lib.dia_codec_conv, lib.dia_codec_convt, "w", ""
         with torch.cuda.device(self.device):
             st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
             for g0 in range(0, len(jobs), self.rows_cap):
@@ -700,19 +765,19 @@ class DeviceCodec:
                         e0.record()
                     if r not in stage_lens:
                         stage_lens[r] = lens * r
-                    a = CodecConvArgs(w=hb.ptr(L["w"]), bias=hb.ptr(L["b"]), alpha=hb.ptr(L.get("alpha")), inv=hb.ptr(L.get("inv")),
+                    a = CodecConvArgs(w=hb.ptr(L[wkey]), bias=hb.ptr(L["b"]), alpha=hb.ptr(L.get("alpha")), inv=hb.ptr(L.get("inv")),
                                       lens=hb.ptr(stage_lens[r]), B=J, T=Tg * r, C_in=L["cin"], C_out=L["cout"], ldx=W * r,
                                       tanh_out=int(bool(L.get("tanh"))))
                     if L["kind"] == "convt":
                         a.x, a.y, a.ldy, a.stride = hb.ptr(cur), hb.ptr(oth), W * r * L["s"], L["s"]
-                        hb.check(lib.dia_codec_convt(C.byref(a), st), "dia_codec_convt")
+                        hb.check(convt(C.byref(a), st), "dia_codec_convt" + sfx)
                         cur, oth = oth, cur
                     elif L.get("res"):                         # the residual unit's 1x1: x is the k-7 output, the sum lands on the unit's input
                         a.x, a.y, a.res, a.ldx, a.ldy, a.k, a.dilation = hb.ptr(oth), hb.ptr(cur), hb.ptr(cur), W * r, W * r, 1, 1
-                        hb.check(lib.dia_codec_conv(C.byref(a), st), "dia_codec_conv")
+                        hb.check(conv(C.byref(a), st), "dia_codec_conv" + sfx)
                     else:
                         a.x, a.y, a.ldy, a.k, a.dilation = hb.ptr(cur), hb.ptr(oth), W * r, L["k"], L["d"]
-                        hb.check(lib.dia_codec_conv(C.byref(a), st), "dia_codec_conv")
+                        hb.check(conv(C.byref(a), st), "dia_codec_conv" + sfx)
                         if not L["snake"] or L.get("tanh"):    # first and last layer: the result is the new stream
                             cur, oth = oth, cur
                     if self.layer_events is not None:

@@ -94,6 +94,10 @@ class Dia:
     # HZ: generate(), generate_audio_batch() and stream_audio() return their samples at this rate, converted from the codec's
     # 44.1 kHz by the native codec's resampler (DeviceCodec.resample / resample_stream); None = the codec's rate, as it comes
     output_sample_rate: Optional[int] = None
+    # the native codec's DECODER precision that codec_path= on the loaders asks load_codec() for: "fp32" (the exact kernel), "bf16x2"
+    # or "bf16" (bf16 MFMA operands in two planes / one; DESIGN.md "Codec: bf16 modes").  The encode side is fp32 in every mode.
+    # load_codec() sets it, on the instance, to the mode it loaded
+    codec_precision = "fp32"
 
     def __init__(self, config: DiaConfig, compute_dtype: Union[str, ComputeDtype] = ComputeDtype.FLOAT32,
                  device: Optional[torch.device] = None):
@@ -192,7 +196,7 @@ class Dia:
         if load_dac:
             dia._load_dac_model()
         if codec_path is not None:
-            dia.load_codec(codec_path)
+            dia.load_codec(codec_path, precision=dia.codec_precision)
         return dia
 
     @classmethod
@@ -213,17 +217,21 @@ class Dia:
         if load_dac:
             dia._load_dac_model()
         if codec_path is not None:
-            dia.load_codec(codec_path)
+            dia.load_codec(codec_path, precision=dia.codec_precision)
         return dia
 
-    def load_codec(self, path_or_state, window: int = 128):
+    def load_codec(self, path_or_state, window: int = 128, precision: str = "fp32"):
         """Set the native DAC codec (dia_hip/codec.py, csrc/codec.hip) on this instance: a DAC ``.pth`` / bare state dict, as a
         path or in memory.  generate() then returns waveforms and generate_audio_batch / stream_audio work; the third-party
         ``dac`` package is not needed.  A missing or unexpected decoder / quantizer key is refused by name.  A checkpoint that
-        also holds the encoder makes load_audio() / encode_audio() and file prompts work; one without still decodes."""
-        from .codec import DeviceCodec
+        also holds the encoder makes load_audio() / encode_audio() and file prompts work; one without still decodes.
+        precision: "fp32", "bf16x2" or "bf16" for the decoder's convolutions; any other value is refused by name.  Voice prompts
+        are encoded in fp32 in every mode."""
+        from .codec import DeviceCodec, precision_planes
+        precision_planes(precision)
         with torch.cuda.device(self.device):
-            self.codec = DeviceCodec(path_or_state, self.device, window=window)
+            self.codec = DeviceCodec(path_or_state, self.device, window=window, precision=precision)
+        self.codec_precision = precision
         return self.codec
 
     def _load_dac_model(self):

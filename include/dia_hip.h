@@ -956,6 +956,26 @@ typedef struct {
  * The residual stays on chip between the stages. */
 int dia_codec_quantize(const dia_codec_quantize_args* a, void* stream);
 
+/* Reduced-precision decoder convolutions (csrc/codec_bf16.hip; DESIGN.md "Codec: bf16 modes").  Two more entry points; no struct
+ * grew and nothing older changed.  dia_codec_conv_bf16 / dia_codec_convt_bf16 are dia_codec_conv / dia_codec_convt over the same
+ * dia_codec_conv_args (fp32 activations in and out, the same `lens` rules, bias, residual, tanh) on v_mfma_f32_32x32x16_bf16:
+ * only the MFMA operands are reduced.  planes = 1 ("bf16"): weight and staged input (after Snake, computed in fp32 as above) are
+ * rounded to bf16, round-to-nearest-even, and one product w_hi x_hi is formed.  planes = 2 ("bf16x2"): both operands also carry
+ * lo = bf16(v - hi) (the subtraction is exact in fp32) and the products w_hi x_hi, w_hi x_lo, w_lo x_hi are accumulated in that
+ * order per (16-channel chunk, tap); w_lo x_lo is dropped: at most 2^-16 of sum |w| |x| (a lo is at most 2^-8 of its value), measured
+ * 2^-17.6 of it for sums of a dozen terms down to 2^-22 for the 5376 of the widest layers.  Accumulation is fp32.  The order depends on nothing
+ * but (channel chunk, tap, product), so rows, windows and streamed chunks are bitwise reproducible within a mode.
+ *
+ * a->w points at a bf16 image the host prepares from the float64-folded fp32 weight (dia_hip/codec.py conv_layout_bf16 /
+ * convt_layout_bf16), 16-byte aligned; Ci = C_in rounded up to 16, Cp = C_out rounded up to 32, both zero-filled; 8 input channels
+ * contiguous per (tap, output channel), so that a lane's A fragment is one 16-byte read:
+ *   dia_codec_conv_bf16   w bf16 [planes][k][Ci / 8][Cp][8]       w[p][j][g][co][u] = plane_p(weight[co][8 g + u][j])
+ *   dia_codec_convt_bf16  w bf16 [planes][s][2][Ci / 8][Cp][8]    w[p][r][t][g][co][u] = plane_p(weight[8 g + u][co][r + t s])
+ * plane_0 = hi, plane_1 = lo.  Refused with DIA_E_ARG before any launch: planes not 1 or 2, and what dia_codec_conv /
+ * dia_codec_convt refuse. */
+int dia_codec_conv_bf16(const dia_codec_conv_args* a, int planes, void* stream);
+int dia_codec_convt_bf16(const dia_codec_conv_args* a, int planes, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Resampler (csrc/resample.hip; DESIGN.md "Resampler"): polyphase sample-rate conversion of a batch of rows in ONE launch.  One
  * new entry point and one new struct; nothing older changed.
