@@ -1,6 +1,7 @@
 // Codec: the Descript Audio Codec in exact fp32.  Decoder: dia_codec_embed / dia_codec_conv / dia_codec_convt (DESIGN.md "Codec");
 // encoder: the same dia_codec_conv plus dia_codec_convs (strided and k-3 forms) and dia_codec_quantize, the residual VQ search
-// (DESIGN.md "Codec: encode side").
+// (DESIGN.md "Codec: encode side").  The argument checks, the geometry of every form, the row prologue, the Snake step and the
+// epilogue are csrc/codec_conv.hpp's, shared with csrc/codec_bf16.hip.
 //
 // One implicit-GEMM kernel serves every convolution of the decoder.  M = output channels, N = time, K = input channels x taps, on
 // v_mfma_f32_32x32x2_f32: f32 operands, f32 accumulate, bit for bit an fmaf chain, so no plane splitting is needed for reference
@@ -25,33 +26,17 @@
 //
 // LDS: 14 KiB of input rows + 42 KiB of weights = 56 KiB static, two workgroups per CU.  Row strides are 32 mod 64 floats, so the
 // two lane halves (k = 0 / 1) of one ds_read hit disjoint banks.
-#include "common.hpp"
-#include "../../include/dia_hip.h"
-#include "errors.hpp"
+#include "codec_conv.hpp"
 #include "launch.hpp"
-#include <cstdarg>
-#include <cstdio>
 
 namespace {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-
-constexpr int NT = 128;                // positions per workgroup
-constexpr int KC = 16;                 // input channels per staged chunk
-constexpr int MAXTAPS = 7;
-constexpr int MAXHALO = 54;            // k 7, dilation 9: 6 * 9
 constexpr int XS = 224;                // staged input row stride: >= NT + MAXHALO, 32 mod 64
 constexpr int WS = 96;                 // staged weight row stride: >= 64, 32 mod 64
 static_assert(XS >= NT + MAXHALO && XS % 64 == 32 && WS >= 64 && WS % 64 == 32, "LDS strides");
 
-struct ConvK {
-  const float* x; const float* w; const float* bias; const float* alpha; const float* inv; const float* res; float* y;
-  const int* lens;
-  int T, C_in, C_out, Cp, ldx, ldy;
-  int ntaps, tap_step, tap_off0;       // tap j reads input position n + tap_off0 + j * tap_step
-  int lo, width;                       // smallest tap offset (<= 0); staged positions per row = NT + largest - smallest
-  int ostride, phases, pad, extra;     // o = n * ostride + phase - pad; n runs over [0, len + extra)
-  int tanh_out;
+struct ConvK : ConvArgs {
+  const float* w;
   int xstride;                         // STRIDED only: s; C_in then counts the staged rows, C_in of the layer x s
 };
 
@@ -63,8 +48,8 @@ __global__ __launch_bounds__(256) void k_codec_conv(ConvK p) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int r = lane & 31, h = lane >> 5;
   const int wm = wave % MW, wn = wave / MW;
-  const int b = blockIdx.z / p.phases, ph = blockIdx.z - b * p.phases;
-  const int lin = p.lens ? min(max(p.lens[b], 0), p.T) : p.T;    // input positions of this row
+  const ConvRow row = conv_row(p);
+  const int b = row.b, ph = row.ph, lin = row.len;               // lin: input positions of this row
   const int len = STRIDED ? lin / p.xstride : lin;               // positions n of this row
   const int n0 = blockIdx.x * NT;
   if (n0 >= len + p.extra) return;                               // workgroup-uniform
@@ -94,10 +79,7 @@ __global__ __launch_bounds__(256) void k_codec_conv(ConvK p) {
         float v = 0.f;
         if (row && i >= 0 && i < lin) {
           v = xr[i];
-          if (p.alpha) {
-            const float s = sinf(al * v);                        // accurate sinf: alpha x is not range-limited
-            v = v + s * s * iv;
-          }
+          if (p.alpha) v = snake(v, al, iv);
         }
         xs[ci * XS + c] = v;
       }
@@ -132,24 +114,7 @@ __global__ __launch_bounds__(256) void k_codec_conv(ConvK p) {
     for (int i = 0; i < NACC; ++i) tot[i] += acc[i];
   }
 
-  const long out_len = (long)len * p.ostride;
-#pragma unroll
-  for (int i = 0; i < NACC; ++i) {
-    const int n = n0 + wn * WN + i * 32 + r;
-    const long o = (long)n * p.ostride + ph - p.pad;
-    const bool col = n < len + p.extra && o >= 0 && o < out_len;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-      const int co = co0 + wm * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
-      if (col && co < p.C_out) {
-        const long at = ((long)b * p.C_out + co) * p.ldy + o;
-        float v = tot[i][e] + p.bias[co];
-        if (p.res) v += p.res[at];
-        if (p.tanh_out) v = tanhf(v);
-        p.y[at] = v;
-      }
-    }
-  }
+  conv_epilogue(p, tot, row, len, n0 + wn * WN + r, co0 + wm * 32, h);
 }
 
 constexpr int ET = 16;                 // frames per embedding workgroup
@@ -267,99 +232,42 @@ __global__ __launch_bounds__(256) void k_codec_quantize(QuantK p) {
   }
 }
 
-int codec_fail(const char* fmt, ...) {
-  char buf[224];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof buf, fmt, ap);
-  va_end(ap);
-  return dia_fail(DIA_E_ARG, buf);
-}
-
-// what dia_codec_conv and dia_codec_convt share; 0 when clean
-int conv_common(const dia_codec_conv_args* a, const char* fn, int phases, int out_per_in, int in_per_out = 1) {
-  if (!a) return codec_fail("%s: null argument", fn);
-  if (!a->x || !a->w || !a->bias || !a->y) return codec_fail("%s: null pointer (x, w, bias and y are required)", fn);
-  if ((a->alpha == nullptr) != (a->inv == nullptr)) return codec_fail("%s: alpha and inv go together", fn);
-  if ((const void*)a->x == (const void*)a->y) return codec_fail("%s: y must not be x", fn);
-  if (((uintptr_t)a->w & 15) != 0) return codec_fail("%s: w must be 16-byte aligned", fn);
-  if (a->C_in < 1 || a->C_in > DIA_CODEC_MAX_CHANNELS || a->C_out < 1 || a->C_out > DIA_CODEC_MAX_CHANNELS)
-    return codec_fail("%s: C_in = %d / C_out = %d outside [1, %d]", fn, a->C_in, a->C_out, DIA_CODEC_MAX_CHANNELS);
-  if (a->T < 1 || a->T > DIA_CODEC_MAX_T) return codec_fail("%s: T = %d outside [1, %d]", fn, a->T, DIA_CODEC_MAX_T);
-  if (a->B < 1 || (long)a->B * phases > 65535) return codec_fail("%s: B = %d outside [1, %d]", fn, a->B, 65535 / phases);
-  if (a->ldx < a->T) return codec_fail("%s: ldx = %d below T = %d", fn, a->ldx, a->T);
-  if ((long)a->ldy < (long)a->T * out_per_in / in_per_out)
-    return codec_fail("%s: ldy = %d below the output length %ld", fn, a->ldy, (long)a->T * out_per_in / in_per_out);
-  if (a->tanh_out != 0 && a->tanh_out != 1) return codec_fail("%s: tanh_out = %d is not 0 or 1", fn, a->tanh_out);
-  return 0;
-}
-
-int conv_launch(const dia_codec_conv_args* a, ConvK k, void* stream, const char* name, bool strided = false) {
-  k.x = a->x; k.w = a->w; k.bias = a->bias; k.alpha = a->alpha; k.inv = a->inv; k.res = a->res; k.y = a->y; k.lens = a->lens;
-  k.T = a->T; k.C_in = a->C_in; k.C_out = a->C_out; k.Cp = (a->C_out + 31) / 32 * 32; k.ldx = a->ldx; k.ldy = a->ldy;
-  k.tanh_out = a->tanh_out;
-  if (strided) {                                                 // K runs over C_in x s staged rows, n over the T / s outputs
-    k.C_in = a->C_in * k.xstride;
-    const int nbs = (a->T / k.xstride + NT - 1) / NT;
-    if (a->C_out <= 32)
-      dia_launch<k_codec_conv<1, true>>(dim3(nbs, 1, a->B), dim3(256), 0, (hipStream_t)stream, k);
-    else
-      dia_launch<k_codec_conv<2, true>>(dim3(nbs, (a->C_out + 63) / 64, a->B), dim3(256), 0, (hipStream_t)stream, k);
-    return dia_check_launch(name);
+// k: the geometry its form has set; xstride != 0: the strided form, where K runs over C_in x s staged rows and n over the T / s outputs
+int conv_launch(const dia_codec_conv_args* a, ConvK k, int xstride, void* stream, const char* name) {
+  conv_fill(a, k);
+  k.w = a->w; k.xstride = xstride;
+  if (xstride) k.C_in = a->C_in * xstride;
+  const dim3 grid = conv_grid(a, k, xstride ? a->T / xstride : a->T);
+  hipStream_t st = (hipStream_t)stream;
+  if (xstride) {
+    if (conv_narrow(a)) dia_launch<k_codec_conv<1, true>>(grid, dim3(256), 0, st, k);
+    else dia_launch<k_codec_conv<2, true>>(grid, dim3(256), 0, st, k);
+  } else {
+    if (conv_narrow(a)) dia_launch<k_codec_conv<1>>(grid, dim3(256), 0, st, k);
+    else dia_launch<k_codec_conv<2>>(grid, dim3(256), 0, st, k);
   }
-  const int nb = (a->T + k.extra + NT - 1) / NT;
-  if (a->C_out <= 32)
-    dia_launch<k_codec_conv<1>>(dim3(nb, 1, a->B * k.phases), dim3(256), 0, (hipStream_t)stream, k);
-  else
-    dia_launch<k_codec_conv<2>>(dim3(nb, (a->C_out + 63) / 64, a->B * k.phases), dim3(256), 0, (hipStream_t)stream, k);
   return dia_check_launch(name);
 }
 
 }  // namespace
 
 extern "C" int dia_codec_conv(const dia_codec_conv_args* a, void* stream) {
-  if (int rc = conv_common(a, "dia_codec_conv", 1, 1)) return rc;
-  if (a->k != 1 && a->k != 7) return codec_fail("dia_codec_conv: kernel size %d is not 1 or 7", a->k);
-  if (a->dilation != 1 && a->dilation != 3 && a->dilation != 9) return codec_fail("dia_codec_conv: dilation %d is not 1, 3 or 9", a->dilation);
-  if (a->k == 1 && a->dilation != 1) return codec_fail("dia_codec_conv: kernel size 1 takes dilation 1, not %d", a->dilation);
-  if (a->stride != 0) return codec_fail("dia_codec_conv: stride = %d belongs to dia_codec_convt; it must be 0 here", a->stride);
   ConvK k = {};
-  const int half = (a->k / 2) * a->dilation;
-  k.ntaps = a->k; k.tap_step = a->dilation; k.tap_off0 = -half; k.lo = -half; k.width = NT + 2 * half;
-  k.ostride = 1; k.phases = 1; k.pad = 0; k.extra = 0;
-  return conv_launch(a, k, stream, "k_codec_conv");
+  if (int rc = conv_form(a, "dia_codec_conv", "dia_codec_convt", k)) return rc;
+  return conv_launch(a, k, 0, stream, "k_codec_conv");
 }
 
 extern "C" int dia_codec_convt(const dia_codec_conv_args* a, void* stream) {
-  const int s = a ? a->stride : 2;
-  if (a && s != 2 && s != 4 && s != 8) return codec_fail("dia_codec_convt: stride %d is not 2, 4 or 8", s);
-  if (int rc = conv_common(a, "dia_codec_convt", s, s)) return rc;
-  if (a->k != 0 && a->k != 2 * s) return codec_fail("dia_codec_convt: kernel size %d is not 2 * stride = %d", a->k, 2 * s);
-  if (a->dilation != 0 && a->dilation != 1) return codec_fail("dia_codec_convt: dilation %d is not supported", a->dilation);
-  if (a->res) return codec_fail("dia_codec_convt: a residual is not supported");
   ConvK k = {};
-  k.ntaps = 2; k.tap_step = -1; k.tap_off0 = 0; k.lo = -1; k.width = NT + 1;
-  k.ostride = s; k.phases = s; k.pad = s / 2; k.extra = 1;
-  return conv_launch(a, k, stream, "k_codec_conv (transposed)");
+  if (int rc = convt_form(a, "dia_codec_convt", k)) return rc;
+  return conv_launch(a, k, 0, stream, "k_codec_conv (transposed)");
 }
 
 extern "C" int dia_codec_convs(const dia_codec_conv_args* a, void* stream) {
-  const int s = a ? a->stride : 0;
-  if (a && s != 0 && s != 2 && s != 4 && s != 8) return codec_fail("dia_codec_convs: stride %d is not 0 (the k-3 form), 2, 4 or 8", s);
-  if (int rc = conv_common(a, "dia_codec_convs", 1, 1, s ? s : 1)) return rc;
-  if (a->dilation != 0 && a->dilation != 1) return codec_fail("dia_codec_convs: dilation %d is not supported", a->dilation);
-  if (a->res) return codec_fail("dia_codec_convs: a residual is not supported");
   ConvK k = {};
-  k.ostride = 1; k.phases = 1; k.pad = 0; k.extra = 0;
-  if (s == 0) {
-    if (a->k != 3) return codec_fail("dia_codec_convs: kernel size %d is not 3 (stride 0) or 2 * stride", a->k);
-    k.ntaps = 3; k.tap_step = 1; k.tap_off0 = -1; k.lo = -1; k.width = NT + 2;
-    return conv_launch(a, k, stream, "k_codec_conv (k 3)");
-  }
-  if (a->k != 0 && a->k != 2 * s) return codec_fail("dia_codec_convs: kernel size %d is not 2 * stride = %d", a->k, 2 * s);
-  if (a->T % s != 0) return codec_fail("dia_codec_convs: T = %d is not a multiple of stride %d", a->T, s);
-  k.ntaps = 2; k.tap_step = 1; k.tap_off0 = 0; k.lo = 0; k.width = NT + 1; k.xstride = s;
-  return conv_launch(a, k, stream, "k_codec_conv (strided)", true);
+  int s = 0;
+  if (int rc = convs_form(a, "dia_codec_convs", k, s)) return rc;
+  return conv_launch(a, k, s, stream, s ? "k_codec_conv (strided)" : "k_codec_conv (k 3)");
 }
 
 extern "C" int dia_codec_quantize(const dia_codec_quantize_args* a, void* stream) {

@@ -12,6 +12,7 @@ from __future__ import annotations
 
 import ctypes as C
 import re
+from contextlib import contextmanager
 from dataclasses import dataclass, field
 from typing import Callable, Dict, List, Optional, Sequence, Tuple, Union
 
@@ -124,38 +125,30 @@ def expected_encoder_keys(cfg: CodecConfig) -> Dict[str, Tuple[int, ...]]:
 _ENCODE_SIDE = re.compile(r"^(encoder\.|quantizer\.quantizers\.\d+\.in_proj\.)")
 
 
-def check_codec_state(cfg: CodecConfig, sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
-    """the decode-side tensors of `sd`; a missing or unexpected decoder / quantizer key, or a wrong shape, is refused by name.
-    Encoder keys and the quantizers' in_proj (the encode side of the same modules) are ignored."""
-    want = expected_keys(cfg)
-    have = {k: v for k, v in sd.items() if not _ENCODE_SIDE.match(k)}
+def _check_state(want: Dict[str, Tuple[int, ...]], have: Dict[str, torch.Tensor], label: str) -> Dict[str, torch.Tensor]:
+    """the tensors of `have` in the order of `want`; a missing or unexpected key, or a wrong shape, is refused by name"""
     missing = [k for k in want if k not in have]
     unexpected = [k for k in have if k not in want]
     if missing:
-        raise KeyError(f"codec checkpoint: missing keys {missing[:8]}{' ...' if len(missing) > 8 else ''}")
+        raise KeyError(f"{label}: missing keys {missing[:8]}{' ...' if len(missing) > 8 else ''}")
     if unexpected:
-        raise KeyError(f"codec checkpoint: unexpected keys {unexpected[:8]}{' ...' if len(unexpected) > 8 else ''}")
+        raise KeyError(f"{label}: unexpected keys {unexpected[:8]}{' ...' if len(unexpected) > 8 else ''}")
     for k, shp in want.items():
         if tuple(have[k].shape) != shp:
-            raise ValueError(f"codec checkpoint: {k} has shape {tuple(have[k].shape)}, expected {shp}")
+            raise ValueError(f"{label}: {k} has shape {tuple(have[k].shape)}, expected {shp}")
     return {k: have[k] for k in want}
+
+
+def check_codec_state(cfg: CodecConfig, sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """the decode-side tensors of `sd`; a missing or unexpected decoder / quantizer key, or a wrong shape, is refused by name.
+    Encoder keys and the quantizers' in_proj (the encode side of the same modules) are ignored."""
+    return _check_state(expected_keys(cfg), {k: v for k, v in sd.items() if not _ENCODE_SIDE.match(k)}, "codec checkpoint")
 
 
 def check_codec_encoder_state(cfg: CodecConfig, sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
     """the encode-side tensors of `sd` (encoder.*, quantizers' in_proj); a missing or unexpected one, or a wrong shape, is refused
     by name.  check_codec_state() is the decode side's and ignores exactly these keys."""
-    want = expected_encoder_keys(cfg)
-    have = {k: v for k, v in sd.items() if _ENCODE_SIDE.match(k)}
-    missing = [k for k in want if k not in have]
-    unexpected = [k for k in have if k not in want]
-    if missing:
-        raise KeyError(f"codec checkpoint (encode side): missing keys {missing[:8]}{' ...' if len(missing) > 8 else ''}")
-    if unexpected:
-        raise KeyError(f"codec checkpoint (encode side): unexpected keys {unexpected[:8]}{' ...' if len(unexpected) > 8 else ''}")
-    for k, shp in want.items():
-        if tuple(have[k].shape) != shp:
-            raise ValueError(f"codec checkpoint (encode side): {k} has shape {tuple(have[k].shape)}, expected {shp}")
-    return {k: have[k] for k in want}
+    return _check_state(expected_encoder_keys(cfg), {k: v for k, v in sd.items() if _ENCODE_SIDE.match(k)}, "codec checkpoint (encode side)")
 
 
 def infer_encoder_config(cfg: CodecConfig, sd: Dict[str, torch.Tensor], kwargs: Optional[dict] = None) -> CodecConfig:
@@ -549,6 +542,13 @@ def _fns():
     return L
 
 
+def _launch_conv(lib, entry: str, planes: int, a: CodecConvArgs, st) -> None:
+    """entry "conv" / "convt" / "convs" with planes 0 (fp32) / 1 / 2 -> dia_codec_<entry> or dia_codec_<entry>_bf16(planes)"""
+    name = f"dia_codec_{entry}_bf16" if planes else f"dia_codec_{entry}"
+    fn = getattr(lib, name)
+    hb.check(fn(C.byref(a), planes, st) if planes else fn(C.byref(a), st), name)
+
+
 def snake_inverse(alpha: torch.Tensor) -> torch.Tensor:
     """1 / (alpha + 1e-9) per channel, in float64, as fp32"""
     return (1.0 / (alpha.detach().to(torch.float64).reshape(-1) + 1e-9)).to(torch.float32)
@@ -579,13 +579,7 @@ def codec_conv(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, *, c_out: i
     a = CodecConvArgs(x=hb.ptr(x), w=hb.ptr(w), bias=hb.ptr(bias), alpha=hb.ptr(alpha), inv=hb.ptr(inv), res=hb.ptr(res), y=hb.ptr(y),
                       lens=hb.ptr(lens), B=B, T=T, C_in=cin, C_out=c_out, ldx=T, ldy=To, k=0 if stride else k,
                       dilation=0 if stride else dilation, stride=stride, tanh_out=int(tanh))
-    L = _fns()
-    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-    if planes:
-        hb.check((L.dia_codec_convt_bf16 if stride else L.dia_codec_conv_bf16)(C.byref(a), planes, st),
-                 "dia_codec_convt_bf16" if stride else "dia_codec_conv_bf16")
-        return y
-    hb.check((L.dia_codec_convt if stride else L.dia_codec_conv)(C.byref(a), st), "dia_codec_convt" if stride else "dia_codec_conv")
+    _launch_conv(_fns(), "convt" if stride else "conv", planes, a, C.c_void_p(torch.cuda.current_stream().cuda_stream))
     return y
 
 
@@ -598,7 +592,7 @@ def codec_convs(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, *, c_out: 
     y = torch.zeros(B, c_out, To, dtype=torch.float32, device=x.device)
     a = CodecConvArgs(x=hb.ptr(x), w=hb.ptr(w), bias=hb.ptr(bias), alpha=hb.ptr(alpha), inv=hb.ptr(inv), y=hb.ptr(y), lens=hb.ptr(lens),
                       B=B, T=T, C_in=cin, C_out=c_out, ldx=T, ldy=To, k=0 if stride else 3, dilation=1, stride=stride)
-    hb.check(_fns().dia_codec_convs(C.byref(a), C.c_void_p(torch.cuda.current_stream().cuda_stream)), "dia_codec_convs")
+    _launch_conv(_fns(), "convs", 0, a, C.c_void_p(torch.cuda.current_stream().cuda_stream))
     return y
 
 
@@ -655,17 +649,11 @@ class DeviceCodec:
         self.layers: List[dict] = []
         rate, per_frame = 1, cfg.latent_dim
         for L in layer_plan(cfg):
-            w = fold_weight_norm(sd[L["key"] + ".weight_g"], sd[L["key"] + ".weight_v"])
-            D = dict(L)
             if self.planes:                                     # a reduced mode holds its own image and no fp32 one
-                D["w_bf16"] = (conv_layout_bf16 if L["kind"] == "conv" else convt_layout_bf16)(w, self.planes).to(dev)
+                lay = conv_layout_bf16 if L["kind"] == "conv" else convt_layout_bf16
+                D = self._upload_layer(L, sd, "w_bf16", lambda w: lay(w, self.planes))
             else:
-                D["w"] = (conv_layout(w) if L["kind"] == "conv" else convt_layout(w)).to(dev)
-            D["b"] = sd[L["key"] + ".bias"].to(torch.float32).to(dev)
-            if L["snake"]:
-                al = sd[L["snake"] + ".alpha"]
-                D["alpha"] = al.reshape(-1).to(torch.float32).to(dev)
-                D["inv"] = snake_inverse(al).to(dev)
+                D = self._upload_layer(L, sd, "w", conv_layout if L["kind"] == "conv" else convt_layout)
             D["rate_in"] = rate
             if L["kind"] == "convt":
                 rate *= L["s"]
@@ -688,6 +676,17 @@ class DeviceCodec:
             self.encoder_error = KeyError("codec checkpoint: no encode side (missing keys ['encoder.block.0.weight_g', ...]); encode() needs "
                                           "the encoder.* and quantizer.quantizers.N.in_proj.* tensors")
 
+    def _upload_layer(self, L: dict, sd: Dict[str, torch.Tensor], wkey: str, layout: Callable[[torch.Tensor], torch.Tensor]) -> dict:
+        """the plan entry L with its device tensors: the folded weight in `layout` under `wkey`, the bias, the Snake's alpha and inverse"""
+        D = dict(L)
+        D[wkey] = layout(fold_weight_norm(sd[L["key"] + ".weight_g"], sd[L["key"] + ".weight_v"])).to(self.device)
+        D["b"] = sd[L["key"] + ".bias"].to(torch.float32).to(self.device)
+        if L["snake"]:
+            al = sd[L["snake"] + ".alpha"]
+            D["alpha"] = al.reshape(-1).to(torch.float32).to(self.device)
+            D["inv"] = snake_inverse(al).to(self.device)
+        return D
+
     def _prepare_encoder(self, sd, whole, meta, workspace_bytes: int) -> None:
         self.cfg = cfg = infer_encoder_config(self.cfg, whole, meta)
         if int(np.prod(cfg.encoder_rates)) != cfg.hop:
@@ -696,15 +695,8 @@ class DeviceCodec:
         dev = self.device
         layers, div, per_frame = [], 1, cfg.hop
         for L in encoder_plan(cfg):
-            w = fold_weight_norm(enc[L["key"] + ".weight_g"], enc[L["key"] + ".weight_v"])
-            D = dict(L)
-            D["w"] = (convs_layout(w) if L["kind"] == "convs" else conv_layout(w)).to(dev)
-            D["b"] = enc[L["key"] + ".bias"].to(torch.float32).to(dev)
-            if L["snake"]:
-                al = enc[L["snake"] + ".alpha"]
-                D["alpha"] = al.reshape(-1).to(torch.float32).to(dev)
-                D["inv"] = snake_inverse(al).to(dev)
-            D["div_in"] = div                                   # samples per position of this layer's input
+            D = self._upload_layer(L, enc, "w", convs_layout if L["kind"] == "convs" else conv_layout)
+            D["div_in"] = div                                  # samples per position of this layer's input
             if L["kind"] == "convs":
                 div *= L["s"]
             per_frame = max(per_frame, L["cin"] * cfg.hop // D["div_in"], L["cout"] * cfg.hop // div)
@@ -729,17 +721,63 @@ class DeviceCodec:
             self._rows = rows
         return self._bufs
 
+    @contextmanager
+    def _timed(self, label: str):
+        """while layer_events is a list: the launches of the block between a (label, start, stop) event pair appended to it"""
+        if self.layer_events is None:
+            yield
+            return
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        self.layer_events.append((label, e0, e1))
+        e0.record()
+        yield
+        e1.record()
+
+    def _window(self, window: Optional[int], why: str = " (the workspace is sized by the codec's window)") -> int:
+        """a call's window (None: the codec's) as an int in [1, the codec's]"""
+        window = self.window if window is None else int(window)
+        if not 1 <= window <= self.window:
+            raise ValueError(f"window = {window} outside [1, {self.window}]{why}")
+        return window
+
+    def _chain(self, lib, st, layers: List[dict], planes: int, cur: torch.Tensor, oth: torch.Tensor, lens: torch.Tensor, J: int,
+               T0: int, W0: int, x0: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """`layers` (self.layers or self.enc_layers) as one chain of batched launches over J rows on the ping-pong (cur, oth) -> the
+        buffer that holds the last layer's output.  The stream enters in cur, or in x0 for the first layer where given.  A layer
+        whose input has "rate_in" r positions (decoder) or 1 / "div_in" d (encoder) per unit of lens runs at T = T0 r / d, leading
+        dimension W0 r / d and lengths lens r / d.  A layer that makes a new stream (transposed, strided, k 3, first and last)
+        reads cur, writes oth and the two swap; inside a residual unit the k-7 reads cur into oth and the 1x1 reads oth and adds
+        onto cur, the unit's input."""
+        stage_lens = {(1, 1): lens}
+        for i, L in enumerate(layers):
+            kind, s = L["kind"], L.get("s", 0)
+            with self._timed(f"{kind} {L['cin']}->{L['cout']} k{L.get('k', 2 * s)} d{L.get('d', 1)}"):
+                r, d = L.get("rate_in", 1), L.get("div_in", 1)
+                if (r, d) not in stage_lens:
+                    stage_lens[r, d] = lens * r if d == 1 else lens // d
+                ld = W0 * r // d
+                a = CodecConvArgs(w=hb.ptr(L["w_bf16" if planes else "w"]), bias=hb.ptr(L["b"]), alpha=hb.ptr(L.get("alpha")),
+                                  inv=hb.ptr(L.get("inv")), lens=hb.ptr(stage_lens[r, d]), B=J, T=T0 * r // d, C_in=L["cin"],
+                                  C_out=L["cout"], ldx=ld, ldy=ld, tanh_out=int(bool(L.get("tanh"))))
+                if L.get("res"):
+                    a.x, a.y, a.res, a.k, a.dilation = hb.ptr(oth), hb.ptr(cur), hb.ptr(cur), 1, 1
+                else:
+                    a.x, a.y = hb.ptr(x0 if i == 0 and x0 is not None else cur), hb.ptr(oth)
+                    if kind == "convt":
+                        a.ldy, a.stride = ld * s, s
+                    elif kind == "convs":
+                        a.ldy, a.stride, a.k, a.dilation = ld // s, s, 2 * s, 1
+                    else:
+                        a.k, a.dilation = L["k"], L["d"]
+                    if kind != "conv" or not L["snake"] or L.get("tanh"):
+                        cur, oth = oth, cur
+                _launch_conv(lib, "convs" if kind == "conv3" else kind, planes, a, st)
+        return cur
+
     def _run(self, jobs: Sequence[np.ndarray]) -> List[np.ndarray]:
         """every job (codes [n_codebooks, n], n <= wmax) decoded as an utterance of its own: rows of one chain of batched launches"""
         cfg, lib = self.cfg, _fns()
         out: List[np.ndarray] = []
-        if self.planes:
-            planes = self.planes
-            conv = lambda a, st: lib.dia_codec_conv_bf16(a, planes, st)
-            convt = lambda a, st: lib.dia_codec_convt_bf16(a, planes, st)
-            wkey, sfx = "w_bf16", "_bf16"
-        else:
-            conv, convt, wkey, sfx = lib.dia_codec_conv, lib.dia_codec_convt, "w", ""
         with torch.cuda.device(self.device):
             st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
             for g0 in range(0, len(jobs), self.rows_cap):
@@ -756,32 +794,7 @@ class DeviceCodec:
                                     codebook_size=cfg.codebook_size, latent_dim=cfg.latent_dim, ld_codes=W, tables=hb.ptr(self.tables),
                                     bias=hb.ptr(self.embed_bias), z=hb.ptr(cur), ldz=W)
                 hb.check(lib.dia_codec_embed(C.byref(ea), st), "dia_codec_embed")
-                stage_lens = {1: lens}
-                for L in self.layers:
-                    r = L["rate_in"]
-                    if self.layer_events is not None:
-                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                        self.layer_events.append((f"{L['kind']} {L['cin']}->{L['cout']} k{L.get('k', 2 * L.get('s', 0))} d{L.get('d', 1)}", e0, e1))
-                        e0.record()
-                    if r not in stage_lens:
-                        stage_lens[r] = lens * r
-                    a = CodecConvArgs(w=hb.ptr(L[wkey]), bias=hb.ptr(L["b"]), alpha=hb.ptr(L.get("alpha")), inv=hb.ptr(L.get("inv")),
-                                      lens=hb.ptr(stage_lens[r]), B=J, T=Tg * r, C_in=L["cin"], C_out=L["cout"], ldx=W * r,
-                                      tanh_out=int(bool(L.get("tanh"))))
-                    if L["kind"] == "convt":
-                        a.x, a.y, a.ldy, a.stride = hb.ptr(cur), hb.ptr(oth), W * r * L["s"], L["s"]
-                        hb.check(convt(C.byref(a), st), "dia_codec_convt" + sfx)
-                        cur, oth = oth, cur
-                    elif L.get("res"):                         # the residual unit's 1x1: x is the k-7 output, the sum lands on the unit's input
-                        a.x, a.y, a.res, a.ldx, a.ldy, a.k, a.dilation = hb.ptr(oth), hb.ptr(cur), hb.ptr(cur), W * r, W * r, 1, 1
-                        hb.check(conv(C.byref(a), st), "dia_codec_conv" + sfx)
-                    else:
-                        a.x, a.y, a.ldy, a.k, a.dilation = hb.ptr(cur), hb.ptr(oth), W * r, L["k"], L["d"]
-                        hb.check(conv(C.byref(a), st), "dia_codec_conv" + sfx)
-                        if not L["snake"] or L.get("tanh"):    # first and last layer: the result is the new stream
-                            cur, oth = oth, cur
-                    if self.layer_events is not None:
-                        self.layer_events[-1][2].record()
+                cur = self._chain(lib, st, self.layers, self.planes, cur, oth, lens, J, Tg, W)
                 wave = cur[:J * W * cfg.hop].view(J, W * cfg.hop).cpu().numpy()
                 for r, j in enumerate(grp):
                     out.append(wave[r, :j.shape[1] * cfg.hop].copy())
@@ -801,9 +814,7 @@ class DeviceCodec:
     def decode_batch(self, rows: Sequence, window: Optional[int] = None) -> List[np.ndarray]:
         """one code tensor [n_codebooks, T_b] (or [1, n_codebooks, T_b]) per utterance -> float32 [T_b * hop] per utterance; every
         row comes out as when decoded alone"""
-        window = self.window if window is None else int(window)
-        if not 1 <= window <= self.window:
-            raise ValueError(f"window = {window} outside [1, {self.window}] (the workspace is sized by the codec's window)")
+        window = self._window(window)
         rows = [self._check_codes(r) for r in rows]
         jobs, plan = [], []
         for b, c in enumerate(rows):
@@ -845,36 +856,7 @@ class DeviceCodec:
                 x0 = torch.from_numpy(host).to(self.device)
                 lens = torch.tensor([j[0].shape[0] for j in grp], dtype=torch.int32, device=self.device)
                 cur, oth = self._workspace(-(-J * self.enc_row_floats // self.row_floats))
-                stage_lens = {1: lens}
-                for L in self.enc_layers:
-                    d = L["div_in"]
-                    if self.layer_events is not None:
-                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                        self.layer_events.append((f"{L['kind']} {L['cin']}->{L['cout']} k{L.get('k', 2 * L.get('s', 0))} d{L.get('d', 1)}", e0, e1))
-                        e0.record()
-                    if d not in stage_lens:
-                        stage_lens[d] = lens // d
-                    ld = W * hop // d
-                    a = CodecConvArgs(w=hb.ptr(L["w"]), bias=hb.ptr(L["b"]), alpha=hb.ptr(L.get("alpha")), inv=hb.ptr(L.get("inv")),
-                                      lens=hb.ptr(stage_lens[d]), B=J, T=Tg * hop // d, C_in=L["cin"], C_out=L["cout"], ldx=ld)
-                    if L["kind"] == "convs":
-                        a.x, a.y, a.ldy, a.stride, a.k, a.dilation = hb.ptr(cur), hb.ptr(oth), ld // L["s"], L["s"], 2 * L["s"], 1
-                        hb.check(lib.dia_codec_convs(C.byref(a), st), "dia_codec_convs")
-                        cur, oth = oth, cur
-                    elif L["kind"] == "conv3":
-                        a.x, a.y, a.ldy, a.k, a.dilation = hb.ptr(cur), hb.ptr(oth), ld, 3, 1
-                        hb.check(lib.dia_codec_convs(C.byref(a), st), "dia_codec_convs")
-                        cur, oth = oth, cur
-                    elif L.get("res"):                         # as in the decoder: the sum lands on the unit's input
-                        a.x, a.y, a.res, a.ldy, a.k, a.dilation = hb.ptr(oth), hb.ptr(cur), hb.ptr(cur), ld, 1, 1
-                        hb.check(lib.dia_codec_conv(C.byref(a), st), "dia_codec_conv")
-                    else:
-                        a.x, a.y, a.ldy, a.k, a.dilation = hb.ptr(x0 if L["cin"] == 1 and not L["snake"] else cur), hb.ptr(oth), ld, L["k"], L["d"]
-                        hb.check(lib.dia_codec_conv(C.byref(a), st), "dia_codec_conv")
-                        if not L["snake"]:                     # the first layer: its result is the new stream
-                            cur, oth = oth, cur
-                    if self.layer_events is not None:
-                        self.layer_events[-1][2].record()
+                cur = self._chain(lib, st, self.enc_layers, 0, cur, oth, lens, J, Tg * hop, W * hop, x0=x0)
                 # the kept frames of every job, gathered to the front of a tensor of their own: the quantiser sees nothing else
                 zall = cur[:J * cfg.latent_dim * W].view(J, cfg.latent_dim, W)
                 Wq = max(j[2] for j in grp)
@@ -882,13 +864,8 @@ class DeviceCodec:
                 at = (first[:, None] + torch.arange(Wq, device=self.device)[None, :]).clamp_(max=W - 1)
                 z = torch.gather(zall, 2, at[:, None, :].expand(J, cfg.latent_dim, Wq)).contiguous()
                 qlens = torch.tensor([j[2] for j in grp], dtype=torch.int32, device=self.device)
-                if self.layer_events is not None:
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    self.layer_events.append((f"quantize {cfg.latent_dim} x {cfg.n_codebooks}", e0, e1))
-                    e0.record()
-                codes = codec_quantize(z, self.qtabs, self.tables, lens=qlens)
-                if self.layer_events is not None:
-                    self.layer_events[-1][2].record()
+                with self._timed(f"quantize {cfg.latent_dim} x {cfg.n_codebooks}"):
+                    codes = codec_quantize(z, self.qtabs, self.tables, lens=qlens)
                 codes_h, z_h = codes.cpu().numpy(), z.cpu().numpy()
                 for r, (_, _, n) in enumerate(grp):
                     out.append((codes_h[r, :, :n].astype(np.int64), z_h[r, :, :n].copy()))
@@ -904,9 +881,7 @@ class DeviceCodec:
         resampled samples)."""
         if self.enc_layers is None:
             raise self.encoder_error
-        window = self.window if window is None else int(window)
-        if not 1 <= window <= self.window:
-            raise ValueError(f"window = {window} outside [1, {self.window}] (the workspace is sized by the codec's window)")
+        window = self._window(window)
         if sample_rates is not None and len(sample_rates) != len(rows):
             raise ValueError("codec: one sample rate (or None) per row")
         hop, waves = self.cfg.hop, []
@@ -974,7 +949,5 @@ class DeviceCodec:
 
     def stream(self, window: Optional[int] = None) -> CodecStream:
         """a streaming state for one utterance on this codec"""
-        window = self.window if window is None else int(window)
-        if not 1 <= window <= self.window:
-            raise ValueError(f"window = {window} outside [1, {self.window}]")
+        window = self._window(window, why="")
         return CodecStream(lambda c: self._run([self._check_codes(c)])[0], self.cfg.n_codebooks, self.cfg.hop, window, self.ctx)

@@ -134,6 +134,50 @@ def _refused(fn, a, word, planes=2):
     return rc == -1 and word in msg
 
 
+def _bad_blocks():
+    """(transposed?, argument block or None) per refusal the fp32 and the bf16 entry points share: every shared check, then every
+    conv and convt form check"""
+    a = _conv_args()
+    alias = _conv_args()
+    alias.y = alias.x
+    t = dict(stride=2, k=4, ldy=16)
+    rows = [(False, None), (True, None)]
+    for name in ("x", "w", "bias", "y"):
+        rows += [(False, _conv_args(**{name: None})), (True, _conv_args(**{name: None}, **t))]
+    rows += [(False, _conv_args(alpha=a.x)), (False, _conv_args(inv=a.x)), (True, _conv_args(alpha=a.x, **t)), (False, alias),
+             (False, _conv_args(w=a.w + 4)), (True, _conv_args(w=a.w + 4, **t))]
+    rows += [(False, _conv_args(**{f: bad})) for f, bad in (("C_in", 0), ("C_in", 4097), ("C_out", 0), ("C_out", 4097))]
+    rows += [(False, _conv_args(T=0)), (False, _conv_args(T=(1 << 24) + 1, ldx=1 << 25, ldy=1 << 25)), (True, _conv_args(T=0, **t)),
+             (False, _conv_args(B=0)), (False, _conv_args(B=65536)), (True, _conv_args(B=8192, stride=8, k=16, ldy=64)),
+             (False, _conv_args(ldx=7)), (False, _conv_args(ldy=7)), (True, _conv_args(stride=4, k=8, ldy=31)),
+             (False, _conv_args(tanh_out=2)), (True, _conv_args(tanh_out=-1, **t))]
+    rows += [(False, _conv_args(k=k)) for k in (0, 3, 5, 9)]
+    rows += [(False, _conv_args(dilation=d)) for d in (0, 2, 4, 27)]
+    rows += [(False, _conv_args(k=1, dilation=3)), (False, _conv_args(stride=2))]
+    rows += [(True, _conv_args(stride=s, k=2 * s, ldy=128)) for s in (0, 1, 3, 16)]
+    rows += [(True, _conv_args(stride=4, k=7, ldy=32)), (True, _conv_args(stride=4, k=8, dilation=3, ldy=32)),
+             (True, _conv_args(stride=4, k=8, dilation=1, ldy=32, res=a.x))]
+    return rows
+
+
+def test_bf16_entries_refuse_what_the_fp32_entries_refuse_in_the_same_words():
+    """one set of checks behind both (csrc/codec_conv.hpp): a bad block is refused by dia_codec_conv / dia_codec_convt and, with
+    planes = 2, by dia_codec_conv_bf16 / dia_codec_convt_bf16, and the two texts differ in the entry points' names alone"""
+    L = K._fns()
+    texts = set()
+    for i, (transposed, a) in enumerate(_bad_blocks()):
+        f32, bf = (L.dia_codec_convt, L.dia_codec_convt_bf16) if transposed else (L.dia_codec_conv, L.dia_codec_conv_bf16)
+        ref = ctypes.byref(a) if a is not None else None
+        assert f32(ref, None) == -1, i
+        want = hb.lib().dia_last_error().decode()
+        assert bf(ref, 2, None) == -1, i
+        got = hb.lib().dia_last_error().decode()
+        renamed = want.replace("dia_codec_convt", "dia_codec_convt_bf16").replace("dia_codec_conv:", "dia_codec_conv_bf16:")
+        assert got == renamed and want.startswith("dia_codec_convt: " if transposed else "dia_codec_conv: "), (i, want, got)
+        texts.add(want)
+    assert len(texts) >= 40, sorted(texts)                       # the rows reach different refusals, not one many times
+
+
 def test_bf16_entries_argument_validation_without_gpu():
     L = K._fns()
     conv, convt = L.dia_codec_conv_bf16, L.dia_codec_convt_bf16
