@@ -1372,6 +1372,64 @@ int launch_attn_mfma(const AttnK& k, int grid_y, int grid_z, hipStream_t st) {
   return dia_check_launch("k_attn_mfma");
 }
 
+// Key-split factor of a launch (its grid z): ~2 workgroups of 4 waves per CU, never more than one split per 128 keys of
+// capacity (the scratch sizing granule), and each split at least one 64-key unit.  The only copy of the rule and the only
+// reader of the attn_nz knob: the FP8 caches merge their slabs in the order of the bf16 ones because all entries split here.
+int key_split(int n_rows, int n_kv_heads, int cap_keys) {
+  const int cap_chunks = (cap_keys + CHUNK - 1) / CHUNK;
+  int max_chunks = (512 + n_rows * n_kv_heads - 1) / (n_rows * n_kv_heads);
+  if (dia_tune(DIA_TUNE_ATTN_NZ) > 0) max_chunks = dia_tune(DIA_TUNE_ATTN_NZ);
+  if (max_chunks > cap_chunks) max_chunks = cap_chunks;
+  return max_chunks < 1 ? 1 : max_chunks;
+}
+
+// What differs between the three entries ahead of the launch: the name in the messages, whether an FP8 cache comes with the
+// call, whether kc / vc must be there, and the entry's own refusals (the message of the first that applies, or nullptr) at
+// their two places in the order of the checks.  That order is part of the ABI: callers and tests see the first refusal.
+using AttnRule = const char* (*)(const dia_attn_args*);
+struct AttnEntry { const char* who; bool fp8, need_kv; AttnRule early = nullptr, late = nullptr; };
+
+// The front end of dia_attn, dia_attn_cross_fp8 and dia_attn_self_fp8: the refusals, the key split (max_chunks, the grid's z)
+// and the AttnK fill.  Every index the kernels derive from the launch shape is checked here against what the caller states
+// about its buffers: ENC reads q row / RoPE row / emits plane row blockIdx.y for blockIdx.y < n_rows, and keys 0..enc_len-1
+// of a kv_cap-row scratch cache; SELF reads RoPE row cur <= kv_cap.
+int attn_front(const AttnEntry& e, const dia_attn_args* a, const dia_kv_fp8_ptrs* f, AttnK& k, int& max_chunks) {
+  static thread_local char msg[160];
+  auto fail = [&](const char* what) { snprintf(msg, sizeof msg, "%s: %s", e.who, what); return dia_fail(DIA_E_ARG, msg); };
+  if (!a || (e.fp8 && !f) || !a->q || !a->P || !a->cos_t || !a->sin_t || (e.need_kv && (!a->kc || !a->vc)) || (f && (!f->k8 || !f->v8 || !f->ks || !f->vs)))
+    return fail("null argument");
+  if (const char* m = e.early ? e.early(a) : nullptr) return fail(m);
+  if (f && (a->kv_cap <= 0 || a->kv_cap % 32 != 0)) return fail("kv_cap must be a positive multiple of 32");
+  if (a->n_rows <= 0 || a->n_kv_heads <= 0) return fail("empty problem");
+  if (a->p_plane_stride % 8 != 0) return fail("plane stride must be a multiple of 8");
+  if (const char* m = e.late ? e.late(a) : nullptr) return fail(m);
+  if (a->mode == DIA_ATTN_ENC && (a->n_rows != a->enc_len || a->enc_len <= 0 || a->enc_len > a->kv_cap)) return fail("ENC needs n_rows == enc_len and 0 < enc_len <= kv_cap");
+  if (a->rope_rows > 0 && ((a->mode == DIA_ATTN_ENC && a->enc_len > a->rope_rows) || (a->mode == DIA_ATTN_SELF && a->kv_cap + 1 > a->rope_rows)))
+    return fail("RoPE tables shorter than the positions this launch can reach");
+  if (a->kv_cap <= 0) return fail("kv_cap must be positive");
+  // (order again: the FP8 entries refuse a narrow plane set and their pointers ahead of the split, dia_attn the planes behind it)
+  const bool narrow = (a->n_kv_heads * a->group * 128 + 31) / 32 > a->p_ktiles;
+  if (f && narrow) return fail("output planes too narrow");
+  if (f && (((uintptr_t)f->k8 & 7) || ((uintptr_t)f->v8 & 7) || ((uintptr_t)f->ks & 3) || ((uintptr_t)f->vs & 3))) return fail("k8 / v8 must be 8-byte aligned, ks / vs 4-byte");
+  max_chunks = key_split(a->n_rows, a->n_kv_heads, a->mode == DIA_ATTN_ENC ? a->enc_len : a->kv_cap);
+  if (max_chunks > 1 && (!a->scratch || !a->tickets)) return fail("more than 128 keys possible: scratch and tickets are required");
+  if (narrow) return fail("output planes too narrow");
+  k = {};
+  k.mode = a->mode; k.n_kv_heads = a->n_kv_heads; k.n_rows = a->n_rows; k.kv_cap = a->kv_cap;
+  k.q = a->q; k.ldq = a->ldq; k.q_off = a->q_off; k.k_off = a->k_off; k.v_off = a->v_off;
+  k.kc = a->kc; k.vc = a->vc; k.enc_len = a->enc_len; k.cos_t = a->cos_t; k.sin_t = a->sin_t;
+  k.P = (bf16_raw*)a->P; k.p_plane_stride = a->p_plane_stride; k.p_ktiles = a->p_ktiles; k.act_f32 = a->act_f32;
+  k.head_map = a->head_map; k.v_blocked = a->v_blocked;
+  const int g = dia_tune(a->mode == DIA_ATTN_CROSS ? DIA_TUNE_ATTN_GPW_CROSS : DIA_TUNE_ATTN_GPW);
+  k.gpw = g > 0 ? g : 1;
+  // the kernels decode the mode branch-free and load cur[]/len[] unconditionally (index 0 when the mode
+  // does not use them): never hand them a null pointer
+  k.cur = a->cur ? a->cur : reinterpret_cast<const int*>(a->cos_t);
+  k.len = a->len ? a->len : reinterpret_cast<const int*>(a->cos_t);
+  k.scratch = a->scratch; k.tickets = a->tickets; k.max_chunks = (a->kv_cap + CHUNK - 1) / CHUNK;
+  return DIA_OK;
+}
+
 }  // namespace
 
 #ifdef DIA_DBG_STAMPS
@@ -1384,6 +1442,7 @@ extern "C" int dia_dbg_astamps(long long* host, int n) {
 }
 #endif
 
+// (the capacity: one slab per 128 keys; key_split decides how many of them a launch uses)
 extern "C" int dia_attn_scratch_floats(int n_rows, int n_kv_heads, int kv_cap) {
   const long chunks = (kv_cap + CHUNK - 1) / CHUNK;
   const long n = (long)n_rows * n_kv_heads * chunks * SLAB;
@@ -1391,44 +1450,10 @@ extern "C" int dia_attn_scratch_floats(int n_rows, int n_kv_heads, int kv_cap) {
 }
 
 extern "C" int dia_attn(const dia_attn_args* a, void* stream) {
-  if (!a || !a->q || !a->kc || !a->vc || !a->P || !a->cos_t || !a->sin_t) return dia_fail(DIA_E_ARG, "dia_attn: null argument");
-  if (a->n_rows <= 0 || a->n_kv_heads <= 0) return dia_fail(DIA_E_ARG, "dia_attn: empty problem");
-  if (a->p_plane_stride % 8 != 0) return dia_fail(DIA_E_ARG, "dia_attn: plane stride must be a multiple of 8");
-  // every index the kernels derive from the launch shape is checked here against what the caller states about its
-  // buffers: ENC reads q row / RoPE row / emits plane row blockIdx.y for blockIdx.y < n_rows, and keys 0..enc_len-1 of
-  // a kv_cap-row scratch cache; SELF reads RoPE row cur <= kv_cap
-  if (a->mode == DIA_ATTN_ENC && (a->n_rows != a->enc_len || a->enc_len <= 0 || a->enc_len > a->kv_cap))
-    return dia_fail(DIA_E_ARG, "dia_attn: ENC needs n_rows == enc_len and 0 < enc_len <= kv_cap");
-  if (a->rope_rows > 0 && ((a->mode == DIA_ATTN_ENC && a->enc_len > a->rope_rows) || (a->mode == DIA_ATTN_SELF && a->kv_cap + 1 > a->rope_rows)))
-    return dia_fail(DIA_E_ARG, "dia_attn: RoPE tables shorter than the positions this launch can reach");
-  if (a->kv_cap <= 0) return dia_fail(DIA_E_ARG, "dia_attn: kv_cap must be positive");
-  const int cap_keys = a->mode == DIA_ATTN_ENC ? a->enc_len : a->kv_cap;
-  const int cap_chunks = (cap_keys + CHUNK - 1) / CHUNK;
-  // key-split factor: ~2 workgroups of 4 waves per CU, never more than one split per 128 keys of
-  // capacity (the scratch sizing granule), and each split at least one 64-key unit
-  int max_chunks = (512 + a->n_rows * a->n_kv_heads - 1) / (a->n_rows * a->n_kv_heads);
-  if (dia_tune(DIA_TUNE_ATTN_NZ) > 0) max_chunks = dia_tune(DIA_TUNE_ATTN_NZ);
-  if (max_chunks > cap_chunks) max_chunks = cap_chunks;
-  if (max_chunks < 1) max_chunks = 1;
-  if (max_chunks > 1 && (!a->scratch || !a->tickets)) return dia_fail(DIA_E_ARG, "dia_attn: more than 128 keys possible: scratch and tickets are required");
-  AttnK k;
-  k.mode = a->mode; k.n_kv_heads = a->n_kv_heads; k.n_rows = a->n_rows; k.kv_cap = a->kv_cap;
-  k.q = a->q; k.ldq = a->ldq; k.q_off = a->q_off; k.k_off = a->k_off; k.v_off = a->v_off;
-  k.kc = a->kc; k.vc = a->vc; k.cur = a->cur; k.len = a->len; k.enc_len = a->enc_len;
-  k.cos_t = a->cos_t; k.sin_t = a->sin_t;
-  k.P = (bf16_raw*)a->P; k.p_plane_stride = a->p_plane_stride; k.p_ktiles = a->p_ktiles; k.act_f32 = a->act_f32;
-  k.head_map = a->head_map; k.v_blocked = a->v_blocked;
-  k.gpw = 1;
-  { const int g = dia_tune(a->mode == DIA_ATTN_CROSS ? DIA_TUNE_ATTN_GPW_CROSS : DIA_TUNE_ATTN_GPW); if (g > 0) k.gpw = g; }
-  // the kernels decode the mode branch-free and load cur[]/len[] unconditionally (index 0 when the mode
-  // does not use them): never hand them a null pointer
-  if (!k.cur) k.cur = reinterpret_cast<const int*>(a->cos_t);
-  if (!k.len) k.len = reinterpret_cast<const int*>(a->cos_t);
-  k.scratch = a->scratch; k.tickets = a->tickets; k.max_chunks = (a->kv_cap + CHUNK - 1) / CHUNK;
-  if ((a->n_kv_heads * a->group * 128 + 31) / 32 > a->p_ktiles) return dia_fail(DIA_E_ARG, "dia_attn: output planes too narrow");
+  AttnK k; int max_chunks;
+  if (const int rc = attn_front({"dia_attn", false, true}, a, nullptr, k, max_chunks)) return rc;
   hipStream_t st = (hipStream_t)stream;
   const bool f32 = a->kv_dtype == DIA_KV_F32;
-  k.kv_plane_stride = 0;
   if (a->kv_dtype == DIA_KV_BF16X2) {
     if (!a->v_blocked || a->kv_plane_stride <= 0 || a->kv_plane_stride % 8 != 0)
       return dia_fail(DIA_E_ARG, "dia_attn: two-plane bf16 K/V needs the blocked V layout and the plane stride of the caches");
@@ -1462,74 +1487,31 @@ extern "C" int dia_attn(const dia_attn_args* a, void* stream) {
 }
 
 extern "C" int dia_attn_cross_fp8(const dia_attn_args* a, const dia_kv_fp8_ptrs* f, void* stream) {
-  if (!a || !f) return dia_fail(DIA_E_ARG, "dia_attn_cross_fp8: null argument");
-  if (!a->q || !a->kc || !a->vc || !a->P || !a->cos_t || !a->sin_t || !f->k8 || !f->v8 || !f->ks || !f->vs)
-    return dia_fail(DIA_E_ARG, "dia_attn_cross_fp8: null argument");
-  if (a->mode != DIA_ATTN_CROSS) return dia_fail(DIA_E_ARG, "dia_attn_cross_fp8: mode must be DIA_ATTN_CROSS");
-  if (a->group != 1) return dia_fail(DIA_E_ARG, "dia_attn_cross_fp8: group must be 1");
-  if (a->kv_dtype != DIA_KV_BF16 || !a->v_blocked) return dia_fail(DIA_E_ARG, "dia_attn_cross_fp8: kv_dtype must be DIA_KV_BF16 with the blocked V layout (v_blocked)");
-  if (a->kv_cap <= 0 || a->kv_cap % 32 != 0) return dia_fail(DIA_E_ARG, "dia_attn_cross_fp8: kv_cap must be a positive multiple of 32");
-  if (a->n_rows <= 0 || a->n_kv_heads <= 0) return dia_fail(DIA_E_ARG, "dia_attn_cross_fp8: empty problem");
-  if (a->p_plane_stride % 8 != 0) return dia_fail(DIA_E_ARG, "dia_attn_cross_fp8: plane stride must be a multiple of 8");
-  if (!a->cur || !a->len) return dia_fail(DIA_E_ARG, "dia_attn_cross_fp8: CROSS needs cur and len");
-  if ((a->n_kv_heads * 128 + 31) / 32 > a->p_ktiles) return dia_fail(DIA_E_ARG, "dia_attn_cross_fp8: output planes too narrow");
-  if (((uintptr_t)f->k8 & 7) || ((uintptr_t)f->v8 & 7) || ((uintptr_t)f->ks & 3) || ((uintptr_t)f->vs & 3))
-    return dia_fail(DIA_E_ARG, "dia_attn_cross_fp8: k8 / v8 must be 8-byte aligned, ks / vs 4-byte");
-  // the key split of dia_attn, so that the slabs merge in the same order
-  const int cap_chunks = (a->kv_cap + CHUNK - 1) / CHUNK;
-  int max_chunks = (512 + a->n_rows * a->n_kv_heads - 1) / (a->n_rows * a->n_kv_heads);
-  if (dia_tune(DIA_TUNE_ATTN_NZ) > 0) max_chunks = dia_tune(DIA_TUNE_ATTN_NZ);
-  if (max_chunks > cap_chunks) max_chunks = cap_chunks;
-  if (max_chunks < 1) max_chunks = 1;
-  if (max_chunks > 1 && (!a->scratch || !a->tickets)) return dia_fail(DIA_E_ARG, "dia_attn_cross_fp8: more than 128 keys possible: scratch and tickets are required");
-  AttnK k = {};
-  k.mode = a->mode; k.n_kv_heads = a->n_kv_heads; k.n_rows = a->n_rows; k.kv_cap = a->kv_cap;
-  k.q = a->q; k.ldq = a->ldq; k.q_off = a->q_off;
-  k.kc = a->kc; k.vc = a->vc; k.cur = a->cur; k.len = a->len;
-  k.cos_t = a->cos_t; k.sin_t = a->sin_t;
-  k.P = (bf16_raw*)a->P; k.p_plane_stride = a->p_plane_stride; k.p_ktiles = a->p_ktiles; k.act_f32 = a->act_f32;
-  k.head_map = a->head_map; k.v_blocked = 1;
-  k.gpw = 1;
-  { const int g = dia_tune(DIA_TUNE_ATTN_GPW_CROSS); if (g > 0) k.gpw = g; }
-  k.scratch = a->scratch; k.tickets = a->tickets; k.max_chunks = cap_chunks;
+  static const AttnEntry E = {"dia_attn_cross_fp8", true, true,
+    [](const dia_attn_args* a) -> const char* {
+      if (a->mode != DIA_ATTN_CROSS) return "mode must be DIA_ATTN_CROSS";
+      if (a->group != 1) return "group must be 1";
+      return a->kv_dtype != DIA_KV_BF16 || !a->v_blocked ? "kv_dtype must be DIA_KV_BF16 with the blocked V layout (v_blocked)" : nullptr; },
+    [](const dia_attn_args* a) -> const char* { return !a->cur || !a->len ? "CROSS needs cur and len" : nullptr; }};
+  AttnK k; int max_chunks;
+  if (const int rc = attn_front(E, a, f, k, max_chunks)) return rc;
   const AttnF8 f8 = {(const uint8_t*)f->k8, (const uint8_t*)f->v8, f->ks, f->vs};
   dia_launch<k_attn_mfma_f8>(dim3(a->n_kv_heads, a->n_rows, max_chunks), dim3(NT), 0, (hipStream_t)stream, k, f8);
   return dia_check_launch("k_attn_mfma_f8");
 }
 
 extern "C" int dia_attn_self_fp8(const dia_attn_args* a, const dia_kv_fp8_ptrs* f, void* stream) {
-  if (!a || !f) return dia_fail(DIA_E_ARG, "dia_attn_self_fp8: null argument");
-  if (!a->q || !a->P || !a->cos_t || !a->sin_t || !f->k8 || !f->v8 || !f->ks || !f->vs)      // (kc / vc: there is no bf16 cache, NULL is fine)
-    return dia_fail(DIA_E_ARG, "dia_attn_self_fp8: null argument");
-  if (a->mode != DIA_ATTN_SELF) return dia_fail(DIA_E_ARG, "dia_attn_self_fp8: mode must be DIA_ATTN_SELF");
-  if (a->kv_dtype != DIA_KV_BF16) return dia_fail(DIA_E_ARG, "dia_attn_self_fp8: kv_dtype must be DIA_KV_BF16 (one plane)");
-  if (!a->v_blocked) return dia_fail(DIA_E_ARG, "dia_attn_self_fp8: the blocked V layout (v_blocked) is required");
-  if (a->kv_cap <= 0 || a->kv_cap % 32 != 0) return dia_fail(DIA_E_ARG, "dia_attn_self_fp8: kv_cap must be a positive multiple of 32");
-  if (a->n_rows <= 0 || a->n_kv_heads <= 0) return dia_fail(DIA_E_ARG, "dia_attn_self_fp8: empty problem");
-  if (a->p_plane_stride % 8 != 0) return dia_fail(DIA_E_ARG, "dia_attn_self_fp8: plane stride must be a multiple of 8");
-  if (!a->cur) return dia_fail(DIA_E_ARG, "dia_attn_self_fp8: SELF needs cur");
-  if (a->group != 1 && a->group != 2 && a->group != 4) return dia_fail(DIA_E_ARG, "dia_attn_self_fp8: GQA group must be 1, 2 or 4");
-  if (a->rope_rows > 0 && a->kv_cap + 1 > a->rope_rows) return dia_fail(DIA_E_ARG, "dia_attn_self_fp8: RoPE tables shorter than the positions this launch can reach");
-  if ((a->n_kv_heads * a->group * 128 + 31) / 32 > a->p_ktiles) return dia_fail(DIA_E_ARG, "dia_attn_self_fp8: output planes too narrow");
-  if (((uintptr_t)f->k8 & 7) || ((uintptr_t)f->v8 & 7) || ((uintptr_t)f->ks & 3) || ((uintptr_t)f->vs & 3))
-    return dia_fail(DIA_E_ARG, "dia_attn_self_fp8: k8 / v8 must be 8-byte aligned, ks / vs 4-byte");
-  // the key split of dia_attn, so that the slabs merge in the same order
-  const int cap_chunks = (a->kv_cap + CHUNK - 1) / CHUNK;
-  int max_chunks = (512 + a->n_rows * a->n_kv_heads - 1) / (a->n_rows * a->n_kv_heads);
-  if (dia_tune(DIA_TUNE_ATTN_NZ) > 0) max_chunks = dia_tune(DIA_TUNE_ATTN_NZ);
-  if (max_chunks > cap_chunks) max_chunks = cap_chunks;
-  if (max_chunks < 1) max_chunks = 1;
-  if (max_chunks > 1 && (!a->scratch || !a->tickets)) return dia_fail(DIA_E_ARG, "dia_attn_self_fp8: more than 128 keys possible: scratch and tickets are required");
-  AttnK k = {};
-  k.mode = a->mode; k.n_kv_heads = a->n_kv_heads; k.n_rows = a->n_rows; k.kv_cap = a->kv_cap;
-  k.q = a->q; k.ldq = a->ldq; k.q_off = a->q_off; k.k_off = a->k_off; k.v_off = a->v_off;
-  k.cur = a->cur; k.len = a->cur;
-  k.cos_t = a->cos_t; k.sin_t = a->sin_t;
-  k.P = (bf16_raw*)a->P; k.p_plane_stride = a->p_plane_stride; k.p_ktiles = a->p_ktiles; k.act_f32 = a->act_f32;
-  k.head_map = a->head_map; k.v_blocked = 1;
-  k.gpw = 1;
-  { const int g = dia_tune(DIA_TUNE_ATTN_GPW); if (g > 0) k.gpw = g; }
-  k.scratch = a->scratch; k.tickets = a->tickets; k.max_chunks = cap_chunks;
+  static const AttnEntry E = {"dia_attn_self_fp8", true, false,            // (kc / vc: there is no bf16 cache, NULL is fine)
+    [](const dia_attn_args* a) -> const char* {
+      if (a->mode != DIA_ATTN_SELF) return "mode must be DIA_ATTN_SELF";
+      if (a->kv_dtype != DIA_KV_BF16) return "kv_dtype must be DIA_KV_BF16 (one plane)";
+      return !a->v_blocked ? "the blocked V layout (v_blocked) is required" : nullptr; },
+    [](const dia_attn_args* a) -> const char* {
+      if (!a->cur) return "SELF needs cur";
+      return a->group != 1 && a->group != 2 && a->group != 4 ? "GQA group must be 1, 2 or 4" : nullptr; }};
+  AttnK k; int max_chunks;
+  if (const int rc = attn_front(E, a, f, k, max_chunks)) return rc;
+  k.len = a->cur;
   const AttnF8W f8 = {(uint8_t*)f->k8, (uint8_t*)f->v8, f->ks, f->vs};
   const dim3 grid(a->n_kv_heads, a->n_rows, max_chunks);
   hipStream_t st = (hipStream_t)stream;

@@ -10,6 +10,7 @@
 #include "launch.hpp"
 #include "tuning.hpp"
 #include <cstdlib>
+#include <string>
 #include <vector>
 #include <algorithm>
 #include <utility>
@@ -684,17 +685,24 @@ extern "C" int dia_engine_set_lora(dia_engine* e, const dia_lora_step* s) {
   return DIA_OK;
 }
 
-extern "C" int dia_engine_set_cross_fp8(dia_engine* e, const dia_kv_fp8_ptrs* layers) {
-  if (!e) return dia_fail(DIA_E_ARG, "dia_engine_set_cross_fp8: null engine");
-  if (e->exec || e->launches > 0) return dia_fail(DIA_E_STATE, "dia_engine_set_cross_fp8: a step has already been issued or captured");
-  if (!layers) { e->f8kv.clear(); return DIA_OK; }
+// dia_engine_set_cross_fp8 / dia_engine_set_self_fp8: the e4m3 caches of every layer, over a capacity (S or T) of whole 32-key granules
+static int set_kv_fp8(const char* who, dia_engine* e, const dia_kv_fp8_ptrs* layers, char cap_name, int32_t dia_engine_desc::*cap,
+                      std::vector<dia_kv_fp8_ptrs> dia_engine::*into) {
+  auto fail = [&](int code, const std::string& what) { return dia_fail(code, (std::string(who) + ": " + what).c_str()); };
+  if (!e) return fail(DIA_E_ARG, "null engine");
+  if (e->exec || e->launches > 0) return fail(DIA_E_STATE, "a step has already been issued or captured");
+  if (!layers) { (e->*into).clear(); return DIA_OK; }
   const dia_engine_desc& d = e->d;
-  if (d.kv_dtype != DIA_KV_BF16 || !d.v_blocked || d.S <= 0 || d.S % 32 != 0)
-    return dia_fail(DIA_E_ARG, "dia_engine_set_cross_fp8: the engine needs bf16 K/V (DIA_KV_BF16) with the blocked V layout and S % 32 == 0");
+  if (d.kv_dtype != DIA_KV_BF16 || !d.v_blocked || d.*cap <= 0 || d.*cap % 32 != 0)
+    return fail(DIA_E_ARG, std::string("the engine needs bf16 K/V (DIA_KV_BF16) with the blocked V layout and ") + cap_name + " % 32 == 0");
   for (int l = 0; l < d.n_layer; ++l)
-    if (!layers[l].k8 || !layers[l].v8 || !layers[l].ks || !layers[l].vs) return dia_fail(DIA_E_ARG, "dia_engine_set_cross_fp8: null buffer in a layer");
-  e->f8kv.assign(layers, layers + d.n_layer);
+    if (!layers[l].k8 || !layers[l].v8 || !layers[l].ks || !layers[l].vs) return fail(DIA_E_ARG, "null buffer in a layer");
+  (e->*into).assign(layers, layers + d.n_layer);
   return DIA_OK;
+}
+
+extern "C" int dia_engine_set_cross_fp8(dia_engine* e, const dia_kv_fp8_ptrs* layers) {
+  return set_kv_fp8("dia_engine_set_cross_fp8", e, layers, 'S', &dia_engine_desc::S, &dia_engine::f8kv);
 }
 
 extern "C" int dia_engine_set_prefetch(dia_engine* e, int lookahead) {
@@ -705,14 +713,5 @@ extern "C" int dia_engine_set_prefetch(dia_engine* e, int lookahead) {
 }
 
 extern "C" int dia_engine_set_self_fp8(dia_engine* e, const dia_kv_fp8_ptrs* layers) {
-  if (!e) return dia_fail(DIA_E_ARG, "dia_engine_set_self_fp8: null engine");
-  if (e->exec || e->launches > 0) return dia_fail(DIA_E_STATE, "dia_engine_set_self_fp8: a step has already been issued or captured");
-  if (!layers) { e->f8self.clear(); return DIA_OK; }
-  const dia_engine_desc& d = e->d;
-  if (d.kv_dtype != DIA_KV_BF16 || !d.v_blocked || d.T <= 0 || d.T % 32 != 0)
-    return dia_fail(DIA_E_ARG, "dia_engine_set_self_fp8: the engine needs bf16 K/V (DIA_KV_BF16) with the blocked V layout and T % 32 == 0");
-  for (int l = 0; l < d.n_layer; ++l)
-    if (!layers[l].k8 || !layers[l].v8 || !layers[l].ks || !layers[l].vs) return dia_fail(DIA_E_ARG, "dia_engine_set_self_fp8: null buffer in a layer");
-  e->f8self.assign(layers, layers + d.n_layer);
-  return DIA_OK;
+  return set_kv_fp8("dia_engine_set_self_fp8", e, layers, 'T', &dia_engine_desc::T, &dia_engine::f8self);
 }

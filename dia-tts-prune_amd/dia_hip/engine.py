@@ -493,6 +493,28 @@ class UtteranceResult:
     text_len: int
 
 
+class KvFp8Cache:
+    """An e4m3 K/V cache, all layers in one allocation per tensor: bytes k8 [n_layer, rows, heads, cap, 128] and v8 (the blocked V layout,
+    [.., cap / 32, 128, 32]), fp32 scales per key ks / vs [n_layer, rows, heads, cap].  Zeroed once: a key that was never written, or is
+    left over in a re-used slot, is finite bytes times a finite scale."""
+
+    def __init__(self, n_layer: int, rows: int, heads: int, cap: int, device=None):
+        z = lambda *s, dt: torch.zeros(n_layer, rows, heads, *s, dtype=dt, device=device)
+        self.k8, self.v8 = z(cap, HEAD_DIM, dt=torch.uint8), z(cap // 32, HEAD_DIM, 32, dt=torch.uint8)
+        self.ks, self.vs = z(cap, dt=torch.float32), z(cap, dt=torch.float32)
+
+    def ptrs(self, layer: Optional[int] = None) -> hb.KvFp8Ptrs:        # the whole allocation, or one layer's view of it
+        k8, v8, ks, vs = (t if layer is None else t[layer] for t in (self.k8, self.v8, self.ks, self.vs))
+        return hb.KvFp8Ptrs(k8=hb.ptr(k8), v8=hb.ptr(v8), ks=hb.ptr(ks), vs=hb.ptr(vs))
+
+    def ptr_array(self):        # every layer's pointers, as dia_engine_set_cross_fp8 / _self_fp8 take them (the engine copies the array)
+        return (hb.KvFp8Ptrs * len(self.k8))(*[self.ptrs(i) for i in range(len(self.k8))])
+
+    @property
+    def nbytes(self) -> int:
+        return sum(t.numel() * t.element_size() for t in (self.k8, self.v8, self.ks, self.vs))
+
+
 class DecodeSession:
     """Buffers + engine for one batch of utterances."""
 
@@ -629,32 +651,19 @@ class DecodeSession:
         self.ld_logits = w.logits.ns * 16
         self.logits = z(self.rows_pad, self.ld_logits)
         pl = (self.kv_planes,) if self.kv_planes > 1 else ()           # two-plane caches: [plane][...]
-        # self_kv="fp8": the self caches ARE four e4m3 buffers (all layers in one allocation each), no bf16 cache beside them.  Zeroed
-        # once: a key that was never written, or is left over in a re-used slot, is finite bytes times a finite scale
-        self.k8_self_all = self.v8_self_all = self.ks_self_all = self.vs_self_all = None
-        if self_kv == "fp8":
-            self.k_self = self.v_self = [None] * d.n_layer
-            self.k8_self_all = z(d.n_layer, self.R, d.kv_heads, self.T, HEAD_DIM, dt=torch.uint8)
-            self.v8_self_all = z(d.n_layer, self.R, d.kv_heads, self.T // 32, HEAD_DIM, 32, dt=torch.uint8)
-            self.ks_self_all = z(d.n_layer, self.R, d.kv_heads, self.T)
-            self.vs_self_all = z(d.n_layer, self.R, d.kv_heads, self.T)
-        else:
-            self.k_self = [z(*pl, self.R, d.kv_heads, self.T, HEAD_DIM, dt=kvt) for _ in range(d.n_layer)]
-            self.v_self = [z(*pl, self.R, d.kv_heads, self.T, HEAD_DIM, dt=kvt) for _ in range(d.n_layer)]
+        # self_kv="fp8": the self caches ARE an e4m3 cache, no bf16 cache beside it
+        self.f8_self = KvFp8Cache(d.n_layer, self.R, d.kv_heads, self.T, dev) if self_kv == "fp8" else None
+        self.k_self = [None if self.f8_self else z(*pl, self.R, d.kv_heads, self.T, HEAD_DIM, dt=kvt) for _ in range(d.n_layer)]
+        self.v_self = [None if self.f8_self else z(*pl, self.R, d.kv_heads, self.T, HEAD_DIM, dt=kvt) for _ in range(d.n_layer)]
         # cross caches of all layers in ONE allocation each (per-layer views): the prefill's merged cross-K/V launch addresses a layer
         # as kc + layer * kv_layer_stride
         self.k_cross_all = z(d.n_layer, *pl, B, d.cross_query_heads, self.S, HEAD_DIM, dt=kvt)
         self.v_cross_all = z(d.n_layer, *pl, B, d.cross_query_heads, self.S, HEAD_DIM, dt=kvt)
         self.k_cross = [self.k_cross_all[i] for i in range(d.n_layer)]
         self.v_cross = [self.v_cross_all[i] for i in range(d.n_layer)]
-        # cross_kv="fp8": the e4m3 copy the step's cross-attention reads, all layers in one allocation each like the bf16 caches (which
-        # stay: +50 % cross-cache memory); zero bytes and zero scales until dia_kv_quantize_fp8 writes a row's granules
-        self.k8_cross_all = self.v8_cross_all = self.ks_cross_all = self.vs_cross_all = None
-        if cross_kv == "fp8":
-            self.k8_cross_all = z(d.n_layer, B, d.cross_query_heads, self.S, HEAD_DIM, dt=torch.uint8)
-            self.v8_cross_all = z(d.n_layer, B, d.cross_query_heads, self.S // 32, HEAD_DIM, 32, dt=torch.uint8)
-            self.ks_cross_all = z(d.n_layer, B, d.cross_query_heads, self.S)
-            self.vs_cross_all = z(d.n_layer, B, d.cross_query_heads, self.S)
+        # cross_kv="fp8": the e4m3 copy the step's cross-attention reads, beside the bf16 caches (which stay: +50 % cross-cache memory);
+        # zero bytes and zero scales until dia_kv_quantize_fp8 writes a row's granules
+        self.f8_cross = KvFp8Cache(d.n_layer, B, d.cross_query_heads, self.S, dev) if cross_kv == "fp8" else None
         self.kv_plane_self = self.R * d.kv_heads * self.T * HEAD_DIM if self.kv_planes > 1 else 0
         self.kv_plane_cross = B * d.cross_query_heads * self.S * HEAD_DIM if self.kv_planes > 1 else 0
         self.text_len = torch.tensor(self.lens, dtype=torch.int32, device=dev)
@@ -873,18 +882,10 @@ class DecodeSession:
                  "dia_engine_create")
         if self.x_alt is not None:
             hb.check(hb.lib().dia_engine_set_x_alt(self._engine, hb.ptr(self.x_alt)), "dia_engine_set_x_alt")
-        if self.cross_kv == "fp8":                                          # the step's cross-attention reads the e4m3 copy
-            f8 = (hb.KvFp8Ptrs * n)()                                       # (the engine copies the array)
-            for i in range(n):
-                f8[i].k8, f8[i].v8 = hb.ptr(self.k8_cross_all[i]), hb.ptr(self.v8_cross_all[i])
-                f8[i].ks, f8[i].vs = hb.ptr(self.ks_cross_all[i]), hb.ptr(self.vs_cross_all[i])
-            hb.check(hb.lib().dia_engine_set_cross_fp8(self._engine, f8), "dia_engine_set_cross_fp8")
-        if self.self_kv == "fp8":                                           # the step's self-attention appends to and reads the e4m3 caches
-            f8 = (hb.KvFp8Ptrs * n)()
-            for i in range(n):
-                f8[i].k8, f8[i].v8 = hb.ptr(self.k8_self_all[i]), hb.ptr(self.v8_self_all[i])
-                f8[i].ks, f8[i].vs = hb.ptr(self.ks_self_all[i]), hb.ptr(self.vs_self_all[i])
-            hb.check(hb.lib().dia_engine_set_self_fp8(self._engine, f8), "dia_engine_set_self_fp8")
+        if self.f8_cross is not None:                                       # the step's cross-attention reads the e4m3 copy
+            hb.check(hb.lib().dia_engine_set_cross_fp8(self._engine, self.f8_cross.ptr_array()), "dia_engine_set_cross_fp8")
+        if self.f8_self is not None:                                        # the step's self-attention appends to and reads the e4m3 caches
+            hb.check(hb.lib().dia_engine_set_self_fp8(self._engine, self.f8_self.ptr_array()), "dia_engine_set_self_fp8")
         if w.quant == "mxfp4":                                              # MXFP4 streams (quant="mxfp4"): beside the description
             f4_layers = (hb.Mxfp4Layer * n)()                               # (the engine copies the array)
             for i, L in enumerate(w.dec_layers):
@@ -1098,8 +1099,7 @@ class DecodeSession:
             rows, ln = list(utt[i0: i0 + hb.SLOTS_PER_CALL]), list(lens[i0: i0 + hb.SLOTS_PER_CALL])
             a = hb.KvFp8Args()
             a.kc, a.vc = hb.ptr(self.k_cross_all), hb.ptr(self.v_cross_all)
-            a.out.k8, a.out.v8 = hb.ptr(self.k8_cross_all), hb.ptr(self.v8_cross_all)
-            a.out.ks, a.out.vs = hb.ptr(self.ks_cross_all), hb.ptr(self.vs_cross_all)
+            a.out = self.f8_cross.ptrs()
             a.B, a.heads, a.S, a.n = self.B, d.cross_query_heads, self.S, len(rows)
             a.row, a.len = (C.c_int32 * len(rows))(*rows), (C.c_int32 * len(rows))(*ln)
             a.n_layer = d.n_layer
@@ -1189,8 +1189,7 @@ class DecodeSession:
             a.q_heads, a.kv_heads, a.kv_cap, a.causal = QH, KVH, self.T, 1
             a.P, a.p_plane_stride, a.p_ktiles = _plane_set(pa, akt)
             if fp8:                                 # kc == vc == NULL: the e4m3 caches are the only self caches
-                f8 = hb.KvFp8Ptrs(k8=hb.ptr(self.k8_self_all[i]), v8=hb.ptr(self.v8_self_all[i]),
-                                  ks=hb.ptr(self.ks_self_all[i]), vs=hb.ptr(self.vs_self_all[i]))
+                f8 = self.f8_self.ptrs(i)
                 hb.check(L.dia_dec_prefill_kv_fp8(C.byref(a), C.byref(f8), st), "dia_dec_prefill_kv_fp8")
                 hb.check(L.dia_dec_prefill_attn_fp8(C.byref(a), C.byref(f8), st), "dia_dec_prefill_attn_fp8")
             else:
@@ -1786,8 +1785,8 @@ class DecodeSession:
     def self_cache_bytes(self) -> int:
         """Bytes of the self K/V caches of all layers and rows as allocated: bf16 / fp32 K and V, or (self_kv="fp8") the e4m3 bytes
         and their scales — (1 + 1/32) / 2 of the bf16 caches at the same R and T."""
-        if self.self_kv == "fp8":
-            return sum(t.numel() * t.element_size() for t in (self.k8_self_all, self.v8_self_all, self.ks_self_all, self.vs_self_all))
+        if self.f8_self is not None:
+            return self.f8_self.nbytes
         return sum(t.numel() * t.element_size() for t in self.k_self + self.v_self)
 
     def step_bytes(self, n_keys: Optional[int] = None) -> int:

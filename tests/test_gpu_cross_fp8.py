@@ -254,13 +254,13 @@ def test_model_equals_bf16_session_over_the_dequantised_caches(mid, graph):
         for r, n in enumerate(f.lens):
             end = -(-n // 32) * 32
             qk, sk = quantize_kv_fp8(f.k_cross_all[:, r, :, :n].cpu())
-            vb = f.v_cross_all[:, r].reshape(f.v8_cross_all[:, r].shape)          # (the bf16 V cache is allocated [.., S, 128] and holds the blocked order)
+            vb = f.v_cross_all[:, r].reshape(f.f8_cross.v8[:, r].shape)           # (the bf16 V cache is allocated [.., S, 128] and holds the blocked order)
             qv, sv = quantize_kv_fp8(lay.v_from_blocked(vb).cpu()[:, :, :n])
-            assert torch.equal(f.k8_cross_all[:, r, :, :n].cpu(), qk) and torch.equal(f.ks_cross_all[:, r, :, :n].cpu(), sk)
-            assert torch.equal(lay.v_from_blocked(f.v8_cross_all[:, r]).cpu()[:, :, :n], qv) and torch.equal(f.vs_cross_all[:, r, :, :n].cpu(), sv)
-            assert (f.k8_cross_all[:, r, :, n:] == 0).all() and (f.ks_cross_all[:, r, :, n:end] == 1).all() and (f.ks_cross_all[:, r, :, end:] == 0).all()
-        kd = dequantize_kv_fp8(f.k8_cross_all.cpu(), f.ks_cross_all.cpu())
-        vd = dequantize_kv_fp8(lay.v_from_blocked(f.v8_cross_all).cpu(), f.vs_cross_all.cpu())
+            assert torch.equal(f.f8_cross.k8[:, r, :, :n].cpu(), qk) and torch.equal(f.f8_cross.ks[:, r, :, :n].cpu(), sk)
+            assert torch.equal(lay.v_from_blocked(f.f8_cross.v8[:, r]).cpu()[:, :, :n], qv) and torch.equal(f.f8_cross.vs[:, r, :, :n].cpu(), sv)
+            assert (f.f8_cross.k8[:, r, :, n:] == 0).all() and (f.f8_cross.ks[:, r, :, n:end] == 1).all() and (f.f8_cross.ks[:, r, :, end:] == 0).all()
+        kd = dequantize_kv_fp8(f.f8_cross.k8.cpu(), f.f8_cross.ks.cpu())
+        vd = dequantize_kv_fp8(lay.v_from_blocked(f.f8_cross.v8).cpu(), f.f8_cross.vs.cpu())
         with torch.cuda.stream(b.stream):
             b.k_cross_all.copy_(kd.bfloat16().to(dev()))
             b.v_cross_all.copy_(lay.v_to_blocked(vd.bfloat16()).reshape(b.v_cross_all.shape).to(dev()))
@@ -301,8 +301,8 @@ def test_slots_equal_solo_runs(mid):
     s = session()
     try:
         out = s.serve(reqs[:2], poll=4) + s.serve(reqs[2:], poll=4)
-        assert (s.k8_cross_all[:, 0, :, 9:32] == 0).all() and (s.ks_cross_all[:, 0, :, 9:32] == 1).all()
-        assert (s.k8_cross_all[:, 0, :, 32:60] != 0).any()            # the longer text's second granule is still there, unread
+        assert (s.f8_cross.k8[:, 0, :, 9:32] == 0).all() and (s.f8_cross.ks[:, 0, :, 9:32] == 1).all()
+        assert (s.f8_cross.k8[:, 0, :, 32:60] != 0).any()            # the longer text's second granule is still there, unread
     finally:
         s.close()
     for r, got in zip(reqs, out):
@@ -339,7 +339,7 @@ def test_refusals_and_the_default_session(mid):
     # the default keyword: no fp8 buffer, the kernels of a session that was never told about the keyword
     s = DecodeSession(w, ids, kv_dtype="bf16", max_tokens=8, seeds=[1])
     try:
-        assert s.cross_kv == "bf16" and s.k8_cross_all is None
+        assert s.cross_kv == "bf16" and s.f8_cross is None
         s.prefill()
         s.time_step()
         names = list(s.last_kernel_names)

@@ -47,8 +47,8 @@ def self_caches(s, b, n):
     """the fp8 self caches of utterance b (both CFG rows), keys [0, n), on the host: k8, v8 in key order, ks, vs"""
     from dia_hip import layout as lay
     rows = slice(2 * b, 2 * b + 2)
-    return [s.k8_self_all[:, rows, :, :n].cpu(), lay.v_from_blocked(s.v8_self_all[:, rows]).cpu()[:, :, :, :n],
-            s.ks_self_all[:, rows, :, :n].cpu(), s.vs_self_all[:, rows, :, :n].cpu()]
+    return [s.f8_self.k8[:, rows, :, :n].cpu(), lay.v_from_blocked(s.f8_self.v8[:, rows]).cpu()[:, :, :, :n],
+            s.f8_self.ks[:, rows, :, :n].cpu(), s.f8_self.vs[:, rows, :, :n].cpu()]
 
 
 def test_closed_fp8_session_batched_against_replay(mid):

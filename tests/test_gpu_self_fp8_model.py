@@ -70,7 +70,7 @@ def test_default_session_enqueues_the_parents_kernels(mid):
     assert names_kw == names_no and not any("self_f8" in n for n in names_kw)
     s = DecodeSession(w, [ids_of(12, 1)], kv_dtype="bf16", max_tokens=8)
     try:
-        assert s.self_kv == "bf16" and s.k8_self_all is None and s.k_self[0] is not None
+        assert s.self_kv == "bf16" and s.f8_self is None and s.k_self[0] is not None
     finally:
         s.close()
 
@@ -90,7 +90,7 @@ def test_slots_equal_solo_runs(mid):
     s = session()
     try:
         out = s.serve(reqs, poll=4)
-        assert s.k_self[0] is None and (s.ks_self_all != 0).any()
+        assert s.k_self[0] is None and (s.f8_self.ks != 0).any()
     finally:
         s.close()
     for r, got in zip(reqs, out):
@@ -182,12 +182,12 @@ def test_self_cache_bytes_and_engine_refusals(mid):
         assert ratio == (1 + 1 / 32) / 2 and ratio <= 0.52
         assert f.step_bytes(100) < b.step_bytes(100)
         assert all(t is None for t in f.k_self + f.v_self) and f._layers[0].k_self is None and f._layers[0].v_self is None
-        assert all(int(t.count_nonzero()) == 0 for t in (f.k8_self_all, f.v8_self_all, f.ks_self_all, f.vs_self_all))     # zeroed once
+        assert all(int(t.count_nonzero()) == 0 for t in (f.f8_self.k8, f.f8_self.v8, f.f8_self.ks, f.f8_self.vs))     # zeroed once
         f.prefill()
         f.decode(1)
         f.sync()
         assert hb.lib().dia_engine_set_self_fp8(f._engine, None) == -3          # DIA_E_STATE: a step has been issued
-        assert (f.ks_self_all[:, :, :, 0] > 0).all() and (f.ks_self_all[:, :, :, 1:] == 0).all()      # one key per row, head and layer
+        assert (f.f8_self.ks[:, :, :, 0] > 0).all() and (f.f8_self.ks[:, :, :, 1:] == 0).all()      # one key per row, head and layer
     finally:
         f.close()
         b.close()
