@@ -17,6 +17,7 @@
 // The output leaves as three bf16 planes in MFMA A-operand order for the o_proj GEMM.
 #include "common.hpp"
 #include "kv_fp8.hpp"
+#include "attn_tile.hpp"
 #include "../../include/dia_hip.h"
 #include "errors.hpp"
 #include "launch.hpp"
@@ -365,14 +366,6 @@ __global__ __launch_bounds__(NT) void k_attn(AttnK p) {
   __syncthreads();
 
   attn_finish<G>(p, part, pm_s, pl_s, &last_s, tid, qrow, kvh, head_row, chunk, nchunks);
-}
-
-__device__ __forceinline__ float row16_max(float v) {
-  v = fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true)));
-  v = fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true)));
-  v = fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, true)));
-  v = fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xF, 0xF, true)));
-  return v;
 }
 
 // bf16 K/V caches, MFMA arithmetic.  Keys are dealt to WAVES in granules of 32: granule g goes to wave
@@ -1129,7 +1122,8 @@ __global__ __launch_bounds__(NT, 2) void k_attn_self_f8(AttnK p, AttnF8W f8) {
 //   k_attn_enc_mfma   grid (head, 16-row query tile): S = Q.K^T and O = P.V on MFMA, every operand as three
 //                     planes -> 9 MFMAs per 16x16x32 product, fp32-exact products; 4 waves split the keys in
 //                     32-key granules, online softmax per query row (rows of a wave's 16x16 tiles live in the
-//                     four 16-lane groups), waves merged through LDS.
+//                     four 16-lane groups), waves merged through LDS.  The q staging, the softmax step and the merge are
+//                     attn_tile.hpp's, shared with the prompt prefill (prefill.hip); the K / V loads and MFMAs are here.
 // Rows are addressed through row_b[] (utterance of a packed row, -1 = padding), seg_off[] / seg_len[].
 struct EncAttnK {
   const float* qkv; int ldq, q_off, k_off, v_off, heads, rows;
@@ -1206,10 +1200,7 @@ __global__ __launch_bounds__(256) void k_enc_kv_planes(EncAttnK p) {
 }
 
 __global__ __launch_bounds__(NT) void k_attn_enc_mfma(EncAttnK p) {
-  __shared__ __attribute__((aligned(16))) bf16_raw qf[4][DIA_NPLANES][16][4][8];     // q planes, A-fragment order
-  __shared__ __attribute__((aligned(16))) bf16_raw pbuf[NWV][DIA_NPLANES][16][32];   // p planes per wave
-  __shared__ float part[NWV * 16 * HD];
-  __shared__ float pm_s[NWV * 16], pl_s[NWV * 16];
+  __shared__ __attribute__((aligned(16))) AttnTile tile;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int h = blockIdx.x, qt = blockIdx.y;
   const int arow = lane & 15, akq = lane >> 4;
@@ -1217,31 +1208,12 @@ __global__ __launch_bounds__(NT) void k_attn_enc_mfma(EncAttnK p) {
   if (b < 0) return;                                   // a tile of padding rows (tiles never straddle utterances)
   const int off = p.seg_off[b], len = p.seg_len[b];
   const long plane = (long)p.heads * p.rows * HD;
-
-  // ---- RoPE(q) of the 16 rows -> three planes in LDS: thread (row = tid>>4, 8 dim pairs)
   {
-    const int r = tid >> 4, m = qt * 16 + r, pos = min(m - off, len - 1);       // rows past the end: recomputed, never emitted
-    const float* qh = p.qkv + (long)min(m, off + len - 1) * p.ldq + p.q_off + h * HD;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int d = (tid & 15) * 4 + i;
-      const float x1 = qh[d], x2 = qh[d + 64];
-      const float c = p.cos_t[(long)pos * 64 + d], s = p.sin_t[(long)pos * 64 + d];
-      const float qv[2] = {x1 * c - x2 * s, x1 * s + x2 * c};
-#pragma unroll
-      for (int e = 0; e < 2; ++e) {
-        const int D = d + 64 * e;
-        __bf16 a, bb, c3;
-        split3(qv[e], a, bb, c3);
-        qf[D >> 5][0][r][(D >> 3) & 3][D & 7] = *reinterpret_cast<const bf16_raw*>(&a);
-        qf[D >> 5][1][r][(D >> 3) & 3][D & 7] = *reinterpret_cast<const bf16_raw*>(&bb);
-        qf[D >> 5][2][r][(D >> 3) & 3][D & 7] = *reinterpret_cast<const bf16_raw*>(&c3);
-      }
-    }
+    const int m = qt * 16 + (tid >> 4);                // rows past the end: the last row recomputed, never emitted
+    attn_tile_stage_q(tile, tid, p.qkv + (long)min(m, off + len - 1) * p.ldq + p.q_off + h * HD, min(m - off, len - 1), p.cos_t, p.sin_t);
   }
   __syncthreads();
 
-  const float scale = 0.08838834764831845f;
   f32x4 O[8];
 #pragma unroll
   for (int nb = 0; nb < 8; ++nb) O[nb] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -1250,15 +1222,16 @@ __global__ __launch_bounds__(NT) void k_attn_enc_mfma(EncAttnK p) {
   for (int r = 0; r < 4; ++r) { mrun[r] = -INFINITY; lrun[r] = 0.f; }
   const bf16_raw* Kh = p.kp + ((long)h * p.rows + off) * HD;
   const bf16_raw* Vh = p.vp + ((long)h * (p.rows >> 5) + (off >> 5)) * HD * 32;
+  const int lim[4] = {len, len, len, len};              // bidirectional: every row sees the utterance's len keys
   const int ngran = (len + 31) >> 5;
-  for (int g = w; g < ngran; g += NWV) {
+  for (int g = w; g < ngran; g += AttnTile::NWV) {
     const int key0 = g << 5;
     f32x4 S[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
       bf16x8 qa[DIA_NPLANES];
 #pragma unroll
-      for (int pl = 0; pl < DIA_NPLANES; ++pl) qa[pl] = *reinterpret_cast<const bf16x8*>(&qf[ks][pl][arow][akq][0]);
+      for (int pl = 0; pl < DIA_NPLANES; ++pl) qa[pl] = *reinterpret_cast<const bf16x8*>(&tile.qf[ks][pl][arow][akq][0]);
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
         const bf16_raw* kr = Kh + (long)(key0 + 16 * t + arow) * HD + 32 * ks + 8 * akq;   // rows < seg padded to 32: in bounds
@@ -1270,36 +1243,15 @@ __global__ __launch_bounds__(NT) void k_attn_enc_mfma(EncAttnK p) {
         }
       }
     }
-    // online softmax per query row: S[t][r] = score(row 4*akq + r, key key0 + 16t + arow)
     float alpha[4];
-    const bool v0 = key0 + arow < len, v1 = key0 + 16 + arow < len;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const float s0 = v0 ? S[0][r] * scale : -INFINITY, s1 = v1 ? S[1][r] * scale : -INFINITY;
-      const float mnew = fmaxf(mrun[r], row16_max(fmaxf(s0, s1)));
-      alpha[r] = (mrun[r] == -INFINITY) ? 0.f : expf(mrun[r] - mnew);
-      const float p0 = (s0 == -INFINITY) ? 0.f : expf(s0 - mnew), p1 = (s1 == -INFINITY) ? 0.f : expf(s1 - mnew);
-      lrun[r] = lrun[r] * alpha[r] + row16_sum(p0 + p1);
-      mrun[r] = mnew;
-      __bf16 a, bb, c3;
-      split3(p0, a, bb, c3);
-      pbuf[w][0][4 * akq + r][arow] = *reinterpret_cast<const bf16_raw*>(&a);
-      pbuf[w][1][4 * akq + r][arow] = *reinterpret_cast<const bf16_raw*>(&bb);
-      pbuf[w][2][4 * akq + r][arow] = *reinterpret_cast<const bf16_raw*>(&c3);
-      split3(p1, a, bb, c3);
-      pbuf[w][0][4 * akq + r][16 + arow] = *reinterpret_cast<const bf16_raw*>(&a);
-      pbuf[w][1][4 * akq + r][16 + arow] = *reinterpret_cast<const bf16_raw*>(&bb);
-      pbuf[w][2][4 * akq + r][16 + arow] = *reinterpret_cast<const bf16_raw*>(&c3);
-    }
-    __builtin_amdgcn_wave_barrier();
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    attn_tile_softmax<false>(tile, w, arow, akq, S, key0, lim, nullptr, nullptr, mrun, lrun, alpha);
 #pragma unroll
     for (int nb = 0; nb < 8; ++nb)
 #pragma unroll
       for (int r = 0; r < 4; ++r) O[nb][r] *= alpha[r];
     bf16x8 pa[DIA_NPLANES];
 #pragma unroll
-    for (int pl = 0; pl < DIA_NPLANES; ++pl) pa[pl] = *reinterpret_cast<const bf16x8*>(&pbuf[w][pl][arow][8 * akq]);
+    for (int pl = 0; pl < DIA_NPLANES; ++pl) pa[pl] = *reinterpret_cast<const bf16x8*>(&tile.pbuf[w][pl][arow][8 * akq]);
     const bf16_raw* Vblk = Vh + (long)g * HD * 32;
 #pragma unroll
     for (int nb = 0; nb < 8; ++nb) {
@@ -1313,34 +1265,7 @@ __global__ __launch_bounds__(NT) void k_attn_enc_mfma(EncAttnK p) {
     }
     __builtin_amdgcn_wave_barrier();     // pbuf is rewritten by the next granule
   }
-  // ---- merge the waves: lane holds dims 16*nb + arow of rows 4*akq + r
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-#pragma unroll
-    for (int nb = 0; nb < 8; ++nb) part[(w * 16 + 4 * akq + r) * HD + 16 * nb + arow] = O[nb][r];
-    if (arow == 0) { pm_s[w * 16 + 4 * akq + r] = mrun[r]; pl_s[w * 16 + 4 * akq + r] = lrun[r]; }
-  }
-  __syncthreads();
-  {
-    const int r = tid >> 4, d0 = (tid & 15) * 8, m = qt * 16 + r;
-    if (m - off >= len) return;                         // padding row inside the last tile of an utterance
-    float mm = -INFINITY;
-#pragma unroll
-    for (int ww = 0; ww < NWV; ++ww) mm = fmaxf(mm, pm_s[ww * 16 + r]);
-    float o[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, Ls = 0.f;
-#pragma unroll
-    for (int ww = 0; ww < NWV; ++ww) {
-      const float pmw = pm_s[ww * 16 + r];
-      const float f = (pmw == -INFINITY) ? 0.f : expf(pmw - mm);
-      Ls += pl_s[ww * 16 + r] * f;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) o[j] += part[(ww * 16 + r) * HD + d0 + j] * f;
-    }
-    const float inv = Ls > 0.f ? 1.0f / Ls : 0.f;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) o[j] *= inv;
-    emit_planes8(p.P, p.p_plane_stride, p.p_ktiles, m, h * HD + d0, o);
-  }
+  attn_tile_merge_emit<8>(tile, tid, O, mrun, lrun, qt * 16, off + len, p.P, p.p_plane_stride, p.p_ktiles, h * HD);
 }
 
 __global__ void k_enc_kv_prep(const float* qkv, int ldq, int k_off, int v_off, int heads, int L, int cap,

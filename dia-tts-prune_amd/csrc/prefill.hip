@@ -10,6 +10,7 @@
 // seg_off a multiple of 32; row_seg[m] = segment of packed row m or -1 (padding); seg_row[s] = 2b + c.
 #include "common.hpp"
 #include "kv_fp8.hpp"
+#include "attn_tile.hpp"
 #include "../../include/dia_hip.h"
 #include "errors.hpp"
 #include "launch.hpp"
@@ -86,25 +87,14 @@ __global__ __launch_bounds__(256) void k_prefill_kv(PrefK p) {
   }
 }
 
-__device__ __forceinline__ float row16_max_p(float v) {
-  v = fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true)));
-  v = fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true)));
-  v = fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, true)));
-  v = fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xF, 0xF, true)));
-  return v;
-}
-
 // Many-query attention over the bf16 caches: grid (query head, 16-row query tile).  q as three planes (exact),
 // K / V straight from the caches as single bf16 operands, p as three planes; 4 waves split the keys in 32-key
-// granules, online softmax per query row, waves merged through LDS (k_attn_enc_mfma with the caches as K/V).
+// granules, online softmax per query row, waves merged through LDS — k_attn_enc_mfma with the caches as K/V: the
+// q staging, the softmax step and the merge are the one copy in attn_tile.hpp, the K / V loads and MFMAs are here.
 // causal: query row r sees keys 0..r of its own cache row; else the cond segment sees the utterance's text keys
 // and the uncond segment gets exact zeros.
 __global__ __launch_bounds__(256) void k_prefill_attn(PrefK p) {
-  constexpr int NWV = 4;
-  __shared__ __attribute__((aligned(16))) bf16_raw qf[4][DIA_NPLANES][16][4][8];
-  __shared__ __attribute__((aligned(16))) bf16_raw pbuf[NWV][DIA_NPLANES][16][32];
-  __shared__ float part[NWV * 16 * HD];
-  __shared__ float pm_s[NWV * 16], pl_s[NWV * 16];
+  __shared__ __attribute__((aligned(16))) AttnTile tile;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int h = blockIdx.x, qt = blockIdx.y;
   const int arow = lane & 15, akq = lane >> 4;
@@ -130,43 +120,29 @@ __global__ __launch_bounds__(256) void k_prefill_attn(PrefK p) {
     Kh = p.kc + base; Vh = p.vc + base;
   }
   {
-    const int r = tid >> 4, m = min(qt * 16 + r, off + len - 1), pos = (m - off) + 1;
-    const float* qh = p.q + (long)m * p.ldq + p.q_off + h * HD;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int d = (tid & 15) * 4 + i;
-      const float x1 = qh[d], x2 = qh[d + 64];
-      const float c = p.cos_t[(long)pos * 64 + d], sn = p.sin_t[(long)pos * 64 + d];
-      const float qv[2] = {x1 * c - x2 * sn, x1 * sn + x2 * c};
-#pragma unroll
-      for (int e = 0; e < 2; ++e) {
-        const int D = d + 64 * e;
-        __bf16 a, bb, c3;
-        split3(qv[e], a, bb, c3);
-        qf[D >> 5][0][r][(D >> 3) & 3][D & 7] = *reinterpret_cast<const bf16_raw*>(&a);
-        qf[D >> 5][1][r][(D >> 3) & 3][D & 7] = *reinterpret_cast<const bf16_raw*>(&bb);
-        qf[D >> 5][2][r][(D >> 3) & 3][D & 7] = *reinterpret_cast<const bf16_raw*>(&c3);
-      }
-    }
+    const int m = min(qt * 16 + (tid >> 4), off + len - 1);
+    attn_tile_stage_q(tile, tid, p.q + (long)m * p.ldq + p.q_off + h * HD, (m - off) + 1, p.cos_t, p.sin_t);
   }
   __syncthreads();
-  const float scale = 0.08838834764831845f;
   f32x4 O[8];
 #pragma unroll
   for (int nb = 0; nb < 8; ++nb) O[nb] = f32x4{0.f, 0.f, 0.f, 0.f};
   float mrun[4], lrun[4];
 #pragma unroll
   for (int r = 0; r < 4; ++r) { mrun[r] = -INFINITY; lrun[r] = 0.f; }
+  int lim[4];                                         // keys query row 4*akq + r may see
+#pragma unroll
+  for (int r = 0; r < 4; ++r) lim[r] = p.causal ? min(nkeys, r0 + 4 * akq + r + 1) : nkeys;
   const int klast = max(nkeys - 1, 0);
   const int ngran = (nkeys + 31) >> 5;
-  for (int g = w; g < ngran; g += NWV) {
+  for (int g = w; g < ngran; g += AttnTile::NWV) {
     const int key0 = g << 5;
     f32x4 S[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
       bf16x8 qa[DIA_NPLANES];
 #pragma unroll
-      for (int pl = 0; pl < DIA_NPLANES; ++pl) qa[pl] = *reinterpret_cast<const bf16x8*>(&qf[ks][pl][arow][akq][0]);
+      for (int pl = 0; pl < DIA_NPLANES; ++pl) qa[pl] = *reinterpret_cast<const bf16x8*>(&tile.qf[ks][pl][arow][akq][0]);
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
         const bf16x8 kb = *reinterpret_cast<const bf16x8*>(Kh + (long)min(key0 + 16 * t + arow, klast) * HD + 32 * ks + 8 * akq);
@@ -175,35 +151,14 @@ __global__ __launch_bounds__(256) void k_prefill_attn(PrefK p) {
       }
     }
     float alpha[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int lim = p.causal ? min(nkeys, r0 + 4 * akq + r + 1) : nkeys;      // keys this query row may see
-      const bool v0 = key0 + arow < lim, v1 = key0 + 16 + arow < lim;
-      const float s0 = v0 ? S[0][r] * scale : -INFINITY, s1 = v1 ? S[1][r] * scale : -INFINITY;
-      const float mnew = fmaxf(mrun[r], row16_max_p(fmaxf(s0, s1)));
-      alpha[r] = (mrun[r] == -INFINITY) ? 0.f : expf(mrun[r] - mnew);
-      const float p0 = (s0 == -INFINITY) ? 0.f : expf(s0 - mnew), p1 = (s1 == -INFINITY) ? 0.f : expf(s1 - mnew);
-      lrun[r] = lrun[r] * alpha[r] + row16_sum(p0 + p1);
-      mrun[r] = mnew;
-      __bf16 a, bb, c3;
-      split3(p0, a, bb, c3);
-      pbuf[w][0][4 * akq + r][arow] = *reinterpret_cast<const bf16_raw*>(&a);
-      pbuf[w][1][4 * akq + r][arow] = *reinterpret_cast<const bf16_raw*>(&bb);
-      pbuf[w][2][4 * akq + r][arow] = *reinterpret_cast<const bf16_raw*>(&c3);
-      split3(p1, a, bb, c3);
-      pbuf[w][0][4 * akq + r][16 + arow] = *reinterpret_cast<const bf16_raw*>(&a);
-      pbuf[w][1][4 * akq + r][16 + arow] = *reinterpret_cast<const bf16_raw*>(&bb);
-      pbuf[w][2][4 * akq + r][16 + arow] = *reinterpret_cast<const bf16_raw*>(&c3);
-    }
-    __builtin_amdgcn_wave_barrier();
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    attn_tile_softmax<false>(tile, w, arow, akq, S, key0, lim, nullptr, nullptr, mrun, lrun, alpha);
 #pragma unroll
     for (int nb = 0; nb < 8; ++nb)
 #pragma unroll
       for (int r = 0; r < 4; ++r) O[nb][r] *= alpha[r];
     bf16x8 pa[DIA_NPLANES];
 #pragma unroll
-    for (int pl = 0; pl < DIA_NPLANES; ++pl) pa[pl] = *reinterpret_cast<const bf16x8*>(&pbuf[w][pl][arow][8 * akq]);
+    for (int pl = 0; pl < DIA_NPLANES; ++pl) pa[pl] = *reinterpret_cast<const bf16x8*>(&tile.pbuf[w][pl][arow][8 * akq]);
     const bf16_raw* Vblk = Vh + (long)g * HD * 32;
 #pragma unroll
     for (int nb = 0; nb < 8; ++nb) {
@@ -213,33 +168,7 @@ __global__ __launch_bounds__(256) void k_prefill_attn(PrefK p) {
     }
     __builtin_amdgcn_wave_barrier();
   }
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-#pragma unroll
-    for (int nb = 0; nb < 8; ++nb) part[(w * 16 + 4 * akq + r) * HD + 16 * nb + arow] = O[nb][r];
-    if (arow == 0) { pm_s[w * 16 + 4 * akq + r] = mrun[r]; pl_s[w * 16 + 4 * akq + r] = lrun[r]; }
-  }
-  __syncthreads();
-  {
-    const int r = tid >> 4, d0 = (tid & 15) * 8, m = qt * 16 + r;
-    if (m - off >= len) return;
-    float mm = -INFINITY;
-#pragma unroll
-    for (int ww = 0; ww < NWV; ++ww) mm = fmaxf(mm, pm_s[ww * 16 + r]);
-    float o[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, Ls = 0.f;
-#pragma unroll
-    for (int ww = 0; ww < NWV; ++ww) {
-      const float pmw = pm_s[ww * 16 + r];
-      const float f = (pmw == -INFINITY) ? 0.f : expf(pmw - mm);
-      Ls += pl_s[ww * 16 + r] * f;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) o[j] += part[(ww * 16 + r) * HD + d0 + j] * f;
-    }
-    const float inv = Ls > 0.f ? 1.0f / Ls : 0.f;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) o[j] *= inv;
-    emit_planes8(p.P, p.p_plane_stride, p.p_ktiles, m, h * HD + d0, o);
-  }
+  attn_tile_merge_emit<6>(tile, tid, O, mrun, lrun, qt * 16, off + len, p.P, p.p_plane_stride, p.p_ktiles, h * HD);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -301,14 +230,11 @@ __global__ __launch_bounds__(256) void k_prefill_kv_f8(PrefK p, PrefF8 f8) {
 // k_prefill_attn (causal) over the e4m3 self caches: 8-byte K / V fragments expanded to bf16 in registers (exact), the scales folded
 // in behind the MFMAs — S[key] *= ks[key] before the softmax scale and the mask, p[key] *= vs[key] before split3, lrun from the
 // unscaled p.  The scales are powers of two, so every MFMA receives products equal to those of k_prefill_attn over bf16 caches
-// holding the dequantised values and the output is the same bit for bit (as long as p * vs is a normal fp32).  A lane holds the score
+// holding the dequantised values and the output is the same bit for bit (as long as p * vs is a normal fp32): everything else that
+// rounds — q staging, softmax step, wave merge — is the same attn_tile.hpp code in both kernels.  A lane holds the score
 // of key key0 + 16t + arow in S[t][.], so it loads that key's two scales; the clamped re-read of klast clamps the K scale index too.
 __global__ __launch_bounds__(256) void k_prefill_attn_f8(PrefK p, PrefF8 f8) {
-  constexpr int NWV = 4;
-  __shared__ __attribute__((aligned(16))) bf16_raw qf[4][DIA_NPLANES][16][4][8];
-  __shared__ __attribute__((aligned(16))) bf16_raw pbuf[NWV][DIA_NPLANES][16][32];
-  __shared__ float part[NWV * 16 * HD];
-  __shared__ float pm_s[NWV * 16], pl_s[NWV * 16];
+  __shared__ __attribute__((aligned(16))) AttnTile tile;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int h = blockIdx.x, qt = blockIdx.y;
   const int arow = lane & 15, akq = lane >> 4;
@@ -324,36 +250,22 @@ __global__ __launch_bounds__(256) void k_prefill_attn_f8(PrefK p, PrefF8 f8) {
   const float* KS = f8.ks + pair_keys;
   const float* VS = f8.vs + pair_keys;
   {
-    const int r = tid >> 4, m = min(qt * 16 + r, off + len - 1), pos = (m - off) + 1;
-    const float* qh = p.q + (long)m * p.ldq + p.q_off + h * HD;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int d = (tid & 15) * 4 + i;
-      const float x1 = qh[d], x2 = qh[d + 64];
-      const float c = p.cos_t[(long)pos * 64 + d], sn = p.sin_t[(long)pos * 64 + d];
-      const float qv[2] = {x1 * c - x2 * sn, x1 * sn + x2 * c};
-#pragma unroll
-      for (int e = 0; e < 2; ++e) {
-        const int D = d + 64 * e;
-        __bf16 a, bb, c3;
-        split3(qv[e], a, bb, c3);
-        qf[D >> 5][0][r][(D >> 3) & 3][D & 7] = *reinterpret_cast<const bf16_raw*>(&a);
-        qf[D >> 5][1][r][(D >> 3) & 3][D & 7] = *reinterpret_cast<const bf16_raw*>(&bb);
-        qf[D >> 5][2][r][(D >> 3) & 3][D & 7] = *reinterpret_cast<const bf16_raw*>(&c3);
-      }
-    }
+    const int m = min(qt * 16 + (tid >> 4), off + len - 1);
+    attn_tile_stage_q(tile, tid, p.q + (long)m * p.ldq + p.q_off + h * HD, (m - off) + 1, p.cos_t, p.sin_t);
   }
   __syncthreads();
-  const float scale = 0.08838834764831845f;
   f32x4 O[8];
 #pragma unroll
   for (int nb = 0; nb < 8; ++nb) O[nb] = f32x4{0.f, 0.f, 0.f, 0.f};
   float mrun[4], lrun[4];
 #pragma unroll
   for (int r = 0; r < 4; ++r) { mrun[r] = -INFINITY; lrun[r] = 0.f; }
+  int lim[4];                                         // keys query row 4*akq + r may see
+#pragma unroll
+  for (int r = 0; r < 4; ++r) lim[r] = min(nkeys, r0 + 4 * akq + r + 1);
   const int klast = max(nkeys - 1, 0);
   const int ngran = (nkeys + 31) >> 5;
-  for (int g = w; g < ngran; g += NWV) {
+  for (int g = w; g < ngran; g += AttnTile::NWV) {
     const int key0 = g << 5;
     f32x4 S[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
     const int kidx[2] = {min(key0 + arow, klast), min(key0 + 16 + arow, klast)};
@@ -363,7 +275,7 @@ __global__ __launch_bounds__(256) void k_prefill_attn_f8(PrefK p, PrefF8 f8) {
     for (int ks = 0; ks < 4; ++ks) {
       bf16x8 qa[DIA_NPLANES];
 #pragma unroll
-      for (int pl = 0; pl < DIA_NPLANES; ++pl) qa[pl] = *reinterpret_cast<const bf16x8*>(&qf[ks][pl][arow][akq][0]);
+      for (int pl = 0; pl < DIA_NPLANES; ++pl) qa[pl] = *reinterpret_cast<const bf16x8*>(&tile.qf[ks][pl][arow][akq][0]);
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
         const bf16x8 kb = expand_e4m3(*reinterpret_cast<const uint2*>(K8 + (long)kidx[t] * HD + 32 * ks + 8 * akq));
@@ -372,35 +284,14 @@ __global__ __launch_bounds__(256) void k_prefill_attn_f8(PrefK p, PrefF8 f8) {
       }
     }
     float alpha[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int lim = min(nkeys, r0 + 4 * akq + r + 1);      // keys this query row may see
-      const bool v0 = key0 + arow < lim, v1 = key0 + 16 + arow < lim;
-      const float s0 = v0 ? mul_rn(mul_rn(S[0][r], ksc[0]), scale) : -INFINITY, s1 = v1 ? mul_rn(mul_rn(S[1][r], ksc[1]), scale) : -INFINITY;
-      const float mnew = fmaxf(mrun[r], row16_max_p(fmaxf(s0, s1)));
-      alpha[r] = (mrun[r] == -INFINITY) ? 0.f : expf(mrun[r] - mnew);
-      const float p0 = (s0 == -INFINITY) ? 0.f : expf(s0 - mnew), p1 = (s1 == -INFINITY) ? 0.f : expf(s1 - mnew);
-      lrun[r] = lrun[r] * alpha[r] + row16_sum(p0 + p1);      // (the sum takes the unscaled p)
-      mrun[r] = mnew;
-      __bf16 a, bb, c3;
-      split3(mul_rn(p0, vsc[0]), a, bb, c3);
-      pbuf[w][0][4 * akq + r][arow] = *reinterpret_cast<const bf16_raw*>(&a);
-      pbuf[w][1][4 * akq + r][arow] = *reinterpret_cast<const bf16_raw*>(&bb);
-      pbuf[w][2][4 * akq + r][arow] = *reinterpret_cast<const bf16_raw*>(&c3);
-      split3(mul_rn(p1, vsc[1]), a, bb, c3);
-      pbuf[w][0][4 * akq + r][16 + arow] = *reinterpret_cast<const bf16_raw*>(&a);
-      pbuf[w][1][4 * akq + r][16 + arow] = *reinterpret_cast<const bf16_raw*>(&bb);
-      pbuf[w][2][4 * akq + r][16 + arow] = *reinterpret_cast<const bf16_raw*>(&c3);
-    }
-    __builtin_amdgcn_wave_barrier();
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    attn_tile_softmax<true>(tile, w, arow, akq, S, key0, lim, ksc, vsc, mrun, lrun, alpha);
 #pragma unroll
     for (int nb = 0; nb < 8; ++nb)
 #pragma unroll
       for (int r = 0; r < 4; ++r) O[nb][r] *= alpha[r];
     bf16x8 pa[DIA_NPLANES];
 #pragma unroll
-    for (int pl = 0; pl < DIA_NPLANES; ++pl) pa[pl] = *reinterpret_cast<const bf16x8*>(&pbuf[w][pl][arow][8 * akq]);
+    for (int pl = 0; pl < DIA_NPLANES; ++pl) pa[pl] = *reinterpret_cast<const bf16x8*>(&tile.pbuf[w][pl][arow][8 * akq]);
     const uint8_t* Vblk = V8 + (long)g * HD * 32;
 #pragma unroll
     for (int nb = 0; nb < 8; ++nb) {
@@ -410,38 +301,7 @@ __global__ __launch_bounds__(256) void k_prefill_attn_f8(PrefK p, PrefF8 f8) {
     }
     __builtin_amdgcn_wave_barrier();
   }
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-#pragma unroll
-    for (int nb = 0; nb < 8; ++nb) part[(w * 16 + 4 * akq + r) * HD + 16 * nb + arow] = O[nb][r];
-    if (arow == 0) { pm_s[w * 16 + 4 * akq + r] = mrun[r]; pl_s[w * 16 + 4 * akq + r] = lrun[r]; }
-  }
-  __syncthreads();
-  {
-    const int r = tid >> 4, d0 = (tid & 15) * 8, m = qt * 16 + r;
-    if (m - off >= len) return;
-    float mm = -INFINITY;
-#pragma unroll
-    for (int ww = 0; ww < NWV; ++ww) mm = fmaxf(mm, pm_s[ww * 16 + r]);
-    float o[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, Ls = 0.f;
-#pragma unroll
-    for (int ww = 0; ww < NWV; ++ww) {
-      const float pmw = pm_s[ww * 16 + r];
-      const float f = (pmw == -INFINITY) ? 0.f : expf(pmw - mm);
-      // the wave merge, each sum spelt as the compiler's contraction leaves `Ls += pl * f; o[j] += part * f` in k_prefill_attn: dims
-      // 0..5 of a thread's eight are fused multiply-adds, dims 6 and 7 and the softmax sum a rounded product and an add (left to
-      // itself the compiler fused other terms here, and rows of more than one granule differed in the last bit)
-      Ls = add_rn(Ls, mul_rn(pl_s[ww * 16 + r], f));
-#pragma unroll
-      for (int j = 0; j < 6; ++j) o[j] = __builtin_fmaf(part[(ww * 16 + r) * HD + d0 + j], f, o[j]);
-#pragma unroll
-      for (int j = 6; j < 8; ++j) o[j] = add_rn(o[j], mul_rn(part[(ww * 16 + r) * HD + d0 + j], f));
-    }
-    const float inv = Ls > 0.f ? 1.0f / Ls : 0.f;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) o[j] *= inv;
-    emit_planes8(p.P, p.p_plane_stride, p.p_ktiles, m, h * HD + d0, o);
-  }
+  attn_tile_merge_emit<6>(tile, tid, O, mrun, lrun, qt * 16, off + len, p.P, p.p_plane_stride, p.p_ktiles, h * HD);
 }
 
 int fill(const dia_dec_prefill_args* a, PrefK& k) {
@@ -456,6 +316,13 @@ int fill(const dia_dec_prefill_args* a, PrefK& k) {
   return DIA_OK;
 }
 
+// what the K/V append and the attention need of the shared arguments, whatever format the caches have
+bool kv_shape_ok(const dia_dec_prefill_args* a) { return a->q && a->cos_t && a->sin_t && a->kv_heads > 0; }
+bool attn_shape_ok(const dia_dec_prefill_args* a) {
+  return kv_shape_ok(a) && a->P && a->q_heads > 0 && a->q_heads % a->kv_heads == 0 && a->p_plane_stride % 8 == 0 &&
+         (a->q_heads * 128 + 31) / 32 <= a->p_ktiles;
+}
+
 }  // namespace
 
 extern "C" int dia_dec_prefill_embed(const dia_dec_prefill_args* a, void* stream) {
@@ -468,7 +335,7 @@ extern "C" int dia_dec_prefill_embed(const dia_dec_prefill_args* a, void* stream
 
 extern "C" int dia_dec_prefill_kv(const dia_dec_prefill_args* a, void* stream) {
   PrefK k; int rc = fill(a, k); if (rc) return rc;
-  if (!a->q || !a->kc || !a->vc || !a->cos_t || !a->sin_t || a->kv_heads <= 0 || a->kv_cap % 32 != 0)
+  if (!kv_shape_ok(a) || !a->kc || !a->vc || a->kv_cap % 32 != 0)
     return dia_fail(DIA_E_ARG, "dia_dec_prefill_kv: bad argument");
   dia_launch<k_prefill_kv>(dim3(a->kv_heads, a->rows / 32), dim3(256), 0, (hipStream_t)stream, k);
   return dia_check_launch("k_prefill_kv");
@@ -495,25 +362,21 @@ int fill_f8(const char* who, const dia_dec_prefill_args* a, const dia_kv_fp8_ptr
 
 extern "C" int dia_dec_prefill_kv_fp8(const dia_dec_prefill_args* a, const dia_kv_fp8_ptrs* f, void* stream) {
   PrefK k; PrefF8 f8; int rc = fill_f8("dia_dec_prefill_kv_fp8", a, f, k, f8); if (rc) return rc;
-  if (!a->q || !a->cos_t || !a->sin_t || a->kv_heads <= 0)
-    return dia_fail(DIA_E_ARG, "dia_dec_prefill_kv_fp8: bad argument");
+  if (!kv_shape_ok(a)) return dia_fail(DIA_E_ARG, "dia_dec_prefill_kv_fp8: bad argument");
   dia_launch<k_prefill_kv_f8>(dim3(a->kv_heads, a->rows / 32), dim3(256), 0, (hipStream_t)stream, k, f8);
   return dia_check_launch("k_prefill_kv_f8");
 }
 
 extern "C" int dia_dec_prefill_attn_fp8(const dia_dec_prefill_args* a, const dia_kv_fp8_ptrs* f, void* stream) {
   PrefK k; PrefF8 f8; int rc = fill_f8("dia_dec_prefill_attn_fp8", a, f, k, f8); if (rc) return rc;
-  if (!a->q || !a->cos_t || !a->sin_t || !a->P || a->q_heads <= 0 || a->kv_heads <= 0 || a->q_heads % a->kv_heads != 0 ||
-      a->p_plane_stride % 8 != 0 || (a->q_heads * 128 + 31) / 32 > a->p_ktiles)
-    return dia_fail(DIA_E_ARG, "dia_dec_prefill_attn_fp8: bad argument");
+  if (!attn_shape_ok(a)) return dia_fail(DIA_E_ARG, "dia_dec_prefill_attn_fp8: bad argument");
   dia_launch<k_prefill_attn_f8>(dim3(a->q_heads, a->rows / 16), dim3(256), 0, (hipStream_t)stream, k, f8);
   return dia_check_launch("k_prefill_attn_f8");
 }
 
 extern "C" int dia_dec_prefill_attn(const dia_dec_prefill_args* a, void* stream) {
   PrefK k; int rc = fill(a, k); if (rc) return rc;
-  if (!a->q || !a->kc || !a->vc || !a->cos_t || !a->sin_t || !a->P || a->q_heads <= 0 || a->kv_heads <= 0 || a->q_heads % a->kv_heads != 0 ||
-      a->kv_cap % 32 != 0 || (!a->causal && !a->text_len) || a->p_plane_stride % 8 != 0 || (a->q_heads * 128 + 31) / 32 > a->p_ktiles)
+  if (!attn_shape_ok(a) || !a->kc || !a->vc || a->kv_cap % 32 != 0 || (!a->causal && !a->text_len))
     return dia_fail(DIA_E_ARG, "dia_dec_prefill_attn: bad argument");
   dia_launch<k_prefill_attn>(dim3(a->q_heads, a->rows / 16), dim3(256), 0, (hipStream_t)stream, k);
   return dia_check_launch("k_prefill_attn");
