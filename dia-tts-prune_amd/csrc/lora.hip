@@ -182,7 +182,7 @@ __global__ __launch_bounds__(LORA_NT) void k_lora_crosskv(LoraK p) {
   int b = p.kv_batch_index, pos = m;
   if (p.row_slot) {                                    // packed batch: row -> (utterance, position), as the CROSSKV epilogue
     b = p.row_slot[m];
-    if (b < 0) return;
+    if (b < 0 || b >= p.n_slots) return;               // (before seg_off[b]: seg_off has n_slots entries)
     pos = m - p.seg_off[b];
   }
   const int a = lora_adapter(p, b);
