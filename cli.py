@@ -16,6 +16,10 @@ converts ``--output`` from 44100 Hz to HZ the same way.  ``--codec-precision {fp
 picks the decoder's arithmetic: the exact fp32 kernel, or bf16 MFMA operands in two planes / one; encoding stays fp32.
 ``--score-codes FILE.npy`` (build-only) generates nothing: it prints the teacher-forced log-likelihood of the given codes under
 the loaded checkpoint (Dia.score) as one JSON line.
+``--compare-audio A.wav B.wav`` (build-only) loads no model and no codec: it prints the multi-scale STFT and log-mel distances between
+the two files (dia_hip/spectral.py) as one JSON line, B brought to A's sample rate by the native resampler and the longer cut to the
+shorter.  ``--codec-roundtrip IN.wav --codec-path FILE`` (build-only) prints the same JSON for the native codec's reconstruction
+(encode -> decode, the decoder in ``--codec-precision``) of the file.  Neither needs the text argument.
 """
 
 from __future__ import annotations
@@ -41,7 +45,7 @@ def set_seed(seed: int):
 
 def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(description="Dia text-to-dialogue on MI355X: text in, audio (or codec codes) out.")
-    p.add_argument("text", type=str, help="text to synthesise ([S1]/[S2] speaker tags); with --audio-prompt give only the new text here, the prompt transcript goes to --audio-prompt-text")
+    p.add_argument("text", type=str, nargs="?", default=None, help="text to synthesise ([S1]/[S2] speaker tags); with --audio-prompt give only the new text here, the prompt transcript goes to --audio-prompt-text")
     p.add_argument("--output", type=str, default=None, help="audio file to write (needs a codec: --codec-path FILE, or the dac package)")
     p.add_argument("--codes-output", type=str, default=None, help="(build-only) path for the codec input codes [1, C, T] as .npy")
     g = p.add_argument_group("Model Loading")
@@ -93,6 +97,13 @@ def build_parser() -> argparse.ArgumentParser:
                    "--audio-prompt (a .npy) is replayed and not scored; needs a local --model-path")
     g.add_argument("--score-output", type=str, default=None, help="with --score-codes: .npz for the per-position arrays "
                    "(lp_cond, lp_cfg, entropy_cfg, valid)")
+    g = p.add_argument_group("Audio distance")
+    g.add_argument("--compare-audio", type=str, nargs=2, default=None, metavar=("A.wav", "B.wav"), help="(build-only) print the multi-scale "
+                   "STFT and log-mel distances between two audio files as one JSON line, then exit: loads no model; B is resampled to A's "
+                   "rate on the device when they differ, and the longer file is cut to the shorter")
+    g.add_argument("--codec-roundtrip", type=str, default=None, metavar="IN.wav", help="(build-only) print the same distances between this "
+                   "file and its reconstruction by the native codec (encode -> decode, the decoder in --codec-precision) as one JSON "
+                   "line, then exit: needs --codec-path with a checkpoint that holds the encoder, loads no model")
     g = p.add_argument_group("Infrastructure")
     g.add_argument("--device", type=str, default=None, help="HIP device such as cuda:0 (default: the current one)")
     g.add_argument("--compute-dtype", type=str, default="bfloat16", choices=["float16", "bfloat16", "float32"], help="K/V cache dtype: bfloat16 (default; float16 is accepted and mapped to it) or float32.")
@@ -258,9 +269,73 @@ def encode_to_file(args) -> int:
         return 1
 
 
+def distance_json(res: dict, **head) -> str:
+    """one JSON line: the metrics, then the terms of every resolution under string keys"""
+    import json
+
+    per = {m: {str(w): t for w, t in r.items()} for m, r in res["per_resolution"].items()}
+    return json.dumps({**head, **{k: v for k, v in res.items() if k != "per_resolution"}, "per_resolution": per})
+
+
+def compare_to_stdout(args) -> int:
+    """--compare-audio: two files through the device's spectral kernel; no model, no codec"""
+    try:
+        from dia_hip.model import read_audio_mono
+        from dia_hip.resample import DeviceResampler
+        from dia_hip.spectral import DeviceSpectral
+
+        device = torch.device(args.device) if args.device else None
+        (a, rate), (b, rate_b) = (read_audio_mono(f) for f in args.compare_audio)
+        if rate_b != rate:
+            b = DeviceResampler(device).resample(np.ascontiguousarray(b, dtype=np.float32), rate_b, rate)
+        res = DeviceSpectral(device).distance(a, b, rate, trim=True)
+        print(distance_json(res, sample_rate=rate, samples=int(min(a.shape[0], b.shape[0]))))
+        return 0
+    except Exception as e:
+        print(f"Error comparing {args.compare_audio[0]} and {args.compare_audio[1]}: {e}")
+        import traceback
+        traceback.print_exc()
+        return 1
+
+
+def roundtrip_to_stdout(args) -> int:
+    """--codec-roundtrip: the file against its reconstruction by the native codec alone"""
+    try:
+        from dia_hip.codec import DeviceCodec
+        from dia_hip.model import read_audio_mono, resample_to
+
+        device = torch.device(args.device) if args.device else None
+        codec = DeviceCodec(args.codec_path, device, precision=args.codec_precision or "fp32")
+        mono, rate = read_audio_mono(args.codec_roundtrip)
+        mono = resample_to(mono, rate, codec.cfg.sample_rate, args.codec_roundtrip, codec)
+        print(distance_json(codec.roundtrip_distance(mono), sample_rate=codec.cfg.sample_rate, samples=int(mono.shape[0]),
+                            codec_precision=codec.precision))
+        return 0
+    except Exception as e:
+        print(f"Error in the codec round trip of {args.codec_roundtrip}: {e}")
+        import traceback
+        traceback.print_exc()
+        return 1
+
+
 def main(argv=None) -> int:
     parser = build_parser()
     args = parser.parse_args(argv)
+    if args.compare_audio or args.codec_roundtrip:
+        if args.compare_audio and args.codec_roundtrip:
+            parser.error("--compare-audio and --codec-roundtrip are separate runs.")
+        if args.output or args.codes_output or args.score_codes or args.slots or args.stream_chunk or args.audio_prompt or args.encode_audio:
+            parser.error("--compare-audio / --codec-roundtrip print distances only: none of --output, --codes-output, --score-codes, "
+                         "--slots, --stream-chunk, --audio-prompt or --encode-audio.")
+        if args.compare_audio:
+            if args.codec_path or args.codec_precision:
+                parser.error("--compare-audio loads no codec: not with --codec-path / --codec-precision.")
+            return compare_to_stdout(args)
+        if not args.codec_path or not Path(args.codec_path).is_file():
+            parser.error("--codec-roundtrip needs --codec-path FILE: a DAC checkpoint that holds the encoder.")
+        return roundtrip_to_stdout(args)
+    if args.text is None:
+        parser.error("the following arguments are required: text")
     if args.encode_audio:
         if not args.codec_path or not Path(args.codec_path).is_file():
             parser.error("--encode-audio needs --codec-path FILE: a DAC checkpoint that holds the encoder.")

@@ -31,6 +31,7 @@ EXPORTS = (
     "dia_codec_embed", "dia_codec_conv", "dia_codec_convt", "dia_codec_convs", "dia_codec_quantize",
     "dia_codec_conv_bf16", "dia_codec_convt_bf16",
     "dia_resample",
+    "dia_spectral",
     "dia_seg_mlp", "dia_seg_workspace_bytes", "dia_seg_workspace_control_bytes", "dia_seg_slots", "dia_seg_supported", "dia_seg_error",
 )
 
@@ -251,6 +252,17 @@ class ResampleArgs(C.Structure):
     ]
 
 
+class SpectralArgs(C.Structure):
+    """dia_spectral_args: a / b / basis / fb / fb_range / partial / out are device pointers, len a HOST array read during the call"""
+    _fields_ = [
+        ("a", C.c_void_p), ("b", C.c_void_p), ("basis", C.c_void_p), ("fb", C.c_void_p), ("fb_range", C.c_void_p),
+        ("partial", C.c_void_p), ("out", C.c_void_p),
+        ("B", C.c_int32), ("ld", C.c_int32), ("window", C.c_int32), ("n_mels", C.c_int32),
+        ("tiles", C.c_int32), ("out_frames", C.c_int32), ("power", C.c_int32), ("_pad0", C.c_int32),
+        ("eps", C.c_double), ("len", C.POINTER(C.c_int32)),
+    ]
+
+
 class DecLayer(C.Structure):
     _fields_ = [
         ("w_qkv", C.c_void_p), ("w_o", C.c_void_p), ("w_cq", C.c_void_p), ("w_co", C.c_void_p),
@@ -381,6 +393,7 @@ def lib() -> C.CDLL:
     for fn in (L.dia_dec_prefill_kv_fp8, L.dia_dec_prefill_attn_fp8):
         fn.argtypes = [C.POINTER(DecPrefillArgs), C.POINTER(KvFp8Ptrs), C.c_void_p]
     L.dia_resample.argtypes = [C.POINTER(ResampleArgs), C.c_void_p]
+    L.dia_spectral.argtypes = [C.POINTER(SpectralArgs), C.c_void_p]
     L.dia_seg_mlp.argtypes = [C.POINTER(SegArgs), C.c_void_p]
     L.dia_seg_workspace_bytes.restype = C.c_int64
     L.dia_seg_workspace_control_bytes.restype = C.c_int64

@@ -667,6 +667,7 @@ class DeviceCodec:
         self.enc_layers: Optional[List[dict]] = None
         self.encoder_error: Optional[Exception] = None
         self._resampler = None                                  # resample.DeviceResampler, made on first use
+        self._spectral = None                                   # spectral.DeviceSpectral, made on first use
         if any(k.startswith("encoder.") for k in whole):
             try:
                 self._prepare_encoder(sd, whole, meta, int(workspace_bytes))
@@ -946,6 +947,25 @@ class DeviceCodec:
         """a resample.ResampleStream for one signal: push(chunk, final) -> the samples that have become final; joined they equal
         resample() of the whole signal bit for bit"""
         return self._resample().stream(rate_in, rate_out)
+
+    # -------------------------------------------------------------------------------------- audio distance
+    def audio_distance(self, a, b, rate: Optional[int] = None, **kw):
+        """the multi-scale STFT and log-mel distances between waveform a and waveform b (or lists, pair by pair) at `rate` Hz
+        (default: the codec's): ``{"stft": x, "mel": y, "per_resolution": {...}}`` per pair (csrc/spectral.hip, DESIGN.md "Audio
+        distance"; keywords as spectral.DeviceSpectral.distance)"""
+        if self._spectral is None:
+            from .spectral import DeviceSpectral
+            self._spectral = DeviceSpectral(self.device)
+        return self._spectral.distance(a, b, int(rate) if rate else self.cfg.sample_rate, **kw)
+
+    def roundtrip_distance(self, wave, **kw):
+        """encode -> decode of mono float samples [L] at the codec's rate (the decoder in this codec's precision), cut to the L
+        samples of the input, then audio_distance against the input"""
+        w = np.ascontiguousarray(np.asarray(wave.detach().cpu() if isinstance(wave, torch.Tensor) else wave, dtype=np.float32).reshape(-1))
+        if w.shape[0] < 1:
+            raise ValueError("codec: an empty waveform has no round trip")
+        y = self.decode(self.encode(w))                         # [1, n_codebooks, T] -> float32 [T * hop], T * hop >= L
+        return self.audio_distance(w, y[:w.shape[0]], **kw)
 
     def stream(self, window: Optional[int] = None) -> CodecStream:
         """a streaming state for one utterance on this codec"""

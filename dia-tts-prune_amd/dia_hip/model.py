@@ -447,6 +447,20 @@ class Dia:
             finally:
                 s.close()
 
+    def audio_distance(self, a, b, sample_rate: int = DEFAULT_SAMPLE_RATE, **kw):
+        """the multi-scale STFT and log-mel distances between waveform a and waveform b (mono float samples, or lists of them pair by
+        pair) at sample_rate Hz, computed on this instance's device (dia_hip/spectral.py, csrc/spectral.hip): per pair
+        ``{"stft": x, "mel": y, "per_resolution": {...}}``.  Needs no codec and no weights; keywords as DeviceSpectral.distance."""
+        if getattr(self, "_spectral", None) is None:
+            from .spectral import DeviceSpectral
+            self._spectral = DeviceSpectral(self.device)
+        return self._spectral.distance(a, b, int(sample_rate), **kw)
+
+    def codec_roundtrip_distance(self, wave, **kw):
+        """what the loaded native codec does to a waveform at its own rate: encode -> decode in the codec's precision, cut to the
+        input's length, audio_distance against the input.  Needs load_codec() of a checkpoint that holds the encoder."""
+        return self._need_codec().roundtrip_distance(wave, **kw)
+
     def _need_codec(self):
         if self.codec is None:
             raise RuntimeError("no native codec loaded: call Dia.load_codec(path_or_state) first")

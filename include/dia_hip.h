@@ -1012,6 +1012,56 @@ typedef struct {
 } dia_resample_args;
 int dia_resample(const dia_resample_args* a, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Audio distance (csrc/spectral.hip; DESIGN.md "Audio distance"): the magnitude spectrogram or the mel spectrogram of ONE
+ * resolution of a ragged batch of rows in ONE launch, and the L1 terms between two batches.  One new entry point and one new
+ * struct; nothing older changed.
+ *
+ * A row of len >= 1 samples has F = 1 + len / H frames, H = window / 4.  Frame f is centred at sample f * H; samples outside
+ * [0, len) read as ZERO (torch.stft(center=True, pad_mode="constant")).  With nbin = window / 2 + 1,
+ *   X[f][k]   = sum_n basis[n][0][k] * x[f H - window / 2 + n]  +  i sum_n basis[n][1][k] * x[...]      k = 0 .. window / 2
+ *   mag[f][k] = |X[f][k]|
+ *   mel[f][m] = sum_k fb[m][k] * mag[f][k]        an fp32 fma chain from 0 over k in [fb_range[m][0], fb_range[m][1]), ascending
+ * The basis holds the window: basis[n][0][k] = w[n] cos(2 pi n k / window), basis[n][1][k] = -w[n] sin(2 pi n k / window).  The
+ * sums over n run on the exact-fp32 MFMA: two samples to a step, each step's fp32 sum of two products added in float64 in
+ * ascending n; mag is the float64 root of the two sums, rounded to fp32.  S = mag when n_mels == 0, else mel.
+ *
+ * b != NULL (distance): partial[r][t] receives, for tile t of DIA_SPECTRAL_TILE_FRAMES consecutive frames of row r,
+ *   [0] sum |Sa - Sb|    [1] sum power * |log10 max(Sa, eps) - log10 max(Sb, eps)|
+ * over the tile's frames < F and all bins (or mels), in float64 and in an order that depends on the tile alone.  The caller adds
+ * the tiles of a row in its own fixed order and divides by F * (nbin or n_mels).  Tiles at or beyond a row's last are not written.
+ * b == NULL (spectra only): out[r][f][.] receives S of row r, f < F; nothing else of out is written.
+ * Either way an element has the same bits whichever row of whichever batch it is computed in.
+ *
+ * Refused with DIA_E_ARG before any HIP call: a null args / a / basis / len; window not a power of two in [32, 2048]; n_mels
+ * outside [0, 320], or > 0 without fb and fb_range; B outside [1, 64]; ld outside [1, 1 << 24]; a len outside [1, ld]; power not
+ * 1 or 2; eps not positive; b without partial, or tiles below the tiles of the longest row; no b and no out, or out_frames below
+ * the frames of the longest row.
+ * ------------------------------------------------------------------------------------------------ */
+#define DIA_SPECTRAL_MAX_ROWS 64           /* rows (row pairs) of one launch */
+#define DIA_SPECTRAL_MAX_T (1 << 24)       /* ld */
+#define DIA_SPECTRAL_MIN_WINDOW 32
+#define DIA_SPECTRAL_MAX_WINDOW 2048
+#define DIA_SPECTRAL_MAX_MELS 320
+#define DIA_SPECTRAL_TILE_FRAMES 16        /* frames of one partial */
+typedef struct {
+  const float* a;              /* device [B][ld] */
+  const float* b;              /* device [B][ld], or NULL: spectra only */
+  const float* basis;          /* device [window][2][window / 2 + 1] */
+  const float* fb;             /* device [n_mels][window / 2 + 1]; unused when n_mels == 0 */
+  const int32_t* fb_range;     /* device [n_mels][2]: the bins [lo, hi) outside which row m of fb is zero (clamped to [0, nbin]) */
+  double* partial;             /* device [B][tiles][2]; required with b */
+  float* out;                  /* device [B][out_frames][window / 2 + 1 or n_mels]; required without b */
+  int32_t B, ld, window, n_mels;
+  int32_t tiles;               /* second extent of partial: at least ceil(F / DIA_SPECTRAL_TILE_FRAMES) of the longest row */
+  int32_t out_frames;          /* second extent of out: at least F of the longest row */
+  int32_t power;               /* 1 or 2: the p of log10(max(S, eps)^p) */
+  int32_t _pad0;
+  double eps;
+  const int32_t* len;          /* HOST [B], read during the call: 1 .. ld */
+} dia_spectral_args;
+int dia_spectral(const dia_spectral_args* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
