@@ -97,6 +97,15 @@ def build_parser() -> argparse.ArgumentParser:
                    "--audio-prompt (a .npy) is replayed and not scored; needs a local --model-path")
     g.add_argument("--score-output", type=str, default=None, help="with --score-codes: .npz for the per-position arrays "
                    "(lp_cond, lp_cfg, entropy_cfg, valid)")
+    g.add_argument("--calibrate-codes", type=str, nargs="+", default=None, metavar="FILE.npy", help="(build-only) one or more .npy of codec "
+                   "frames [T, 9] or delayed token buffers: instead of generating, force them through the loaded checkpoint and write the "
+                   "per-channel activation statistics of every prunable kernel's input to --stats-output (Dia.calibrate), what "
+                   "offline_prune.py --act-stats takes; the text belongs to every file unless --calibrate-texts is given; needs a local "
+                   "--model-path, loaded dense and uncompacted")
+    g.add_argument("--calibrate-texts", type=str, default=None, metavar="FILE.txt", help="with --calibrate-codes: one transcript per line, in "
+                   "the order of the codes files")
+    g.add_argument("--stats-output", type=str, default=None, help="with --calibrate-codes: the .npz the statistics go to; an existing file "
+                   "of the same model is merged into (sums and row counts add)")
     g = p.add_argument_group("Audio distance")
     g.add_argument("--compare-audio", type=str, nargs=2, default=None, metavar=("A.wav", "B.wav"), help="(build-only) print the multi-scale "
                    "STFT and log-mel distances between two audio files as one JSON line, then exit: loads no model; B is resampled to A's "
@@ -248,6 +257,27 @@ def score_to_stdout(dia, args, text: str, prompt) -> int:
     return 0
 
 
+def calibrate_to_file(dia, args, text: str) -> int:
+    """--calibrate-codes: Dia.calibrate over the files' codes; the statistics to --stats-output, a summary as one JSON line"""
+    import json
+
+    from dia_hip.calib import ActStats
+
+    codes = [np.load(f) for f in args.calibrate_codes]
+    texts = [text] * len(codes)
+    if args.calibrate_texts:
+        texts = [ln.strip() for ln in Path(args.calibrate_texts).read_text().splitlines() if ln.strip()]
+        if len(texts) != len(codes):
+            raise ValueError(f"--calibrate-texts holds {len(texts)} lines for {len(codes)} codes files")
+    out = Path(args.stats_output)
+    prior = ActStats.load(str(out)) if out.is_file() else None
+    stats = dia.calibrate(texts, codes, cfg_scale=args.cfg_scale, stats=prior)
+    out.parent.mkdir(parents=True, exist_ok=True)
+    stats.save(str(out))
+    print(json.dumps(dict(files=len(codes), kernels=len(stats.names()), rows_min=min(stats.rows.values()), rows_max=max(stats.rows.values()))))
+    return 0
+
+
 def encode_to_file(args) -> int:
     """--encode-audio: the file through the native codec alone, codes [T, C] to --codes-output"""
     try:
@@ -354,12 +384,24 @@ def main(argv=None) -> int:
         args.no_dac = True
     elif args.score_output:
         parser.error("--score-output needs --score-codes.")
+    if args.calibrate_codes:
+        if not args.stats_output:
+            parser.error("--calibrate-codes needs --stats-output FILE.npz.")
+        if not Path(args.model_path).is_dir() and not (args.pruned_checkpoint and args.config):
+            parser.error("--calibrate-codes needs --model-path: a local model directory holding config.json and the checkpoint "
+                         "(or --pruned-checkpoint with --config).")
+        if args.score_codes or args.output or args.codes_output or args.slots or args.stream_chunk or args.audio_prompt or args.codec_path:
+            parser.error("--calibrate-codes generates nothing: not with --score-codes, --output, --codes-output, --slots, --stream-chunk, "
+                         "--audio-prompt or --codec-path.")
+        args.no_dac = True
+    elif args.stats_output or args.calibrate_texts:
+        parser.error("--stats-output / --calibrate-texts need --calibrate-codes.")
     if args.audio_prompt and not args.audio_prompt_text:
         parser.error("--audio-prompt needs its transcript: pass --audio-prompt-text")
     bank_dirs = parse_adapter_flags(parser, args)
     if args.pruned_checkpoint and not args.config and not Path(args.model_path).is_dir():
         parser.error("--pruned-checkpoint needs --config unless --model-path is a local directory with a config.json")
-    if not args.output and not args.codes_output and not args.score_codes:
+    if not args.output and not args.codes_output and not args.score_codes and not args.calibrate_codes:
         parser.error("one of --output / --codes-output is required.")
     if args.slots < 0 or (args.slots and (args.audio_prompt or not args.codes_output or args.output)):
         parser.error("--slots N needs N > 0, --codes-output, and neither --audio-prompt nor --output.")
@@ -431,6 +473,14 @@ def main(argv=None) -> int:
             return score_to_stdout(dia, args, args.text.strip(), None if prompt is None else prompt.numpy())
         except Exception as e:
             print(f"Error during scoring: {e}")
+            import traceback
+            traceback.print_exc()
+            return 1
+    if args.calibrate_codes:
+        try:
+            return calibrate_to_file(dia, args, args.text.strip())
+        except Exception as e:
+            print(f"Error during calibration: {e}")
             import traceback
             traceback.print_exc()
             return 1

@@ -31,6 +31,10 @@ struct dia_engine {
   const void* f4_logits = nullptr;      // ... and of the logits head
   bool score_on = false;                // dia_engine_set_score: every step scores the forced row between the logits GEMM and the sampler
   dia_score_args score = {};
+  bool calib_on = false;                // dia_engine_set_calib: every step accumulates the activation statistics of each GEMM input in front of the GEMM
+  std::vector<double*> calib_acc;       // ... per tap (6 * l + m, the logits head last): the accumulator,
+  std::vector<int32_t> calib_kt;        // ... its k-tiles
+  int64_t* calib_counters = nullptr;    // ... and the device row counters
   std::vector<dia_lora_layer> lora;     // dia_engine_set_lora: the adapter tables of the two decode sites per layer (empty: no LoRA launches)
   const int32_t* lora_slot = nullptr;   // ... and the device array adapter_of_slot [B]
   int lora_adapters = 0;
@@ -49,6 +53,7 @@ struct dia_engine {
 int dia_prefetch_launch(const void* ptr, long nbytes, int nblocks, hipStream_t st);
 int dia_score_validate(const dia_score_args* a, const char* who);
 int dia_lora_validate(const dia_lora_args* a, const char* who);
+int dia_act_stats_validate(const dia_act_stats_args* a, const char* who);
 static int ensure_sink();
 static int dia_lora_noop(void* st);
 
@@ -127,11 +132,17 @@ static mat_w mat_weights(const dia_engine* e, int l, int m) {
 
 // The launches of one step, in order: launch(layer, what) for every one, `what` a dia_step_mat or one of the launches below.
 // enqueue_step issues them; the prefetch list and dia_engine_launches_per_step walk the same sequence.
-enum { ATTN_SELF = DIA_MAT_COUNT, ATTN_CROSS, SEG_MLP, SAMPLER, SCORE, LORA_QKV, LORA_CQ };
+// CALIB + m: dia_engine_set_calib's tap in front of matrix m (a dia_act_stats over the planes m is about to read)
+enum { ATTN_SELF = DIA_MAT_COUNT, ATTN_CROSS, SEG_MLP, SAMPLER, SCORE, LORA_QKV, LORA_CQ, CALIB };
 template <class Launch>
 static int step_sequence(const dia_engine* e, bool with_sampler, Launch&& launch) {
   int rc = DIA_OK;                   // the first failure ends the sequence
-  auto run = [&](int l, std::initializer_list<int> seq) { for (int what : seq) if (!rc) rc = launch(l, what); };
+  auto run = [&](int l, std::initializer_list<int> seq) {
+    for (int what : seq) {
+      if (!rc && e->calib_on && what < DIA_MAT_COUNT) rc = launch(l, CALIB + what);
+      if (!rc) rc = launch(l, what);
+    }
+  };
   for (int l = 0; l < e->d.n_layer; ++l) {
     if (!e->seg || l == 0) run(l, {DIA_MAT_QKV});
     if (e->lora.empty()) run(l, {ATTN_SELF, DIA_MAT_O, DIA_MAT_CQ, ATTN_CROSS});
@@ -326,6 +337,26 @@ static int enqueue_step(dia_engine* e, bool with_sampler) {
     defer = ok;
   }
 
+  // dia_engine_set_calib: the statistics of the rows matrix m of layer l is about to contract with, scaled as m scales them
+  auto step_tap = [&](int l, int m) {
+    const dia_gemm_args g = step_gemm(l, m);
+    const int i = l < d.n_layer ? 6 * l + m : 6 * d.n_layer;
+    dia_act_stats_args a = {};
+    a.x = g.A; a.plane_stride = g.a_plane_stride; a.ktiles = g.a_ktiles; a.ktiles_used = e->calib_kt[i]; a.M = R; a.rows_pad = d.rows_pad;
+    a.act_f32 = F; a.ssq_in = g.ssq_in; a.ssq_in_n = g.ssq_in_n; a.ssq_ld = g.ssq_ld; a.inv_d = g.inv_d; a.eps = g.eps;
+    a.rows_per_slot = 2; a.cur = d.sample.cur; a.first_step = d.sample.first_step; a.fsm = d.sample.fsm; a.T = d.T;
+    a.acc = e->calib_acc[i]; a.counter = e->calib_counters + i;
+    return a;
+  };
+  if (e->calib_on && e->launches == 0 && !e->exec) {      // every tap's descriptor is checked before the first launch of the first step
+    for (int l = 0; l <= d.n_layer; ++l)
+      for (int m = (l < d.n_layer ? 0 : DIA_MAT_LOGITS); m < (l < d.n_layer ? DIA_MAT_LOGITS : DIA_MAT_COUNT); ++m) {
+        const dia_act_stats_args a = step_tap(l, m);
+        const int vrc = dia_act_stats_validate(&a, "dia_engine_set_calib");
+        if (vrc) return vrc;
+      }
+  }
+
   int n = 0;
   bool fused = false;         // the wi launch of this layer ran wo as well
   const int rc = step_sequence(e, with_sampler, [&](int l, int what) -> int {
@@ -360,6 +391,9 @@ static int enqueue_step(dia_engine* e, bool with_sampler) {
       rc = dia_sample(&d.sample, st);
     } else if (what == SCORE) {
       rc = dia_score(&e->score, st);
+    } else if (what >= CALIB) {
+      const dia_act_stats_args ca = step_tap(l, what - CALIB);
+      rc = dia_act_stats(&ca, st);
     } else if (what == LORA_QKV || what == LORA_CQ) {
       // the rows the projection read: layer l's residual stream — under deferral the q/k/v launch of layer l > 0 has just written it (xnew)
       const dia_lora_args la = lora_site(e, l, what == LORA_CQ, xbuf(l));
@@ -475,7 +509,7 @@ extern "C" int dia_engine_decode(dia_engine* e, int n_steps, int use_graph) {
       if (rc0) return rc0;
       e->pf_w.clear();
       (void)step_sequence(e, true, [&](int l, int what) {
-        const mat_w w = what < DIA_MAT_COUNT ? mat_weights(e, l, what) : mat_w{};      // (attention, the sampler, a segment: nothing)
+        const mat_w w = what < DIA_MAT_COUNT ? mat_weights(e, l, what) : mat_w{};      // (attention, the sampler, a segment, a tap: nothing)
         e->pf_w.push_back({w.w, (long)w.kt * w.ns * 1024});
         return DIA_OK;
       });
@@ -647,6 +681,43 @@ extern "C" int dia_engine_set_score(dia_engine* e, const dia_score_args* a) {
     e->score = *a;
   }
   e->score_on = a != nullptr;
+  return DIA_OK;
+}
+
+extern "C" int dia_engine_set_calib(dia_engine* e, const dia_calib_args* a) {
+  if (!e) return dia_fail(DIA_E_ARG, "dia_engine_set_calib: null engine");
+  if (e->exec || e->launches > 0) return dia_fail(DIA_E_STATE, "dia_engine_set_calib: a step has already been issued or captured");
+  if (!a) { e->calib_on = false; e->calib_acc.clear(); e->calib_kt.clear(); e->calib_counters = nullptr; return DIA_OK; }
+  const dia_engine_desc& d = e->d;
+  const dia_sample_args& sp = d.sample;
+  if (a->n_layer != d.n_layer || !a->acc || !a->kt || !a->counters)
+    return dia_fail(DIA_E_ARG, "dia_engine_set_calib: n_layer differs from the engine's, or a null acc / kt / counters");
+  if (!sp.teacher) return dia_fail(DIA_E_ARG, "dia_engine_set_calib: calibration needs a teacher-forced engine (sample.teacher)");
+  if (sp.slot_cfg_scale || sp.slot_temperature || sp.slot_top_p || sp.slot_top_k || sp.slot_max_tokens)
+    return dia_fail(DIA_E_ARG, "dia_engine_set_calib: calibration is for closed batches, this sampler has per-slot state");
+  if (!sp.cur) return dia_fail(DIA_E_ARG, "dia_engine_set_calib: the gate needs sample.cur");
+  if (e->seg) return dia_fail(DIA_E_ARG, "dia_engine_set_calib: the persistent MLP segments keep the inputs of co, wi, wo and q/k/v inside their launch (seg must be off)");
+  if (dia_tune(DIA_TUNE_MLP_FUSE) > 0) return dia_fail(DIA_E_ARG, "dia_engine_set_calib: the knob mlp_fuse keeps wo's input inside the fused launch");
+  if (dia_tune(DIA_TUNE_WO_DIAG) == 1) return dia_fail(DIA_E_ARG, "dia_engine_set_calib: the knob wo_diag changes the partial sums behind wo");
+  if (sp.embed.cmap) return dia_fail(DIA_E_ARG, "dia_engine_set_calib: compacted checkpoint (compaction map on the first layer's q/k/v input)");
+  for (int l = 0; l < d.n_layer; ++l) {
+    const dia_dec_layer& L = e->layers[l];
+    if (L.cmap_ca || L.cmap_mlp || L.cmap_next || L.smap_qkv || L.smap_cq)
+      return dia_fail(DIA_E_ARG, "dia_engine_set_calib: compacted checkpoint (strip or compaction map on an edge of the step)");
+  }
+  const int n = 6 * d.n_layer + 1;
+  const int akt = (max(d.q_heads, d.cq_heads) * 128) / 32;
+  for (int i = 0; i < n; ++i) {
+    const int m = i < 6 * d.n_layer ? i % 6 : DIA_MAT_LOGITS;
+    const int in = STEP_MATS[m].in;
+    const int cap = in == PL_X ? d.D / 32 : (in == PL_A ? akt : d.F / 32);
+    if (!a->acc[i] || a->kt[i] <= 0 || a->kt[i] > cap) return dia_fail(DIA_E_ARG, "dia_engine_set_calib: a tap without acc, or k-tiles outside (0, k-tiles of its plane set]");
+  }
+  e->calib_acc.assign(a->acc, a->acc + n);
+  e->calib_kt.assign(a->kt, a->kt + n);
+  e->calib_counters = a->counters;
+  e->calib_on = true;
+  e->wo_defer = 0;            // the in-launch merge: every q/k/v input reaches planes_x
   return DIA_OK;
 }
 

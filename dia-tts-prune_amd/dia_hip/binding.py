@@ -25,6 +25,7 @@ EXPORTS = (
     "dia_embed_text", "dia_embed_tokens", "dia_sample", "dia_slot_admit", "dia_slot_retire", "dia_emit_frames", "dia_prefetch", "dia_engine_create", "dia_engine_destroy",
     "dia_engine_decode", "dia_engine_set_prefetch", "dia_engine_set_x_alt", "dia_engine_step_logits_only", "dia_engine_profile_step", "dia_engine_time_step", "dia_timed_kernel_name", "dia_engine_launches_per_step", "dia_mxfp8_classes", "dia_mxfp4_classes", "dia_engine_set_mxfp4",
     "dia_score", "dia_engine_set_score",
+    "dia_act_stats", "dia_engine_set_calib",
     "dia_lora_apply", "dia_lora_crosskv", "dia_engine_set_lora",
     "dia_kv_quantize_fp8", "dia_attn_cross_fp8", "dia_engine_set_cross_fp8",
     "dia_attn_self_fp8", "dia_engine_set_self_fp8", "dia_dec_prefill_kv_fp8", "dia_dec_prefill_attn_fp8",
@@ -180,6 +181,23 @@ class ScoreArgs(C.Structure):
         ("eos", C.c_int32), ("pad", C.c_int32), ("bos", C.c_int32), ("_pad0", C.c_int32),
         ("tokens", C.c_void_p), ("cur", C.c_void_p), ("first_step", C.c_void_p), ("fsm", C.c_void_p), ("out", C.c_void_p),
     ]
+
+
+class ActStatsArgs(C.Structure):
+    """dia_act_stats_args: per-channel sums of squares of one activation plane set's counted rows (csrc/calib.hip)"""
+    _fields_ = [
+        ("x", C.c_void_p), ("plane_stride", C.c_int64), ("ktiles", C.c_int32), ("ktiles_used", C.c_int32),
+        ("M", C.c_int32), ("rows_pad", C.c_int32), ("act_f32", C.c_int32), ("ssq_in_n", C.c_int32),
+        ("ssq_in", C.c_void_p), ("ssq_ld", C.c_int32), ("inv_d", C.c_float), ("eps", C.c_float), ("rows_per_slot", C.c_int32),
+        ("row_mask", C.c_void_p), ("cur", C.c_void_p), ("first_step", C.c_void_p), ("fsm", C.c_void_p),
+        ("T", C.c_int32), ("_pad0", C.c_int32), ("acc", C.c_void_p), ("counter", C.c_void_p),
+    ]
+
+
+class CalibArgs(C.Structure):
+    """dia_calib_args: acc / kt are HOST arrays of 6 * n_layer + 1 taps (copied), counters a device array"""
+    _fields_ = [("n_layer", C.c_int32), ("_pad0", C.c_int32), ("acc", C.POINTER(C.c_void_p)), ("kt", C.POINTER(C.c_int32)),
+                ("counters", C.c_void_p)]
 
 
 LORA_MAX_RANK, LORA_MAX_SEGS = 64, 3                     # DIA_LORA_MAX_RANK, DIA_LORA_MAX_SEGS
@@ -382,6 +400,8 @@ def lib() -> C.CDLL:
     L.dia_engine_set_mxfp4.argtypes = [C.c_void_p, C.POINTER(Mxfp4Streams)]
     L.dia_score.argtypes = [C.POINTER(ScoreArgs), C.c_void_p]
     L.dia_engine_set_score.argtypes = [C.c_void_p, C.POINTER(ScoreArgs)]
+    L.dia_act_stats.argtypes = [C.POINTER(ActStatsArgs), C.c_void_p]
+    L.dia_engine_set_calib.argtypes = [C.c_void_p, C.POINTER(CalibArgs)]
     L.dia_lora_apply.argtypes = [C.POINTER(LoraArgs), C.c_void_p]
     L.dia_lora_crosskv.argtypes = [C.POINTER(LoraCrossKvArgs), C.c_void_p]
     L.dia_engine_set_lora.argtypes = [C.c_void_p, C.POINTER(LoraStep)]

@@ -528,7 +528,7 @@ class DecodeSession:
                  s_cap: Optional[int] = None, audio_prompts: Optional[Sequence[Optional[np.ndarray]]] = None,
                  prompt_prefill: str = "auto", attention: str = "auto", score: bool = False,
                  adapters=None, adapter_ids: Optional[Sequence[Union[None, str, int]]] = None, cross_kv: str = "bf16",
-                 self_kv: str = "bf16", _slotted: bool = False):
+                 self_kv: str = "bf16", calibrate: bool = False, _slotted: bool = False):
         """audio_prompts: per utterance None or int codes [Tp, C] (reference model.py:311-353).  The prompt
         rows are replayed through the decode step before sampling starts (semantics: oracle.generate), or — with
         bf16 caches — prefilled as one packed MFMA batch; prompt_prefill="replay" forces the replay.
@@ -548,7 +548,29 @@ class DecodeSession:
         self_kv="fp8": the SELF caches are e4m3 bytes with one power-of-two scale per key and head (DESIGN.md "FP8 self K/V"): the step's
         self-attention quantises the new key as it appends it, k_self / v_self are not allocated (self_cache_bytes is 0.516 of the
         bf16 session's) and audio prompts replay through the decode step unless prompt_prefill="batched".  Needs bf16 K/V with the blocked V layout and
-        audio_length % 32 == 0; independent of cross_kv.  "bf16" (default): nothing of it exists."""
+        audio_length % 32 == 0; independent of cross_kv.  "bf16" (default): nothing of it exists.
+        calibrate=True (with teacher_tokens): the encoder pass and every step also accumulate, in front of each GEMM, the per-channel
+        sum of squares of its input rows on the device (dia_act_stats; DESIGN.md "Activation statistics"); act_stats() downloads them
+        once at the end.  Closed teacher-forced sessions only: slots, adapters=, a compacted checkpoint and seg="on" raise ValueError.
+        So do forced rows of unequal lengths or a max_tokens other than their length: teacher forcing acts on no EOS, so the rows behind
+        a shorter utterance would be counted.  Goes together with score=True."""
+        if calibrate:
+            why = None
+            if teacher_tokens is None:
+                why = "it measures teacher-forced rows: pass teacher_tokens"
+            elif _slotted:
+                why = "slots: a slot session admits and retires requests while it runs, calibration is for closed batches"
+            elif adapters is not None:
+                why = "adapters=: the statistics are the base model's, an adapter's correction is not part of any pruned kernel"
+            elif w.compacted:
+                why = "a compacted checkpoint: its kernels contract permuted, shortened channel lists (load it with compact='off')"
+            elif w.seg_layers:
+                why = "seg='on': the persistent MLP segments keep the inputs of co, wi and wo inside their launch"
+            elif len({int(np.asarray(t).shape[0]) for t in teacher_tokens}) != 1 or (max_tokens is not None and int(max_tokens) != int(np.asarray(teacher_tokens[0]).shape[0])):
+                why = ("forced rows of different lengths (or another max_tokens): every step counts the rows of every utterance, and a "
+                       "teacher-forced utterance does not end before max_tokens")
+            if why is not None:
+                raise ValueError(f"calibrate=True is not served with {why}")
         if adapter_ids is not None and adapters is None:
             raise ValueError("adapter_ids needs adapters= (an AdapterBank)")
         if score and (teacher_tokens is None or _slotted):
@@ -759,6 +781,9 @@ class DecodeSession:
             self._init_adapters(adapter_ids)
         # teacher-forced scoring: lp_cond, lp_cfg, H_cfg per row and channel; NaN = no step has scored this position
         self.scores = torch.full((B, self.T, self.C, 3), float("nan"), dtype=torch.float32, device=dev) if score else None
+        self._calib = None
+        if calibrate:
+            self._init_calib()
         self._engine = C.c_void_p()
         self._build_engine()
         self.prefilled = self.slotted            # slots are prefilled one by one, at admission
@@ -798,6 +823,53 @@ class DecodeSession:
     def _lora_common(self, a, x, ldx, D, gain, M):
         a.x, a.ldx, a.D, a.gain, a.eps, a.M = x, ldx, D, hb.ptr(gain), float(self.cfg.model.normalization_layer_epsilon), M
         a.adapter_of_slot, a.n_slots, a.n_adapters = hb.ptr(self.adapter_of_slot), self.B, len(self.adapters)
+
+    # ------------------------------------------------------------------ activation statistics (DESIGN.md "Activation statistics")
+    def _init_calib(self):
+        """one float64 accumulator per tap (the decode step's 6 * n_layer + 1, then the encoder pass's 4 * n_layer + 1) and one row
+        counter each; a tap's width is the contraction size of the kernels behind it"""
+        from . import calib as cal
+        from .weights import param_shapes
+        shp = param_shapes(self.cfg)
+        taps = cal.decoder_tap_names(self.cfg) + cal.encoder_tap_names(self.cfg)
+        kt = []
+        for names in taps:
+            Ks = {cal.contraction_size(k, shp[k]) for k in names}
+            if len(Ks) != 1 or next(iter(Ks)) % 32 != 0:
+                raise ValueError(f"calibrate=True: the kernels behind the tap of {names[0]} contract {sorted(Ks)} channels (one size, a multiple of 32)")
+            kt.append(next(iter(Ks)) // 32)
+        self._calib = dict(names=taps, kt=kt, n_dec=len(cal.decoder_tap_names(self.cfg)),
+                           acc=[torch.zeros(32 * k, dtype=torch.float64, device=self.dev) for k in kt],
+                           counters=torch.zeros(len(taps), dtype=torch.int64, device=self.dev))
+
+    def _enc_tap(self, st, i, P, kt, row_mask, M, ssq=None, width=0, eps=0.0):
+        """dia_act_stats over the encoder pass's plane set P in front of the GEMM of encoder tap i (bf16 planes; ssq: the normed stream)"""
+        c = self._calib
+        j = c["n_dec"] + i
+        a = hb.ActStatsArgs()
+        a.x, a.plane_stride, a.ktiles = _plane_set(P, kt)
+        a.ktiles_used, a.M, a.rows_pad, a.act_f32 = c["kt"][j], M, M, 0
+        if ssq is not None:
+            a.ssq_in, a.ssq_in_n, a.ssq_ld, a.inv_d, a.eps = hb.ptr(ssq), width // 16, M, 1.0 / width, eps
+        a.row_mask = hb.ptr(row_mask)
+        a.acc, a.counter = hb.ptr(c["acc"][j]), c["counters"].data_ptr() + 8 * j
+        hb.check(hb.lib().dia_act_stats(C.byref(a), st), "dia_act_stats")
+
+    def act_stats(self):
+        """calib.ActStats of everything this session has counted so far (calibrate=True); synchronises"""
+        from . import calib as cal
+        if self._calib is None:
+            raise hb.DiaHipError("act_stats(): the session was not built with calibrate=True")
+        self.sync()
+        c = self._calib
+        counts = c["counters"].cpu().numpy()
+        out = cal.ActStats.zeros(self.cfg)
+        for j, names in enumerate(c["names"]):
+            v = c["acc"][j].cpu().numpy()
+            for k in names:
+                out.sums[k] = v.copy()
+                out.rows[k] = int(counts[j])
+        return out
 
     # ------------------------------------------------------------------ engine descriptor
     def _embed_args(self) -> hb.EmbedArgs:
@@ -899,6 +971,14 @@ class DecodeSession:
             sc.cfg_scale, sc.eos, sc.pad, sc.bos = sp.cfg_scale, sp.eos, sp.pad, sp.bos
             sc.tokens, sc.cur, sc.first_step, sc.fsm, sc.out = sp.tokens, sp.cur, sp.first_step, sp.fsm, hb.ptr(self.scores)
             hb.check(hb.lib().dia_engine_set_score(self._engine, C.byref(sc)), "dia_engine_set_score")
+        if self._calib is not None:                                         # one dia_act_stats in front of every GEMM of the step
+            c = self._calib
+            nd = c["n_dec"]
+            acc = (C.c_void_p * nd)(*[hb.ptr(t) for t in c["acc"][:nd]])   # (the engine copies both arrays)
+            kts = (C.c_int32 * nd)(*c["kt"][:nd])
+            ca = hb.CalibArgs(n_layer=n, acc=C.cast(acc, C.POINTER(C.c_void_p)), kt=C.cast(kts, C.POINTER(C.c_int32)),
+                              counters=c["counters"].data_ptr())
+            hb.check(hb.lib().dia_engine_set_calib(self._engine, C.byref(ca)), "dia_engine_set_calib")
         if self.adapters is not None:                                       # unmerged adapters: two more launches per layer
             bank, QH, KVH = self.adapters, d.gqa_query_heads, d.kv_heads
             ll = (hb.LoraLayer * n)()                                       # (the engine copies the array)
@@ -1013,6 +1093,11 @@ class DecodeSession:
                                               ssq.data_ptr() + offs[i] * 4, Mp, hb.ptr(w.enc_cmap_first), st), "dia_embed_text")
 
                 gemm = partial(_launch_gemm, st, M=Mp, ssq=ssq, ssq_ld=Mp, width=E, eps=eps, w_planes=w.weight_planes)
+                # calibrate=True: the statistics of the rows in front of every GEMM; every packed row of an utterance counts, no padding row
+                tap = None
+                if self._calib is not None:
+                    live_rows = (row_b >= 0).to(torch.uint8)
+                    tap = partial(self._enc_tap, st, row_mask=live_rows, M=Mp)
 
                 def cross_kv(kc, vc):               # the cross-K/V epilogue writes every utterance's rows of these caches (row_b / seg_off)
                     return (hb.ptr(kc), hb.ptr(vc), self.kv_code, d.cross_query_heads, self.S, 0, self.v_blocked, self.kv_plane_cross,
@@ -1022,6 +1107,8 @@ class DecodeSession:
                     Hl = EL["heads"]                 # live heads of this layer (all of them unless the checkpoint was pruned)
                     nq = 3 * Hl * HEAD_DIM
                     if Hl > 0:
+                        if tap:
+                            tap(4 * i, px, ekt, ssq=ssq, width=E, eps=eps)
                         gemm(px, ekt, EL["qkv"], hb.EPI_SCALE_STORE, ssq_in=True, out=qkv, ldo=nq)
                         segs = [bank.seg(("enc", i, p_), j * Hl * HEAD_DIM) for j, p_ in enumerate("qkv")] if bank is not None else []
                         segs = [s_ for s_ in segs if s_.n_cols]
@@ -1039,11 +1126,17 @@ class DecodeSession:
                         ea_.cos_t, ea_.sin_t, ea_.kp, ea_.vp = hb.ptr(w.cos_t), hb.ptr(w.sin_t), hb.ptr(kp), hb.ptr(vp)
                         ea_.P, ea_.p_plane_stride, ea_.p_ktiles = _plane_set(pa, akt)
                         hb.check(L.dia_enc_attn(C.byref(ea_), st), "dia_enc_attn")
+                        if tap:
+                            tap(4 * i + 1, pa, akt)
                         gemm(pa, akt, EL["o"], hb.EPI_RESID_EMIT, out=x, ldo=E, gnext=EL["g_mlp"], P=px, p_kt=ekt, ssq_out=True,
                              cmap=EL["cmap_mlp"])
                     else:
                         raise hb.DiaHipError("encoder layer with every attention head pruned is not supported")
+                    if tap:
+                        tap(4 * i + 2, px, ekt, ssq=ssq, width=E, eps=eps)
                     gemm(px, ekt, EL["wi"], hb.EPI_SWIGLU_EMIT, ssq_in=True, P=ph, p_kt=hkt)
+                    if tap:
+                        tap(4 * i + 3, ph, hkt)
                     gnext = w.enc_layers[i + 1]["g_sa"] if i + 1 < len(w.enc_layers) else w.enc_norm
                     # 17..128 rows: wo (K = 4096) as two K halves per strip, so that it rides the z-form of the 16-row kernel instead
                     # of the generic one (whose 4-m-tile form spills)
@@ -1055,6 +1148,8 @@ class DecodeSession:
                     gemm(ph, hkt, EL["wo"], hb.EPI_RESID_EMIT, out=x, ldo=E, gnext=gnext, P=px, p_kt=ekt, ssq_out=True,
                          cmap=EL["cmap_next"], sk=wo_sk)
                 # px now holds planes(x * encoder.norm.weight); ssq the row sums of squares of x
+                if tap:
+                    tap(4 * len(w.enc_layers), px, ekt, ssq=ssq, width=E, eps=eps)
                 ckv_all = w.ckv_all() if hb.get_tuning("ckv_merge") != 0 else None
                 if ckv_all is not None:             # ONE launch for the 18 layers: their input is the same (18 x 13.8 -> 1 x ~100 us at 98 rows)
                     gemm(px, ekt, ckv_all, hb.EPI_CROSSKV, ssq_in=True, kv=cross_kv(self.k_cross_all, self.v_cross_all),

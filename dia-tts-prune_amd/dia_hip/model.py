@@ -136,7 +136,11 @@ class Dia:
             # leaves the missing tensors at their random initialisation; listed in INTEGRATION.md
             raise RuntimeError(f"Missing keys in checkpoint: {missing}")
         with torch.cuda.device(self.device):
+            # sparse_weights="2:4": the checkpoint is taken as the 2:4 one it is said to be and never compacted.  An activation-aware
+            # 2:4 pruning (offline_prune.py --act-stats) zeroes a whole input channel wherever that channel is among the two weakest of
+            # its group in every column; to the structure detection such rows look like structured pruning
             self.model = DeviceWeights(self.config, sd, self.device, sparse=self.sparse_weights,
+                                       compact="off" if self.sparse_weights == "2:4" else "auto",
                                        quant=self.weight_format if self.weight_format in ("mxfp8", "mxfp4") else "off")
             # DenseGeneral kernels are streamed as ONE bf16 tile set by the fast kernels.  A checkpoint whose values are
             # bf16-representable (bf16-trained weights stored as fp32, the synthetic ones) loses nothing.  A genuine fp32
@@ -376,6 +380,59 @@ class Dia:
         """score_batch for one utterance"""
         return self.score_batch([text], [codes], audio_prompts=None if audio_prompt is None else [audio_prompt], cfg_scale=cfg_scale,
                                 audio_prompt_texts=[audio_prompt_text], adapters=[adapter])[0]
+
+    @torch.inference_mode()
+    def calibrate(self, texts: Sequence[str], codes_list: Sequence, *, audio_prompts: Optional[Sequence] = None,
+                  cfg_scale: float = 3.0, audio_prompt_texts: Optional[Sequence[Optional[str]]] = None, use_graph: bool = True,
+                  batch: int = 8, stats: Optional["ActStats"] = None) -> "ActStats":
+        """Activation statistics of the loaded checkpoint over known audio codes (DESIGN.md "Activation statistics"): the texts and
+        codes are forced through the model as score_batch forces them (score.teacher_rows), up to ``batch`` (1..8) utterances of equal
+        row count per decode session, and every GEMM input's per-channel sum of squares is accumulated on the device.  Returns one ActStats over all of
+        them, merged into ``stats`` when given (statistics of earlier calls).  What offline_prune.py --act-stats takes.
+        The checkpoint must be loaded uncompacted, without seg="on"; no adapter takes part."""
+        from .calib import ActStats
+        from .score import check_prompt_rows, teacher_rows
+
+        if self.model is None:
+            raise RuntimeError("no weights loaded")
+        n = len(texts)
+        if n < 1 or len(codes_list) != n or not 1 <= batch <= 8:
+            raise ValueError("calibrate: at least one text, as many codes, and batch in 1..8")
+        prompts = [None] * n if audio_prompts is None else [None if p is None else (p.detach().cpu().numpy() if isinstance(p, torch.Tensor) else np.asarray(p)) for p in audio_prompts]
+        apt = audio_prompt_texts or [None] * n
+        rows = [teacher_rows(self.config, c.detach().cpu().numpy() if isinstance(c, torch.Tensor) else c, prompt=p)
+                for c, p in zip(codes_list, prompts)]
+        for r, p in zip(rows, prompts):
+            if p is not None:
+                check_prompt_rows(self.config, r, p)
+            if r.shape[0] > self.config.data.audio_length:
+                raise ValueError(f"{r.shape[0]} token rows do not fit audio_length {self.config.data.audio_length}")
+        ids = [encode_text(effective_text(t, a), self.config) for t, a in zip(texts, apt)]
+        out = stats
+        # a teacher-forced utterance runs to the session's max_tokens: a session takes utterances of one row count, so that no step
+        # counts rows behind an utterance's codes
+        by_len: Dict[int, List[int]] = {}
+        for i, r in enumerate(rows):
+            by_len.setdefault(r.shape[0], []).append(i)
+        chunks = [idx[i: i + batch] for _, idx in sorted(by_len.items()) for i in range(0, len(idx), batch)]
+        # the session generate() would use, except that forced rows are replayed (the batched prompt prefill does not serve them)
+        caches = dict(cross_kv=self.cross_kv, prompt_prefill="replay" if self.prompt_prefill == "batched" else self.prompt_prefill)
+        caches["self_kv"] = self.self_kv
+        for sel in chunks:
+            mt = rows[sel[0]].shape[0]
+            with torch.cuda.device(self.device):
+                s = DecodeSession(self.model, [ids[i] for i in sel], kv_dtype=self._kv_dtype(), max_tokens=mt, **caches,
+                                  cfg_scale=cfg_scale, temperature=0.0, teacher_tokens=[rows[i] for i in sel],
+                                  audio_prompts=[prompts[i] for i in sel], calibrate=True)
+                try:
+                    s.prefill()
+                    s.decode(mt - 1, use_graph=use_graph)
+                    part = s.act_stats()
+                    s._raise_if_invalid()
+                finally:
+                    s.close()
+            out = part if out is None else out.merge(part)
+        return out
 
     @torch.inference_mode()
     def generate_stream(self, requests_or_texts: Sequence[Union[str, GenerationRequest]], slots: int = 8,

@@ -691,6 +691,69 @@ int dia_mxfp4_classes(int rows);
  * Scoring is for closed teacher-forced batches: DIA_E_ARG when the engine's sample.teacher == 0 or its sampler has per-slot state,
  * and for everything dia_score refuses. */
 int dia_engine_set_score(dia_engine* e, const dia_score_args* a);
+
+/* ------------------------------------------------------------------------------------------------
+ * Activation statistics for activation-aware pruning (csrc/calib.hip; DESIGN.md "Activation statistics").  The reference prunes by
+ * weight magnitude alone (offline_prune.py:82-156); Wanda ranks by |W[k][n]| * ||x_k||_2 and needs, per matrix, the sum of
+ * squares of every input channel over a calibration set.  One launch, for one activation plane set:
+ *   acc[k] += sum over counted rows m, in ascending m, of (double)v * (double)v      k in [0, 32 * ktiles_used)
+ *   v       = fl32( x[m][k] * scale[m] )
+ * x[m][k] is read from fp32 tiles (act_f32 = 1: [mtile][ktile][lane][8]) or from three bf16 planes (act_f32 = 0: x = (hi + mid) + lo
+ * in fp32, exact by construction).  scale[m] = 1 without ssq_in, else the row's inverse RMS as the GEMV consumers form it, in
+ * fp32 with contraction off:
+ *   q = 0;  for i = 0 .. ssq_in_n - 1, ascending:  q = fl32(q + ssq_in[i * ssq_ld + m]);
+ *   scale[m] = 1.0f / sqrtf( fl32( fl32(q * inv_d) + eps ) )          (division and square root correctly rounded)
+ * A row counts iff  (row_mask == NULL or row_mask[m] != 0)  and, with rows_per_slot == 2, the gate of dia_score holds for
+ * utterance b = m / 2:  first_step[b] <= cur[b] < T, cur[b] >= 0 and fsm[b][3] == 0.  Rows m >= M (tile padding) are never read.
+ * *counter advances by the number of counted rows (one thread).  One thread owns 8 consecutive channels and walks the rows in
+ * order; there are no atomics and no cross-thread sums, so acc[k] has the same bits however the rows are spread over launches that
+ * keep their order, and under graph replay as eager.  Nothing but acc and counter is written.
+ * DIA_E_ARG with a message, before any HIP call: a null x, acc or counter; ktiles <= 0; ktiles_used outside [0, ktiles]; rows_pad
+ * not a positive multiple of 16; M <= 0 or M > rows_pad; three planes with plane_stride < rows_pad * ktiles * 32; ssq_in without
+ * ssq_in_n > 0 or with ssq_ld < M; rows_per_slot other than 0 and 2; the gate without cur or without T > 0; x or acc not
+ * 16-byte aligned. */
+typedef struct {
+  const void* x;               /* plane set: fp32 tiles, or three bf16 planes plane_stride elements apart */
+  int64_t plane_stride;        /* elements between the bf16 planes (act_f32 = 0) */
+  int32_t ktiles;              /* k-tiles (32 channels) per m-tile of the plane set: its row pitch */
+  int32_t ktiles_used;         /* k-tiles to accumulate, from 0; 0 = ktiles */
+  int32_t M;                   /* rows */
+  int32_t rows_pad;            /* rows the plane set holds: 16 * its m-tiles */
+  int32_t act_f32;
+  int32_t ssq_in_n;            /* partial sums per row */
+  const float* ssq_in;         /* [ssq_in_n][ssq_ld] strip partial sums of squares, or NULL: scale 1 */
+  int32_t ssq_ld;
+  float inv_d;
+  float eps;
+  int32_t rows_per_slot;       /* 0: no gate; 2: rows 2b and 2b + 1 belong to utterance b (M <= 2 * entries of cur) */
+  const uint8_t* row_mask;     /* device [M] or NULL */
+  const int32_t* cur;          /* device [B] (the gate) */
+  const int32_t* first_step;   /* [B] or NULL = 1 everywhere */
+  const int32_t* fsm;          /* [B][8] or NULL = nobody is done */
+  int32_t T;
+  int32_t _pad0;
+  double* acc;                 /* device [32 * ktiles_used], read and written */
+  int64_t* counter;            /* device, one per call site */
+} dia_act_stats_args;
+int dia_act_stats(const dia_act_stats_args* a, void* stream);
+
+/* The taps of a calibrating engine, in the order a step issues them: for layer l = 0 .. n_layer - 1 one per matrix of
+ * dia_step_mat (index 6 * l + m: qkv, o, cq, co, wi, wo), then the logits head's (index 6 * n_layer).  Each is one dia_act_stats on
+ * the plane set its matrix is about to contract with (PL_X with the row scale its consumer uses, PL_A, PL_H), gated as dia_score. */
+typedef struct {
+  int32_t n_layer;             /* must equal dia_engine_desc.n_layer */
+  int32_t _pad0;
+  double* const* acc;          /* host array [6 * n_layer + 1] of device arrays, copied; acc[i] holds 32 * kt[i] doubles */
+  const int32_t* kt;           /* host array [6 * n_layer + 1]: k-tiles of every tap (the matrix's K / 32), copied */
+  int64_t* counters;           /* device [6 * n_layer + 1] */
+} dia_calib_args;
+/* before the first step (DIA_E_STATE afterwards): every step then issues one dia_act_stats in front of each of its GEMMs, eager and
+ * in the captured graph: 6 * n_layer + 1 more launches, which dia_engine_launches_per_step, the prefetch list and the profile walk
+ * see.  A calibrating engine keeps wo's in-launch merge (under deferral the q/k/v input of layers > 0 never reaches planes_x; the
+ * two forms are bit-identical).  NULL = the step without them, launch for launch.  DIA_E_ARG: an engine that is not teacher-forced
+ * or whose sampler has per-slot state, compaction or strip maps on any edge, persistent segments, the knobs mlp_fuse and wo_diag,
+ * a tap wider than its plane set, and everything dia_act_stats refuses for a tap. */
+int dia_engine_set_calib(dia_engine* e, const dia_calib_args* a);
 /* number of kernel launches in one decode step */
 int dia_engine_launches_per_step(const dia_engine* e);
 

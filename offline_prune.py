@@ -26,12 +26,16 @@ def main(argv=None) -> int:
     p.add_argument("--model-path", type=str, required=True, help="directory of the dense model: config.json plus its checkpoint")
     p.add_argument("--output-dir", type=str, required=True, help="where pytorch_model.bin and config.json of the pruned model go")
     p.add_argument("--prune-mode", type=str, required=True, choices=["unstructured", "structured", "2:4"],
-                   help="global magnitude pruning of single weights, whole slices along --prune-dim, or 2:4 semi-structured (2 of every 4 consecutive K of each column)")
+                   help="global magnitude pruning of single weights (with --act-stats: per output column), whole slices along --prune-dim, or 2:4 semi-structured (2 of every 4 consecutive K of each column)")
     p.add_argument("--prune-amount", type=float, required=True, help="share of weights (unstructured) or of slices per matrix (structured) to zero, strictly between 0 and 1")
     p.add_argument("--prune-dim", type=int, default=0, help="structured mode: the axis whose slices are ranked and zeroed")
     p.add_argument("--prune-norm", type=int, default=2, choices=[1, 2], help="structured mode: rank slices by their L1 or L2 norm")
     p.add_argument("--device", type=str, default="cpu", help="accepted for compatibility; the tool runs on the CPU")
     p.add_argument("--compute-dtype", type=str, default="float32", choices=["float32"], help="pruning arithmetic is float32")
+    p.add_argument("--act-stats", type=str, default=None, metavar="FILE",
+                   help="activation statistics (.npz of cli.py --calibrate-codes / Dia.calibrate): every mode ranks by |W[k, n]| * RMS of input "
+                        "channel k (Wanda) instead of |W[k, n]|.  unstructured then zeroes the --prune-amount lowest scores of EVERY OUTPUT "
+                        "COLUMN of each kernel (Wanda's comparison group), unlike the global L1 ranking over all kernels used without it")
     a = p.parse_args(argv)
     if not (0.0 < a.prune_amount < 1.0):
         print("Error: --prune-amount must be between 0.0 and 1.0 (exclusive).")
@@ -56,13 +60,22 @@ def main(argv=None) -> int:
     except Exception as e:
         print(f"Error loading model: {e}")
         return 1
-    print(f"\nApplying {a.prune_mode} pruning...")
+    stats = None
+    if a.act_stats:
+        from dia_hip.calib import ActStats
+        try:
+            stats = ActStats.load(a.act_stats)
+            stats.check_against(cfg)
+        except Exception as e:
+            print(f"Error loading activation statistics: {e}")
+            return 1
+    print(f"\nApplying {a.prune_mode} pruning{' with activation statistics' if stats is not None else ''}...")
     if a.prune_mode == "unstructured":
-        psd = unstructured_prune_state_dict(cfg, sd, a.prune_amount)
+        psd = unstructured_prune_state_dict(cfg, sd, a.prune_amount, act_stats=stats)
     elif a.prune_mode == "2:4":
-        psd = semi_structured_prune_state_dict(cfg, sd)
+        psd = semi_structured_prune_state_dict(cfg, sd, act_stats=stats)
     else:
-        psd, _ = structured_prune_state_dict(cfg, sd, a.prune_amount, dim=a.prune_dim, n=a.prune_norm)
+        psd, _ = structured_prune_state_dict(cfg, sd, a.prune_amount, dim=a.prune_dim, n=a.prune_norm, act_stats=stats)
     print(f"Achieved sparsity: {sparsity(cfg, psd):.4f}")
     print(f"\nSaving pruned model to {a.output_dir}...")
     torch.save(dict(psd), out / "pytorch_model.bin")
