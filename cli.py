@@ -106,6 +106,11 @@ def build_parser() -> argparse.ArgumentParser:
                    "the order of the codes files")
     g.add_argument("--stats-output", type=str, default=None, help="with --calibrate-codes: the .npz the statistics go to; an existing file "
                    "of the same model is merged into (sums and row counts add)")
+    g.add_argument("--gram-output", type=str, default=None, metavar="FILE.npz", help="with --calibrate-codes: also accumulate the Gram matrix of every "
+                   "decode-step GEMM input (Dia.calibrate(gram=True)) and write them here, what offline_quantize.py --gram-stats takes; an "
+                   "existing file of the same model is merged into.  T (T + 1) / 2 * 8 KiB of device memory per tap of T = K / 32 k-tiles")
+    g.add_argument("--gram-layers", type=str, default=None, metavar="A:B", help="with --gram-output: only decoder layers A .. B - 1 (index n_layer "
+                   "is the logits head), to bound memory; runs over disjoint ranges merge into one file")
     g = p.add_argument_group("Audio distance")
     g.add_argument("--compare-audio", type=str, nargs=2, default=None, metavar=("A.wav", "B.wav"), help="(build-only) print the multi-scale "
                    "STFT and log-mel distances between two audio files as one JSON line, then exit: loads no model; B is resampled to A's "
@@ -261,7 +266,7 @@ def calibrate_to_file(dia, args, text: str) -> int:
     """--calibrate-codes: Dia.calibrate over the files' codes; the statistics to --stats-output, a summary as one JSON line"""
     import json
 
-    from dia_hip.calib import ActStats
+    from dia_hip.calib import ActStats, GramStats
 
     codes = [np.load(f) for f in args.calibrate_codes]
     texts = [text] * len(codes)
@@ -271,10 +276,23 @@ def calibrate_to_file(dia, args, text: str) -> int:
             raise ValueError(f"--calibrate-texts holds {len(texts)} lines for {len(codes)} codes files")
     out = Path(args.stats_output)
     prior = ActStats.load(str(out)) if out.is_file() else None
-    stats = dia.calibrate(texts, codes, cfg_scale=args.cfg_scale, stats=prior)
+    summary = {}
+    if args.gram_output:
+        gout = Path(args.gram_output)
+        layers = None
+        if args.gram_layers:
+            first, _, end = args.gram_layers.partition(":")
+            layers = (int(first), int(end))
+        stats, grams = dia.calibrate(texts, codes, cfg_scale=args.cfg_scale, stats=prior, gram=True, gram_layers=layers,
+                                     gram_stats=GramStats.load(str(gout)) if gout.is_file() else None)
+        gout.parent.mkdir(parents=True, exist_ok=True)
+        grams.save(str(gout))
+        summary = dict(gram_taps=len(grams.taps()), gram_rows_min=min(grams.rows.values()), gram_bytes=int(sum(v.nbytes for v in grams.packed.values())))
+    else:
+        stats = dia.calibrate(texts, codes, cfg_scale=args.cfg_scale, stats=prior)
     out.parent.mkdir(parents=True, exist_ok=True)
     stats.save(str(out))
-    print(json.dumps(dict(files=len(codes), kernels=len(stats.names()), rows_min=min(stats.rows.values()), rows_max=max(stats.rows.values()))))
+    print(json.dumps(dict(files=len(codes), kernels=len(stats.names()), rows_min=min(stats.rows.values()), rows_max=max(stats.rows.values()), **summary)))
     return 0
 
 
@@ -394,8 +412,12 @@ def main(argv=None) -> int:
             parser.error("--calibrate-codes generates nothing: not with --score-codes, --output, --codes-output, --slots, --stream-chunk, "
                          "--audio-prompt or --codec-path.")
         args.no_dac = True
-    elif args.stats_output or args.calibrate_texts:
-        parser.error("--stats-output / --calibrate-texts need --calibrate-codes.")
+    elif args.stats_output or args.calibrate_texts or args.gram_output:
+        parser.error("--stats-output / --calibrate-texts / --gram-output need --calibrate-codes.")
+    if args.gram_layers and not args.gram_output:
+        parser.error("--gram-layers needs --gram-output.")
+    if args.gram_layers and (args.gram_layers.count(":") != 1 or not all(v.isdigit() for v in args.gram_layers.split(":"))):
+        parser.error("--gram-layers takes A:B, two layer indices.")
     if args.audio_prompt and not args.audio_prompt_text:
         parser.error("--audio-prompt needs its transcript: pass --audio-prompt-text")
     bank_dirs = parse_adapter_flags(parser, args)

@@ -9,6 +9,7 @@
 #include "errors.hpp"
 #include "launch.hpp"
 #include "tuning.hpp"
+#include <cstdio>
 #include <cstdlib>
 #include <string>
 #include <vector>
@@ -35,6 +36,10 @@ struct dia_engine {
   std::vector<double*> calib_acc;       // ... per tap (6 * l + m, the logits head last): the accumulator,
   std::vector<int32_t> calib_kt;        // ... its k-tiles
   int64_t* calib_counters = nullptr;    // ... and the device row counters
+  bool gram_on = false;                 // dia_engine_set_gram: the same taps with dia_act_gram, at the taps that have a matrix
+  std::vector<double*> gram_ptr;        // ... per tap: the packed Gram matrix or nullptr (no launch),
+  std::vector<int32_t> gram_kt;         // ... its k-tiles
+  int64_t* gram_counters = nullptr;     // ... and the device row counters
   std::vector<dia_lora_layer> lora;     // dia_engine_set_lora: the adapter tables of the two decode sites per layer (empty: no LoRA launches)
   const int32_t* lora_slot = nullptr;   // ... and the device array adapter_of_slot [B]
   int lora_adapters = 0;
@@ -54,6 +59,7 @@ int dia_prefetch_launch(const void* ptr, long nbytes, int nblocks, hipStream_t s
 int dia_score_validate(const dia_score_args* a, const char* who);
 int dia_lora_validate(const dia_lora_args* a, const char* who);
 int dia_act_stats_validate(const dia_act_stats_args* a, const char* who);
+int dia_act_gram_validate(const dia_act_gram_args* a, const char* who);
 static int ensure_sink();
 static int dia_lora_noop(void* st);
 
@@ -133,13 +139,16 @@ static mat_w mat_weights(const dia_engine* e, int l, int m) {
 // The launches of one step, in order: launch(layer, what) for every one, `what` a dia_step_mat or one of the launches below.
 // enqueue_step issues them; the prefetch list and dia_engine_launches_per_step walk the same sequence.
 // CALIB + m: dia_engine_set_calib's tap in front of matrix m (a dia_act_stats over the planes m is about to read)
-enum { ATTN_SELF = DIA_MAT_COUNT, ATTN_CROSS, SEG_MLP, SAMPLER, SCORE, LORA_QKV, LORA_CQ, CALIB };
+// GRAM + m: dia_engine_set_gram's tap in the same place (a dia_act_gram), issued only where the tap has a matrix
+enum { ATTN_SELF = DIA_MAT_COUNT, ATTN_CROSS, SEG_MLP, SAMPLER, SCORE, LORA_QKV, LORA_CQ, CALIB, GRAM = CALIB + DIA_MAT_COUNT };
+static inline int tap_index(const dia_engine* e, int l, int m) { return l < e->d.n_layer ? 6 * l + m : 6 * e->d.n_layer; }
 template <class Launch>
 static int step_sequence(const dia_engine* e, bool with_sampler, Launch&& launch) {
   int rc = DIA_OK;                   // the first failure ends the sequence
   auto run = [&](int l, std::initializer_list<int> seq) {
     for (int what : seq) {
       if (!rc && e->calib_on && what < DIA_MAT_COUNT) rc = launch(l, CALIB + what);
+      if (!rc && e->gram_on && what < DIA_MAT_COUNT && e->gram_ptr[tap_index(e, l, what)]) rc = launch(l, GRAM + what);
       if (!rc) rc = launch(l, what);
     }
   };
@@ -348,6 +357,26 @@ static int enqueue_step(dia_engine* e, bool with_sampler) {
     a.acc = e->calib_acc[i]; a.counter = e->calib_counters + i;
     return a;
   };
+  // dia_engine_set_gram: the same rows, into the tap's packed Gram matrix
+  auto step_gram = [&](int l, int m) {
+    const dia_gemm_args g = step_gemm(l, m);
+    const int i = tap_index(e, l, m);
+    dia_act_gram_args a = {};
+    a.x = g.A; a.plane_stride = g.a_plane_stride; a.ktiles = g.a_ktiles; a.ktiles_used = e->gram_kt[i]; a.M = R; a.rows_pad = d.rows_pad;
+    a.act_f32 = F; a.ssq_in = g.ssq_in; a.ssq_in_n = g.ssq_in_n; a.ssq_ld = g.ssq_ld; a.inv_d = g.inv_d; a.eps = g.eps;
+    a.rows_per_slot = 2; a.cur = d.sample.cur; a.first_step = d.sample.first_step; a.fsm = d.sample.fsm; a.T = d.T;
+    a.gram = e->gram_ptr[i]; a.counter = e->gram_counters + i;
+    return a;
+  };
+  if (e->gram_on && e->launches == 0 && !e->exec) {       // as below: checked before the first launch of the first step
+    for (int l = 0; l <= d.n_layer; ++l)
+      for (int m = (l < d.n_layer ? 0 : DIA_MAT_LOGITS); m < (l < d.n_layer ? DIA_MAT_LOGITS : DIA_MAT_COUNT); ++m) {
+        if (!e->gram_ptr[tap_index(e, l, m)]) continue;
+        const dia_act_gram_args a = step_gram(l, m);
+        const int vrc = dia_act_gram_validate(&a, "dia_engine_set_gram");
+        if (vrc) return vrc;
+      }
+  }
   if (e->calib_on && e->launches == 0 && !e->exec) {      // every tap's descriptor is checked before the first launch of the first step
     for (int l = 0; l <= d.n_layer; ++l)
       for (int m = (l < d.n_layer ? 0 : DIA_MAT_LOGITS); m < (l < d.n_layer ? DIA_MAT_LOGITS : DIA_MAT_COUNT); ++m) {
@@ -391,6 +420,9 @@ static int enqueue_step(dia_engine* e, bool with_sampler) {
       rc = dia_sample(&d.sample, st);
     } else if (what == SCORE) {
       rc = dia_score(&e->score, st);
+    } else if (what >= GRAM) {
+      const dia_act_gram_args ga = step_gram(l, what - GRAM);
+      rc = dia_act_gram(&ga, st);
     } else if (what >= CALIB) {
       const dia_act_stats_args ca = step_tap(l, what - CALIB);
       rc = dia_act_stats(&ca, st);
@@ -684,39 +716,73 @@ extern "C" int dia_engine_set_score(dia_engine* e, const dia_score_args* a) {
   return DIA_OK;
 }
 
+// what a tapped step needs of its engine, for dia_engine_set_calib and dia_engine_set_gram alike; cap[i]: the k-tiles of tap i's plane set
+static int tap_preconditions(const dia_engine* e, const char* who, int n_layer, bool have_arrays, std::vector<int>* cap) {
+  char msg[256];
+  auto fail = [&](const char* why) { snprintf(msg, sizeof msg, "%s: %s", who, why); return dia_fail(DIA_E_ARG, msg); };
+  const dia_engine_desc& d = e->d;
+  const dia_sample_args& sp = d.sample;
+  if (n_layer != d.n_layer || !have_arrays) return fail("n_layer differs from the engine's, or a null array");
+  if (!sp.teacher) return fail("calibration needs a teacher-forced engine (sample.teacher)");
+  if (sp.slot_cfg_scale || sp.slot_temperature || sp.slot_top_p || sp.slot_top_k || sp.slot_max_tokens)
+    return fail("calibration is for closed batches, this sampler has per-slot state");
+  if (!sp.cur) return fail("the gate needs sample.cur");
+  if (e->seg) return fail("the persistent MLP segments keep the inputs of co, wi, wo and q/k/v inside their launch (seg must be off)");
+  if (dia_tune(DIA_TUNE_MLP_FUSE) > 0) return fail("the knob mlp_fuse keeps wo's input inside the fused launch");
+  if (dia_tune(DIA_TUNE_WO_DIAG) == 1) return fail("the knob wo_diag changes the partial sums behind wo");
+  if (sp.embed.cmap) return fail("compacted checkpoint (compaction map on the first layer's q/k/v input)");
+  for (int l = 0; l < d.n_layer; ++l) {
+    const dia_dec_layer& L = e->layers[l];
+    if (L.cmap_ca || L.cmap_mlp || L.cmap_next || L.smap_qkv || L.smap_cq)
+      return fail("compacted checkpoint (strip or compaction map on an edge of the step)");
+  }
+  const int n = 6 * d.n_layer + 1;
+  const int akt = (max(d.q_heads, d.cq_heads) * 128) / 32;
+  cap->resize(n);
+  for (int i = 0; i < n; ++i) {
+    const int m = i < 6 * d.n_layer ? i % 6 : DIA_MAT_LOGITS;
+    const int in = STEP_MATS[m].in;
+    (*cap)[i] = in == PL_X ? d.D / 32 : (in == PL_A ? akt : d.F / 32);
+  }
+  return DIA_OK;
+}
+
 extern "C" int dia_engine_set_calib(dia_engine* e, const dia_calib_args* a) {
   if (!e) return dia_fail(DIA_E_ARG, "dia_engine_set_calib: null engine");
   if (e->exec || e->launches > 0) return dia_fail(DIA_E_STATE, "dia_engine_set_calib: a step has already been issued or captured");
   if (!a) { e->calib_on = false; e->calib_acc.clear(); e->calib_kt.clear(); e->calib_counters = nullptr; return DIA_OK; }
-  const dia_engine_desc& d = e->d;
-  const dia_sample_args& sp = d.sample;
-  if (a->n_layer != d.n_layer || !a->acc || !a->kt || !a->counters)
-    return dia_fail(DIA_E_ARG, "dia_engine_set_calib: n_layer differs from the engine's, or a null acc / kt / counters");
-  if (!sp.teacher) return dia_fail(DIA_E_ARG, "dia_engine_set_calib: calibration needs a teacher-forced engine (sample.teacher)");
-  if (sp.slot_cfg_scale || sp.slot_temperature || sp.slot_top_p || sp.slot_top_k || sp.slot_max_tokens)
-    return dia_fail(DIA_E_ARG, "dia_engine_set_calib: calibration is for closed batches, this sampler has per-slot state");
-  if (!sp.cur) return dia_fail(DIA_E_ARG, "dia_engine_set_calib: the gate needs sample.cur");
-  if (e->seg) return dia_fail(DIA_E_ARG, "dia_engine_set_calib: the persistent MLP segments keep the inputs of co, wi, wo and q/k/v inside their launch (seg must be off)");
-  if (dia_tune(DIA_TUNE_MLP_FUSE) > 0) return dia_fail(DIA_E_ARG, "dia_engine_set_calib: the knob mlp_fuse keeps wo's input inside the fused launch");
-  if (dia_tune(DIA_TUNE_WO_DIAG) == 1) return dia_fail(DIA_E_ARG, "dia_engine_set_calib: the knob wo_diag changes the partial sums behind wo");
-  if (sp.embed.cmap) return dia_fail(DIA_E_ARG, "dia_engine_set_calib: compacted checkpoint (compaction map on the first layer's q/k/v input)");
-  for (int l = 0; l < d.n_layer; ++l) {
-    const dia_dec_layer& L = e->layers[l];
-    if (L.cmap_ca || L.cmap_mlp || L.cmap_next || L.smap_qkv || L.smap_cq)
-      return dia_fail(DIA_E_ARG, "dia_engine_set_calib: compacted checkpoint (strip or compaction map on an edge of the step)");
-  }
-  const int n = 6 * d.n_layer + 1;
-  const int akt = (max(d.q_heads, d.cq_heads) * 128) / 32;
-  for (int i = 0; i < n; ++i) {
-    const int m = i < 6 * d.n_layer ? i % 6 : DIA_MAT_LOGITS;
-    const int in = STEP_MATS[m].in;
-    const int cap = in == PL_X ? d.D / 32 : (in == PL_A ? akt : d.F / 32);
-    if (!a->acc[i] || a->kt[i] <= 0 || a->kt[i] > cap) return dia_fail(DIA_E_ARG, "dia_engine_set_calib: a tap without acc, or k-tiles outside (0, k-tiles of its plane set]");
-  }
+  std::vector<int> cap;
+  const int rc = tap_preconditions(e, "dia_engine_set_calib", a->n_layer, a->acc && a->kt && a->counters, &cap);
+  if (rc) return rc;
+  if (e->gram_on) return dia_fail(DIA_E_ARG, "dia_engine_set_calib: the engine already has dia_engine_set_gram, whose diagonals are these statistics");
+  const int n = (int)cap.size();
+  for (int i = 0; i < n; ++i)
+    if (!a->acc[i] || a->kt[i] <= 0 || a->kt[i] > cap[i]) return dia_fail(DIA_E_ARG, "dia_engine_set_calib: a tap without acc, or k-tiles outside (0, k-tiles of its plane set]");
   e->calib_acc.assign(a->acc, a->acc + n);
   e->calib_kt.assign(a->kt, a->kt + n);
   e->calib_counters = a->counters;
   e->calib_on = true;
+  e->wo_defer = 0;            // the in-launch merge: every q/k/v input reaches planes_x
+  return DIA_OK;
+}
+
+extern "C" int dia_engine_set_gram(dia_engine* e, const dia_gram_args* a) {
+  if (!e) return dia_fail(DIA_E_ARG, "dia_engine_set_gram: null engine");
+  if (e->exec || e->launches > 0) return dia_fail(DIA_E_STATE, "dia_engine_set_gram: a step has already been issued or captured");
+  if (!a) { e->gram_on = false; e->gram_ptr.clear(); e->gram_kt.clear(); e->gram_counters = nullptr; return DIA_OK; }
+  std::vector<int> cap;
+  const int rc = tap_preconditions(e, "dia_engine_set_gram", a->n_layer, a->gram && a->kt && a->counters, &cap);
+  if (rc) return rc;
+  if (e->calib_on) return dia_fail(DIA_E_ARG, "dia_engine_set_gram: the engine already has dia_engine_set_calib (the Gram's diagonal is the same statistic)");
+  const int n = (int)cap.size();
+  for (int i = 0; i < n; ++i) {
+    if (a->kt[i] <= 0 || a->kt[i] > cap[i]) return dia_fail(DIA_E_ARG, "dia_engine_set_gram: a tap's k-tiles outside (0, k-tiles of its plane set]");
+    if (reinterpret_cast<uintptr_t>(a->gram[i]) & 15) return dia_fail(DIA_E_ARG, "dia_engine_set_gram: a tap's gram is not 16-byte aligned");
+  }
+  e->gram_ptr.assign(a->gram, a->gram + n);
+  e->gram_kt.assign(a->kt, a->kt + n);
+  e->gram_counters = a->counters;
+  e->gram_on = true;
   e->wo_defer = 0;            // the in-launch merge: every q/k/v input reaches planes_x
   return DIA_OK;
 }

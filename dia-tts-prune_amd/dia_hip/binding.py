@@ -26,6 +26,7 @@ EXPORTS = (
     "dia_engine_decode", "dia_engine_set_prefetch", "dia_engine_set_x_alt", "dia_engine_step_logits_only", "dia_engine_profile_step", "dia_engine_time_step", "dia_timed_kernel_name", "dia_engine_launches_per_step", "dia_mxfp8_classes", "dia_mxfp4_classes", "dia_engine_set_mxfp4",
     "dia_score", "dia_engine_set_score",
     "dia_act_stats", "dia_engine_set_calib",
+    "dia_act_gram", "dia_engine_set_gram",
     "dia_lora_apply", "dia_lora_crosskv", "dia_engine_set_lora",
     "dia_kv_quantize_fp8", "dia_attn_cross_fp8", "dia_engine_set_cross_fp8",
     "dia_attn_self_fp8", "dia_engine_set_self_fp8", "dia_dec_prefill_kv_fp8", "dia_dec_prefill_attn_fp8",
@@ -197,6 +198,17 @@ class ActStatsArgs(C.Structure):
 class CalibArgs(C.Structure):
     """dia_calib_args: acc / kt are HOST arrays of 6 * n_layer + 1 taps (copied), counters a device array"""
     _fields_ = [("n_layer", C.c_int32), ("_pad0", C.c_int32), ("acc", C.POINTER(C.c_void_p)), ("kt", C.POINTER(C.c_int32)),
+                ("counters", C.c_void_p)]
+
+
+class ActGramArgs(C.Structure):
+    """dia_act_gram_args: the fields of dia_act_stats_args, the packed Gram matrix in the place of acc (csrc/gram.hip)"""
+    _fields_ = [(("gram", t) if n == "acc" else (n, t)) for n, t in ActStatsArgs._fields_]
+
+
+class GramArgs(C.Structure):
+    """dia_gram_args: gram / kt are HOST arrays of 6 * n_layer + 1 taps (copied; a NULL gram = no launch), counters a device array"""
+    _fields_ = [("n_layer", C.c_int32), ("_pad0", C.c_int32), ("gram", C.POINTER(C.c_void_p)), ("kt", C.POINTER(C.c_int32)),
                 ("counters", C.c_void_p)]
 
 
@@ -402,6 +414,8 @@ def lib() -> C.CDLL:
     L.dia_engine_set_score.argtypes = [C.c_void_p, C.POINTER(ScoreArgs)]
     L.dia_act_stats.argtypes = [C.POINTER(ActStatsArgs), C.c_void_p]
     L.dia_engine_set_calib.argtypes = [C.c_void_p, C.POINTER(CalibArgs)]
+    L.dia_act_gram.argtypes = [C.POINTER(ActGramArgs), C.c_void_p]
+    L.dia_engine_set_gram.argtypes = [C.c_void_p, C.POINTER(GramArgs)]
     L.dia_lora_apply.argtypes = [C.POINTER(LoraArgs), C.c_void_p]
     L.dia_lora_crosskv.argtypes = [C.POINTER(LoraCrossKvArgs), C.c_void_p]
     L.dia_engine_set_lora.argtypes = [C.c_void_p, C.POINTER(LoraStep)]

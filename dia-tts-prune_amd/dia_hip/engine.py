@@ -528,7 +528,7 @@ class DecodeSession:
                  s_cap: Optional[int] = None, audio_prompts: Optional[Sequence[Optional[np.ndarray]]] = None,
                  prompt_prefill: str = "auto", attention: str = "auto", score: bool = False,
                  adapters=None, adapter_ids: Optional[Sequence[Union[None, str, int]]] = None, cross_kv: str = "bf16",
-                 self_kv: str = "bf16", calibrate: bool = False, _slotted: bool = False):
+                 self_kv: str = "bf16", calibrate: Union[bool, str] = False, gram_layers=None, _slotted: bool = False):
         """audio_prompts: per utterance None or int codes [Tp, C] (reference model.py:311-353).  The prompt
         rows are replayed through the decode step before sampling starts (semantics: oracle.generate), or — with
         bf16 caches — prefilled as one packed MFMA batch; prompt_prefill="replay" forces the replay.
@@ -553,7 +553,16 @@ class DecodeSession:
         sum of squares of its input rows on the device (dia_act_stats; DESIGN.md "Activation statistics"); act_stats() downloads them
         once at the end.  Closed teacher-forced sessions only: slots, adapters=, a compacted checkpoint and seg="on" raise ValueError.
         So do forced rows of unequal lengths or a max_tokens other than their length: teacher forcing acts on no EOS, so the rows behind
-        a shorter utterance would be counted.  Goes together with score=True."""
+        a shorter utterance would be counted.  Goes together with score=True.
+        calibrate="gram": everything calibrate=True does, except that the decode step's taps run dia_act_gram (DESIGN.md "Gram matrices
+        and GPTQ") and accumulate the full Gram matrix of each GEMM input, for the layers of gram_layers (None: every decoder layer and the
+        logits head; else layer indices or a (first, end) tuple, index n_layer standing for the logits head — T (T + 1) / 2 * 8 KiB per tap of
+        T k-tiles).  gram_stats() downloads the matrices; act_stats() keeps working, the diagonals supplying the step's sums (an
+        unselected layer's names then hold no row).  The same refusals."""
+        if calibrate not in (False, True, "gram"):
+            raise ValueError(f"calibrate is False, True or 'gram', not {calibrate!r}")
+        if gram_layers is not None and calibrate != "gram":
+            raise ValueError("gram_layers needs calibrate='gram'")
         if calibrate:
             why = None
             if teacher_tokens is None:
@@ -570,7 +579,7 @@ class DecodeSession:
                 why = ("forced rows of different lengths (or another max_tokens): every step counts the rows of every utterance, and a "
                        "teacher-forced utterance does not end before max_tokens")
             if why is not None:
-                raise ValueError(f"calibrate=True is not served with {why}")
+                raise ValueError(f"calibrate={calibrate!r} is not served with {why}")
         if adapter_ids is not None and adapters is None:
             raise ValueError("adapter_ids needs adapters= (an AdapterBank)")
         if score and (teacher_tokens is None or _slotted):
@@ -783,7 +792,7 @@ class DecodeSession:
         self.scores = torch.full((B, self.T, self.C, 3), float("nan"), dtype=torch.float32, device=dev) if score else None
         self._calib = None
         if calibrate:
-            self._init_calib()
+            self._init_calib(gram=calibrate == "gram", gram_layers=gram_layers)
         self._engine = C.c_void_p()
         self._build_engine()
         self.prefilled = self.slotted            # slots are prefilled one by one, at admission
@@ -825,9 +834,10 @@ class DecodeSession:
         a.adapter_of_slot, a.n_slots, a.n_adapters = hb.ptr(self.adapter_of_slot), self.B, len(self.adapters)
 
     # ------------------------------------------------------------------ activation statistics (DESIGN.md "Activation statistics")
-    def _init_calib(self):
+    def _init_calib(self, gram=False, gram_layers=None):
         """one float64 accumulator per tap (the decode step's 6 * n_layer + 1, then the encoder pass's 4 * n_layer + 1) and one row
-        counter each; a tap's width is the contraction size of the kernels behind it"""
+        counter each; a tap's width is the contraction size of the kernels behind it.  gram: the decode step's taps get a packed Gram
+        matrix instead (the selected ones) and no vector"""
         from . import calib as cal
         from .weights import param_shapes
         shp = param_shapes(self.cfg)
@@ -838,9 +848,14 @@ class DecodeSession:
             if len(Ks) != 1 or next(iter(Ks)) % 32 != 0:
                 raise ValueError(f"calibrate=True: the kernels behind the tap of {names[0]} contract {sorted(Ks)} channels (one size, a multiple of 32)")
             kt.append(next(iter(Ks)) // 32)
-        self._calib = dict(names=taps, kt=kt, n_dec=len(cal.decoder_tap_names(self.cfg)),
-                           acc=[torch.zeros(32 * k, dtype=torch.float64, device=self.dev) for k in kt],
+        n_dec = len(cal.decoder_tap_names(self.cfg))
+        sel = set(cal.gram_layer_taps(self.cfg, gram_layers)) if gram else set()
+        self._calib = dict(names=taps, kt=kt, n_dec=n_dec,
+                           acc=[None if gram and j < n_dec else torch.zeros(32 * k, dtype=torch.float64, device=self.dev) for j, k in enumerate(kt)],
                            counters=torch.zeros(len(taps), dtype=torch.int64, device=self.dev))
+        if gram:
+            self._calib["gram"] = [torch.zeros(cal.gram_tiles(32 * kt[j]) * 1024, dtype=torch.float64, device=self.dev) if j in sel else None
+                                   for j in range(n_dec)]
 
     def _enc_tap(self, st, i, P, kt, row_mask, M, ssq=None, width=0, eps=0.0):
         """dia_act_stats over the encoder pass's plane set P in front of the GEMM of encoder tap i (bf16 planes; ssq: the normed stream)"""
@@ -864,12 +879,31 @@ class DecodeSession:
         c = self._calib
         counts = c["counters"].cpu().numpy()
         out = cal.ActStats.zeros(self.cfg)
+        if "gram" in c:                        # the step's sums are the diagonals of its Gram matrices
+            self._gram_stats(counts).to_act_stats(into=out)
         for j, names in enumerate(c["names"]):
+            if c["acc"][j] is None:
+                continue
             v = c["acc"][j].cpu().numpy()
             for k in names:
                 out.sums[k] = v.copy()
                 out.rows[k] = int(counts[j])
         return out
+
+    def _gram_stats(self, counts):
+        from . import calib as cal
+        c = self._calib
+        keys = cal.gram_tap_keys(self.cfg)
+        sel = [j for j, g in enumerate(c["gram"]) if g is not None]
+        return cal.GramStats({keys[j]: c["gram"][j].cpu().numpy() for j in sel}, {keys[j]: int(counts[j]) for j in sel},
+                             {keys[j]: c["names"][j] for j in sel}, cal._shape_fields(self.cfg))
+
+    def gram_stats(self):
+        """calib.GramStats of everything the selected taps have counted so far (calibrate="gram"); synchronises"""
+        if self._calib is None or "gram" not in self._calib:
+            raise hb.DiaHipError("gram_stats(): the session was not built with calibrate='gram'")
+        self.sync()
+        return self._gram_stats(self._calib["counters"].cpu().numpy())
 
     # ------------------------------------------------------------------ engine descriptor
     def _embed_args(self) -> hb.EmbedArgs:
@@ -971,7 +1005,15 @@ class DecodeSession:
             sc.cfg_scale, sc.eos, sc.pad, sc.bos = sp.cfg_scale, sp.eos, sp.pad, sp.bos
             sc.tokens, sc.cur, sc.first_step, sc.fsm, sc.out = sp.tokens, sp.cur, sp.first_step, sp.fsm, hb.ptr(self.scores)
             hb.check(hb.lib().dia_engine_set_score(self._engine, C.byref(sc)), "dia_engine_set_score")
-        if self._calib is not None:                                         # one dia_act_stats in front of every GEMM of the step
+        if self._calib is not None and "gram" in self._calib:               # one dia_act_gram in front of every GEMM of the selected layers
+            c = self._calib
+            nd = c["n_dec"]
+            gp = (C.c_void_p * nd)(*[hb.ptr(t) for t in c["gram"]])         # (the engine copies both arrays; None = no launch)
+            kts = (C.c_int32 * nd)(*c["kt"][:nd])
+            ga = hb.GramArgs(n_layer=n, gram=C.cast(gp, C.POINTER(C.c_void_p)), kt=C.cast(kts, C.POINTER(C.c_int32)),
+                             counters=c["counters"].data_ptr())
+            hb.check(hb.lib().dia_engine_set_gram(self._engine, C.byref(ga)), "dia_engine_set_gram")
+        elif self._calib is not None:                                       # one dia_act_stats in front of every GEMM of the step
             c = self._calib
             nd = c["n_dec"]
             acc = (C.c_void_p * nd)(*[hb.ptr(t) for t in c["acc"][:nd]])   # (the engine copies both arrays)

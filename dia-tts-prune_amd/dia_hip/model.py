@@ -384,12 +384,16 @@ class Dia:
     @torch.inference_mode()
     def calibrate(self, texts: Sequence[str], codes_list: Sequence, *, audio_prompts: Optional[Sequence] = None,
                   cfg_scale: float = 3.0, audio_prompt_texts: Optional[Sequence[Optional[str]]] = None, use_graph: bool = True,
-                  batch: int = 8, stats: Optional["ActStats"] = None) -> "ActStats":
+                  batch: int = 8, stats: Optional["ActStats"] = None, gram: bool = False, gram_layers=None,
+                  gram_stats: Optional["GramStats"] = None):
         """Activation statistics of the loaded checkpoint over known audio codes (DESIGN.md "Activation statistics"): the texts and
         codes are forced through the model as score_batch forces them (score.teacher_rows), up to ``batch`` (1..8) utterances of equal
         row count per decode session, and every GEMM input's per-channel sum of squares is accumulated on the device.  Returns one ActStats over all of
         them, merged into ``stats`` when given (statistics of earlier calls).  What offline_prune.py --act-stats takes.
-        The checkpoint must be loaded uncompacted, without seg="on"; no adapter takes part."""
+        The checkpoint must be loaded uncompacted, without seg="on"; no adapter takes part.
+        gram=True (DESIGN.md "Gram matrices and GPTQ"): the sessions run with calibrate="gram" and the call returns
+        ``(ActStats, GramStats)``, the Gram matrices of the decode step's GEMM inputs for the layers of ``gram_layers`` (None: all of them
+        and the logits head; see DecodeSession), merged into ``gram_stats`` when given.  What offline_quantize.py --gram-stats takes."""
         from .calib import ActStats
         from .score import check_prompt_rows, teacher_rows
 
@@ -408,7 +412,7 @@ class Dia:
             if r.shape[0] > self.config.data.audio_length:
                 raise ValueError(f"{r.shape[0]} token rows do not fit audio_length {self.config.data.audio_length}")
         ids = [encode_text(effective_text(t, a), self.config) for t, a in zip(texts, apt)]
-        out = stats
+        out, gout = stats, gram_stats
         # a teacher-forced utterance runs to the session's max_tokens: a session takes utterances of one row count, so that no step
         # counts rows behind an utterance's codes
         by_len: Dict[int, List[int]] = {}
@@ -423,16 +427,20 @@ class Dia:
             with torch.cuda.device(self.device):
                 s = DecodeSession(self.model, [ids[i] for i in sel], kv_dtype=self._kv_dtype(), max_tokens=mt, **caches,
                                   cfg_scale=cfg_scale, temperature=0.0, teacher_tokens=[rows[i] for i in sel],
-                                  audio_prompts=[prompts[i] for i in sel], calibrate=True)
+                                  audio_prompts=[prompts[i] for i in sel], calibrate="gram" if gram else True,
+                                  gram_layers=gram_layers if gram else None)
                 try:
                     s.prefill()
                     s.decode(mt - 1, use_graph=use_graph)
                     part = s.act_stats()
+                    gpart = s.gram_stats() if gram else None
                     s._raise_if_invalid()
                 finally:
                     s.close()
             out = part if out is None else out.merge(part)
-        return out
+            if gram:
+                gout = gpart if gout is None else gout.merge(gpart)
+        return (out, gout) if gram else out
 
     @torch.inference_mode()
     def generate_stream(self, requests_or_texts: Sequence[Union[str, GenerationRequest]], slots: int = 8,

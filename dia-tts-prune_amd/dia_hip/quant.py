@@ -147,6 +147,131 @@ def mxfp4_quantize_state_dict(cfg: DiaConfig, sd: Dict[str, torch.Tensor]) -> "O
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
+# GPTQ (Frantar et al. 2022) onto the MX grids (DESIGN.md "Gram matrices and GPTQ"): walk the contraction axis and push every
+# element's rounding error into the weights not rounded yet, weighted by the Hessian of the layer's output error H = X^T X / rows,
+# which calib.GramStats supplies (csrc/gram.hip measures it on the running model).  Offline host code, float64 NumPy.  The grid is
+# the one of the functions above: the block's E8M0 exponent by the same rule, taken from the block as the updates so far have left
+# it, and the element rule restated in float64 (a float64 -> float32 -> e4m3 cast would round twice).  No activation reordering:
+# the MX blocks are fixed runs of 32 K and a permutation would cut across them.
+_MX_FMT = {"mxfp4": (2, E2M1_MAX), "mxfp8": (8, E4M3_MAX)}
+
+
+def _mx_exponent_np(blk, ebias: int):
+    """int [N]: the E8M0 exponent of one block [<= 32, N] (float64), the rule of mxfp8_quantize_2d / mxfp4_quantize_2d"""
+    import numpy as np
+    amax = np.abs(blk).max(axis=0)
+    e = np.frexp(amax)[1].astype(np.int64) - 1 - ebias
+    return np.clip(np.where(amax > 0, e, 0), E_MIN, E_MAX)
+
+
+def _mx_round_row_np(v, e, fmt: str):
+    """float64 [N] -> the nearest element of the format times 2^e: clamp first, then the ties of mxfp4_quantize_2d (the even code) /
+    of the e4m3 cast (nearest even)"""
+    import numpy as np
+    s = np.clip(np.ldexp(v, -e), -_MX_FMT[fmt][1], _MX_FMT[fmt][1])
+    mag = np.abs(s)
+    if fmt == "mxfp4":
+        code = np.zeros(mag.shape, dtype=np.int64)
+        for i, m in enumerate(E2M1_MIDPOINTS):
+            code += (mag > m) if i % 2 == 0 else (mag >= m)
+        q = np.asarray(E2M1_VALUES)[code]
+    else:
+        # e4m3fn: 3 mantissa bits, normals from 2^-6, subnormals in steps of 2^-9; rint is nearest-even on the scaled mantissa
+        p = np.maximum(np.frexp(mag)[1].astype(np.int64) - 1, -6)
+        q = np.ldexp(np.rint(np.ldexp(mag, 3 - p)), p - 3)
+    q = np.copysign(q, s)
+    if fmt == "mxfp4":
+        q = q + 0.0                   # one code per value: no negative zero (the e4m3 cast keeps it)
+    return np.ldexp(q, e)
+
+
+def gptq_factor(gram, rows: int, damp: float = 0.01):
+    """float64 [K, K] upper triangular U with H^-1 = U^T U, for H = gram / rows: a channel with H_kk == 0 decoupled (H_kk = 1, its
+    row and column zero: it was silent in calibration and keeps its plain rounding), damp * mean(diag H) added to the diagonal"""
+    import numpy as np
+    if rows <= 0:
+        raise ValueError("gptq: the Gram matrix counted no row")
+    H = np.array(gram, dtype=np.float64) / float(rows)
+    if H.ndim != 2 or H.shape[0] != H.shape[1]:
+        raise ValueError("gptq: the Gram matrix must be square")
+    d = np.diagonal(H).copy()
+    dead = d == 0
+    H[dead, :] = 0
+    H[:, dead] = 0
+    H[dead, dead] = 1.0
+    mean = float(d.mean())
+    H[np.diag_indices_from(H)] += damp * (mean if mean > 0 else 1.0)
+    return np.ascontiguousarray(np.linalg.cholesky(np.linalg.inv(H)).T)
+
+
+def gptq_apply(w2d: torch.Tensor, U, fmt: str, block: int = 128) -> torch.Tensor:
+    """[K, N] -> fp32 [K, N] on the grid of ``fmt`` by GPTQ with the factor of gptq_factor.  k ascending; at every k % 32 == 0 the
+    block's exponent is fixed from the current block; err = (w_k - q_k) / U_kk goes into the rows behind, eagerly inside a run of
+    ``block`` rows and as one matrix product behind it"""
+    import numpy as np
+    if fmt not in _MX_FMT:
+        raise ValueError(f"gptq: fmt is mxfp4 or mxfp8, not {fmt!r}")
+    if block <= 0 or block % MX_BLOCK:
+        raise ValueError(f"gptq: block must be a positive multiple of {MX_BLOCK}")
+    K, N = w2d.shape
+    if U.shape != (K, K):
+        raise ValueError(f"gptq: the Gram matrix has {U.shape[0]} channels, the kernel contracts {K}")
+    W = w2d.detach().cpu().double().numpy().copy()
+    Q = np.empty_like(W)
+    e = None
+    for i1 in range(0, K, block):
+        i2 = min(i1 + block, K)
+        W1, U1 = W[i1:i2], U[i1:i2, i1:i2]
+        err = np.empty((i2 - i1, N))
+        for i in range(i2 - i1):
+            k = i1 + i
+            if k % MX_BLOCK == 0:
+                e = _mx_exponent_np(W[k: min(k + MX_BLOCK, K)], _MX_FMT[fmt][0])
+            Q[k] = _mx_round_row_np(W1[i], e, fmt)
+            err[i] = (W1[i] - Q[k]) / U1[i, i]
+            if i + 1 < i2 - i1:
+                W1[i + 1:] -= np.outer(U1[i, i + 1:], err[i])
+        if i2 < K:
+            W[i2:] -= U[i1:i2, i2:].T @ err
+    out = torch.from_numpy(Q.astype(np.float32))
+    # the exponent was fixed before the block's rows moved: where a block's largest value has dropped a binade since, the quantiser
+    # reads a smaller exponent from the result, and an e4m3 value of mantissa 1.875 then lands on 480 > 448.  Such a block takes the
+    # nearest representable values (uncompensated), so that dequantise(quantise(out)) == out always holds
+    proj = (mxfp4_round_2d if fmt == "mxfp4" else mxfp8_round_2d)(out)
+    return out if torch.equal(proj, out) else proj
+
+
+def gptq_quantize_2d(w2d: torch.Tensor, gram, rows: int, fmt: str, damp: float = 0.01, block: int = 128) -> torch.Tensor:
+    """[K, N] -> fp32 [K, N]: the MXFP4 / MXFP8-representable matrix GPTQ finds for the Gram matrix ``gram`` (float64 [K, K], the sum of
+    x x^T over ``rows`` calibration rows).  With a diagonal ``gram`` this is mxfp4_round_2d / mxfp8_round_2d."""
+    return gptq_apply(w2d, gptq_factor(gram, rows, damp), fmt, block)
+
+
+def gptq_quantize_state_dict(cfg: DiaConfig, sd: Dict[str, torch.Tensor], gram_stats, fmt: str, damp: float = 0.01,
+                             block: int = 128) -> "OrderedDict[str, torch.Tensor]":
+    """As mxfp4_quantize_state_dict / mxfp8_quantize_state_dict with GPTQ in the place of round-to-nearest: every kernel of
+    ``mx_names(cfg)`` against the Gram matrix of its input (``gram_stats``: a calib.GramStats covering all of them); the kernels of
+    one tap (q/k/v) share one factorisation.  Everything else untouched."""
+    gram_stats.check_against(cfg, mx_names(cfg))
+    out: "OrderedDict[str, torch.Tensor]" = OrderedDict((k, v.clone()) for k, v in sd.items())
+    tap, U = None, None
+    for name in sorted(mx_names(cfg), key=gram_stats.tap_of):
+        if gram_stats.tap_of(name) != tap:
+            tap = gram_stats.tap_of(name)
+            U = gptq_factor(gram_stats.dense(name), gram_stats.rows[tap], damp)
+        w = sd[name]
+        out[name] = gptq_apply(_kernel_2d(name, w.float()), U, fmt, block).reshape(w.shape)
+    return out
+
+
+def calibration_error(gram, delta: torch.Tensor) -> float:
+    """tr(delta^T G delta) = ||X delta||_F^2: the squared output error of a kernel changed by ``delta`` [K, N] on the calibration rows"""
+    import numpy as np
+    d = delta.detach().cpu().double().numpy()
+    return float(np.einsum("kn,kn->", d, np.asarray(gram, dtype=np.float64) @ d))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
 # FP8 cross K/V (DESIGN.md "FP8 cross K/V"): e4m3 elements with ONE scale per key (the 128 values of a head's K or V row), the
 # reference dia_kv_quantize_fp8 (csrc/attn.hip) is pinned to.  The scale is the smallest power of two 2^e with amax / 2^e <= 448
 # (so amax / scale lies in (224, 448] and nothing saturates), e >= KV_E_MIN (the smallest normal fp32), 1 for an all-zero key;

@@ -754,6 +754,62 @@ typedef struct {
  * or whose sampler has per-slot state, compaction or strip maps on any edge, persistent segments, the knobs mlp_fuse and wo_diag,
  * a tap wider than its plane set, and everything dia_act_stats refuses for a tap. */
 int dia_engine_set_calib(dia_engine* e, const dia_calib_args* a);
+
+/* ------------------------------------------------------------------------------------------------
+ * Gram matrices for error-compensated quantisation (csrc/gram.hip; DESIGN.md "Gram matrices and GPTQ").  GPTQ needs, per matrix,
+ * H = X^T X / rows over the calibration rows of the GEMM's input.  One launch, for one activation plane set, read exactly as
+ * dia_act_stats reads it (the same x, planes, row scale rounding by rounding, row rule; rows m >= M are never read):
+ *   v[m][k]  = fl32( x[m][k] * scale[m] )
+ *   G[i][j] += sum over counted rows m, in ascending m, of (double)v[m][i] * (double)v[m][j]       for j's tile <= i's tile
+ * The product of two widened floats is exact in double: one rounding per element and counted row, by a VALU fma (no f64 MFMA).
+ * G is packed as the lower triangle of 32 x 32 tiles, T = ktiles_used (0 = ktiles): tile (ti, tj), tj <= ti, lies at index
+ * ti (ti + 1) / 2 + tj, each tile 1024 doubles row-major, G[32 ti + r][32 tj + c] at r * 32 + c.  Diagonal tiles are stored whole
+ * and are symmetric bit for bit.  gram holds T (T + 1) / 2 * 1024 doubles; nothing outside them, *counter aside, is written.
+ * One thread owns its patch of G and walks the rows in order: no atomics, no cross-thread sums, so G has the same bits however the
+ * rows are spread over launches that keep their order, and under graph replay as eager; its diagonal is dia_act_stats's acc bit for
+ * bit.  A launch that counts no row leaves G untouched (and unread).
+ * DIA_E_ARG with a message, before any HIP call: everything dia_act_stats refuses (gram in the place of acc), a null gram, a gram
+ * that is not 16-byte aligned, and more than 2048 k-tiles (the tile index is decoded in 32-bit arithmetic). */
+typedef struct {
+  const void* x;               /* the fields of dia_act_stats_args, with the same meaning ... */
+  int64_t plane_stride;
+  int32_t ktiles;
+  int32_t ktiles_used;
+  int32_t M;
+  int32_t rows_pad;
+  int32_t act_f32;
+  int32_t ssq_in_n;
+  const float* ssq_in;
+  int32_t ssq_ld;
+  float inv_d;
+  float eps;
+  int32_t rows_per_slot;
+  const uint8_t* row_mask;
+  const int32_t* cur;
+  const int32_t* first_step;
+  const int32_t* fsm;
+  int32_t T;
+  int32_t _pad0;
+  double* gram;                /* ... and the packed matrix: device [T (T + 1) / 2][32][32], read and written */
+  int64_t* counter;            /* device, one per call site */
+} dia_act_gram_args;
+int dia_act_gram(const dia_act_gram_args* a, void* stream);
+
+/* The counterpart of dia_engine_set_calib for Gram matrices: the same taps in the same order (6 * l + m, the logits head last).  At
+ * every tap whose gram[i] is non-NULL the step issues one dia_act_gram where a calibrating engine issues dia_act_stats; a NULL entry
+ * means no launch for that tap, so a caller bounds memory by layer (kt[i] is still read and checked). */
+typedef struct {
+  int32_t n_layer;             /* must equal dia_engine_desc.n_layer */
+  int32_t _pad0;
+  double* const* gram;         /* host array [6 * n_layer + 1] of device arrays or NULL, copied; gram[i] holds kt[i] (kt[i] + 1) / 2 tiles */
+  const int32_t* kt;           /* host array [6 * n_layer + 1]: k-tiles of every tap (the matrix's K / 32), copied */
+  int64_t* counters;           /* device [6 * n_layer + 1] */
+} dia_gram_args;
+/* before the first step (DIA_E_STATE afterwards): one more launch per non-NULL tap, eager and in the captured graph, which
+ * dia_engine_launches_per_step, the prefetch list and the profile walk see; wo's in-launch merge is kept.  NULL = the step without
+ * them, launch for launch.  DIA_E_ARG: everything dia_engine_set_calib refuses, an engine that already has dia_engine_set_calib (the
+ * Gram's diagonal is the same statistic, bit for bit), and everything dia_act_gram refuses for a tap. */
+int dia_engine_set_gram(dia_engine* e, const dia_gram_args* a);
 /* number of kernel launches in one decode step */
 int dia_engine_launches_per_step(const dia_engine* e);
 

@@ -28,11 +28,15 @@ def main(argv=None) -> int:
     p.add_argument("--output-dir", type=str, required=True, help="where pytorch_model.bin and config.json of the quantised model go")
     p.add_argument("--format", type=str, default="mxfp8", choices=["mxfp8", "mxfp4"],
                    help="mxfp8 = e4m3 elements, mxfp4 = e2m1 elements; an E8M0 scale per 32 K of a column")
+    p.add_argument("--gram-stats", type=str, default=None, metavar="FILE.npz",
+                   help="Gram matrices of the decode step's GEMM inputs (cli.py --calibrate-codes ... --gram-output): quantise by GPTQ, pushing "
+                        "every element's rounding error into the weights behind it, instead of rounding to nearest")
+    p.add_argument("--damp", type=float, default=0.01, help="with --gram-stats: the share of the Hessian's mean diagonal added to its diagonal")
     a = p.parse_args(argv)
 
     from dia_hip import weights as W
     from dia_hip.pruning import _kernel_2d
-    from dia_hip.quant import mxfp4_quantize_state_dict, mxfp8_names, mxfp8_quantize_state_dict
+    from dia_hip.quant import calibration_error, gptq_quantize_state_dict, mxfp4_quantize_state_dict, mxfp8_names, mxfp8_quantize_state_dict
 
     out = Path(a.output_dir)
     out.mkdir(parents=True, exist_ok=True)
@@ -49,6 +53,25 @@ def main(argv=None) -> int:
         return 1
     print(f"\nQuantising to {a.format}...")
     qsd = (mxfp4_quantize_state_dict if a.format == "mxfp4" else mxfp8_quantize_state_dict)(cfg, sd)
+    if a.gram_stats:
+        from dia_hip.calib import GramStats
+        try:
+            grams = GramStats.load(a.gram_stats)
+            grams.check_against(cfg)
+        except Exception as e:
+            print(f"Error loading Gram matrices: {e}")
+            return 1
+        rtn = qsd
+        print(f"GPTQ against {a.gram_stats} (damp {a.damp})...")
+        qsd = gptq_quantize_state_dict(cfg, sd, grams, a.format, damp=a.damp)
+        err = {"round-to-nearest": 0.0, "GPTQ": 0.0}
+        for k in mxfp8_names(cfg):                     # sum over the kernels of tr(delta^T G delta), the output error on the calibration rows
+            G, w = grams.dense(k), _kernel_2d(k, sd[k])
+            err["round-to-nearest"] += calibration_error(G, _kernel_2d(k, rtn[k]) - w)
+            err["GPTQ"] += calibration_error(G, _kernel_2d(k, qsd[k]) - w)
+        for kind, v in err.items():
+            print(f"Calibration-set output error, {kind}: {v:.6e}")
+        print(f"GPTQ / round-to-nearest: {err['GPTQ'] / max(err['round-to-nearest'], 1e-300):.4f}")
     num = sum(float((_kernel_2d(k, qsd[k]) - _kernel_2d(k, sd[k])).pow(2).sum()) for k in mxfp8_names(cfg))
     den = sum(float(sd[k].pow(2).sum()) for k in mxfp8_names(cfg))
     print(f"Relative RMS error of the quantised kernels: {(num / max(den, 1e-30)) ** 0.5:.4f}")
