@@ -124,9 +124,11 @@ def build_parser() -> argparse.ArgumentParser:
     g.add_argument("--fp32-weights", type=str, default="exact", choices=["exact", "bf16x2", "round"],
                    help="compute_dtype float32 with a checkpoint bf16 cannot hold: exact = three bf16 planes (generic kernel), "
                         "bf16x2 = hi + lo bf16 planes (relative error <= 2^-17, tuned kernels), round = one rounded bf16 tile set")
-    g.add_argument("--sparse-weights", type=str, default="off", choices=["off", "2:4"],
+    g.add_argument("--sparse-weights", type=str, default="off", choices=["off", "2:4", "unstructured"],
                    help="2:4 = the checkpoint is 2:4-pruned (offline_prune.py --prune-mode 2:4): batch 1-2 decode steps stream its "
-                        "decoder matrices in the compressed 2:4 form (sparse MFMA); off = dense tiles only")
+                        "decoder matrices in the compressed 2:4 form (sparse MFMA); unstructured = the checkpoint is unstructured-pruned "
+                        "(--prune-mode unstructured): it also carries lossless mask + window streams of those matrices, which batch 1-2 "
+                        "steps stream for the classes of the knob usparse (DIA_TUNE=usparse=127: all; default none); off = dense tiles only")
     g.add_argument("--weight-format", type=str, default="bf16", choices=["bf16", "mxfp8", "mxfp4"],
                    help="mxfp8 = the checkpoint is MXFP8-quantised (offline_quantize.py): batch 1-8 decode steps stream its decoder "
                         "matrices as e4m3 elements + block scales (half the weight bytes); mxfp4 = the same for an MXFP4-quantised "

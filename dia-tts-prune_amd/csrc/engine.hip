@@ -30,6 +30,8 @@ struct dia_engine {
   float* x_alt = nullptr;         // dia_engine_set_x_alt: the residual stream of odd layers while wo_defer is in force
   std::vector<dia_mxfp4_layer> f4;      // dia_engine_set_mxfp4: the MXFP4 streams per layer (empty: none) ...
   const void* f4_logits = nullptr;      // ... and of the logits head
+  std::vector<dia_us_layer> us;         // dia_engine_set_usparse: the unstructured sparse streams per layer (empty: none) ...
+  dia_us_mat us_logits = {};            // ... and of the logits head
   bool score_on = false;                // dia_engine_set_score: every step scores the forced row between the logits GEMM and the sampler
   dia_score_args score = {};
   bool calib_on = false;                // dia_engine_set_calib: every step accumulates the activation statistics of each GEMM input in front of the GEMM
@@ -100,6 +102,15 @@ extern "C" int dia_mxfp4_classes(int rows) {
   return (rows <= 4 ? mask : mask >> 8) & ((1 << DIA_MAT_COUNT) - 1);
 }
 
+// Unstructured sparse streams: opt-in by the knob usparse.  No class won a repetition of the in-step A/B (profiles/r21_usparse_speed.txt,
+// scratch/usparse_speed.py: 3-23 % fewer frames/s per class), so none streams by default (DESIGN.md "Unstructured sparse weight stream"); <= 4 rows only (the kernel's range)
+constexpr int USPARSE_DEFAULT = 0;
+extern "C" int dia_usparse_classes(int rows) {
+  if (rows <= 0 || rows > 4) return 0;
+  const int knob = dia_tune(DIA_TUNE_USPARSE);
+  return (knob >= 0 ? knob : USPARSE_DEFAULT) & ((1 << DIA_MAT_COUNT) - 1);
+}
+
 // The step's GEMM launches, one row per dia_step_mat (the row index is also the MXFP8 class bit): where the matrix and its streams live in
 // dia_dec_layer (the logits head: dia_engine_desc, see mat_weights), its epilogue, the planes it reads and emits, what it writes
 enum { PL_NONE = -1, PL_X, PL_A, PL_H };                // activation planes: the normed residual stream, attention output, MLP hidden
@@ -109,11 +120,12 @@ struct step_mat_row {
   const void* dia_dec_layer::*w; int32_t dia_dec_layer::*kt; int32_t dia_dec_layer::*ns;      // dense tiles, kt * ns * 1024 bytes
   const void* dia_dec_layer::*w24; const void* dia_dec_layer::*wf8;                            // 2:4 and MXFP8 streams
   const void* dia_mxfp4_layer::*wf4;                                                           // MXFP4 stream (dia_engine_set_mxfp4)
+  dia_us_mat dia_us_layer::*wus;                                                               // unstructured sparse stream (dia_engine_set_usparse)
   int epi, in, out, emit;
   const int32_t* dia_dec_layer::*cmap;                  // RESID_EMIT: the consumer's compaction map and norm weight (null: the next
   const float* dia_dec_layer::*gnext;                   // layer's g_sa, or the final norm)
 };
-#define MAT(M, m) DIA_MAT_##M, &dia_dec_layer::w_##m, &dia_dec_layer::kt_##m, &dia_dec_layer::ns_##m, &dia_dec_layer::w_##m##_24, &dia_dec_layer::w_##m##_f8, &dia_mxfp4_layer::w_##m
+#define MAT(M, m) DIA_MAT_##M, &dia_dec_layer::w_##m, &dia_dec_layer::kt_##m, &dia_dec_layer::ns_##m, &dia_dec_layer::w_##m##_24, &dia_dec_layer::w_##m##_f8, &dia_mxfp4_layer::w_##m, &dia_us_layer::w_##m
 constexpr step_mat_row STEP_MATS[DIA_MAT_COUNT] = {
   {MAT(QKV, qkv), DIA_EPI_SCALE_STORE, PL_X, OUT_QKV, PL_NONE, nullptr, nullptr},      // q/k/v projection of the pre-SA-normed row (layers.py:541, 273-275)
   {MAT(O, o), DIA_EPI_RESID_EMIT, PL_A, OUT_X, PL_X, &dia_dec_layer::cmap_ca, &dia_dec_layer::g_ca},       // o_proj + residual; emits the pre-CA-normed planes (layers.py:341-343, 555, 560)
@@ -121,19 +133,20 @@ constexpr step_mat_row STEP_MATS[DIA_MAT_COUNT] = {
   {MAT(CO, co), DIA_EPI_RESID_EMIT, PL_A, OUT_X, PL_X, &dia_dec_layer::cmap_mlp, &dia_dec_layer::g_mlp},   // cross o_proj + residual; emits the pre-MLP-normed planes
   {MAT(WI, wi), DIA_EPI_SWIGLU_EMIT, PL_X, OUT_NONE, PL_H, nullptr, nullptr},          // SwiGLU MLP (layers.py:95-104)
   {MAT(WO, wo), DIA_EPI_RESID_EMIT, PL_H, OUT_X, PL_X, &dia_dec_layer::cmap_next, nullptr},
-  {DIA_MAT_LOGITS, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, DIA_EPI_SCALE_STORE, PL_X, OUT_LOGITS, PL_NONE, nullptr, nullptr},   // final norm + logits (layers.py:714-717)
+  {DIA_MAT_LOGITS, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, DIA_EPI_SCALE_STORE, PL_X, OUT_LOGITS, PL_NONE, nullptr, nullptr},   // final norm + logits (layers.py:714-717)
 };
 #undef MAT
 constexpr bool rows_in_order(int m = 0) { return m == DIA_MAT_COUNT || (STEP_MATS[m].mat == m && rows_in_order(m + 1)); }
 static_assert(rows_in_order(), "row m of STEP_MATS describes matrix m of dia_step_mat");
 
-struct mat_w { const void* w; int kt, ns; const void *w24, *wf8, *wf4; };
+struct mat_w { const void* w; int kt, ns; const void *w24, *wf8, *wf4; const dia_us_mat* wus; };
 static mat_w mat_weights(const dia_engine* e, int l, int m) {
   const dia_engine_desc& d = e->d;
-  if (m == DIA_MAT_LOGITS) return {d.w_logits, d.kt_logits, d.ns_logits, d.w_logits_24, d.w_logits_f8, e->f4_logits};
+  if (m == DIA_MAT_LOGITS) return {d.w_logits, d.kt_logits, d.ns_logits, d.w_logits_24, d.w_logits_f8, e->f4_logits, e->us_logits.stream ? &e->us_logits : nullptr};
   const dia_dec_layer& L = e->layers[l];
   const step_mat_row& r = STEP_MATS[m];
-  return {L.*r.w, L.*r.kt, L.*r.ns, L.*r.w24, L.*r.wf8, e->f4.empty() ? nullptr : e->f4[l].*r.wf4};
+  return {L.*r.w, L.*r.kt, L.*r.ns, L.*r.w24, L.*r.wf8, e->f4.empty() ? nullptr : e->f4[l].*r.wf4,
+          (e->us.empty() || !(e->us[l].*r.wus).stream) ? nullptr : &(e->us[l].*r.wus)};
 }
 
 // The launches of one step, in order: launch(layer, what) for every one, `what` a dia_step_mat or one of the launches below.
@@ -274,6 +287,13 @@ static int enqueue_step(dia_engine* e, bool with_sampler) {
     else { g.sk_scratch = d.sk_scratch; g.sk_tickets = d.sk_tickets; }
     return true;
   };
+  // unstructured sparse streams (dia_engine_set_usparse): at <= 4 rows the launch classes of dia_usparse_classes, K split as for the MX
+  // streams.  W is the engine's own copy of the dia_us_mat, which outlives the descriptor
+  const int us_mask = mx_ok ? dia_usparse_classes(R) : 0;
+  auto us = [&](dia_gemm_args& g, const dia_us_mat* m, int cls) {
+    if (!m || g.w_format != DIA_W_DENSE) return false;
+    return mx(g, m, DIA_W_USPARSE, us_mask, cls);
+  };
   bool wo_pair = false;             // of the wo descriptor built last
   // <= 4 rows: wo's two K slices merged by the launch behind it (the next layer's q/k/v projection, the logits head) while it stages
   // its row, instead of wo's ticket hand-off (dia_gemm_wo_deferred) — decided below, once every descriptor can be looked at.
@@ -311,7 +331,7 @@ static int enqueue_step(dia_engine* e, bool with_sampler) {
     }
     sparse24(g, w.w24);
     // a matrix with both streams: the smaller one; what refuses it (class off, no K split that fits) leaves the other its turn
-    if (!mx(g, w.wf4, DIA_W_MXFP4, f4_mask, m)) mx(g, w.wf8, DIA_W_MXFP8, f8_mask, m);
+    if (!us(g, w.wus, m) && !mx(g, w.wf4, DIA_W_MXFP4, f4_mask, m)) mx(g, w.wf8, DIA_W_MXFP8, f8_mask, m);
     if (defer && (m == DIA_MAT_LOGITS || (m == DIA_MAT_QKV && l > 0))) g.gnext = L ? L->g_sa : d.g_final;     // the consumer norms the row itself
     return g;
   };
@@ -325,7 +345,7 @@ static int enqueue_step(dia_engine* e, bool with_sampler) {
     w.xnew = l < d.n_layer ? xbuf(l) : nullptr;   // (nothing reads x behind the logits head: the sampler's embedding overwrites it)
     return w;
   };
-  // every wo and every launch behind one in the shape the deferred kernels serve: dense one-plane tiles (no 2:4 / MXFP8 / MXFP4 stream picked),
+  // every wo and every launch behind one in the shape the deferred kernels serve: dense one-plane tiles (no 2:4 / unstructured sparse / MXFP8 / MXFP4 stream picked),
   // K 8192 in two slices -> a row of D = 2048, no compaction map on the edge; else the whole model keeps the in-launch merge
   if (R <= 4 && F && d.w_planes <= 1 && !seg && !diag && e->wo_defer != 0 && dia_tune(DIA_TUNE_WO_DEFER) != 0 && dia_tune(DIA_TUNE_MLP_FUSE) <= 0 &&
       e->x_alt && d.sk_scratch && d.D == 2048 && (d.sk_scratch_floats > 0 ? d.sk_scratch_floats : (int64_t)(d.D / 16) * 4 * 512) >= 2 * slice_floats) {
@@ -696,6 +716,25 @@ extern "C" int dia_engine_set_mxfp4(dia_engine* e, const dia_mxfp4_streams* s) {
   e->f4.clear();
   if (s) e->f4.assign(s->layers, s->layers + s->n_layer);
   e->f4_logits = s ? s->w_logits : nullptr;
+  return DIA_OK;
+}
+
+extern "C" int dia_engine_set_usparse(dia_engine* e, const dia_us_streams* s) {
+  if (!e) return dia_fail(DIA_E_ARG, "dia_engine_set_usparse: null engine");
+  if (e->exec || e->launches > 0) return dia_fail(DIA_E_STATE, "dia_engine_set_usparse: a step has already been issued or captured");
+  if (s && (s->n_layer != e->d.n_layer || !s->layers)) return dia_fail(DIA_E_ARG, "dia_engine_set_usparse: one dia_us_layer per decoder layer");
+  const auto bad = [](const dia_us_mat& m) { return m.stream && m.rate != 4 && m.rate != 2; };
+  if (s) {
+    bool ok = !bad(s->w_logits);
+    for (int l = 0; l < s->n_layer && ok; ++l) {
+      const dia_us_layer& L = s->layers[l];
+      ok = !bad(L.w_qkv) && !bad(L.w_o) && !bad(L.w_cq) && !bad(L.w_co) && !bad(L.w_wi) && !bad(L.w_wo);
+    }
+    if (!ok) return dia_fail(DIA_E_ARG, "dia_engine_set_usparse: a stream's rate must be 4 or 2");
+  }
+  e->us.clear();
+  if (s) e->us.assign(s->layers, s->layers + s->n_layer);
+  e->us_logits = s ? s->w_logits : dia_us_mat{};
   return DIA_OK;
 }
 

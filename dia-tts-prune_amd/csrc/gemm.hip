@@ -2336,13 +2336,17 @@ static int gemm_impl(const dia_gemm_args* a, const dia_wo_defer_args* wd, void* 
   if (a->M <= 0 || a->KT <= 0 || a->nstrips <= 0) return dia_fail(DIA_E_ARG, "dia_gemm: empty problem");
   if (wd && (a->w_format != DIA_W_DENSE || a->w_layout != 0 || a->w_planes > 1 || a->sp_blocks || a->sp_toff))
     return dia_fail(DIA_E_ARG, "dia_gemm_wo_deferred: dense one-plane weight tiles only");
-  if (a->w_format != DIA_W_DENSE && a->w_format != DIA_W_SPARSE24 && a->w_format != DIA_W_MXFP8 && a->w_format != DIA_W_MXFP4) return dia_fail(DIA_E_ARG, "dia_gemm: unknown w_format");
+  if (a->w_format != DIA_W_DENSE && a->w_format != DIA_W_SPARSE24 && a->w_format != DIA_W_MXFP8 && a->w_format != DIA_W_MXFP4 && a->w_format != DIA_W_USPARSE) return dia_fail(DIA_E_ARG, "dia_gemm: unknown w_format");
   if (a->w_format == DIA_W_SPARSE24) {      // 2:4 sparse weight stream (gemm_sparse.hip)
     const int rc = dia_gemm_sparse24_check(a);
     if (rc != DIA_OK) return rc;
   }
   if (a->w_format == DIA_W_MXFP8 || a->w_format == DIA_W_MXFP4) {      // MX e4m3 / e2m1 weight stream (gemm_mx.hip)
     const int rc = dia_gemm_mx_check(a);
+    if (rc != DIA_OK) return rc;
+  }
+  if (a->w_format == DIA_W_USPARSE) {      // unstructured sparse weight stream (gemm_us.hip)
+    const int rc = dia_gemm_us_check(a);
     if (rc != DIA_OK) return rc;
   }
   if (a->w_planes == 2) {
@@ -2389,6 +2393,7 @@ static int gemm_impl(const dia_gemm_args* a, const dia_wo_defer_args* wd, void* 
 
   if (a->w_format == DIA_W_SPARSE24) return dia_gemm_sparse24(a, stream);
   if (a->w_format == DIA_W_MXFP8 || a->w_format == DIA_W_MXFP4) return dia_gemm_mx(a, stream);
+  if (a->w_format == DIA_W_USPARSE) return dia_gemm_us(a, stream);
   if (a->sp_blocks || a->sp_toff) {       // zero-skipping stream of an unstructured-pruned matrix: kernel-level experiment
 #ifdef DIA_EXPERIMENTS
     return dia_exp_gemm_sparse(a, stream);

@@ -421,3 +421,6 @@ int dia_gemm_sparse24(const dia_gemm_args* a, void* stream);
 // gemm_mx.hip: dia_gemm with w_format == DIA_W_MXFP8 / DIA_W_MXFP4 (MX e4m3 / e2m1 weight stream, M <= 16)
 int dia_gemm_mx_check(const dia_gemm_args* a);
 int dia_gemm_mx(const dia_gemm_args* a, void* stream);
+// gemm_us.hip: dia_gemm with w_format == DIA_W_USPARSE (unstructured sparse weight stream, M <= 4)
+int dia_gemm_us_check(const dia_gemm_args* a);
+int dia_gemm_us(const dia_gemm_args* a, void* stream);

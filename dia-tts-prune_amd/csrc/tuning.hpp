@@ -36,6 +36,8 @@ enum dia_tune_id {
   DIA_TUNE_GEMV_SPEC,          // gemv_spec: 0 = the 1-4-row projections at K = 2048 keep the generic k_gemv_small<8, 8, RS, false, true, true> instead of
                                // the per-epilogue forms k_gemv_small<RS, Form> (csrc/gemm.hip, small_spec_serves; A/B)
                                // otherwise a mask of the forms in use: 1 = those projections, 2 = the deferred-wo consumer, 4 = its producer (gemv_spec_on)
+  DIA_TUNE_USPARSE,            // usparse: which launch classes stream the unstructured sparse streams at <= 4 rows (dia_usparse_classes, dia_engine_set_usparse):
+                               // bit c = matrix c of dia_step_mat; 0 = dense tiles everywhere; unset = the measured default (csrc/engine.hip)
   // ---- EXPERIMENTS=1 builds only
   DIA_TUNE_MLP_FUSE,           // mlp_fuse: 1 = wi + wo as one persistent launch at batch 1 (dia_mlp_fused)
   DIA_TUNE_TILE_V,             // tile_v: prefill tile kernel variant (0..5; 3 = wave-specialised default)

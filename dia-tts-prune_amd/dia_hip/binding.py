@@ -17,13 +17,13 @@ LIB_PATH = os.environ.get("DIA_HIP_LIB") or os.path.join(_HERE, "libdia_hip.so")
 ABI_VERSION = 8
 KV_F32, KV_BF16, KV_BF16X2 = 0, 1, 2
 EPI_SCALE_STORE, EPI_RESID_EMIT, EPI_SWIGLU_EMIT, EPI_CROSSKV = 0, 1, 2, 3
-W_DENSE, W_SPARSE24, W_MXFP8, W_MXFP4 = 0, 1, 2, 4         # dia_gemm_args.w_format (3 is not assigned)
+W_DENSE, W_SPARSE24, W_MXFP8, W_MXFP4, W_USPARSE = 0, 1, 2, 4, 5         # dia_gemm_args.w_format (3 is not assigned)
 ATTN_SELF, ATTN_CROSS, ATTN_ENC = 0, 1, 2
 
 EXPORTS = (
     "dia_last_error", "dia_abi_version", "dia_device_count", "dia_set_tuning", "dia_get_tuning", "dia_has_experiments", "dia_gemm", "dia_gemm_timed", "dia_gemm_wo_deferred", "dia_mlp_fused", "dia_mlp_fused_timed", "dia_engine_mlp_fused", "dia_attn", "dia_attn_scratch_floats", "dia_enc_kv_prep", "dia_enc_attn", "dia_dec_prefill_embed", "dia_dec_prefill_kv", "dia_dec_prefill_attn",
     "dia_embed_text", "dia_embed_tokens", "dia_sample", "dia_slot_admit", "dia_slot_retire", "dia_emit_frames", "dia_prefetch", "dia_engine_create", "dia_engine_destroy",
-    "dia_engine_decode", "dia_engine_set_prefetch", "dia_engine_set_x_alt", "dia_engine_step_logits_only", "dia_engine_profile_step", "dia_engine_time_step", "dia_timed_kernel_name", "dia_engine_launches_per_step", "dia_mxfp8_classes", "dia_mxfp4_classes", "dia_engine_set_mxfp4",
+    "dia_engine_decode", "dia_engine_set_prefetch", "dia_engine_set_x_alt", "dia_engine_step_logits_only", "dia_engine_profile_step", "dia_engine_time_step", "dia_timed_kernel_name", "dia_engine_launches_per_step", "dia_mxfp8_classes", "dia_mxfp4_classes", "dia_engine_set_mxfp4", "dia_usparse_classes", "dia_engine_set_usparse",
     "dia_score", "dia_engine_set_score",
     "dia_act_stats", "dia_engine_set_calib",
     "dia_act_gram", "dia_engine_set_gram",
@@ -68,6 +68,19 @@ class Mxfp4Layer(C.Structure):
 
 class Mxfp4Streams(C.Structure):
     _fields_ = [("n_layer", C.c_int32), ("_pad", C.c_int32), ("layers", C.POINTER(Mxfp4Layer)), ("w_logits", C.c_void_p)]
+
+
+class UsMat(C.Structure):
+    """dia_us_mat: one matrix as an unstructured sparse stream (layout.tile_weight_us); dia_gemm_args.W points to one with W_USPARSE"""
+    _fields_ = [("stream", C.c_void_p), ("rate", C.c_int32), ("_pad", C.c_int32)]
+
+
+class UsLayer(C.Structure):
+    _fields_ = [("w_" + k, UsMat) for k in ("qkv", "o", "cq", "co", "wi", "wo")]
+
+
+class UsStreams(C.Structure):
+    _fields_ = [("n_layer", C.c_int32), ("_pad", C.c_int32), ("layers", C.POINTER(UsLayer)), ("w_logits", UsMat)]
 
 
 class WoDeferArgs(C.Structure):
@@ -410,6 +423,8 @@ def lib() -> C.CDLL:
     L.dia_mxfp8_classes.argtypes = [C.c_int]
     L.dia_mxfp4_classes.argtypes = [C.c_int]
     L.dia_engine_set_mxfp4.argtypes = [C.c_void_p, C.POINTER(Mxfp4Streams)]
+    L.dia_usparse_classes.argtypes = [C.c_int]
+    L.dia_engine_set_usparse.argtypes = [C.c_void_p, C.POINTER(UsStreams)]
     L.dia_score.argtypes = [C.POINTER(ScoreArgs), C.c_void_p]
     L.dia_engine_set_score.argtypes = [C.c_void_p, C.POINTER(ScoreArgs)]
     L.dia_act_stats.argtypes = [C.POINTER(ActStatsArgs), C.c_void_p]
@@ -452,6 +467,11 @@ def mxfp8_mask(rows: int) -> int:
     """launch classes (bit m = matrix m of engine.STEP_MATS) that a decode step of `rows` rows streams as MXFP8 when the model carries
     the streams: the library's measured default, or the knob mxfp8"""
     return int(lib().dia_mxfp8_classes(int(rows)))
+
+
+def usparse_mask(rows: int) -> int:
+    """as mxfp8_mask for the unstructured sparse streams and the knob usparse (0 above 4 rows)"""
+    return int(lib().dia_usparse_classes(int(rows)))
 
 
 def mxfp4_mask(rows: int) -> int:

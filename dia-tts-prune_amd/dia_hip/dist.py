@@ -65,6 +65,9 @@ def broadcast_weights(w, src: int = 0, group=None) -> int:
     if hi[1] != 0:
         raise ValueError("compacted (structured-pruned) weights have checkpoint-dependent shapes: "
                          "load the checkpoint on every rank instead of broadcasting")
+    if getattr(w, "sparse", "off") == "unstructured":
+        raise ValueError("unstructured sparse streams have checkpoint-dependent sizes: load and tile the checkpoint on every rank "
+                         "instead of broadcasting")
     if lo != hi:
         raise ValueError(f"weight arenas differ across ranks (bytes, compacted, weight planes, 2:4 / MXFP8 / MXFP4 streams): min {lo}, max {hi}; "
                          "build the receivers with DeviceWeights.empty_like_config(cfg, device, weight_planes=..., sparse=..., quant=...)")

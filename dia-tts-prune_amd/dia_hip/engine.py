@@ -60,6 +60,24 @@ class TiledW:
         return self.kt // 2 if self.planes == 2 else self.kt
 
 
+@dataclass
+class UsW:
+    """One matrix as an unstructured sparse stream (layout.tile_weight_us): the uint8 stream, its rate, K/32 and N/16"""
+    t: torch.Tensor
+    rate: int
+    kt: int
+    ns: int
+
+    @property
+    def nbytes(self) -> int:
+        return self.t.numel()
+
+
+# a matrix keeps a stream only when it is smaller than this share of its dense tiles (1.0 = smaller at all: the stream reached no
+# break-even at any measured ratio, profiles/r21_usparse_speed.txt)
+US_MAX_RATIO = 1.0
+
+
 def _plane_set(P: torch.Tensor, kt: int):
     """(pointer, plane stride, k-tiles) of an activation plane set [plane][m-tile][kt][64][8]"""
     return hb.ptr(P), P[0].numel(), kt
@@ -150,11 +168,26 @@ class DeviceWeights:
         which form a step used beyond summation order.  Every K must be a multiple of 512; not with sparse="2:4",
         weight_planes != 1, a compacted checkpoint or seg="on".
         "mxfp4" = the same for an MXFP4-representable checkpoint (offline_quantize.py --format mxfp4; quant.is_mxfp4) and MXFP4
-        streams (layout.tile_weight_fp4: e2m1 elements, 0.266 of the dense bytes), under the same conditions."""
+        streams (layout.tile_weight_fp4: e2m1 elements, 0.266 of the dense bytes), under the same conditions.
+        sparse: "unstructured" = an unstructured-pruned checkpoint (offline_prune.py --prune-mode unstructured) also carries the
+        same matrices as lossless lane-local fixed-rate streams (layout.tile_weight_us: an 8-bit mask and a window of 4 or 2 bf16
+        values per lane and k-tile plus an overflow list; the rate is chosen per matrix by the smaller stream), which decode steps
+        of at most 4 rows (batch 1-2) stream for the launch classes the knob usparse enables (binding.usparse_mask).  A matrix
+        whose stream is not smaller than US_MAX_RATIO of its dense tiles carries none (its entry is None) and stays dense.
+        us_bytes / dense_bytes map every matrix name to its stream's bytes (0: none) and its dense tiles' bytes.  Every K must be a
+        multiple of 512; not with weight_planes != 1, seg="on", quant != "off" or a compacted checkpoint.  The stream sizes
+        depend on the data, so such a model is not broadcast (dist.broadcast_weights): every rank loads and tiles the checkpoint."""
         if weight_planes not in _TILERS:
             raise ValueError("weight_planes must be 1, 2 or 3")
-        if sparse not in ("off", "2:4"):
-            raise ValueError('sparse must be "off" or "2:4"')
+        if sparse not in ("off", "2:4", "unstructured"):
+            raise ValueError('sparse must be "off", "2:4" or "unstructured"')
+        if sparse == "unstructured" and weight_planes != 1:
+            raise hb.DiaHipError("sparse='unstructured': the stream holds one bf16 weight plane (weight_planes must be 1)")
+        if sparse == "unstructured" and seg == "on":
+            raise hb.DiaHipError("sparse='unstructured': the persistent MLP segments stream dense ring arenas (seg must be 'off')")
+        if sparse == "unstructured" and quant != "off":
+            raise hb.DiaHipError(f"sparse='unstructured': the unstructured sparse stream and the {quant.upper()} stream exclude each other "
+                                 "(quant must be 'off')")
         if sparse == "2:4" and weight_planes != 1:
             raise hb.DiaHipError("sparse='2:4': the 2:4 stream holds one bf16 weight plane (weight_planes must be 1)")
         if sparse == "2:4" and seg == "on":
@@ -170,6 +203,8 @@ class DeviceWeights:
             raise hb.DiaHipError(f"quant='{quant}': the persistent MLP segments stream dense ring arenas (seg must be 'off')")
         self.sparse = sparse
         self.quant = quant
+        self.us_bytes: Dict[str, int] = {}              # sparse="unstructured": matrix name -> bytes of its stream (0: none) ...
+        self.dense_bytes: Dict[str, int] = {}           # ... and of its dense tiles
         self.weight_planes = weight_planes
         m, e, d = cfg.model, cfg.model.encoder, cfg.model.decoder
         if d.gqa_head_dim != HEAD_DIM or d.cross_head_dim != HEAD_DIM or e.head_dim != HEAD_DIM:
@@ -187,6 +222,7 @@ class DeviceWeights:
         self.logits = self._tile(lw[keep_logits.to(device)] if keep_logits is not None else lw)
         self.logits_cols = lw.shape[1]
         self.logits24 = self._tile24("decoder.logits_dense", lw) if sparse == "2:4" else None
+        self.logits_us = self._tile_us("decoder.logits_dense", lw) if sparse == "unstructured" else None
         self.logits_f8 = self._tile_mx("decoder.logits_dense", lw, quant) if quant == "mxfp8" else None
         self.logits_f4 = self._tile_mx("decoder.logits_dense", lw, quant) if quant == "mxfp4" else None
         npos = max(cfg.data.audio_length, cfg.data.text_length) + 1
@@ -224,6 +260,16 @@ class DeviceWeights:
         if not is_2of4(w2d):
             raise hb.DiaHipError(f"sparse='2:4': {name} is not 2:4 sparse (more than 2 non-zeros in a group of 4 consecutive K)")
         return TiledW(*lay.tile_weight_24(w2d))
+
+    def _tile_us(self, name, w2d) -> Optional["UsW"]:
+        """the unstructured sparse stream of a matrix at the rate that makes it smaller, or None when it is not smaller than
+        US_MAX_RATIO of the dense tiles"""
+        if w2d.shape[0] % 512:
+            raise hb.DiaHipError(f"sparse='unstructured': {name}: K = {w2d.shape[0]} is not a multiple of 512")
+        pick = lay.us_choose(w2d, US_MAX_RATIO)
+        self.dense_bytes[name] = (w2d.shape[0] // 32) * ((w2d.shape[1] + 15) // 16) * 1024
+        self.us_bytes[name] = pick[4] if pick is not None else 0
+        return UsW(pick[0], pick[1], pick[2], pick[3]) if pick is not None else None
 
     @staticmethod
     def _tile_mx(name, w2d, quant) -> TiledW:
@@ -291,6 +337,9 @@ class DeviceWeights:
         if self.sparse == "2:4" and self.compacted:
             raise hb.DiaHipError("sparse='2:4': a compacted (structured-pruned) checkpoint has no 2:4 form; load it with compact='off' "
                                  "or prune with --prune-mode 2:4")
+        if self.sparse == "unstructured" and self.compacted:
+            raise hb.DiaHipError("sparse='unstructured': a compacted (structured-pruned) checkpoint has no unstructured sparse stream; "
+                                 "load it with compact='off'")
         if self.quant != "off" and self.compacted:
             raise hb.DiaHipError(f"quant='{self.quant}': a compacted (structured-pruned) checkpoint has no {self.quant.upper()} stream; "
                                  "load it with compact='off'")
@@ -337,6 +386,7 @@ class DeviceWeights:
             for k in DEC_MATS:
                 L[k] = self._tile(mats[k])
                 L[k + "24"] = self._tile24(p + k, mats[k]) if self.sparse == "2:4" else None
+                L[k + "us"] = self._tile_us(p + k, mats[k]) if self.sparse == "unstructured" else None
                 L[k + "f8"] = self._tile_mx(p + k, mats[k], self.quant) if self.quant == "mxfp8" else None
                 L[k + "f4"] = self._tile_mx(p + k, mats[k], self.quant) if self.quant == "mxfp4" else None
             # experiment (knob wo_diag=1): wo once more in the diagonal layout (4-column groups: 256 workgroups with the whole K each)
@@ -406,6 +456,11 @@ class DeviceWeights:
             for L in self.dec_layers:
                 out += [L[k + "24"].t for k in DEC_MATS]
             out.append(self.logits24.t)
+        if self.sparse == "unstructured":           # the unstructured sparse streams, in the same place (the matrices that have one)
+            for L in self.dec_layers:
+                out += [L[k + "us"].t for k in DEC_MATS if L[k + "us"] is not None]
+            if self.logits_us is not None:
+                out.append(self.logits_us.t)
         if self.quant == "mxfp8":                   # the MXFP8 streams (quant="mxfp8"), after everything the dense model holds
             for L in self.dec_layers:
                 out += [L[k + "f8"].t for k in DEC_MATS]
@@ -441,6 +496,9 @@ class DeviceWeights:
         loads the checkpoint itself instead of receiving a broadcast).  `weight_planes` must be the sender's
         (dist.broadcast_weights checks it on every rank before the arena travels)."""
         from .weights import param_shapes
+        if sparse == "unstructured":
+            raise hb.DiaHipError("sparse='unstructured': the stream sizes depend on the checkpoint, so there is no arena to receive; "
+                                 "load and tile the checkpoint on every rank")
         sd = {k: torch.zeros(shp, dtype=torch.float32, device=device) for k, shp in param_shapes(cfg).items()}
         return cls(cfg, sd, device, compact="off", weight_planes=weight_planes, seg=seg, sparse=sparse, quant=quant)
 
@@ -455,15 +513,21 @@ class DeviceWeights:
         at most 4 rows) and the MXFP8 streams for the matrices of STEP_MATS the library enables at this row count (quant="mxfp8",
         at most 16 rows: binding.mxfp8_mask; quant="mxfp4": the MXFP4 streams, binding.mxfp4_mask)."""
         every = self.sparse == "2:4" and rows <= 4
+        us = hb.usparse_mask(rows) if self.sparse == "unstructured" else 0
         mx = {"mxfp8": hb.mxfp8_mask, "mxfp4": hb.mxfp4_mask}[self.quant](rows) if self.quant != "off" else 0
         sfx = "f4" if self.quant == "mxfp4" else "f8"
         logits_mx = self.logits_f4 if self.quant == "mxfp4" else self.logits_f8
 
         def w(L, k):
+            if us >> STEP_MATS.index(k) & 1 and L[k + "us"] is not None:
+                return L[k + "us"].nbytes
             if mx >> STEP_MATS.index(k) & 1:
                 return L[k + sfx].nbytes
             return L[k + "24"].nbytes if every else L[k].nbytes
-        n = logits_mx.nbytes if mx >> STEP_MATS.index("logits") & 1 else (self.logits24.nbytes if every else self.logits.nbytes)
+        if us >> STEP_MATS.index("logits") & 1 and self.logits_us is not None:
+            n = self.logits_us.nbytes
+        else:
+            n = logits_mx.nbytes if mx >> STEP_MATS.index("logits") & 1 else (self.logits24.nbytes if every else self.logits.nbytes)
         for L in self.dec_layers:
             n += sum(w(L, k) for k in DEC_MATS)
         return n
@@ -999,6 +1063,14 @@ class DecodeSession:
                     setattr(f4_layers[i], "w_" + f, hb.ptr(L[f + "f4"].t))
             f4 = hb.Mxfp4Streams(n_layer=n, layers=C.cast(f4_layers, C.POINTER(hb.Mxfp4Layer)), w_logits=hb.ptr(w.logits_f4.t))
             hb.check(hb.lib().dia_engine_set_mxfp4(self._engine, C.byref(f4)), "dia_engine_set_mxfp4")
+        if w.sparse == "unstructured":                                      # unstructured sparse streams: beside the description
+            us_layers = (hb.UsLayer * n)()                                  # (the engine copies the array)
+            mat = lambda u: hb.UsMat(stream=hb.ptr(u.t), rate=u.rate) if u is not None else hb.UsMat()
+            for i, L in enumerate(w.dec_layers):
+                for f in DEC_MATS:
+                    setattr(us_layers[i], "w_" + f, mat(L[f + "us"]))
+            us = hb.UsStreams(n_layer=n, layers=C.cast(us_layers, C.POINTER(hb.UsLayer)), w_logits=mat(w.logits_us))
+            hb.check(hb.lib().dia_engine_set_usparse(self._engine, C.byref(us)), "dia_engine_set_usparse")
         if self.scores is not None:
             sp, sc = ed.sample, hb.ScoreArgs()
             sc.logits, sc.ld_logits, sc.B, sc.T, sc.C, sc.V = sp.logits, sp.ld_logits, sp.B, sp.T, sp.C, sp.V

@@ -383,6 +383,143 @@ def untile_weight_fp4(stream: torch.Tensor, K: int, N: int) -> torch.Tensor:
     return mxfp4_dequantize_2d(codes.contiguous(), scales.contiguous())[:K, :N].contiguous()
 
 
+# ---- unstructured sparse weight stream (dia_gemm_args.w_format = DIA_W_USPARSE, csrc/gemm_us.hip) ---------------------
+US_GROUP = 16                            # k-tiles (32 K each) behind one mask block
+US_RATES = (4, 2)                        # bf16 slots of a lane's window per k-tile
+
+
+def us_group_bytes(rate: int) -> int:
+    """mask block + value slots of one group: 9 KiB at rate 4, 5 KiB at rate 2 (16 KiB dense)"""
+    return 1024 + rate * 2048
+
+
+def us_stream_bytes(nstrips: int, groups: int, rate: int, n_overflow: int) -> int:
+    """bytes of the stream tile_weight_us returns: fixed part + run table + overflow entries (each padded to 16) + 16"""
+    return (nstrips * groups * us_group_bytes(rate) + _ceil(4 * (nstrips * groups * 16 + 1), 16)
+            + _ceil(4 * n_overflow, 16) + 16)
+
+
+def _us_lane_tiles(w2d: torch.Tensor):
+    """[K, N] -> int16 bf16 bits [ns, G, 16 k-tiles, 64 lanes, 8] in the dense B-operand mapping, K padded to whole groups"""
+    K, N = w2d.shape
+    Np = _ceil(N, 16)
+    kt, ns = _ceil(K, 32) // 32, Np // 16
+    G = (kt + US_GROUP - 1) // US_GROUP
+    wp = torch.zeros(G * US_GROUP * 32, Np, dtype=torch.bfloat16, device=w2d.device)
+    wp[:K, :N] = w2d.to(torch.bfloat16)
+    # (G, i, kq, j, strip, c) -> (strip, G, i, lane = 16 kq + c, j)
+    t = wp.reshape(G, US_GROUP, 4, 8, ns, 16).permute(4, 0, 1, 2, 5, 3).reshape(ns, G, US_GROUP, 64, 8).contiguous()
+    return t, kt, ns, G
+
+
+def tile_weight_us(w2d: torch.Tensor, rate: int) -> Tuple[torch.Tensor, int, int]:
+    """[K, N] float -> (stream uint8 [bytes], K/32, N/16): the bf16 values of an unstructured-pruned matrix as a lane-local
+    fixed-rate stream plus an overflow list, in the order csrc/gemm_us.hip reads.  Lossless for any matrix (a dense one spills
+    everything beyond `rate` per lane and k-tile).  K is zero-padded to a multiple of 32, N to 16, the k-tiles to whole groups
+    of 16 (G = ceil(K/32 / 16)).  "Non-zero" is ``value != 0`` after rounding to bf16: a negative zero is dropped.
+
+    Lane l of k-tile t of a strip owns the dense B-operand elements j = 0..7 = W[32 t + 8 (l >> 4) + j][16 strip + (l & 15)].
+    The stream is three parts back to back:
+
+    1. fixed part ``[ns][G][us_group_bytes(rate)]``.  A group of 16 k-tiles is a 1 KiB mask block ``[64 lanes][16 bytes]``
+       (byte i of lane l = the mask of k-tile i of the group, bit j = element j is non-zero) followed by value slots of 1 KiB
+       ``[64 lanes][16 bytes]``.  A lane's WINDOW of a k-tile is its first `rate` non-zeros in element order as bf16, the rest
+       of the window zero.  rate 4: slot p holds the windows (8 bytes) of k-tiles 2p, 2p + 1 — 8 slots, 9 KiB per group;
+       rate 2: slot p holds the windows (4 bytes) of k-tiles 4p .. 4p + 3 — 4 slots, 5 KiB per group.
+    2. run table, uint32 ``[ns * G * 16 + 1]`` at byte ns * G * us_group_bytes(rate): entry (strip * G + g) * 16 + c is the index
+       of the first overflow entry of column c of group g of the strip; the last entry is the total.  Padded to 16 bytes.
+    3. overflow entries, uint32 each, ordered by (strip, group, column, k): ``k within the group (0..511) | bf16 bits << 16``,
+       the non-zeros of a lane and k-tile beyond its window.  Padded to 16 bytes, then 16 zero bytes.
+
+    us_stream_bytes(ns, G, rate, entries) is the size.  Every read of the kernel (clamped prefetches included) lies inside.
+    The returned K/32 is ceil(K / 32) as for the other tilers, while the stream holds G * 16 k-tiles per strip: dia_gemm takes
+    KT = G * 16 only, i.e. the two agree for K a multiple of 512 and a stream of any other K is for untile_weight_us alone."""
+    if rate not in US_RATES:
+        raise ValueError("tile_weight_us: rate must be 4 or 2")
+    t, kt, ns, G = _us_lane_tiles(w2d)
+    dev = t.device
+    bits = t.view(torch.int16)
+    nz = t != 0                                                         # (-0.0 != 0 is false: dropped)
+    nzi = nz.to(torch.int64)
+    rank = torch.cumsum(nzi, dim=-1) - nzi                              # non-zeros before element j
+    mask = (nzi << torch.arange(8, device=dev)).sum(dim=-1)             # [ns, G, 16, 64]
+    keep, spill = nz & (rank < rate), nz & (rank >= rate)
+    win = torch.zeros(ns, G, US_GROUP, 64, rate + 1, dtype=torch.int16, device=dev)
+    win.scatter_(-1, torch.where(keep, rank, torch.full_like(rank, rate)), torch.where(keep, bits, torch.zeros_like(bits)))
+    slot_kt = 8 // rate                                                 # k-tiles per value slot
+    vals = win[..., :rate].reshape(ns, G, US_GROUP // slot_kt, slot_kt, 64, rate).permute(0, 1, 2, 4, 3, 5)
+    vals = vals.contiguous().view(torch.uint8).reshape(ns, G, -1)
+    masks = mask.permute(0, 1, 3, 2).to(torch.uint8).reshape(ns, G, 1024)
+    fixed = torch.cat([masks, vals], dim=2).reshape(-1)
+    # overflow: (strip, G, i, kq, c, j) -> (strip, G, c, i, kq, j), so that nonzero() walks the runs in (column, k) order
+    sp = spill.reshape(ns, G, US_GROUP, 4, 16, 8).permute(0, 1, 4, 2, 3, 5)
+    sb = bits.reshape(ns, G, US_GROUP, 4, 16, 8).permute(0, 1, 4, 2, 3, 5)
+    idx = torch.nonzero(sp)                                             # [E, 6]
+    kk = 32 * idx[:, 3] + 8 * idx[:, 4] + idx[:, 5]
+    ent = kk | ((sb[sp].to(torch.int64) & 0xFFFF) << 16)
+    cnt = sp.reshape(ns * G * 16, -1).sum(dim=1)
+    table = torch.zeros(ns * G * 16 + 1, dtype=torch.int64, device=dev)
+    table[1:] = torch.cumsum(cnt, 0)
+
+    def u32_bytes(v, pad):
+        b = (v.to(torch.int64)[:, None] >> (8 * torch.arange(4, device=dev))) & 0xFF
+        out = torch.zeros(_ceil(4 * v.numel(), 16) + pad, dtype=torch.uint8, device=dev)
+        out[: 4 * v.numel()] = b.to(torch.uint8).reshape(-1)
+        return out
+    stream = torch.cat([fixed, u32_bytes(table, 0), u32_bytes(ent, 16)]).contiguous()
+    assert stream.numel() == us_stream_bytes(ns, G, rate, int(ent.numel()))
+    return stream, kt, ns
+
+
+def untile_weight_us(stream: torch.Tensor, K: int, N: int, rate: int) -> torch.Tensor:
+    """inverse of tile_weight_us (test helper): fp32 [K, N]"""
+    kt, ns = _ceil(K, 32) // 32, _ceil(N, 16) // 16
+    G = (kt + US_GROUP - 1) // US_GROUP
+    dev = stream.device
+    gb = us_group_bytes(rate)
+    fixed = stream[: ns * G * gb].reshape(ns, G, gb)
+    mask = fixed[:, :, :1024].reshape(ns, G, 64, US_GROUP).permute(0, 1, 3, 2).to(torch.int64)            # [ns, G, 16, 64]
+    slot_kt = 8 // rate
+    win = fixed[:, :, 1024:].contiguous().view(torch.int16).reshape(ns, G, US_GROUP // slot_kt, 64, slot_kt, rate)
+    win = win.permute(0, 1, 2, 4, 3, 5).reshape(ns, G, US_GROUP, 64, rate)
+    nz = (mask[..., None] >> torch.arange(8, device=dev)) & 1
+    rank = torch.cumsum(nz, dim=-1) - nz
+    keep = (nz == 1) & (rank < rate)
+    bits = torch.where(keep, torch.gather(win, -1, rank.clamp(max=rate - 1)), torch.zeros((), dtype=torch.int16, device=dev))
+    nt = ns * G * 16 + 1
+    to = ns * G * gb
+
+    def u32(b):
+        return (b.reshape(-1, 4).to(torch.int64) << (8 * torch.arange(4, device=dev))).sum(dim=1)
+    table = u32(stream[to: to + 4 * nt])
+    eo = to + _ceil(4 * nt, 16)
+    ent = u32(stream[eo: eo + 4 * int(table[-1])])
+    run = torch.repeat_interleave(torch.arange(nt - 1, device=dev), table[1:] - table[:-1])
+    strip, g, c = run // (G * 16), (run // 16) % G, run % 16
+    kk = ent & 0x1FF
+    v = ((ent >> 16) - ((ent >> 31) << 16)).to(torch.int16)
+    bits = bits.contiguous()
+    bits[strip, g, kk >> 5, 16 * ((kk >> 3) & 3) + c, kk & 7] = v
+    return untile_weight(bits.view(torch.bfloat16).reshape(ns, G * US_GROUP, 64, 8), K, N)
+
+
+def us_choose(w2d: torch.Tensor, max_ratio: float = 1.0):
+    """the smaller of the two streams of a matrix, or None when it is not below max_ratio of the dense tiles' bytes:
+    (stream, rate, K/32, N/16, stream bytes, dense bytes).  K/32 and N/16 are tile_weight_us's: ceil(K / 32), NOT padded to the
+    whole groups the stream holds — the kernel takes KT a multiple of 16 only, so K must be a multiple of 512 for a stream that
+    is to be launched (DeviceWeights checks it); the dense bytes count the same unpadded k-tiles"""
+    best = None
+    for rate in US_RATES:
+        s, kt, ns = tile_weight_us(w2d, rate)
+        if best is None or s.numel() < best[0].numel():
+            best = (s, rate, kt, ns)
+    s, rate, kt, ns = best
+    dense = ns * kt * 1024
+    if s.numel() >= max_ratio * dense:
+        return None
+    return s, rate, kt, ns, int(s.numel()), dense
+
+
 # ---- ring layout of the persistent MLP segment (csrc/seg.hip) ------------------------------------------------------
 SEG_CUS = 256            # one workgroup per CU of an MI355X
 SEG_K = 2048             # contraction length of one slot (16 tiles of 128 k x 4 columns)

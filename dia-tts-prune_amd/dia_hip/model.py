@@ -72,6 +72,8 @@ class Dia:
     fp32_weights = "exact"
     # "2:4": a 2:4-pruned checkpoint (offline_prune.py --prune-mode 2:4) also carries its decoder matrices and logits head as 2:4
     # sparse streams, which decode steps of batch 1-2 stream instead of the dense tiles (DeviceWeights sparse="2:4"); "off" = dense
+    # "unstructured": an unstructured-pruned checkpoint also carries those matrices as lossless lane-local fixed-rate streams (DeviceWeights
+    # sparse="unstructured"), streamed at batch 1-2 for the launch classes the knob usparse enables (none by default)
     sparse_weights = "off"
     # "mxfp8": an MXFP8-quantised checkpoint (offline_quantize.py) also carries its decoder matrices and logits head as MXFP8
     # streams, which decode steps of batch 1-8 stream instead of the dense tiles (DeviceWeights quant="mxfp8"); "mxfp4": the same
@@ -140,7 +142,7 @@ class Dia:
             # 2:4 pruning (offline_prune.py --act-stats) zeroes a whole input channel wherever that channel is among the two weakest of
             # its group in every column; to the structure detection such rows look like structured pruning
             self.model = DeviceWeights(self.config, sd, self.device, sparse=self.sparse_weights,
-                                       compact="off" if self.sparse_weights == "2:4" else "auto",
+                                       compact="off" if self.sparse_weights in ("2:4", "unstructured") else "auto",
                                        quant=self.weight_format if self.weight_format in ("mxfp8", "mxfp4") else "off")
             # DenseGeneral kernels are streamed as ONE bf16 tile set by the fast kernels.  A checkpoint whose values are
             # bf16-representable (bf16-trained weights stored as fp32, the synthetic ones) loses nothing.  A genuine fp32

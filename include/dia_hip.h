@@ -47,6 +47,9 @@ extern "C" {
 #define DIA_W_MXFP4 4      /* OCP MX e2m1 stream (dia_hip/layout.py tile_weight_fp4), KT = K/32.  (3 is not assigned: dia_gemm keeps
                             * refusing it as an unknown format, as callers and tests written against the previous header expect) */
 
+#define DIA_W_USPARSE 5    /* lane-local fixed-rate stream of an unstructured-pruned bf16 matrix (dia_hip/layout.py tile_weight_us), KT = K/32;
+                            * W is a HOST pointer to a dia_us_mat (below) */
+
 /* attention modes */
 #define DIA_ATTN_SELF 0   /* decoder self-attention over the growing cache (layers.py:541-555) */
 #define DIA_ATTN_CROSS 1  /* decoder cross-attention over encoder K/V, cond rows (layers.py:560-574) */
@@ -179,11 +182,30 @@ typedef struct {
    * v_mfma_f32_16x16x32_bf16 in registers) and KT = K/32, a multiple of 16 and at most 128 per workgroup (KT / sk).  Same
    * restrictions as DIA_W_SPARSE24; results equal the dense tiles of the same matrix up to summation order.
    * DIA_W_MXFP4: the same with e2m1 elements (dia_hip/layout.py tile_weight_fp4: the scale block followed by 4 KiB of elements, two
-   * per byte); same shapes, restrictions and results as DIA_W_MXFP8. */
+   * per byte); same shapes, restrictions and results as DIA_W_MXFP8.
+   * DIA_W_USPARSE: W points to a dia_us_mat in HOST memory (read during the call only) that names the stream of an unstructured-pruned
+   * matrix and its rate; KT = K/32 as for the MX streams (a multiple of 16, at most 128 per workgroup).  M <= 4 only; otherwise the
+   * restrictions of DIA_W_SPARSE24.  Lossless: results equal the dense tiles of the same matrix up to summation order. */
   int32_t w_format;
   int32_t _pad2;
 } dia_gemm_args;
 int dia_gemm(const dia_gemm_args* a, void* stream);
+/* One matrix as an unstructured sparse stream (dia_gemm_args.w_format = DIA_W_USPARSE; dia_hip/layout.py tile_weight_us(w, rate)).
+ * With ns = nstrips, G = KT / 16 groups of 16 k-tiles and R = rate the device bytes at `stream` are, back to back:
+ *   1. fixed part [ns][G][1024 + 2048 R]: per group a 1 KiB mask block [64 lanes][16 bytes] (byte i of lane l: bit j = element j of
+ *      the lane's dense B-operand fragment of k-tile i, W[32 t + 8 (l >> 4) + j][16 strip + (l & 15)], is non-zero), then value slots
+ *      of 1 KiB [64 lanes][16 bytes]: a lane's window of a k-tile = its first R non-zeros in element order as bf16 (R = 4: slot p
+ *      holds the 8-byte windows of k-tiles 2p, 2p + 1; R = 2: the 4-byte windows of k-tiles 4p .. 4p + 3);
+ *   2. run table uint32 [ns * G * 16 + 1], padded to 16 bytes: entry (strip * G + g) * 16 + c = index of the first overflow entry of
+ *      column c of group g of the strip, the last entry the total;
+ *   3. overflow entries uint32 (k within the group | bf16 bits << 16) ordered by (strip, group, column, k): the non-zeros beyond the
+ *      windows; padded to 16 bytes plus 16 zero bytes.
+ * stream == NULL: the matrix has no stream (the engine keeps its dense tiles). */
+typedef struct {
+  const void* stream;       /* device, 16-byte aligned */
+  int32_t rate;             /* 4 or 2 */
+  int32_t _pad;
+} dia_us_mat;
 /* wo's cross-workgroup split-K merged by the launch that FOLLOWS it instead of inside it (M <= 4, dense one-plane weights, fp32
  * activation tiles, no cmap; anything else returns DIA_E_ARG and the caller keeps the in-launch merge through dia_gemm).  The
  * launch is described by a dia_gemm_args as for dia_gemm, plus:
@@ -685,6 +707,23 @@ typedef struct {
 int dia_engine_set_mxfp4(dia_engine* e, const dia_mxfp4_streams* s);
 /* as dia_mxfp8_classes for the MXFP4 streams and the knob "mxfp4" */
 int dia_mxfp4_classes(int rows);
+/* Unstructured sparse streams of the matrices a decode step streams (dia_gemm_args.w_format = DIA_W_USPARSE, KT = kt_* of
+ * dia_dec_layer / kt_logits), handed to an engine beside its description as the MXFP4 streams are.  stream == NULL = dense only. */
+typedef struct {
+  dia_us_mat w_qkv, w_o, w_cq, w_co, w_wi, w_wo;
+} dia_us_layer;
+typedef struct {
+  int32_t n_layer;                  /* must equal dia_engine_desc.n_layer */
+  int32_t _pad;
+  const dia_us_layer* layers;       /* host array [n_layer], copied */
+  dia_us_mat w_logits;
+} dia_us_streams;
+/* before the first step (DIA_E_STATE afterwards): a step of at most 4 rows then streams the matrices that have a stream here and that
+ * dia_usparse_classes enables, under the conditions of the MX streams; a 2:4 stream of the same matrix goes first, an MX stream
+ * after.  NULL = none.  The streams hold the same numbers as the dense tiles. */
+int dia_engine_set_usparse(dia_engine* e, const dia_us_streams* s);
+/* as dia_mxfp8_classes for the unstructured sparse streams and the knob "usparse": bits 0-6 = matrices of dia_step_mat; 0 above 4 rows */
+int dia_usparse_classes(int rows);
 /* before the first step (DIA_E_STATE afterwards): every step then issues dia_score(a) between its logits GEMM and its sampler, eager
  * and in the captured graph, and dia_engine_launches_per_step reports one more; dia_engine_step_logits_only still ends at the
  * logits.  *a is copied; its pointers must stay valid while the engine steps.  NULL = the step without it, launch for launch.
