@@ -20,11 +20,15 @@ the loaded checkpoint (Dia.score) as one JSON line.
 the two files (dia_hip/spectral.py) as one JSON line, B brought to A's sample rate by the native resampler and the longer cut to the
 shorter.  ``--codec-roundtrip IN.wav --codec-path FILE`` (build-only) prints the same JSON for the native codec's reconstruction
 (encode -> decode, the decoder in ``--codec-precision``) of the file.  Neither needs the text argument.
+``--speed-factor X`` (build-only, with ``--output`` and ``--codec-path``) is the reference application's speed slider on the device
+(dia_hip/timescale.py): ``--speed-mode interp`` (default) is its np.interp, ``wsola`` keeps the pitch and is the mode ``--stream-chunk``
+takes.  ``--time-scale IN.wav --speed-factor X --output OUT.wav`` stretches a file, loads no model and needs no text argument.
 """
 
 from __future__ import annotations
 
 import argparse
+import math
 import os
 import random
 import sys
@@ -118,6 +122,15 @@ def build_parser() -> argparse.ArgumentParser:
     g.add_argument("--codec-roundtrip", type=str, default=None, metavar="IN.wav", help="(build-only) print the same distances between this "
                    "file and its reconstruction by the native codec (encode -> decode, the decoder in --codec-precision) as one JSON "
                    "line, then exit: needs --codec-path with a checkpoint that holds the encoder, loads no model")
+    g = p.add_argument_group("Speed factor")
+    g.add_argument("--speed-factor", type=float, default=None, metavar="X", help="(build-only) stretch the generated waveform on the device, "
+                   "clamped to [0.1, 5], below 1 = slower (the reference application's speed slider): needs --output and --codec-path; "
+                   "runs at the codec's rate, before --output-rate")
+    g.add_argument("--speed-mode", type=str, default=None, choices=["interp", "wsola"], help="(build-only) interp (default) = the reference's "
+                   "np.interp, which moves the pitch with the tempo; wsola = waveform-similarity overlap-add, which keeps the pitch and is "
+                   "the only mode --stream-chunk takes")
+    g.add_argument("--time-scale", type=str, default=None, metavar="IN.wav", help="(build-only) stretch this audio file by --speed-factor in "
+                   "--speed-mode on the device and write it to --output, then exit: loads no model and no codec")
     g = p.add_argument_group("Infrastructure")
     g.add_argument("--device", type=str, default=None, help="HIP device such as cuda:0 (default: the current one)")
     g.add_argument("--compute-dtype", type=str, default="bfloat16", choices=["float16", "bfloat16", "float32"], help="K/V cache dtype: bfloat16 (default; float16 is accepted and mapped to it) or float32.")
@@ -227,11 +240,12 @@ def stream_audio_to_file(dia, args, full_text: str) -> int:
     state = dia.codec.stream()
     rate = dia.output_sample_rate or dia.codec.cfg.sample_rate
     to_rate = dia.codec.resample_stream(dia.codec.cfg.sample_rate, rate)       # equal rates: chunks pass through
+    to_speed = dia.codec.time_scale_stream(dia.speed_factor)                   # speed 1: chunks pass through
     samples, frames = [], []
     for _, start, codes, final in dia.stream_frames([full_text], 1, max_tokens=args.max_tokens, seeds=None if args.seed is None else [args.seed],
                                                     chunk=args.stream_chunk, adapters=used_adapters(args), cfg_scale=args.cfg_scale,
                                                     temperature=args.temperature, top_p=args.top_p, cfg_filter_top_k=args.cfg_filter_top_k):
-        y = to_rate.push(state.push(codes, final), final)
+        y = to_rate.push(to_speed.push(state.push(codes, final), final), final)
         frames.append(codes)
         samples.append(y)
         if args.verbose:
@@ -348,6 +362,25 @@ def compare_to_stdout(args) -> int:
         return 1
 
 
+def time_scale_to_file(args) -> int:
+    """--time-scale: the file through the device's time-scaling kernels at its own rate; no model, no codec"""
+    try:
+        from dia_hip.model import _save_wav_pcm16, read_audio_mono
+        from dia_hip.timescale import DeviceTimescale
+
+        mono, rate = read_audio_mono(args.time_scale)
+        y = DeviceTimescale(torch.device(args.device) if args.device else None).time_scale(
+            np.ascontiguousarray(mono, dtype=np.float32), args.speed_factor, args.speed_mode or "interp")
+        _save_wav_pcm16(args.output, y, rate)
+        print(f"{args.time_scale}: {mono.shape[0]} samples -> {y.shape[0]} at {rate} Hz ({args.speed_mode or 'interp'}), saved to {args.output}")
+        return 0
+    except Exception as e:
+        print(f"Error time-scaling {args.time_scale}: {e}")
+        import traceback
+        traceback.print_exc()
+        return 1
+
+
 def roundtrip_to_stdout(args) -> int:
     """--codec-roundtrip: the file against its reconstruction by the native codec alone"""
     try:
@@ -371,6 +404,25 @@ def roundtrip_to_stdout(args) -> int:
 def main(argv=None) -> int:
     parser = build_parser()
     args = parser.parse_args(argv)
+    if args.speed_factor is not None and not math.isfinite(args.speed_factor):
+        parser.error("--speed-factor X needs a finite number.")
+    if args.speed_mode is not None and args.speed_factor is None:
+        parser.error("--speed-mode needs --speed-factor X.")
+    if args.time_scale:
+        if args.speed_factor is None or not args.output or not args.output.lower().endswith(".wav"):
+            parser.error("--time-scale IN.wav needs --speed-factor X and --output OUT.wav.")
+        if (args.compare_audio or args.codec_roundtrip or args.codes_output or args.score_codes or args.slots or args.stream_chunk
+                or args.audio_prompt or args.encode_audio or args.codec_path or args.codec_precision or args.output_rate is not None):
+            parser.error("--time-scale stretches one file: none of --compare-audio, --codec-roundtrip, --codes-output, --score-codes, "
+                         "--slots, --stream-chunk, --audio-prompt, --encode-audio, --codec-path, --codec-precision or --output-rate.")
+        return time_scale_to_file(args)
+    if args.speed_factor is not None:
+        if not args.output or not args.codec_path or args.score_codes or args.encode_audio or args.compare_audio or args.codec_roundtrip:
+            parser.error("--speed-factor X stretches the generated waveform: it needs --output and --codec-path (the native codec "
+                         "runs the time-scaling).")
+        if args.stream_chunk and (args.speed_mode or "interp") != "wsola":
+            parser.error("--speed-factor with --stream-chunk needs --speed-mode wsola: interp cannot stream (its positions depend "
+                         "on the total length).")
     if args.compare_audio or args.codec_roundtrip:
         if args.compare_audio and args.codec_roundtrip:
             parser.error("--compare-audio and --codec-roundtrip are separate runs.")
@@ -477,6 +529,8 @@ def main(argv=None) -> int:
         if args.codec_path:
             dia.load_codec(args.codec_path, precision=args.codec_precision or "fp32")
             dia.output_sample_rate = args.output_rate
+            if args.speed_factor is not None:
+                dia.speed_factor, dia.speed_mode = args.speed_factor, args.speed_mode or "interp"
             print(f"Native codec loaded from {args.codec_path}" + (f" ({args.codec_precision} decoder)" if args.codec_precision else ""))
         if bank_dirs:
             dia.load_adapters(bank_dirs)

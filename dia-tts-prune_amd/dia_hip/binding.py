@@ -33,6 +33,7 @@ EXPORTS = (
     "dia_codec_embed", "dia_codec_conv", "dia_codec_convt", "dia_codec_convs", "dia_codec_quantize",
     "dia_codec_conv_bf16", "dia_codec_convt_bf16",
     "dia_resample",
+    "dia_timescale",
     "dia_spectral",
     "dia_seg_mlp", "dia_seg_workspace_bytes", "dia_seg_workspace_control_bytes", "dia_seg_slots", "dia_seg_supported", "dia_seg_error",
 )
@@ -295,6 +296,22 @@ class ResampleArgs(C.Structure):
     ]
 
 
+TS_INTERP, TS_WSOLA = 0, 1                                # DIA_TS_INTERP / DIA_TS_WSOLA
+TS_OPEN = -1                                              # DIA_TS_OPEN
+
+
+class TimescaleArgs(C.Structure):
+    """dia_timescale_args: x / y / win / centre / delta are device pointers, the nine per-row arrays HOST arrays read during the call"""
+    _fields_ = [
+        ("x", C.c_void_p), ("y", C.c_void_p), ("win", C.c_void_p), ("centre", C.c_void_p), ("delta", C.c_void_p),
+        ("mode", C.c_int32), ("B", C.c_int32), ("ldx", C.c_int32), ("ldy", C.c_int32), ("ldk", C.c_int32),
+        ("window", C.c_int32), ("tolerance", C.c_int32), ("_pad0", C.c_int32),
+        ("in_start", C.POINTER(C.c_int64)), ("out_start", C.POINTER(C.c_int64)), ("total", C.POINTER(C.c_int64)),
+        ("out_total", C.POINTER(C.c_int64)), ("k0", C.POINTER(C.c_int64)), ("k1", C.POINTER(C.c_int64)),
+        ("delta_prev", C.POINTER(C.c_int32)), ("in_count", C.POINTER(C.c_int32)), ("out_count", C.POINTER(C.c_int32)),
+    ]
+
+
 class SpectralArgs(C.Structure):
     """dia_spectral_args: a / b / basis / fb / fb_range / partial / out are device pointers, len a HOST array read during the call"""
     _fields_ = [
@@ -442,6 +459,7 @@ def lib() -> C.CDLL:
     for fn in (L.dia_dec_prefill_kv_fp8, L.dia_dec_prefill_attn_fp8):
         fn.argtypes = [C.POINTER(DecPrefillArgs), C.POINTER(KvFp8Ptrs), C.c_void_p]
     L.dia_resample.argtypes = [C.POINTER(ResampleArgs), C.c_void_p]
+    L.dia_timescale.argtypes = [C.POINTER(TimescaleArgs), C.c_void_p]
     L.dia_spectral.argtypes = [C.POINTER(SpectralArgs), C.c_void_p]
     L.dia_seg_mlp.argtypes = [C.POINTER(SegArgs), C.c_void_p]
     L.dia_seg_workspace_bytes.restype = C.c_int64

@@ -667,6 +667,7 @@ class DeviceCodec:
         self.enc_layers: Optional[List[dict]] = None
         self.encoder_error: Optional[Exception] = None
         self._resampler = None                                  # resample.DeviceResampler, made on first use
+        self._timescaler = None                                 # timescale.DeviceTimescale, made on first use
         self._spectral = None                                   # spectral.DeviceSpectral, made on first use
         if any(k.startswith("encoder.") for k in whole):
             try:
@@ -947,6 +948,23 @@ class DeviceCodec:
         """a resample.ResampleStream for one signal: push(chunk, final) -> the samples that have become final; joined they equal
         resample() of the whole signal bit for bit"""
         return self._resample().stream(rate_in, rate_out)
+
+    def _timescale(self):
+        if self._timescaler is None:
+            from .timescale import DeviceTimescale
+            self._timescaler = DeviceTimescale(self.device)
+        return self._timescaler
+
+    def time_scale(self, waves, speed: float, mode: str = "interp", window: int = 1024, tolerance: int = 512):
+        """mono float samples [N], or a list of them, stretched to float32 [int(N / speed)] each on this codec's device
+        (csrc/timescale.hip, DESIGN.md "Speed factor"): "interp" is the reference application's speed factor, "wsola" keeps the
+        pitch; speed 1 returns the input"""
+        return self._timescale().time_scale(waves, speed, mode, window, tolerance)
+
+    def time_scale_stream(self, speed: float, window: int = 1024, tolerance: int = 512, mode: str = "wsola"):
+        """a timescale.TimescaleStream for one signal: push(chunk, final) -> the samples that have become final; joined they equal
+        time_scale(mode="wsola") of the whole signal bit for bit.  mode "interp" cannot stream: ValueError"""
+        return self._timescale().stream(speed, window, tolerance, mode)
 
     # -------------------------------------------------------------------------------------- audio distance
     def audio_distance(self, a, b, rate: Optional[int] = None, **kw):

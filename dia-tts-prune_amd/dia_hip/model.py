@@ -96,6 +96,12 @@ class Dia:
     # HZ: generate(), generate_audio_batch() and stream_audio() return their samples at this rate, converted from the codec's
     # 44.1 kHz by the native codec's resampler (DeviceCodec.resample / resample_stream); None = the codec's rate, as it comes
     output_sample_rate: Optional[int] = None
+    # the reference application's speed factor (clamped to [0.1, 5], below 1 = slower): generate(), generate_audio_batch() and
+    # stream_audio() stretch their waveform by it on the device, at the codec's rate and before output_sample_rate's conversion
+    # (DeviceCodec.time_scale / time_scale_stream; DESIGN.md "Speed factor").  speed_mode "interp" is the reference's np.interp
+    # (the pitch moves with the tempo; cannot stream), "wsola" keeps the pitch.  1.0 = every call launches what it did without it
+    speed_factor: float = 1.0
+    speed_mode: str = "interp"
     # the native codec's DECODER precision that codec_path= on the loaders asks load_codec() for: "fp32" (the exact kernel), "bf16x2"
     # or "bf16" (bf16 MFMA operands in two planes / one; DESIGN.md "Codec: bf16 modes").  The encode side is fp32 in every mode.
     # load_codec() sets it, on the instance, to the mode it loaded
@@ -538,9 +544,35 @@ class Dia:
         """generate_batch (same arguments), then the native codec over all utterances at once: one float32 waveform
         [T'_b * 512] per utterance, each as when decoded alone.  Needs load_codec()."""
         codec = self._need_codec()
-        waves = codec.decode_batch(self.generate_batch(texts, *args, **kw))
+        speed = self._speed(codec)
         rate = self._output_rate(codec)
+        waves = codec.decode_batch(self.generate_batch(texts, *args, **kw))
+        if speed is not None:
+            waves = codec.time_scale(waves, speed, self.speed_mode)
         return codec.resample(waves, codec.cfg.sample_rate, rate) if rate else waves
+
+    def _speed(self, codec) -> Optional[float]:
+        """speed_factor, clamped, where it asks for a time-scaling, else None; the time-scaling is the native codec's"""
+        from .timescale import MODES, clamp_speed
+        if isinstance(self.speed_factor, bool) or not isinstance(self.speed_factor, (int, float)):
+            raise ValueError(f"speed_factor = {self.speed_factor!r} is not a number")
+        if self.speed_mode not in MODES:
+            raise ValueError(f"speed_mode = {self.speed_mode!r} is not one of {MODES}")
+        speed = clamp_speed(self.speed_factor)
+        if speed == 1.0:
+            return None
+        if codec is None or not hasattr(codec, "time_scale"):
+            raise RuntimeError(f"speed_factor = {self.speed_factor} needs the native codec's time-scaling: call Dia.load_codec(path_or_state) first")
+        return speed
+
+    def time_scale(self, wave, speed: float, mode: Optional[str] = None, window: int = 1024, tolerance: int = 512):
+        """mono float samples [N] (or a list of them) stretched to float32 [int(N / speed)] on this instance's device
+        (dia_hip/timescale.py, csrc/timescale.hip): mode "interp" (default: speed_mode) is the reference application's speed factor,
+        "wsola" keeps the pitch.  Needs no codec and no weights."""
+        if getattr(self, "_timescale", None) is None:
+            from .timescale import DeviceTimescale
+            self._timescale = DeviceTimescale(self.device)
+        return self._timescale.time_scale(wave, speed, self.speed_mode if mode is None else mode, window, tolerance)
 
     def _output_rate(self, codec) -> Optional[int]:
         """output_sample_rate where it asks for another rate than the codec's, else None; the conversion is the native codec's"""
@@ -553,23 +585,35 @@ class Dia:
             raise RuntimeError(f"output_sample_rate = {rate} Hz needs the native codec's resampler: call Dia.load_codec(path_or_state) first")
         return int(rate)
 
-    @torch.inference_mode()
     def stream_audio(self, requests_or_texts: Sequence[Union[str, GenerationRequest]], slots: int = 8, **kw):
         """stream_frames (same arguments) with the native codec behind it: yields (request index, start sample, samples, final)
         while the utterances run.  The samples of a request, joined, equal codec.decode() of its whole code tensor; the last
         context_frames frames of a running utterance are held back until more arrive or it ends (DESIGN.md "Codec").  Needs
-        load_codec().  With output_sample_rate set the samples are at that rate and equal codec.resample() of the whole waveform."""
+        load_codec().  With output_sample_rate set the samples are at that rate and equal codec.resample() of the whole waveform.
+        With speed_factor other than 1 they are time-scaled first, per request by a WSOLA stream, and joined equal
+        codec.time_scale(..., "wsola") of the whole waveform; speed_mode "interp" cannot stream and is refused here, before
+        anything runs."""
+        if self.codec is not None and self._speed(self.codec) is not None and self.speed_mode == "interp":
+            raise ValueError("stream_audio: speed_mode 'interp' cannot stream (its positions depend on the utterance's total length); "
+                             "set speed_mode = 'wsola'")
+        return self._stream_audio(requests_or_texts, slots, **kw)
+
+    @torch.inference_mode()
+    def _stream_audio(self, requests_or_texts, slots, **kw):
         codec = self._need_codec()
         rate = self._output_rate(codec)
+        speed = self._speed(codec)
         states, starts = {}, {}
         for i, _, codes, final in self.stream_frames(requests_or_texts, slots, **kw):
             st = states.get(i)
             if st is None:
-                st = states[i] = (codec.stream(), codec.resample_stream(codec.cfg.sample_rate, rate) if rate else None)
+                st = states[i] = (codec.stream(), codec.time_scale_stream(speed) if speed is not None else None,
+                                  codec.resample_stream(codec.cfg.sample_rate, rate) if rate else None)
                 starts[i] = 0
             y = st[0].push(codes, final)
-            if st[1] is not None:                               # one resampling state per request: start offsets count output-rate samples
-                y = st[1].push(y, final)
+            for nxt in st[1:]:                                  # one time-scaling and one resampling state per request: start
+                if nxt is not None:                             # offsets count delivered samples
+                    y = nxt.push(y, final)
             yield i, starts[i], y, final
             starts[i] += y.shape[0]
             if final:
@@ -656,8 +700,11 @@ class Dia:
         """codes [1, C, T'] -> waveform: through the native codec when load_codec() set one (at output_sample_rate when that is
         set), else through the third-party codec (model.py:535-544)."""
         rate = self._output_rate(self.codec)
+        speed = self._speed(self.codec)
         if self.codec is not None:
             wave = self.codec.decode(codec_input)
+            if speed is not None:
+                wave = self.codec.time_scale(wave, speed, self.speed_mode)
             return self.codec.resample(wave, self.codec.cfg.sample_rate, rate) if rate else wave
         if self.dac_model is None:
             raise RuntimeError("DAC model not loaded. Cannot decode audio.")

@@ -1220,6 +1220,67 @@ typedef struct {
 } dia_spectral_args;
 int dia_spectral(const dia_spectral_args* a, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Speed factor (csrc/timescale.hip; DESIGN.md "Speed factor"): time-scaling of a batch of rows, by linear interpolation (the
+ * reference application's np.interp over np.linspace, which moves the pitch) or by WSOLA (waveform-similarity overlap-add, which
+ * keeps it).  One new entry point and one new struct; nothing older changed.
+ *
+ * A row is a WINDOW of a longer signal x of `total` samples, as in dia_resample_args: it holds input samples
+ * [in_start, in_start + in_count) at x[b][0 ..] and receives outputs [out_start, out_start + out_count) at y[b][0 ..].  x reads as
+ * ZERO outside [0, total) and outside the window (the caller sees to it that nothing inside the signal that the row needs lies
+ * outside the window: dia_hip/timescale.py checks before it launches); memory outside x[b][0 .. in_count) is never read, memory
+ * outside y[b][0 .. out_count) and delta[b][0 .. k1 - k0) never written.
+ *
+ * DIA_TS_INTERP: the signal has N = total[b] samples and M = out_total[b] outputs.  Output j (absolute) is
+ *   pos = j == M - 1 ? N - 1 : (double)(j * (N - 1)) / (M - 1)        (0 when M == 1)
+ *   i   = min(floor(pos), N - 2),    y[j] = (float)(((double)x[i + 1] - x[i]) * (pos - i) + x[i])        (x[0] when N == 1)
+ * total must be a length (not open); window, tolerance, win, centre, delta, k0, k1, delta_prev and ldk are not read.
+ *
+ * DIA_TS_WSOLA: W = window, D = tolerance, Hs = W / 2; frame k is centred at output k * Hs and nominally at input c_k.  The row
+ * searches frames [k0, k1): centre[b][i] holds c_{k0 - 1 + i} - in_start for i = 0 .. k1 - k0 (entry 0 is not read when k0 == 0),
+ * delta_prev[b] is delta of frame k0 - 1.  With p_k = c_k + delta_k - Hs:
+ *   delta_0 = 0;  for k >= 1  delta_k = arg max over d in [-D, D] of corr(d) = sum_{n < W} x[p_{k-1} + Hs + n] * x[c_k + d - Hs + n]
+ * every corr(d) ONE fp32 fma chain from 0 in ascending n, so its bits depend on the samples alone; among equal maxima the smallest
+ * |d| wins, then the negative one; a NaN never wins (all NaN: 0).  delta[b][i] receives delta_{k0 + i}.  Then output m, which must
+ * lie in [(k0 - 1) * Hs, (k1 - 1) * Hs), has the two frames ka = m / Hs and ka + 1:
+ *   nb = m - ka * Hs, na = nb + Hs,   y[m] = fmaf(win[nb], x[p_{ka + 1} + nb], win[na] * x[p_ka + na])
+ * The search of a row is sequential in k: one workgroup per row.  total[b] may be DIA_TS_OPEN; out_total is not read.
+ *
+ * Refused with DIA_E_ARG before any HIP call: a null args / x / y or a null host array; a mode other than the two; B outside
+ * [1, 64]; ldx or ldy outside [1, 1 << 24]; in_count outside [0, ldx]; out_count outside [0, ldy]; negative in_start / out_start;
+ * a total that is neither a length nor DIA_TS_OPEN.  INTERP: an open total, out_total < 1, outputs beyond out_total.  WSOLA:
+ * null win / centre / delta; window not a power of two in [64, 4096]; tolerance outside [0, window]; ldk < 1; k0 < 0; k1 < k0;
+ * k1 - k0 > ldk; outputs outside the frames' range.
+ * ------------------------------------------------------------------------------------------------ */
+#define DIA_TS_INTERP 0
+#define DIA_TS_WSOLA 1
+#define DIA_TS_MAX_ROWS 64                 /* rows of one launch */
+#define DIA_TS_MAX_T (1 << 24)             /* ldx, ldy */
+#define DIA_TS_MIN_WINDOW 64
+#define DIA_TS_MAX_WINDOW 4096
+#define DIA_TS_OPEN (-1)                   /* total[b] of a running stream: the signal has no end yet */
+typedef struct {
+  const float* x;              /* device [B][ldx] */
+  float* y;                    /* device [B][ldy]; never x */
+  const float* win;            /* device [window]: the periodic Hann window 0.5 - 0.5 cos(2 pi n / window), rounded once from float64 */
+  const int32_t* centre;       /* device [B][ldk + 1]: c_k - in_start of frames k0 - 1 .. k1 */
+  int32_t* delta;              /* device [B][ldk]: receives delta of frames k0 .. k1 - 1 */
+  int32_t mode;                /* DIA_TS_INTERP / DIA_TS_WSOLA */
+  int32_t B, ldx, ldy, ldk;
+  int32_t window, tolerance;
+  int32_t _pad0;
+  const int64_t* in_start;     /* HOST [B], read during the call (as all below): absolute index of x[b][0], >= 0 */
+  const int64_t* out_start;    /* HOST [B]: absolute index of y[b][0], >= 0 */
+  const int64_t* total;        /* HOST [B]: the signal's length N, or DIA_TS_OPEN */
+  const int64_t* out_total;    /* HOST [B]: INTERP: the number of outputs M of the whole signal */
+  const int64_t* k0;           /* HOST [B]: WSOLA: the first frame to search */
+  const int64_t* k1;           /* HOST [B]: WSOLA: one past the last */
+  const int32_t* delta_prev;   /* HOST [B]: WSOLA: delta of frame k0 - 1 (not read when k0 == 0) */
+  const int32_t* in_count;     /* HOST [B]: 0 .. ldx */
+  const int32_t* out_count;    /* HOST [B]: 0 .. ldy */
+} dia_timescale_args;
+int dia_timescale(const dia_timescale_args* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
