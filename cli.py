@@ -23,6 +23,9 @@ shorter.  ``--codec-roundtrip IN.wav --codec-path FILE`` (build-only) prints the
 ``--speed-factor X`` (build-only, with ``--output`` and ``--codec-path``) is the reference application's speed slider on the device
 (dia_hip/timescale.py): ``--speed-mode interp`` (default) is its np.interp, ``wsola`` keeps the pitch and is the mode ``--stream-chunk``
 takes.  ``--time-scale IN.wav --speed-factor X --output OUT.wav`` stretches a file, loads no model and needs no text argument.
+``--loudness LUFS [--peak-ceiling DBTP]`` (build-only, with ``--output`` and ``--codec-path``; not with ``--stream-chunk``) brings the
+generated waveform to an ITU-R BS.1770-4 integrated loudness under a true-peak ceiling by one gain on the device (dia_hip/loudness.py),
+as the last step.  ``--measure-loudness IN.wav`` prints a file's loudness and peaks as one JSON line; it loads no model either.
 """
 
 from __future__ import annotations
@@ -131,6 +134,16 @@ def build_parser() -> argparse.ArgumentParser:
                    "the only mode --stream-chunk takes")
     g.add_argument("--time-scale", type=str, default=None, metavar="IN.wav", help="(build-only) stretch this audio file by --speed-factor in "
                    "--speed-mode on the device and write it to --output, then exit: loads no model and no codec")
+    g = p.add_argument_group("Loudness")
+    g.add_argument("--loudness", type=float, default=None, metavar="LUFS", help="(build-only) bring the generated waveform to this integrated "
+                   "loudness (ITU-R BS.1770-4) by one gain on the device, lowered where the true peak would cross --peak-ceiling (a pure "
+                   "gain, not a limiter): needs --output and --codec-path; runs last, after --speed-factor and --output-rate; not with "
+                   "--stream-chunk (the gain depends on the whole utterance)")
+    g.add_argument("--peak-ceiling", type=float, default=None, metavar="DBTP", help="(build-only) true-peak ceiling of --loudness in dBTP "
+                   "(default -1)")
+    g.add_argument("--measure-loudness", type=str, default=None, metavar="IN.wav", help="(build-only) print the integrated loudness (LUFS), "
+                   "the true peak (dBTP) and the sample peak (dBFS) of this audio file as one JSON line, then exit: loads no model and "
+                   "no codec")
     g = p.add_argument_group("Infrastructure")
     g.add_argument("--device", type=str, default=None, help="HIP device such as cuda:0 (default: the current one)")
     g.add_argument("--compute-dtype", type=str, default="bfloat16", choices=["float16", "bfloat16", "float32"], help="K/V cache dtype: bfloat16 (default; float16 is accepted and mapped to it) or float32.")
@@ -362,6 +375,26 @@ def compare_to_stdout(args) -> int:
         return 1
 
 
+def loudness_to_stdout(args) -> int:
+    """--measure-loudness: the file through the device's loudness meter at its own rate; no model, no codec"""
+    try:
+        import json
+
+        from dia_hip.loudness import DeviceLoudness
+        from dia_hip.model import read_audio_mono
+
+        mono, rate = read_audio_mono(args.measure_loudness)
+        r = DeviceLoudness(torch.device(args.device) if args.device else None).measure(np.ascontiguousarray(mono, dtype=np.float32), rate)
+        print(json.dumps({"loudness_lufs": r["loudness"], "true_peak_dbtp": r["true_peak"], "sample_peak_dbfs": r["sample_peak"],
+                          "sample_rate": int(rate), "samples": int(mono.shape[0])}))
+        return 0
+    except Exception as e:
+        print(f"Error measuring {args.measure_loudness}: {e}")
+        import traceback
+        traceback.print_exc()
+        return 1
+
+
 def time_scale_to_file(args) -> int:
     """--time-scale: the file through the device's time-scaling kernels at its own rate; no model, no codec"""
     try:
@@ -408,6 +441,25 @@ def main(argv=None) -> int:
         parser.error("--speed-factor X needs a finite number.")
     if args.speed_mode is not None and args.speed_factor is None:
         parser.error("--speed-mode needs --speed-factor X.")
+    if args.peak_ceiling is not None and args.loudness is None:
+        parser.error("--peak-ceiling needs --loudness LUFS.")
+    if args.measure_loudness:
+        if (args.loudness is not None or args.time_scale or args.speed_factor is not None or args.output or args.compare_audio
+                or args.codec_roundtrip or args.codes_output or args.score_codes or args.slots or args.stream_chunk or args.audio_prompt
+                or args.encode_audio or args.codec_path or args.codec_precision or args.output_rate is not None):
+            parser.error("--measure-loudness measures one file: none of --loudness, --time-scale, --speed-factor, --output, "
+                         "--compare-audio, --codec-roundtrip, --codes-output, --score-codes, --slots, --stream-chunk, --audio-prompt, "
+                         "--encode-audio, --codec-path, --codec-precision or --output-rate.")
+        return loudness_to_stdout(args)
+    if args.loudness is not None:
+        if not math.isfinite(args.loudness) or (args.peak_ceiling is not None and not math.isfinite(args.peak_ceiling)):
+            parser.error("--loudness LUFS and --peak-ceiling DBTP need finite numbers.")
+        if (not args.output or not args.codec_path or args.time_scale or args.score_codes or args.encode_audio or args.compare_audio
+                or args.codec_roundtrip):
+            parser.error("--loudness LUFS normalises the generated waveform: it needs --output and --codec-path (the native codec "
+                         "runs the meter).")
+        if args.stream_chunk:
+            parser.error("--loudness cannot be combined with --stream-chunk: the gain depends on the whole utterance.")
     if args.time_scale:
         if args.speed_factor is None or not args.output or not args.output.lower().endswith(".wav"):
             parser.error("--time-scale IN.wav needs --speed-factor X and --output OUT.wav.")
@@ -531,6 +583,9 @@ def main(argv=None) -> int:
             dia.output_sample_rate = args.output_rate
             if args.speed_factor is not None:
                 dia.speed_factor, dia.speed_mode = args.speed_factor, args.speed_mode or "interp"
+            if args.loudness is not None:
+                dia.loudness_target = args.loudness
+                dia.peak_ceiling = -1.0 if args.peak_ceiling is None else args.peak_ceiling
             print(f"Native codec loaded from {args.codec_path}" + (f" ({args.codec_precision} decoder)" if args.codec_precision else ""))
         if bank_dirs:
             dia.load_adapters(bank_dirs)

@@ -34,6 +34,7 @@ EXPORTS = (
     "dia_codec_conv_bf16", "dia_codec_convt_bf16",
     "dia_resample",
     "dia_timescale",
+    "dia_loudness",
     "dia_spectral",
     "dia_seg_mlp", "dia_seg_workspace_bytes", "dia_seg_workspace_control_bytes", "dia_seg_slots", "dia_seg_supported", "dia_seg_error",
 )
@@ -312,6 +313,22 @@ class TimescaleArgs(C.Structure):
     ]
 
 
+LOUD_MEASURE, LOUD_APPLY = 0, 1                           # DIA_LOUD_MEASURE / DIA_LOUD_APPLY
+
+
+class LoudnessArgs(C.Structure):
+    """dia_loudness_args: x / y / steps / peaks / ws / table / bank are device pointers, the five arrays at the end HOST arrays read
+    during the call"""
+    _fields_ = [
+        ("x", C.c_void_p), ("y", C.c_void_p), ("steps", C.c_void_p), ("peaks", C.c_void_p), ("ws", C.c_void_p), ("table", C.c_void_p),
+        ("bank", C.c_void_p), ("ws_doubles", C.c_int64),
+        ("mode", C.c_int32), ("B", C.c_int32), ("ldx", C.c_int32), ("ldy", C.c_int32), ("ld_steps", C.c_int32),
+        ("step", C.c_int32), ("chunk", C.c_int32), ("chunks", C.c_int32), ("nt", C.c_int32), ("_pad0", C.c_int32),
+        ("first", C.POINTER(C.c_int32)), ("len", C.POINTER(C.c_int32)), ("in_off", C.POINTER(C.c_int32)),
+        ("out_count", C.POINTER(C.c_int32)), ("gain", C.POINTER(C.c_double)),
+    ]
+
+
 class SpectralArgs(C.Structure):
     """dia_spectral_args: a / b / basis / fb / fb_range / partial / out are device pointers, len a HOST array read during the call"""
     _fields_ = [
@@ -460,6 +477,7 @@ def lib() -> C.CDLL:
         fn.argtypes = [C.POINTER(DecPrefillArgs), C.POINTER(KvFp8Ptrs), C.c_void_p]
     L.dia_resample.argtypes = [C.POINTER(ResampleArgs), C.c_void_p]
     L.dia_timescale.argtypes = [C.POINTER(TimescaleArgs), C.c_void_p]
+    L.dia_loudness.argtypes = [C.POINTER(LoudnessArgs), C.c_void_p]
     L.dia_spectral.argtypes = [C.POINTER(SpectralArgs), C.c_void_p]
     L.dia_seg_mlp.argtypes = [C.POINTER(SegArgs), C.c_void_p]
     L.dia_seg_workspace_bytes.restype = C.c_int64

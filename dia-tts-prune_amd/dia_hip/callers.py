@@ -146,11 +146,19 @@ def stream_chunks_codes(dia, text: str, *, slots: int = 8, chunk: int = 16, chun
 
 
 def generate_long(dia, text: str, **kw) -> Optional[np.ndarray]:
-    """as the front-end: decode every batch, join with 0.2 s of silence (app.py:238-250).  Needs the codec."""
+    """as the front-end: decode every batch, join with 0.2 s of silence (app.py:238-250).  Needs the codec.  With
+    dia.loudness_target set the JOINED waveform is normalised, once: one gain for the whole text, the silence included."""
     segs: List[np.ndarray] = []
+    target = dia._loudness(dia.codec) if getattr(dia, "loudness_target", None) is not None else None
     parts = generate_long_codes(dia, text, **kw)
     for i, codes in enumerate(parts):
-        segs.append(dia._generate_output(codes))
+        segs.append(dia._generate_output(codes) if target is None else dia._generate_output(codes, normalize=False))
         if i + 1 < len(parts):
             segs.append(np.zeros(int(DEFAULT_SAMPLE_RATE * 0.2), dtype=np.float32))
-    return np.concatenate(segs) if segs else None
+    if not segs:
+        return None
+    wave = np.concatenate(segs)
+    if target is not None:
+        rate = dia._output_rate(dia.codec) or dia.codec.cfg.sample_rate
+        wave = dia.codec.normalize_loudness(wave, rate, target, float(dia.peak_ceiling))[0]
+    return wave

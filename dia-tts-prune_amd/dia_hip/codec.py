@@ -668,6 +668,7 @@ class DeviceCodec:
         self.encoder_error: Optional[Exception] = None
         self._resampler = None                                  # resample.DeviceResampler, made on first use
         self._timescaler = None                                 # timescale.DeviceTimescale, made on first use
+        self._loudness = None                                   # loudness.DeviceLoudness, made on first use
         self._spectral = None                                   # spectral.DeviceSpectral, made on first use
         if any(k.startswith("encoder.") for k in whole):
             try:
@@ -965,6 +966,23 @@ class DeviceCodec:
         """a timescale.TimescaleStream for one signal: push(chunk, final) -> the samples that have become final; joined they equal
         time_scale(mode="wsola") of the whole signal bit for bit.  mode "interp" cannot stream: ValueError"""
         return self._timescale().stream(speed, window, tolerance, mode)
+
+    # -------------------------------------------------------------------------------------- loudness
+    def _loud(self):
+        if self._loudness is None:
+            from .loudness import DeviceLoudness
+            self._loudness = DeviceLoudness(self.device)
+        return self._loudness
+
+    def measure_loudness(self, waves, rate: Optional[int] = None):
+        """mono float samples [N], or a list of them, at `rate` Hz (default: the codec's) -> per row {"loudness": LUFS (ITU-R
+        BS.1770-4, integrated), "true_peak": dBTP, "sample_peak": dBFS, "steps": ...} (csrc/loudness.hip, DESIGN.md "Loudness")"""
+        return self._loud().measure(waves, int(rate) if rate else self.cfg.sample_rate)
+
+    def normalize_loudness(self, waves, rate: Optional[int] = None, target: float = -23.0, peak: float = -1.0, **kw):
+        """-> (waves, reports): every row brought to `target` LUFS by one gain, lowered where the true peak would cross `peak` dBTP
+        (a pure gain, not a limiter; keywords as loudness.DeviceLoudness.normalize)"""
+        return self._loud().normalize(waves, int(rate) if rate else self.cfg.sample_rate, target, peak, **kw)
 
     # -------------------------------------------------------------------------------------- audio distance
     def audio_distance(self, a, b, rate: Optional[int] = None, **kw):

@@ -11,6 +11,7 @@ reference hard-codes B=1, dia/state.py:83-84) and a ``load_dac`` switch for offl
 
 from __future__ import annotations
 
+import math
 import time
 from dataclasses import dataclass
 from enum import Enum
@@ -102,6 +103,13 @@ class Dia:
     # (the pitch moves with the tempo; cannot stream), "wsola" keeps the pitch.  1.0 = every call launches what it did without it
     speed_factor: float = 1.0
     speed_mode: str = "interp"
+    # LUFS: generate(), generate_audio_batch() and generate_long() bring their waveform to this integrated loudness (ITU-R
+    # BS.1770-4) by ONE gain per utterance, lowered where the true peak would cross peak_ceiling (dBTP): a pure gain, not a limiter
+    # (DeviceCodec.normalize_loudness; DESIGN.md "Loudness").  It is the LAST step, after the speed factor and the resampler, at the
+    # delivered rate, so the ceiling holds for the samples the caller gets.  stream_audio() refuses it: the gain depends on the whole
+    # utterance.  None = nothing new is constructed or launched
+    loudness_target: Optional[float] = None
+    peak_ceiling: float = -1.0
     # the native codec's DECODER precision that codec_path= on the loaders asks load_codec() for: "fp32" (the exact kernel), "bf16x2"
     # or "bf16" (bf16 MFMA operands in two planes / one; DESIGN.md "Codec: bf16 modes").  The encode side is fp32 in every mode.
     # load_codec() sets it, on the instance, to the mode it loaded
@@ -546,10 +554,36 @@ class Dia:
         codec = self._need_codec()
         speed = self._speed(codec)
         rate = self._output_rate(codec)
+        target = self._loudness(codec)
         waves = codec.decode_batch(self.generate_batch(texts, *args, **kw))
         if speed is not None:
             waves = codec.time_scale(waves, speed, self.speed_mode)
-        return codec.resample(waves, codec.cfg.sample_rate, rate) if rate else waves
+        if rate:
+            waves = codec.resample(waves, codec.cfg.sample_rate, rate)
+        if target is not None:
+            waves = codec.normalize_loudness(waves, rate or codec.cfg.sample_rate, target, float(self.peak_ceiling))[0]
+        return waves
+
+    def _loudness(self, codec) -> Optional[float]:
+        """loudness_target where it asks for a normalisation, else None; the normalisation is the native codec's"""
+        t = self.loudness_target
+        if t is None:
+            return None
+        for name, v in (("loudness_target", t), ("peak_ceiling", self.peak_ceiling)):
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v):
+                raise ValueError(f"{name} = {v!r} is not a finite number")
+        if codec is None or not hasattr(codec, "normalize_loudness"):
+            raise RuntimeError(f"loudness_target = {t} needs the native codec's loudness meter: call Dia.load_codec(path_or_state) first")
+        return float(t)
+
+    def measure_loudness(self, wave, sample_rate: int = DEFAULT_SAMPLE_RATE):
+        """mono float samples [N] (or a list of them) at sample_rate -> {"loudness": LUFS (ITU-R BS.1770-4, integrated),
+        "true_peak": dBTP, "sample_peak": dBFS, "steps": ...} per row, on this instance's device (dia_hip/loudness.py,
+        csrc/loudness.hip).  Needs no codec and no weights."""
+        if getattr(self, "_loudness_meter", None) is None:
+            from .loudness import DeviceLoudness
+            self._loudness_meter = DeviceLoudness(self.device)
+        return self._loudness_meter.measure(wave, int(sample_rate))
 
     def _speed(self, codec) -> Optional[float]:
         """speed_factor, clamped, where it asks for a time-scaling, else None; the time-scaling is the native codec's"""
@@ -592,7 +626,10 @@ class Dia:
         load_codec().  With output_sample_rate set the samples are at that rate and equal codec.resample() of the whole waveform.
         With speed_factor other than 1 they are time-scaled first, per request by a WSOLA stream, and joined equal
         codec.time_scale(..., "wsola") of the whole waveform; speed_mode "interp" cannot stream and is refused here, before
-        anything runs."""
+        anything runs, and so is a loudness_target: its gain depends on the whole utterance."""
+        if self.loudness_target is not None:
+            raise ValueError("stream_audio: loudness_target cannot stream (the gain depends on the whole utterance's loudness and "
+                             "true peak); set loudness_target = None and normalise the joined samples")
         if self.codec is not None and self._speed(self.codec) is not None and self.speed_mode == "interp":
             raise ValueError("stream_audio: speed_mode 'interp' cannot stream (its positions depend on the utterance's total length); "
                              "set speed_mode = 'wsola'")
@@ -696,16 +733,22 @@ class Dia:
             print(f"Error during final decoding: {e}")
             return None
 
-    def _generate_output(self, codec_input: np.ndarray) -> Optional[np.ndarray]:
+    def _generate_output(self, codec_input: np.ndarray, normalize: bool = True) -> Optional[np.ndarray]:
         """codes [1, C, T'] -> waveform: through the native codec when load_codec() set one (at output_sample_rate when that is
-        set), else through the third-party codec (model.py:535-544)."""
+        set), else through the third-party codec (model.py:535-544).  normalize=False leaves loudness_target to the caller
+        (generate_long normalises the joined waveform once)."""
         rate = self._output_rate(self.codec)
         speed = self._speed(self.codec)
+        target = self._loudness(self.codec) if normalize else None
         if self.codec is not None:
             wave = self.codec.decode(codec_input)
             if speed is not None:
                 wave = self.codec.time_scale(wave, speed, self.speed_mode)
-            return self.codec.resample(wave, self.codec.cfg.sample_rate, rate) if rate else wave
+            if rate:
+                wave = self.codec.resample(wave, self.codec.cfg.sample_rate, rate)
+            if target is not None:
+                wave = self.codec.normalize_loudness(wave, rate or self.codec.cfg.sample_rate, target, float(self.peak_ceiling))[0]
+            return wave
         if self.dac_model is None:
             raise RuntimeError("DAC model not loaded. Cannot decode audio.")
         codes = torch.from_numpy(codec_input.astype(np.int64)).to(self.device)
@@ -720,24 +763,29 @@ class Dia:
     # encoded by DeviceCodec.encode.  Without one the methods keep the reference's names, arguments and failure behaviour
     # (reference model.py:546-595), which need the dac package and torchaudio.
     @torch.inference_mode()
-    def encode_audio(self, wave, sample_rate: int = DEFAULT_SAMPLE_RATE) -> torch.Tensor:
+    def encode_audio(self, wave, sample_rate: int = DEFAULT_SAMPLE_RATE, normalize_lufs: Optional[float] = None) -> torch.Tensor:
         """mono float samples [L] (array or tensor) -> codec frames [T, C] (int64), through the native codec: zeros on the right up
         to a multiple of 512 samples (DAC's preprocess), T = ceil(L / 512).  A rate other than the codec's is resampled by the
-        codec's own resampler (resample_to)."""
+        codec's own resampler (resample_to).  normalize_lufs: the waveform is brought to that loudness (under peak_ceiling) at the
+        codec's rate before it is encoded; None encodes it at the level it has."""
         codec = self._need_codec()
         w = np.asarray(wave.detach().cpu() if isinstance(wave, torch.Tensor) else wave, dtype=np.float32)
         if w.ndim == 2:
             w = w.mean(axis=0)
         w = resample_to(w.reshape(-1), int(sample_rate), codec.cfg.sample_rate, "the waveform", codec)
+        if normalize_lufs is not None:
+            w = codec.normalize_loudness(w, codec.cfg.sample_rate, float(normalize_lufs), float(self.peak_ceiling))[0]
         return torch.from_numpy(codec.encode(w)[0].T.copy())
 
-    def load_audio(self, audio_path: str) -> torch.Tensor:
+    def load_audio(self, audio_path: str, normalize_lufs: Optional[float] = None) -> torch.Tensor:
         """waveform file -> codec frames [T, C] for ``generate(audio_prompt=...)`` (mono; any sample rate with the native codec,
-        which resamples to its 44.1 kHz on the device)."""
+        which resamples to its 44.1 kHz on the device).  normalize_lufs: as encode_audio (native codec only)."""
         if self.codec is not None and self.codec.has_encoder:
             mono, rate = read_audio_mono(audio_path)
             mono = resample_to(mono, rate, self.codec.cfg.sample_rate, audio_path, self.codec)
-            return self.encode_audio(mono, self.codec.cfg.sample_rate)
+            return self.encode_audio(mono, self.codec.cfg.sample_rate, normalize_lufs)
+        if normalize_lufs is not None:
+            raise RuntimeError("normalize_lufs needs the native codec's loudness meter: call Dia.load_codec(path_or_state) first")
         codec = self.dac_model
         if codec is None:
             raise RuntimeError("DAC model not loaded. Cannot encode audio.")

@@ -1281,6 +1281,69 @@ typedef struct {
 } dia_timescale_args;
 int dia_timescale(const dia_timescale_args* a, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Loudness (csrc/loudness.hip; DESIGN.md "Loudness"): the sample arithmetic of an ITU-R BS.1770-4 meter for a ragged batch of mono
+ * rows, and a gain.  One new entry point and one new struct; nothing older changed.
+ *
+ * DIA_LOUD_MEASURE.  Row b has len[b] samples at x[b][0 ..]; step = round(rate / 10) samples (100 ms).  The row's samples run
+ * through the K-weighting, two biquads in cascade (transposed direct form II, float64 state, every product an fma):
+ *   y = b0 x + s1;  s1 = b1 x + s2 - a1 y;  s2 = b2 x - a2 y        shelf, then the high-pass on y
+ * and steps[b][s] receives the float64 sum of the squared outputs of samples [s step, (s + 1) step) for every WHOLE step
+ * s < len[b] / step.  The recursion is evaluated as the linear system it is: a step is cut into `chunks` chunks of `chunk` samples
+ * (the last one shorter: step - (chunks - 1) chunk, in [1, chunk]); every chunk's zero-state end state, a carry over the chunks
+ * of a step and then over the steps of the row, and a second run of every chunk from its true initial state, whose squares are
+ * added in ascending sample order per chunk and in ascending chunk order per step.  No atomics: an element has the same bits
+ * whichever row of whichever batch it is computed in.
+ * table (device, float64) holds what the carry needs, A being the 4 x 4 zero-input transition of the state
+ * (s1, s2 of the shelf, s1, s2 of the high-pass) over one sample, matrices row-major:
+ *   [0, 10)  shelf b0 b1 b2 a1 a2, high-pass b0 b1 b2 a1 a2        [10, 26)  A^chunk        [26, 42)  A^step
+ *   [42 + 16 c, 58 + 16 c)  A^(c chunk), c < chunks
+ * peaks[b][0] receives max |x| over the row, peaks[b][1] the larger of it and max |.| over the row 4 x oversampled:
+ *   output 4 q + p = sum_k bank[p][k] * x[q + first[p] + k]        q < len[b], p < 4, k < nt
+ * one fp32 fmaf chain from 0 in ascending k, x zero outside [0, len[b]); bank is the library's own 1 -> 4 resampling bank.  The
+ * oversampled signal is never stored.  An empty row has peaks 0 and no steps.
+ * ws is scratch of at least DIA_LOUD_WS_DOUBLES(B, ld_steps, chunks) doubles, ws_doubles its size.
+ *
+ * DIA_LOUD_APPLY.  y[b][i] = (float)((double)x[b][in_off[b] + i] * gain[b]) for i < out_count[b]: one rounding per sample.
+ * Memory outside x[b][0 .. len[b]) is never read, memory outside y[b][0 .. out_count[b]) never written.
+ *
+ * Refused with DIA_E_ARG before any HIP call: a null args / x / len; a mode other than the two; B outside [1, 64]; ldx outside
+ * [1, 1 << 24]; a len outside [0, ldx].  MEASURE: null steps / peaks / ws / table / bank / first; step outside [8, 19200]; chunk
+ * outside [1, step]; chunks != ceil(step / chunk) or above 64; nt outside [1, 32]; a first[p] + k that leaves [-32, 32];
+ * ld_steps < 1 or below a row's whole steps; ws_doubles too small.  APPLY: null y / in_off / out_count / gain; y == x; ldy outside
+ * [1, 1 << 24]; in_off < 0; out_count outside [0, ldy]; in_off + out_count > len; a gain that is not finite.
+ * ------------------------------------------------------------------------------------------------ */
+#define DIA_LOUD_MEASURE 0
+#define DIA_LOUD_APPLY 1
+#define DIA_LOUD_MAX_ROWS 64               /* rows of one launch */
+#define DIA_LOUD_MAX_T (1 << 24)           /* ldx, ldy */
+#define DIA_LOUD_MIN_STEP 8
+#define DIA_LOUD_MAX_STEP 19200            /* 192 kHz: a step is staged in LDS */
+#define DIA_LOUD_MAX_CHUNKS 64             /* one lane per chunk of a step */
+#define DIA_LOUD_MAX_TAPS 32
+#define DIA_LOUD_TABLE_DOUBLES(chunks) (42 + 16 * (chunks))
+#define DIA_LOUD_WS_DOUBLES(B, ld_steps, chunks) ((int64_t)(B) * ((int64_t)(ld_steps) * (8 + 4 * (chunks)) + (ld_steps) + 1))
+typedef struct {
+  const float* x;              /* device [B][ldx] */
+  float* y;                    /* device [B][ldy]; never x.  APPLY */
+  double* steps;               /* device [B][ld_steps].  MEASURE */
+  float* peaks;                /* device [B][2]: sample peak, true peak (linear).  MEASURE */
+  double* ws;                  /* device [ws_doubles].  MEASURE */
+  const double* table;         /* device [DIA_LOUD_TABLE_DOUBLES(chunks)].  MEASURE */
+  const float* bank;           /* device [4][nt].  MEASURE */
+  int64_t ws_doubles;
+  int32_t mode;                /* DIA_LOUD_MEASURE / DIA_LOUD_APPLY */
+  int32_t B, ldx, ldy, ld_steps;
+  int32_t step, chunk, chunks, nt;
+  int32_t _pad0;
+  const int32_t* first;        /* HOST [4], read during the call (as all below).  MEASURE */
+  const int32_t* len;          /* HOST [B]: 0 .. ldx */
+  const int32_t* in_off;       /* HOST [B].  APPLY */
+  const int32_t* out_count;    /* HOST [B]: 0 .. ldy.  APPLY */
+  const double* gain;          /* HOST [B]: linear.  APPLY */
+} dia_loudness_args;
+int dia_loudness(const dia_loudness_args* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
