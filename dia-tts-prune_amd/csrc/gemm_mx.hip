@@ -20,25 +20,20 @@
 //          byte select b takes byte b); slot p holds its dwords of k-tiles 4p .. 4p + 3: 4 slots, 4352 bytes per group, 0.265625
 //          of the dense tiles'.  One 16-byte load feeds four B fragments: a wave's 8 k-tiles are two loads per strip, its 16 four.
 //
-// One workgroup owns one 16-column strip (persistent form: several, the next one's weights streaming during this one's
-// reduction and epilogue); its waves split K into ranges of KPW k-tiles (8 = half a group, 16 = a whole one); gridDim.y > 1
-// splits K across workgroups (wo) with the dense path's hand-off (splitk_combine).  Every weight load of a wave is issued
-// before its first MFMA.  Activations:
-//   RS = 4   M <= 4: the workgroup's K range of the first 4 rows is staged once into LDS as bf16 planes (as k_gemv_small)
+// The frame around the inner loop (LDS prefix, activation image, row scales, wave sum, split-K hand-off, epilogue, strip loop)
+// is gemv_frame.hpp's.  A wave's K range is KPW k-tiles (8 = half a group, 16 = a whole one); every weight load of a wave is
+// issued before its first MFMA.  Activations:
+//   RS = 4   M <= 4: the frame's LDS image
 //   RS = 16  5..16 rows: each wave holds the three bf16 planes of its K range's fragments in registers for every strip it walks
 //            (as k_gemm16: 96 VGPRs at 8 k-tiles per wave); with 16 k-tiles per wave it reads them from L2 inside the loop
-// Partial tiles of the waves are summed through LDS in wave order; the element-per-thread epilogue (run_epilogue_rows) follows.
-#include "gemm_common.hpp"
-#include <cstdio>
+#include "gemv_frame.hpp"
 
 namespace {
 
 constexpr int MX_GROUP = 16;                       // k-tiles per stream group (layout.FP8_GROUP)
-constexpr int MX_MAXW = 8;                         // waves per workgroup
 constexpr int MX_SCALE_BYTES = 256;                // scale block of a group
 constexpr int MX_SLOT_BYTES = 1024;                // one value slot
 
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
 typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
 
@@ -79,20 +74,16 @@ struct Fp4 {
 };
 static_assert(Fp8::GROUP_BYTES == 8448 && Fp4::GROUP_BYTES == 4352, "the group sizes of dia_hip/layout.py");
 
-constexpr size_t mx_smem_fixed() { return sizeof(f32x4) * 2 * MX_MAXW * 64 + sizeof(float) * (16 * 17 + 16); }
-size_t mx_smem(int ktw, int rs) { return mx_smem_fixed() + (rs == 4 ? (size_t)DIA_NPLANES * ktw * 4 * rs * 16 : 0); }
+size_t mx_smem(int ktw, int rs) { return gf_lds_bytes() + (rs == 4 ? gf_image_bytes(ktw) : 0); }
 
 template <class Fmt, int KPW, int RS, bool MULTI>
-__global__ __launch_bounds__(MX_MAXW * 64) void k_gemm_mx(GemmK p) {
+__global__ __launch_bounds__(GF_MAXW * 64) void k_gemm_mx(GemmK p) {
   static_assert(KPW == 8 || KPW == 16, "half a stream group or a whole one per wave");
   constexpr int NS = KPW / Fmt::SLOT_KT;               // value slots per wave
   constexpr int NSC = KPW / 4;                         // dwords of scale bytes per wave
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  f32x4* red = reinterpret_cast<f32x4*>(smem_raw);                                   // [2][MX_MAXW][64]
-  float* tile = reinterpret_cast<float*>(smem_raw + sizeof(f32x4) * 2 * MX_MAXW * 64); // [16][17] (split-K hand-off)
-  float* inv_s = tile + 16 * 17;                                                     // [16]
-  bf16x8* As = reinterpret_cast<bf16x8*>(inv_s + 16);                               // RS = 4: [plane][kt][kq][row]
-  __shared__ int sk_flag;
+  const GfLds L = gf_lds(smem_raw);
+  bf16x8* As = reinterpret_cast<bf16x8*>(L.rest);                                    // RS = 4: [plane][kt][kq][row]
 
   const int NT = blockDim.x, NW = NT >> 6;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -119,7 +110,7 @@ __global__ __launch_bounds__(MX_MAXW * 64) void k_gemm_mx(GemmK p) {
   const float* Af = reinterpret_cast<const float*>(p.A);
 
   // ---- small, L2-resident operands first (see k_gemv_small): activation image / fragments, row scales
-  constexpr int CE = (KPW * 4 * RS + 63) / 64;        // RS = 4: image entries per thread (KPW k-tiles x 4 quarters x RS rows per wave)
+  constexpr int CE = gf_image_ce(KPW);
   const int nentries = ktw * 4 * RS;
   float4 ex[RS == 4 ? CE : 1], ey[RS == 4 ? CE : 1];
   constexpr int AP = (RS == 16 && KPW == 8) ? KPW : 1;   // RS = 16: fragments of the wave's k-tiles held from the start
@@ -130,31 +121,13 @@ __global__ __launch_bounds__(MX_MAXW * 64) void k_gemm_mx(GemmK p) {
     f[0] = s0[0]; f[1] = s0[1];
   };
   if constexpr (RS == 4) {
-    const long kta = (long)blockIdx.y * ktw;           // first activation k-tile of the range
-#pragma unroll
-    for (int u = 0; u < CE; ++u) {
-      const int c = min(tid + u * NT, nentries - 1);
-      const int row = c % RS, kq = (c / RS) & 3, kt = c / (4 * RS);
-      const float4* src = reinterpret_cast<const float4*>(Af + ((kta + kt) * 64 + min(row, p.M - 1) + 16 * kq) * 8);
-      ex[u] = src[0]; ey[u] = src[1];
-    }
+    gf_image_load<KPW>(p, tid, NT, ex, ey);
   } else if constexpr (AP == KPW) {
 #pragma unroll
     for (int i = 0; i < KPW; ++i) load_frag(af[i], kt0 + i);
   }
-  // row scales: 8 threads per row, 16 strip partials each requested at once on clamped addresses (as k_gemv_small: a loop of
-  // dependent loads here delayed the weight stream by 4 us in the step); summed after the weight loads are in flight
-  const bool has_norm = p.ssq_in != nullptr;
-  const int s_row = tid >> 3, s_part = tid & 7;
-  const bool s_thread = tid < 128 && has_norm;
   float sq[16];
-#pragma unroll
-  for (int i = 0; i < 16; ++i) sq[i] = 0.f;
-  if (s_thread) {
-    const float* sp = p.ssq_in + min(s_row, p.M - 1);
-#pragma unroll
-    for (int i = 0; i < 16; ++i) sq[i] = sp[(long)min(s_part + 8 * i, p.ssq_in_n - 1) * p.ssq_ld];
-  }
+  gf_scales_load(p, tid, sq);
   __builtin_amdgcn_sched_barrier(0);
   u32x4 b0[NS], b1[MULTI ? NS : 1];
   unsigned c0[NSC], c1[MULTI ? NSC : 1];
@@ -165,37 +138,13 @@ __global__ __launch_bounds__(MX_MAXW * 64) void k_gemm_mx(GemmK p) {
 #pragma unroll
     for (int i = 0; i < KPW; ++i) split3x8(af[i][0], af[i][1], a3[i][0], a3[i][1], a3[i][2]);
   }
-  if constexpr (RS == 4) {
-#pragma unroll
-    for (int u = 0; u < CE; ++u)
-      if (tid + u * NT < nentries) {
-        const int c = tid + u * NT;
-        bf16x8 h, mi, lo;
-        split3x8(ex[u], ey[u], h, mi, lo);
-        As[c] = h; As[nentries + c] = mi; As[2 * nentries + c] = lo;
-      }
-  }
-  for (int t = tid; t < 128; t += NT) {              // (a one-wave workgroup also serves rows 8..15, loading them here)
-    const int r = t >> 3, part = t & 7;
-    float s0 = 0.f;
-    if (t == tid) {
-#pragma unroll
-      for (int i = 0; i < 16; ++i) s0 += (part + 8 * i < p.ssq_in_n && r < p.M) ? sq[i] : 0.f;
-      if (has_norm && r < p.M)
-        for (int i = part + 128; i < p.ssq_in_n; i += 8) s0 += p.ssq_in[(long)i * p.ssq_ld + r];   // D > 2048 only
-    } else if (has_norm && r < p.M) {
-      for (int i = part; i < p.ssq_in_n; i += 8) s0 += p.ssq_in[(long)i * p.ssq_ld + r];
-    }
-    s0 += __shfl_xor(s0, 1, 64);
-    s0 += __shfl_xor(s0, 2, 64);
-    s0 += __shfl_xor(s0, 4, 64);
-    if (part == 0) inv_s[r] = has_norm ? rsqrtf(s0 * p.inv_d + p.eps) : 1.0f;
-  }
+  if constexpr (RS == 4) gf_image_store<KPW>(As, tid, NT, ex, ey);
+  gf_scales_reduce(p, tid, NT, sq, L.inv_s);
   lds_barrier();                                      // image + row scales visible; the weight loads stay in flight
 
   const int arow = min(lane & 15, RS - 1), akq = lane >> 4;
   int sbuf = 0;
-  auto body = [&](u32x4* bc, unsigned* cc, u32x4* bn, unsigned* cn, int strip) {
+  auto body = [&](u32x4* bc, unsigned* cc, u32x4* bn, unsigned* cn, int strip) __attribute__((always_inline)) {
     const int next = strip + G;
     if constexpr (MULTI) load_strip(bn, cn, DIA_PREFETCH_CLAMP(next, p.nstrips));   // unconditional: see k_gemv_small
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
@@ -220,60 +169,15 @@ __global__ __launch_bounds__(MX_MAXW * 64) void k_gemm_mx(GemmK p) {
       acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(mi, b, acc, 0, 0, 0);
       acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(lo, b, acc, 0, 0, 0);
     }
-    // cross-wave sum: element (row m, column c) of the output tile sits in lane 16 (m >> 2) + c, register m & 3 of every wave
-    f32x4* rb = red + sbuf * (MX_MAXW * 64);
+    f32x4* rb = L.red + sbuf * (GF_MAXW * 64);
     sbuf ^= 1;
-    if (RS == 16 || lane < 16) rb[w * 64 + lane] = acc;
+    gf_tile_store<RS, false>(rb, w, lane, acc);
     lds_barrier();
-    const bool split = !MULTI && gridDim.y > 1;
-    constexpr int NE = (16 * RS + 63) / 64;          // epilogue elements per thread (at least one wave per workgroup)
-    float vs[NE];
-#pragma unroll
-    for (int u = 0; u < NE; ++u) {
-      const int e = tid + u * NT;
-      vs[u] = 0.f;
-      if (e < 16 * RS) {
-        const int m = e >> 4, c = e & 15;
-        const float* rf = reinterpret_cast<const float*>(rb) + ((m >> 2) * 16 + c) * 4 + (m & 3);
-        float v = rf[0];
-        for (int ww = 1; ww < NW; ++ww) v += rf[ww * 256];
-        vs[u] = v;
-        if (split) tile[m * 17 + c] = v;
-      }
-    }
-    if (split) {            // cross-workgroup split-K (wo): the last arriver sums the slabs in split order and runs the epilogue
-      // (splitk_combine publishes all 16 rows of the tile: rows RS.. carry zeros, never read back)
-      if constexpr (RS < 16)
-        for (int e = 16 * RS + tid; e < 256; e += NT) tile[(e >> 4) * 17 + (e & 15)] = 0.f;
-      lds_barrier();
-      if (!splitk_combine(p, tile, strip, tid, &sk_flag)) return;
-#pragma unroll
-      for (int u = 0; u < NE; ++u)
-        if (tid + u * NT < 16 * RS) vs[u] = tile[((tid + u * NT) >> 4) * 17 + ((tid + u * NT) & 15)];
-    }
-#pragma unroll
-    for (int u = 0; u < NE; ++u) {
-      const int e = tid + u * NT;
-      if (e >= 16 * RS) break;
-      float xpre1 = 0.f, gpre1 = 1.f;
-      if (p.epi == DIA_EPI_RESID_EMIT) {
-        const int m = e >> 4, n = strip * 16 + (e & 15);
-        xpre1 = p.out[(long)min(m, p.M - 1) * p.ldo + n];
-        gpre1 = p.gnext[n];
-      }
-      run_epilogue_rows<RS, true>(p, vs[u], inv_s, e, strip, xpre1, gpre1);
-    }
+    float vs[gf_ne(RS)];
+    gf_wave_sum<RS, false>(rb, tid, NT, vs);
+    gf_finish<RS, MULTI>(p, L, vs, tid, NT, strip);
   };
-  if constexpr (MULTI) {
-    int strip = blockIdx.x;                            // strip pairs, then at most one more (see k_gemv_small)
-    for (; strip + G < p.nstrips; strip += 2 * G) {
-      body(b0, c0, b1, c1, strip);
-      body(b1, c1, b0, c0, strip + G);
-    }
-    if (strip < p.nstrips) body(b0, c0, b1, c1, strip);
-  } else {
-    body(b0, c0, b1, c1, blockIdx.x);
-  }
+  gf_strips<MULTI>(p.nstrips, [&](int strip) { body(b0, c0, b1, c1, strip); }, [&](int strip) { body(b1, c1, b0, c0, strip); });
 }
 
 template <class Fmt, int KPW, int RS>
@@ -291,7 +195,7 @@ int launch_mx(const GemmK& k, int nw, int sk, int spw, hipStream_t st) {
 
 template <class Fmt>
 int launch_mx_shape(const GemmK& k, int ktw, int sk, int spw, bool image, hipStream_t st) {
-  const int kpw = ktw / 8 <= MX_MAXW ? 8 : 16;
+  const int kpw = ktw / 8 <= GF_MAXW ? 8 : 16;
   const int nw = ktw / kpw;
   if (kpw == 8) return image ? launch_mx<Fmt, 8, 4>(k, nw, sk, spw, st) : launch_mx<Fmt, 8, 16>(k, nw, sk, spw, st);
   return image ? launch_mx<Fmt, 16, 4>(k, nw, sk, 1, st) : launch_mx<Fmt, 16, 16>(k, nw, sk, 1, st);
@@ -302,37 +206,24 @@ int launch_mx_shape(const GemmK& k, int ktw, int sk, int spw, bool image, hipStr
 // dia_gemm with w_format == DIA_W_MXFP8 / DIA_W_MXFP4: what an MX stream cannot serve (checked before dia_gemm's other weight forms)
 int dia_gemm_mx_check(const dia_gemm_args* a) {
   const char* name = a->w_format == DIA_W_MXFP4 ? Fp4::NAME : Fp8::NAME;
-  auto refuse = [name](const char* what) {           // "dia_gemm: the MXFP8 stream <what>" (dia_fail copies its message)
-    char msg[160];
-    snprintf(msg, sizeof msg, "dia_gemm: the %s stream %s", name, what);
-    return dia_fail(DIA_E_ARG, msg);
-  };
-  if (a->w_planes > 1) return refuse("holds one weight encoding (w_planes must be 0 or 1)");
-  if (a->w_layout == 1) return refuse("has no diagonal layout (w_layout must be 0)");
-  if (a->sp_blocks || a->sp_toff) return refuse("and the zero-skipping stream (sp_blocks) exclude each other");
-  if (a->epi == DIA_EPI_CROSSKV) return refuse("has no CROSSKV epilogue (prefill only)");
-  if (a->cmap || a->strip_map) return refuse("has no compaction maps (cmap / strip_map)");
-  if (a->M > 16) return refuse("serves at most 16 rows");
-  const bool emits = a->epi == DIA_EPI_RESID_EMIT || a->epi == DIA_EPI_SWIGLU_EMIT;
-  if (!(a->act_f32 & 1) || (emits && !(a->act_f32 & 2))) return refuse("needs fp32 activation tiles in and out (act_f32 = 3), not planes");
-  if (!a->W) return refuse("needs W");
-  if (a->epi == DIA_EPI_RESID_EMIT && !a->gnext) return refuse("needs gnext with RESID_EMIT");
-  const int sk = a->sk > 1 ? a->sk : 1;
+  const int rc = gf_check_common(a, name, 16);
+  if (rc != DIA_OK) return rc;
+  if (!a->W) return gf_refuse(name, "needs W");
+  const int sk = gf_shape(a).sk;
   if (a->KT % MX_GROUP != 0 || a->KT % sk != 0 || (a->KT / sk) % MX_GROUP != 0)
-    return refuse("needs K a multiple of 512 per workgroup (whole groups of 16 k-tiles)");
-  if (a->KT / sk > 16 * MX_MAXW) return refuse("serves at most 128 k-tiles per workgroup (K <= 4096; use split-K)");
+    return gf_refuse(name, "needs K a multiple of 512 per workgroup (whole groups of 16 k-tiles)");
+  if (a->KT / sk > 16 * GF_MAXW) return gf_refuse(name, "serves at most 128 k-tiles per workgroup (K <= 4096; use split-K)");
   return DIA_OK;
 }
 
 // the launch (dia_gemm has run dia_gemm_mx_check and its own argument checks)
 int dia_gemm_mx(const dia_gemm_args* a, void* stream) {
-  const int sk = a->sk > 1 ? a->sk : 1;
-  if (sk > 1 && (!a->sk_scratch || !a->sk_tickets)) return dia_fail(DIA_E_ARG, "dia_gemm: split-K needs sk_scratch, sk_tickets and KT % sk == 0");
-  const int ktw = a->KT / sk;                          // k-tiles per workgroup
+  const int rc = gf_check_splitk(a);
+  if (rc != DIA_OK) return rc;
+  const auto [sk, ktw, spw] = gf_shape(a);
   GemmK k;
   fill_gemmk(a, k);
   hipStream_t st = (hipStream_t)stream;
-  const int spw = stream_spw(a->spw, a->nstrips);      // persistent form: next strip's weights in flight during this one's epilogue
   const bool image = a->M <= 4;                        // (128 k-tiles x 4 rows x 3 planes = 96 KiB at most)
   if (a->w_format == DIA_W_MXFP4) return launch_mx_shape<Fp4>(k, ktw, sk, spw, image, st);
   return launch_mx_shape<Fp8>(k, ktw, sk, spw, image, st);

@@ -1,5 +1,6 @@
 // 2:4 sparse decode GEMV: out[M][N] = X[M][K] . W[K][N] for M <= 16 rows with W 2:4-pruned along K and streamed in the
-// compressed form of dia_hip/layout.py tile_weight_24 (dia_gemm_args.w_format = DIA_W_SPARSE24).
+// compressed form of dia_hip/layout.py tile_weight_24 (dia_gemm_args.w_format = DIA_W_SPARSE24).  The frame around the inner
+// loop (LDS prefix, activation image, row scales, wave sum, split-K hand-off, epilogue, strip loop) is gemv_frame.hpp's.
 //
 // Mapping (CDNA4): v_smfmac_f32_16x16x64_bf16 takes a 2:4-compressed 16 x 64 A operand (8 bf16 + a 16-bit index word per lane)
 // and a dense 64 x 16 B operand (16 bf16 per lane).  The WEIGHTS are the A operand — the reverse of the dense kernels, where they
@@ -8,21 +9,17 @@
 // k-tile t is the A fragment pair of dense k-tiles 2t and 2t + 1 of the fp32 activation tiles, split into hi / mid / lo bf16
 // in registers: three smfmac per sparse k-tile, products exact w.r.t. the fp32 activations as in the dense kernels.
 //
-// One workgroup owns one 16-column strip (persistent form: several, the next one's weights streaming during this one's
-// reduction and epilogue); its waves split K into ranges of KPW sparse k-tiles = KPW / 8 stream groups (metadata block +
-// 8 value slots, 9 KiB); gridDim.y > 1 splits K across workgroups (wo) with the dense path's hand-off (splitk_combine).
-// Every weight load of a wave is issued before its first smfmac.  Activations:
-//   RS = 4   M <= 4: the workgroup's K range of the first 4 rows is staged once into LDS as bf16 planes (as k_gemv_small)
+// A wave's K range is KPW sparse k-tiles = KPW / 8 stream groups (metadata block + 8 value slots, 9 KiB) = 2 KPW dense k-tiles
+// of the activations.  Every weight load of a wave is issued before its first smfmac.  Activations:
+//   RS = 4   M <= 4: the frame's LDS image
 //   RS = 16  5..16 rows (and M <= 4 when that image would not fit): each wave loads its fragments from the fp32 tiles, ahead of
 //            its weights; one strip per workgroup (the persistent form would hold the fragments and two weight buffers: spills)
-// Partial tiles of the waves are summed through LDS in wave order; the element-per-thread epilogue (run_epilogue_rows) follows.
-#include "gemm_common.hpp"
+#include "gemv_frame.hpp"
 
 namespace {
 
 constexpr int SP_GROUP = 8;                  // sparse k-tiles per stream group (layout.SP24_GROUP)
 constexpr int SP_SLOTS = SP_GROUP + 1;       // metadata block + value slots, 1 KiB each
-constexpr int SP_MAXW = 8;                   // waves per workgroup
 
 typedef __attribute__((ext_vector_type(16))) __bf16 bf16x16;
 
@@ -30,19 +27,15 @@ __device__ __forceinline__ bf16x16 cat16(const bf16x8 lo, const bf16x8 hi) {
   return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15);
 }
 
-constexpr size_t sp_smem_fixed() { return sizeof(f32x4) * 2 * SP_MAXW * 64 + sizeof(float) * (16 * 17 + 16); }
-size_t sp_smem(int kt32w, int rs) { return sp_smem_fixed() + (rs == 4 ? (size_t)DIA_NPLANES * kt32w * 4 * rs * 16 : 0); }
+size_t sp_smem(int kt32w, int rs) { return gf_lds_bytes() + (rs == 4 ? gf_image_bytes(kt32w) : 0); }
 
 template <int KPW, int RS, bool MULTI>
-__global__ __launch_bounds__(SP_MAXW * 64) void k_gemv24(GemmK p) {
+__global__ __launch_bounds__(GF_MAXW * 64) void k_gemv24(GemmK p) {
   static_assert(KPW % SP_GROUP == 0, "whole stream groups per wave");
   constexpr int NG = KPW / SP_GROUP;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  f32x4* red = reinterpret_cast<f32x4*>(smem_raw);                                   // [2][SP_MAXW][64]
-  float* tile = reinterpret_cast<float*>(smem_raw + sizeof(f32x4) * 2 * SP_MAXW * 64); // [16][17] (split-K hand-off)
-  float* inv_s = tile + 16 * 17;                                                     // [16]
-  bf16x8* As = reinterpret_cast<bf16x8*>(inv_s + 16);                               // RS = 4: [plane][kt32][kq][row]
-  __shared__ int sk_flag;
+  const GfLds L = gf_lds(smem_raw);
+  bf16x8* As = reinterpret_cast<bf16x8*>(L.rest);                                    // RS = 4: [plane][kt32][kq][row]
 
   const int NT = blockDim.x, NW = NT >> 6;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -63,8 +56,8 @@ __global__ __launch_bounds__(SP_MAXW * 64) void k_gemv24(GemmK p) {
   const float* Af = reinterpret_cast<const float*>(p.A);
 
   // ---- small, L2-resident operands first (see k_gemv_small): activation image / fragments, row scales
-  constexpr int CE = (2 * KPW * 4 * RS + 63) / 64;    // RS = 4: image entries per thread (2 KPW dense k-tiles x 4 quarters x RS rows per wave)
-  const int kt32w = 2 * ktw, nentries = kt32w * 4 * RS;
+  constexpr int CE = gf_image_ce(2 * KPW);
+  const int nentries = 2 * ktw * 4 * RS;
   float4 ex[RS == 4 ? CE : 1], ey[RS == 4 ? CE : 1];
   constexpr int AP = (RS == 16 && KPW <= 8) ? KPW : 1;   // RS = 16: fragments of the wave's k-tiles held from the start
   float4 af[AP][4];
@@ -75,67 +68,25 @@ __global__ __launch_bounds__(SP_MAXW * 64) void k_gemv24(GemmK p) {
     f[0] = s0[0]; f[1] = s0[1]; f[2] = s1[0]; f[3] = s1[1];
   };
   if constexpr (RS == 4) {
-    const long kta = (long)blockIdx.y * kt32w;         // first dense activation k-tile of the range
-#pragma unroll
-    for (int u = 0; u < CE; ++u) {
-      const int c = min(tid + u * NT, nentries - 1);
-      const int row = c % RS, kq = (c / RS) & 3, kt = c / (4 * RS);
-      const float4* src = reinterpret_cast<const float4*>(Af + ((kta + kt) * 64 + row + 16 * kq) * 8);
-      ex[u] = src[0]; ey[u] = src[1];
-    }
+    gf_image_load<2 * KPW>(p, tid, NT, ex, ey);
   } else if constexpr (AP == KPW) {
 #pragma unroll
     for (int i = 0; i < KPW; ++i) load_frag(af[i], kt0 + i);
   }
-  // row scales: 8 threads per row, 16 strip partials each requested at once on clamped addresses (as k_gemv_small: a loop of
-  // dependent loads here delayed the weight stream by 4 us in the step); summed after the weight loads are in flight
-  const bool has_norm = p.ssq_in != nullptr;
-  const int s_row = tid >> 3, s_part = tid & 7;
-  const bool s_thread = tid < 128 && has_norm;
   float sq[16];
-#pragma unroll
-  for (int i = 0; i < 16; ++i) sq[i] = 0.f;
-  if (s_thread) {
-    const float* sp = p.ssq_in + min(s_row, p.M - 1);
-#pragma unroll
-    for (int i = 0; i < 16; ++i) sq[i] = sp[(long)min(s_part + 8 * i, p.ssq_in_n - 1) * p.ssq_ld];
-  }
+  gf_scales_load(p, tid, sq);
   __builtin_amdgcn_sched_barrier(0);
   bf16x8 b0[KPW], b1[MULTI ? KPW : 1];
   u32x4 m0[NG], m1[MULTI ? NG : 1];
   load_strip(b0, m0, blockIdx.x);                     // the HBM stream starts here
   __builtin_amdgcn_sched_barrier(0);
-  if constexpr (RS == 4) {
-#pragma unroll
-    for (int u = 0; u < CE; ++u)
-      if (tid + u * NT < nentries) {
-        const int c = tid + u * NT;
-        bf16x8 h, mi, lo;
-        split3x8(ex[u], ey[u], h, mi, lo);
-        As[c] = h; As[nentries + c] = mi; As[2 * nentries + c] = lo;
-      }
-  }
-  for (int t = tid; t < 128; t += NT) {              // (a one-wave workgroup also serves rows 8..15, loading them here)
-    const int r = t >> 3, part = t & 7;
-    float s0 = 0.f;
-    if (t == tid) {
-#pragma unroll
-      for (int i = 0; i < 16; ++i) s0 += (part + 8 * i < p.ssq_in_n && r < p.M) ? sq[i] : 0.f;
-      if (has_norm && r < p.M)
-        for (int i = part + 128; i < p.ssq_in_n; i += 8) s0 += p.ssq_in[(long)i * p.ssq_ld + r];   // D > 2048 only
-    } else if (has_norm && r < p.M) {
-      for (int i = part; i < p.ssq_in_n; i += 8) s0 += p.ssq_in[(long)i * p.ssq_ld + r];
-    }
-    s0 += __shfl_xor(s0, 1, 64);
-    s0 += __shfl_xor(s0, 2, 64);
-    s0 += __shfl_xor(s0, 4, 64);
-    if (part == 0) inv_s[r] = has_norm ? rsqrtf(s0 * p.inv_d + p.eps) : 1.0f;
-  }
+  if constexpr (RS == 4) gf_image_store<2 * KPW>(As, tid, NT, ex, ey);
+  gf_scales_reduce(p, tid, NT, sq, L.inv_s);
   lds_barrier();                                      // image + row scales visible; the weight loads stay in flight
 
   const int arow = min(lane & 15, RS - 1), akq = lane >> 4;
   int sbuf = 0;
-  auto body = [&](bf16x8* bc, u32x4* mc, bf16x8* bn, u32x4* mn, int strip) {
+  auto body = [&](bf16x8* bc, u32x4* mc, bf16x8* bn, u32x4* mn, int strip) __attribute__((always_inline)) {
     const int next = strip + G;
     if constexpr (MULTI) load_strip(bn, mn, DIA_PREFETCH_CLAMP(next, p.nstrips));   // unconditional: see k_gemv_small
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
@@ -169,60 +120,15 @@ __global__ __launch_bounds__(SP_MAXW * 64) void k_gemv24(GemmK p) {
         acc = __builtin_amdgcn_smfmac_f32_16x16x64_bf16(bc[i], cat16(lo[0], lo[1]), acc, (int)word, 0, 1);
       }
     }
-    // cross-wave sum: element (row m, column c) of the output tile sits in lane 16 (c >> 2) + m, register c & 3 of every wave
-    f32x4* rb = red + sbuf * (SP_MAXW * 64);
+    f32x4* rb = L.red + sbuf * (GF_MAXW * 64);
     sbuf ^= 1;
-    if (RS == 16 || (lane & 15) < RS) rb[w * 64 + lane] = acc;
+    gf_tile_store<RS, true>(rb, w, lane, acc);       // (the weights are the A operand: the transposed tile)
     lds_barrier();
-    const bool split = !MULTI && gridDim.y > 1;
-    constexpr int NE = (16 * RS + 63) / 64;          // epilogue elements per thread (at least one wave per workgroup)
-    float vs[NE];
-#pragma unroll
-    for (int u = 0; u < NE; ++u) {
-      const int e = tid + u * NT;
-      vs[u] = 0.f;
-      if (e < 16 * RS) {
-        const int m = e >> 4, c = e & 15;
-        const float* rf = reinterpret_cast<const float*>(rb) + ((c >> 2) * 16 + m) * 4 + (c & 3);
-        float v = rf[0];
-        for (int ww = 1; ww < NW; ++ww) v += rf[ww * 256];
-        vs[u] = v;
-        if (split) tile[m * 17 + c] = v;
-      }
-    }
-    if (split) {            // cross-workgroup split-K (wo): the last arriver sums the slabs in split order and runs the epilogue
-      // (splitk_combine publishes all 16 rows of the tile: rows RS.. carry zeros, never read back)
-      if constexpr (RS < 16)
-        for (int e = 16 * RS + tid; e < 256; e += NT) tile[(e >> 4) * 17 + (e & 15)] = 0.f;
-      lds_barrier();
-      if (!splitk_combine(p, tile, strip, tid, &sk_flag)) return;
-#pragma unroll
-      for (int u = 0; u < NE; ++u)
-        if (tid + u * NT < 16 * RS) vs[u] = tile[((tid + u * NT) >> 4) * 17 + ((tid + u * NT) & 15)];
-    }
-#pragma unroll
-    for (int u = 0; u < NE; ++u) {
-      const int e = tid + u * NT;
-      if (e >= 16 * RS) break;
-      float xpre1 = 0.f, gpre1 = 1.f;
-      if (p.epi == DIA_EPI_RESID_EMIT) {
-        const int m = e >> 4, n = strip * 16 + (e & 15);
-        xpre1 = p.out[(long)min(m, p.M - 1) * p.ldo + n];
-        gpre1 = p.gnext[n];
-      }
-      run_epilogue_rows<RS, true>(p, vs[u], inv_s, e, strip, xpre1, gpre1);
-    }
+    float vs[gf_ne(RS)];
+    gf_wave_sum<RS, true>(rb, tid, NT, vs);
+    gf_finish<RS, MULTI>(p, L, vs, tid, NT, strip);
   };
-  if constexpr (MULTI) {
-    int strip = blockIdx.x;                            // strip pairs, then at most one more (see k_gemv_small)
-    for (; strip + G < p.nstrips; strip += 2 * G) {
-      body(b0, m0, b1, m1, strip);
-      body(b1, m1, b0, m0, strip + G);
-    }
-    if (strip < p.nstrips) body(b0, m0, b1, m1, strip);
-  } else {
-    body(b0, m0, b1, m1, blockIdx.x);
-  }
+  gf_strips<MULTI>(p.nstrips, [&](int strip) { body(b0, m0, b1, m1, strip); }, [&](int strip) { body(b1, m1, b0, m0, strip); });
 }
 
 template <int KPW, int RS>
@@ -242,37 +148,29 @@ int launch24(const GemmK& k, int nw, int sk, int spw, hipStream_t st) {
 
 // dia_gemm with w_format == DIA_W_SPARSE24: what the sparse stream cannot serve (checked before dia_gemm's other weight forms)
 int dia_gemm_sparse24_check(const dia_gemm_args* a) {
-  if (a->w_planes > 1) return dia_fail(DIA_E_ARG, "dia_gemm: the 2:4 sparse stream holds one bf16 weight plane (w_planes must be 0 or 1)");
-  if (a->w_layout == 1) return dia_fail(DIA_E_ARG, "dia_gemm: the 2:4 sparse stream has no diagonal layout (w_layout must be 0)");
-  if (a->sp_blocks || a->sp_toff) return dia_fail(DIA_E_ARG, "dia_gemm: the 2:4 sparse stream and the zero-skipping stream (sp_blocks) exclude each other");
-  if (a->epi == DIA_EPI_CROSSKV) return dia_fail(DIA_E_ARG, "dia_gemm: the 2:4 sparse stream has no CROSSKV epilogue (prefill only)");
-  if (a->cmap || a->strip_map) return dia_fail(DIA_E_ARG, "dia_gemm: the 2:4 sparse stream has no compaction maps (cmap / strip_map)");
-  if (a->M > 16) return dia_fail(DIA_E_ARG, "dia_gemm: the 2:4 sparse stream serves at most 16 rows");
-  const bool emits = a->epi == DIA_EPI_RESID_EMIT || a->epi == DIA_EPI_SWIGLU_EMIT;
-  if (!(a->act_f32 & 1) || (emits && !(a->act_f32 & 2)))
-    return dia_fail(DIA_E_ARG, "dia_gemm: the 2:4 sparse stream needs fp32 activation tiles in and out (act_f32 = 3)");
-  if (!a->W) return dia_fail(DIA_E_ARG, "dia_gemm: the 2:4 sparse stream needs W");
-  if (a->epi == DIA_EPI_RESID_EMIT && !a->gnext) return dia_fail(DIA_E_ARG, "dia_gemm: the 2:4 sparse stream needs gnext with RESID_EMIT");
+  const int rc = gf_check_common(a, "2:4 sparse", 16, "holds one bf16 weight plane (w_planes must be 0 or 1)",
+                                 "needs fp32 activation tiles in and out (act_f32 = 3)");
+  if (rc != DIA_OK) return rc;
+  if (!a->W) return gf_refuse("2:4 sparse", "needs W");
   if (2 * a->KT > a->a_ktiles) return dia_fail(DIA_E_ARG, "dia_gemm: weight K exceeds the activation tiles' K");
   return DIA_OK;
 }
 
 // the launch (dia_gemm has run dia_gemm_sparse24_check and its own argument checks)
 int dia_gemm_sparse24(const dia_gemm_args* a, void* stream) {
-  const int sk = a->sk > 1 ? a->sk : 1;
-  if (sk > 1 && (!a->sk_scratch || !a->sk_tickets || a->KT % sk != 0)) return dia_fail(DIA_E_ARG, "dia_gemm: split-K needs sk_scratch, sk_tickets and KT % sk == 0");
-  const int ktw = a->KT / sk;                          // sparse k-tiles per workgroup
+  const int rc = gf_check_splitk(a);
+  if (rc != DIA_OK) return rc;
+  const auto [sk, ktw, spw] = gf_shape(a);             // ktw: sparse k-tiles per workgroup
   if (a->KT % SP_GROUP != 0 || ktw % SP_GROUP != 0)
-    return dia_fail(DIA_E_ARG, "dia_gemm: the 2:4 sparse stream needs K a multiple of 512 per workgroup (whole groups of 8 sparse k-tiles)");
+    return gf_refuse("2:4 sparse", "needs K a multiple of 512 per workgroup (whole groups of 8 sparse k-tiles)");
   GemmK k;
   fill_gemmk(a, k);
   hipStream_t st = (hipStream_t)stream;
-  int kpw = (ktw / 8 <= SP_MAXW) ? 8 : ((ktw % 16 == 0 && ktw / 16 <= SP_MAXW) ? 16 : 0);
+  int kpw = (ktw / 8 <= GF_MAXW) ? 8 : ((ktw % 16 == 0 && ktw / 16 <= GF_MAXW) ? 16 : 0);
   if (!kpw)
-    return dia_fail(DIA_E_ARG, "dia_gemm: the 2:4 sparse stream needs the sparse k-tiles per workgroup (KT / sk) to be at most 64, "
-                               "or a multiple of 16 up to 128 (K <= 8192 per workgroup; use split-K)");
+    return gf_refuse("2:4 sparse", "needs the sparse k-tiles per workgroup (KT / sk) to be at most 64, "
+                                   "or a multiple of 16 up to 128 (K <= 8192 per workgroup; use split-K)");
   const int nw = ktw / kpw;
-  const int spw = stream_spw(a->spw, a->nstrips);      // persistent form: next strip's weights in flight during this one's epilogue
   const bool image = a->M <= 4 && sp_smem(2 * ktw, 4) <= 150 * 1024;
   if (kpw == 8) return image ? launch24<8, 4>(k, nw, sk, spw, st) : launch24<8, 16>(k, nw, sk, spw, st);
   return launch24<16, 16>(k, nw, sk, 1, st);

@@ -2,12 +2,12 @@
 // as the lane-local fixed-rate stream of dia_hip/layout.py tile_weight_us (dia_gemm_args.w_format = DIA_W_USPARSE, W = a HOST
 // dia_us_mat naming the stream and its rate).  Lossless: the stream holds exactly the numbers of the dense tiles.
 //
-// A kernel of its own beside k_gemm_mx, not a third trait of it: what the two share is the frame (small operands first, every
-// weight load of a wave before its first MFMA, the LDS image of RS = 4, the wave-order sum, run_epilogue_rows), and the frame is
-// copied here at RS = 4 only.  What differs sits inside that frame's body in three places — the B fragment needs an LDS table
-// where the MX formats need a scale, a second per-strip operand (the overflow run bounds and entries) travels with the weights,
-// and a VALU pass adds into the tile between the MFMA loop and the wave sum — so a trait would have had to grow hooks at each of
-// them, and the 5..16-row forms of k_gemm_mx (RS = 16) have no counterpart here (DESIGN.md "Unstructured sparse weight stream").
+// A kernel of its own beside k_gemm_mx, not a third trait of it: what the two share is the frame, and that is gemv_frame.hpp's
+// functions, called here at RS = 4 only.  What differs sits inside the strip body in three places — the B fragment needs an LDS
+// table where the MX formats need a scale, a second per-strip operand (the overflow run bounds and entries) travels with the
+// weights, and a VALU pass adds into the tile between the wave sum and the finish — so a trait would have had to grow hooks at
+// each of them, and the 5..16-row forms of k_gemm_mx (RS = 16) have no counterpart here (DESIGN.md "Unstructured sparse weight
+// stream").
 //
 // Mapping (CDNA4): the weights stay the B operand of the dense v_mfma_f32_16x16x32_bf16 (lane l: column l & 15 of the strip,
 // K = 8 (l >> 4) + [0, 8) of the k-tile).  Per lane and k-tile the stream holds an 8-bit mask (bit j = element j is non-zero) and
@@ -24,19 +24,15 @@
 // bounds travel with the weight loads, the first PRE entries of every thread are requested before the MFMA loop.  A strip whose
 // K range has no entry at all (the range's first and last bound are equal: one pair of table words, the same for every thread)
 // skips the pass, its LDS exchange and its sum.
-#include "gemm_common.hpp"
-#include <cstdio>
+#include "gemv_frame.hpp"
 
 namespace {
 
 constexpr int US_GROUP = 16;                       // k-tiles per stream group (layout.US_GROUP)
-constexpr int US_MAXW = 8;                         // waves per workgroup
 constexpr int US_MASK_BYTES = 1024;                // mask block of a group: [64 lanes][16 k-tiles]
 constexpr int US_SLOT_BYTES = 1024;                // one value slot: [64 lanes][16 bytes]
 constexpr int US_PRE = 4;                          // overflow entries per thread requested before the MFMA loop
-constexpr int US_OSLOTS = US_MAXW * 4;             // threads per column in the overflow pass, at most
-
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+constexpr int US_OSLOTS = GF_MAXW * 4;             // threads per column in the overflow pass, at most
 
 constexpr int us_group_bytes(int rate) { return US_MASK_BYTES + rate * 2 * US_SLOT_BYTES; }
 static_assert(us_group_bytes(4) == 9216 && us_group_bytes(2) == 5120, "the group sizes of dia_hip/layout.py");
@@ -47,15 +43,11 @@ struct UsK {
   const unsigned* oent;      // overflow entries
 };
 
-// LDS: wave partial tiles [2][US_MAXW][64] f32x4, split-K tile [16][17], row scales [16], overflow sums [2][US_OSLOTS][4][16],
-// selector table [256] u32x4, then the activation image [3 planes][k-tile][quarter][4 rows] bf16x8
-constexpr size_t us_smem_fixed() {
-  return sizeof(f32x4) * 2 * US_MAXW * 64 + sizeof(float) * (16 * 17 + 16) + sizeof(float) * 2 * US_OSLOTS * 64 + sizeof(u32x4) * 256;
-}
-size_t us_smem(int ktw) { return us_smem_fixed() + (size_t)DIA_NPLANES * ktw * 4 * 4 * 16; }
+// LDS behind the frame's prefix: overflow sums [2][US_OSLOTS][4][16], selector table [256] u32x4, then the activation image
+size_t us_smem(int ktw) { return gf_lds_bytes() + sizeof(float) * 2 * US_OSLOTS * 64 + sizeof(u32x4) * 256 + gf_image_bytes(ktw); }
 
 template <int R, int KPW, bool MULTI>
-__global__ __launch_bounds__(US_MAXW * 64) void k_gemm_us(UsK q) {
+__global__ __launch_bounds__(GF_MAXW * 64) void k_gemm_us(UsK q) {
   static_assert((R == 4 || R == 2) && (KPW == 8 || KPW == 16), "window slots; half a stream group or a whole one per wave");
   const GemmK& p = q.g;
   constexpr int RS = 4;
@@ -65,13 +57,10 @@ __global__ __launch_bounds__(US_MAXW * 64) void k_gemm_us(UsK q) {
   constexpr int GB = us_group_bytes(R);
   constexpr int SS = 64 / KPW;                         // threads per overflow run
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  f32x4* red = reinterpret_cast<f32x4*>(smem_raw);                                   // [2][US_MAXW][64]
-  float* tile = reinterpret_cast<float*>(smem_raw + sizeof(f32x4) * 2 * US_MAXW * 64); // [16][17] (split-K hand-off)
-  float* inv_s = tile + 16 * 17;                                                     // [16]
-  float* ored = inv_s + 16;                                                          // [2][US_OSLOTS][4][16]
+  const GfLds L = gf_lds(smem_raw);
+  float* ored = reinterpret_cast<float*>(L.rest);                                    // [2][US_OSLOTS][4][16]
   u32x4* seltab = reinterpret_cast<u32x4*>(ored + 2 * US_OSLOTS * 64);               // [256]
   bf16x8* As = reinterpret_cast<bf16x8*>(seltab + 256);                              // [plane][kt][kq][row]
-  __shared__ int sk_flag;
 
   const int NT = blockDim.x, NW = NT >> 6;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -105,34 +94,13 @@ __global__ __launch_bounds__(US_MAXW * 64) void k_gemm_us(UsK q) {
 #pragma unroll
     for (int i = 0; i < NS; ++i) b[i] = DIA_WLOAD(reinterpret_cast<const u32x4*>(Wv + so + (long)i * US_SLOT_BYTES));
   };
-  const float* Af = reinterpret_cast<const float*>(p.A);
 
   // ---- small, L2-resident operands first (see k_gemv_small): activation image, row scales
-  constexpr int CE = (KPW * 4 * RS + 63) / 64;        // image entries per thread (KPW k-tiles x 4 quarters x RS rows per wave)
   const int nentries = ktw * 4 * RS;
-  float4 ex[CE], ey[CE];
-  {
-    const long kta = (long)blockIdx.y * ktw;           // first activation k-tile of the range
-#pragma unroll
-    for (int u = 0; u < CE; ++u) {
-      const int c = min(tid + u * NT, nentries - 1);
-      const int row = c % RS, kq = (c / RS) & 3, kt = c / (4 * RS);
-      const float4* src = reinterpret_cast<const float4*>(Af + ((kta + kt) * 64 + min(row, p.M - 1) + 16 * kq) * 8);
-      ex[u] = src[0]; ey[u] = src[1];
-    }
-  }
-  // row scales: 8 threads per row, 16 strip partials each requested at once on clamped addresses (as k_gemm_mx)
-  const bool has_norm = p.ssq_in != nullptr;
-  const int s_row = tid >> 3, s_part = tid & 7;
-  const bool s_thread = tid < 128 && has_norm;
+  float4 ex[gf_image_ce(KPW)], ey[gf_image_ce(KPW)];
+  gf_image_load<KPW>(p, tid, NT, ex, ey);
   float sq[16];
-#pragma unroll
-  for (int i = 0; i < 16; ++i) sq[i] = 0.f;
-  if (s_thread) {
-    const float* sp = p.ssq_in + min(s_row, p.M - 1);
-#pragma unroll
-    for (int i = 0; i < 16; ++i) sq[i] = sp[(long)min(s_part + 8 * i, p.ssq_in_n - 1) * p.ssq_ld];
-  }
+  gf_scales_load(p, tid, sq);
   __builtin_amdgcn_sched_barrier(0);
   u32x4 b0[NS], b1[MULTI ? NS : 1];
   unsigned m0[NM], m1[MULTI ? NM : 1];
@@ -158,37 +126,15 @@ __global__ __launch_bounds__(US_MAXW * 64) void k_gemm_us(UsK q) {
     }
     seltab[m] = sel;
   }
-#pragma unroll
-  for (int u = 0; u < CE; ++u)
-    if (tid + u * NT < nentries) {
-      const int c = tid + u * NT;
-      bf16x8 h, mi, lo;
-      split3x8(ex[u], ey[u], h, mi, lo);
-      As[c] = h; As[nentries + c] = mi; As[2 * nentries + c] = lo;
-    }
-  for (int t = tid; t < 128; t += NT) {              // (a one-wave workgroup also serves rows 8..15, loading them here)
-    const int r = t >> 3, part = t & 7;
-    float s0 = 0.f;
-    if (t == tid) {
-#pragma unroll
-      for (int i = 0; i < 16; ++i) s0 += (part + 8 * i < p.ssq_in_n && r < p.M) ? sq[i] : 0.f;
-      if (has_norm && r < p.M)
-        for (int i = part + 128; i < p.ssq_in_n; i += 8) s0 += p.ssq_in[(long)i * p.ssq_ld + r];   // D > 2048 only
-    } else if (has_norm && r < p.M) {
-      for (int i = part; i < p.ssq_in_n; i += 8) s0 += p.ssq_in[(long)i * p.ssq_ld + r];
-    }
-    s0 += __shfl_xor(s0, 1, 64);
-    s0 += __shfl_xor(s0, 2, 64);
-    s0 += __shfl_xor(s0, 4, 64);
-    if (part == 0) inv_s[r] = has_norm ? rsqrtf(s0 * p.inv_d + p.eps) : 1.0f;
-  }
-  lds_barrier();                                      // image, table and row scales visible; the weight loads stay in flight
+  gf_image_store<KPW>(As, tid, NT, ex, ey);
+  gf_scales_reduce(p, tid, NT, sq, L.inv_s);
+  lds_barrier();                                     // image, table and row scales visible; the weight loads stay in flight
 
   const int arow = min(lane & 15, RS - 1), akq = lane >> 4;
   const unsigned short* Ab = reinterpret_cast<const unsigned short*>(As);      // the image as bf16 bits
   const int plane_e = nentries * 8;                   // elements of one image plane
   int sbuf = 0;
-  auto body = [&](u32x4* bc, unsigned* mc, unsigned* oc, u32x4* bn, unsigned* mn, unsigned* on, int strip) {
+  auto body = [&](u32x4* bc, unsigned* mc, unsigned* oc, u32x4* bn, unsigned* mn, unsigned* on, int strip) __attribute__((always_inline)) {
     const int next = strip + G;
     if constexpr (MULTI) load_strip(bn, mn, on, DIA_PREFETCH_CLAMP(next, p.nstrips));   // unconditional: see k_gemv_small
     // this thread's overflow entries oc[0] + osub, + SS, ... below oc[1]: the first US_PRE in flight during the MFMA loop
@@ -235,56 +181,23 @@ __global__ __launch_bounds__(US_MAXW * 64) void k_gemm_us(UsK q) {
       for (int u = 0; u < US_PRE; ++u) add(en[u]);
       for (unsigned i = ob + US_PRE * SS; i < oe; i += SS) add(q.oent[i]);
     }
-    // cross-wave sum: element (row m, column c) of the output tile sits in lane 16 (m >> 2) + c, register m & 3 of every wave;
-    // the overflow sums of thread t at [t >> 4][row][column]
-    f32x4* rb = red + sbuf * (US_MAXW * 64);
+    // the overflow sums of thread t go beside the wave's tile, at [t >> 4][row][column] ...
+    f32x4* rb = L.red + sbuf * (GF_MAXW * 64);
     float* ob_s = ored + sbuf * (US_OSLOTS * 64);
     sbuf ^= 1;
-    if (lane < 16) rb[w * 64 + lane] = acc;
+    gf_tile_store<RS, false>(rb, w, lane, acc);
     if (spills) {
 #pragma unroll
       for (int m = 0; m < RS; ++m) ob_s[((tid >> 4) * RS + m) * 16 + ocol] = oa[m];
     }
     lds_barrier();
-    const bool split = !MULTI && gridDim.y > 1;
-    float vs = 0.f;
-    if (tid < 16 * RS) {
-      const int m = tid >> 4, c = tid & 15;
-      const float* rf = reinterpret_cast<const float*>(rb) + c * 4 + m;
-      float v = rf[0];
-      for (int ww = 1; ww < NW; ++ww) v += rf[ww * 256];
-      if (spills)
-        for (int r = 0; r < NW * 4; ++r) v += ob_s[(r * RS + m) * 16 + c];
-      vs = v;
-      if (split) tile[m * 17 + c] = v;
-    }
-    if (split) {            // cross-workgroup split-K (wo): the last arriver sums the slabs in split order and runs the epilogue
-      // (splitk_combine publishes all 16 rows of the tile: rows RS.. carry zeros, never read back)
-      for (int e = 16 * RS + tid; e < 256; e += NT) tile[(e >> 4) * 17 + (e & 15)] = 0.f;
-      lds_barrier();
-      if (!splitk_combine(p, tile, strip, tid, &sk_flag)) return;
-      if (tid < 16 * RS) vs = tile[(tid >> 4) * 17 + (tid & 15)];
-    }
-    if (tid < 16 * RS) {
-      float xpre1 = 0.f, gpre1 = 1.f;
-      if (p.epi == DIA_EPI_RESID_EMIT) {
-        const int m = tid >> 4, n = strip * 16 + (tid & 15);
-        xpre1 = p.out[(long)min(m, p.M - 1) * p.ldo + n];
-        gpre1 = p.gnext[n];
-      }
-      run_epilogue_rows<RS, true>(p, vs, inv_s, tid, strip, xpre1, gpre1);
-    }
+    float vs[gf_ne(RS)];                              // (one: thread t < 64 finishes row t >> 4, column t & 15)
+    gf_wave_sum<RS, false>(rb, tid, NT, vs);
+    if (spills && tid < 16 * RS)                      // ... and are added in thread order behind the waves' partial tiles
+      for (int r = 0; r < NW * 4; ++r) vs[0] += ob_s[(r * RS + (tid >> 4)) * 16 + (tid & 15)];
+    gf_finish<RS, MULTI>(p, L, vs, tid, NT, strip);
   };
-  if constexpr (MULTI) {
-    int strip = blockIdx.x;                            // strip pairs, then at most one more (see k_gemv_small)
-    for (; strip + G < p.nstrips; strip += 2 * G) {
-      body(b0, m0, o0, b1, m1, o1, strip);
-      body(b1, m1, o1, b0, m0, o0, strip + G);
-    }
-    if (strip < p.nstrips) body(b0, m0, o0, b1, m1, o1, strip);
-  } else {
-    body(b0, m0, o0, b1, m1, o1, blockIdx.x);
-  }
+  gf_strips<MULTI>(p.nstrips, [&](int strip) { body(b0, m0, o0, b1, m1, o1, strip); }, [&](int strip) { body(b1, m1, o1, b0, m0, o0, strip); });
 }
 
 template <int R, int KPW>
@@ -302,7 +215,7 @@ int launch_us(const UsK& k, int nw, int sk, int spw, hipStream_t st) {
 
 template <int R>
 int launch_us_shape(const UsK& k, int ktw, int sk, int spw, hipStream_t st) {
-  const int kpw = ktw / 8 <= US_MAXW ? 8 : 16;
+  const int kpw = ktw / 8 <= GF_MAXW ? 8 : 16;
   const int nw = ktw / kpw;
   return kpw == 8 ? launch_us<R, 8>(k, nw, sk, spw, st) : launch_us<R, 16>(k, nw, sk, 1, st);
 }
@@ -311,36 +224,25 @@ int launch_us_shape(const UsK& k, int ktw, int sk, int spw, hipStream_t st) {
 
 // dia_gemm with w_format == DIA_W_USPARSE: what the stream cannot serve (checked before dia_gemm's other weight forms)
 int dia_gemm_us_check(const dia_gemm_args* a) {
-  auto refuse = [](const char* what) {               // "dia_gemm: the unstructured sparse stream <what>" (dia_fail copies its message)
-    char msg[192];
-    snprintf(msg, sizeof msg, "dia_gemm: the unstructured sparse stream %s", what);
-    return dia_fail(DIA_E_ARG, msg);
-  };
-  if (a->w_planes > 1) return refuse("holds one weight encoding (w_planes must be 0 or 1)");
-  if (a->w_layout == 1) return refuse("has no diagonal layout (w_layout must be 0)");
-  if (a->sp_blocks || a->sp_toff) return refuse("and the zero-skipping stream (sp_blocks) exclude each other");
-  if (a->epi == DIA_EPI_CROSSKV) return refuse("has no CROSSKV epilogue (prefill only)");
-  if (a->cmap || a->strip_map) return refuse("has no compaction maps (cmap / strip_map)");
-  if (a->M > 4) return refuse("serves at most 4 rows");
-  const bool emits = a->epi == DIA_EPI_RESID_EMIT || a->epi == DIA_EPI_SWIGLU_EMIT;
-  if (!(a->act_f32 & 1) || (emits && !(a->act_f32 & 2))) return refuse("needs fp32 activation tiles in and out (act_f32 = 3), not planes");
+  const char* name = "unstructured sparse";
+  const int rc = gf_check_common(a, name, 4);
+  if (rc != DIA_OK) return rc;
   const dia_us_mat* m = static_cast<const dia_us_mat*>(a->W);
-  if (!m || !m->stream) return refuse("needs W to point to a dia_us_mat that names the stream (w_format = DIA_W_USPARSE)");
-  if (m->rate != 4 && m->rate != 2) return refuse("has windows of 4 or 2 values (dia_us_mat.rate)");
-  if (a->epi == DIA_EPI_RESID_EMIT && !a->gnext) return refuse("needs gnext with RESID_EMIT");
-  const int sk = a->sk > 1 ? a->sk : 1;
+  if (!m || !m->stream) return gf_refuse(name, "needs W to point to a dia_us_mat that names the stream (w_format = DIA_W_USPARSE)");
+  if (m->rate != 4 && m->rate != 2) return gf_refuse(name, "has windows of 4 or 2 values (dia_us_mat.rate)");
+  const int sk = gf_shape(a).sk;
   if (a->KT % US_GROUP != 0 || a->KT % sk != 0 || (a->KT / sk) % US_GROUP != 0)
-    return refuse("needs K a multiple of 512 per workgroup (whole groups of 16 k-tiles)");
-  if (a->KT / sk > 16 * US_MAXW) return refuse("serves at most 128 k-tiles per workgroup (K <= 4096; use split-K)");
+    return gf_refuse(name, "needs K a multiple of 512 per workgroup (whole groups of 16 k-tiles)");
+  if (a->KT / sk > 16 * GF_MAXW) return gf_refuse(name, "serves at most 128 k-tiles per workgroup (K <= 4096; use split-K)");
   return DIA_OK;
 }
 
 // the launch (dia_gemm has run dia_gemm_us_check and its own argument checks)
 int dia_gemm_us(const dia_gemm_args* a, void* stream) {
-  const int sk = a->sk > 1 ? a->sk : 1;
-  if (sk > 1 && (!a->sk_scratch || !a->sk_tickets)) return dia_fail(DIA_E_ARG, "dia_gemm: split-K needs sk_scratch, sk_tickets and KT % sk == 0");
+  const int rc = gf_check_splitk(a);
+  if (rc != DIA_OK) return rc;
   const dia_us_mat* m = static_cast<const dia_us_mat*>(a->W);
-  const int ktw = a->KT / sk;                          // k-tiles per workgroup
+  const auto [sk, ktw, spw] = gf_shape(a);
   UsK k;
   fill_gemmk(a, k.g);
   // the three parts of the stream (layout.tile_weight_us): fixed part, run table (padded to 16 bytes), overflow entries
@@ -351,6 +253,5 @@ int dia_gemm_us(const dia_gemm_args* a, void* stream) {
   k.otab = reinterpret_cast<const unsigned*>(base + tab_off);
   k.oent = reinterpret_cast<const unsigned*>(base + tab_off + (4 * (runs + 1) + 15) / 16 * 16);
   hipStream_t st = (hipStream_t)stream;
-  const int spw = stream_spw(a->spw, a->nstrips);      // persistent form: next strip's weights in flight during this one's epilogue
   return m->rate == 4 ? launch_us_shape<4>(k, ktw, sk, spw, st) : launch_us_shape<2>(k, ktw, sk, spw, st);
 }

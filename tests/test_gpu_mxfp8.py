@@ -25,7 +25,7 @@ def dev():
     return torch.device("cuda:0")
 
 
-def gemm(X, w, epi, *, fp8, sk=None, ssq=True, x0=None, gnext=None, spw=0, expect=hb.check):
+def gemm(X, w, epi, *, fp8, sk=None, ssq=True, x0=None, gnext=None, spw=0, expect=hb.check, ssq_n=8):
     """one dia_gemm launch with fp32 activation tiles in and out; returns (out, emitted activations [M, width], ssq_out, ssq_in)"""
     d = dev()
     M, K = X.shape
@@ -43,8 +43,8 @@ def gemm(X, w, epi, *, fp8, sk=None, ssq=True, x0=None, gnext=None, spw=0, expec
     keep = [A, Wt]
     sin = None
     if ssq:
-        sin = (torch.rand(8, ssq_ld, generator=torch.Generator().manual_seed(M + K)) + 0.5).to(d)
-        g.ssq_in, g.ssq_in_n, g.inv_d, g.eps = hb.ptr(sin), 8, 1.0 / 64, 1e-5
+        sin = (torch.rand(ssq_n, ssq_ld, generator=torch.Generator().manual_seed(M + K)) + 0.5).to(d)
+        g.ssq_in, g.ssq_in_n, g.inv_d, g.eps = hb.ptr(sin), ssq_n, 1.0 / (8 * ssq_n), 1e-5
     g.ssq_ld = ssq_ld
     out = P = sso = None
     if epi == hb.EPI_SCALE_STORE:
@@ -86,7 +86,7 @@ def reference(X, w, epi, sin=None, x0=None, gnext=None):
     M = X.shape[0]
     inv = torch.ones(M, dtype=torch.float64)
     if sin is not None:
-        inv = torch.rsqrt(sin[:, :M].double().sum(dim=0) / 64 + 1e-5)
+        inv = torch.rsqrt(sin[:, :M].double().sum(dim=0) / (8 * sin.shape[0]) + 1e-5)
     acc = X64 @ W64
     if epi == hb.EPI_SCALE_STORE:
         return acc * inv[:, None], None, None
@@ -106,7 +106,7 @@ def check_close(got, want, what, tol=TOL):
     assert err <= tol * scale, (what, err, scale)
 
 
-def case(M, K, N, epi, seed, sk=None, spw=0):
+def case(M, K, N, epi, seed, sk=None, spw=0, ssq_n=8):
     gen = torch.Generator().manual_seed(seed)
     X = torch.randn(M, K, generator=gen)
     w = torch.randn(K, N, generator=gen) * 0.05
@@ -118,8 +118,8 @@ def case(M, K, N, epi, seed, sk=None, spw=0):
     x0 = torch.randn(M, Np, generator=gen) if epi == hb.EPI_RESID_EMIT else None
     gn = (torch.rand(Np, generator=gen) + 0.5) if epi == hb.EPI_RESID_EMIT else None
     ssq = epi != hb.EPI_RESID_EMIT
-    f8 = gemm(X, w, epi, fp8=True, sk=sk, ssq=ssq, x0=x0, gnext=gn, spw=spw)
-    dn = gemm(X, w, epi, fp8=False, sk=sk, ssq=ssq, x0=x0, gnext=gn, spw=spw)
+    f8 = gemm(X, w, epi, fp8=True, sk=sk, ssq=ssq, x0=x0, gnext=gn, spw=spw, ssq_n=ssq_n)
+    dn = gemm(X, w, epi, fp8=False, sk=sk, ssq=ssq, x0=x0, gnext=gn, spw=spw, ssq_n=ssq_n)
     wp = torch.zeros(K, Np)
     wp[:, :N] = w
     ro, re, rs = reference(X, wp, epi, sin=f8[3], x0=x0, gnext=gn)
@@ -172,6 +172,12 @@ def test_mxfp8_logits_shape(M):
 def test_mxfp8_wi_persistent_form(M):
     """wi: 1024 strips (4 strips per workgroup, next strip prefetched), SWIGLU_EMIT"""
     case(M, 2048, 16384, hb.EPI_SWIGLU_EMIT, seed=99 + M)
+
+
+def test_mxfp8_row_scales_past_128_partials():
+    """ssq_in_n = 136 (D = 2176): the row-scale reduction's tail loop behind the 16 partials a thread requests at once (the MX
+    kernel has at least two waves, so no thread serves a second row: that branch runs in the 2:4 kernel's K = 512 cases)"""
+    case(3, 512, 256, hb.EPI_SCALE_STORE, seed=136, ssq_n=136)
 
 
 def test_mxfp8_rejections():

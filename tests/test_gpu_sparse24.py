@@ -30,7 +30,7 @@ def prune24(w):
     return (g * keep).reshape(K, N).bfloat16().float()
 
 
-def gemm(X, w, epi, *, sparse, sk=None, ssq=True, x0=None, gnext=None, spw=0, expect=hb.check):
+def gemm(X, w, epi, *, sparse, sk=None, ssq=True, x0=None, gnext=None, spw=0, expect=hb.check, ssq_n=8):
     """one dia_gemm launch with fp32 activation tiles in and out; returns (out, emitted activations [M, width], ssq_out)"""
     d = dev()
     M, K = X.shape
@@ -51,8 +51,8 @@ def gemm(X, w, epi, *, sparse, sk=None, ssq=True, x0=None, gnext=None, spw=0, ex
     ssq_ld = 16
     keep = [A, Wt]
     if ssq:
-        sin = (torch.rand(8, ssq_ld, generator=torch.Generator().manual_seed(M + K)) + 0.5).to(d)
-        g.ssq_in, g.ssq_in_n, g.ssq_ld, g.inv_d, g.eps = hb.ptr(sin), 8, ssq_ld, 1.0 / 64, 1e-5
+        sin = (torch.rand(ssq_n, ssq_ld, generator=torch.Generator().manual_seed(M + K)) + 0.5).to(d)
+        g.ssq_in, g.ssq_in_n, g.ssq_ld, g.inv_d, g.eps = hb.ptr(sin), ssq_n, ssq_ld, 1.0 / (8 * ssq_n), 1e-5
         keep.append(sin)
     g.ssq_ld = ssq_ld
     out = P = sso = None
@@ -94,7 +94,7 @@ def reference(X, w, epi, sin=None, x0=None, gnext=None):
     M = X.shape[0]
     inv = torch.ones(M, dtype=torch.float64)
     if sin is not None:
-        inv = torch.rsqrt(sin[:, :M].double().sum(dim=0) / 64 + 1e-5)
+        inv = torch.rsqrt(sin[:, :M].double().sum(dim=0) / (8 * sin.shape[0]) + 1e-5)
     acc = X64 @ W64
     if epi == hb.EPI_SCALE_STORE:
         return acc * inv[:, None], None, None
@@ -113,7 +113,7 @@ def check_close(got, want, tol=2e-5):
     assert err <= tol * scale, (err, scale)
 
 
-def case(M, K, N, epi, seed, sk=None, spw=0):
+def case(M, K, N, epi, seed, sk=None, spw=0, ssq_n=8):
     gen = torch.Generator().manual_seed(seed)
     X = torch.randn(M, K, generator=gen)
     w = prune24(torch.randn(K, N, generator=gen) * 0.05)
@@ -121,8 +121,8 @@ def case(M, K, N, epi, seed, sk=None, spw=0):
     x0 = torch.randn(M, (N + 15) // 16 * 16, generator=gen) if epi == hb.EPI_RESID_EMIT else None
     gn = (torch.rand(N, generator=gen) + 0.5) if epi == hb.EPI_RESID_EMIT else None
     ssq = epi != hb.EPI_RESID_EMIT
-    sp = gemm(X, w, epi, sparse=True, sk=sk, ssq=ssq, x0=x0, gnext=gn, spw=spw)
-    dn = gemm(X, w, epi, sparse=False, sk=sk, ssq=ssq, x0=x0, gnext=gn, spw=spw)
+    sp = gemm(X, w, epi, sparse=True, sk=sk, ssq=ssq, x0=x0, gnext=gn, spw=spw, ssq_n=ssq_n)
+    dn = gemm(X, w, epi, sparse=False, sk=sk, ssq=ssq, x0=x0, gnext=gn, spw=spw, ssq_n=ssq_n)
     ro, re, rs = reference(X, w, epi, sin=sp[3], x0=x0, gnext=gn)
     if ro is not None:
         check_close(sp[0][:, :N], ro[:, :N])
@@ -178,6 +178,13 @@ def test_sparse_logits_shape(M):
 def test_sparse_wi_persistent_form():
     """wi: 1024 strips at batch 1 (4 strips per workgroup, next strip prefetched), SWIGLU_EMIT"""
     case(2, 2048, 16384, hb.EPI_SWIGLU_EMIT, seed=99)
+
+
+def test_sparse_row_scales_past_128_partials():
+    """ssq_in_n = 136 (D = 2176): the row-scale reduction's tail loop behind the 16 partials a thread requests at once, in a
+    one-wave workgroup (K = 512), whose threads also serve rows 8..15 (the M = 16, K = 512 cases above run that branch with
+    ssq_in present and every row live)"""
+    case(3, 512, 256, hb.EPI_SCALE_STORE, seed=136, ssq_n=136)
 
 
 def test_sparse_rejections():

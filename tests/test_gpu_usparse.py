@@ -24,7 +24,7 @@ def dev():
     return torch.device("cuda:0")
 
 
-def gemm(X, w, epi, *, rate, sk=None, ssq=True, x0=None, gnext=None, spw=0):
+def gemm(X, w, epi, *, rate, sk=None, ssq=True, x0=None, gnext=None, spw=0, ssq_n=8):
     """one dia_gemm launch with fp32 activation tiles in and out (rate 0: the dense tiles); returns (out, emitted activations
     [M, width], ssq_out, ssq_in)"""
     d = dev()
@@ -45,8 +45,8 @@ def gemm(X, w, epi, *, rate, sk=None, ssq=True, x0=None, gnext=None, spw=0):
     keep = [A, Wt, um]
     sin = None
     if ssq:
-        sin = (torch.rand(8, ssq_ld, generator=torch.Generator().manual_seed(M + K)) + 0.5).to(d)
-        g.ssq_in, g.ssq_in_n, g.inv_d, g.eps = hb.ptr(sin), 8, 1.0 / 64, 1e-5
+        sin = (torch.rand(ssq_n, ssq_ld, generator=torch.Generator().manual_seed(M + K)) + 0.5).to(d)
+        g.ssq_in, g.ssq_in_n, g.inv_d, g.eps = hb.ptr(sin), ssq_n, 1.0 / (8 * ssq_n), 1e-5
     g.ssq_ld = ssq_ld
     out = P = sso = None
     if epi == hb.EPI_SCALE_STORE:
@@ -87,7 +87,7 @@ def reference(X, w, epi, sin=None, x0=None, gnext=None):
     M = X.shape[0]
     inv = torch.ones(M, dtype=torch.float64)
     if sin is not None:
-        inv = torch.rsqrt(sin[:, :M].double().sum(dim=0) / 64 + 1e-5)
+        inv = torch.rsqrt(sin[:, :M].double().sum(dim=0) / (8 * sin.shape[0]) + 1e-5)
     acc = X64 @ W64
     if epi == hb.EPI_SCALE_STORE:
         return acc * inv[:, None], None, None
@@ -113,7 +113,7 @@ def pruned(K, N, zeros, gen):
     return w * (torch.rand(K, N, generator=gen) >= zeros)
 
 
-def case(M, K, N, epi, seed, zeros, sk=None, spw=0, rates=(4, 2)):
+def case(M, K, N, epi, seed, zeros, sk=None, spw=0, rates=(4, 2), ssq_n=8):
     gen = torch.Generator().manual_seed(seed)
     X = torch.randn(M, K, generator=gen)
     w = pruned(K, N, zeros, gen)
@@ -124,13 +124,13 @@ def case(M, K, N, epi, seed, zeros, sk=None, spw=0, rates=(4, 2)):
     x0 = torch.randn(M, Np, generator=gen) if epi == hb.EPI_RESID_EMIT else None
     gn = (torch.rand(Np, generator=gen) + 0.5) if epi == hb.EPI_RESID_EMIT else None
     ssq = epi != hb.EPI_RESID_EMIT
-    dn = gemm(X, w, epi, rate=0, sk=sk, ssq=ssq, x0=x0, gnext=gn, spw=spw)
+    dn = gemm(X, w, epi, rate=0, sk=sk, ssq=ssq, x0=x0, gnext=gn, spw=spw, ssq_n=ssq_n)
     wp = torch.zeros(K, Np)
     wp[:, :N] = w
     ro, re, rs = reference(X, wp, epi, sin=dn[3], x0=x0, gnext=gn)
     for rate in rates:
-        us = gemm(X, w, epi, rate=rate, sk=sk, ssq=ssq, x0=x0, gnext=gn, spw=spw)
-        again = gemm(X, w, epi, rate=rate, sk=sk, ssq=ssq, x0=x0, gnext=gn, spw=spw)
+        us = gemm(X, w, epi, rate=rate, sk=sk, ssq=ssq, x0=x0, gnext=gn, spw=spw, ssq_n=ssq_n)
+        again = gemm(X, w, epi, rate=rate, sk=sk, ssq=ssq, x0=x0, gnext=gn, spw=spw, ssq_n=ssq_n)
         for a, b in zip(us[:3], again[:3]):                 # fixed summation order: the same bits on every call
             assert (a is None and b is None) or torch.equal(a, b)
         if ro is not None:
@@ -202,6 +202,12 @@ def test_usparse_wi_persistent_form():
 def test_usparse_fully_dense_matrix(K):
     """maximal overflow: every lane-tile spills 8 - R values (the loop behind the prefetched entries runs)"""
     case(4, K, 48, hb.EPI_SCALE_STORE, seed=K + 3, zeros=0.0)
+
+
+def test_usparse_row_scales_past_128_partials():
+    """ssq_in_n = 136 (D = 2176): the row-scale reduction's tail loop behind the 16 partials a thread requests at once (the
+    kernel has at least two waves, so no thread serves a second row)"""
+    case(3, 512, 256, hb.EPI_SCALE_STORE, seed=136, zeros=0.6, rates=(4,), ssq_n=136)
 
 
 def test_usparse_rejections():
