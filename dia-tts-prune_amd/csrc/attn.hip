@@ -58,11 +58,15 @@ __device__ long long g_astamps[8192 * 8];
 
 // Shared tail of both attention kernels: merge the NWV per-wave partials (LDS, fixed order), then —
 // when the pair was split over several workgroups — publish to the slab, take a ticket, and let the
-// last arriver merge all splits in split order; finally normalise and emit the planes.
-template <int G>
+// last arriver merge all splits in split order; finally normalise and emit the planes.  MERGE = false (a form whose keys
+// never leave one workgroup, nchunks == 1 by construction): no slab, no ticket, last_s_ptr unused.
+// Rounding order of the wave merge: FUSED < 0 leaves it to the compiler's contraction, which is what every kernel here had when its
+// bits were pinned.  A form whose tail compiles in another context says the order of the body it replaces (read from that body's ISA, as
+// attn_tile_merge_emit does): the softmax sum by a rounded product and a rounded add, dims 0..FUSED-1 of a thread's eight by fused
+// multiply-add, the rest like the sum.
+template <int G, bool MERGE = true, int FUSED = -1>
 __device__ __forceinline__ void attn_finish(const AttnK& p, const float* part, const float* pm_s, const float* pl_s,
                                             int* last_s_ptr, int tid, int qrow, int kvh, int head_row, int chunk, int nchunks) {
-  int& last_s = *last_s_ptr;
   // ---- G*16 threads own 8 output dims each ------------------------------------------------------------
   const bool o_thread = tid < G * 16;
   const int og = tid >> 4, od0 = (tid & 15) * 8;
@@ -79,14 +83,23 @@ __device__ __forceinline__ void attn_finish(const AttnK& p, const float* part, c
     for (int ww = 0; ww < NWV; ++ww) {
       const float pmw = pm_s[ww * 8 + og];
       const float f = (pmw == -INFINITY) ? 0.f : expf(pmw - mm);
-      L2 += pl_s[ww * 8 + og] * f;
+      if constexpr (FUSED < 0) {
+        L2 += pl_s[ww * 8 + og] * f;
 #pragma unroll
-      for (int j = 0; j < 8; ++j) o[j] += part[(ww * G + og) * HD + od0 + j] * f;
+        for (int j = 0; j < 8; ++j) o[j] += part[(ww * G + og) * HD + od0 + j] * f;
+      } else {
+        L2 = add_rn(L2, mul_rn(pl_s[ww * 8 + og], f));
+#pragma unroll
+        for (int j = 0; j < FUSED; ++j) o[j] = __builtin_fmaf(part[(ww * G + og) * HD + od0 + j], f, o[j]);
+#pragma unroll
+        for (int j = FUSED; j < 8; ++j) o[j] = add_rn(o[j], mul_rn(part[(ww * G + og) * HD + od0 + j], f));
+      }
     }
     M = mm; Lsum = L2;
   }
 
-  if (nchunks > 1) {
+  if (MERGE && nchunks > 1) {
+    int& last_s = *last_s_ptr;
     // Publish this chunk's slab, take a ticket; the last arriver merges.  The hand-off uses agent-scope
     // RELAXED atomics (sc1 stores/loads: written through to / read from the device coherence point) with the
     // ordering made explicit — stores acknowledged (vmcnt 0) before the ticket is taken, slab loads issued
@@ -396,6 +409,226 @@ __global__ __launch_bounds__(NT) void k_attn(AttnK p) {
 template <int G, int PL>
 struct MfmaFrag { bf16x8 kb[PL][2][4]; bf16x8 vb[PL][8]; };
 
+// ---- the stages of k_attn_mfma, ONE spelling each: the generic kernel and its one-shape forms (below) are put together from
+// them, so that a form rounds like the generic body by construction.  Lane roles: arow = lane & 15, akq = lane >> 4.
+// a pointer that went through an asm operand has lost its address space: said again, the load is a global one (a flat load counts on
+// both wait counters and would wait behind the K/V requests)
+using gfloat = __attribute__((address_space(1))) float;
+template <int G> using AttnQf = bf16_raw[4][DIA_NPLANES][G][4][8];      // q planes in A-fragment order
+using AttnPbuf = bf16_raw[2][16][32];                                   // one wave's p planes (hi, lo) of the current granule
+template <int PL> using AttnNew = bf16_raw[PL][HD];                     // the owner wave's LDS copy of the k / v it appends
+
+// where the (row, kv head) pair's keys are and which granules this wave takes: g_first, g_first + gstride, ... < ngran
+struct AttnKeys { bf16_raw* Kc; bf16_raw* Vc; long plane_stride; int nkeys, klast, ngran, g_first, gstride; };
+
+// q staging + RoPE: wave w < G ropes dims lane, lane + 64 of head w -> three bf16 planes in LDS
+// (dim D of head w -> k-step D>>5, lane quarter (D>>3)&3, element D&7 of row w)
+template <int G>
+__device__ __forceinline__ void attn_stage_q(AttnQf<G>& qf, int w, int lane, float qx1, float qx2, float rc, float rs) {
+  if (w < G) {
+    const float qv[2] = {qx1 * rc - qx2 * rs, qx1 * rs + qx2 * rc};
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+      const int D = lane + 64 * e;
+      __bf16 a, b, c;
+      split3(qv[e], a, b, c);
+      qf[D >> 5][0][w][(D >> 3) & 3][D & 7] = *reinterpret_cast<const bf16_raw*>(&a);
+      qf[D >> 5][1][w][(D >> 3) & 3][D & 7] = *reinterpret_cast<const bf16_raw*>(&b);
+      qf[D >> 5][2][w][(D >> 3) & 3][D & 7] = *reinterpret_cast<const bf16_raw*>(&c);
+    }
+  }
+}
+
+// granule load: the 32 keys of granule gi as K fragments (rows clamped to the last key) and the blocked V granule
+template <int G, int PL>
+__device__ __forceinline__ void attn_load_gran(MfmaFrag<G, PL>& f, const AttnKeys& kk, int gi, int arow, int akq) {
+  const int key0 = gi << 5;
+  // all K planes first (S = Q.K^T runs before P.V, and vmcnt retires in order), then the V planes
+#pragma unroll
+  for (int pl = 0; pl < PL; ++pl) {
+    const bf16_raw* Kp = kk.Kc + pl * kk.plane_stride;
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks)
+        f.kb[pl][t][ks] = KVLOAD(reinterpret_cast<const bf16x8*>(Kp + (long)min(key0 + 16 * t + arow, kk.klast) * HD + 32 * ks + 8 * akq));
+  }
+#pragma unroll
+  for (int pl = 0; pl < PL; ++pl) {
+    const bf16_raw* Vblk = kk.Vc + pl * kk.plane_stride + (long)gi * HD * 32;
+#pragma unroll
+    for (int nb = 0; nb < 8; ++nb) f.vb[pl][nb] = KVLOAD(reinterpret_cast<const bf16x8*>(Vblk + (long)(16 * nb + arow) * 32 + 8 * akq));
+  }
+}
+
+// the append of the wave that owns the new slot's granule (SELF): RoPE(k), k into the row layout and v into the blocked layout,
+// and a bf16 copy of both in LDS for the wave's own fragments.  k dims lane, lane + 64 (roped); v dims lane, lane + 64
+template <int PL>
+__device__ __forceinline__ void attn_append(AttnNew<PL>& knew_s, AttnNew<PL>& vnew_s, const AttnKeys& kk, int slot, int lane,
+                                            float kx1, float kx2, float vx1, float vx2, float rc, float rs) {
+  const int gslot = slot >> 5;
+  float kv4[4] = {kx1 * rc - kx2 * rs, kx1 * rs + kx2 * rc, vx1, vx2};
+#pragma unroll
+  for (int pl = 0; pl < PL; ++pl) {       // plane pl = bf16 of what the planes before it left over (hi, then lo)
+    bf16_raw r4[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const __bf16 b = (__bf16)kv4[e];
+      r4[e] = *reinterpret_cast<const bf16_raw*>(&b);
+      kv4[e] -= (float)b;
+    }
+    knew_s[pl][lane] = r4[0]; knew_s[pl][lane + 64] = r4[1]; vnew_s[pl][lane] = r4[2]; vnew_s[pl][lane + 64] = r4[3];
+    bf16_raw* Kp = kk.Kc + pl * kk.plane_stride;
+    Kp[(long)slot * HD + lane] = r4[0]; Kp[(long)slot * HD + lane + 64] = r4[1];
+    bf16_raw* vdst = kk.Vc + pl * kk.plane_stride + (long)gslot * HD * 32 + (slot & 31);
+    vdst[(long)lane * 32] = r4[2]; vdst[(long)(lane + 64) * 32] = r4[3];
+  }
+}
+
+// one granule of the trip: S = Q.K^T, the online softmax step, O += P.V.  APPEND: the owner wave takes the fragments of the slot
+// written this step from its LDS copy (knew_s / vnew_s; without APPEND they are not there and owner / slot are not read).
+template <int G, int PL, bool APPEND>
+__device__ __forceinline__ void attn_consume(MfmaFrag<G, PL>& f, int gi, const AttnQf<G>& qf, AttnPbuf& pb, const AttnNew<PL>* knew_p, const AttnNew<PL>* vnew_p,
+                                             bool owner, int slot, int nkeys, int lane, f32x4 (&O)[8], float (&mrun)[4], float (&lrun)[4]) {
+  const int arow = lane & 15, akq = lane >> 4;
+  const int qrow_l = min(arow, G - 1);        // q fragments are re-read from LDS per k-step (rows >= G alias row G-1: their score rows are unused)
+  const float scale = 0.08838834764831845f;
+  const int key0 = gi << 5;
+  if constexpr (APPEND) {
+    if (owner && gi == (slot >> 5)) {                 // the slot written this step: fragments from the LDS copy
+      const AttnNew<PL>& knew_s = *knew_p;
+      const AttnNew<PL>& vnew_s = *vnew_p;
+      const int ts = (slot >> 4) & 1, ns = slot & 15, js = slot & 7, kqs = (slot & 31) >> 3;
+#pragma unroll
+      for (int pl = 0; pl < PL; ++pl) {
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) {
+          const bf16x8 kn = *reinterpret_cast<const bf16x8*>(&knew_s[pl][32 * ks + 8 * akq]);
+#pragma unroll
+          for (int t = 0; t < 2; ++t)
+            if (t == ts && arow == ns) f.kb[pl][t][ks] = kn;
+        }
+#pragma unroll
+        for (int nb = 0; nb < 8; ++nb) {
+          const bf16_raw vr = vnew_s[pl][16 * nb + arow];
+          const __bf16 vn = *reinterpret_cast<const __bf16*>(&vr);
+#pragma unroll
+          for (int j = 0; j < 8; ++j)
+            if (j == js && akq == kqs) f.vb[pl][nb][j] = vn;
+        }
+      }
+    }
+  }
+  f32x4 S[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
+#pragma unroll
+  for (int ks = 0; ks < 4; ++ks)
+#pragma unroll
+    for (int pl = 0; pl < DIA_NPLANES; ++pl) {
+      const bf16x8 qa = *reinterpret_cast<const bf16x8*>(&qf[ks][pl][qrow_l][akq][0]);
+      // two K planes: q_hi.(K_hi + K_lo) + q_mid.K_hi — the products left out (q_mid.K_lo, q_lo.K) are below 2^-16 of the
+      // score, the resolution two K planes have anyway; one plane: all three q planes (exact q against bf16 K)
+#pragma unroll
+      for (int kp = 0; kp < PL; ++kp) {
+        if (PL == 2 && (pl + kp > 1)) continue;
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+          S[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qa, f.kb[kp][t][ks], S[t], 0, 0, 0);
+      }
+    }
+  // online softmax: in lanes 0..15, S[t][g] is the score of head g against key key0 + 16t + lane
+  float alpha[4];
+  const bool v0 = key0 + arow < nkeys, v1 = key0 + 16 + arow < nkeys;
+#pragma unroll
+  for (int g = 0; g < G; ++g) {
+    const float s0 = v0 ? S[0][g] * scale : -INFINITY, s1 = v1 ? S[1][g] * scale : -INFINITY;
+    const float mnew = fmaxf(mrun[g], row16_max(fmaxf(s0, s1)));
+    alpha[g] = (mrun[g] == -INFINITY) ? 0.f : __expf(mrun[g] - mnew);
+    const float p0 = (s0 == -INFINITY) ? 0.f : __expf(s0 - mnew), p1 = (s1 == -INFINITY) ? 0.f : __expf(s1 - mnew);
+    lrun[g] = lrun[g] * alpha[g] + row16_sum(p0 + p1);
+    mrun[g] = mnew;
+    if (lane < 16) {      // p -> LDS as hi + lo bf16, [plane][head][key]
+      const __bf16 h0 = (__bf16)p0, h1 = (__bf16)p1;
+      const __bf16 l0 = (__bf16)(p0 - (float)h0), l1 = (__bf16)(p1 - (float)h1);
+      pb[0][g][lane] = *reinterpret_cast<const bf16_raw*>(&h0);
+      pb[0][g][16 + lane] = *reinterpret_cast<const bf16_raw*>(&h1);
+      pb[1][g][lane] = *reinterpret_cast<const bf16_raw*>(&l0);
+      pb[1][g][16 + lane] = *reinterpret_cast<const bf16_raw*>(&l1);
+    }
+  }
+  __builtin_amdgcn_wave_barrier();
+  // rescale what is accumulated (register r of lanes 0..15 = head r)
+#pragma unroll
+  for (int nb = 0; nb < 8; ++nb)
+#pragma unroll
+    for (int g = 0; g < G; ++g) O[nb][g] *= alpha[g];
+  const bf16x8 pa0 = *reinterpret_cast<const bf16x8*>(&pb[0][arow][8 * akq]);
+  const bf16x8 pa1 = *reinterpret_cast<const bf16x8*>(&pb[1][arow][8 * akq]);
+#pragma unroll
+  for (int nb = 0; nb < 8; ++nb)
+#pragma unroll
+    for (int vp = 0; vp < PL; ++vp) {
+      O[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pa0, f.vb[vp][nb], O[nb], 0, 0, 0);
+      if (vp == 0) O[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pa1, f.vb[vp][nb], O[nb], 0, 0, 0);     // (p_lo.V_lo: below 2^-16)
+    }
+  __builtin_amdgcn_wave_barrier();     // pbuf is rewritten by the next granule
+}
+
+// the trip over this wave's granules; fa holds granule g_first (requested in the prologue).  Two granules per trip: the other
+// register set is loading while one is consumed.  Steady state first — three granules known to exist, NO branch around a prefetch:
+// behind an `if` the waits of the consuming MFMAs have to serve the path without the new loads too, the compiler then counts as
+// if they had not been issued and every granule waited for the one requested just before it (no overlap at all; the GEMM kernels
+// had the same: gemm.hip DIA_PREFETCH_CLAMP) — then a tail of at most two granules in the old, branchy form.
+// (fb: one-plane caches only — two planes take the registers of both buffers)
+// STEADY = false: the caller knows that no wave has more than two granules (at most 2 * 4 granules in one workgroup).
+template <int G, int PL, bool APPEND, bool STEADY = true>
+__device__ __forceinline__ void attn_trip(MfmaFrag<G, PL>& fa, const AttnKeys& kk, const AttnQf<G>& qf, AttnPbuf& pb, const AttnNew<PL>* knew_p, const AttnNew<PL>* vnew_p,
+                                          bool owner, int slot, int lane, f32x4 (&O)[8], float (&mrun)[4], float (&lrun)[4]) {
+  const int arow = lane & 15, akq = lane >> 4;
+  const int ngran = kk.ngran, gstride = kk.gstride, g_first = kk.g_first;
+#pragma unroll
+  for (int nb = 0; nb < 8; ++nb) O[nb] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int g = 0; g < 4; ++g) { mrun[g] = -INFINITY; lrun[g] = 0.f; }
+  auto consume = [&](MfmaFrag<G, PL>& f, int gi) { attn_consume<G, PL, APPEND>(f, gi, qf, pb, knew_p, vnew_p, owner, slot, kk.nkeys, lane, O, mrun, lrun); };
+  if constexpr (PL == 1) {
+    MfmaFrag<G, PL> fb;
+    int gi = g_first;
+    if constexpr (STEADY)
+      for (; gi + 2 * gstride < ngran; gi += 2 * gstride) {
+        attn_load_gran(fb, kk, gi + gstride, arow, akq);
+        consume(fa, gi);
+        attn_load_gran(fa, kk, gi + 2 * gstride, arow, akq);
+        consume(fb, gi + gstride);
+      }
+    if (gi < ngran) {                // fa holds granule gi
+      const int g1 = gi + gstride;
+      if (g1 < ngran) attn_load_gran(fb, kk, g1, arow, akq);
+      consume(fa, gi);
+      if (g1 < ngran) consume(fb, g1);
+    }
+  } else {
+    for (int gi = g_first; gi < ngran; gi += gstride) {
+      if (gi != g_first) attn_load_gran(fa, kk, gi, arow, akq);
+      consume(fa, gi);
+    }
+  }
+}
+
+// in-workgroup wave merge, first half: every wave's partial -> LDS (lanes 0..15: dim 16*nb + lane, register g = head); attn_finish
+// sums them in wave order behind the barrier
+template <int G>
+__device__ __forceinline__ void attn_wave_parts(float* part, float* pm_s, float* pl_s, int w, int lane, const f32x4 (&O)[8], const float (&mrun)[4], const float (&lrun)[4]) {
+  if (lane < 16) {
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+#pragma unroll
+      for (int nb = 0; nb < 8; ++nb) part[(w * G + g) * HD + 16 * nb + lane] = O[nb][g];
+      if (lane == 0) { pm_s[w * 8 + g] = mrun[g]; pl_s[w * 8 + g] = lrun[g]; }
+    }
+  }
+  __syncthreads();
+}
+
 template <int G, int PL = 1>
 __global__ __launch_bounds__(NT, 2) void k_attn_mfma(AttnK p) {
   __shared__ __attribute__((aligned(16))) bf16_raw qf[4][DIA_NPLANES][G][4][8];   // q planes in A-fragment order
@@ -450,192 +683,158 @@ __global__ __launch_bounds__(NT, 2) void k_attn_mfma(AttnK p) {
   const int klast = max(nkeys - 1, 0);
   const int gstride = NWV * nchunks;
   const int g_first = chunk * NWV + w;
-  auto load_gran = [&](MfmaFrag<G, PL>& f, int gi) {
-    const int key0 = gi << 5;
-    // all K planes first (S = Q.K^T runs before P.V, and vmcnt retires in order), then the V planes
-#pragma unroll
-    for (int pl = 0; pl < PL; ++pl) {
-      const bf16_raw* Kp = Kc + pl * p.kv_plane_stride;
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks)
-          f.kb[pl][t][ks] = KVLOAD(reinterpret_cast<const bf16x8*>(Kp + (long)min(key0 + 16 * t + arow, klast) * HD + 32 * ks + 8 * akq));
-    }
-#pragma unroll
-    for (int pl = 0; pl < PL; ++pl) {
-      const bf16_raw* Vblk = Vc + pl * p.kv_plane_stride + (long)gi * HD * 32;
-#pragma unroll
-      for (int nb = 0; nb < 8; ++nb) f.vb[pl][nb] = KVLOAD(reinterpret_cast<const bf16x8*>(Vblk + (long)(16 * nb + arow) * 32 + 8 * akq));
-    }
-  };
-  MfmaFrag<G, PL> fa, fb;        // (fb: one-plane caches only — two planes take the registers of both buffers)
+  const AttnKeys kk = {Kc, Vc, p.kv_plane_stride, nkeys, klast, ngran, g_first, gstride};
+  MfmaFrag<G, PL> fa;
   const bool have0 = g_first < ngran;
-  load_gran(fa, have0 ? g_first : 0);          // idle waves re-read granule 0 (cache hit) and never use it
+  attn_load_gran(fa, kk, have0 ? g_first : 0, arow, akq);          // idle waves re-read granule 0 (cache hit) and never use it
 
   // ---- RoPE(q) -> LDS; the wave that owns the new slot's granule ropes k, appends k (row layout) and
   //      v (blocked layout) and keeps a bf16 copy in LDS for its own fragments
-  if (w < G) {      // dim D of head w -> k-step D>>5, lane quarter (D>>3)&3, element D&7 of row w
-    const float qv[2] = {qx1 * rc - qx2 * rs, qx1 * rs + qx2 * rc};
-#pragma unroll
-    for (int e = 0; e < 2; ++e) {
-      const int D = lane + 64 * e;
-      __bf16 a, b, c;
-      split3(qv[e], a, b, c);
-      qf[D >> 5][0][w][(D >> 3) & 3][D & 7] = *reinterpret_cast<const bf16_raw*>(&a);
-      qf[D >> 5][1][w][(D >> 3) & 3][D & 7] = *reinterpret_cast<const bf16_raw*>(&b);
-      qf[D >> 5][2][w][(D >> 3) & 3][D & 7] = *reinterpret_cast<const bf16_raw*>(&c);
-    }
-  }
+  attn_stage_q<G>(qf, w, lane, qx1, qx2, rc, rs);
   const int gslot = slot >> 5;
   const bool owner = slot >= 0 && (gslot % gstride) == g_first;      // wave-uniform
-  if (owner) {
-    float kv4[4] = {kx1 * rc - kx2 * rs, kx1 * rs + kx2 * rc, vx1, vx2};      // k dims lane, lane + 64 (roped); v dims lane, lane + 64
-#pragma unroll
-    for (int pl = 0; pl < PL; ++pl) {       // plane pl = bf16 of what the planes before it left over (hi, then lo)
-      bf16_raw r4[4];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const __bf16 b = (__bf16)kv4[e];
-        r4[e] = *reinterpret_cast<const bf16_raw*>(&b);
-        kv4[e] -= (float)b;
-      }
-      knew_s[pl][lane] = r4[0]; knew_s[pl][lane + 64] = r4[1]; vnew_s[pl][lane] = r4[2]; vnew_s[pl][lane + 64] = r4[3];
-      bf16_raw* Kp = Kc + pl * p.kv_plane_stride;
-      Kp[(long)slot * HD + lane] = r4[0]; Kp[(long)slot * HD + lane + 64] = r4[1];
-      bf16_raw* vdst = Vc + pl * p.kv_plane_stride + (long)gslot * HD * 32 + (slot & 31);
-      vdst[(long)lane * 32] = r4[2]; vdst[(long)(lane + 64) * 32] = r4[3];
-    }
-  }
+  if (owner) attn_append<PL>(knew_s, vnew_s, kk, slot, lane, kx1, kx2, vx1, vx2, rc, rs);
   lds_barrier();     // q (and the owner's k/v copy) in LDS; global loads stay in flight
   ASTAMP(2);
 
-  // q fragments are re-read from LDS per k-step (rows >= G alias row G-1: their score rows are unused)
-  const int qrow_l = min(arow, G - 1);
-  const float scale = 0.08838834764831845f;
   f32x4 O[8];
-#pragma unroll
-  for (int nb = 0; nb < 8; ++nb) O[nb] = f32x4{0.f, 0.f, 0.f, 0.f};
   float mrun[4], lrun[4];
-#pragma unroll
-  for (int g = 0; g < 4; ++g) { mrun[g] = -INFINITY; lrun[g] = 0.f; }
-
-  auto consume = [&](MfmaFrag<G, PL>& f, int gi) {
-    const int key0 = gi << 5;
-    if (owner && gi == gslot) {                 // the slot written this step: fragments from the LDS copy
-      const int ts = (slot >> 4) & 1, ns = slot & 15, js = slot & 7, kqs = (slot & 31) >> 3;
-#pragma unroll
-      for (int pl = 0; pl < PL; ++pl) {
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
-          const bf16x8 kn = *reinterpret_cast<const bf16x8*>(&knew_s[pl][32 * ks + 8 * akq]);
-#pragma unroll
-          for (int t = 0; t < 2; ++t)
-            if (t == ts && arow == ns) f.kb[pl][t][ks] = kn;
-        }
-#pragma unroll
-        for (int nb = 0; nb < 8; ++nb) {
-          const bf16_raw vr = vnew_s[pl][16 * nb + arow];
-          const __bf16 vn = *reinterpret_cast<const __bf16*>(&vr);
-#pragma unroll
-          for (int j = 0; j < 8; ++j)
-            if (j == js && akq == kqs) f.vb[pl][nb][j] = vn;
-        }
-      }
-    }
-    f32x4 S[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks)
-#pragma unroll
-      for (int pl = 0; pl < DIA_NPLANES; ++pl) {
-        const bf16x8 qa = *reinterpret_cast<const bf16x8*>(&qf[ks][pl][qrow_l][akq][0]);
-        // two K planes: q_hi.(K_hi + K_lo) + q_mid.K_hi — the products left out (q_mid.K_lo, q_lo.K) are below 2^-16 of the
-        // score, the resolution two K planes have anyway; one plane: all three q planes (exact q against bf16 K)
-#pragma unroll
-        for (int kp = 0; kp < PL; ++kp) {
-          if (PL == 2 && (pl + kp > 1)) continue;
-#pragma unroll
-          for (int t = 0; t < 2; ++t)
-            S[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qa, f.kb[kp][t][ks], S[t], 0, 0, 0);
-        }
-      }
-    // online softmax: in lanes 0..15, S[t][g] is the score of head g against key key0 + 16t + lane
-    float alpha[4];
-    const bool v0 = key0 + arow < nkeys, v1 = key0 + 16 + arow < nkeys;
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-      const float s0 = v0 ? S[0][g] * scale : -INFINITY, s1 = v1 ? S[1][g] * scale : -INFINITY;
-      const float mnew = fmaxf(mrun[g], row16_max(fmaxf(s0, s1)));
-      alpha[g] = (mrun[g] == -INFINITY) ? 0.f : __expf(mrun[g] - mnew);
-      const float p0 = (s0 == -INFINITY) ? 0.f : __expf(s0 - mnew), p1 = (s1 == -INFINITY) ? 0.f : __expf(s1 - mnew);
-      lrun[g] = lrun[g] * alpha[g] + row16_sum(p0 + p1);
-      mrun[g] = mnew;
-      if (lane < 16) {      // p -> LDS as hi + lo bf16, [plane][head][key]
-        const __bf16 h0 = (__bf16)p0, h1 = (__bf16)p1;
-        const __bf16 l0 = (__bf16)(p0 - (float)h0), l1 = (__bf16)(p1 - (float)h1);
-        pbuf[w][0][g][lane] = *reinterpret_cast<const bf16_raw*>(&h0);
-        pbuf[w][0][g][16 + lane] = *reinterpret_cast<const bf16_raw*>(&h1);
-        pbuf[w][1][g][lane] = *reinterpret_cast<const bf16_raw*>(&l0);
-        pbuf[w][1][g][16 + lane] = *reinterpret_cast<const bf16_raw*>(&l1);
-      }
-    }
-    __builtin_amdgcn_wave_barrier();
-    // rescale what is accumulated (register r of lanes 0..15 = head r)
-#pragma unroll
-    for (int nb = 0; nb < 8; ++nb)
-#pragma unroll
-      for (int g = 0; g < G; ++g) O[nb][g] *= alpha[g];
-    const bf16x8 pa0 = *reinterpret_cast<const bf16x8*>(&pbuf[w][0][arow][8 * akq]);
-    const bf16x8 pa1 = *reinterpret_cast<const bf16x8*>(&pbuf[w][1][arow][8 * akq]);
-#pragma unroll
-    for (int nb = 0; nb < 8; ++nb)
-#pragma unroll
-      for (int vp = 0; vp < PL; ++vp) {
-        O[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pa0, f.vb[vp][nb], O[nb], 0, 0, 0);
-        if (vp == 0) O[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pa1, f.vb[vp][nb], O[nb], 0, 0, 0);     // (p_lo.V_lo: below 2^-16)
-      }
-    __builtin_amdgcn_wave_barrier();     // pbuf is rewritten by the next granule
-  };
-
-  // two granules per trip: the other register set is loading while one is consumed.  Steady state first — three granules
-  // known to exist, NO branch around a prefetch: behind an `if` the waits of the consuming MFMAs have to serve the path
-  // without the new loads too, the compiler then counts as if they had not been issued and every granule waited for the
-  // one requested just before it (no overlap at all; the GEMM kernels had the same: gemm.hip DIA_PREFETCH_CLAMP) — then a
-  // tail of at most two granules in the old, branchy form.
-  if constexpr (PL == 1) {
-    int gi = g_first;
-    for (; gi + 2 * gstride < ngran; gi += 2 * gstride) {
-      load_gran(fb, gi + gstride);
-      consume(fa, gi);
-      load_gran(fa, gi + 2 * gstride);
-      consume(fb, gi + gstride);
-    }
-    if (gi < ngran) {                // fa holds granule gi
-      const int g1 = gi + gstride;
-      if (g1 < ngran) load_gran(fb, g1);
-      consume(fa, gi);
-      if (g1 < ngran) consume(fb, g1);
-    }
-  } else {
-    for (int gi = g_first; gi < ngran; gi += gstride) {
-      if (gi != g_first) load_gran(fa, gi);
-      consume(fa, gi);
-    }
-  }
+  attn_trip<G, PL, true>(fa, kk, qf, pbuf[w], &knew_s, &vnew_s, owner, slot, lane, O, mrun, lrun);
   ASTAMP(3);
-  // per-wave partial -> LDS (lanes 0..15: dim 16*nb + lane, register g = head)
-  if (lane < 16) {
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-#pragma unroll
-      for (int nb = 0; nb < 8; ++nb) part[(w * G + g) * HD + 16 * nb + lane] = O[nb][g];
-      if (lane == 0) { pm_s[w * 8 + g] = mrun[g]; pl_s[w * 8 + g] = lrun[g]; }
-    }
-  }
-  __syncthreads();
+  attn_wave_parts<G>(part, pm_s, pl_s, w, lane, O, mrun, lrun);
   ASTAMP(4);
   attn_finish<G>(p, part, pm_s, pl_s, &last_s, tid, qrow, kvh, head_row, chunk, nchunks);
 }
+
+// ---- One-shape forms of the two attention launches of the 1-4-row decode step (knob attn_spec; attn_form_of decides at the launch).
+// As the k_gemv_small forms (gemm.hip): overloads of k_attn_mfma on the FUNCTION parameter list with the template parameter list of
+// the generic instantiation they replace, so the instantiation name a launch reports stays what it was.  What the prologue needs in
+// front of its first K/V request comes as leading arguments: 14 dwords of them arrive preloaded in SGPRs here (16 user SGPRs less the
+// kernarg pointer), which is the pointers the first requests go through and the strides.  The by-value AttnK behind them is not
+// preloaded and carries the rest: the RoPE tables, fetched beside cur[] under one wait, and what the tail reads.  a_q = q + q_off;
+// a_pair / a_row = elements of one (row, kv head) pair / of one row of a cache (kv_cap * 128, times n_kv_heads; the host checks
+// that they fit an int).  The stages are the generic kernel's, in its order: the bits are the same.
+//
+// CROSS_GENERIC_FUSED: how many of a thread's eight output dims k_attn_mfma<1, 1>(AttnK) accumulates by fused multiply-add in its wave
+// merge (attn_finish); the other dims and the softmax sum take a rounded product and a rounded add.  It is the contraction the
+// compiler chose for that body, read from its gfx950 ISA as built by ROCm 7.2.0 (AMD clang 22.0.0git, roc-7.2.0): behind the last
+// s_barrier but one, three v_pk_fma_f32 per wave (dims 0-5) and v_mul_f32 + v_pk_add_f32 for dims 6, 7.  A toolchain that contracts the
+// generic body differently shows as test_cross_form_equals_generic failing from 33 keys on (two waves to merge) with no source
+// change: read the new count the same way (hipcc -S --cuda-device-only with the Makefile's flags) and put it here.
+constexpr int CROSS_GENERIC_FUSED = 6;
+
+// Cross form: k_attn_mfma<1, 1>, CROSS over one-plane bf16 caches of at most 256 keys, no head_map.  Every length such a cache can
+// hold is ONE chunk of at most two granules per wave under the generic rule (ngran <= 8 -> gpw >= 2 -> nchunks == 1), so there is no
+// chunk arithmetic, no slab, ticket or merge and no steady-state loop; a second split that key_split launches for 129..256 keys of
+// capacity exits at entry, as it does in the generic body behind its loads.  No k / v re-reads of q, no slot, no append.
+// cur[] (the RoPE position) and len[] are two scalar loads under one counter: they come back together, cos / sin go out ahead of the
+// granule as in the generic body (vmcnt retires in order: RoPE must not wait behind 16 KB of K/V).
+template <int G, int PL>
+__global__ __launch_bounds__(NT, 2) void k_attn_mfma(const float* a_q, const int* a_len, const int* a_cur, bf16_raw* a_kc, bf16_raw* a_vc,
+                                                     int a_ldq, int a_pair, int a_row, AttnK p) {
+  static_assert(G == 1 && PL == 1, "the cross form");
+  __shared__ __attribute__((aligned(16))) bf16_raw qf[4][DIA_NPLANES][G][4][8];
+  __shared__ float part[NWV * G * HD];
+  __shared__ float pm_s[NWV * 8], pl_s[NWV * 8];
+  __shared__ __attribute__((aligned(16))) bf16_raw pbuf[NWV][2][16][32];
+  if (blockIdx.z) return;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int kvh = blockIdx.x, by = blockIdx.y;
+  const int arow = lane & 15, akq = lane >> 4;
+  ASTAMP(0);
+  const int qrow = 2 * by + 1;
+  const float* qh = a_q + (long)qrow * a_ldq + kvh * HD;      // every wave reads the head, wave 0 ropes it
+  const float qx1 = qh[lane], qx2 = qh[lane + 64];
+  int pos = a_cur[by], len = a_len[by];
+  const float* cos_t = p.cos_t;
+  const float* sin_t = p.sin_t;
+  // every scalar load of the prologue in flight together, behind the q requests, and ONE wait: left to itself the compiler takes
+  // them one round trip after the other, each in front of its first use
+  asm volatile("" : "+s"(pos), "+s"(len), "+s"(cos_t), "+s"(sin_t) : : "memory");
+  const int nkeys = min(len, 2 * NWV * 32);                   // (a length past the capacity the host vouched for is not followed out of the cache)
+  ASTAMP(1);
+  const float rc = ((const gfloat*)cos_t)[(long)pos * 64 + lane], rs = ((const gfloat*)sin_t)[(long)pos * 64 + lane];
+  // the granule needs len[] alone and the scheduler would put its 16 requests (8 K, 8 V) in front of q, cos and sin: RoPE and the LDS hand-off
+  // would then run behind the K/V latency instead of under it, and nothing is won in front (cur[] and len[] come back together)
+  asm volatile("" : : : "memory");
+  const AttnKeys kk = {a_kc + (long)by * a_row + (long)kvh * a_pair, a_vc + (long)by * a_row + (long)kvh * a_pair, 0,
+                       nkeys, max(nkeys - 1, 0), (nkeys + 31) >> 5, w, NWV};
+  MfmaFrag<G, PL> fa;
+  attn_load_gran(fa, kk, w < kk.ngran ? w : 0, arow, akq);     // idle waves re-read granule 0 (cache hit) and never use it
+  attn_stage_q<G>(qf, w, lane, qx1, qx2, rc, rs);
+  lds_barrier();     // q in LDS; global loads stay in flight
+  ASTAMP(2);
+  f32x4 O[8];
+  float mrun[4], lrun[4];
+  attn_trip<G, PL, false, false>(fa, kk, qf, pbuf[w], nullptr, nullptr, false, -1, lane, O, mrun, lrun);
+  ASTAMP(3);
+  attn_wave_parts<G>(part, pm_s, pl_s, w, lane, O, mrun, lrun);
+  ASTAMP(4);
+  p.mode = DIA_ATTN_CROSS; p.head_map = nullptr;
+  attn_finish<G, false, CROSS_GENERIC_FUSED>(p, part, pm_s, pl_s, nullptr, tid, qrow, kvh, by, 0, 1);
+}
+
+// Self form: k_attn_mfma<4, 1>, SELF over one-plane bf16 caches, no head_map.  Row = kv row = grid y, position = keys = cur[y / 2],
+// new slot = cur - 1: no len[] load, no mode selects, no head_map loop.  Key split, owner append and slab merge as in the generic body.
+template <int G, int PL>
+__global__ __launch_bounds__(NT, 2) void k_attn_mfma(const float* a_q, const int* a_cur, bf16_raw* a_kc, bf16_raw* a_vc,
+                                                     int a_ldq, int a_koff, int a_voff, int a_pair, int a_row, int a_gpw, AttnK p) {
+  static_assert(G == 4 && PL == 1, "the self form");
+  __shared__ __attribute__((aligned(16))) bf16_raw qf[4][DIA_NPLANES][G][4][8];
+  __shared__ float part[NWV * G * HD];
+  __shared__ float pm_s[NWV * 8], pl_s[NWV * 8];
+  __shared__ __attribute__((aligned(16))) bf16_raw pbuf[NWV][2][16][32];
+  __shared__ __attribute__((aligned(16))) bf16_raw knew_s[PL][HD], vnew_s[PL][HD];
+  __shared__ int last_s;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int kvh = blockIdx.x, by = blockIdx.y, chunk = blockIdx.z;
+  const int arow = lane & 15, akq = lane >> 4;
+  ASTAMP(0);
+  // ---- loads that do not need cur[]: this wave's q head and the new k / v of the kv head (a_koff / a_voff: from a_q)
+  const float* qr = a_q + (long)by * a_ldq;
+  const float* qh = qr + (kvh * G + min(w, G - 1)) * HD;
+  const float* kh = qr + a_koff + kvh * HD;
+  const float* vh = qr + a_voff + kvh * HD;
+  const float qx1 = qh[lane], qx2 = qh[lane + 64];
+  const float kx1 = kh[lane], kx2 = kh[lane + 64];
+  const float vx1 = vh[lane], vx2 = vh[lane + 64];
+
+  int c_cur = a_cur[by >> 1];
+  const float* cos_t = p.cos_t;
+  const float* sin_t = p.sin_t;
+  int NZ = gridDim.z;
+  asm volatile("" : "+s"(c_cur), "+s"(cos_t), "+s"(sin_t), "+s"(NZ) : : "memory");      // (as in the cross form: one wait for the scalar loads, behind the q / k / v requests)
+  const int nkeys = c_cur, pos = c_cur, slot = c_cur - 1;
+  const int ngran = (nkeys + 31) >> 5;
+  const int gpw = (ngran <= 2 * NWV) ? max(a_gpw, 2) : a_gpw;      // (the generic kernel's rule)
+  const int nchunks = min(NZ, max(1, (ngran + NWV * gpw - 1) / (NWV * gpw)));
+  if (chunk >= nchunks) return;
+  ASTAMP(1);
+  const float rc = ((const gfloat*)cos_t)[(long)pos * 64 + lane], rs = ((const gfloat*)sin_t)[(long)pos * 64 + lane];
+  const int gstride = NWV * nchunks, g_first = chunk * NWV + w;
+  const AttnKeys kk = {a_kc + (long)by * a_row + (long)kvh * a_pair, a_vc + (long)by * a_row + (long)kvh * a_pair, 0,
+                       nkeys, max(nkeys - 1, 0), ngran, g_first, gstride};
+  MfmaFrag<G, PL> fa;
+  attn_load_gran(fa, kk, g_first < ngran ? g_first : 0, arow, akq);
+  attn_stage_q<G>(qf, w, lane, qx1, qx2, rc, rs);
+  const bool owner = slot >= 0 && ((slot >> 5) % gstride) == g_first;      // wave-uniform
+  if (owner) attn_append<PL>(knew_s, vnew_s, kk, slot, lane, kx1, kx2, vx1, vx2, rc, rs);
+  lds_barrier();
+  ASTAMP(2);
+  f32x4 O[8];
+  float mrun[4], lrun[4];
+  attn_trip<G, PL, true>(fa, kk, qf, pbuf[w], &knew_s, &vnew_s, owner, slot, lane, O, mrun, lrun);
+  ASTAMP(3);
+  attn_wave_parts<G>(part, pm_s, pl_s, w, lane, O, mrun, lrun);
+  ASTAMP(4);
+  p.mode = DIA_ATTN_SELF; p.head_map = nullptr;
+  attn_finish<G>(p, part, pm_s, pl_s, &last_s, tid, by, kvh, by, chunk, nchunks);
+}
+
+// the overloads behind one instantiation name, told apart by their parameter lists
+template <int G, int PL> constexpr auto attn_generic = static_cast<void (*)(AttnK)>(k_attn_mfma<G, PL>);
+constexpr auto attn_cross_form = static_cast<void (*)(const float*, const int*, const int*, bf16_raw*, bf16_raw*, int, int, int, AttnK)>(k_attn_mfma<1, 1>);
+constexpr auto attn_self_form = static_cast<void (*)(const float*, const int*, bf16_raw*, bf16_raw*, int, int, int, int, int, int, AttnK)>(k_attn_mfma<4, 1>);
 
 // ---------------------------------------------------------------------------------------------------
 // FP8 cross K/V (dia_hip.h "FP8 cross K/V"): k_attn_mfma<1, 1> for DIA_ATTN_CROSS over the e4m3 copy of the cross caches.
@@ -1290,10 +1489,46 @@ int launch_attn(const AttnK& k, int grid_y, int grid_z, hipStream_t st) {
   return dia_check_launch("k_attn");
 }
 
+// The host rule of the one-shape forms: which body serves a dia_attn call that its checks have passed.  A form is taken only
+// where every fact it has compiled in holds, anything else falls through to the generic kernel without a word:
+//   both    the MFMA kernel's caches (blocked V, one bf16 plane), no head_map, at most 4 rows, cache rows that fit an int
+//           (the row limit: nothing in the forms depends on the row count, grid y is independent — but only 1-4 rows were tested
+//           and measured, and wider batches keep the body they were measured with)
+//   cross   CROSS, group 1, capacity <= 256 keys (one chunk whatever the length; key_split gives such a launch 1 or 2 splits)
+//   self    SELF, group 4
+// knob attn_spec: unset = both, 0 = the generic body everywhere, otherwise a mask for the A/B of one form: 1 = cross, 2 = self
+enum { ATTN_FORM_GENERIC = 0, ATTN_FORM_CROSS = 1, ATTN_FORM_SELF = 2 };
+constexpr int FORM_CROSS_MAX_KEYS = 2 * NWV * 32;
+int attn_form_of(const dia_attn_args* a) {
+  const int v = dia_tune(DIA_TUNE_ATTN_SPEC);
+  if (!a->v_blocked || a->kv_dtype != DIA_KV_BF16 || a->head_map || a->kv_cap <= 0 || a->kv_cap % 32 != 0) return ATTN_FORM_GENERIC;
+  if ((long)a->n_kv_heads * a->kv_cap * HD > 0x7fffffffL) return ATTN_FORM_GENERIC;
+  if (a->mode == DIA_ATTN_CROSS && a->group == 1 && a->n_rows <= 2 && a->kv_cap <= FORM_CROSS_MAX_KEYS && (v < 0 || (v & ATTN_FORM_CROSS))) return ATTN_FORM_CROSS;
+  if (a->mode == DIA_ATTN_SELF && a->group == 4 && a->n_rows <= 4 && (v < 0 || (v & ATTN_FORM_SELF))) return ATTN_FORM_SELF;
+  return ATTN_FORM_GENERIC;
+}
+
 template <int G>
-int launch_attn_mfma(const AttnK& k, int grid_y, int grid_z, hipStream_t st) {
-  if (k.kv_plane_stride > 0) dia_launch<k_attn_mfma<G, 2>>(dim3(k.n_kv_heads, grid_y, grid_z), dim3(NT), 0, st, k);
-  else dia_launch<k_attn_mfma<G, 1>>(dim3(k.n_kv_heads, grid_y, grid_z), dim3(NT), 0, st, k);
+int launch_attn_mfma(const AttnK& k, int form, int grid_y, int grid_z, hipStream_t st) {
+  const dim3 grid(k.n_kv_heads, grid_y, grid_z);
+  // (elements of one (row, kv head) pair and of one row of a cache: attn_form_of has checked that they fit an int where a form is taken)
+  if constexpr (G == 1) {
+    if (form == ATTN_FORM_CROSS) {
+      const int pair = k.kv_cap * HD, row = k.n_kv_heads * pair;
+      dia_launch<attn_cross_form>(grid, dim3(NT), 0, st, k.q + k.q_off, k.len, k.cur, (bf16_raw*)k.kc, (bf16_raw*)k.vc, k.ldq, pair, row, k);
+      return dia_check_launch("k_attn_mfma");
+    }
+  }
+  if constexpr (G == 4) {
+    if (form == ATTN_FORM_SELF) {
+      const int pair = k.kv_cap * HD, row = k.n_kv_heads * pair;
+      dia_launch<attn_self_form>(grid, dim3(NT), 0, st, k.q + k.q_off, k.cur, (bf16_raw*)k.kc, (bf16_raw*)k.vc, k.ldq, k.k_off - k.q_off, k.v_off - k.q_off,
+                                 pair, row, k.gpw, k);
+      return dia_check_launch("k_attn_mfma");
+    }
+  }
+  if (k.kv_plane_stride > 0) dia_launch<attn_generic<G, 2>>(grid, dim3(NT), 0, st, k);
+  else dia_launch<attn_generic<G, 1>>(grid, dim3(NT), 0, st, k);
   return dia_check_launch("k_attn_mfma");
 }
 
@@ -1374,6 +1609,11 @@ extern "C" int dia_attn_scratch_floats(int n_rows, int n_kv_heads, int kv_cap) {
   return n > 0x7fffffffL ? -1 : (int)n;
 }
 
+// the form (0 generic, 1 cross, 2 self) dia_attn would launch for these arguments under the current attn_spec — the rule alone, nothing
+// is read through the pointers and nothing is launched (pure; not part of dia_hip.h: two bodies share one instantiation name, so the
+// tests ask the rule which one a launch takes)
+extern "C" int dia_attn_form(const dia_attn_args* a) { return a ? attn_form_of(a) : ATTN_FORM_GENERIC; }
+
 extern "C" int dia_attn(const dia_attn_args* a, void* stream) {
   AttnK k; int max_chunks;
   if (const int rc = attn_front({"dia_attn", false, true}, a, nullptr, k, max_chunks)) return rc;
@@ -1388,9 +1628,10 @@ extern "C" int dia_attn(const dia_attn_args* a, void* stream) {
     if (f32 || a->mode == DIA_ATTN_ENC || a->kv_cap % 32 != 0) return dia_fail(DIA_E_ARG, "dia_attn: v_blocked needs bf16 K/V, SELF/CROSS mode and kv_cap % 32 == 0");
     if (a->mode == DIA_ATTN_SELF && !a->cur) return dia_fail(DIA_E_ARG, "dia_attn: SELF needs cur");
     if (a->mode == DIA_ATTN_CROSS && (!a->cur || !a->len || a->group != 1)) return dia_fail(DIA_E_ARG, "dia_attn: CROSS needs cur, len and group 1");
-    if (a->group == 4) return launch_attn_mfma<4>(k, a->n_rows, max_chunks, st);
-    if (a->group == 2) return launch_attn_mfma<2>(k, a->n_rows, max_chunks, st);
-    if (a->group == 1) return launch_attn_mfma<1>(k, a->n_rows, max_chunks, st);
+    const int form = attn_form_of(a);
+    if (a->group == 4) return launch_attn_mfma<4>(k, form, a->n_rows, max_chunks, st);
+    if (a->group == 2) return launch_attn_mfma<2>(k, form, a->n_rows, max_chunks, st);
+    if (a->group == 1) return launch_attn_mfma<1>(k, form, a->n_rows, max_chunks, st);
     return dia_fail(DIA_E_ARG, "dia_attn: GQA group must be 1, 2 or 4");
   }
   switch (a->mode) {

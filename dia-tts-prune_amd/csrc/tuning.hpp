@@ -38,6 +38,9 @@ enum dia_tune_id {
                                // otherwise a mask of the forms in use: 1 = those projections, 2 = the deferred-wo consumer, 4 = its producer (gemv_spec_on)
   DIA_TUNE_USPARSE,            // usparse: which launch classes stream the unstructured sparse streams at <= 4 rows (dia_usparse_classes, dia_engine_set_usparse):
                                // bit c = matrix c of dia_step_mat; 0 = dense tiles everywhere; unset = the measured default (csrc/engine.hip)
+  DIA_TUNE_ATTN_SPEC,          // attn_spec: which one-shape forms of k_attn_mfma serve the 1-4-row decode step (csrc/attn.hip, attn_form_of; A/B): a mask,
+                               // 1 = the cross form (k_attn_mfma<1, 1>, at most 256 keys of capacity), 2 = the self form (k_attn_mfma<4, 1>);
+                               // 0 = the generic body everywhere; unset = both
   // ---- EXPERIMENTS=1 builds only
   DIA_TUNE_MLP_FUSE,           // mlp_fuse: 1 = wi + wo as one persistent launch at batch 1 (dia_mlp_fused)
   DIA_TUNE_TILE_V,             // tile_v: prefill tile kernel variant (0..5; 3 = wave-specialised default)
